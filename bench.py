@@ -21,6 +21,8 @@ tallied per call by the search driver.  `value_physical` counts wh
 After the timed region the last fit of rank 0 is compared with the oracle-generated golden of the same workload
 (tests/golden/cfg*.npz: interaction matrix and gibbs-call sequence exact, BIC trace 1e-9, draws 1e-9 of the column
 scale, numpy stream equal): `parity_checked` / `parity` in the JSON line, exit code 3 on a mismatch.
+--dump-outputs DIR writes what the fits of the last timed step returned (draws, interaction matrix, BIC trace) as .npy
+files: the datasets and chains are seeded, so two builds can be compared output for output.
 
 N > 1 (--mode):
   fits        every rank fits its own dataset(s) (independent fits are the unit that shards without a data-path
@@ -169,6 +171,27 @@ def compare_with_golden(name, model, betas, mtx, evs, state):
     else:
         out['ok'] = False
     return out
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs writes at most this much
+
+
+def dump_outputs(directory, results):
+    """--dump-outputs: what the last timed step returned to its caller -- `results`: dataset unit -> the (betas, mtx, evs) of
+    that unit's fit -- as <directory>/unit<u>_{betas,mtx,evs}.npy, float64.  Datasets and chains are seeded by the
+    configuration, so two builds run with the same arguments can be compared file by file.  Beyond DUMP_BYTES in all, every
+    array keeps the same fraction of its rows: a sample drawn from a fixed seed, the same rows in every run."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {f'unit{unit}_{name}': np.asarray(a, dtype=np.float64)
+              for unit, fit in sorted(results.items()) for name, a in zip(('betas', 'mtx', 'evs'), fit)}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_BYTES - 128 * len(arrays)              # (a .npy header is 128 bytes)
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        if total > budget:
+            keep = a.shape[0] * budget // total
+            a = a[np.sort(rng.choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(directory, name + '.npy'), a)
 
 
 def mfma_flops_issued_over_algorithmic(trace_lines):
@@ -622,7 +645,7 @@ def HostReducedBackend(ctx, comm):
     return _host_reduced_backend()(ctx, comm)
 
 
-def fits_worker(cfg, k, procs, local, unit_ids, rows, steps, warmup, start, done, gate=None, domain=None):
+def fits_worker(cfg, k, procs, local, unit_ids, rows, steps, warmup, start, done, gate=None, domain=None, outputs=False):
     """One of the worker PROCESSES of `--config 4 --procs P`: its own device context(s), host threads and L3 domain; fits
     its share of the rank's datasets back to back.  (Threads of one process share the interpreter lock of the Python
     drivers; processes do not: 13.7 / 21.9 / 32.8 / 40.6 fits/s with 1 / 2 / 3 / 4 of them on one MI355X.)"""
@@ -697,7 +720,9 @@ def fits_worker(cfg, k, procs, local, unit_ids, rows, steps, warmup, start, done
             for key in tot:
                 tot[key] += t[key]
         kern[name] = tot
-    done.put(dict(worker=k, elapsed=elapsed, prep_s=prep_s, stats=acc, kern=kern))
+    # --dump-outputs: what the last pass over this worker's datasets returned
+    last = {unit: (model.betas, model.mtx, model.evs) for unit, (model, _) in zip(unit_ids, fits)} if outputs else None
+    done.put(dict(worker=k, elapsed=elapsed, prep_s=prep_s, stats=acc, kern=kern, outputs=last))
 
 
 def fits_with_worker_processes(args, cfg, rank, world, local, procs):
@@ -712,7 +737,8 @@ def fits_with_worker_processes(args, cfg, rank, world, local, procs):
     ctx_mp = mp.get_context('spawn')                        # before this process has initialised the GPU
     start, done = ctx_mp.Barrier(procs + 1), ctx_mp.Queue()
     workers = [ctx_mp.Process(target=fits_worker, args=(cfg, k, procs, local, units[k::procs], rows, args.steps,
-                                                            args.warmup, start, done)) for k in range(procs)]
+                                                            args.warmup, start, done),
+                              kwargs=dict(outputs=bool(args.dump_outputs))) for k in range(procs)]
     for w in workers:
         w.start()
 
@@ -730,6 +756,8 @@ def fits_with_worker_processes(args, cfg, rank, world, local, procs):
     elapsed = time.perf_counter() - t0
     for w in workers:
         w.join(60)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {unit: fit for r in results for unit, fit in r['outputs'].items()})
 
     kern = {}
     for name, _ in KERNEL_SLOTS():
@@ -854,7 +882,12 @@ def main():
     ap.add_argument('--no-throughput', action='store_true',
                     help='skip the secondary measurement of the default run (several fits sharing the GPU)')
     ap.add_argument('--launch-check', action='store_true', help=argparse.SUPPRESS)    # tests: bring the ranks up, nothing else
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the fits of the last one returned (posterior draws, interaction '
+                         'matrix, BIC of every sub-stage) as DIR/unit<u>_{betas,mtx,evs}.npy (float64, at most 64 MB in all)')
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error('--dump-outputs writes the results of the last timed step: --steps must be at least 1')
 
     from fokl_gpy_amd import dist
     rank, world, local = dist.env_rank_world()
@@ -1118,6 +1151,10 @@ def main():
         end_state = np.random.get_state()
         for _, backend, *_ in fits:
             backend.ctx.timing_enable(False)
+    # what the last timed step returned (one fit for all ranks: every rank holds the same result, rank 0 writes it)
+    if args.dump_outputs and (rank == 0 or not one_fit_for_all):
+        dump_outputs(args.dump_outputs, {unit: (model.betas, model.mtx, model.evs)
+                                         for unit, (model, *_) in zip(units, fits)})
 
     kern = {}
     for name, kid in KERNEL_SLOTS():
