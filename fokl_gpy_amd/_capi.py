@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get('FOKL_HIP_LIBRARY', os.path.join(_HERE, 'libfokl_hip.s
 
 UNIQUE_ID_BYTES = 128
 K_BASIS, K_GRAM, K_RESID, K_PREDICT, K_RESID_MF, K_GRAM_MFMA, K_GRAM_REDUCE = 0, 1, 2, 3, 4, 5, 6
+K_INTEGRATE, K_BAND = 7, 8
+INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
 RESID_TERMS_LAYOUTS = ((8, 1), (16, 1), (8, 2), (4, 4), (2, 8), (8, 4), (16, 2), (4, 8))    # inputs x orders per input (csrc/fokl_hip.hip)
@@ -155,6 +157,8 @@ SIGNATURES = {
     'fokl_rng_gammas': (c_int, [c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_i64, c_vp]),
     'fokl_gp_integrate': (c_int, [c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
                                   c_dbl, c_vp, c_vp]),
+    'fokl_gp_integrate_ensemble': (c_int, [c_vp, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp, c_vp, c_int, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
     'fokl_dchain_create': (c_int, [c_int, c_int, c_vp]),
     'fokl_dchain_destroy': (None, [c_vp]),
     'fokl_dchain_submit': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp,
@@ -1805,6 +1809,20 @@ class DeviceContext:
         self._ck(self._lib.fokl_predict(self._h, _ptr(s), nc, _ptr(betas), draws, int(cut or 0), _ptr(mean),
                                         _ptr(bounds)))
         return (mean, bounds) if cut is not None else mean
+
+    def gp_integrate_ensemble(self, n_members, n_states, n_other, n_steps, betas, per_member, mtx, rows, cols, sources,
+                              n_src, forcing, norms, table, n_basis, width, h, y0, cut=None, want_members=False):
+        """fokl_gp_integrate_ensemble (GP_Integrate.GP_Integrate_ensemble assembles the arguments): betas / mtx / sources
+        are ctypes pointer arrays, the rest numpy; -> (mean [n_states, n_steps + 1], bounds [..., 2] or None if cut is
+        None, members [n_members, n_states, n_steps + 1] or None).  Needs no uploaded dataset and leaves one alone."""
+        mean = np.empty((n_states, n_steps + 1), dtype=np.float64)
+        bounds = np.empty((n_states, n_steps + 1, 2), dtype=np.float64) if cut is not None else None
+        members = np.empty((n_members, n_states, n_steps + 1), dtype=np.float64) if want_members else None
+        self._ck(self._lib.fokl_gp_integrate_ensemble(
+            self._h, int(n_members), int(n_states), int(n_other), int(n_steps), betas, _ptr(per_member), mtx, _ptr(rows),
+            _ptr(cols), sources, _ptr(n_src), _ptr(forcing), _ptr(norms), _ptr(table), int(n_basis), int(width), float(h),
+            _ptr(y0), int(y0.ndim == 2), int(cut or 0), _ptr(mean), _ptr(bounds), _ptr(members)))
+        return mean, bounds, members
 
     def read_slot(self, slot, row0=0, nrows=None):
         nrows = self.n - row0 if nrows is None else nrows

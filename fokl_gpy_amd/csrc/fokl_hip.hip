@@ -1834,6 +1834,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_chain_device.inc"
 #include "fokl_spectral_device.inc"
 #include "fokl_predict.inc"
+#include "fokl_integrate_device.inc"
 #include "fokl_probe.inc"
 #include "fokl_dgemm_device.inc"
 

@@ -36,6 +36,15 @@ extern "C" int fokl_device_count(int *count)
     return FOKL_ERR_HIP;
 }
 
+// GP_Integrate over an ensemble runs on the device only (fokl_integrate_device.inc); the single trajectory is host code.
+extern "C" int fokl_gp_integrate_ensemble(fokl_ctx *, int, int, int, int64_t, const double *const *, const int32_t *,
+                                          const int32_t *const *, const int32_t *, const int32_t *, const int32_t *const *,
+                                          const int32_t *, const double *, const double *, const double *, int, int, double,
+                                          const double *, int, int, double *, double *, double *)
+{
+    return FOKL_ERR_HIP;
+}
+
 // The device chain engine and page-locked memory do not exist in these builds: the native search (fokl_search.cpp) is
 // then created without an engine and falls back to ordinary memory for its tapes.
 extern "C" int fokl_host_alloc(size_t, void **out)

@@ -47,7 +47,9 @@ extern "C" {
 #define FOKL_K_GRAM_MFMA 5      /* K2 launches bound by the fp64 MFMA roof (2 N nr nc / peak flops > 8 N distinct columns /
                                    peak bytes, i.e. nr nc / distinct > ~39); FOKL_K_GRAM then holds the HBM-bound ones */
 #define FOKL_K_GRAM_REDUCE 6    /* K2's second kernel: fixed-order sum of the per-workgroup partial blocks (bytes = slabs read) */
-#define FOKL_K_COUNT   7
+#define FOKL_K_INTEGRATE 7      /* GP_Integrate over an ensemble: the Runge-Kutta launches (bytes = points written)   */
+#define FOKL_K_BAND    8        /* ... and its mean / order-statistic launches (bytes = points read)                  */
+#define FOKL_K_COUNT   9
 
 typedef struct fokl_ctx fokl_ctx;
 
@@ -349,6 +351,40 @@ int fokl_gp_integrate(int n_states, int n_other, int64_t n_steps, const double *
                       const int32_t *const *source, const int32_t *n_source, const double *forcing,
                       const double *norms, const double *spline_table, int n_basis, int width, double h, double *y,
                       double *trajectory);
+
+/*
+ * The same integration for n_members members at once on the device, and the mean and order-statistic bounds over the
+ * members at every time point: one member per posterior draw and / or per initial state (trajectory uncertainty).
+ * The model description is fokl_gp_integrate's, pointer for pointer (host memory, same layouts, same meaning), with:
+ *   betas[k]           [mtx_rows[k] + 1] shared by every member if betas_per_member[k] == 0, else
+ *                      [n_members, mtx_rows[k] + 1] row-major (rows = draws as a fit returns them);
+ *   y0                 [n_states] shared if y0_per_member == 0, else [n_members, n_states]; NOT advanced;
+ *   forcing, norms, spline_table, h   shared by all members.
+ * Member e integrates row e of every per-member array.  Outputs, host memory:
+ *   mean    [n_states, n_steps + 1]                 mean over members (fixed summation order: reproducible bit for bit);
+ *   bounds  [n_states, n_steps + 1, 2] or NULL      (sorted[cut], sorted[n_members - cut]) of the members' values at that
+ *                                                   point, fokl_predict's convention (FR:973-977): 1 <= cut < n_members.
+ *                                                   Sorted in LDS: at most 16 384 members, FOKL_ERR_ARG beyond (mean and
+ *                                                   members have no such limit);
+ *   members [n_members, n_states, n_steps + 1] or NULL   every trajectory (point 0 is the initial state).
+ * A member's arithmetic is fokl_gp_integrate's operation for operation, except that a cubic's X^2 and X^3 are products
+ * where the host calls pow (<= 1 ulp per cubic), and that the piece index is clamped to the table for inputs outside
+ * [0, 1] (a forcing value beyond its normalisation) where the host reads past it.
+ * Limits (FOKL_ERR_ARG, nothing is launched): width must be 499; orders within the table; at most
+ * FOKL_INTEGRATE_MAX_STATES states (the kernel keeps the stage vectors in registers); coefficients + distinct
+ * (input, order) factors of all models + states together at most 287 (they live in LDS, 64 members wide).
+ * Needs a context, no dataset: everything it uses is uploaded by the call and freed before it returns; the context's
+ * dataset, slots and pending launches are left alone (it may be called between fits).  The time axis is cut into
+ * launches of at most 512 steps (FOKL_INTEGRATE_STEPS_PER_LAUNCH overrides; the cut changes no bit of the result), so no
+ * launch runs long and only one launch's points are resident.  Kernel times: FOKL_K_INTEGRATE, FOKL_K_BAND.  Blocking.
+ */
+#define FOKL_INTEGRATE_MAX_STATES 4
+int fokl_gp_integrate_ensemble(fokl_ctx *ctx, int n_members, int n_states, int n_other, int64_t n_steps,
+                               const double *const *betas, const int32_t *betas_per_member, const int32_t *const *mtx,
+                               const int32_t *mtx_rows, const int32_t *mtx_cols, const int32_t *const *source,
+                               const int32_t *n_source, const double *forcing, const double *norms,
+                               const double *spline_table, int n_basis, int width, double h, const double *y0,
+                               int y0_per_member, int cut, double *mean, double *bounds, double *members);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* multi-GPU: one process per GPU, RCCL over xGMI                                                          */
