@@ -5,11 +5,14 @@ Keeps the reference's public surface (``src/FoKL/FoKLRoutines.py``, "FR"): the c
 defaults (FR:205-216), ``clean`` (FR:441), ``fit`` (FR:1202), ``evaluate`` (FR:851), ``coverage3`` (FR:982),
 ``bss_derivatives`` (FR:594), ``evaluate_basis`` (FR:807), ``save`` / ``load`` / ``clear`` and the result attributes
 ``betas, avg_betas, mtx, evs, inputs, data, minmax, trainlog``.  The numerics of ``fit``, ``evaluate`` and
-``bss_derivatives`` run on the GPU through ``libfokl_hip.so`` (see ``engine.py`` and ``include/fokl_hip.h``); there
-is no CPU fallback -- without the library or a gfx950 device they raise.
+``bss_derivatives`` run on the GPU through ``libfokl_hip.so`` (see ``engine.py`` and ``include/fokl_hip.h``), and so
+do ``fitupdate`` (``update=True``: the sequential-updating fit, FR:1850-2583) and ``optimize`` -- where the model is
+largest or smallest, for every posterior draw at once (``optimize.py``); there is no CPU fallback -- without the library
+or a gfx950 device they raise.
 
-Deliberately NOT rebuilt (out of the hot-path scope): ``fitupdate`` (``update=True``),
-``to_pyomo``; calling them raises ``NotImplementedError``.
+Deliberately NOT rebuilt: ``to_pyomo`` (FR:1796-1805), a symbolic export for Pyomo's solvers; calling it raises
+``NotImplementedError``.  ``optimize`` is what this package offers in its place: the question the export exists to
+answer, asked of the device.
 
 Device selection is by environment (``FOKL_DEVICE``, else ``LOCAL_RANK``, else 0), never by a new keyword:
 unknown keywords must keep raising ``ValueError`` exactly like the reference (FR:78).
@@ -28,6 +31,7 @@ from . import getKernels
 from . import _capi
 from . import engine as _engine
 from . import update as _update
+from . import optimize as _optimize
 
 
 def _column_min_max(a):
@@ -1260,6 +1264,19 @@ class FoKL:
         self.fit_trace = trace
         self.avg_betas = np.mean(betas, axis=0)
         return betas, mtx, evs
+
+    def optimize(self, **kwargs):
+        """Where the fitted model is largest (``sense='max'``) or smallest, for every posterior draw at once on the
+        device: ``optimize.optimize`` with this model's ``betas``, ``mtx``, ``phis``, ``minmax`` and ``kernel`` (pass
+        ``betas`` / ``mtx`` to override), which documents the keywords -- sense, objective, bounds, starts, max_iter, tol,
+        ReturnBounds, ReturnAll -- and the result.  'Bernoulli Polynomials' models only."""
+        if not hasattr(self, 'minmax'):
+            raise ValueError("optimize needs the model's minmax (set by clean / fit, or model.minmax = [[min, max], ...])")
+        for name in ('betas', 'mtx'):
+            if kwargs.get(name) is None:
+                kwargs[name] = getattr(self, name)
+        kwargs.setdefault('device', self._backend())
+        return _optimize.optimize(phis=self.phis, minmax=self.minmax, kernel=self.kernel, **kwargs)
 
     def to_pyomo(self, *args, **kwargs):
         raise NotImplementedError("to_pyomo (FR:1796-1805) is outside the scope of this build")

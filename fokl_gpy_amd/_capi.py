@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get('FOKL_HIP_LIBRARY', os.path.join(_HERE, 'libfokl_hip.s
 UNIQUE_ID_BYTES = 128
 K_BASIS, K_GRAM, K_RESID, K_PREDICT, K_RESID_MF, K_GRAM_MFMA, K_GRAM_REDUCE = 0, 1, 2, 3, 4, 5, 6
 K_INTEGRATE, K_BAND = 7, 8
+K_OPTIMIZE = 9
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
@@ -159,6 +160,8 @@ SIGNATURES = {
                                   c_dbl, c_vp, c_vp]),
     'fokl_gp_integrate_ensemble': (c_int, [c_vp, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_vp, c_vp, c_int, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
+    'fokl_model_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_dbl,
+                                    c_int, c_dbl, c_vp, c_vp, c_vp, c_vp]),
     'fokl_dchain_create': (c_int, [c_int, c_int, c_vp]),
     'fokl_dchain_destroy': (None, [c_vp]),
     'fokl_dchain_submit': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp,
@@ -1823,6 +1826,29 @@ class DeviceContext:
             _ptr(cols), sources, _ptr(n_src), _ptr(forcing), _ptr(norms), _ptr(table), int(n_basis), int(width), float(h),
             _ptr(y0), int(y0.ndim == 2), int(cut or 0), _ptr(mean), _ptr(bounds), _ptr(members)))
         return mean, bounds, members
+
+    def model_optimize(self, mtx, betas, table, lo, hi, starts, sign, max_iter, tol):
+        """fokl_model_optimize (optimize.optimize assembles the arguments, all in normalised coordinates): mtx int32
+        [terms, m], betas [E, terms + 1], table [n_basis, width], lo / hi [m], starts [S, m], sign +1 (minimise) or -1
+        -> (x [E, S, m], model value [E, S], iterations [E, S], status [E, S]).  Needs no uploaded dataset and leaves
+        one alone."""
+        mtx = np.ascontiguousarray(mtx, dtype=np.int32)
+        betas, table, starts = (np.ascontiguousarray(a, dtype=np.float64) for a in (betas, table, starts))
+        lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+        n_terms, m = mtx.shape
+        if betas.ndim != 2 or betas.shape[1] != n_terms + 1 or starts.ndim != 2 or starts.shape[1] != m or \
+                lo.shape != (m,) or hi.shape != (m,) or table.ndim != 2:
+            raise ValueError("model_optimize: array shapes disagree")
+        E, S = betas.shape[0], starts.shape[0]
+        x = np.empty((E, S, m), dtype=np.float64)
+        f = np.empty((E, S), dtype=np.float64)
+        iterations = np.empty((E, S), dtype=np.int32)
+        status = np.empty((E, S), dtype=np.int32)
+        self._ck(self._lib.fokl_model_optimize(
+            self._h, int(m), int(n_terms), _ptr(mtx), int(E), _ptr(betas), _ptr(table), int(table.shape[0]),
+            int(table.shape[1]), _ptr(lo), _ptr(hi), int(S), _ptr(starts), float(sign), int(max_iter), float(tol), _ptr(x),
+            _ptr(f), _ptr(iterations), _ptr(status)))
+        return x, f, iterations, status
 
     def read_slot(self, slot, row0=0, nrows=None):
         nrows = self.n - row0 if nrows is None else nrows

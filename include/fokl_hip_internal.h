@@ -9,6 +9,7 @@
  *                              the search's per-evaluation work next to the kill-test loop (FR:1650-1690)
  *   fokl_dchain_* / fokl_dspectral_* / fokl_device_dgemm* / fokl_host_alloc
  *                              the device engines behind G3 (and the opt-in G2) and their page-locked memory
+ *   fokl_model_optimize        the multistart optimiser behind fokl_gpy_amd/optimize.py (the boundary's header is full)
  *
  * Same conventions as fokl_hip.h (return codes, row-major fp64, FR = /root/reference/src/FoKL/FoKLRoutines.py).
  */
@@ -554,6 +555,39 @@ int fokl_dspectral_stats(fokl_dspectral *engine, int64_t *submitted, int64_t *la
 /* Page-locked host memory for tapes: the device reads such a tape in place (no copy calls on the dispatcher). */
 int fokl_host_alloc(size_t bytes, void **out);
 int fokl_host_free(void *ptr);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Optimising a fitted model over its posterior (csrc/fokl_optimize_device.inc; fokl_gpy_amd/optimize.py)     */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/*
+ * n_draws x n_starts box-constrained local solves of a 'Bernoulli Polynomials' model at once, one lane per solve:
+ *     minimise  sign * ( betas[e][0] + sum_t betas[e][t + 1] * prod_j phi_{mtx[t][j]}(x_j) )   over  lo <= x <= hi
+ * for every draw e from every start s, in NORMALISED coordinates (the caller de-normalises).  Host memory, row-major:
+ *   mtx    [n_terms, n_inputs]   orders, 0 = the input is not in the term
+ *   betas  [n_draws, n_terms + 1]
+ *   table  [n_basis, width]      row o - 1 holds the o + 1 coefficients of order o, constant first (fokl_upload's
+ *                                Bernoulli layout); an order needs o <= n_basis and o < width
+ *   lo, hi [n_inputs]            the box; lo[j] == hi[j] fixes input j
+ *   starts [n_starts, n_inputs]  clipped to the box
+ *   sign   +1 minimises the model, -1 maximises it;  tol  bound on max_j |P(x - g)_j - x_j| (P clips to the box)
+ * Outputs: x [n_draws, n_starts, n_inputs] the end points, f [n_draws, n_starts] the MODEL's value there,
+ * iterations and status [n_draws, n_starts]: 0 converged, 1 iteration limit (max_iter), 2 non-finite value or gradient,
+ * 3 stalled (no trial point of the line search, Newton or steepest descent, decreases the value).
+ * The iteration -- projected Newton on the active set, Cholesky modified in place where the Hessian is not positive
+ * definite, halving along the projection arc under an Armijo test with a rounding allowance -- is stated in numpy by
+ * optimize.solve_host, which the kernel is tested against: same results up to the rounding of differently ordered sums.
+ * Limits (FOKL_ERR_ARG with a text, nothing is launched): at most 16 inputs; 3 x distinct (input, order) factors +
+ * n_inputs (n_inputs + 1) / 2 + 3 n_inputs <= 288 (a solve's values live in LDS, 64 solves wide, within 144 KB); orders
+ * within the table; lo <= hi, finite; n_draws * n_starts <= 1 048 576; sign +-1, max_iter >= 0, tol >= 0.
+ * Needs a context, no dataset: everything it uses is uploaded by the call and freed before it returns; the context's
+ * dataset, slots and pending launches are left alone (it may be called between fits).  One launch for all solves.
+ * Kernel time: FOKL_K_OPTIMIZE.  Blocking.
+ */
+int fokl_model_optimize(fokl_ctx *ctx, int n_inputs, int n_terms, const int32_t *mtx, int n_draws, const double *betas,
+                        const double *table, int n_basis, int width, const double *lo, const double *hi, int n_starts,
+                        const double *starts, double sign, int max_iter, double tol, double *x, double *f,
+                        int32_t *iterations, int32_t *status);
 
 #ifdef __cplusplus
 }
