@@ -90,6 +90,7 @@ SIGNATURES = {
     'fokl_pool_wait': (c_int, [c_vp]),
     'fokl_pool_busy_seconds': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_pool_noise_waits': (c_int, [c_vp, c_vp, c_vp]),
+    'fokl_pool_chain_segments': (c_int, [c_vp, c_vp, c_vp]),
     'fokl_thread_cpu_seconds': (c_int, [c_vp, c_int]),
     'fokl_pool_stream_stats': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_stream_create': (c_int, [c_vp, c_i32, c_i32, c_dbl, c_int, c_vp, c_int, c_vp]),
@@ -154,6 +155,8 @@ SIGNATURES = {
     'fokl_finish_tape_blocks': (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     'fokl_gibbs_chain_from_finished_tape': (c_int, [c_vp, c_vp, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_vp,
                                                     c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_gibbs_chain_segments_host': (c_int, [c_vp, c_vp, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_vp, c_vp,
+                                               c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
     'fokl_rng_normals': (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'fokl_rng_gammas': (c_int, [c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_i64, c_vp]),
     'fokl_gp_integrate': (c_int, [c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
@@ -620,6 +623,33 @@ def gibbs_chain_from_finished_tape(lamb, qty, b, btau, dtd, sigsqd0, tausqd0, ta
     return w, bool(flag.value)
 
 
+CHAIN_SEGMENTS, CHAIN_WARM = 8, 64      # include/fokl_hip_internal.h: FOKL_CHAIN_SEGMENTS, FOKL_CHAIN_WARM
+
+
+def gibbs_chain_segments_host(lamb, qty, b, btau, dtd, sigsqd0, tausqd0, tape, follow=False, segments=CHAIN_SEGMENTS,
+                              warm=CHAIN_WARM, states=False):
+    """gibbs_chain_from_finished_tape with the recursion in verified segments (fokl_gibbs_chain_segments_host).  Returns
+    (w, bstar_negative, bad_cut), with states=True also the sigsqd and tausqd of every iteration."""
+    lamb = np.ascontiguousarray(lamb, dtype=np.float64)
+    qty = np.ascontiguousarray(qty, dtype=np.float64)
+    p1 = lamb.shape[0]
+    if p1 != tape.p1:
+        raise ValueError("tape was recorded for a different model size")
+    w = np.empty((tape.draws, p1), dtype=np.float64)
+    sigs = np.empty(tape.draws, dtype=np.float64) if states else None
+    taus = np.empty(tape.draws, dtype=np.float64) if states else None
+    flag, bad_cut = ctypes.c_int32(0), ctypes.c_int32(0)
+    ptr = tape.pointers()
+    _check(load().fokl_gibbs_chain_segments_host(_ptr(lamb), _ptr(qty), p1, float(b), float(btau), float(dtd),
+                                                 float(sigsqd0), float(tausqd0), tape.draws, ptr[0], ptr[3], ptr[4],
+                                                 tape.block_done_pointer() if follow else None, tape.BLOCK, _ptr(w),
+                                                 _ptr(sigs) if states else None, _ptr(taus) if states else None,
+                                                 ctypes.byref(flag), int(segments), int(warm), ctypes.byref(bad_cut)))
+    if states:
+        return w, bool(flag.value), bool(bad_cut.value), sigs, taus
+    return w, bool(flag.value), bool(bad_cut.value)
+
+
 # ---------------------------------------------------------------------------------------------------------
 # host threads of one fit
 # ---------------------------------------------------------------------------------------------------------
@@ -864,7 +894,10 @@ class HostPool:
         _check(self._lib.fokl_pool_noise_waits(self._h, ctypes.byref(w[0]), ctypes.byref(w[1])))
         b, ww, seg, ga, ge = c_dbl(0), c_dbl(0), c_i64(0), c_i64(0), c_i64(0)
         _check(self._lib.fokl_pool_stream_stats(self._h, *[ctypes.byref(x) for x in (b, ww, seg, ga, ge)]))
+        cs = [c_i64(0), c_i64(0)]
+        _check(self._lib.fokl_pool_chain_segments(self._h, ctypes.byref(cs[0]), ctypes.byref(cs[1])))
         return dict(noise=v[0].value, chain=v[1].value, finish=v[2].value, spectral=v[3].value,
+                    host_chains_segmented=cs[0].value, host_chain_recuts=cs[1].value,
                     noise_queue_wait=w[0].value, noise_verdict_wait=w[1].value, bulk=b.value, walker_wait=ww.value,
                     stream_segments=seg.value, gamma_attempts=ga.value, gamma_attempts_exact=ge.value)
 

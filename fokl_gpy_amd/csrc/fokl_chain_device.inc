@@ -527,8 +527,8 @@ __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__rest
 // wavefront from start to end, as before: results never depend on the cut, only the time does.  2000 iterations become 314
 // dependent ones: 0.9 ms -> 0.15 ms per chain, and the chain of a sub-stage's model is what its statistics -- hence its kill
 // tests -- wait for.  Draws agree with the one-piece recursion to the check's tolerance times O(1) (contraction, no growth).
-constexpr int kChainSegments = 8;
-constexpr int kChainWarm = 64;
+constexpr int kChainSegments = FOKL_CHAIN_SEGMENTS;         // (fokl_hip_internal.h: the host chain cuts the same way)
+constexpr int kChainWarm = FOKL_CHAIN_WARM;
 constexpr int kChainGammas = 32;                            // gammas staged per wavefront at a time (wave-private LDS)
 
 template <int T>

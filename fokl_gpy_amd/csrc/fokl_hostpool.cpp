@@ -46,6 +46,7 @@ extern void fokl_set_global_error(const std::string &msg);   // fokl_hip.hip
 // fokl_sampler.cpp (library-internal)
 extern "C" __attribute__((visibility("hidden"))) void fokl_finish_tape_rows(int p1, double *normals, const double *pair_r2,
                                                                             const int32_t *lead, int k0, int k1);
+extern "C" __attribute__((visibility("hidden"))) int64_t fokl_chain_follow_waited_ns();     // fokl_sampler.cpp
 extern "C" __attribute__((visibility("hidden"))) int fokl_gibbs_chain_from_raw_blocks(
     const double *lamb, const double *qty, int p1, double b, double btau, double dtd, double sigsqd0, double tausqd0,
     int draws, const double *normals, const double *pair_r2, const int32_t *lead, const double *gam_sig,
@@ -182,6 +183,9 @@ struct fokl_host_pool {
     int32_t *mt_pos = nullptr, *has_gauss = nullptr;
     double *gauss_cache = nullptr;
     std::atomic<int64_t> noise_busy_ns{0}, chain_busy_ns{0}, finish_busy_ns{0}, spectral_busy_ns{0};
+    std::atomic<int64_t> chains_segmented{0}, chain_recuts{0};     // fokl_pool_chain_segments
+    // FOKL_CHAIN_PROFILE=1: one line per host chain on a finished tape (queued, waiting for the tape, recursion, statistics)
+    bool chain_profile = std::getenv("FOKL_CHAIN_PROFILE") != nullptr;
     // where the serial resource waits: for the next request (empty queue) and for the verdict on a tentative tape
     std::atomic<int64_t> noise_queue_wait_ns{0}, noise_verdict_wait_ns{0};
     // completion of any job (fokl_pool_wait spins briefly, then sleeps here: a fit must not burn a core per waiter --
@@ -675,13 +679,32 @@ fokl_host_job *run(fokl_host_pool *pool, fokl_host_job *job)
         busy = &pool->finish_busy_ns;
         break;
     case Kind::chain:
+        if (pool->chain_profile) job->t_start = now_ns();
         if (job->block_done) {
-            rc = fokl_gibbs_chain_from_finished_tape(job->lamb, job->qty, job->p1, job->b, job->btau, job->dtd,
-                                                     job->sigsqd0, job->tausqd0, job->draws, job->normals,
-                                                     job->gam_sig, job->gam_tau, job->block_done, job->block,
-                                                     job->w_out, nullptr, nullptr, job->bstar_negative);
+            // in verified segments (one piece for draws < 4 FOKL_CHAIN_WARM or FOKL_HCHAIN_RECURSION=serial); the chain of
+            // an unfinished tape below stays in one piece: its rows are completed one at a time as the recursion goes
+            int32_t recut = 0;
+            rc = fokl_gibbs_chain_segments_host(job->lamb, job->qty, job->p1, job->b, job->btau, job->dtd, job->sigsqd0,
+                                                job->tausqd0, job->draws, job->normals, job->gam_sig, job->gam_tau,
+                                                job->block_done, job->block, job->w_out, nullptr, nullptr,
+                                                job->bstar_negative, FOKL_CHAIN_SEGMENTS, FOKL_CHAIN_WARM, &recut);
+            const char *recursion = std::getenv("FOKL_HCHAIN_RECURSION");
+            if (job->draws >= 4 * FOKL_CHAIN_WARM && !(recursion && std::strcmp(recursion, "serial") == 0))
+                pool->chains_segmented.fetch_add(1, std::memory_order_relaxed);
+            if (recut) pool->chain_recuts.fetch_add(1, std::memory_order_relaxed);
+            const auto t_chain = std::chrono::steady_clock::now();
             if (rc != FOKL_OK) err = "chain: invalid arguments or the tape producer failed";
             if (rc == FOKL_OK && job->then) job->then(job->then_arg);       // (the draws are complete: what follows from them)
+            if (pool->chain_profile) {
+                // where a sub-stage model's chain spends its time (tools/chain_wait_split.py adds the lines up per fit)
+                const auto us = [](std::chrono::steady_clock::duration d) {
+                    return 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(d).count();
+                };
+                const double waited = 1e-3 * (double)fokl_chain_follow_waited_ns();
+                std::fprintf(stderr, "fokl_chain: p1 %d draws %d queued %.1f us, waited for the tape %.1f us, recursion %.1f us, "
+                                     "statistics %.1f us, recut %d\n", job->p1, job->draws, 1e-3 * (double)(job->t_start - job->t_submit),
+                             waited, us(t_chain - t0) - waited, us(std::chrono::steady_clock::now() - t_chain), (int)recut);
+            }
             busy = &pool->chain_busy_ns;
             break;
         }
@@ -1177,6 +1200,7 @@ extern "C" int fokl_pool_submit_chain(fokl_host_pool *pool, const double *lamb, 
     else
         job->raw_block_done = block_done;                   // ... or only expand them: the chain completes each row
     *out = job;
+    if (pool->chain_profile) job->t_submit = now_ns();
     submit(pool->chain_q, job);
     return FOKL_OK;
 }
@@ -1408,6 +1432,18 @@ extern "C" int fokl_pool_stream_stats(const fokl_host_pool *pool, double *bulk_b
         return FOKL_ERR_ARG;
     }
     return fokl_stream_stats(pool->stream, bulk_busy_s, walker_wait_s, segments, gamma_attempts, gamma_attempts_exact);
+}
+
+// Host chains that ran in verified segments, and those among them that failed the check and ran again in one piece.
+extern "C" int fokl_pool_chain_segments(const fokl_host_pool *pool, int64_t *segmented, int64_t *recuts)
+{
+    if (!pool) {
+        fokl_set_global_error("fokl_pool_chain_segments: null pool");
+        return FOKL_ERR_ARG;
+    }
+    if (segmented) *segmented = pool->chains_segmented.load();
+    if (recuts) *recuts = pool->chain_recuts.load();
+    return FOKL_OK;
 }
 
 // Where the noise thread -- the serial resource of a fit -- was not recording: waiting for the next request with an

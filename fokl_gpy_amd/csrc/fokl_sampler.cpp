@@ -570,6 +570,15 @@ __attribute__((noinline)) void record_tape(LegacyRng &r, int p1, int draws, doub
 
 }  // namespace
 
+// The recursion with a chain's pieces across SIMD lanes (fokl_chain_lanes.inc): this file's two builds hold the portable and
+// the AVX-512 statement, fokl_vlog.cpp the AVX2 one.
+#ifdef FOKL_SAMPLER_WIDE
+#define FOKL_CHAIN_LANES_NAME fokl_chain_lanes_wide
+#else
+#define FOKL_CHAIN_LANES_NAME fokl_chain_lanes_portable
+#endif
+#include "fokl_chain_lanes.inc"
+
 #ifdef FOKL_SAMPLER_WIDE
 
 // chain_vector_portable with one 512-bit register per set of eight lanes (library-internal).
@@ -766,6 +775,29 @@ inline void follow_wait(int &spins)
     }
 }
 
+// FOKL_CHAIN_PROFILE: how long this thread's chains have stood waiting for blocks of their tapes (the pool reads and
+// clears it around a chain job).  The clock is read only when a block is found missing.
+thread_local int64_t t_follow_waited_ns = 0;
+
+struct FollowClock {
+    std::chrono::steady_clock::time_point t0;
+    bool waiting = false;
+    void missing()
+    {
+        if (!waiting) {
+            waiting = true;
+            t0 = std::chrono::steady_clock::now();
+        }
+    }
+    void there()
+    {
+        if (waiting) {
+            waiting = false;
+            t_follow_waited_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        }
+    }
+};
+
 // One Gibbs iteration given its p1 normals and two standard gammas (FR:1521-1548 in the eigenbasis).
 struct ChainState {
     double sigsqd, tausqd;
@@ -923,6 +955,7 @@ extern "C" int fokl_gibbs_chain_from_finished_tape(const double *lamb, const dou
     }
     ChainState st{sigsqd0, tausqd0};
     int ready_block = -1;
+    FollowClock clock;
     for (int k = 0; k < draws; ++k) {
         if (block_done && k / block > ready_block) {
             const int blk = k / block;
@@ -933,8 +966,10 @@ extern "C" int fokl_gibbs_chain_from_finished_tape(const double *lamb, const dou
                     fokl_set_global_error("fokl_gibbs_chain_from_finished_tape: the tape producer failed");
                     return FOKL_ERR_STATE;
                 }
+                clock.missing();
                 follow_wait(spins);
             }
+            clock.there();
             ready_block = blk;
         }
         chain_step(lamb, qty, p1, b, btau, dtd, normals + (size_t)k * p1, gam_sig[k], gam_tau[k],
@@ -943,6 +978,161 @@ extern "C" int fokl_gibbs_chain_from_finished_tape(const double *lamb, const dou
         if (taus_out) taus_out[k] = st.tausqd;
     }
     if (bstar_negative) *bstar_negative = st.flagged;
+    return FOKL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The same recursion in SEGMENTS.  It is a chain through two scalars only, and it forgets them within a few dozen
+// iterations (fokl_chain_device.inc, "the recursion in SEGMENTS", has the argument): the draws are cut into `segments`
+// pieces, piece s starts `warm` iterations early from the chain's initial state, stores nothing and reports nothing
+// before its own first iteration, and must hold there the state the piece before it ends on -- checked once all pieces
+// have run, both scalars to 1e-14 relative.  A chain that fails the check, or one that met bstar < 0, is run again by
+// fokl_gibbs_chain_from_finished_tape from the initial state, every row rewritten: results never depend on the cut by more
+// than the check's tolerance, and a flagged chain returns exactly what it always did.
+//
+// The pieces advance side by side in the lanes of one thread (fokl_chain_lanes.inc: 2000 dependent iterations become 314,
+// the horizontal sums and the scalar tail of an iteration become vector statements).  FOKL_HCHAIN_MAPPING=pieces runs
+// them one after the other through chain_step instead -- the definition the lane form is tested against, and what pieces
+// handed to several threads would compute.  FOKL_HCHAIN_RECURSION=serial: the one-piece function, whatever the arguments.
+// ---------------------------------------------------------------------------------------------------------
+
+extern "C" __attribute__((visibility("hidden"))) void fokl_chain_lanes_avx2(const fokl_lane_chain *, fokl_lane_state *,
+                                                                            int, int);       // fokl_vlog.cpp
+extern "C" __attribute__((visibility("hidden"))) void fokl_chain_lanes_wide(const fokl_lane_chain *, fokl_lane_state *,
+                                                                            int, int);       // fokl_sampler_wide.o
+
+namespace {
+
+bool env_is(const char *name, const char *value)
+{
+    const char *v = std::getenv(name);
+    return v && std::strcmp(v, value) == 0;
+}
+
+// rows [0, upto) of a tape that other threads finish block by block: wait for them (blocks settle in any order)
+int follow_blocks(const int32_t *block_done, int block, int upto, int &ready_blocks)
+{
+    if (!block_done) return FOKL_OK;
+    const int want = (upto + block - 1) / block;
+    FollowClock clock;
+    for (int spins = 0; ready_blocks < want;) {
+        const int32_t flag = __atomic_load_n(block_done + ready_blocks, __ATOMIC_ACQUIRE);
+        if (flag > 0) {
+            ++ready_blocks;
+            spins = 0;
+        } else if (flag < 0) {
+            return FOKL_ERR_STATE;
+        } else {
+            clock.missing();
+            follow_wait(spins);
+        }
+    }
+    clock.there();
+    return FOKL_OK;
+}
+
+}  // namespace
+
+// nanoseconds the calling thread's chains have waited for their tapes since the last call (fokl_hostpool.cpp, FOKL_CHAIN_PROFILE)
+FOKL_INTERNAL int64_t fokl_chain_follow_waited_ns()
+{
+    const int64_t waited = t_follow_waited_ns;
+    t_follow_waited_ns = 0;
+    return waited;
+}
+
+extern "C" int fokl_gibbs_chain_segments_host(const double *lamb, const double *qty, int p1, double b, double btau,
+                                              double dtd, double sigsqd0, double tausqd0, int draws,
+                                              const double *normals, const double *gam_sig, const double *gam_tau,
+                                              const int32_t *block_done, int block, double *w_out, double *sigs_out,
+                                              double *taus_out, int32_t *bstar_negative, int segments, int warm,
+                                              int32_t *bad_cut)
+{
+    if (!lamb || !qty || !normals || !gam_sig || !gam_tau || !w_out || p1 <= 0 || draws < 0 ||
+        (block_done && block < 1) || segments < 1 || segments > kLanePieces || warm < 0) {
+        fokl_set_global_error("fokl_gibbs_chain_segments_host: null pointer, empty model, or segments outside 1..8");
+        return FOKL_ERR_ARG;
+    }
+    if (bad_cut) *bad_cut = 0;
+    const int pieces = draws >= 4 * warm && draws > 0 ? segments : 1;
+    if (pieces == 1 || env_is("FOKL_HCHAIN_RECURSION", "serial"))
+        return fokl_gibbs_chain_from_finished_tape(lamb, qty, p1, b, btau, dtd, sigsqd0, tausqd0, draws, normals, gam_sig,
+                                                   gam_tau, block_done, block, w_out, sigs_out, taus_out, bstar_negative);
+    const int piece = (draws + pieces - 1) / pieces;
+    fokl_lane_state st;
+    for (int s = 0; s < kLanePieces; ++s) {
+        st.sigsqd[s] = st.begin[s][0] = sigsqd0;
+        st.tausqd[s] = st.begin[s][1] = tausqd0;
+    }
+    st.flagged = 0;
+    int ready_blocks = 0;
+    bool producer_failed = false;
+    if (env_is("FOKL_HCHAIN_MAPPING", "pieces")) {
+        std::vector<double> skip((size_t)p1);
+        for (int s = 0; s < pieces && !producer_failed; ++s) {
+            const int k_write = std::min(s * piece, draws), k_end = std::min(k_write + piece, draws);
+            ChainState cs{sigsqd0, tausqd0};
+            for (int k = std::max(s * piece - warm, 0); k < k_end; ++k) {
+                if (follow_blocks(block_done, block, k + 1, ready_blocks) != FOKL_OK) {
+                    producer_failed = true;
+                    break;
+                }
+                if (k == k_write) {
+                    st.begin[s][0] = cs.sigsqd;
+                    st.begin[s][1] = cs.tausqd;
+                }
+                chain_step(lamb, qty, p1, b, btau, dtd, normals + (size_t)k * p1, gam_sig[k], gam_tau[k],
+                           k >= k_write ? w_out + (size_t)k * p1 : skip.data(), cs);
+                if (k >= k_write && sigs_out) sigs_out[k] = cs.sigsqd;
+                if (k >= k_write && taus_out) taus_out[k] = cs.tausqd;
+            }
+            st.sigsqd[s] = cs.sigsqd;
+            st.tausqd[s] = cs.tausqd;
+            st.flagged |= cs.flagged;
+        }
+    } else {
+        fokl_lane_chain c{lamb, qty, normals, gam_sig, gam_tau, w_out, sigs_out, taus_out, p1, draws, pieces, piece, warm,
+                          b, btau, dtd};
+        const int isa = chain_vector_isa();
+        auto *steps = isa == 2 ? fokl_chain_lanes_wide : (isa == 1 ? fokl_chain_lanes_avx2 : fokl_chain_lanes_portable);
+        // step j reads rows up to that of the last piece that has rows, (last piece) piece - warm + j: most of the tape has
+        // to be there before the first step, the rest is followed block by block
+        int last = pieces - 1;
+        while (last > 0 && last * piece >= draws) --last;
+        const int steps_total = warm + piece;
+        for (int j = 0; j < steps_total && !producer_failed;) {
+            int upto = steps_total;
+            if (block_done) {
+                const int top = std::min(last * piece - warm + j, draws - 1);            // (>= 0: draws >= 4 warm)
+                if (follow_blocks(block_done, block, top + 1, ready_blocks) != FOKL_OK) {
+                    producer_failed = true;
+                    break;
+                }
+                const int rows_ready = std::min(ready_blocks * block, draws);
+                upto = rows_ready >= draws ? steps_total : std::min(steps_total, rows_ready - (last * piece - warm));
+            }
+            steps(&c, &st, j, upto);
+            j = upto;
+        }
+    }
+    if (producer_failed) {
+        fokl_set_global_error("fokl_gibbs_chain_segments_host: the tape producer failed");
+        return FOKL_ERR_STATE;
+    }
+    // every piece but the first must have begun where the piece before it ended
+    bool bad = st.flagged != 0;
+    for (int s = 1; s < pieces && !bad; ++s) {
+        if (std::min(s * piece, draws) >= draws) break;     // (an empty piece)
+        const double want[2] = {st.sigsqd[s - 1], st.tausqd[s - 1]};
+        for (int q = 0; q < 2; ++q)
+            if (!(std::fabs(st.begin[s][q] - want[q]) <= 1e-14 * std::fabs(want[q]))) bad = true;
+    }
+    if (bad) {
+        if (bad_cut) *bad_cut = 1;
+        return fokl_gibbs_chain_from_finished_tape(lamb, qty, p1, b, btau, dtd, sigsqd0, tausqd0, draws, normals, gam_sig,
+                                                   gam_tau, block_done, block, w_out, sigs_out, taus_out, bstar_negative);
+    }
+    if (bstar_negative) *bstar_negative = 0;
     return FOKL_OK;
 }
 

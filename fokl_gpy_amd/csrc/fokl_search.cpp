@@ -358,6 +358,7 @@ struct fokl_search {
     std::deque<Outcome *> pending;
     // FOKL_SEARCH_PROFILE=1: where the kill-test loop's own time goes (seconds per section, printed when the search ends)
     bool profile = std::getenv("FOKL_SEARCH_PROFILE") != nullptr;
+    bool chain_profile = std::getenv("FOKL_CHAIN_PROFILE") != nullptr;     // (fokl_hostpool.cpp prints the chain's side)
     double prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::deque<Outcome *> zombies;          // device chains nobody will look at: slots go back once they have run
     std::vector<Outcome *> device_outcomes;  // every device-chained outcome alive (all released when the search ends)
@@ -948,6 +949,8 @@ int wait_host_chain(fokl_search *s, Outcome *o)
         o->chain_waited = true;
         s->stats[S_T_CHAIN] += now_s() - t0;
         s->stats[S_CHAINS_MATERIALISED] += 1;
+        if (s->chain_profile)
+            std::fprintf(stderr, "fokl_search: waited %.1f us for the host chain of p1 %d\n", 1e6 * (now_s() - t0), o->spec->p1);
         if (o->chain_status == FOKL_OK && o->flag && *o->flag)
             o->chain_status = fail(s, FOKL_ERR_NUMERIC,
                                    "bstar < 0 inside the Gibbs chain (only possible with b <= 0): the noise tape "
@@ -2017,19 +2020,57 @@ extern "C" int fokl_outcome_draws(fokl_search *s, fokl_outcome *h, const double 
 // reduction along axis 0 does.  Waits for the chain.
 #define FOKL_STATS_CLONES __attribute__((target_clones("avx512f", "avx2", "default")))
 namespace {
+// beta[k][c] for rows k0 .. k1 - 1.  Every sum starts at 0.0 and takes w[k][j] B[j][c] for j ascending, product and sum rounded
+// separately -- the statement is `b[c] = 0; for j: b[c] += w[k][j] * B[j][c]`.  Written that way the loop is a chain of
+// load-add-store through memory p1 long per row (0.8 ms behind the chain of a 144-column model, more than the chain itself);
+// here kStatRows rows x kStatCols columns of sums stay in registers while j runs, which changes when a sum is formed and
+// not what is added to it in which order: the same bits.  B is copied once with its rows padded to whole groups of columns.
+constexpr int kStatRows = 4, kStatCols = 16;
+
+typedef double stat_v8 __attribute__((vector_size(64)));
+typedef double stat_v8u __attribute__((vector_size(64), aligned(8), may_alias));
+
+template <int R>
+inline __attribute__((always_inline)) void betas_block(const double *__restrict__ w, const double *__restrict__ Bp, int p1,
+                                                       int count, int stride, double *__restrict__ out)
+{
+    for (int c0 = 0; c0 < stride; c0 += kStatCols) {
+        stat_v8 lo[R], hi[R];
+        for (int r = 0; r < R; ++r) lo[r] = hi[r] = stat_v8{0, 0, 0, 0, 0, 0, 0, 0};
+        const int nc = std::min(kStatCols, count - c0);
+        if (nc > 8) {
+            for (int j = 0; j < p1; ++j) {
+                const double *__restrict__ q = Bp + (size_t)j * stride + c0;
+                const stat_v8 q_lo = *reinterpret_cast<const stat_v8u *>(q), q_hi = *reinterpret_cast<const stat_v8u *>(q + 8);
+                for (int r = 0; r < R; ++r) {
+                    const double wj = w[(size_t)r * p1 + j];
+                    lo[r] += wj * q_lo;
+                    hi[r] += wj * q_hi;
+                }
+            }
+        } else {                                            // (the upper eight columns of this group are padding)
+            for (int j = 0; j < p1; ++j) {
+                const stat_v8 q_lo = *reinterpret_cast<const stat_v8u *>(Bp + (size_t)j * stride + c0);
+                for (int r = 0; r < R; ++r) lo[r] += w[(size_t)r * p1 + j] * q_lo;
+            }
+        }
+        for (int r = 0; r < R; ++r)
+            for (int c = 0; c < nc; ++c) out[(size_t)r * count + c0 + c] = c < 8 ? lo[r][c] : hi[r][c - 8];
+    }
+}
+
 FOKL_STATS_CLONES void betas_of_rows(const double *__restrict__ w, const double *__restrict__ B, int p1, int count, int k0,
                                      int k1, double *__restrict__ out)
 {
-    for (int k = k0; k < k1; ++k) {
-        const double *__restrict__ row = w + (size_t)k * p1;
-        double *__restrict__ b = out + (size_t)(k - k0) * count;
-        for (int c = 0; c < count; ++c) b[c] = 0.0;
-        for (int j = 0; j < p1; ++j) {
-            const double wj = row[j];
-            const double *__restrict__ q = B + (size_t)j * count;
-            for (int c = 0; c < count; ++c) b[c] += wj * q[c];
-        }
-    }
+    const int stride = (count + kStatCols - 1) / kStatCols * kStatCols;
+    std::vector<double> padded((size_t)p1 * stride, 0.0);
+    for (int j = 0; j < p1; ++j)
+        for (int c = 0; c < count; ++c) padded[(size_t)j * stride + c] = B[(size_t)j * count + c];
+    const double *__restrict__ Bp = padded.data();
+    int k = k0;
+    for (; k + kStatRows <= k1; k += kStatRows)
+        betas_block<kStatRows>(w + (size_t)k * p1, Bp, p1, count, stride, out + (size_t)(k - k0) * count);
+    for (; k < k1; ++k) betas_block<1>(w + (size_t)k * p1, Bp, p1, count, stride, out + (size_t)(k - k0) * count);
 }
 }  // namespace
 

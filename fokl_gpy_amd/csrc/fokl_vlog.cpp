@@ -69,3 +69,8 @@ extern "C" __attribute__((visibility("hidden"))) void fokl_chain_vector_avx2(
     out[1] = ((a_ty[0] + a_ty[4]) + (a_ty[2] + a_ty[6])) + ((a_ty[1] + a_ty[5]) + (a_ty[3] + a_ty[7]));
     out[2] = ((a_ww[0] + a_ww[4]) + (a_ww[2] + a_ww[6])) + ((a_ww[1] + a_ww[5]) + (a_ww[3] + a_ww[7]));
 }
+
+// The recursion with a chain's pieces across SIMD lanes, two 256-bit registers per set of eight pieces (fokl_sampler.cpp:
+// fokl_gibbs_chain_segments_host picks the statement as chain_vector_part does).
+#define FOKL_CHAIN_LANES_NAME fokl_chain_lanes_avx2
+#include "fokl_chain_lanes.inc"

@@ -1249,6 +1249,8 @@ class ForwardSelection:
                                   pool_finish_s=busy['finish'], pool_spectral_s=busy['spectral'],
                                   noise_queue_wait_s=busy['noise_queue_wait'],
                                   noise_verdict_wait_s=busy['noise_verdict_wait'],
+                                  host_chains_segmented=busy.get('host_chains_segmented', 0),
+                                  host_chain_recuts=busy.get('host_chain_recuts', 0),
                                   spectral_remote=self.host.remote_results, exchanges=self.host.exchanges,
                                   spectral_submitted=self.stats.get('spectral_submitted', 0) + self.host.spectral_submitted)
                 self.host = None

@@ -9,6 +9,8 @@
  *                              the search's per-evaluation work next to the kill-test loop (FR:1650-1690)
  *   fokl_dchain_* / fokl_dspectral_* / fokl_device_dgemm* / fokl_host_alloc
  *                              the device engines behind G3 (and the opt-in G2) and their page-locked memory
+ *   fokl_gibbs_chain_segments_host
+ *                              a host chain's recursion in verified segments (the boundary's header is full)
  *   fokl_model_optimize        the multistart optimiser behind fokl_gpy_amd/optimize.py (the boundary's header is full)
  *
  * Same conventions as fokl_hip.h (return codes, row-major fp64, FR = /root/reference/src/FoKL/FoKLRoutines.py).
@@ -240,6 +242,35 @@ int fokl_pool_noise_waits(const fokl_host_pool *pool, double *queue_wait, double
  * threads, spectral threads, the stream's bulk threads, the device-chain dispatchers (live).  -> 6, or an error.  What a fit
  * costs in CPU and where: the figure that bounds fits running side by side on a host with a CPU quota. */
 int fokl_thread_cpu_seconds(double *seconds, int count);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* A host chain's recursion in verified segments (csrc/fokl_sampler.cpp, csrc/fokl_chain_lanes.inc)          */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/* How a chain is cut, on the device (gibbs_chain_segments_kernel) and on the host: pieces, and the iterations a piece
+ * starts early. */
+#define FOKL_CHAIN_SEGMENTS 8
+#define FOKL_CHAIN_WARM 64
+
+/*
+ * fokl_gibbs_chain_from_finished_tape (same arguments, same waiting on block_done) with the draws cut into `segments`
+ * pieces (1..8) when draws >= 4 * warm, one piece otherwise: piece s runs iterations [max(s piece - warm, 0),
+ * min((s + 1) piece, draws)), piece = ceil(draws / segments), from (sigsqd0, tausqd0) and writes nothing before s piece.
+ * Accepted if every non-empty piece but the first holds, in front of its first own iteration, the state the piece before
+ * it ended on (both scalars, |have - want| <= 1e-14 |want|) and no piece met bstar < 0; otherwise the one-piece function
+ * runs from the initial state, every row is rewritten and *bad_cut = 1 (NULL allowed) -- a flagged chain returns exactly
+ * what fokl_gibbs_chain_from_finished_tape returns.  Within a piece an iteration is the one-piece function's, bit for bit
+ * from the same entering state, in the portable, AVX2 and AVX-512 statements alike (FOKL_CHAIN_ISA).  The pieces run in
+ * the SIMD lanes of the calling thread; FOKL_HCHAIN_MAPPING=pieces runs them one after the other (tests), and
+ * FOKL_HCHAIN_RECURSION=serial calls the one-piece function whatever the arguments.
+ */
+int fokl_gibbs_chain_segments_host(const double *lamb, const double *qty, int p1, double b, double btau, double dtd,
+                                   double sigsqd0, double tausqd0, int draws, const double *normals,
+                                   const double *gam_sig, const double *gam_tau, const int32_t *block_done, int block,
+                                   double *w_out, double *sigs_out, double *taus_out, int32_t *bstar_negative,
+                                   int segments, int warm, int32_t *bad_cut);
+/* Host chains of this pool that ran in segments, and those among them that failed the check and ran again in one piece. */
+int fokl_pool_chain_segments(const fokl_host_pool *pool, int64_t *segmented, int64_t *recuts);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* The search's per-evaluation work off the driver thread: tapes on order, G2 ahead, chains, kill tests     */
