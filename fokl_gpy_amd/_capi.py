@@ -181,6 +181,7 @@ SIGNATURES = {
     'fokl_dchain_fetch_w': (c_int, [c_vp, c_i64, c_vp]),
     'fokl_dchain_release': (c_int, [c_vp, c_i64]),
     'fokl_dchain_stats': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_dchain_recuts': (c_int, [c_vp, c_vp]),
     'fokl_dspectral_create': (c_int, [c_int, c_vp]),
     'fokl_dspectral_destroy': (None, [c_vp]),
     'fokl_dspectral_max_columns': (c_int, []),
@@ -1269,7 +1270,7 @@ class DeviceChainJob:
         self._mark = float(ticket) if ticket is not None else 0.0
         self._misses = 0
         if stats_address:
-            self._area = np.ctypeslib.as_array((ctypes.c_double * (6 + p1)).from_address(stats_address))
+            self._area = np.ctypeslib.as_array((ctypes.c_double * (7 + p1)).from_address(stats_address))
             self._flag = ctypes.c_double.from_address(stats_address + 8 * (4 + p1))
 
     def resolve(self, commit):
@@ -1308,6 +1309,21 @@ class DeviceChainJob:
         if self._area is not None and self._ran():
             return float(self._area[5 + self.p1])
         return 0.0
+
+    @property
+    def rows_averaged(self):
+        """How many rows (from ``stat_first`` on) the mean of w was formed over."""
+        self.wait()
+        return int(self._stats[3])
+
+    @property
+    def bad_cut(self):
+        """True when the segmented recursion found the chain not to forget its state within a warm-up and ran it again in
+        one piece (read in place: before ``release``)."""
+        self.wait()
+        if self._area is None:
+            raise RuntimeError("device chain: released, its statistics area belongs to another chain")
+        return bool(self._area[6 + self.p1] != 0.0)
 
     @property
     def last_state(self):
@@ -1412,7 +1428,10 @@ class DeviceChainEngine:
         busy, issued, launches, staged = c_dbl(0), c_i64(0), c_i64(0), c_i64(0)
         _check(self._lib.fokl_dchain_stats(self._h, ctypes.byref(busy), ctypes.byref(issued), ctypes.byref(launches),
                                            ctypes.byref(staged)))
-        return dict(dispatch_s=busy.value, issued=issued.value, launches=launches.value, staged=staged.value)
+        recuts = c_i64(0)
+        _check(self._lib.fokl_dchain_recuts(self._h, ctypes.byref(recuts)))
+        return dict(dispatch_s=busy.value, issued=issued.value, launches=launches.value, staged=staged.value,
+                    recuts=recuts.value)
 
 
 class DeviceSpectralJob:

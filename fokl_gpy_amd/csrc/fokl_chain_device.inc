@@ -39,10 +39,11 @@ struct ChainArgs {
     double *normals;                     // [draws][p1] device, finished
     double *gam_sig, *gam_tau;           // [draws] device
     double *w;                           // [draws][p1] device
-    double *stats;                       // [5 + p1] page-locked host memory: flagged, last sigsqd, last tausqd, rows, mean w
+    double *stats;                       // [7 + p1] page-locked host memory: flagged, last sigsqd, last tausqd, rows, mean w
                                          // [p1], and -- written last -- the job's ticket: the host's completion flag
     double b, btau, dtd, sigsqd0, tausqd0, ticket;
-    double seconds_per_tick;             // of wall_clock64: the kernel times itself (stats[5 + p1], after the ticket's slot)
+    double seconds_per_tick;             // of wall_clock64: the kernel times itself (stats[5 + p1], after the ticket's slot;
+                                         // stats[6 + p1]: 1.0 when the segmented recursion ran the chain again in one piece)
     int p1, draws, stat_first, finished;
     // the tape as ROWS OF POSITIONS (round 4: fokl_stream_walk): expanded on the device from its own copy of the stream
     const fokl_tape_row *rows;           // [draws] page-locked host memory, or NULL: the arrays above
@@ -448,7 +449,9 @@ __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__rest
                 } else {
                     const double two_b = 2.0 * bstar, r_gs = gam[2][k & (GCH - 1)];
                     inv_tau = (gt * two_b) * rcp_newton1(q_ww * gs + a.btau * two_b);   // the next iteration's critical path
-                    sig = bstar > 0.0 ? (bstar * rsq_newton1(bstar)) * r_gs : 0.0;
+                    // (bstar == 0: sigma = 0 without 0 * inf; bstar NaN -- the rows behind a flagged one -- stays NaN, as
+                    // the host chain's last sigma^2 does)
+                    sig = bstar > 0.0 ? (bstar * rsq_newton1(bstar)) * r_gs : bstar;
                     sigsqd = sig * sig;
                 }
                 continue;
@@ -506,6 +509,7 @@ __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__rest
         gstore(a.stats + 2, tausqd);
         gstore(a.stats + 3, (double)rows);
         gstore(a.stats + 5 + p1, (double)(wall_clock64() - t_begin) * a.seconds_per_tick);   // the chain's own duration
+        gstore(a.stats + 6 + p1, 0.0);                      // (no cut to fail: a recycled slot never shows an old 1)
     }
     // the ticket is the completion flag the host polls (plain loads from its own page-locked memory -- no runtime call):
     // everything above is visible system-wide before it
@@ -524,9 +528,11 @@ __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__rest
 // from the chain's initial state, throws those iterations away, and must arrive at its first real iteration with the state the
 // piece before it ENDS on -- which is checked (both scalars to 1e-14 relative) once all pieces have run.  A chain whose state
 // is not forgotten that fast (a prior precision comparable to its small eigenvalues) fails the check and is run again by one
-// wavefront from start to end, as before: results never depend on the cut, only the time does.  2000 iterations become 314
-// dependent ones: 0.9 ms -> 0.15 ms per chain, and the chain of a sub-stage's model is what its statistics -- hence its kill
-// tests -- wait for.  Draws agree with the one-piece recursion to the check's tolerance times O(1) (contraction, no growth).
+// wavefront from start to end, as before (stats[6 + p1] says so, and the engine counts such chains: they are paid for
+// twice).  A cut that passes is exact to the check's tolerance, not to the bit: the draws of an accepted cut agree with the
+// one-piece recursion to 1e-14 times O(1) (contraction, no growth), those of a chain that was run again are the one-piece
+// recursion's bits.  2000 iterations become 314 dependent ones: 0.9 ms -> 0.15 ms per chain, and the chain of a sub-stage's
+// model is what its statistics -- hence its kill tests -- wait for.
 constexpr int kChainSegments = FOKL_CHAIN_SEGMENTS;         // (fokl_hip_internal.h: the host chain cuts the same way)
 constexpr int kChainWarm = FOKL_CHAIN_WARM;
 constexpr int kChainGammas = 32;                            // gammas staged per wavefront at a time (wave-private LDS)
@@ -611,7 +617,7 @@ __device__ __forceinline__ void chain_segment(const ChainArgs &a, const ChainLan
             } else {
                 const double two_b = 2.0 * bstar;
                 inv_tau = (gt * two_b) * rcp_newton1(q_ww * gs + a.btau * two_b);
-                sig = bstar > 0.0 ? (bstar * rsq_newton1(bstar)) * r_gs : 0.0;
+                sig = bstar > 0.0 ? (bstar * rsq_newton1(bstar)) * r_gs : bstar;    // (0 stays 0, NaN stays NaN)
                 sigsqd = sig * sig;
             }
         }
@@ -720,10 +726,15 @@ __global__ __launch_bounds__(64 * kChainSegments) void gibbs_chain_segments_kern
         gstore(a.stats + 2, 1.0 / fin[1]);
         gstore(a.stats + 3, (double)rows);
         gstore(a.stats + 5 + p1, (double)(wall_clock64() - t_begin) * a.seconds_per_tick);
-        gstore(a.stats + 6 + p1, (double)bad_cut);          // (diagnostic: this chain ran as one piece after all)
+        gstore(a.stats + 6 + p1, (double)bad_cut);          // this chain ran as one piece after all (DeviceChainJob.bad_cut)
     }
-    __syncthreads();
+    // All eight wavefronts have stored into host memory (means of the columns from 64 on, rows of w): each one makes its
+    // own stores visible system-wide FIRST, the barrier then tells thread 0 that every fence is behind, and only then is
+    // the ticket stored.  (Barrier first, fences second let thread 0 pass its own fence and publish the ticket while
+    // another wavefront's means were still on their way: the barrier does not wait for outstanding stores.)
     __threadfence_system();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (the fence's own wait, spelled out: the compiler may not drop it)
+    __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_store(a.stats + 4 + p1, a.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -782,6 +793,7 @@ struct ChainJob {
     int status = FOKL_OK;
     std::string error;
     int64_t t_submit = 0;
+    std::atomic<bool> counted{false};                                   // its fallback indicator has been added to `recuts`
 };
 
 }  // namespace
@@ -800,6 +812,7 @@ struct fokl_dchain {
     bool stop = false;
     int flush = 0;                                                      // somebody waits: issue what is there at once
     bool fast = true;                                                   // FOKL_DCHAIN_RECURSION = fast (default) | exact
+    bool segments = true;                                               // ... | serial: the fast recursion on one wavefront
     double seconds_per_tick = 1e-8;                                     // wall_clock64 (hipDeviceAttributeWallClockRate)
     int batch_target = 16;                                              // FOKL_DCHAIN_BATCH
     int64_t batch_delay_ns = 1000000;                                   // FOKL_DCHAIN_DELAY_US
@@ -814,6 +827,7 @@ struct fokl_dchain {
     std::atomic<int64_t> segments_made{0}, rows_jobs{0};
     std::thread dispatcher;
     std::atomic<int64_t> busy_ns{0}, issued{0}, launches{0}, staged{0};
+    std::atomic<int64_t> recuts{0};                                     // chains that failed their cut and ran again in one piece
     int64_t ph[6] = {0, 0, 0, 0, 0, 0};   // development: where the dispatcher's time goes (FOKL_DCHAIN_TRACE)
     std::string err;
 };
@@ -901,13 +915,12 @@ bool device_can_read(const void *ptr, size_t bytes)
     return at >= it->first && at + bytes <= it->first + it->second;
 }
 
-// FOKL_DCHAIN_RECURSION=serial: the fast recursion on one wavefront from start to end (round 5) instead of in segments
-const bool g_chain_segments = !(std::getenv("FOKL_DCHAIN_RECURSION") && std::strcmp(std::getenv("FOKL_DCHAIN_RECURSION"), "serial") == 0);
-
+// segments == false (FOKL_DCHAIN_RECURSION=serial when the engine was created): the fast recursion on one wavefront from
+// start to end (round 5) instead of in segments
 template <int T>
-void launch_chain(const fokl::ChainArgs *d_jobs, int count, hipStream_t stream, bool fast)
+void launch_chain(const fokl::ChainArgs *d_jobs, int count, hipStream_t stream, bool fast, bool segments)
 {
-    if (fast && g_chain_segments)
+    if (fast && segments)
         hipLaunchKernelGGL((fokl::gibbs_chain_segments_kernel<T>), dim3((unsigned)count), dim3(64 * fokl::kChainSegments), 0,
                            stream, d_jobs);
     else if (fast)
@@ -1120,13 +1133,13 @@ int dchain_issue(fokl_dchain *e, std::vector<ChainJob *> &batch_jobs, int batch_
         while (last < batch_jobs.size() && chain_class(batch_jobs[last]->p1) == cls) ++last;
         const int count = (int)(last - first);
         switch (cls) {
-        case 1: launch_chain<1>(d_args + first, count, stream, e->fast); break;
-        case 2: launch_chain<2>(d_args + first, count, stream, e->fast); break;
-        case 3: launch_chain<3>(d_args + first, count, stream, e->fast); break;
-        case 4: launch_chain<4>(d_args + first, count, stream, e->fast); break;
-        case 6: launch_chain<6>(d_args + first, count, stream, e->fast); break;
-        case 8: launch_chain<8>(d_args + first, count, stream, e->fast); break;
-        default: launch_chain<kChainMaxT>(d_args + first, count, stream, e->fast); break;
+        case 1: launch_chain<1>(d_args + first, count, stream, e->fast, e->segments); break;
+        case 2: launch_chain<2>(d_args + first, count, stream, e->fast, e->segments); break;
+        case 3: launch_chain<3>(d_args + first, count, stream, e->fast, e->segments); break;
+        case 4: launch_chain<4>(d_args + first, count, stream, e->fast, e->segments); break;
+        case 6: launch_chain<6>(d_args + first, count, stream, e->fast, e->segments); break;
+        case 8: launch_chain<8>(d_args + first, count, stream, e->fast, e->segments); break;
+        default: launch_chain<kChainMaxT>(d_args + first, count, stream, e->fast, e->segments); break;
         }
         e->launches.fetch_add(1, std::memory_order_relaxed);
         first = last;
@@ -1328,13 +1341,17 @@ ChainJob *dchain_settled(fokl_dchain *e, int64_t ticket, int *rc)
     return job;
 }
 
-// The job has run: the recursion kernel's last store is the job's ticket behind its statistics.
-int dchain_complete(fokl_dchain *e, const ChainJob *job, bool block)
+// The job has run: the recursion kernel's last store is the job's ticket behind its statistics.  The first caller to see
+// that also reads the job's fallback indicator (the slot is the job's until it is released) into the engine's counter.
+int dchain_complete(fokl_dchain *e, ChainJob *job, bool block)
 {
-    const double *flag = e->slots[(size_t)job->slot].h_stats + 4 + job->p1;
-    if (flag_set(flag, (double)job->ticket)) return 1;
-    if (!block) return 0;
-    return await_flag(flag, (double)job->ticket, job->stream);
+    const double *stats = e->slots[(size_t)job->slot].h_stats;
+    const double *flag = stats + 4 + job->p1;
+    int ran = flag_set(flag, (double)job->ticket) ? 1 : 0;
+    if (!ran && block) ran = await_flag(flag, (double)job->ticket, job->stream);
+    if (ran == 1 && !job->counted.exchange(true, std::memory_order_relaxed) && stats[6 + job->p1] != 0.0)
+        e->recuts.fetch_add(1, std::memory_order_relaxed);
+    return ran;
 }
 
 }  // namespace
@@ -1374,7 +1391,10 @@ extern "C" int fokl_dchain_create(int device, int slots, fokl_dchain **out)
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0)
         e->seconds_per_tick = 1e-3 / (double)khz;
-    if (const char *v = std::getenv("FOKL_DCHAIN_RECURSION")) e->fast = std::strcmp(v, "exact") != 0;
+    if (const char *v = std::getenv("FOKL_DCHAIN_RECURSION")) {
+        e->fast = std::strcmp(v, "exact") != 0;
+        e->segments = std::strcmp(v, "serial") != 0;
+    }
     if (const char *v = std::getenv("FOKL_DCHAIN_STREAMS")) e->n_streams = std::max(1, std::min(kChainStreams, std::atoi(v)));
     if (const char *v = std::getenv("FOKL_DCHAIN_BATCH")) e->batch_target = std::max(1, std::min(kChainBatchMax, std::atoi(v)));
     if (const char *v = std::getenv("FOKL_DCHAIN_DELAY_US")) e->batch_delay_ns = 1000LL * std::max(0, std::atoi(v));
@@ -1701,6 +1721,13 @@ extern "C" int fokl_dchain_stats(fokl_dchain *e, double *busy_seconds, int64_t *
     if (issued) *issued = e->issued.load(std::memory_order_relaxed);
     if (launches) *launches = e->launches.load(std::memory_order_relaxed);
     if (staged) *staged = e->staged.load(std::memory_order_relaxed);
+    return FOKL_OK;
+}
+
+extern "C" int fokl_dchain_recuts(fokl_dchain *e, int64_t *recuts)
+{
+    if (!e || !recuts) return dchain_fail(e, FOKL_ERR_ARG, "fokl_dchain_recuts: null pointer");
+    *recuts = e->recuts.load(std::memory_order_relaxed);
     return FOKL_OK;
 }
 

@@ -510,10 +510,11 @@ void fokl_run_destroy(fokl_run *run);
  * last tau^2, rows averaged, mean over rows stat_first .. draws - 1 of w} -- what the kill tests look at
  * (FR:1671: mean intercept draw = mean w . Q[0, :]).  fokl_dchain_fetch_w copies the draws in the eigenbasis
  * w [draws, p1] (betas = w Q') to the host; fokl_dchain_release frees the slot (idempotent).
- * `stats_area` (may be NULL) receives the address of the job's statistics in page-locked host memory: the five + p1
+ * `stats_area` (may be NULL) receives the address of the job's statistics in page-locked host memory: the seven + p1
  * doubles the recursion kernel writes -- the four + p1 of fokl_dchain_wait, then the job's ticket (as a double),
  * stored last with system-wide release semantics: a caller may poll that word instead of calling fokl_dchain_poll;
- * one more double behind it holds the seconds the chain's wavefront ran (the kernel's own clock).
+ * behind it the seconds the chain's kernel ran (its own clock), and 1.0 when the segmented recursion found that the
+ * chain does not forget its state within a warm-up and ran it again in one piece (0.0 otherwise).
  * The area belongs to the job's slot: valid until the job is released.
  * Errors: FOKL_ERR_STATE when every slot is taken (the caller runs that chain on the host). */
 int fokl_dchain_create(int device, int slots, fokl_dchain **out);
@@ -553,6 +554,9 @@ int fokl_dchain_try_release(fokl_dchain *engine, int64_t ticket);
  * queued, at once when somebody waits for a result); `staged` = chains whose tape was not in page-locked memory and
  * went through copy calls + a device staging buffer instead of being read in place */
 int fokl_dchain_stats(fokl_dchain *engine, double *busy_seconds, int64_t *issued, int64_t *launches, int64_t *staged);
+/* chains, among those seen to have run (wait, poll, fetch or release), that the segmented recursion ran a second time in
+ * one piece: each costs a one-wavefront chain on top of the segmented one */
+int fokl_dchain_recuts(fokl_dchain *engine, int64_t *recuts);
 
 /* ---- G2 on the device: eigen-decompositions of candidate models' XtX sub-blocks -------------------------------------
  * Replaces, for models of up to FOKL_DSPECTRAL_MAX_COLUMNS columns, the scipy.linalg.eigh call of FoKLRoutines.py:1499

@@ -261,3 +261,20 @@ class StandInChainEngine:
 
     def close(self):
         self._pool.shutdown(wait=True)
+
+
+def slow_chain_case(p1, draws=2000, extra=4.0, finish=True):
+    """A chain that stays FINITE and does not forget: a gamma shape of p1 / 2 + `extra` carries sigma^2 from one iteration to
+    the next with the weight ~ (p1 / 2) / (p1 / 2 + extra), and the cut holds once that weight to the 64th power is below
+    1e-14 -- never at extra = 4, always (p1 <= 130) at extra = 400.  dtd stands well above sum qty^2 / lamb, so bstar stays
+    positive.  -> lamb, qty, (b, btau, dtd, sigsqd0, tausqd0), tape.
+    (tests/test_chain_segments_host.py on the host twin, tests/test_chain_device.py on the device.)"""
+    np.random.seed(7 + p1)
+    tape = _capi.noise_tape(p1, draws, p1 / 2 + extra, p1 / 2 + 3.0, _capi.LegacyStream())
+    if finish:
+        _capi.finish_tape_blocks(tape)
+    rng = np.random.default_rng(p1)
+    lamb = np.sort(rng.random(p1) * 10 + 1e-3)
+    qty = rng.standard_normal(p1) * np.sqrt(lamb) * 3
+    dtd = np.sum(qty ** 2 / lamb) * 1.5 + 10
+    return lamb, qty, (50.0, 2.0, dtd, 5.0, 0.9), tape

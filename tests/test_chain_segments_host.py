@@ -8,7 +8,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import ROOT
+from helpers import ROOT, slow_chain_case as slow_case
 from fokl_gpy_amd import _capi
 
 SIZES = (1, 7, 8, 9, 64, 100, 145)
@@ -98,15 +98,22 @@ def test_other_cuts_and_warm_ups(mapping):
 @pytest.mark.parametrize('name', ['lanes', 'pieces'])
 def test_a_chain_that_does_not_forget_runs_in_one_piece(name, mapping):
     """(d) A gamma shape barely above p1 / 2 carries sigma^2 from one iteration to the next almost undamped: the pieces do not
-    meet, bad_cut is reported and the result is the one-piece recursion's, bit for bit."""
-    p1 = 100
-    lamb, qty, tape = _case(p1, 2000, astar=p1 / 2 + 4.0, atau_star=p1 / 2 + 3.0)
-    lamb = lamb * 1e-4                                                   # eigenvalues comparable to 1 / tausqd
-    args = (50.0, 2.0, 40.0, 5.0, 0.9)
-    want, want_flag = _capi.gibbs_chain_from_finished_tape(lamb, qty, *args, tape)
-    mapping(mapping=name)
-    w, flag, bad_cut = _capi.gibbs_chain_segments_host(lamb, qty, *args, tape)
-    assert bad_cut and flag == want_flag and _same_bits(w, want)
+    meet at FINITE states, bad_cut is reported and the result is the one-piece recursion's, bit for bit.  (Not a flagged
+    chain: every draw is finite.  That case is test_a_flagged_chain_returns_what_it_always_did.)"""
+    for p1 in (20, 100, 200):
+        lamb, qty, args, tape = slow_case(p1)
+        want, want_flag = _capi.gibbs_chain_from_finished_tape(lamb, qty, *args, tape)
+        assert not want_flag and np.isfinite(want).all()
+        mapping(mapping=name)
+        w, flag, bad_cut = _capi.gibbs_chain_segments_host(lamb, qty, *args, tape)
+        assert bad_cut and not flag and np.isfinite(w).all() and _same_bits(w, want)
+        # the same model under a gamma shape that forgets: the cut holds, the draws are the one-piece recursion's to 1e-12
+        if p1 <= 130:
+            lamb, qty, args, tape = slow_case(p1, extra=400.0)
+            want, _ = _capi.gibbs_chain_from_finished_tape(lamb, qty, *args, tape)
+            w, flag, bad_cut = _capi.gibbs_chain_segments_host(lamb, qty, *args, tape)
+            assert not bad_cut and not flag
+            assert np.max(np.abs(w - want) / np.max(np.abs(want), axis=0)) < 1e-12
 
 
 @pytest.mark.parametrize('name', ['lanes', 'pieces'])
