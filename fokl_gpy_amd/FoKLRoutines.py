@@ -12,7 +12,8 @@ or a gfx950 device they raise.
 
 Deliberately NOT rebuilt: ``to_pyomo`` (FR:1796-1805), a symbolic export for Pyomo's solvers; calling it raises
 ``NotImplementedError``.  ``optimize`` is what this package offers in its place: the question the export exists to
-answer, asked of the device.
+answer, asked of the device.  ``optimize.optimize_system`` covers the export's other uses -- several models in one
+problem (one's output another's input), an output pinned to a value, constraints on outputs.
 
 Device selection is by environment (``FOKL_DEVICE``, else ``LOCAL_RANK``, else 0), never by a new keyword:
 unknown keywords must keep raising ``ValueError`` exactly like the reference (FR:78).

@@ -17,6 +17,7 @@ UNIQUE_ID_BYTES = 128
 K_BASIS, K_GRAM, K_RESID, K_PREDICT, K_RESID_MF, K_GRAM_MFMA, K_GRAM_REDUCE = 0, 1, 2, 3, 4, 5, 6
 K_INTEGRATE, K_BAND = 7, 8
 K_OPTIMIZE = 9
+K_OPTIMIZE_SYSTEM = 10
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
@@ -165,6 +166,9 @@ SIGNATURES = {
                                            c_vp, c_vp, c_int, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
     'fokl_model_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_dbl,
                                     c_int, c_dbl, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_system_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int,
+                                     c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp,
+                                     c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_dchain_create': (c_int, [c_int, c_int, c_vp]),
     'fokl_dchain_destroy': (None, [c_vp]),
     'fokl_dchain_submit': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp,
@@ -1901,6 +1905,41 @@ class DeviceContext:
             int(table.shape[1]), _ptr(lo), _ptr(hi), int(S), _ptr(starts), float(sign), int(max_iter), float(tol), _ptr(x),
             _ptr(f), _ptr(iterations), _ptr(status)))
         return x, f, iterations, status
+
+    def system_optimize(self, p):
+        """fokl_system_optimize for a system prepared by ``optimize._prepare_system`` (common normalised coordinates)
+        -> (x [E, S, n], objective [E, S], violation [E, S], model values [E, S, K], multipliers [E, S, C], iterations
+        [E, S], status [E, S]): what ``optimize.solve_system_host`` returns.  Needs no uploaded dataset and leaves one
+        alone."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        n, K, cons = int(p['n']), int(p['K']), p['cons']
+        C = len(cons)
+        n_inputs, n_terms = i32([m.shape[1] for m in p['mtxs']]), i32([m.shape[0] for m in p['mtxs']])
+        mtx = i32(np.concatenate([np.asarray(m, dtype=np.int32).ravel() for m in p['mtxs']]))
+        var_of = i32(np.concatenate(p['var_of']))
+        shift, slope = f64(np.concatenate(p['shift'])), f64(np.concatenate(p['slope']))
+        betas, table, starts, lo, hi = f64(p['coef']), f64(p['table']), f64(p['starts']), f64(p['lo']), f64(p['hi'])
+        if betas.ndim != 2 or betas.shape[1] != int(n_terms.sum()) + K or starts.ndim != 2 or starts.shape[1] != n or \
+                lo.shape != (n,) or hi.shape != (n,) or table.ndim != 2 or var_of.shape != shift.shape or \
+                var_of.shape[0] != int(n_inputs.sum()):
+            raise ValueError("system_optimize: array shapes disagree")
+        con_model, con_var = i32([c['model'] for c in cons]), i32([c['var'] for c in cons])
+        con_par = f64([[c['lo'], c['hi'], c['scale'], c['offset'], c['span']] for c in cons]).reshape(C, 5)
+        obj_var = int(p['obj_var'])
+        offset, span = (0.0, 1.0) if obj_var >= 0 else (0.0, 0.0)          # a variable objective: its normalised coordinate
+        E, S = betas.shape[0], starts.shape[0]
+        x = np.empty((E, S, n), dtype=np.float64)
+        f, violation = np.empty((E, S), dtype=np.float64), np.empty((E, S), dtype=np.float64)
+        y, mu = np.empty((E, S, K), dtype=np.float64), np.empty((E, S, C), dtype=np.float64)
+        iterations, status = np.empty((E, S), dtype=np.int32), np.empty((E, S), dtype=np.int32)
+        self._ck(self._lib.fokl_system_optimize(
+            self._h, n, K, _ptr(n_inputs), _ptr(n_terms), _ptr(mtx), _ptr(var_of), _ptr(shift), _ptr(slope), int(E),
+            _ptr(betas), _ptr(table), int(table.shape[0]), int(table.shape[1]), _ptr(lo), _ptr(hi), int(S), _ptr(starts),
+            int(p['obj_model']), obj_var, offset, span, float(p['sign']), C, _ptr(con_model), _ptr(con_var), _ptr(con_par),
+            int(p['max_iter']), float(p['tol']), float(p['ctol']), _ptr(x), _ptr(f), _ptr(violation), _ptr(y), _ptr(mu),
+            _ptr(iterations), _ptr(status)))
+        return x, f, violation, y, mu, iterations, status
 
     def read_slot(self, slot, row0=0, nrows=None):
         nrows = self.n - row0 if nrows is None else nrows

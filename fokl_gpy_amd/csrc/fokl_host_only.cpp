@@ -53,6 +53,17 @@ extern "C" int fokl_model_optimize(fokl_ctx *, int, int, const int32_t *, int, c
     return FOKL_ERR_HIP;
 }
 
+// Neither does the constrained optimiser over a system of models (fokl_optimize_system_device.inc;
+// optimize.solve_system_host).
+extern "C" int fokl_system_optimize(fokl_ctx *, int, int, const int32_t *, const int32_t *, const int32_t *, const int32_t *,
+                                    const double *, const double *, int, const double *, const double *, int, int,
+                                    const double *, const double *, int, const double *, int, int, double, double, double, int,
+                                    const int32_t *, const int32_t *, const double *, int, double, double, double *, double *,
+                                    double *, double *, double *, int32_t *, int32_t *)
+{
+    return FOKL_ERR_HIP;
+}
+
 // The device chain engine and page-locked memory do not exist in these builds: the native search (fokl_search.cpp) is
 // then created without an engine and falls back to ordinary memory for its tapes.
 extern "C" int fokl_host_alloc(size_t, void **out)

@@ -12,6 +12,7 @@
  *   fokl_gibbs_chain_segments_host
  *                              a host chain's recursion in verified segments (the boundary's header is full)
  *   fokl_model_optimize        the multistart optimiser behind fokl_gpy_amd/optimize.py (the boundary's header is full)
+ *   fokl_system_optimize       its constrained counterpart over a system of models (optimize.optimize_system)
  *
  * Same conventions as fokl_hip.h (return codes, row-major fp64, FR = /root/reference/src/FoKL/FoKLRoutines.py).
  */
@@ -623,6 +624,56 @@ int fokl_model_optimize(fokl_ctx *ctx, int n_inputs, int n_terms, const int32_t 
                         const double *table, int n_basis, int width, const double *lo, const double *hi, int n_starts,
                         const double *starts, double sign, int max_iter, double tol, double *x, double *f,
                         int32_t *iterations, int32_t *status);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Constrained optimisation over a system of models (csrc/fokl_optimize_system_device.inc; optimize.py)       */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/*
+ * n_draws x n_starts constrained local solves over a SYSTEM of 'Bernoulli Polynomials' models at once, one lane per
+ * solve, in the COMMON normalised coordinates z [n_vars] of optimize.optimize_system (which assembles all of this):
+ *     minimise  sign * objective(z)   over  lo <= z <= hi   subject to the constraints below,
+ * by a bound-constrained augmented Lagrangian whose inner iteration is fokl_model_optimize's projected Newton step.
+ * Model k reads shift + slope * z[var_of] at each of its inputs.  Host memory, row-major, the models' pieces one after
+ * the other:
+ *   n_inputs, n_terms [n_models]
+ *   mtx      model k's [n_terms[k], n_inputs[k]] orders (0 = the input is not in the term)
+ *   var_of, shift, slope   per model and input: the variable it reads (each at most once per model) and the map
+ *   betas    [n_draws, sum_k (n_terms[k] + 1)]   a draw's row: every model's coefficients side by side, constant first
+ *   table    [n_basis, width]   as for fokl_model_optimize
+ *   lo, hi   [n_vars] the box, lo[v] == hi[v] fixes a variable;  starts [n_starts, n_vars], clipped to the box
+ *   objective: model obj_model's output (obj_var = -1), or obj_offset + obj_span * z[obj_var] (obj_model = -1)
+ *   sign     +1 minimises, -1 maximises
+ *   constraints, ordered by model, per model at most one range and then at most one tie:
+ *     con_model [n_con]   the model whose output r the constraint reads
+ *     con_var   [n_con]   -1: a range;  v >= 0: a tie, r = output - (offset + span * z[v]), an equality at 0
+ *     con_par   [n_con, 5]   lo, hi, scale, offset, span: lo <= r <= hi with -inf / +inf for a missing side, lo == hi an
+ *                            equality; residuals are divided by scale (> 0) before ctol applies
+ *   tol      bound on the projected gradient of the merit function;  ctol  bound on the scaled residuals (for an
+ *            inequality that holds: on the distance of its multiplier from complementarity)
+ * Outputs: x [n_draws, n_starts, n_vars] end points, f [.., ..] the OBJECTIVE there, violation [.., ..] the largest
+ * scaled residual, y [.., .., n_models] every model's value, multipliers [.., .., n_con] d merit / d r of every
+ * constraint (first-order estimates: >= 0 upper side, <= 0 lower side, 0 inactive), iterations and status: 0 converged,
+ * 1 iteration limit, 2 non-finite, 3 stalled, 4 infeasible (ended with violation > ctol).  An iteration is a Newton step
+ * or a multiplier / penalty update; max_iter counts both.  The statement the kernel is tested against is
+ * optimize.solve_system_host.
+ * Limits (FOKL_ERR_ARG with a text, nothing is launched): n_vars <= 16; n_models <= 8; 3 x (most distinct (input,
+ * order) factors of one model) + n_vars (n_vars + 1) / 2 + 3 n_vars + 2 n_models + 2 n_con <= 288 (a solve's values
+ * live in LDS, 64 solves wide, within 144 KB); orders within the table; lo <= hi, finite; variable and model indices in
+ * range; n_draws * n_starts <= 1 048 576; sign +-1; max_iter, tol, ctol >= 0.
+ * Needs a context, no dataset: everything it uses is uploaded by the call and freed before it returns; the context's
+ * dataset, slots and pending launches are left alone.  The solves are sliced over launches of at most
+ * 4 194 304 / max_iter solves (whole wavefronts, at least one), so that no launch is asked for more solve-iterations
+ * than that.  Kernel time: FOKL_K_OPTIMIZE_SYSTEM (one entry per launch).  Blocking.
+ */
+int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, const int32_t *n_inputs, const int32_t *n_terms,
+                         const int32_t *mtx, const int32_t *var_of, const double *shift, const double *slope, int n_draws,
+                         const double *betas, const double *table, int n_basis, int width, const double *lo,
+                         const double *hi, int n_starts, const double *starts, int obj_model, int obj_var,
+                         double obj_offset, double obj_span, double sign, int n_con, const int32_t *con_model,
+                         const int32_t *con_var, const double *con_par, int max_iter, double tol, double ctol, double *x,
+                         double *f, double *violation, double *y, double *multipliers, int32_t *iterations,
+                         int32_t *status);
 
 #ifdef __cplusplus
 }
