@@ -120,6 +120,32 @@ static int fail(fokl_ctx *ctx, int code, const std::string &msg)
             return fail(ctx, FOKL_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));                \
     } while (0)
 
+// device allocations of one call, released on every way out
+struct DeviceBuffers {
+    std::vector<void *> owned;
+    ~DeviceBuffers()
+    {
+        for (void *p : owned) (void)hipFree(p);
+    }
+    template <typename T>
+    hipError_t get(T **out, size_t count)
+    {
+        void *p = nullptr;
+        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) owned.push_back(p);
+        *out = static_cast<T *>(p);
+        return e;
+    }
+    // get, filled with `count` elements from the host (none: nothing is copied)
+    template <typename T>
+    hipError_t upload(T **out, const void *host, size_t count)
+    {
+        hipError_t e = get(out, count);
+        if (e == hipSuccess && count) e = hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice);
+        return e;
+    }
+};
+
 // ---------------------------------------------------------------------------------------------------------
 // timing helpers: HIP events on the context's own stream
 // ---------------------------------------------------------------------------------------------------------
@@ -1837,6 +1863,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_integrate_device.inc"
 #include "fokl_probe.inc"
 #include "fokl_dgemm_device.inc"
+#include "fokl_optimize_core.inc"
 #include "fokl_optimize_device.inc"
 #include "fokl_optimize_system_device.inc"
 

@@ -45,7 +45,8 @@ extern "C" int fokl_gp_integrate_ensemble(fokl_ctx *, int, int, int, int64_t, co
     return FOKL_ERR_HIP;
 }
 
-// The multistart optimiser runs on the device only (fokl_optimize_device.inc); its statement is optimize.solve_host.
+// The multistart optimiser runs on the device only (fokl_optimize_device.inc on fokl_optimize_core.inc); its statement is
+// optimize.solve_host.
 extern "C" int fokl_model_optimize(fokl_ctx *, int, int, const int32_t *, int, const double *, const double *, int, int,
                                    const double *, const double *, int, const double *, double, int, double, double *,
                                    double *, int32_t *, int32_t *)

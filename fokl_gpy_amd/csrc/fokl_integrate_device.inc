@@ -242,24 +242,6 @@ __global__ __launch_bounds__(256) void ensemble_transpose_kernel(const double *_
 
 namespace {
 
-// device allocations of one call, released on every way out
-struct GiBuffers {
-    std::vector<void *> owned;
-    ~GiBuffers()
-    {
-        for (void *p : owned) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t get(T **out, size_t count)
-    {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) owned.push_back(p);
-        *out = static_cast<T *>(p);
-        return e;
-    }
-};
-
 template <int NS>
 void gi_launch(fokl_ctx *ctx, int grid, size_t lds_bytes, const GiSystem &sys, const int *fac_src, const int *fac_ord,
                const int4 *entries, const double *table, const double *coef, const double *forcing, double *state,
@@ -415,33 +397,22 @@ extern "C" int fokl_gp_integrate_ensemble(fokl_ctx *ctx, int n_members, int n_st
     const int chunk_cap = (int)std::min<int64_t>(per_launch + 1, n_points);
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    GiBuffers buf;
+    DeviceBuffers buf;
     int *d_src = nullptr, *d_ord = nullptr;
     int4 *d_entries = nullptr;
     double *d_table = nullptr, *d_coef = nullptr, *d_forcing = nullptr, *d_state = nullptr, *d_points = nullptr,
            *d_mean = nullptr, *d_bounds = nullptr, *d_members = nullptr;
-    HIP_TRY(ctx, buf.get(&d_src, fac_src.size()));
-    HIP_TRY(ctx, buf.get(&d_ord, fac_ord.size()));
-    HIP_TRY(ctx, buf.get(&d_entries, entries.size() / 4));
-    HIP_TRY(ctx, buf.get(&d_table, table.size()));
-    HIP_TRY(ctx, buf.get(&d_coef, coef.size()));
-    HIP_TRY(ctx, buf.get(&d_forcing, (size_t)n_steps * n_other));
-    HIP_TRY(ctx, buf.get(&d_state, state.size()));
+    HIP_TRY(ctx, buf.upload(&d_src, fac_src.data(), fac_src.size()));
+    HIP_TRY(ctx, buf.upload(&d_ord, fac_ord.data(), fac_ord.size()));
+    HIP_TRY(ctx, buf.upload(&d_entries, entries.data(), entries.size() / 4));
+    HIP_TRY(ctx, buf.upload(&d_table, table.data(), table.size()));
+    HIP_TRY(ctx, buf.upload(&d_coef, coef.data(), coef.size()));
+    HIP_TRY(ctx, buf.upload(&d_forcing, forcing, (size_t)n_steps * n_other));
+    HIP_TRY(ctx, buf.upload(&d_state, state.data(), state.size()));
     HIP_TRY(ctx, buf.get(&d_points, (size_t)n_states * chunk_cap * ld));
     HIP_TRY(ctx, buf.get(&d_mean, (size_t)n_states * n_points));
     if (bounds) HIP_TRY(ctx, buf.get(&d_bounds, (size_t)n_states * n_points * 2));
     if (members) HIP_TRY(ctx, buf.get(&d_members, E * n_states * chunk_cap));
-    if (!fac_src.empty()) {
-        HIP_TRY(ctx, hipMemcpy(d_src, fac_src.data(), fac_src.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_ord, fac_ord.data(), fac_ord.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (!entries.empty())
-        HIP_TRY(ctx, hipMemcpy(d_entries, entries.data(), entries.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_coef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (n_other > 0 && n_steps > 0)
-        HIP_TRY(ctx, hipMemcpy(d_forcing, forcing, (size_t)n_steps * n_other * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_state, state.data(), state.size() * sizeof(double), hipMemcpyHostToDevice));
 
     hipError_t lds_ok = hipSuccess;
     switch (n_states) {

@@ -1,13 +1,15 @@
 // Constrained optimisation over a SYSTEM of Bernoulli-polynomial models, per posterior draw (textually included by
-// fokl_hip.hip behind fokl_optimize_device.inc): one bound-constrained augmented-Lagrangian solve per (draw, start), all
-// solves at once.  The algorithm is stated in numpy by fokl_gpy_amd/optimize.py (solve_system_host; the module docstring
-// lists the steps); this file is that statement, one lane per solve.  Compiled under the tree's -ffp-contract=off.
+// fokl_hip.hip behind fokl_optimize_core.inc and fokl_optimize_device.inc): one bound-constrained augmented-Lagrangian
+// solve per (draw, start), all solves at once.  The algorithm is stated in numpy by fokl_gpy_amd/optimize.py
+// (solve_system_host; the module docstring lists the steps); this file is that statement, one lane per solve.  Compiled
+// under the tree's -ffp-contract=off.
 //
 // system_optimize_kernel: 64 solves per wavefront, one wavefront per workgroup, solve n = draw n / S, start n % S, as
-// in model_optimize_kernel, whose Newton step (op_newton) it shares and whose arc search it repeats.  What the problem
-// is -- every model's term entries, its factors' (variable, order, shift, slope), the polynomial coefficients, the box,
-// the constraint list -- is wave-uniform: scalar loads.  A draw's coefficients (the models' rows side by side) are
-// scalar loads when S is a multiple of 64 (UNIFORM), per-lane loads otherwise.  A solve's own values sit in LDS as
+// in model_optimize_kernel.  The evaluation of a model and the Newton step are fokl_optimize_core.inc's; what is here is
+// the merit function around them and the multiplier / penalty updates.  What the problem is -- every model's term
+// entries, its factors' (variable, order, shift, slope), the polynomial coefficients, the box, the constraint list -- is
+// wave-uniform: scalar loads.  A draw's coefficients (the models' rows side by side) are scalar loads when S is a
+// multiple of 64 (UNIFORM), per-lane loads otherwise.  A solve's own values sit in LDS as
 // [item][lane], touched by their own lane only (no barriers):
 //     3 F            phi, phi', phi'' of the distinct (input, order) factors of ONE model: the models are evaluated one
 //                    after the other through the same rows, F = the largest model's count
@@ -52,112 +54,6 @@ struct SysCon {
 
 // max(a, b) that keeps a NaN in either (numpy.maximum)
 __device__ __forceinline__ double sys_max(double a, double b) { return a != a ? a : !(b <= a) ? b : a; }
-
-// the iterate, or the trial point P(x + alpha d), of variable v
-template <bool TRIAL>
-__device__ __forceinline__ double sys_point(const SysProblem &p, const double *box, const double *xs, const double *dv,
-                                            double alpha, int v)
-{
-    const double x = xs[v * OP_LANES];
-    return TRIAL ? fmin(fmax(x + alpha * dv[v * OP_LANES], box[v]), box[p.n + v]) : x;
-}
-
-// phi (with LEVEL 2 also phi', phi'' in the common coordinate) of one model's factors: the model reads a + b z
-template <int LEVEL, bool TRIAL>
-__device__ __forceinline__ void sys_factors(const SysProblem &p, const SysData &s, int slot0, int n_slots, const double *xs,
-                                            const double *dv, double alpha, double *fac)
-{
-    for (int i = 0; i < n_slots; ++i) {
-        const int v = s.slot_var[slot0 + i], order = s.slot_ord[slot0 + i];
-        const double a = s.slot_map[2 * (slot0 + i)], b = s.slot_map[2 * (slot0 + i) + 1];
-        const double *c = s.table + (size_t)(order - 1) * p.width;
-        const double x = a + b * sys_point<TRIAL>(p, s.box, xs, dv, alpha, v);
-        double value = c[order], slope = 0.0, bend = 0.0;
-        for (int k = order - 1; k >= 0; --k) {
-            if (LEVEL == 2) {
-                bend = bend * x + slope;
-                slope = slope * x + value;
-            }
-            value = value * x + c[k];
-        }
-        fac[(3 * i) * OP_LANES] = value;
-        if (LEVEL == 2) {
-            fac[(3 * i + 1) * OP_LANES] = slope * b;
-            fac[(3 * i + 2) * OP_LANES] = 2.0 * bend * (b * b);
-        }
-    }
-}
-
-// One model from its factor values: value e and sum of |terms|; with LEVEL 2 also its PLAIN gradient added into gm [n][64]
-// and `weight` x its Hessian added into H.  The entries are model_optimize_kernel's (slots in ascending variable order).
-template <int LEVEL>
-__device__ __forceinline__ void sys_terms(int n_entries, const int *__restrict__ slot_var, const int4 *__restrict__ entries,
-                                          const int *__restrict__ long_slots, const double *__restrict__ coef,
-                                          double weight, const double *fac, double *gm, double *H, double &e, double &noise)
-{
-    e = coef[0];
-    noise = fabs(e);
-#pragma unroll 2
-    for (int t = 0; t < n_entries; ++t) {
-        const int4 d = entries[t];
-        const double w = coef[d.w], wh = weight * w;
-        if (d.x >= 0) {
-            const double a0 = fac[(3 * d.x) * OP_LANES];
-            const double a1 = d.y >= 0 ? fac[(3 * d.y) * OP_LANES] : 1.0;
-            const double a2 = d.z >= 0 ? fac[(3 * d.z) * OP_LANES] : 1.0;
-            const double term = w * (a0 * a1 * a2);
-            e += term;
-            noise += fabs(term);
-            if (LEVEL == 2) {
-                const int j0 = slot_var[d.x], h0 = j0 * (j0 + 1) / 2;
-                const double b0 = fac[(3 * d.x + 1) * OP_LANES], c0 = fac[(3 * d.x + 2) * OP_LANES];
-                gm[j0 * OP_LANES] += w * (a1 * a2) * b0;
-                H[(h0 + j0) * OP_LANES] += wh * (a1 * a2) * c0;
-                if (d.y >= 0) {
-                    const int j1 = slot_var[d.y], h1 = j1 * (j1 + 1) / 2;
-                    const double b1 = fac[(3 * d.y + 1) * OP_LANES], c1 = fac[(3 * d.y + 2) * OP_LANES];
-                    gm[j1 * OP_LANES] += w * (a0 * a2) * b1;
-                    H[(h1 + j1) * OP_LANES] += wh * (a0 * a2) * c1;
-                    H[(h1 + j0) * OP_LANES] += wh * a2 * b1 * b0;
-                    if (d.z >= 0) {
-                        const int j2 = slot_var[d.z], h2 = j2 * (j2 + 1) / 2;
-                        const double b2 = fac[(3 * d.z + 1) * OP_LANES], c2 = fac[(3 * d.z + 2) * OP_LANES];
-                        gm[j2 * OP_LANES] += w * (a0 * a1) * b2;
-                        H[(h2 + j2) * OP_LANES] += wh * (a0 * a1) * c2;
-                        H[(h2 + j0) * OP_LANES] += wh * a1 * b2 * b0;
-                        H[(h2 + j1) * OP_LANES] += wh * a0 * b2 * b1;
-                    }
-                }
-            }
-        } else {
-            const int k = -1 - d.x;
-            const int *list = long_slots + d.y;
-            double product = 1.0;
-            for (int i = 0; i < k; ++i) product *= fac[(3 * list[i]) * OP_LANES];
-            const double term = w * product;
-            e += term;
-            noise += fabs(term);
-            if (LEVEL == 2) {
-                for (int a = 0; a < k; ++a) {
-                    const int sa = list[a], ja = slot_var[sa], ha = ja * (ja + 1) / 2;
-                    double rest = 1.0;
-                    for (int i = 0; i < k; ++i)
-                        if (i != a) rest *= fac[(3 * list[i]) * OP_LANES];
-                    const double ba = fac[(3 * sa + 1) * OP_LANES];
-                    gm[ja * OP_LANES] += w * rest * ba;
-                    H[(ha + ja) * OP_LANES] += wh * rest * fac[(3 * sa + 2) * OP_LANES];
-                    for (int b = 0; b < a; ++b) {
-                        const int sb = list[b], jb = slot_var[sb];
-                        double both = 1.0;
-                        for (int i = 0; i < k; ++i)
-                            if (i != a && i != b) both *= fac[(3 * list[i]) * OP_LANES];
-                        H[(ha + jb) * OP_LANES] += wh * both * ba * fac[(3 * sb + 1) * OP_LANES];
-                    }
-                }
-            }
-        }
-    }
-}
 
 // One constraint at residual r (optimize.py: _constraint).  par: lo, hi, scale (lo == hi: an equality, whose multiplier
 // is the upper side's; -inf / +inf: no such side).  Which branch runs is wave-uniform.
@@ -209,9 +105,10 @@ __device__ __forceinline__ void sys_values(const SysProblem &p, const SysData &s
     for (int k = 0; k < p.n_models; ++k) {
         const int *md = s.models + k * SYS_MODEL_WORDS;
         double e, noise;
-        sys_factors<0, TRIAL>(p, s, md[2], md[3], xs, dv, alpha, fac);
-        sys_terms<0>(md[0], s.slot_var + md[2], s.entries + md[1], s.long_slots, coef + md[4], 0.0, fac, nullptr, nullptr, e,
-                     noise);
+        op_factors<0, TRIAL, true>(md[3], s.slot_var + md[2], s.slot_ord + md[2], s.slot_map + 2 * md[2], s.table, p.width,
+                                   p.n, s.box, xs, dv, alpha, fac);
+        op_terms<0>(md[0], s.slot_var + md[2], s.entries + md[1], s.long_slots, coef + md[4], 1.0, 0.0, fac, nullptr, nullptr,
+                    e, noise);
         ev[k * OP_LANES] = e;
         nz[k * OP_LANES] = noise;
     }
@@ -228,7 +125,7 @@ __device__ __forceinline__ SysCon sys_constraint_at(const SysProblem &p, const S
     double r = ev[k * OP_LANES];
     reach = nz[k * OP_LANES];
     if (u >= 0) {
-        const double tied = par[3] + par[4] * sys_point<TRIAL>(p, s.box, xs, dv, alpha, u);
+        const double tied = par[3] + par[4] * op_point<TRIAL>(p.n, s.box, xs, dv, alpha, u);
         r = r - tied;
         reach = reach + fabs(tied);
     }
@@ -246,7 +143,7 @@ __device__ __forceinline__ void sys_merit(const SysProblem &p, const SysData &s,
         L = p.sign * ev[p.obj_model * OP_LANES];
         size = nz[p.obj_model * OP_LANES];
     } else {
-        const double value = p.obj_offset + p.obj_span * sys_point<TRIAL>(p, s.box, xs, dv, alpha, p.obj_var);
+        const double value = p.obj_offset + p.obj_span * op_point<TRIAL>(p.n, s.box, xs, dv, alpha, p.obj_var);
         L = p.sign * value;
         size = fabs(value);
     }
@@ -288,8 +185,9 @@ __device__ __forceinline__ void sys_derivatives(const SysProblem &p, const SysDa
         }
         for (int j = 0; j < n; ++j) gm[j * OP_LANES] = 0.0;
         double e, noise;
-        sys_factors<2, false>(p, s, md[2], md[3], xs, gm, 0.0, fac);
-        sys_terms<2>(md[0], s.slot_var + md[2], s.entries + md[1], s.long_slots, coef + md[4], weight, fac, gm, H, e, noise);
+        op_factors<2, false, true>(md[3], s.slot_var + md[2], s.slot_ord + md[2], s.slot_map + 2 * md[2], s.table, p.width, n,
+                                   s.box, xs, gm, 0.0, fac);
+        op_terms<2>(md[0], s.slot_var + md[2], s.entries + md[1], s.long_slots, coef + md[4], 1.0, weight, fac, gm, H, e, noise);
         for (int j = 0; j < n; ++j) g[j * OP_LANES] += weight * gm[j * OP_LANES];
         if (md[6] > md[5] && (tie < 0 || md[6] - md[5] > 1))          // the rank-one terms of the range constraints
             for (int i = 0; i < n; ++i)
@@ -349,15 +247,10 @@ __global__ __launch_bounds__(OP_LANES) void system_optimize_kernel(SysProblem p,
         sys_values<false>(p, s, coef, xs, dv, 0.0, fac, ev, nz);
         sys_merit<false>(p, s, xs, dv, 0.0, ev, nz, lam, rho, F, noise, viol, measure);
         sys_derivatives(p, s, coef, xs, ev, nz, lam, rho, fac, g, H, dv);
-        double pg = 0.0;
-        unsigned active = fixed;
-        bool finite = fabs(F) <= DBL_MAX;
-        for (int j = 0; j < n; ++j) {
-            const double x = xs[j * OP_LANES], gj = g[j * OP_LANES], lo = box[j], hi = box[n + j];
-            finite = finite && fabs(gj) <= DBL_MAX;
-            pg = fmax(pg, fabs(fmin(fmax(x - gj, lo), hi) - x));
-            if ((x <= lo && gj > 0.0) || (x >= hi && gj < 0.0)) active |= 1u << j;
-        }
+        double pg;
+        unsigned active;
+        bool finite;
+        op_survey(n, box, xs, g, F, fixed, finite, pg, active);
         const bool settled = pg <= p.tol && measure <= p.ctol;
         if (status < 0 && (!finite || settled || it == p.max_iter)) {
             status = !finite ? OP_NON_FINITE : settled ? OP_CONVERGED : OP_ITERATION_LIMIT;
@@ -386,51 +279,16 @@ __global__ __launch_bounds__(OP_LANES) void system_optimize_kernel(SysProblem p,
             target = fmax(p.ctol, SYS_FEASIBLE_SHRINK * target);
         }
         if (update && !good) rho = fmin(SYS_RHO_GROWTH * rho, SYS_RHO_MAX);
-        const bool stepping = status < 0 && !update;
-        op_newton(n, active, H, g, dv);
-        double reach = 0.0;
-        bool use_steepest = steepest;
-        for (int j = 0; j < n; ++j) {
-            const double dj = fabs(dv[j * OP_LANES]);
-            use_steepest = use_steepest || !(dj <= DBL_MAX);
-            reach = fmax(reach, dj);
-        }
-        if (use_steepest) {
-            reach = 0.0;
-            for (int j = 0; j < n; ++j) {
-                const double dj = ((active >> j) & 1u) ? 0.0 : -g[j * OP_LANES];
-                dv[j * OP_LANES] = dj;
-                reach = fmax(reach, fabs(dj));
-            }
-        }
-        if (reach > 1.0)
-            for (int j = 0; j < n; ++j) dv[j * OP_LANES] = dv[j * OP_LANES] / reach;
-        double alpha = 1.0;
-        bool searching = stepping;
-        for (int h = 0; h <= OP_MAX_HALVINGS && __any(searching); ++h) {
+        const bool stalled = op_step(n, box, active, status < 0 && !update, F, noise, H, g, dv, xs, steepest, [&](double alpha) {
             double Ft, noise_t, viol_t, measure_t;
             sys_values<true>(p, s, coef, xs, dv, alpha, fac, ev, nz);
             sys_merit<true>(p, s, xs, dv, alpha, ev, nz, lam, rho, Ft, noise_t, viol_t, measure_t);
-            double slope = 0.0, moved = 0.0;
-            for (int j = 0; j < n; ++j) {
-                const double x = xs[j * OP_LANES];
-                const double step = fmin(fmax(x + alpha * dv[j * OP_LANES], box[j]), box[n + j]) - x;
-                slope = slope + g[j * OP_LANES] * step;
-                moved = fmax(moved, fabs(step));
-            }
-            const bool ok = Ft <= F + OP_ARMIJO * fmin(slope, 0.0) + OP_NOISE * noise && moved > 0.0;
-            if (searching && !ok) alpha = alpha * 0.5;
-            searching = searching && !ok;
-        }
-        const bool failed = searching;                                 // no trial point passed
-        if (stepping && !failed)
-            for (int j = 0; j < n; ++j)
-                xs[j * OP_LANES] = fmin(fmax(xs[j * OP_LANES] + alpha * dv[j * OP_LANES], box[j]), box[n + j]);
-        if (failed && use_steepest) {
+            return Ft;
+        });
+        if (stalled) {
             status = OP_STALLED;
             iterations = it;
         }
-        steepest = failed && !use_steepest;
     }
     // the results at the end point: objective, violation, every model's value, first-order multipliers
     double F, noise, viol, measure;
@@ -480,23 +338,17 @@ extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, con
                                            std::to_string(SYS_MAX_MODELS));
     if (n_con > SYS_MAX_CONSTRAINTS)
         return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_con) + " constraints, at most a range and a tie per model");
-    if (!(sign == 1.0 || sign == -1.0) || max_iter < 0 || !(tol >= 0.0) || !(ctol >= 0.0))
-        return fail(ctx, FOKL_ERR_ARG, who + "sign must be +1 or -1, max_iter, tol and ctol not negative");
     if ((obj_model >= 0) == (obj_var >= 0) || obj_model >= n_models || obj_var >= n_vars ||
         (obj_var >= 0 && !(std::fabs(obj_offset) <= DBL_MAX && std::fabs(obj_span) <= DBL_MAX)))
         return fail(ctx, FOKL_ERR_ARG, who + "the objective is one model's output or one decision variable");
-    for (int j = 0; j < n_vars; ++j)
-        if (!(lo[j] <= hi[j]) || !(std::fabs(lo[j]) <= DBL_MAX) || !(std::fabs(hi[j]) <= DBL_MAX))
-            return fail(ctx, FOKL_ERR_ARG, who + "empty or inverted box at variable " + std::to_string(j));
-    if ((int64_t)n_draws * n_starts > OP_MAX_SOLVES)
-        return fail(ctx, FOKL_ERR_ARG, who + std::to_string((int64_t)n_draws * n_starts) +
-                                           " solves, one call runs at most " +
-                                           std::to_string(OP_MAX_SOLVES));
+    const std::string refusal = op_refusal(sign, max_iter >= 0 && tol >= 0.0 && ctol >= 0.0, "max_iter, tol and ctol", n_vars,
+                                           lo, hi, "variable", n_draws, n_starts);
+    if (!refusal.empty()) return fail(ctx, FOKL_ERR_ARG, who + refusal);
 
-    // ---- the models as the kernel reads them: per model its distinct (input, order) factors with the variable and the
-    //      map they read, and model_optimize_kernel's 16-byte term entries over the model's own slots ----
-    std::vector<int32_t> models((size_t)n_models * SYS_MODEL_WORDS, 0), slot_var, slot_ord, entries, long_slots;
-    std::vector<double> slot_map;
+    // ---- the models as the kernel reads them: per model its distinct (variable, order) factors with the map they read,
+    //      and the 16-byte term entries over the model's own slots ----
+    std::vector<int32_t> models((size_t)n_models * SYS_MODEL_WORDS, 0);
+    OpTables tables;
     int max_slots = 0, n_coef = 0, total_terms = 0;
     size_t in0 = 0, mtx0 = 0;
     for (int k = 0; k < n_models; ++k) {
@@ -514,41 +366,14 @@ extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, con
             if (!(std::fabs(shift[in0 + j]) <= DBL_MAX) || !(std::fabs(slope[in0 + j]) <= DBL_MAX))
                 return fail(ctx, FOKL_ERR_ARG, who + "model " + std::to_string(k) + " has a non-finite input map");
         }
-        std::map<std::pair<int, int>, int> slot_of;                    // (variable, order) -> the model's slot
-        const int slot0 = (int)slot_var.size(), entry0 = (int)entries.size() / 4;
-        for (int t = 0; t < terms; ++t) {
-            std::vector<std::pair<int, int>> row;                      // (variable, slot): ascending variable order
-            for (int j = 0; j < m; ++j) {
-                const int order = mtx[mtx0 + (size_t)t * m + j];
-                if (order < 0 || order > n_basis || order >= width)
-                    return fail(ctx, FOKL_ERR_ARG, who + "basis order outside the coefficient table");
-                if (order == 0) continue;
-                const int v = var_of[in0 + j];
-                const auto found = slot_of.emplace(std::make_pair(v, order), (int)slot_var.size() - slot0);
-                if (found.second) {
-                    slot_var.push_back(v);
-                    slot_ord.push_back(order);
-                    slot_map.push_back(shift[in0 + j]);
-                    slot_map.push_back(slope[in0 + j]);
-                }
-                row.emplace_back(v, found.first->second);
-            }
-            std::sort(row.begin(), row.end());
-            int32_t ent[4] = {-1, -1, -1, t + 1};
-            if (row.empty() || row.size() > 3) {
-                ent[0] = -1 - (int32_t)row.size();
-                ent[1] = (int32_t)long_slots.size();
-                for (const auto &r : row) long_slots.push_back(r.second);
-            } else {
-                for (size_t i = 0; i < row.size(); ++i) ent[i] = row[i].second;
-            }
-            entries.insert(entries.end(), ent, ent + 4);
-        }
+        const int slot0 = (int)tables.slot_var.size(), entry0 = (int)tables.entries.size() / 4;
+        if (!op_pack_model(mtx + mtx0, m, terms, var_of + in0, shift + in0, slope + in0, n_basis, width, tables))
+            return fail(ctx, FOKL_ERR_ARG, who + "basis order outside the coefficient table");
         int32_t *md = models.data() + (size_t)k * SYS_MODEL_WORDS;
         md[0] = terms;
         md[1] = entry0;
         md[2] = slot0;
-        md[3] = (int)slot_var.size() - slot0;
+        md[3] = (int)tables.slot_var.size() - slot0;
         md[4] = n_coef;
         md[5] = md[6] = 0;
         max_slots = std::max(max_slots, md[3]);
@@ -603,26 +428,28 @@ extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, con
                                            std::to_string(OP_LDS_BUDGET / (OP_LANES * sizeof(double))));
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    GiBuffers buf;                                                     // fokl_integrate_device.inc: freed on every way out
+    DeviceBuffers buf;
     const size_t N = (size_t)n_draws * n_starts, n = (size_t)n_vars, K = (size_t)n_models, C = (size_t)n_con;
+    std::vector<double> box(lo, lo + n);
+    box.insert(box.end(), hi, hi + n);
     int *d_models = nullptr, *d_var = nullptr, *d_ord = nullptr, *d_long = nullptr, *d_cm = nullptr, *d_cv = nullptr;
     int *d_it = nullptr, *d_st = nullptr;
     int4 *d_entries = nullptr;
     double *d_map = nullptr, *d_table = nullptr, *d_box = nullptr, *d_par = nullptr, *d_starts = nullptr, *d_betas = nullptr;
     double *d_x = nullptr, *d_f = nullptr, *d_viol = nullptr, *d_y = nullptr, *d_mu = nullptr;
-    HIP_TRY(ctx, buf.get(&d_models, models.size()));
-    HIP_TRY(ctx, buf.get(&d_var, slot_var.size()));
-    HIP_TRY(ctx, buf.get(&d_ord, slot_ord.size()));
-    HIP_TRY(ctx, buf.get(&d_map, slot_map.size()));
-    HIP_TRY(ctx, buf.get(&d_long, long_slots.size()));
-    HIP_TRY(ctx, buf.get(&d_entries, entries.size() / 4));
-    HIP_TRY(ctx, buf.get(&d_table, (size_t)n_basis * width));
-    HIP_TRY(ctx, buf.get(&d_box, 2 * n));
-    HIP_TRY(ctx, buf.get(&d_cm, C));
-    HIP_TRY(ctx, buf.get(&d_cv, C));
-    HIP_TRY(ctx, buf.get(&d_par, C * SYS_CON_WORDS));
-    HIP_TRY(ctx, buf.get(&d_starts, (size_t)n_starts * n));
-    HIP_TRY(ctx, buf.get(&d_betas, (size_t)n_draws * n_coef));
+    HIP_TRY(ctx, buf.upload(&d_models, models.data(), models.size()));
+    HIP_TRY(ctx, buf.upload(&d_var, tables.slot_var.data(), tables.slot_var.size()));
+    HIP_TRY(ctx, buf.upload(&d_ord, tables.slot_ord.data(), tables.slot_ord.size()));
+    HIP_TRY(ctx, buf.upload(&d_map, tables.slot_map.data(), tables.slot_map.size()));
+    HIP_TRY(ctx, buf.upload(&d_long, tables.long_slots.data(), tables.long_slots.size()));
+    HIP_TRY(ctx, buf.upload(&d_entries, tables.entries.data(), tables.entries.size() / 4));
+    HIP_TRY(ctx, buf.upload(&d_table, table, (size_t)n_basis * width));
+    HIP_TRY(ctx, buf.upload(&d_box, box.data(), box.size()));
+    HIP_TRY(ctx, buf.upload(&d_cm, con_model, C));
+    HIP_TRY(ctx, buf.upload(&d_cv, con_var, C));
+    HIP_TRY(ctx, buf.upload(&d_par, con_par, C * SYS_CON_WORDS));
+    HIP_TRY(ctx, buf.upload(&d_starts, starts, (size_t)n_starts * n));
+    HIP_TRY(ctx, buf.upload(&d_betas, betas, (size_t)n_draws * n_coef));
     HIP_TRY(ctx, buf.get(&d_x, N * n));
     HIP_TRY(ctx, buf.get(&d_f, N));
     HIP_TRY(ctx, buf.get(&d_viol, N));
@@ -630,23 +457,6 @@ extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, con
     HIP_TRY(ctx, buf.get(&d_mu, N * C));
     HIP_TRY(ctx, buf.get(&d_it, N));
     HIP_TRY(ctx, buf.get(&d_st, N));
-    auto up = [&](void *dst, const void *src, size_t bytes) {
-        return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
-    };
-    HIP_TRY(ctx, up(d_models, models.data(), models.size() * sizeof(int)));
-    HIP_TRY(ctx, up(d_var, slot_var.data(), slot_var.size() * sizeof(int)));
-    HIP_TRY(ctx, up(d_ord, slot_ord.data(), slot_ord.size() * sizeof(int)));
-    HIP_TRY(ctx, up(d_map, slot_map.data(), slot_map.size() * sizeof(double)));
-    HIP_TRY(ctx, up(d_long, long_slots.data(), long_slots.size() * sizeof(int)));
-    HIP_TRY(ctx, up(d_entries, entries.data(), entries.size() * sizeof(int)));
-    HIP_TRY(ctx, up(d_table, table, (size_t)n_basis * width * sizeof(double)));
-    HIP_TRY(ctx, up(d_box, lo, n * sizeof(double)));
-    HIP_TRY(ctx, up(d_box + n, hi, n * sizeof(double)));
-    HIP_TRY(ctx, up(d_cm, con_model, C * sizeof(int)));
-    HIP_TRY(ctx, up(d_cv, con_var, C * sizeof(int)));
-    HIP_TRY(ctx, up(d_par, con_par, C * SYS_CON_WORDS * sizeof(double)));
-    HIP_TRY(ctx, up(d_starts, starts, (size_t)n_starts * n * sizeof(double)));
-    HIP_TRY(ctx, up(d_betas, betas, (size_t)n_draws * n_coef * sizeof(double)));
     SysData s{};
     s.models = d_models;
     s.slot_var = d_var;
@@ -660,11 +470,8 @@ extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, con
     s.box = d_box;
     s.con_par = d_par;
 
-    const bool uniform = n_starts % OP_LANES == 0;                     // a wavefront belongs to one draw
-    const void *kernel = uniform ? reinterpret_cast<const void *>(system_optimize_kernel<true>)
-                                 : reinterpret_cast<const void *>(system_optimize_kernel<false>);
-    if (lds_bytes > 64 * 1024)
-        HIP_TRY(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OP_LDS_BUDGET));
+    decltype(&system_optimize_kernel<true>) kernel = nullptr;
+    HIP_TRY(ctx, op_pick(system_optimize_kernel<true>, system_optimize_kernel<false>, n_starts, lds_bytes, &kernel));
     // a launch is asked for at most SYS_ITERATION_CAP solve-iterations (solves x max_iter), in whole wavefronts
     const int64_t per_launch = std::max<int64_t>(OP_LANES, SYS_ITERATION_CAP / std::max(1, max_iter) / OP_LANES * OP_LANES);
     for (int64_t first = 0; first < (int64_t)N; first += per_launch) {
@@ -675,12 +482,8 @@ extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, con
         // per iterate and solve roughly: 50 flops and 9 + 18 LDS accesses per term over the value and derivative passes
         TimedRegion timed(ctx, FOKL_K_OPTIMIZE_SYSTEM, 8.0 * count * (n + K + C + 4.0) + 8.0 * (double)n_draws * n_coef,
                           count * 50.0 * std::max(1, total_terms));
-        if (uniform)
-            hipLaunchKernelGGL(system_optimize_kernel<true>, dim3(grid), dim3(OP_LANES), lds_bytes, ctx->stream, p, s,
-                               d_starts, d_betas, d_x, d_f, d_viol, d_y, d_mu, d_it, d_st);
-        else
-            hipLaunchKernelGGL(system_optimize_kernel<false>, dim3(grid), dim3(OP_LANES), lds_bytes, ctx->stream, p, s,
-                               d_starts, d_betas, d_x, d_f, d_viol, d_y, d_mu, d_it, d_st);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(OP_LANES), lds_bytes, ctx->stream, p, s, d_starts, d_betas, d_x, d_f,
+                           d_viol, d_y, d_mu, d_it, d_st);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

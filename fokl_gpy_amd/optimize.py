@@ -27,7 +27,8 @@ smooth on the box the search is confined to, so every solve is a projected Newto
 
 ``optimize`` runs the solves on the device (``fokl_model_optimize``: one lane per solve; without the library or a gfx950
 device it raises, there is no host fallback).  ``optimize_host`` is the same algorithm in numpy with no device: the
-STATEMENT the kernel is tested against.  It carries a batch of solves through every numpy operation (each solve sees
+STATEMENT the kernel is tested against.  Step 1 is ``_model_parts`` and steps 3-5 are ``_newton_step``, for this solver
+and for the system solver below alike -- as both kernels have them from ``csrc/fokl_optimize_core.inc``.  It carries a batch of solves through every numpy operation (each solve sees
 exactly the element-wise arithmetic it would see alone) because a Python loop over 32 000 solves is of no use to a test.
 The device and the host may differ in the last bits of a sum (the order of the terms differs), which can flip a
 line-search test: compare results, not iterates.
@@ -206,18 +207,29 @@ def _prepare(betas, mtx, phis, minmax, kernel, sense, objective, bounds, starts,
                 tol=float(tol), low=low, span=span, box=box, objective=objective)
 
 
+def _true_scale(xn, offset, span, lo, hi, box):
+    """Normalised points xn [..., n] in true scale; a point on a face of the box [n, 2] is ON it."""
+    out = offset + xn * span
+    out = np.where(xn == lo, box[:, 0], out)
+    return np.where(xn == hi, box[:, 1], out)
+
+
+def _over_draws(x, f):
+    """The mean and the order statistics over the draws' optima x [E, n], f [E]."""
+    E = f.shape[0]
+    cut = bounds_cut(E)
+    xs, fs = np.sort(x, axis=0), np.sort(f)
+    return dict(x_mean=x.mean(axis=0), f_mean=float(f.mean()), x_bounds=np.stack([xs[cut], xs[E - cut]], axis=1),
+                f_bounds=np.array([fs[cut], fs[E - cut]]))
+
+
 def _assemble(p, x_all, f_all, it_all, st_all, ReturnBounds, ReturnAll):
     """The best start of every draw, true-scale coordinates and, over the draws, the mean and the order statistics."""
     E, S = f_all.shape
     key = np.where(np.isfinite(f_all) & (st_all != NON_FINITE), p['sign'] * f_all, np.inf)
     best = np.argmin(key, axis=1)
     rows = np.arange(E)
-
-    def true_scale(xn):
-        out = p['low'] + xn * p['span']
-        out = np.where(xn == p['lo'], p['box'][:, 0], out)            # a point on a face of the box is ON it
-        return np.where(xn == p['hi'], p['box'][:, 1], out)
-
+    true_scale = lambda xn: _true_scale(xn, p['low'], p['span'], p['lo'], p['hi'], p['box'])
     x, f, status = true_scale(x_all[rows, best]), f_all[rows, best], st_all[rows, best]
     res = OptimizeResult()
     if p['objective'] == 'mean':
@@ -225,10 +237,7 @@ def _assemble(p, x_all, f_all, it_all, st_all, ReturnBounds, ReturnAll):
     else:
         res.update(x=x, f=f, status=status)
         if ReturnBounds and E >= 2:
-            cut = bounds_cut(E)
-            xs, fs = np.sort(x, axis=0), np.sort(f)
-            res.update(x_mean=x.mean(axis=0), f_mean=float(f.mean()),
-                       x_bounds=np.stack([xs[cut], xs[E - cut]], axis=1), f_bounds=np.array([fs[cut], fs[E - cut]]))
+            res.update(_over_draws(x, f))
     if ReturnAll:
         res.update(x_all=true_scale(x_all), f_all=f_all, iterations_all=it_all, status_all=st_all, best_start=best)
     return res
@@ -321,15 +330,19 @@ class TermTable:
                     self.to_hess[a, b, self.n_hess if ja == m else ja * (ja + 1) // 2 + jb, t] = 1.0
 
 
-def _evaluate(tt, table, x, coef, sign, level):
-    """F = sign * model at x [B, m] with coefficients coef [B, terms + 1]: (F [B], sum |term| [B]) and with level 2 also
-    the gradient [m, B] and the Hessian's lower triangle [m (m + 1) / 2, B] (entry i (i + 1) / 2 + j, j <= i)."""
-    B = x.shape[0]
+def _model_parts(tt, table, z, coef, level, scale=1.0, weight=None, maps=None):
+    """Step 1 for one model at z [B, n] with coefficients coef [B, terms + 1]: e = scale x its value [B] and sum |term|
+    [B]; with level 2 also scale x its gradient [n, B] and ``weight`` (a number, or [B]) x its Hessian's lower triangle
+    [n (n + 1) / 2, B] (entry i (i + 1) / 2 + j, j <= i).  scale is +-1: the plain value and gradient or their exact
+    negatives.  With maps = (a, b) [n] each the model reads a + b z and the derivatives are with respect to z; without,
+    it reads z itself (no 0 + 1 * z)."""
+    B = z.shape[0]
     fac = np.empty((tt.n_slots + 1, 3, B))
     fac[tt.n_slots] = np.array([1.0, 0.0, 0.0])[:, None]
     for s in range(tt.n_slots):
         c = table[tt.order[s] - 1]
-        xs = x[:, tt.src[s]]
+        v = tt.src[s]
+        xs = z[:, v] if maps is None else maps[0][v] + maps[1][v] * z[:, v]
         value = np.full(B, c[tt.order[s]])
         slope = np.zeros(B)
         bend = np.zeros(B)
@@ -337,18 +350,22 @@ def _evaluate(tt, table, x, coef, sign, level):
             bend = bend * xs + slope
             slope = slope * xs + value
             value = value * xs + c[k]
-        fac[s, 0], fac[s, 1], fac[s, 2] = value, slope, 2.0 * bend
-    w = sign * coef[:, 1:].T                                         # [terms, B]
+        if maps is None:
+            fac[s, 0], fac[s, 1], fac[s, 2] = value, slope, 2.0 * bend
+        else:
+            fac[s, 0], fac[s, 1], fac[s, 2] = value, slope * maps[1][v], 2.0 * bend * (maps[1][v] * maps[1][v])
+    w = scale * coef[:, 1:].T                                        # [terms, B]
     A = fac[tt.slots, 0]                                             # [terms, width, B]
     product = A[:, 0].copy()
     for i in range(1, tt.width):
         product = product * A[:, i]
     each = w * product
-    F = sign * coef[:, 0] + each.sum(axis=0)
-    noise = np.abs(sign * coef[:, 0]) + np.abs(each).sum(axis=0)
+    e = scale * coef[:, 0] + each.sum(axis=0)
+    noise = np.abs(scale * coef[:, 0]) + np.abs(each).sum(axis=0)
     if level == 0:
-        return F, noise
+        return e, noise
     D1, D2 = fac[tt.slots, 1], fac[tt.slots, 2]
+    wh = weight * coef[:, 1:].T
 
     def others(skip):
         out = np.ones((tt.n_terms, B))
@@ -360,13 +377,18 @@ def _evaluate(tt, table, x, coef, sign, level):
     grad = np.zeros((tt.m + 1, B))
     hess = np.zeros((tt.n_hess + 1, B))
     with np.errstate(invalid='ignore', over='ignore'):
-        for a in range(tt.width):
-            rest = w * others((a,))
-            grad += tt.to_grad[a] @ (rest * D1[:, a])
-            hess += tt.to_hess[a, a] @ (rest * D2[:, a])
-            for b in range(a):
-                hess += tt.to_hess[a, b] @ (w * others((a, b)) * D1[:, a] * D1[:, b])
-    return F, noise, grad[:tt.m], hess[:tt.n_hess]
+        for i in range(tt.width):
+            rest = others((i,))
+            grad += tt.to_grad[i] @ (w * rest * D1[:, i])
+            hess += tt.to_hess[i, i] @ (wh * rest * D2[:, i])
+            for j in range(i):
+                hess += tt.to_hess[i, j] @ (wh * others((i, j)) * D1[:, i] * D1[:, j])
+    return e, noise, grad[:tt.m], hess[:tt.n_hess]
+
+
+def _evaluate(tt, table, x, coef, sign, level):
+    """F = sign * model at x [B, m]: (F, sum |term|) and with level 2 also its gradient and Hessian triangle."""
+    return _model_parts(tt, table, x, coef, level, scale=sign, weight=sign)
 
 
 def _direction(H, g, active):
@@ -402,6 +424,41 @@ def _direction(H, g, active):
     return d
 
 
+def _newton_step(x, F, noise, g, H, lo, hi, stepping, steepest, merit_at):
+    """Steps 3-5 for the solves ``stepping`` [B] at the iterates x [B, m], where the merit is F [B] (sum of magnitudes
+    ``noise``) with gradient g [m, B] and Hessian triangle H (factored in place); ``merit_at(points)`` is the merit at
+    trial points [B, m].  x moves in place where a trial point passes.  Returns (failed, use_steepest): no trial point
+    passed; the direction was projected steepest descent (asked for by ``steepest``, or the Newton one was not finite)."""
+    B, m = x.shape
+    xt = x.T                                                         # [m, B]
+    lo_c, hi_c = lo[:, None], hi[:, None]
+    with np.errstate(invalid='ignore', over='ignore'):
+        active = (lo_c == hi_c) | ((xt <= lo_c) & (g > 0)) | ((xt >= hi_c) & (g < 0))
+        d = _direction(H, g, active)
+        reach = np.max(np.abs(d), axis=0)
+        use_steepest = steepest | ~(reach <= np.finfo(np.float64).max)
+        d = np.where(use_steepest, np.where(active, 0.0, -g), d)
+        reach = np.max(np.abs(d), axis=0)
+        d = np.where(reach > 1.0, d / reach, d)
+        alpha = np.ones(B)
+        searching = stepping.copy()
+        for _ in range(MAX_HALVINGS + 1):
+            if not searching.any():
+                break
+            trial = np.minimum(np.maximum(xt + alpha * d, lo_c), hi_c)
+            Ft = merit_at(np.ascontiguousarray(trial.T))
+            step = trial - xt
+            slope = np.zeros(B)
+            for j in range(m):
+                slope = slope + g[j] * step[j]
+            ok = (Ft <= F + ARMIJO * np.minimum(slope, 0.0) + NOISE * noise) & (np.max(np.abs(step), axis=0) > 0)
+            take = searching & ok
+            x[take] = trial.T[take]
+            searching = searching & ~ok
+            alpha = np.where(searching, alpha * 0.5, alpha)
+    return searching, use_steepest
+
+
 def _solve_block(tt, table, coef, lo, hi, x, sign, max_iter, tol):
     B, m = x.shape
     x = x.copy()
@@ -409,7 +466,6 @@ def _solve_block(tt, table, coef, lo, hi, x, sign, max_iter, tol):
     iterations = np.zeros(B, dtype=np.int32)
     f_end = np.full(B, np.nan)
     steepest = np.zeros(B, dtype=bool)
-    fixed = (lo == hi)[:, None]
     lo_c, hi_c = lo[:, None], hi[:, None]
     for it in range(max_iter + 1):
         running = status < 0
@@ -433,31 +489,8 @@ def _solve_block(tt, table, coef, lo, hi, x, sign, max_iter, tol):
         running = status < 0
         if not running.any():
             break
-        with np.errstate(invalid='ignore', over='ignore'):
-            active = fixed | ((xt <= lo_c) & (g > 0)) | ((xt >= hi_c) & (g < 0))
-            d = _direction(H, g, active)
-            reach = np.max(np.abs(d), axis=0)
-            use_steepest = steepest | ~(reach <= np.finfo(np.float64).max)
-            d = np.where(use_steepest, np.where(active, 0.0, -g), d)
-            reach = np.max(np.abs(d), axis=0)
-            d = np.where(reach > 1.0, d / reach, d)
-            alpha = np.ones(B)
-            searching = running.copy()
-            for _ in range(MAX_HALVINGS + 1):
-                if not searching.any():
-                    break
-                trial = np.minimum(np.maximum(xt + alpha * d, lo_c), hi_c)
-                Ft, _ = _evaluate(tt, table, np.ascontiguousarray(trial.T), coef, sign, 0)
-                step = trial - xt
-                slope = np.zeros(B)
-                for j in range(m):
-                    slope = slope + g[j] * step[j]
-                ok = (Ft <= F + ARMIJO * np.minimum(slope, 0.0) + NOISE * noise) & (np.max(np.abs(step), axis=0) > 0)
-                take = searching & ok
-                x[take] = trial.T[take]
-                searching = searching & ~ok
-                alpha = np.where(searching, alpha * 0.5, alpha)
-        failed = searching                                           # no trial point passed
+        failed, use_steepest = _newton_step(x, F, noise, g, H, lo, hi, running, steepest,
+                                            lambda trial: _evaluate(tt, table, trial, coef, sign, 0)[0])
         stop(failed & use_steepest, STALLED)
         steepest = failed & ~use_steepest
     return x, sign * f_end, iterations, status
@@ -720,11 +753,7 @@ def _assemble_system(p, out, ReturnBounds, ReturnAll):
     best = np.where(none, np.argmin(np.where(finite, viol_all, np.inf), axis=1), best)
     rows = np.arange(E)
 
-    def true_scale(xn):
-        out = p['vmin'] + xn * p['vspan']
-        out = np.where(xn == p['lo'], p['box'][:, 0], out)            # a point on a face of the box is ON it
-        return np.where(xn == p['hi'], p['box'][:, 1], out)
-
+    true_scale = lambda xn: _true_scale(xn, p['vmin'], p['vspan'], p['lo'], p['hi'], p['box'])
     if p['obj_var'] >= 0:
         f_all = true_scale(x_all)[..., p['obj_var']]
     x, f, status = true_scale(x_all[rows, best]), f_all[rows, best], st_all[rows, best]
@@ -739,10 +768,7 @@ def _assemble_system(p, out, ReturnBounds, ReturnAll):
                multipliers={name: pick(mu[:, i]) for i, name in enumerate(names)},
                status=int(status[0]) if one else status, variables=list(p['variables']), constraint_names=names)
     if not one and ReturnBounds and E >= 2:
-        cut = bounds_cut(E)
-        xs, fs = np.sort(x, axis=0), np.sort(f)
-        res.update(x_mean=x.mean(axis=0), f_mean=float(f.mean()),
-                   x_bounds=np.stack([xs[cut], xs[E - cut]], axis=1), f_bounds=np.array([fs[cut], fs[E - cut]]))
+        res.update(_over_draws(x, f))
     if ReturnAll:
         res.update(x_all=true_scale(x_all), f_all=f_all, violation_all=viol_all, y_all=y_all, multipliers_all=mu_all,
                    iterations_all=it_all, status_all=st_all, best_start=best)
@@ -815,56 +841,6 @@ def _expanded(p, k):
     return wide, a, b
 
 
-def _model_parts(tt, table, a, b, z, coef, level, weight=None):
-    """Model value e [B] and sum |term| [B] at the common coordinates z [B, n] (the model reads a + b z); with level 2
-    also its plain gradient [n, B] and ``weight`` [B] x its Hessian's lower triangle [n (n + 1) / 2, B]."""
-    B = z.shape[0]
-    fac = np.empty((tt.n_slots + 1, 3, B))
-    fac[tt.n_slots] = np.array([1.0, 0.0, 0.0])[:, None]
-    for s in range(tt.n_slots):
-        c = table[tt.order[s] - 1]
-        v = tt.src[s]
-        xs = a[v] + b[v] * z[:, v]
-        value = np.full(B, c[tt.order[s]])
-        slope = np.zeros(B)
-        bend = np.zeros(B)
-        for k in range(tt.order[s] - 1, -1, -1):
-            bend = bend * xs + slope
-            slope = slope * xs + value
-            value = value * xs + c[k]
-        fac[s, 0], fac[s, 1], fac[s, 2] = value, slope * b[v], 2.0 * bend * (b[v] * b[v])
-    w = coef[:, 1:].T
-    A = fac[tt.slots, 0]
-    product = A[:, 0].copy()
-    for i in range(1, tt.width):
-        product = product * A[:, i]
-    each = w * product
-    e = coef[:, 0] + each.sum(axis=0)
-    noise = np.abs(coef[:, 0]) + np.abs(each).sum(axis=0)
-    if level == 0:
-        return e, noise
-    D1, D2 = fac[tt.slots, 1], fac[tt.slots, 2]
-    wh = weight * w
-
-    def others(skip):
-        out = np.ones((tt.n_terms, B))
-        for i in range(tt.width):
-            if i not in skip:
-                out = out * A[:, i]
-        return out
-
-    grad = np.zeros((tt.m + 1, B))
-    hess = np.zeros((tt.n_hess + 1, B))
-    with np.errstate(invalid='ignore', over='ignore'):
-        for i in range(tt.width):
-            rest = others((i,))
-            grad += tt.to_grad[i] @ (w * rest * D1[:, i])
-            hess += tt.to_hess[i, i] @ (wh * rest * D2[:, i])
-            for j in range(i):
-                hess += tt.to_hess[i, j] @ (wh * others((i, j)) * D1[:, i] * D1[:, j])
-    return e, noise, grad[:tt.m], hess[:tt.n_hess]
-
-
 def _constraint(c, r, lam_lo, lam_hi, rho):
     """One constraint at residual r [B] (the output, minus the tied variable's value for a tie): its summand of the merit
     function, d merit / d r, the weight of its rank-one Hessian term, its scaled violation, the measure the updates and
@@ -910,7 +886,7 @@ class _System:
 
     def values(self, z, coef):
         """Every model's value [K, B] and sum |term| [K, B] at z [B, n]."""
-        out = [_model_parts(tt, self.p['table'], a, b, z, coef[:, self.offsets[k]:self.offsets[k + 1]], 0)
+        out = [_model_parts(tt, self.p['table'], z, coef[:, self.offsets[k]:self.offsets[k + 1]], 0, maps=(a, b))
                for k, (tt, a, b) in enumerate(self.parts)]
         return np.array([o[0] for o in out]), np.array([o[1] for o in out])
 
@@ -952,8 +928,8 @@ class _System:
             g[p['obj_var']] += p['sign']
         with np.errstate(invalid='ignore', over='ignore'):
             for k, (tt, a, b) in enumerate(self.parts):
-                _, _, gm, Hk = _model_parts(tt, p['table'], a, b, z, coef[:, self.offsets[k]:self.offsets[k + 1]], 2,
-                                            weight[k])
+                _, _, gm, Hk = _model_parts(tt, p['table'], z, coef[:, self.offsets[k]:self.offsets[k + 1]], 2,
+                                            weight=weight[k], maps=(a, b))
                 H += Hk
                 g += weight[k] * gm
                 plain = np.zeros(B)
@@ -986,7 +962,6 @@ def _solve_system_block(system, coef, x, max_iter):
     rho = np.full(B, RHO_START)
     inner = np.full(B, max(tol, INNER_START) if C else tol)
     target = np.full(B, max(ctol, FEASIBLE_START))
-    fixed = (lo == hi)[:, None]
     lo_c, hi_c = lo[:, None], hi[:, None]
     for it in range(max_iter + 1):
         running = status < 0
@@ -1024,33 +999,12 @@ def _solve_system_block(system, coef, x, max_iter):
         running = (status < 0) & ~update
         if not running.any():
             continue
-        with np.errstate(invalid='ignore', over='ignore'):
-            active = fixed | ((xt <= lo_c) & (g > 0)) | ((xt >= hi_c) & (g < 0))
-            d = _direction(H, g, active)
-            reach = np.max(np.abs(d), axis=0)
-            use_steepest = steepest | ~(reach <= np.finfo(np.float64).max)
-            d = np.where(use_steepest, np.where(active, 0.0, -g), d)
-            reach = np.max(np.abs(d), axis=0)
-            d = np.where(reach > 1.0, d / reach, d)
-            alpha = np.ones(B)
-            searching = running.copy()
-            for _ in range(MAX_HALVINGS + 1):
-                if not searching.any():
-                    break
-                trial = np.minimum(np.maximum(xt + alpha * d, lo_c), hi_c)
-                zt = np.ascontiguousarray(trial.T)
-                et, nt = system.values(zt, coef)
-                Ft = system.merit(zt, et, nt, lam, rho)[0]
-                step = trial - xt
-                slope = np.zeros(B)
-                for j in range(n):
-                    slope = slope + g[j] * step[j]
-                ok = (Ft <= F + ARMIJO * np.minimum(slope, 0.0) + NOISE * noise) & (np.max(np.abs(step), axis=0) > 0)
-                take = searching & ok
-                x[take] = trial.T[take]
-                searching = searching & ~ok
-                alpha = np.where(searching, alpha * 0.5, alpha)
-        failed = searching
+
+        def merit_at(trial):
+            et, nt = system.values(trial, coef)
+            return system.merit(trial, et, nt, lam, rho)[0]
+
+        failed, use_steepest = _newton_step(x, F, noise, g, H, lo, hi, running, steepest, merit_at)
         stop(failed & use_steepest, STALLED)
         steepest = failed & ~use_steepest
     # the results at the end point: objective, violation, every model's value, first-order multipliers
