@@ -7,15 +7,17 @@
 //                        and finishes it on the way: raw accepted polar pairs (x2, x1) -> normals f x2, f x1,
 //                        f = sqrt(-2 log r2 / r2), r2 = x1^2 + x2^2 re-formed from the pair (the same two separately
 //                        rounded products and one addition the recorder made: fokl_sampler.cpp polar_pairs_raw);
-//   gibbs_chain_kernel   one wavefront per chain.  Lane i + 64 t owns eigen-direction i: d = 1 / (lamb + 1 / tau2),
-//                        w = d qty + sigma sqrt(d) v (FR:1521-1528 in the eigenbasis, as fokl_sampler.cpp chain_step),
-//                        the three quadratic forms summed in the HOST chain's order (eight partial sums, element i to
-//                        partial i mod 8, ascending i, fixed combination tree) so that the recursion sees the same
-//                        bits; sigma^2 / tau^2 from the tape's two standard gammas (FR:1532-1548); the mean of w over
-//                        the rows the kill tests look at (FR:1671) accumulated on the fly.
-//
-// Results differ from fokl_gibbs_chain only through log(): the device's is within an ulp of glibc's, which reaches the
-// draws at the 1e-16 level (tests/test_gpu_parity.py bounds 1e-13 of the column scale).
+//   gibbs_chain_kernel   (FOKL_DCHAIN_RECURSION=exact) one wavefront per chain.  Lane i + 64 t owns eigen-direction i:
+//                        d = 1 / (lamb + 1 / tau2), w = d qty + sigma sqrt(d) v (FR:1521-1528 in the eigenbasis, as
+//                        fokl_sampler.cpp chain_step), the three quadratic forms summed in the HOST chain's order (eight
+//                        partial sums, element i to partial i mod 8, ascending i, fixed combination tree) so that the
+//                        recursion sees the same bits; sigma^2 / tau^2 from the tape's two standard gammas
+//                        (FR:1532-1548); the mean of w over the rows the kill tests look at (FR:1671) accumulated on
+//                        the fly.  Its results differ from fokl_gibbs_chain only through log(): the device's is within
+//                        an ulp of glibc's, which reaches the draws at the 1e-16 level;
+//   gibbs_chain_segments_kernel   (the default) the same recursion with its reciprocals folded and its sums in registers
+//                        (chain_segment: the one statement of it), as eight verified pieces on eight wavefronts, or
+//                        (=serial) as one piece on one.
 //
 // A small engine around the kernels (fokl_dchain_*): jobs are queued by the driver as soon as a tape is COMMITTED; a
 // dispatcher thread sleeps until the recorder has finished that tape, then issues H2D copies, the two kernels and the
@@ -306,31 +308,24 @@ __device__ __forceinline__ double wave_total(double x)
     return (from_lane(x, 0) + from_lane(x, 16)) + (from_lane(x, 32) + from_lane(x, 48));
 }
 
-// blockIdx.x = job of the batch (all of one size class T = elements per lane); one wavefront per chain.
-//
-// FAST == false: the host chain's operations in the host chain's order (fokl_sampler.cpp chain_step) -- on finished
-// normals the draws are the host's bit for bit; nine divisions / square roots stand in a row on the recursion's critical
-// path, ~1 us per Gibbs iteration.
-// FAST == true (default): the same recursion with the reciprocals folded --
-//     sigma^2' = bstar / g_s                      for 1 / ((1 / bstar) g_s)
-//     1/tau^2' = 2 g_t bstar / (C g_s + 2 btau bstar)   for 1 / (1 / ((1 / btau*) g_t)),  btau* = C / (2 sigma^2') + btau
-//     C / tau^2 = C * (1/tau^2)
-// -- which leaves three long operations on the critical path (d = 1 / (lamb + 1/tau^2), sqrt(d), the quotient of
-// 1/tau^2').  Round 5: those three are Newton-refined hardware seeds (s = rsq(lamb + 1/tau^2), sqrt(d) = s, d = s s;
-// sigma = sqrt(bstar) rsq(g_s) with rsq(g_s) formed when the gammas are staged; the quotient as a product with rcp), and
-// the three sums of an iteration are formed in registers (per-lane partial over its T elements, DPP steps inside the rows
-// of 16, the four row sums through scalar registers) instead of in the host chain's order through LDS and a barrier: 0.53
-// -> 0.3x us per iteration at up to 64 columns.  Every such step differs from the host's by a rounding or two; the chain
-// does not amplify that (draws agree with the host chain to ~1e-15 of the column scale, bounded by 1e-13 in
-// tests/test_chain_device.py).
-// Round 6: two of the three sums leave the critical path.  With A = sqrt(d) qty, B = sigma v (w = sqrt(d) (A + B)):
-//     (lamb + 1/tau^2) w^2 - 2 w qty = (A + B)^2 - 2 A (A + B) = B^2 - A^2,
-// so   bstar = b + (dtd - sum_j d_j qty_j^2 + sigma^2 sum_j v_j^2) / 2:
-// the sum of a row's squared normals does not depend on the recursion at all (formed beside it, on the same wavefront, from
-// the row already in registers), sum_j d_j qty_j^2 needs d alone, and sum_j w_j^2 (for 1/tau^2') is the only sum behind w.
-// The seeds take ONE Newton step (rsq_newton1 / rcp_newton1), sigma' = bstar rsq(bstar) rsq(g_s).  Dependent instructions
-// per iteration ~48 -> ~33: 1.05 -> 0.7x ms per 2000 iterations at up to 64 columns.
-template <int T, bool FAST>
+// The ticket is the completion flag the host polls (plain loads from its own page-locked memory -- no runtime call); every
+// kernel that completes this way ends here (spectral_vectors_kernel too).  All wavefronts of the workgroup have stored into
+// host memory: each one makes its own stores visible system-wide FIRST, the barrier then tells thread 0 that every fence is
+// behind, and only then is the ticket stored.  (Barrier first, fences second let thread 0 pass its own fence and publish the
+// ticket while another wavefront's stores were still on their way: the barrier does not wait for outstanding stores.)
+__device__ __forceinline__ void publish_ticket(double *word, double ticket)
+{
+    __threadfence_system();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (the fence's own wait, spelled out: the compiler may not drop it)
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(word, ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// FOKL_DCHAIN_RECURSION=exact.  blockIdx.x = job of the batch (all of one size class T = elements per lane); one wavefront
+// per chain.  The host chain's operations in the host chain's order (fokl_sampler.cpp chain_step) -- on finished normals the
+// draws are the host's bit for bit; nine divisions / square roots stand in a row on the recursion's critical path, ~1 us per
+// Gibbs iteration.
+template <int T>
 __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__restrict__ jobs)
 {
     // rows of normals (and the two gammas) are fetched U iterations ahead into a ring of registers: a row's load is a
@@ -344,7 +339,7 @@ __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__rest
     // fit next to a chain, ran after the others, and the launch took up to twice as long (fp64-MFMA-bound Gram launches
     // in situ: 0.70 of the peak without chains on the device, 0.55 with)
     constexpr int GCH = 128;
-    __shared__ double gam[3][GCH];                          // (FAST: [2] = 1 / sqrt(g_s))
+    __shared__ double gam[2][GCH];
     const ChainArgs a = jobs[blockIdx.x];
     const long long t_begin = wall_clock64();
     const int lane = threadIdx.x, p1 = a.p1, draws = a.draws;
@@ -357,9 +352,6 @@ __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__rest
         qt[t] = i < p1 ? gload(a.qty + i) : 0.0;
         sum_w[t] = 0.0;
     }
-    double qt2[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) qt2[t] = qt[t] * qt[t];
     // Loads are unconditional on clamped indices (a select on a loaded value makes the compiler wait for the load where
     // the select stands; lanes beyond p1 and rows beyond the last compute values nobody stores or sums).
     int col[T];
@@ -373,7 +365,6 @@ __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__rest
         for (int t = 0; t < T; ++t) vbuf[u][t] = gload(a.normals + (size_t)ku * p1 + col[t]);
     }
     double sigsqd = a.sigsqd0, tausqd = a.tausqd0;
-    double inv_tau = 1.0 / tausqd, sig = sqrt(sigsqd);
     int flagged = 0;
     const int s = lane >> 3, l = lane & 7;                  // lanes 0..23: partial l of sum s
     for (int k0 = 0; k0 < draws; k0 += U) {
@@ -385,40 +376,19 @@ __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__rest
                 __syncthreads();
                 for (int j = lane; j < GCH; j += 64) {
                     const int kj = min(k + j, last);
-                    const double g_s = gload(a.gam_sig + kj);
-                    gam[0][j] = g_s;
+                    gam[0][j] = gload(a.gam_sig + kj);
                     gam[1][j] = gload(a.gam_tau + kj);
-                    if (FAST) gam[2][j] = rsq_newton(g_s);
                 }
                 __syncthreads();
             }
             const double gs = gam[0][k & (GCH - 1)], gt = gam[1][k & (GCH - 1)];
             double (*buf)[64 * T] = red[k & 1];
             const double *mine = buf[s < 3 ? s : 0];
-            if (!FAST) {
-                inv_tau = 1.0 / tausqd;
-                sig = sqrt(sigsqd);
-            }
-            double part_f = 0.0, part_vv = 0.0, part_ww = 0.0;              // FAST: this lane's share of the three sums
+            const double inv_tau = 1.0 / tausqd;
+            const double sig = sqrt(sigsqd);
 #pragma unroll
             for (int t = 0; t < T; ++t) {
                 const int i = lane + 64 * t;
-                if (FAST) {
-                    const double v = vbuf[u][t];
-                    const double bv = sig * v;                              // (off the critical path: sigma is known early)
-                    const double root = rsq_newton1(lam[t] + inv_tau);
-                    const double d = root * root;
-                    const double z = __builtin_fma(root, qt[t], bv);
-                    const double wi = root * z;
-                    if (i < p1) {
-                        gstore(a.w + (size_t)k * p1 + i, wi);
-                        part_f = __builtin_fma(qt2[t], d, part_f);
-                        part_vv = __builtin_fma(v, v, part_vv);
-                        part_ww = __builtin_fma(wi, wi, part_ww);
-                        if (k >= a.stat_first) sum_w[t] += wi;
-                    }
-                    continue;
-                }
                 const double d = 1.0 / (lam[t] + inv_tau);
                 const double root = sqrt(d);
                 const double wi = d * qt[t] + sig * (root * vbuf[u][t]);
@@ -437,25 +407,6 @@ __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__rest
 #pragma unroll
                 for (int t = 0; t < T; ++t) vbuf[u][t] = gload(a.normals + (size_t)kn * p1 + col[t]);
             }
-            if (FAST) {
-                const double q_vv = wave_total(part_vv);                    // (independent of the recursion)
-                const double q_f = wave_total(part_f), q_ww = wave_total(part_ww);
-                const double bstar = a.b + 0.5 * ((a.dtd - q_f) + sigsqd * q_vv);
-                if (bstar < 0.0) {
-                    flagged = 1;
-                    sigsqd = __builtin_nan("");
-                    inv_tau = __builtin_nan("");
-                    sig = __builtin_nan("");
-                } else {
-                    const double two_b = 2.0 * bstar, r_gs = gam[2][k & (GCH - 1)];
-                    inv_tau = (gt * two_b) * rcp_newton1(q_ww * gs + a.btau * two_b);   // the next iteration's critical path
-                    // (bstar == 0: sigma = 0 without 0 * inf; bstar NaN -- the rows behind a flagged one -- stays NaN, as
-                    // the host chain's last sigma^2 does)
-                    sig = bstar > 0.0 ? (bstar * rsq_newton1(bstar)) * r_gs : bstar;
-                    sigsqd = sig * sig;
-                }
-                continue;
-            }
             __syncthreads();
             // the host chain's order (fokl_sampler.cpp chain_vector_portable): partial l takes the elements i = l,
             // l + 8, ... in ascending order; all reads issued before the dependent additions (compile-time trip count)
@@ -471,32 +422,17 @@ __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__rest
             acc += row_down<2>(acc);
             acc += row_down<1>(acc);
             const double q_lam = from_lane(acc, 0), q_ty = from_lane(acc, 8), q_ww = from_lane(acc, 16);
-            if (FAST) {
-                const double bstar = a.b + 0.5 * (q_lam - 2.0 * q_ty + a.dtd + q_ww * inv_tau);
-                if (bstar < 0.0) {
-                    flagged = 1;
-                    sigsqd = __builtin_nan("");
-                    inv_tau = __builtin_nan("");
-                } else {
-                    const double two_b = 2.0 * bstar;
-                    inv_tau = (gt * two_b) / (q_ww * gs + a.btau * two_b);   // the next iteration's critical path
-                    sigsqd = bstar / gs;
-                }
-                sig = sqrt(sigsqd);
+            const double bstar = a.b + 0.5 * (q_lam - 2.0 * q_ty + a.dtd + q_ww / tausqd);
+            if (bstar < 0.0) {
+                flagged = 1;                                // the tape holds a gamma the reference would not have drawn
+                sigsqd = __builtin_nan("");
             } else {
-                const double bstar = a.b + 0.5 * (q_lam - 2.0 * q_ty + a.dtd + q_ww / tausqd);
-                if (bstar < 0.0) {
-                    flagged = 1;                            // the tape holds a gamma the reference would not have drawn
-                    sigsqd = __builtin_nan("");
-                } else {
-                    sigsqd = 1.0 / ((1.0 / bstar) * gs);
-                }
-                const double btau_star = (1.0 / (2.0 * sigsqd)) * q_ww + a.btau;
-                tausqd = 1.0 / ((1.0 / btau_star) * gt);
+                sigsqd = 1.0 / ((1.0 / bstar) * gs);
             }
+            const double btau_star = (1.0 / (2.0 * sigsqd)) * q_ww + a.btau;
+            tausqd = 1.0 / ((1.0 / btau_star) * gt);
         }
     }
-    if (FAST) tausqd = 1.0 / inv_tau;
     const int rows = draws > a.stat_first ? draws - a.stat_first : 0;
 #pragma unroll
     for (int t = 0; t < T; ++t) {
@@ -511,18 +447,32 @@ __global__ __launch_bounds__(64) void gibbs_chain_kernel(const ChainArgs *__rest
         gstore(a.stats + 5 + p1, (double)(wall_clock64() - t_begin) * a.seconds_per_tick);   // the chain's own duration
         gstore(a.stats + 6 + p1, 0.0);                      // (no cut to fail: a recycled slot never shows an old 1)
     }
-    // the ticket is the completion flag the host polls (plain loads from its own page-locked memory -- no runtime call):
-    // everything above is visible system-wide before it
-    __syncthreads();
-    __threadfence_system();
-    if (lane == 0) {
-        __hip_atomic_store(a.stats + 4 + p1, a.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    publish_ticket(a.stats + 4 + p1, a.ticket);
 }
 
-// ---- the recursion in SEGMENTS (round 6) -----------------------------------------------------------------------------
-// The D-iteration loop is a chain only through two scalars, sigma^2 and 1/tau^2, and it forgets them fast: bstar carries the
-// old sigma^2 with the weight sum v^2 / 2 against a gamma variate of shape ~ n / 2 (a factor ~ p1 / n per iteration), and
+// ---- the FAST recursion (FOKL_DCHAIN_RECURSION = fast, the default, or serial) -------------------------------------------
+// The same recursion as gibbs_chain_kernel's with the reciprocals folded --
+//     sigma^2' = bstar / g_s                      for 1 / ((1 / bstar) g_s)
+//     1/tau^2' = 2 g_t bstar / (C g_s + 2 btau bstar)   for 1 / (1 / ((1 / btau*) g_t)),  btau* = C / (2 sigma^2') + btau
+//     C / tau^2 = C * (1/tau^2)
+// -- which leaves three long operations on the critical path (d = 1 / (lamb + 1/tau^2), sqrt(d), the quotient of
+// 1/tau^2').  Round 5: those three are Newton-refined hardware seeds (s = rsq(lamb + 1/tau^2), sqrt(d) = s, d = s s;
+// sigma = sqrt(bstar) rsq(g_s) with rsq(g_s) formed when the gammas are staged; the quotient as a product with rcp), and
+// the three sums of an iteration are formed in registers (per-lane partial over its T elements, DPP steps inside the rows
+// of 16, the four row sums through scalar registers) instead of in the host chain's order through LDS and a barrier: 0.53
+// -> 0.3x us per iteration at up to 64 columns.  Every such step differs from the host's by a rounding or two; the chain
+// does not amplify that (draws agree with the host chain to ~1e-15 of the column scale, bounded by 1e-13 in
+// tests/test_chain_device.py).
+// Round 6: two of the three sums leave the critical path.  With A = sqrt(d) qty, B = sigma v (w = sqrt(d) (A + B)):
+//     (lamb + 1/tau^2) w^2 - 2 w qty = (A + B)^2 - 2 A (A + B) = B^2 - A^2,
+// so   bstar = b + (dtd - sum_j d_j qty_j^2 + sigma^2 sum_j v_j^2) / 2:
+// the sum of a row's squared normals does not depend on the recursion at all (formed beside it, on the same wavefront, from
+// the row already in registers), sum_j d_j qty_j^2 needs d alone, and sum_j w_j^2 (for 1/tau^2') is the only sum behind w.
+// The seeds take ONE Newton step (rsq_newton1 / rcp_newton1), sigma' = bstar rsq(bstar) rsq(g_s).  Dependent instructions
+// per iteration ~48 -> ~33: 1.05 -> 0.7x ms per 2000 iterations at up to 64 columns.
+//
+// IN SEGMENTS (round 6).  The D-iteration loop is a chain only through two scalars, sigma^2 and 1/tau^2, and it forgets them
+// fast: bstar carries the old sigma^2 with the weight sum v^2 / 2 against a gamma variate of shape ~ n / 2 (a factor ~ p1 / n per iteration), and
 // 1/tau^2 enters through d_j = 1 / (lamb_j + 1/tau^2), next to nothing where lamb_j is large.  So the 2000 iterations are cut
 // into kChainSegments pieces, one wavefront each, side by side in one workgroup: piece s starts kChainWarm iterations EARLY
 // from the chain's initial state, throws those iterations away, and must arrive at its first real iteration with the state the
@@ -543,13 +493,16 @@ struct ChainLane {
     int col[T];
 };
 
-// iterations [k_begin, k_end) of the FAST recursion on one wavefront; rows before k_write are warm-up (nothing stored, nothing
-// summed); the state in front of iteration k_write is left in at_write[0..1].  gam: this wavefront's [3][kChainGammas] of LDS.
+// The one statement of the fast iteration: a piece of the default kernel, its one-wavefront fallback and the whole chain of
+// FOKL_DCHAIN_RECURSION=serial all run it, which is what "the fallback equals the serial mode bit for bit" rests on.
+// Iterations [k_begin, k_end) on one wavefront; rows before k_write are warm-up (nothing stored, nothing summed); the state
+// in front of iteration k_write is left in at_write[0..1].  gam: this wavefront's [3][kChainGammas] of LDS.
 template <int T>
 __device__ __forceinline__ void chain_segment(const ChainArgs &a, const ChainLane<T> &c, int lane, double *gam, int k_begin,
                                               int k_write, int k_end, double &sigsqd, double &inv_tau, double &sig,
                                               double (&sum_w)[T], int &flagged, double (&at_write)[2])
 {
+    // rows of normals are fetched U iterations ahead into a ring of registers (see gibbs_chain_kernel)
     constexpr int U = T <= 2 ? 8 : (T <= 4 ? 4 : 2);
     constexpr int G = kChainGammas;
     const int p1 = a.p1, last = max(a.draws - 1, 0);
@@ -583,12 +536,12 @@ __device__ __forceinline__ void chain_segment(const ChainArgs &a, const ChainLan
                 at_write[1] = inv_tau;
             }
             const bool real = k >= k_write;
-            double part_f = 0.0, part_vv = 0.0, part_ww = 0.0;
+            double part_f = 0.0, part_vv = 0.0, part_ww = 0.0;              // this lane's share of the three sums
 #pragma unroll
             for (int t = 0; t < T; ++t) {
                 const int i = lane + 64 * t;
                 const double v = vbuf[u][t];
-                const double bv = sig * v;
+                const double bv = sig * v;                                  // (off the critical path: sigma is known early)
                 const double root = rsq_newton1(c.lam[t] + inv_tau);
                 const double d = root * root;
                 const double z = __builtin_fma(root, c.qt[t], bv);
@@ -601,34 +554,37 @@ __device__ __forceinline__ void chain_segment(const ChainArgs &a, const ChainLan
                     if (real && k >= a.stat_first) sum_w[t] += wi;
                 }
             }
+            // this slot of the ring is free: row k + U goes into it (consumed U iterations from now)
             {
                 const int kn = min(k + U, last);
 #pragma unroll
                 for (int t = 0; t < T; ++t) vbuf[u][t] = gload(a.normals + (size_t)kn * p1 + c.col[t]);
             }
-            const double q_vv = wave_total(part_vv);
+            const double q_vv = wave_total(part_vv);                        // (independent of the recursion)
             const double q_f = wave_total(part_f), q_ww = wave_total(part_ww);
             const double bstar = a.b + 0.5 * ((a.dtd - q_f) + sigsqd * q_vv);
             if (bstar < 0.0) {
-                if (real) flagged = 1;
+                if (real) flagged = 1;                      // the tape holds a gamma the reference would not have drawn
                 sigsqd = __builtin_nan("");
                 inv_tau = __builtin_nan("");
                 sig = __builtin_nan("");
             } else {
                 const double two_b = 2.0 * bstar;
-                inv_tau = (gt * two_b) * rcp_newton1(q_ww * gs + a.btau * two_b);
-                sig = bstar > 0.0 ? (bstar * rsq_newton1(bstar)) * r_gs : bstar;    // (0 stays 0, NaN stays NaN)
+                inv_tau = (gt * two_b) * rcp_newton1(q_ww * gs + a.btau * two_b);   // the next iteration's critical path
+                // (bstar == 0: sigma = 0 without 0 * inf; bstar NaN -- the rows behind a flagged one -- stays NaN, as
+                // the host chain's last sigma^2 does)
+                sig = bstar > 0.0 ? (bstar * rsq_newton1(bstar)) * r_gs : bstar;
                 sigsqd = sig * sig;
             }
         }
     }
 }
 
-// blockIdx.x = job of the batch; kChainSegments wavefronts per chain (see above)
-template <int T>
-__global__ __launch_bounds__(64 * kChainSegments) void gibbs_chain_segments_kernel(const ChainArgs *__restrict__ jobs)
+// blockIdx.x = job of the batch; S wavefronts per chain: kChainSegments pieces (see above), or -- S = 1,
+// FOKL_DCHAIN_RECURSION=serial -- the whole chain as the one piece of one wavefront: no cut to check, bad_cut stays 0
+template <int T, int S = kChainSegments>
+__global__ __launch_bounds__(64 * S) void gibbs_chain_segments_kernel(const ChainArgs *__restrict__ jobs)
 {
-    constexpr int S = kChainSegments;
     __shared__ double gam[S][3 * kChainGammas];
     __shared__ double begin_state[S][2], end_state[S][2];
     __shared__ double mean_acc[64 * T];
@@ -644,7 +600,7 @@ __global__ __launch_bounds__(64 * kChainSegments) void gibbs_chain_segments_kern
         c.lam[t] = i < p1 ? gload(a.lamb + i) : 1.0;
         c.qt[t] = i < p1 ? gload(a.qty + i) : 0.0;
         c.qt2[t] = c.qt[t] * c.qt[t];
-        c.col[t] = min(i, p1 - 1);
+        c.col[t] = min(i, p1 - 1);                          // (loads on clamped indices: see gibbs_chain_kernel)
         sum_w[t] = 0.0;
     }
     if (threadIdx.x == 0) {
@@ -681,7 +637,7 @@ __global__ __launch_bounds__(64 * kChainSegments) void gibbs_chain_segments_kern
         bad_cut = bad;
     }
     __syncthreads();
-    if (bad_cut) {
+    if (S > 1 && bad_cut) {
         // not forgotten within the warm-up: the whole chain on one wavefront, from the initial state (rows rewritten)
         if (wave == 0) {
 #pragma unroll
@@ -705,7 +661,8 @@ __global__ __launch_bounds__(64 * kChainSegments) void gibbs_chain_segments_kern
         end_state[S - 1][1] = inv_tau;
     }
     if (flagged && lane == 0) atomicOr(&any_flag, 1);
-    // the mean of w over the rows the kill tests look at: the pieces' sums in piece order (the same bits every time)
+    // the mean of w over the rows the kill tests look at: the pieces' sums in piece order (the same bits every time; a sum
+    // starts at + 0.0 and never becomes - 0.0, so 0.0 + sum is the sum itself: one piece's mean is its own sum's quotient)
     for (int w2 = 0; w2 < S; ++w2) {
         __syncthreads();
         if (wave == w2) {
@@ -728,15 +685,9 @@ __global__ __launch_bounds__(64 * kChainSegments) void gibbs_chain_segments_kern
         gstore(a.stats + 5 + p1, (double)(wall_clock64() - t_begin) * a.seconds_per_tick);
         gstore(a.stats + 6 + p1, (double)bad_cut);          // this chain ran as one piece after all (DeviceChainJob.bad_cut)
     }
-    // All eight wavefronts have stored into host memory (means of the columns from 64 on, rows of w): each one makes its
-    // own stores visible system-wide FIRST, the barrier then tells thread 0 that every fence is behind, and only then is
-    // the ticket stored.  (Barrier first, fences second let thread 0 pass its own fence and publish the ticket while
-    // another wavefront's means were still on their way: the barrier does not wait for outstanding stores.)
-    __threadfence_system();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (the fence's own wait, spelled out: the compiler may not drop it)
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(a.stats + 4 + p1, a.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_ticket(a.stats + 4 + p1, a.ticket);             // (means of the columns from 64 on and rows of w: all S wavefronts)
 }
+
 
 }  // namespace fokl
 
@@ -915,8 +866,8 @@ bool device_can_read(const void *ptr, size_t bytes)
     return at >= it->first && at + bytes <= it->first + it->second;
 }
 
-// segments == false (FOKL_DCHAIN_RECURSION=serial when the engine was created): the fast recursion on one wavefront from
-// start to end (round 5) instead of in segments
+// FOKL_DCHAIN_RECURSION when the engine was created: the fast recursion in segments (default), the same statement as one
+// piece on one wavefront from start to end (serial: segments == false), or the host chain's own operations (exact)
 template <int T>
 void launch_chain(const fokl::ChainArgs *d_jobs, int count, hipStream_t stream, bool fast, bool segments)
 {
@@ -924,9 +875,9 @@ void launch_chain(const fokl::ChainArgs *d_jobs, int count, hipStream_t stream, 
         hipLaunchKernelGGL((fokl::gibbs_chain_segments_kernel<T>), dim3((unsigned)count), dim3(64 * fokl::kChainSegments), 0,
                            stream, d_jobs);
     else if (fast)
-        hipLaunchKernelGGL((fokl::gibbs_chain_kernel<T, true>), dim3((unsigned)count), dim3(64), 0, stream, d_jobs);
+        hipLaunchKernelGGL((fokl::gibbs_chain_segments_kernel<T, 1>), dim3((unsigned)count), dim3(64), 0, stream, d_jobs);
     else
-        hipLaunchKernelGGL((fokl::gibbs_chain_kernel<T, false>), dim3((unsigned)count), dim3(64), 0, stream, d_jobs);
+        hipLaunchKernelGGL((fokl::gibbs_chain_kernel<T>), dim3((unsigned)count), dim3(64), 0, stream, d_jobs);
 }
 
 inline int chain_class(int p1)
@@ -1354,6 +1305,61 @@ int dchain_complete(fokl_dchain *e, ChainJob *job, bool block)
     return ran;
 }
 
+// A job with the fields both ways of handing over a tape share; the caller adds the tape itself.
+ChainJob *new_job(int p1, int draws, int stat_first, const double *lamb, const double *qty, double b, double btau, double dtd,
+                  double sigsqd0, double tausqd0, const double *gam_sig, const double *gam_tau, const int32_t *progress)
+{
+    auto *job = new ChainJob();
+    job->p1 = p1;
+    job->draws = draws;
+    job->stat_first = stat_first;
+    job->b = b;
+    job->btau = btau;
+    job->dtd = dtd;
+    job->sigsqd0 = sigsqd0;
+    job->tausqd0 = tausqd0;
+    job->model.assign(lamb, lamb + p1);
+    job->model.insert(job->model.end(), qty, qty + p1);
+    job->gam_sig = gam_sig;
+    job->gam_tau = gam_tau;
+    job->progress = progress;
+    job->t_submit = dchain_now_ns();
+    return job;
+}
+
+// Takes the job over (it is deleted on failure): a free slot, the slot's statistics area with its completion word cleared,
+// the job's ticket, and the job into the dispatcher's queue.  who: the entry point, for the error text.
+int enqueue_job(fokl_dchain *e, ChainJob *job, const char *who, int64_t *ticket, const double **stats_area)
+{
+    {
+        std::lock_guard<std::mutex> lock(e->m);
+        for (size_t i = 0; i < e->slots.size(); ++i)
+            if (!e->slots[i].busy) {
+                job->slot = (int)i;
+                break;
+            }
+        if (job->slot < 0) {
+            delete job;
+            return dchain_fail(e, FOKL_ERR_STATE, std::string(who) + ": every slot holds a chain that was not released");
+        }
+        ChainSlot &slot = e->slots[(size_t)job->slot];
+        if (ensure_stats(e, slot, job->p1) != FOKL_OK) {    // (allocated once per slot, for the largest model)
+            delete job;
+            return FOKL_ERR_HIP;
+        }
+        slot.busy = true;
+        job->ticket = e->next_ticket++;
+        slot.ticket = job->ticket;
+        __atomic_store_n(reinterpret_cast<int64_t *>(slot.h_stats + 4 + job->p1), (int64_t)0, __ATOMIC_RELEASE);
+        e->jobs[job->ticket] = job;
+        e->queue.push_back(job);
+        *ticket = job->ticket;
+        if (stats_area) *stats_area = slot.h_stats;
+    }
+    e->cv_queue.notify_one();
+    return FOKL_OK;
+}
+
 }  // namespace
 
 extern "C" __attribute__((visibility("hidden"))) int64_t fokl_dchain_dispatcher_cpu_ns()
@@ -1451,53 +1457,13 @@ extern "C" int fokl_dchain_submit(fokl_dchain *e, int p1, int draws, const doubl
         return dchain_fail(e, FOKL_ERR_ARG, "fokl_dchain_submit: null pointer, empty model or bad block size");
     if (p1 > 64 * kChainMaxT)
         return dchain_fail(e, FOKL_ERR_ARG, "fokl_dchain_submit: more columns than the device chain handles (768)");
-    auto *job = new ChainJob();
-    job->p1 = p1;
-    job->draws = draws;
-    job->stat_first = stat_first;
+    ChainJob *job = new_job(p1, draws, stat_first, lamb, qty, b, btau, dtd, sigsqd0, tausqd0, gam_sig, gam_tau, progress);
     job->finished = finished ? 1 : 0;
-    job->b = b;
-    job->btau = btau;
-    job->dtd = dtd;
-    job->sigsqd0 = sigsqd0;
-    job->tausqd0 = tausqd0;
-    job->model.assign(lamb, lamb + p1);
-    job->model.insert(job->model.end(), qty, qty + p1);
     job->normals = normals;
     job->lead = lead;
-    job->gam_sig = gam_sig;
-    job->gam_tau = gam_tau;
-    job->progress = progress;
     job->block_done = block_done;
     job->block = block;
-    job->t_submit = dchain_now_ns();
-    {
-        std::lock_guard<std::mutex> lock(e->m);
-        for (size_t i = 0; i < e->slots.size(); ++i)
-            if (!e->slots[i].busy) {
-                job->slot = (int)i;
-                break;
-            }
-        if (job->slot < 0) {
-            delete job;
-            return dchain_fail(e, FOKL_ERR_STATE, "fokl_dchain_submit: every slot holds a chain that was not released");
-        }
-        ChainSlot &slot = e->slots[(size_t)job->slot];
-        if (ensure_stats(e, slot, p1) != FOKL_OK) {          // grows only: a model larger than the slot has seen
-            delete job;
-            return FOKL_ERR_HIP;
-        }
-        slot.busy = true;
-        job->ticket = e->next_ticket++;
-        slot.ticket = job->ticket;
-        __atomic_store_n(reinterpret_cast<int64_t *>(slot.h_stats + 4 + p1), (int64_t)0, __ATOMIC_RELEASE);
-        e->jobs[job->ticket] = job;
-        e->queue.push_back(job);
-        *ticket = job->ticket;
-        if (stats_area) *stats_area = slot.h_stats;
-    }
-    e->cv_queue.notify_one();
-    return FOKL_OK;
+    return enqueue_job(e, job, "fokl_dchain_submit", ticket, stats_area);
 }
 
 // The page-locked ring the host's bulk threads leave the stream's pre-states in (fokl_stream_create / fokl_pool_create),
@@ -1559,53 +1525,14 @@ extern "C" int fokl_dchain_submit_rows(fokl_dchain *e, int p1, int draws, const 
     if (!device_can_read(rows, (size_t)draws * sizeof(fokl_tape_row)) || !device_can_read(gam_sig, (size_t)draws * sizeof(double)) ||
         !device_can_read(gam_tau, (size_t)draws * sizeof(double)))
         return dchain_fail(e, FOKL_ERR_ARG, "fokl_dchain_submit_rows: the rows must lie in page-locked memory (fokl_host_alloc)");
-    auto *job = new ChainJob();
-    job->p1 = p1;
-    job->draws = draws;
-    job->stat_first = stat_first;
-    job->b = b;
-    job->btau = btau;
-    job->dtd = dtd;
-    job->sigsqd0 = sigsqd0;
-    job->tausqd0 = tausqd0;
+    ChainJob *job = new_job(p1, draws, stat_first, lamb, qty, b, btau, dtd, sigsqd0, tausqd0, gam_sig, gam_tau, progress);
     job->astar = astar;
     job->atau_star = atau_star;
-    job->model.assign(lamb, lamb + p1);
-    job->model.insert(job->model.end(), qty, qty + p1);
     job->rows = rows;
     job->span = span;
-    job->gam_sig = gam_sig;
-    job->gam_tau = gam_tau;
-    job->progress = progress;
-    job->t_submit = dchain_now_ns();
-    {
-        std::lock_guard<std::mutex> lock(e->m);
-        for (size_t i = 0; i < e->slots.size(); ++i)
-            if (!e->slots[i].busy) {
-                job->slot = (int)i;
-                break;
-            }
-        if (job->slot < 0) {
-            delete job;
-            return dchain_fail(e, FOKL_ERR_STATE, "fokl_dchain_submit_rows: every slot holds a chain that was not released");
-        }
-        ChainSlot &slot = e->slots[(size_t)job->slot];
-        if (ensure_stats(e, slot, p1) != FOKL_OK) {
-            delete job;
-            return FOKL_ERR_HIP;
-        }
-        slot.busy = true;
-        job->ticket = e->next_ticket++;
-        slot.ticket = job->ticket;
-        __atomic_store_n(reinterpret_cast<int64_t *>(slot.h_stats + 4 + p1), (int64_t)0, __ATOMIC_RELEASE);
-        e->jobs[job->ticket] = job;
-        e->queue.push_back(job);
-        *ticket = job->ticket;
-        if (stats_area) *stats_area = slot.h_stats;
-    }
-    e->rows_jobs.fetch_add(1, std::memory_order_relaxed);
-    e->cv_queue.notify_one();
-    return FOKL_OK;
+    const int rc = enqueue_job(e, job, "fokl_dchain_submit_rows", ticket, stats_area);
+    if (rc == FOKL_OK) e->rows_jobs.fetch_add(1, std::memory_order_relaxed);
+    return rc;
 }
 
 extern "C" int fokl_dchain_stream_stats(fokl_dchain *e, int64_t *segments_made, int64_t *rows_jobs)

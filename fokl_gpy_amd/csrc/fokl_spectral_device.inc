@@ -478,12 +478,8 @@ __global__ __launch_bounds__(64 * kSpectralColumnsPerGroup) void spectral_vector
         gstore(o_mom + 4, (double)(wall_clock64() - hdr.t_begin) * a.seconds_per_tick);
         gstore(o_mom + 5, hdr.converged ? 0.0 : 1.0);
     }
-    // every wavefront has stored rows of Q', eigenvalues and betahat into the result area: each fences its own stores
-    // system-wide, the barrier collects the fences, then thread 0 publishes the ticket (as gibbs_chain_segments_kernel)
-    __threadfence_system();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(o_mom + 6, a.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    // every wavefront has stored rows of Q', eigenvalues and betahat into the result area (fokl_chain_device.inc: the order)
+    publish_ticket(o_mom + 6, a.ticket);
 }
 
 }  // namespace fokl
