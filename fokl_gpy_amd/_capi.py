@@ -169,6 +169,9 @@ SIGNATURES = {
     'fokl_system_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int,
                                      c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp,
                                      c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_embedded_hmc': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
+                                  ctypes.c_uint32, c_vp, c_dbl, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_embedded_rng': (c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int, c_int, c_vp]),
     'fokl_dchain_create': (c_int, [c_int, c_int, c_vp]),
     'fokl_dchain_destroy': (None, [c_vp]),
     'fokl_dchain_submit': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp,
@@ -250,6 +253,14 @@ def _check(rc, ctx=None):
     if rc != 0:
         msg = load().fokl_last_error(ctx)
         raise FoklNativeError(rc, msg.decode() if msg else "unknown error")
+
+
+def embedded_rng(seed, chain, draw, purpose, count):
+    """The numbers the embedded-GP sampler draws (fokl_embedded_rng: Philox 4x32-10 keyed by (seed, chain), counter
+    (draw, purpose, index)); host code, no device."""
+    out = np.empty(int(count), dtype=np.float64)
+    _check(load().fokl_embedded_rng(int(seed) & 0xFFFFFFFF, int(chain), int(draw), int(purpose), int(count), _ptr(out)))
+    return out
 
 
 def device_count():
@@ -1940,6 +1951,38 @@ class DeviceContext:
             int(p['max_iter']), float(p['tol']), float(p['ctol']), _ptr(x), _ptr(f), _ptr(violation), _ptr(y), _ptr(mu),
             _ptr(iterations), _ptr(status)))
         return x, f, violation, y, mu, iterations, status
+
+    def embedded_hmc(self, n_gps, term_slots, col_slots, ops, consts, result, chains, draws, leapfrog, seed, q0=None,
+                     eps0=0.0, adapt=True, want_grad0=False, want_proposal=False):
+        """fokl_embedded_hmc (embedded.py assembles the arguments) over the uploaded dataset: term_slots the basis columns
+        (ones first), col_slots the equation's columns, ops int32 [n_ops, 3] and consts the tape -> dict of states
+        [chains, draws + 1, D], potential, accepted, eps_hist [chains, draws // 50], inv_mass, eps_final, status, mass_updated
+        (and grad0 / proposal when asked for)."""
+        term_slots = np.ascontiguousarray(term_slots, dtype=np.int32)
+        col_slots = np.ascontiguousarray(col_slots, dtype=np.int32).reshape(-1)
+        ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 3)
+        consts = np.ascontiguousarray(consts, dtype=np.float64).reshape(-1)
+        chains, draws, n_coef = int(chains), int(draws), term_slots.shape[0]
+        D = int(n_gps) * n_coef + 1
+        if q0 is not None:
+            q0 = np.ascontiguousarray(q0, dtype=np.float64)
+            if q0.shape != (chains, D):
+                raise ValueError("embedded_hmc: q0 must be [chains, D]")
+        rows, wins = max(chains, 0), max(draws, 0) // 50
+        out = dict(states=np.empty((rows, max(draws, 0) + 1, D)), potential=np.empty((rows, max(draws, 0) + 1)),
+                   accepted=np.empty((rows, max(draws, 0) + 1), dtype=np.int32), eps_hist=np.empty((rows, wins)),
+                   inv_mass=np.empty((rows, D)), eps_final=np.empty(rows), flags=np.empty((rows, 2), dtype=np.int32),
+                   grad0=np.empty((rows, D)) if want_grad0 else None,
+                   proposal=np.empty((rows, D + 1)) if want_proposal else None)
+        self._ck(self._lib.fokl_embedded_hmc(
+            self._h, int(n_gps), n_coef, _ptr(term_slots), col_slots.shape[0], _ptr(col_slots), ops.shape[0], _ptr(ops),
+            consts.shape[0], _ptr(consts), int(result), chains, draws, int(leapfrog), int(seed) & 0xFFFFFFFF, _ptr(q0),
+            float(eps0), int(bool(adapt)), _ptr(out['states']), _ptr(out['potential']), _ptr(out['accepted']),
+            _ptr(out['eps_hist']), _ptr(out['inv_mass']), _ptr(out['eps_final']), _ptr(out['flags']), _ptr(out['grad0']),
+            _ptr(out['proposal'])))
+        flags = out.pop('flags')
+        out['status'], out['mass_updated'] = flags[:, 0].copy(), flags[:, 1].astype(bool)
+        return out
 
     def read_slot(self, slot, row0=0, nrows=None):
         nrows = self.n - row0 if nrows is None else nrows

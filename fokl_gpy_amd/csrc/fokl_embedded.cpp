@@ -1,0 +1,16 @@
+// The host's view of the embedded-GP sampler's random numbers (fokl_philox.h): embedded.full_sample_host draws through
+// this entry what hmc_chain_kernel draws on the device, so a transition can be compared value for value.
+#include <cstdint>
+
+#include "../../include/fokl_hip_internal.h"
+#include "fokl_philox.h"
+
+extern "C" int fokl_embedded_rng(uint32_t seed, uint32_t chain, uint32_t draw, int purpose, int count, double *out)
+{
+    if (count < 0 || (count > 0 && !out) || purpose < fokl::EMB_PURPOSE_MOMENTUM || purpose > fokl::EMB_PURPOSE_SEARCH)
+        return FOKL_ERR_ARG;
+    for (int j = 0; j < count; ++j)
+        out[j] = purpose == fokl::EMB_PURPOSE_ACCEPT ? fokl::emb_uniform(seed, chain, draw, (uint32_t)purpose, (uint32_t)j)
+                                                     : fokl::emb_normal(seed, chain, draw, (uint32_t)purpose, (uint32_t)j);
+    return FOKL_OK;
+}

@@ -1866,6 +1866,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_optimize_core.inc"
 #include "fokl_optimize_device.inc"
 #include "fokl_optimize_system_device.inc"
+#include "fokl_embedded_device.inc"
 
 #if defined(FOKL_GT_STAMP) || defined(FOKL_GD_STAMP)
 // diagnostic builds only (tools/k2_clock.sh, tools/k2_phases.sh): the clock stamps of the last Gram launch

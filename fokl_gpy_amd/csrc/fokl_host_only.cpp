@@ -65,6 +65,15 @@ extern "C" int fokl_system_optimize(fokl_ctx *, int, int, const int32_t *, const
     return FOKL_ERR_HIP;
 }
 
+// The embedded-GP sampler's chains run on the device only (fokl_embedded_device.inc); its statement is
+// embedded.full_sample_host, and its random numbers (fokl_embedded_rng) are host code and present here.
+extern "C" int fokl_embedded_hmc(fokl_ctx *, int, int, const int32_t *, int, const int32_t *, int, const int32_t *, int,
+                                 const double *, int32_t, int, int, int, uint32_t, const double *, double, int, double *,
+                                 double *, int32_t *, double *, double *, double *, int32_t *, double *, double *)
+{
+    return FOKL_ERR_HIP;
+}
+
 // The device chain engine and page-locked memory do not exist in these builds: the native search (fokl_search.cpp) is
 // then created without an engine and falls back to ordinary memory for its tapes.
 extern "C" int fokl_host_alloc(size_t, void **out)

@@ -1,0 +1,61 @@
+// The random numbers of the embedded-GP sampler (fokl_embedded_device.inc, fokl_embedded.cpp): Philox 4x32-10, counter
+// based, so the kernel and the host statement draw the same numbers without sharing a state.  One header for both sides.
+//
+//   key     = (seed, chain)                  counter = (draw, purpose, index, 0)
+//   words   = philox4x32_10(counter, key)    -> two uniforms of 53 bits, u_a from words 0-1 and u_b from words 2-3
+//   uniform = u_a                            in [0, 1)
+//   normal  = sqrt(-2 ln(1 - u_a)) cos(2 pi u_b)          (Box-Muller, one normal per counter: 1 - u_a is in (0, 1])
+//
+// Nothing here touches numpy's global stream or the fit's MT19937 machinery.
+#ifndef FOKL_PHILOX_H
+#define FOKL_PHILOX_H
+
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define FOKL_HD __host__ __device__ inline
+#else
+#define FOKL_HD inline
+#endif
+
+namespace fokl {
+
+constexpr int EMB_PURPOSE_MOMENTUM = 0;   // the momentum of transition `draw`
+constexpr int EMB_PURPOSE_ACCEPT = 1;     // its accept uniform (index 0)
+constexpr int EMB_PURPOSE_SEARCH = 2;     // the momentum of the step search that runs at `draw` (0, or the mass update's)
+
+FOKL_HD void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
+{
+    for (int round = 0; round < 10; ++round) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0, c1 = n1, c2 = n2, c3 = n3;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
+FOKL_HD double emb_unit(uint32_t hi, uint32_t lo)
+{
+    return ((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+FOKL_HD double emb_uniform(uint32_t seed, uint32_t chain, uint32_t draw, uint32_t purpose, uint32_t index)
+{
+    uint32_t w[4];
+    philox4x32_10(draw, purpose, index, 0u, seed, chain, w);
+    return emb_unit(w[0], w[1]);
+}
+
+FOKL_HD double emb_normal(uint32_t seed, uint32_t chain, uint32_t draw, uint32_t purpose, uint32_t index)
+{
+    uint32_t w[4];
+    philox4x32_10(draw, purpose, index, 0u, seed, chain, w);
+    return sqrt(-2.0 * log(1.0 - emb_unit(w[0], w[1]))) * cos(6.283185307179586476925 * emb_unit(w[2], w[3]));
+}
+
+}  // namespace fokl
+
+#endif

@@ -13,6 +13,9 @@
  *                              a host chain's recursion in verified segments (the boundary's header is full)
  *   fokl_model_optimize        the multistart optimiser behind fokl_gpy_amd/optimize.py (the boundary's header is full)
  *   fokl_system_optimize       its constrained counterpart over a system of models (optimize.optimize_system)
+ *   fokl_embedded_hmc / fokl_embedded_rng
+ *                              the HMC chains of GPs embedded in a user equation (fokl_gpy_amd/embedded.py) and their
+ *                              counter-based random numbers as the host sees them
  *
  * Same conventions as fokl_hip.h (return codes, row-major fp64, FR = /root/reference/src/FoKL/FoKLRoutines.py).
  */
@@ -674,6 +677,51 @@ int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, const int32_t 
                          const int32_t *con_var, const double *con_par, int max_iter, double tol, double ctol, double *x,
                          double *f, double *violation, double *y, double *multipliers, int32_t *iterations,
                          int32_t *status);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Embedded GPs: HMC chains of GPs inside a traced equation (csrc/fokl_embedded_device.inc; embedded.py)     */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/*
+ * n_chains Hamiltonian Monte Carlo chains, ONE WORKGROUP PER CHAIN and the whole chain in one launch, of the model
+ *     data_i = equation(g_0i .. g_{K-1}i; columns) + noise,   g_k = X beta_k,   q = (beta_0 .. beta_{K-1}, ln sigma^2)
+ * over the dataset uploaded to the context (fokl_upload; data is FOKL_SLOT_Y).  X is the n_coef basis columns in
+ * term_slots (intercept first: FOKL_SLOT_ONES, then what fokl_build_terms built), shared by the K GPs.
+ *   col_slots [n_cols]     slots holding the equation's known columns (fokl_write_slot)
+ *   ops       [n_ops, 3]   the tape in single-assignment form: (opcode, a, b).  Opcodes 0 add, 1 sub, 2 mul, 3 div
+ *                          (binary); 4 neg, 5 exp, 6 log, 7 sqrt, 8 square, 9 reciprocal (unary, b ignored); 10 power
+ *                          with a constant exponent (b a constant).  An operand is (kind << 8) | index: kind 0 a value
+ *                          (index k < K is GP k, index K + o the result of operation o, which must precede its use),
+ *                          kind 1 column `index`, kind 2 constant `index`.
+ *   consts    [n_consts]   result: the operand (kind 0) that is the equation's value
+ *   q0        [n_chains, D] start states, D = K n_coef + 1, or NULL for all ones
+ *   eps0      > 0: the first step size (no step search at the start); 0: find_reasonable_epsilon
+ *   adapt     non-zero: the step size is rescaled every 50 draws by the window's acceptance count and the inverse mass
+ *             becomes the per-parameter variance of states 401 .. 500 after draw 500 (if 5 of those draws moved)
+ * Random numbers: Philox 4x32-10 keyed by (seed, chain), counter (draw, purpose, index) -- fokl_embedded_rng below.
+ * Outputs (host): states [n_chains, draws + 1, D] (row 0 the start), potential U and accept flags [n_chains, draws + 1],
+ * eps_hist [n_chains, draws / 50] the step size after every window, inv_mass [n_chains, D], eps_final [n_chains],
+ * status [n_chains, 2]: (0 ok | 1 no step: the capped step search found no finite step, the rest of the chain is NaN;
+ * 1 if the mass update fired).  Optional (may be NULL): grad0 [n_chains, D] dU/dq at the start, proposal
+ * [n_chains, D + 1] the last transition's proposal and its potential.
+ * The statement the kernel is tested against is embedded.full_sample_host.
+ * Limits (FOKL_ERR_ARG with a text, nothing is launched): K in 1 .. 8; n_cols <= 16; n_ops <= 32; n_consts <= 64;
+ * D <= 257; rows x n_coef <= 4 194 304 (all chains stream the same X from the last-level cache); n_chains <= 4096;
+ * draws <= 1 000 000; leapfrog in 1 .. 1000; a well-formed tape; slots in range.  The dataset, its slots and pending
+ * launches are left alone; per-chain scratch is allocated by the call and freed before it returns.  Blocking.
+ */
+int fokl_embedded_hmc(fokl_ctx *ctx, int n_gps, int n_coef, const int32_t *term_slots, int n_cols,
+                      const int32_t *col_slots, int n_ops, const int32_t *ops, int n_consts, const double *consts,
+                      int32_t result, int n_chains, int draws, int leapfrog, uint32_t seed, const double *q0, double eps0,
+                      int adapt, double *states, double *potential, int32_t *accepted, double *eps_hist, double *inv_mass,
+                      double *eps_final, int32_t *status, double *grad0, double *proposal);
+
+/*
+ * out[j], j < count: the numbers chain `chain` of a run seeded `seed` draws at `draw` for `purpose` -- 0 the momentum of
+ * transition `draw` (standard normals, one per parameter), 1 its accept uniform (j = 0), 2 the momentum of the step
+ * search that runs at `draw` (0 at the start, 500 after the mass update).  Host code, no device (csrc/fokl_philox.h).
+ */
+int fokl_embedded_rng(uint32_t seed, uint32_t chain, uint32_t draw, int purpose, int count, double *out);
 
 #ifdef __cplusplus
 }
