@@ -23,6 +23,7 @@ RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
 RESID_TERMS_LAYOUTS = ((8, 1), (16, 1), (8, 2), (4, 4), (2, 8), (8, 4), (16, 2), (4, 8))    # inputs x orders per input (csrc/fokl_hip.hip)
 SLOT_ONES, SLOT_Y, SLOT_FIRST_FREE = 0, 1, 2
+PREDICT_NONE, PREDICT_VALU_LDS, PREDICT_VALU_GLOBAL, PREDICT_MFMA = 0, 1, 2, 3     # fokl_predict_report's kernel ids
 
 c_int, c_i32, c_i64, c_dbl, c_vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
 
@@ -55,6 +56,7 @@ SIGNATURES = {
     'fokl_bic_resid_fetch': (c_int, [c_vp, c_vp, c_int]),
     'fokl_bic_resid_terms_launch': (c_int, [c_vp, c_vp, c_int, c_vp]),
     'fokl_predict': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp]),
+    'fokl_predict_report': (c_int, [c_vp, c_vp]),
     'fokl_read_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_write_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_timing_enable': (c_int, [c_vp, c_int]),
@@ -1879,6 +1881,16 @@ class DeviceContext:
         self._ck(self._lib.fokl_predict(self._h, _ptr(s), nc, _ptr(betas), draws, int(cut or 0), _ptr(mean),
                                         _ptr(bounds)))
         return (mean, bounds) if cut is not None else mean
+
+    def predict_report(self):
+        """What the last ``predict`` on this context ran (fokl_predict_report): ``kernel`` (PREDICT_*), ``wide`` (basis values
+        read from the columns, not from LDS), ``grid`` workgroups over ``tiles`` row tiles (16 rows on the matrix-pipe
+        kernel, 64 on the VALU kernel), and of the matrix-pipe kernel's ``tiles_done`` the ``tiles_fallback`` that went
+        through its exact fallback pass (both 0 for the VALU kernel).  PREDICT_NONE and zeros after a refused call."""
+        out = np.zeros(6, dtype=np.int64)
+        self._ck(self._lib.fokl_predict_report(self._h, _ptr(out)))
+        return dict(kernel=int(out[0]), wide=bool(out[1]), grid=int(out[2]), tiles=int(out[3]), tiles_done=int(out[4]),
+                    tiles_fallback=int(out[5]))
 
     def gp_integrate_ensemble(self, n_members, n_states, n_other, n_steps, betas, per_member, mtx, rows, cols, sources,
                               n_src, forcing, norms, table, n_basis, width, h, y0, cut=None, want_members=False):

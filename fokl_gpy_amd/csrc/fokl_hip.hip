@@ -92,6 +92,7 @@ struct fokl_ctx {
     size_t gram_pending = 0;            // doubles of the block fokl_gram_fetch will return; 0 = none on its way
     hipEvent_t gram_done = nullptr;
     hipEvent_t resid_done = nullptr;     // behind the residual pass's result copy: its fetch waits for this, not for what was queued after it
+    int64_t predict_report[6] = {0, 0, 0, 0, 0, 0};   // what the last fokl_predict call ran (fokl_predict_report)
 
     // timing
     bool timing = false;

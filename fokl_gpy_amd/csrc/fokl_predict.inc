@@ -13,7 +13,12 @@ constexpr int PR_MAX_K = 128;
 // GLOBAL_LISTS: the two sorted lists of a wavefront live in device memory (`lists`, (klo + khi) x 64 doubles per
 // workgroup) instead of LDS -- bounds over more than ~5 000 draws need the 128-th and later order statistics, more than
 // LDS holds next to the basis values.  Slow (every insertion shifts through L2) and rare; same arithmetic, same result.
-template <bool GLOBAL_LISTS>
+// GLOBAL_X: a model too wide for its rows' basis values to sit in LDS (about 300 terms) reads them from the columns
+// themselves, PR_XG at a time so that the loads travel together: once per group of four draws, i.e. once for the
+// mean-only call, out of L2 after that (64 rows x nc doubles per wavefront).  Same order of summation.
+constexpr int PR_XG = 8;
+
+template <bool GLOBAL_LISTS, bool GLOBAL_X>
 __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__restrict__ slot_ptr,
                                                              const int *__restrict__ slots, int nc,
                                                              const double *__restrict__ betas, int draws, int klo,
@@ -21,9 +26,10 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__re
                                                              double *__restrict__ bounds, double *__restrict__ lists)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    double *xrow = lds;                              // [nc][64]
+    double *xrow = lds;                              // [nc][64] (none with GLOBAL_X)
     // [klo][64] ascending: lo[klo-1] is the klo-th smallest so far; [khi][64] descending: hi[khi-1] the khi-th largest
-    double *lo = GLOBAL_LISTS ? lists + (size_t)blockIdx.x * (klo + khi) * PR_THREADS : xrow + (size_t)nc * PR_THREADS;
+    double *lo = GLOBAL_LISTS ? lists + (size_t)blockIdx.x * (klo + khi) * PR_THREADS
+                              : xrow + (GLOBAL_X ? 0 : (size_t)nc * PR_THREADS);
     double *hi = lo + (size_t)klo * PR_THREADS;
     const int lane = threadIdx.x;
     const bool want_bounds = bounds != nullptr;
@@ -31,8 +37,9 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__re
     for (int64_t base = (int64_t)blockIdx.x * PR_THREADS; base < n; base += (int64_t)gridDim.x * PR_THREADS) {
         const int64_t r = base + lane;
         const bool in = r < n;
-        for (int j = 0; j < nc; ++j)
-            xrow[j * PR_THREADS + lane] = in ? *(__attribute__((address_space(1))) const double *)(slot_ptr[slots[j]] + r) : 0.0;
+        if (!GLOBAL_X)
+            for (int j = 0; j < nc; ++j)
+                xrow[j * PR_THREADS + lane] = in ? *(__attribute__((address_space(1))) const double *)(slot_ptr[slots[j]] + r) : 0.0;
         if (want_bounds) {
             for (int k = 0; k < klo; ++k) lo[k * PR_THREADS + lane] = INFINITY;
             for (int k = 0; k < khi; ++k) hi[k * PR_THREADS + lane] = -INFINITY;
@@ -41,11 +48,33 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__re
         for (int d0 = 0; d0 < draws; d0 += 4) {
             double acc[4] = {0.0, 0.0, 0.0, 0.0};
             const int nd = min(4, draws - d0);
-            for (int j = 0; j < nc; ++j) {
-                const double xv = xrow[j * PR_THREADS + lane];
+            if (GLOBAL_X) {
+                const int64_t rx = in ? r : n - 1;           // a lane past the end reads the last row; it stores nothing
+                int j = 0;
+                for (; j + PR_XG <= nc; j += PR_XG) {
+                    double xg[PR_XG];
 #pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (q < nd) acc[q] = __builtin_fma(betas[(size_t)(d0 + q) * nc + j], xv, acc[q]);
+                    for (int u = 0; u < PR_XG; ++u)
+                        xg[u] = *(__attribute__((address_space(1))) const double *)(slot_ptr[slots[j + u]] + rx);
+#pragma unroll
+                    for (int u = 0; u < PR_XG; ++u)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            if (q < nd) acc[q] = __builtin_fma(betas[(size_t)(d0 + q) * nc + j + u], xg[u], acc[q]);
+                }
+                for (; j < nc; ++j) {
+                    const double xv = *(__attribute__((address_space(1))) const double *)(slot_ptr[slots[j]] + rx);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (q < nd) acc[q] = __builtin_fma(betas[(size_t)(d0 + q) * nc + j], xv, acc[q]);
+                }
+            } else {
+                for (int j = 0; j < nc; ++j) {
+                    const double xv = xrow[j * PR_THREADS + lane];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (q < nd) acc[q] = __builtin_fma(betas[(size_t)(d0 + q) * nc + j], xv, acc[q]);
+                }
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -94,7 +123,9 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__re
 // expected.  Those few are appended (no loop, so no divergence) to per-lane candidate buffers; afterwards every lane
 // sorts its handful and the four quarters of a row are merged up to the klo-th / khi-th value.  A row with too few
 // candidates, or a lane with more than PM_CAP, sends the tile through the exact fallback: the same pass with
-// per-lane sorted lists of the klo / khi best kept up to date draw by draw, merged the same way.
+// per-lane sorted lists of the klo / khi best kept up to date draw by draw, merged the same way.  What a launch did is
+// counted for fokl_predict_report: tally[0] += the tiles a wavefront processed (lane 0, once, at its end), tally[1] += 1
+// for a tile on its way into the fallback (lane 0; nothing is counted inside the filter pass itself).
 constexpr int PM_THREADS = 64;
 constexpr int PM_DT = 4;
 constexpr int PM_CAP = 32;
@@ -105,7 +136,8 @@ __global__ __launch_bounds__(PM_THREADS) void predict_mfma_kernel(double *const 
                                                                   const double *__restrict__ beta_mean,
                                                                   const double *__restrict__ beta_cov, double z,
                                                                   int klo, int khi, int64_t n,
-                                                                  double *__restrict__ mean, double *__restrict__ bounds)
+                                                                  double *__restrict__ mean, double *__restrict__ bounds,
+                                                                  unsigned long long *__restrict__ tally)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int cap = max(PM_CAP, max(klo, khi));      // rows of the two buffers (the fallback keeps klo / khi per lane)
@@ -114,8 +146,9 @@ __global__ __launch_bounds__(PM_THREADS) void predict_mfma_kernel(double *const 
     double *hi = lo + (size_t)cap * PM_THREADS;      // [cap][64]: candidates above, or the descending list
     const int lane = threadIdx.x, col = lane & 15, quad = lane >> 4;
     const int64_t n_tiles = (n + 15) / 16;
+    int64_t tile = blockIdx.x;
 
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    for (; tile < n_tiles; tile += gridDim.x) {
         const int64_t r = tile * 16 + col;
         const bool in = r < n;
         for (int k = quad; k < ncp; k += 4)
@@ -214,7 +247,10 @@ __global__ __launch_bounds__(PM_THREADS) void predict_mfma_kernel(double *const 
                     row_hi += c_hi[q];
                 }
                 const bool bad = in && (n_lo > PM_CAP || n_hi > PM_CAP || row_lo < klo || row_hi < khi);
-                if (__any(bad)) continue;                    // wave-uniform: the exact fallback for this tile
+                if (__any(bad)) {                            // wave-uniform: the exact fallback for this tile
+                    if (lane == 0) atomicAdd(&tally[1], 1ull);
+                    continue;
+                }
                 // sort my few candidates in place (ascending below, descending above), pad to the list length
                 for (int i = 1; i < n_lo; ++i) {
                     const double key = lo[i * PM_THREADS + lane];
@@ -285,14 +321,35 @@ __global__ __launch_bounds__(PM_THREADS) void predict_mfma_kernel(double *const 
         }
         __syncthreads();
     }
+    // the trips this wavefront's loop took, from where its tile index ended
+    if (lane == 0) atomicAdd(&tally[0], (unsigned long long)((tile - blockIdx.x) / gridDim.x));
 }
 
 }  // namespace fokl
+
+// What the last fokl_predict call on a context did (fokl_predict_report): which kernel, over what grid, and how many of
+// the matrix-pipe kernel's tiles took the exact fallback.  A call refused before its launch leaves kernel 0.
+static void predict_note(fokl_ctx *ctx, int kernel, bool wide, int64_t grid, int64_t tiles)
+{
+    ctx->predict_report[0] = kernel;
+    ctx->predict_report[1] = wide ? 1 : 0;
+    ctx->predict_report[2] = grid;
+    ctx->predict_report[3] = tiles;
+    ctx->predict_report[4] = ctx->predict_report[5] = 0;
+}
+
+extern "C" int fokl_predict_report(const fokl_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return fail(nullptr, FOKL_ERR_ARG, "fokl_predict_report: null argument");
+    std::memcpy(out, ctx->predict_report, sizeof ctx->predict_report);
+    return FOKL_OK;
+}
 
 extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, int draws, int cut,
                             double *mean, double *bounds)
 {
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, "fokl_predict: null context");
+    predict_note(ctx, FOKL_PREDICT_NONE, false, 0, 0);
     if (!ctx->have_data) return fail(ctx, FOKL_ERR_STATE, "fokl_predict: call fokl_upload first");
     if (nc <= 0 || draws <= 0 || !betas || !mean) return fail(ctx, FOKL_ERR_ARG, "fokl_predict: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -313,12 +370,15 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
     const bool use_mfma = bounds && draws >= 64 && lds_mfma <= 150 * 1024 && !(forced && std::strcmp(forced, "valu") == 0);
     if (use_mfma) {
         const size_t beta_off = ((size_t)nc * sizeof(int) + 7) & ~(size_t)7;
-        const size_t arg_bytes = beta_off + ((size_t)ncp * dp + ncp + (size_t)ncp * ncp) * sizeof(double);
+        // argument block: slots | betas' | their mean | their covariance | the kernel's two tile counts (zero on arrival)
+        const size_t arg_doubles = (size_t)ncp * dp + ncp + (size_t)ncp * ncp;
+        const size_t tally_off = beta_off + arg_doubles * sizeof(double);
+        const size_t arg_bytes = tally_off + 2 * sizeof(unsigned long long);
         rc = begin_args(ctx, arg_bytes);
         if (rc) return rc;
         std::memcpy(ctx->h_args, slots, (size_t)nc * sizeof(int));
         double *bt = reinterpret_cast<double *>(ctx->h_args + beta_off);
-        std::memset(bt, 0, ((size_t)ncp * dp + ncp + (size_t)ncp * ncp) * sizeof(double));
+        std::memset(bt, 0, arg_bytes - beta_off);
         for (int d = 0; d < draws; ++d)
             for (int k = 0; k < nc; ++k) bt[(size_t)k * dp + d] = betas[(size_t)d * nc + k];
         // mean and (population) covariance of the draws: the filter's model of a row's predictions
@@ -347,38 +407,55 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
         if (rc) return rc;
         double *d_res = nullptr;
         HIP_TRY(ctx, hipMalloc((void **)&d_res, n * 3 * sizeof(double)));
+        unsigned long long *d_tally = reinterpret_cast<unsigned long long *>(ctx->d_args + tally_off);
         const int64_t tiles = ((int64_t)n + 15) / 16;
         const int grid = (int)std::min<int64_t>(tiles, (int64_t)cu_count(ctx) * 16);
+        hipError_t le = hipSuccess;
+        if (lds_mfma > 64 * 1024)
+            le = hipFuncSetAttribute(reinterpret_cast<const void *>(predict_mfma_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+        if (le != hipSuccess) {
+            (void)hipFree(d_res);
+            return fail(ctx, FOKL_ERR_HIP, std::string("fokl_predict: ") + hipGetErrorString(le));
+        }
         {
             TimedRegion timed(ctx, FOKL_K_PREDICT, 8.0 * (double)n * (nc + 3), 2.0 * (double)n * nc * draws);
-            if (lds_mfma > 64 * 1024)
-                HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(predict_mfma_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
             hipLaunchKernelGGL(predict_mfma_kernel, dim3(grid), dim3(PM_THREADS), lds_mfma, ctx->stream,
                                ctx->d_slot_ptr, reinterpret_cast<const int *>(ctx->d_args), nc, ncp,
                                reinterpret_cast<const double *>(ctx->d_args + beta_off), draws, dp,
                                reinterpret_cast<const double *>(ctx->d_args + beta_off) + (size_t)ncp * dp,
                                reinterpret_cast<const double *>(ctx->d_args + beta_off) + (size_t)ncp * dp + ncp, z,
-                               klo, khi, ctx->n, d_res, d_res + n);
-            hipError_t le = hipGetLastError();
+                               klo, khi, ctx->n, d_res, d_res + n, d_tally);
+            le = hipGetLastError();
             if (le != hipSuccess) {
                 (void)hipFree(d_res);
                 return fail(ctx, FOKL_ERR_HIP, std::string("predict_mfma_kernel launch: ") + hipGetErrorString(le));
             }
         }
+        unsigned long long tally[2] = {0, 0};
         hipError_t e = hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess) e = hipMemcpy(mean, d_res, n * sizeof(double), hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(bounds, d_res + n, n * 2 * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(tally, d_tally, sizeof tally, hipMemcpyDeviceToHost);
         (void)hipFree(d_res);
         if (e != hipSuccess) return fail(ctx, FOKL_ERR_HIP, std::string("fokl_predict: ") + hipGetErrorString(e));
+        predict_note(ctx, FOKL_PREDICT_MFMA, false, grid, tiles);
+        ctx->predict_report[4] = (int64_t)tally[0];
+        ctx->predict_report[5] = (int64_t)tally[1];
         return FOKL_OK;
     }
 
     // the sorted lists of the order statistics move to device memory when they do not fit LDS next to the basis values
     // (bounds over more than ~5 000 draws: klo > PR_MAX_K) -- the reference sorts any number of draws per row (FR:971-977)
-    const bool global_lists = bounds && (klo > PR_MAX_K || (size_t)(nc + klo + khi) * PR_THREADS * sizeof(double) > 150 * 1024);
-    const size_t lds_bytes = (size_t)(nc + (global_lists ? 0 : klo + khi)) * PR_THREADS * sizeof(double);
-    if (lds_bytes > 150 * 1024) return fail(ctx, FOKL_ERR_ARG, "fokl_predict: model has too many terms for one LDS tile");
+    bool global_lists = bounds && (klo > PR_MAX_K || (size_t)(nc + klo + khi) * PR_THREADS * sizeof(double) > 150 * 1024);
+    size_t lds_bytes = (size_t)(nc + (global_lists ? 0 : klo + khi)) * PR_THREADS * sizeof(double);
+    // ... and a model whose basis values alone do not fit (about 300 terms) leaves them in the columns: LDS then holds the
+    // lists only, which fit whenever klo <= PR_MAX_K -- the reference evaluates a model of any width (FR:966-978)
+    const bool wide = lds_bytes > 150 * 1024;
+    if (wide) {
+        global_lists = bounds && klo > PR_MAX_K;
+        lds_bytes = bounds && !global_lists ? (size_t)(klo + khi) * PR_THREADS * sizeof(double) : 0;
+    }
 
     // argument block: slots | betas ; outputs: mean | bounds in a dedicated allocation
     const size_t beta_off = ((size_t)nc * sizeof(int) + 7) & ~(size_t)7;
@@ -394,7 +471,9 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
     HIP_TRY(ctx, hipMalloc((void **)&d_res, n * 3 * sizeof(double)));
     double *d_mean = d_res, *d_bounds = bounds ? d_res + n : nullptr;
     const int64_t row_blocks = ((int64_t)n + PR_THREADS - 1) / PR_THREADS;
-    const int grid = (int)std::min<int64_t>(row_blocks, (int64_t)cu_count(ctx) * (global_lists ? 4 : 8));
+    // wavefronts per CU: what LDS admits once the basis values are not in it, enough of them to hide the columns' latency
+    const int per_cu = global_lists ? 4 : !wide ? 8 : (int)std::min<size_t>(32, 160 * 1024 / std::max<size_t>(lds_bytes, 1));
+    const int grid = (int)std::min<int64_t>(row_blocks, (int64_t)cu_count(ctx) * per_cu);
     double *d_lists = nullptr;
     if (global_lists) {
         hipError_t ea = hipMalloc((void **)&d_lists, (size_t)grid * (klo + khi) * PR_THREADS * sizeof(double));
@@ -404,16 +483,19 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
         }
     }
     {
-        TimedRegion timed(ctx, FOKL_K_PREDICT, 8.0 * (double)n * (nc + 3), 2.0 * (double)n * nc * draws);
-        auto fn = global_lists ? predict_kernel<true> : predict_kernel<false>;
+        auto fn = wide ? (global_lists ? predict_kernel<true, true> : predict_kernel<false, true>)
+                       : (global_lists ? predict_kernel<true, false> : predict_kernel<false, false>);
+        hipError_t e = hipSuccess;
         if (lds_bytes > 64 * 1024)
-            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(PR_THREADS), lds_bytes, ctx->stream, ctx->d_slot_ptr,
-                           reinterpret_cast<const int *>(ctx->d_args), nc,
-                           reinterpret_cast<const double *>(ctx->d_args + beta_off), draws, klo, khi, ctx->n, d_mean,
-                           d_bounds, d_lists);
-        hipError_t e = hipGetLastError();
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+        if (e == hipSuccess) {
+            TimedRegion timed(ctx, FOKL_K_PREDICT, 8.0 * (double)n * (nc + 3), 2.0 * (double)n * nc * draws);
+            hipLaunchKernelGGL(fn, dim3(grid), dim3(PR_THREADS), lds_bytes, ctx->stream, ctx->d_slot_ptr,
+                               reinterpret_cast<const int *>(ctx->d_args), nc,
+                               reinterpret_cast<const double *>(ctx->d_args + beta_off), draws, klo, khi, ctx->n, d_mean,
+                               d_bounds, d_lists);
+            e = hipGetLastError();
+        }
         if (e != hipSuccess) {
             (void)hipFree(d_res);
             if (d_lists) (void)hipFree(d_lists);
@@ -426,5 +508,6 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
     if (e == hipSuccess && bounds) e = hipMemcpy(bounds, d_bounds, n * 2 * sizeof(double), hipMemcpyDeviceToHost);
     (void)hipFree(d_res);
     if (e != hipSuccess) return fail(ctx, FOKL_ERR_HIP, std::string("fokl_predict: ") + hipGetErrorString(e));
+    predict_note(ctx, global_lists ? FOKL_PREDICT_VALU_GLOBAL : FOKL_PREDICT_VALU_LDS, wide, grid, row_blocks);
     return FOKL_OK;
 }

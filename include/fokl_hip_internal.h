@@ -13,6 +13,8 @@
  *                              a host chain's recursion in verified segments (the boundary's header is full)
  *   fokl_model_optimize        the multistart optimiser behind fokl_gpy_amd/optimize.py (the boundary's header is full)
  *   fokl_system_optimize       its constrained counterpart over a system of models (optimize.optimize_system)
+ *   fokl_predict_report        which kernel the last fokl_predict call ran, over what grid, and how many of its tiles took
+ *                              the exact fallback (the boundary's header is full)
  *   fokl_embedded_hmc / fokl_embedded_rng
  *                              the HMC chains of GPs embedded in a user equation (fokl_gpy_amd/embedded.py) and their
  *                              counter-based random numbers as the host sees them
@@ -722,6 +724,33 @@ int fokl_embedded_hmc(fokl_ctx *ctx, int n_gps, int n_coef, const int32_t *term_
  * search that runs at `draw` (0 at the start, 500 after the mass update).  Host code, no device (csrc/fokl_philox.h).
  */
 int fokl_embedded_rng(uint32_t seed, uint32_t chain, uint32_t draw, int purpose, int count, double *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* What a prediction ran (csrc/fokl_predict.inc)                                                             */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/* out[0] of fokl_predict_report */
+enum {
+    FOKL_PREDICT_NONE = 0,        /* no call yet, or the last one was refused or failed: nothing to report */
+    FOKL_PREDICT_VALU_LDS = 1,    /* predict_kernel, order-statistic lists in LDS (or none: mean only) */
+    FOKL_PREDICT_VALU_GLOBAL = 2, /* predict_kernel, lists in device memory (klo > 128, or no room next to the basis values) */
+    FOKL_PREDICT_MFMA = 3         /* predict_mfma_kernel */
+};
+
+/*
+ * The last fokl_predict call on `ctx`, out [6] (host):
+ *   out[0]  the kernel it launched (above); a call that returned an error leaves FOKL_PREDICT_NONE and zeros
+ *   out[1]  1 if the model was too wide for its rows' basis values to sit in LDS and the VALU kernel read them from the
+ *           columns (about 300 terms and more), else 0
+ *   out[2]  the launch's grid (workgroups = wavefronts)
+ *   out[3]  the row tiles it covered: 16-row tiles of predict_mfma_kernel, 64-row blocks of predict_kernel; more tiles
+ *           than workgroups means the kernel's grid-stride loop went round again
+ *   out[4]  tiles predict_mfma_kernel counted as processed (= out[3] if every one was visited once), 0 for predict_kernel
+ *   out[5]  those among them whose filter pass did not yield the bounds and which went through the exact fallback pass
+ *           (same numbers at about a third of the speed), 0 for predict_kernel
+ * Host values and two device counters copied back with the results: no launch, no synchronisation of its own.
+ */
+int fokl_predict_report(const fokl_ctx *ctx, int64_t *out);
 
 #ifdef __cplusplus
 }

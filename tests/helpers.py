@@ -17,6 +17,27 @@ GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 from oracle import fokl_oracle as O  # noqa: E402
 from fokl_gpy_amd import getKernels, _capi  # noqa: E402
 
+_PHIS = {}
+
+
+def upload(ctx, x, y, kid):
+    """Dataset (x, y) to the device context with kernel ``kid``'s coefficient table; -> that table."""
+    if kid not in _PHIS:
+        _PHIS[kid] = (getKernels.table_to_phis(np.load(os.path.join(GOLDEN, 'spline_phis.npz'))['table'])
+                      if kid == O.KERNEL_SPLINES else getKernels.bernoulli())
+    packed, nb, width = getKernels.pack_phis(_PHIS[kid], kid)
+    ctx.upload(x, y, kid, packed, nb, width)
+    return _PHIS[kid]
+
+
+def load_columns(ctx, cols):
+    """Columns [n, k] into the slots 2 .. 2 + k - 1 of the uploaded dataset."""
+    n, k = cols.shape
+    ctx.reserve_slots(2 + k)
+    for j in range(k):
+        ctx.write_slot(2 + j, cols[:, j])
+
+
 FIT_CASES = ['bern_m1', 'bern_m3', 'bern_m3_gimmie_tol1', 'bern_m4_way3', 'bern_m6', 'bern_m8_capped',
              'testdata10_default', 'testdata10_changed', 'splines_m4', 'sigmoid_splines']
 

@@ -13,7 +13,7 @@ import warnings
 import numpy as np
 import pytest
 
-from helpers import GOLDEN, FIT_CASES, load_case
+from helpers import GOLDEN, FIT_CASES, load_case, upload, load_columns
 from fokl_gpy_amd import _capi, getKernels, FoKLRoutines, engine
 from oracle import fokl_oracle as O
 
@@ -21,13 +21,6 @@ pytestmark = pytest.mark.gpu
 
 BERN = getKernels.bernoulli()
 SPL = getKernels.table_to_phis(np.load(os.path.join(GOLDEN, 'spline_phis.npz'))['table'])
-
-
-def upload(ctx, x, y, kid):
-    phis = SPL if kid == O.KERNEL_SPLINES else BERN
-    packed, nb, width = getKernels.pack_phis(phis, kid)
-    ctx.upload(x, y, kid, packed, nb, width)
-    return phis
 
 
 def build_and_read(ctx, terms):
@@ -171,13 +164,6 @@ def test_argument_errors_are_reported(device_ctx):
 # ---------------------------------------------------------------------------------------------------------
 # K2 Gram, K3 residual, predict
 # ---------------------------------------------------------------------------------------------------------
-
-def load_columns(ctx, cols):
-    n, k = cols.shape
-    ctx.reserve_slots(2 + k)
-    for j in range(k):
-        ctx.write_slot(2 + j, cols[:, j])
-
 
 def dev_kernels_built(ctx):
     """The retired Gram kernels (round-1 panels = path 3, 4x4x4 tile lists, third LDS-DMA buffer) are compiled only into
@@ -463,6 +449,10 @@ def test_predict_bounds_when_the_draws_are_far_from_gaussian(device_ctx):
     skew = np.exp(2.0 * rng.standard_normal((draws, 7)))
     for betas in (wild, same, skew):
         mean, bounds = device_ctx.predict(sl, betas, cut)
+        ran = device_ctx.predict_report()
+        assert ran['kernel'] == _capi.PREDICT_MFMA and ran['tiles_done'] == ran['tiles'] == (n + 15) // 16
+        if betas is not skew:
+            assert ran['tiles_fallback'] == ran['tiles'], ran        # the claim above, through the kernel's own count
         mod = X @ betas.T
         srt = np.sort(mod, axis=1)
         scale = np.abs(mod).max(axis=1) + 1e-300
