@@ -24,6 +24,10 @@ RESID_TERMS_MAX_ORDER = 8
 RESID_TERMS_LAYOUTS = ((8, 1), (16, 1), (8, 2), (4, 4), (2, 8), (8, 4), (16, 2), (4, 8))    # inputs x orders per input (csrc/fokl_hip.hip)
 SLOT_ONES, SLOT_Y, SLOT_FIRST_FREE = 0, 1, 2
 PREDICT_NONE, PREDICT_VALU_LDS, PREDICT_VALU_GLOBAL, PREDICT_MFMA = 0, 1, 2, 3     # fokl_predict_report's kernel ids
+# fokl_fit_report's kernel names, by id: Gram / residual / basis launch
+GRAM_KERNELS = ('none', 'valu', 'tiles', 'dma', 'panel', 'tiles4')
+RESID_KERNELS = ('none', 'columns', 'matrix_free')
+BASIS_KERNELS = ('none', 'reg_table', 'lds_table')
 
 c_int, c_i32, c_i64, c_dbl, c_vp = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
 
@@ -57,6 +61,7 @@ SIGNATURES = {
     'fokl_bic_resid_terms_launch': (c_int, [c_vp, c_vp, c_int, c_vp]),
     'fokl_predict': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp]),
     'fokl_predict_report': (c_int, [c_vp, c_vp]),
+    'fokl_fit_report': (c_int, [c_vp, c_int, c_vp, c_int]),
     'fokl_read_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_write_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_timing_enable': (c_int, [c_vp, c_int]),
@@ -1891,6 +1896,50 @@ class DeviceContext:
         self._ck(self._lib.fokl_predict_report(self._h, _ptr(out)))
         return dict(kernel=int(out[0]), wide=bool(out[1]), grid=int(out[2]), tiles=int(out[3]), tiles_done=int(out[4]),
                     tiles_fallback=int(out[5]))
+
+    def _fit_report(self, which, count):
+        out = np.zeros(count, dtype=np.int64)
+        self._ck(self._lib.fokl_fit_report(self._h, which, _ptr(out), count))
+        return [int(v) for v in out]
+
+    def gram_report(self):
+        """What the last ``gram`` / ``gram_launch`` on this context ran (fokl_fit_report): ``kernel`` ('valu', 'tiles' = the
+        k-split teams of gram_tiles_kernel, 'dma' = gram_tiles_dma_kernel; development builds also 'panel', 'tiles4'), its
+        template arguments ``nt8`` (tiles per wavefront), ``half``, ``loaders``, ``lds_buffers``, ``ks``, ``depth``, the
+        ``rows_per_chunk``, the plan's ``groups``, ``ct``, ``nt``, the LDS-DMA ``pieces`` and ``lds_bytes``, the row cut ``S``
+        and the ``chunks_per_workgroup`` of the busiest workgroup (above 1: its chunk loop went round), ``nr_pad``,
+        ``nc_pad``, the ``slabs`` reduced ``reduce_epb`` elements per block, ``row_tiles``, ``col_tiles`` and the ``lanes``
+        per workgroup.  'none' and zeros after a refused call."""
+        keys = ('kernel', 'nt8', 'half', 'loaders', 'lds_buffers', 'ks', 'depth', 'rows_per_chunk', 'groups', 'ct', 'nt',
+                'pieces', 'lds_bytes', 'S', 'chunks_per_workgroup', 'nr_pad', 'nc_pad', 'slabs', 'reduce_epb', 'row_tiles',
+                'col_tiles', 'lanes')
+        ran = dict(zip(keys, self._fit_report(0, len(keys))))
+        ran['kernel'], ran['half'] = GRAM_KERNELS[ran['kernel']], bool(ran['half'])
+        return ran
+
+    def resid_report(self):
+        """What the last residual pass launched on this context ran: ``kernel`` ('columns' = resid_kernel over stored
+        columns, 'matrix_free'), ``columns`` (matrix-free: terms), ``batches`` of 256 columns (above 1: the column table
+        is reloaded per row tile), ``grid`` workgroups over ``row_tiles`` tiles of 512 rows (more tiles than workgroups:
+        the tile loop went round), and the matrix-free ``layout`` (inputs x orders per input), ``order_class``, ``inputs``.
+        'none' and zeros after a refused launch."""
+        v = self._fit_report(1, 9)
+        return dict(kernel=RESID_KERNELS[v[0]], columns=v[1], batches=v[2], grid=v[3], row_tiles=v[4], layout=(v[5], v[6]),
+                    order_class=v[7], inputs=v[8])
+
+    def basis_report(self):
+        """What the last ``build_terms`` / ``build_terms_deriv`` on this context ran: the ``launches`` it split into, how
+        many of them took the ``lds_table`` kernel, and ``first``, ``last``, ``last_lds`` = dict(kernel ('reg_table',
+        'lds_table'), splines, lanes, factors, slabs, grid, row_tiles) of those launches ('none' and zeros where there was
+        none).  Zero launches after a refused call."""
+        v = self._fit_report(2, 23)
+        keys = ('kernel', 'splines', 'lanes', 'factors', 'slabs', 'grid', 'row_tiles')
+
+        def one(rec):
+            d = dict(zip(keys, rec))
+            d['kernel'], d['splines'] = BASIS_KERNELS[d['kernel']], bool(d['splines'])
+            return d
+        return dict(launches=v[0], lds_table=v[1], first=one(v[2:9]), last=one(v[9:16]), last_lds=one(v[16:23]))
 
     def gp_integrate_ensemble(self, n_members, n_states, n_other, n_steps, betas, per_member, mtx, rows, cols, sources,
                               n_src, forcing, norms, table, n_basis, width, h, y0, cut=None, want_members=False):

@@ -93,6 +93,11 @@ struct fokl_ctx {
     hipEvent_t gram_done = nullptr;
     hipEvent_t resid_done = nullptr;     // behind the residual pass's result copy: its fetch waits for this, not for what was queued after it
     int64_t predict_report[6] = {0, 0, 0, 0, 0, 0};   // what the last fokl_predict call ran (fokl_predict_report)
+    // what the last Gram block, residual pass and fokl_build_terms call ran (fokl_fit_report): host values noted while
+    // enqueuing, zeros after a call that was refused or failed
+    int64_t gram_report[FOKL_GRAM_REPORT_LEN] = {};
+    int64_t resid_report[FOKL_RESID_REPORT_LEN] = {};
+    int64_t basis_report[FOKL_BASIS_REPORT_LEN] = {};
 
     // timing
     bool timing = false;
@@ -745,6 +750,18 @@ static int launch_basis(fokl_ctx *ctx, const int32_t *terms, const int32_t *slot
     hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds_bytes, ctx->stream, ctx->d_x, ctx->ld, ctx->n, ctx->d_phis,
                        ctx->width, d_plan, d_arr, ctx->d_slot_ptr, deriv);
     HIP_TRY(ctx, hipGetLastError());
+    {
+        // fokl_fit_report: this launch as the call's first (once), its last, and its last LDS-table launch
+        const int64_t rec[7] = {reg_table ? FOKL_BASIS_REG_TABLE : FOKL_BASIS_LDS_TABLE, splines ? 1 : 0, threads, U, NS,
+                                grid, n_tiles};
+        int64_t *rep = ctx->basis_report;
+        if (rep[0]++ == 0) std::memcpy(rep + 2, rec, sizeof rec);
+        std::memcpy(rep + 9, rec, sizeof rec);
+        if (!reg_table) {
+            rep[1] += 1;
+            std::memcpy(rep + 16, rec, sizeof rec);
+        }
+    }
     return FOKL_OK;
 }
 
@@ -774,6 +791,7 @@ extern "C" int fokl_build_terms_deriv(fokl_ctx *ctx, const int32_t *terms, int T
 static int build_terms_impl(fokl_ctx *ctx, const int32_t *terms, int T, const int32_t *slots, const DerivSpec &deriv)
 {
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, "fokl_build_terms: null context");
+    std::memset(ctx->basis_report, 0, sizeof ctx->basis_report);         // launch_basis notes what runs
     if (!ctx->have_data) return fail(ctx, FOKL_ERR_STATE, "fokl_build_terms: call fokl_upload first");
     if (T < 0 || (T > 0 && (!terms || !slots))) return fail(ctx, FOKL_ERR_ARG, "fokl_build_terms: null pointer");
     if (T == 0) return FOKL_OK;
@@ -804,7 +822,9 @@ static int build_terms_impl(fokl_ctx *ctx, const int32_t *terms, int T, const in
     for (int j = 0; j < T; ++j) {
         int nz = 0;
         for (int k = 0; k < m; ++k) nz += terms[(size_t)j * m + k] != 0;
-        if (nz > max_fac) max_fac = std::min(nz, lds_fac);
+        // (refused here, before the terms in front of it are launched: a refused call builds nothing)
+        if (nz > lds_fac) return fail(ctx, FOKL_ERR_ARG, "fokl_build_terms: a single term has more factors than fit in LDS");
+        if (nz > max_fac) max_fac = nz;
     }
     int begin = 0;
     while (begin < T) {
@@ -820,10 +840,12 @@ static int build_terms_impl(fokl_ctx *ctx, const int32_t *terms, int T, const in
             for (auto &p : add) seen[p] = 1;
             ++end;
         }
-        if (end == begin)
-            return fail(ctx, FOKL_ERR_ARG, "fokl_build_terms: a single term has more factors than fit in LDS");
-        rc = launch_basis(ctx, terms, slots, begin, end, deriv);
-        if (rc) return rc;
+        if (end == begin) rc = fail(ctx, FOKL_ERR_ARG, "fokl_build_terms: a single term has more factors than fit in LDS");
+        if (!rc) rc = launch_basis(ctx, terms, slots, begin, end, deriv);
+        if (rc) {
+            std::memset(ctx->basis_report, 0, sizeof ctx->basis_report);
+            return rc;
+        }
         begin = end;
     }
     return FOKL_OK;
@@ -1238,6 +1260,8 @@ extern "C" int fokl_gram_plan(const int32_t *row_slots, int nr, const int32_t *c
 static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const int32_t *col_slots, int nc, int path,
                         int allreduce, bool aside)
 {
+    std::memset(ctx->gram_report, 0, sizeof ctx->gram_report);     // fokl_fit_report: filled when everything is enqueued
+    int64_t rep[FOKL_GRAM_REPORT_LEN] = {};
     if (!ctx->have_data) return fail(ctx, FOKL_ERR_STATE, "fokl_gram: call fokl_upload first");
     if (nr <= 0 || nc <= 0) return fail(ctx, FOKL_ERR_ARG, "fokl_gram: empty block");
     if (path < 0 || path > 3) return fail(ctx, FOKL_ERR_ARG, "fokl_gram: path must be 0, 1, 2 or 3");
@@ -1352,6 +1376,8 @@ static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const i
             S = (int)std::max<int64_t>(1, std::min<int64_t>(n_chunks, target));
             rc = ensure_slab(ctx, (size_t)S * nr_pad * nc_pad);
             if (rc) return rc;
+            rep[0] = FOKL_GRAM_TILES4, rep[1] = pl.nt, rep[7] = 32, rep[12] = (int64_t)lds, rep[21] = G4S_THREADS;
+            rep[14] = (n_chunks + S - 1) / S;
             TimedRegion timed(ctx, gram_slot, bytes, flops);      // brackets the Gram kernel only
             hipLaunchKernelGGL(fn, dim3(S, (unsigned)pl.groups.size()), dim3(G4S_THREADS), lds, ctx->stream,
                                ctx->d_slot_ptr, d_icols, pl.nci, d_groups, pl.ct, ctx->n, ctx->d_slab, nr_pad, nc_pad,
@@ -1402,6 +1428,8 @@ static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const i
             rc = ensure_slab(ctx, (size_t)S * nr_pad * nc_pad);
             if (rc) return rc;
             const uint32_t zero_units = (uint32_t)((reinterpret_cast<uintptr_t>(ctx->d_zero) - reinterpret_cast<uintptr_t>(grid_base)) >> 8);
+            rep[0] = FOKL_GRAM_DMA, rep[1] = (pl.nt + 1) / 2, rep[3] = loaders, rep[4] = nbuf, rep[7] = 32, rep[11] = pieces;
+            rep[12] = (int64_t)lds, rep[14] = (n_chunks + S - 1) / S, rep[21] = GD_THREADS + 64 * loaders;
             TimedRegion timed(ctx, gram_slot, bytes, flops);      // brackets the Gram kernel only
             hipLaunchKernelGGL(fn, dim3(S, (unsigned)pl.groups.size()), dim3(GD_THREADS + 64 * loaders), lds, ctx->stream,
                                d_groups, pl.ct, pieces, ctx->n, ctx->d_slab, nr_pad, nc_pad, grid_base, zero_units);
@@ -1422,6 +1450,8 @@ static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const i
             S = (int)std::max<int64_t>(1, std::min<int64_t>(n_chunks, target));
             rc = ensure_slab(ctx, (size_t)S * pl.ks * nr_pad * nc_pad);
             if (rc) return rc;
+            rep[0] = FOKL_GRAM_TILES, rep[1] = pl.nt, rep[7] = R, rep[12] = (int64_t)lds, rep[21] = GT_THREADS;
+            rep[14] = (n_chunks + S - 1) / S;
             TimedRegion timed(ctx, gram_slot, bytes, flops);      // brackets the Gram kernel only
             hipLaunchKernelGGL(fn, dim3(S, (unsigned)pl.groups.size()), dim3(GT_THREADS), lds, ctx->stream,
                                ctx->d_slot_ptr, d_icols, pl.nci, d_groups, pl.ct, pl.rb_shift, ctx->n, ctx->d_slab,
@@ -1435,6 +1465,9 @@ static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const i
                                ctx->d_slab, S * pl.ks, nr, nc, nr_pad, nc_pad, epb, d_perm, d_dst);
         }
         HIP_TRY(ctx, hipGetLastError());
+        rep[2] = pl.half ? 1 : 0, rep[5] = pl.ks, rep[6] = pl.depth, rep[8] = (int64_t)pl.groups.size(), rep[9] = pl.ct;
+        rep[10] = pl.nt, rep[13] = S, rep[15] = nr_pad, rep[16] = nc_pad, rep[17] = (int64_t)S * pl.ks, rep[18] = epb;
+        rep[19] = pl.it, rep[20] = pl.jt;
     } else {
         const size_t arg_bytes = (size_t)(nr + nc) * sizeof(int);
         rc = begin_args(ctx, arg_bytes);
@@ -1479,6 +1512,7 @@ static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const i
             const int target = std::max(1, (per_cu * cus) / (gz * gy));
             S = (int)std::max<int64_t>(1, std::min<int64_t>(n_chunks, target));
             grid = dim3(S, gy, gz);
+            rep[0] = FOKL_GRAM_PANEL, rep[7] = GM_R, rep[8] = gy * gz, rep[14] = (n_chunks + S - 1) / S, rep[21] = GM_THREADS;
         } else {
 #endif
             const int gz = (nr + GV_TI - 1) / GV_TI, gy = (nc + GV_TJ - 1) / GV_TJ;
@@ -1488,7 +1522,10 @@ static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const i
             const int target = std::max(1, (8 * cus) / (gz * gy));
             S = (int)std::max<int64_t>(1, std::min<int64_t>(n_row_blocks, target));
             grid = dim3(S, gy, gz);
+            rep[0] = FOKL_GRAM_VALU, rep[7] = GV_THREADS * 2, rep[8] = gy * gz, rep[14] = (n_row_blocks + S - 1) / S;
+            rep[21] = GV_THREADS;
         }
+        rep[5] = rep[6] = 1, rep[13] = rep[17] = S, rep[15] = nr_pad, rep[16] = nc_pad, rep[18] = epb;
         rc = ensure_slab(ctx, (size_t)S * nr_pad * nc_pad);
         if (rc) return rc;
         {
@@ -1518,6 +1555,7 @@ static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const i
         if (rc) return rc;
     }
     HIP_TRY(ctx, hipMemcpyAsync(h_dst, d_dst, (size_t)nr * nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    std::memcpy(ctx->gram_report, rep, sizeof rep);
     return FOKL_OK;
 }
 
@@ -1580,6 +1618,7 @@ extern "C" int fokl_gram_fetch(fokl_ctx *ctx, double *out, int64_t count)
 extern "C" int fokl_bic_resid_launch(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betahat)
 {
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, "fokl_bic_resid_launch: null context");
+    std::memset(ctx->resid_report, 0, sizeof ctx->resid_report);     // fokl_fit_report: filled when the pass is enqueued
     if (!ctx->have_data) return fail(ctx, FOKL_ERR_STATE, "fokl_bic_resid_launch: call fokl_upload first");
     if (nc <= 0 || !betahat) return fail(ctx, FOKL_ERR_ARG, "fokl_bic_resid_launch: empty model or null pointer");
     if (ctx->resid_pending) return fail(ctx, FOKL_ERR_STATE, "fokl_bic_resid_launch: previous launch not fetched");
@@ -1618,6 +1657,10 @@ extern "C" int fokl_bic_resid_launch(fokl_ctx *ctx, const int32_t *slots, int nc
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rout, ctx->d_rout, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->resid_done, ctx->stream));
     ctx->resid_pending = true;
+    {
+        const int64_t rep[FOKL_RESID_REPORT_LEN] = {FOKL_RESID_COLUMNS, nc, (nc + RS_BATCH - 1) / RS_BATCH, S, n_row_blocks};
+        std::memcpy(ctx->resid_report, rep, sizeof rep);
+    }
     return FOKL_OK;
 }
 
@@ -1641,6 +1684,7 @@ static const ResidQuadLayout kResidQuadLayouts[] = {FOKL_RQ_LAYOUT(8, 1), FOKL_R
 extern "C" int fokl_bic_resid_terms_launch(fokl_ctx *ctx, const int32_t *terms, int n_terms, const double *betahat)
 {
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, "fokl_bic_resid_terms_launch: null context");
+    std::memset(ctx->resid_report, 0, sizeof ctx->resid_report);     // fokl_fit_report: filled when the pass is enqueued
     if (!ctx->have_data) return fail(ctx, FOKL_ERR_STATE, "fokl_bic_resid_terms_launch: call fokl_upload first");
     if (n_terms < 0 || !betahat || (n_terms > 0 && !terms))
         return fail(ctx, FOKL_ERR_ARG, "fokl_bic_resid_terms_launch: null pointer");
@@ -1755,6 +1799,11 @@ extern "C" int fokl_bic_resid_terms_launch(fokl_ctx *ctx, const int32_t *terms, 
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rout, ctx->d_rout, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->resid_done, ctx->stream));
     ctx->resid_pending = true;
+    {
+        const int64_t rep[FOKL_RESID_REPORT_LEN] = {FOKL_RESID_MATRIX_FREE, n_terms, 0, S, n_row_blocks, GM, KM,
+                                                    splines ? 0 : top_order <= 2 ? 2 : top_order <= 4 ? 4 : RT_MAX_ORDER, G};
+        std::memcpy(ctx->resid_report, rep, sizeof rep);
+    }
     return FOKL_OK;
 }
 
@@ -1785,6 +1834,19 @@ extern "C" int fokl_bic_resid(fokl_ctx *ctx, const int32_t *slots, int nc, const
     int rc = fokl_bic_resid_launch(ctx, slots, nc, betahat);
     if (rc) return rc;
     return fokl_bic_resid_fetch(ctx, out, allreduce);
+}
+
+// What the last Gram block, residual pass or fokl_build_terms call on a context ran: the values its launcher noted.
+extern "C" int fokl_fit_report(const fokl_ctx *ctx, int which, int64_t *out, int count)
+{
+    if (!ctx || !out || count < 0) return fail(nullptr, FOKL_ERR_ARG, "fokl_fit_report: null argument");
+    const int64_t *src = which == FOKL_REPORT_GRAM ? ctx->gram_report : which == FOKL_REPORT_RESID ? ctx->resid_report
+                         : which == FOKL_REPORT_BASIS ? ctx->basis_report : nullptr;
+    const int len = which == FOKL_REPORT_GRAM ? FOKL_GRAM_REPORT_LEN : which == FOKL_REPORT_RESID ? FOKL_RESID_REPORT_LEN
+                                                                                                  : FOKL_BASIS_REPORT_LEN;
+    if (!src) return fail(nullptr, FOKL_ERR_ARG, "fokl_fit_report: which must be FOKL_REPORT_GRAM, _RESID or _BASIS");
+    std::memcpy(out, src, (size_t)std::min(count, len) * sizeof(int64_t));
+    return FOKL_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------

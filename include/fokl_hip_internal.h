@@ -15,6 +15,8 @@
  *   fokl_system_optimize       its constrained counterpart over a system of models (optimize.optimize_system)
  *   fokl_predict_report        which kernel the last fokl_predict call ran, over what grid, and how many of its tiles took
  *                              the exact fallback (the boundary's header is full)
+ *   fokl_fit_report            the same for the fit's kernels: which Gram instance, residual branch and basis kernels the
+ *                              last launches ran, with their launch parameters
  *   fokl_embedded_hmc / fokl_embedded_rng
  *                              the HMC chains of GPs embedded in a user equation (fokl_gpy_amd/embedded.py) and their
  *                              counter-based random numbers as the host sees them
@@ -751,6 +753,51 @@ enum {
  * Host values and two device counters copied back with the results: no launch, no synchronisation of its own.
  */
 int fokl_predict_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* What the fit kernels ran: K1 basis build, K2 Gram block, K3 residual moments (csrc/fokl_hip.hip)          */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/* `which` of fokl_fit_report and the length of each report */
+enum { FOKL_REPORT_GRAM = 0, FOKL_REPORT_RESID = 1, FOKL_REPORT_BASIS = 2 };
+#define FOKL_GRAM_REPORT_LEN 24
+#define FOKL_RESID_REPORT_LEN 10
+#define FOKL_BASIS_REPORT_LEN 24
+/* out[0] of the Gram report */
+enum {
+    FOKL_GRAM_NONE = 0,     /* no block yet, or the last call was refused or failed */
+    FOKL_GRAM_VALU = 1,     /* gram_valu_kernel + reduce_slabs_kernel (path 1; blocks of at most 64 elements) */
+    FOKL_GRAM_TILES = 2,    /* gram_tiles_kernel + reduce_slabs_sym_kernel: the k-split teams of blocks of one or two tiles */
+    FOKL_GRAM_DMA = 3,      /* gram_tiles_dma_kernel + reduce_slabs_sym_kernel: every other block */
+    FOKL_GRAM_PANEL = 4,    /* gram_mfma_kernel (path 3; development builds) */
+    FOKL_GRAM_TILES4 = 5    /* gram_tiles4s_kernel (development builds) */
+};
+/* out[0] of the residual report; a basis launch's kernel */
+enum { FOKL_RESID_NONE = 0, FOKL_RESID_COLUMNS = 1, FOKL_RESID_MATRIX_FREE = 2 };
+enum { FOKL_BASIS_NONE = 0, FOKL_BASIS_REG_TABLE = 1, FOKL_BASIS_LDS_TABLE = 2 };
+
+/*
+ * What the last launch of a kind on `ctx` ran, out [count] (host; the report's first `count` values):
+ * FOKL_REPORT_GRAM, of the last fokl_gram / fokl_gram_launch:
+ *   out[0]  the kernel (above)             out[1]  its NT: tiles per wavefront (LDS-DMA: ordinary tiles, NT8)
+ *   out[2]  1 = half-tile slots (HALF)     out[3]  loader wavefronts (LW)         out[4]  LDS buffers (0: not LDS-DMA)
+ *   out[5]  ks: wavefronts per tile        out[6]  depth: chunks in flight        out[7]  rows per chunk
+ *   out[8]  groups (gridDim.y)             out[9]  ct: staged column tiles        out[10] nt: ordinary entries per list
+ *   out[11] LDS-DMA pieces per buffer      out[12] dynamic LDS bytes              out[13] the row cut S (gridDim.x)
+ *   out[14] chunks the busiest workgroup walks, ceil(chunks / S): above 1 the chunk loop went round
+ *   out[15] nr_pad   out[16] nc_pad        out[17] slabs the reduction summed     out[18] its elements per block
+ *   out[19] row tiles   out[20] column tiles of the internal order   out[21] lanes per workgroup
+ * FOKL_REPORT_RESID, of the last fokl_bic_resid_launch / fokl_bic_resid_terms_launch (and the calls built on them):
+ *   out[0]  stored columns or matrix-free  out[1]  columns (matrix-free: terms)   out[2]  batches of RS_BATCH columns: above
+ *           1 the table is reloaded per row tile     out[3]  grid     out[4]  row tiles: above the grid the tile loop went round
+ *   out[5], out[6]  the matrix-free layout GM x KM   out[7]  its order class (2, 4, 8; 0: splines)   out[8]  its inputs
+ * FOKL_REPORT_BASIS, of the last fokl_build_terms / fokl_build_terms_deriv:
+ *   out[0]  launches it split into         out[1]  those that ran the LDS-table kernel
+ *   out[2 + 7 r ..], r = 0 the first launch, 1 the last, 2 the last LDS-table launch (zeros: there was none):
+ *           kernel (above), 1 = splines, lanes per workgroup, distinct factors, spline slabs in LDS, grid, row tiles
+ * A call that was refused or failed leaves zeros.  Host values noted while enqueuing: no launch, no synchronisation.
+ */
+int fokl_fit_report(const fokl_ctx *ctx, int which, int64_t *out, int count);
 
 #ifdef __cplusplus
 }

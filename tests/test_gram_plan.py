@@ -75,6 +75,29 @@ KINDS = _kinds()
 
 SHAPES = [(1, 1), (2, 3), (8, 10), (16, 16), (17, 33), (28, 38), (56, 58), (56, 66), (65, 131), (70, 150), (56, 176),
           (33, 40), (48, 48), (200, 60), (120, 300)]
+# the widths models have today (586, 768 and 1000 columns): 12 to 16 staged column tiles per group, ten tiles per list, up
+# to 24 groups and 16 row tiles (four bands of four) -- the plans tests/test_fit_kernels_device.py runs on the device
+WIDE_SHAPES = [(1, 1000), (8, 1000), (24, 768), (32, 150), (48, 150), (40, 180), (48, 586), (72, 768), (100, 586), (104, 300),
+               (160, 768), (200, 202), (256, 1000)]
+
+
+@pytest.mark.parametrize('nr,nc', WIDE_SHAPES)
+def test_wide_tile_lists_reproduce_the_block(nr, nc):
+    """The search's pattern and a disjoint column list at the wide shapes, on 20-bit integers (64 rows: exact in double)."""
+    rng = np.random.default_rng(nr * 1000 + nc)
+    n, pool = 64, nr + nc + 4
+    cols = rng.integers(-2 ** 20 + 1, 2 ** 20, size=(n, pool)).astype(np.float64)
+    rs = (2 + rng.permutation(pool - 2)[:nr]).astype(np.int32)
+    rest = np.setdiff1d(np.arange(2, pool), rs)
+    search = np.concatenate([[0], rest[:nc - nr - 2], rs, [1]]).astype(np.int32)
+    assert search.shape[0] == nc
+    seen = dict(ct=0, nt=0)
+    for cs in (search, rest[:nc].astype(np.int32), rng.integers(0, pool, nc).astype(np.int32)):
+        out, pl = replay(cols, rs, cs)
+        assert np.array_equal(out, cols[:, rs].T @ cols[:, cs])
+        seen = dict(ct=max(seen['ct'], pl['ct']), nt=max(seen['nt'], pl['nt']))
+    if nc >= 586:
+        assert seen['ct'] >= 14 and (seen['nt'] >= 9 or nr <= 24)
 
 
 @pytest.mark.parametrize('nr,nc', SHAPES)
