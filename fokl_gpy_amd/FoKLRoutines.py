@@ -33,6 +33,7 @@ from . import _capi
 from . import engine as _engine
 from . import update as _update
 from . import optimize as _optimize
+from . import population as _population
 
 
 def _column_min_max(a):
@@ -1278,6 +1279,32 @@ class FoKL:
                 kwargs[name] = getattr(self, name)
         kwargs.setdefault('device', self._backend())
         return _optimize.optimize(phis=self.phis, minmax=self.minmax, kernel=self.kernel, **kwargs)
+
+    def propagate(self, inputs=None, data=None, clean=False, **kwargs):
+        """What the fitted model does over a POPULATION of inputs, for every posterior draw at once on the device (the
+        transpose of ``evaluate``, which reduces over the draws for every row): ``population.propagate`` with this
+        model's ``betas``, ``mtx``, ``phis`` and ``kernel`` (pass ``betas`` / ``mtx`` to override), which documents the
+        keywords -- data, thresholds, quantiles, passes, sensitivity, draws, ReturnBounds -- and the result.  ``inputs``
+        [S, M] default to the model's own; ``clean=True`` normalises them with the model's ``minmax`` exactly as
+        ``evaluate`` does.  ``draws=None`` uses all rows of ``betas``, an integer the last ``draws`` rows, in order: numpy's
+        random stream is not consumed and ``setnos`` is left alone."""
+        for name in ('betas', 'mtx'):
+            if kwargs.get(name) is None:
+                kwargs[name] = getattr(self, name)
+        if inputs is None:
+            if _str_to_bool(clean):
+                warnings.warn("Cleaning was already performed on default 'inputs', so overriding 'clean' to False.",
+                              category=UserWarning)
+            inputs = self.inputs
+        elif _str_to_bool(clean):
+            if not hasattr(self, 'minmax'):
+                raise ValueError("propagate(clean=True) needs the model's minmax (set by clean / fit, or model.minmax = "
+                                 "[[min, max], ...])")
+            kwargs_to_clean = dict(_CLEAN_DEFAULTS)
+            kwargs_to_clean['minmax'] = self.minmax
+            inputs = self.clean(inputs, kwargs_from_other=kwargs_to_clean)
+        kwargs.setdefault('device', self._backend())
+        return _population.propagate(phis=self.phis, kernel=self.kernel, inputs=inputs, data=data, **kwargs)
 
     def to_pyomo(self, *args, **kwargs):
         raise NotImplementedError("to_pyomo (FR:1796-1805) is outside the scope of this build")

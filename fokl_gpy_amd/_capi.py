@@ -18,12 +18,15 @@ K_BASIS, K_GRAM, K_RESID, K_PREDICT, K_RESID_MF, K_GRAM_MFMA, K_GRAM_REDUCE = 0,
 K_INTEGRATE, K_BAND = 7, 8
 K_OPTIMIZE = 9
 K_OPTIMIZE_SYSTEM = 10
+K_POPULATION = 11
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
 RESID_TERMS_LAYOUTS = ((8, 1), (16, 1), (8, 2), (4, 4), (2, 8), (8, 4), (16, 2), (4, 8))    # inputs x orders per input (csrc/fokl_hip.hip)
 SLOT_ONES, SLOT_Y, SLOT_FIRST_FREE = 0, 1, 2
 PREDICT_NONE, PREDICT_VALU_LDS, PREDICT_VALU_GLOBAL, PREDICT_MFMA = 0, 1, 2, 3     # fokl_predict_report's kernel ids
+POPULATION_COEFFICIENTS = ('none', 'registers', 'table')      # fokl_population_report: where the draw coefficients lived
+POPULATION_MAX_CUTS = 32
 # fokl_fit_report's kernel names, by id: Gram / residual / basis launch
 GRAM_KERNELS = ('none', 'valu', 'tiles', 'dma', 'panel', 'tiles4')
 RESID_KERNELS = ('none', 'columns', 'matrix_free')
@@ -62,6 +65,8 @@ SIGNATURES = {
     'fokl_predict': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp]),
     'fokl_predict_report': (c_int, [c_vp, c_vp]),
     'fokl_fit_report': (c_int, [c_vp, c_int, c_vp, c_int]),
+    'fokl_population_stats': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    'fokl_population_report': (c_int, [c_vp, c_vp]),
     'fokl_read_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_write_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_timing_enable': (c_int, [c_vp, c_int]),
@@ -1896,6 +1901,40 @@ class DeviceContext:
         self._ck(self._lib.fokl_predict_report(self._h, _ptr(out)))
         return dict(kernel=int(out[0]), wide=bool(out[1]), grid=int(out[2]), tiles=int(out[3]), tiles_done=int(out[4]),
                     tiles_fallback=int(out[5]))
+
+    def population_stats(self, slots, betas, shift, cuts=None, with_data=False):
+        """fokl_population_stats over the uploaded rows: the columns ``slots`` times every row of ``betas`` [E, nc], reduced
+        over the ROWS per draw -> (moments [E, 6] = sum(y - c), sum((y - c)^2), min, max, sum(e), sum(e^2) with c = ``shift``
+        [E] and e = the uploaded y - y (zeros without ``with_data``), above [E, K] int64 = rows with y > ``cuts`` [E, K],
+        K <= 32).  Two calls with the same arguments return the same bits."""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        if betas.ndim != 2 or betas.shape[1] != s.shape[0]:
+            raise ValueError("betas columns must match the slot list")
+        E = betas.shape[0]
+        shift = np.ascontiguousarray(shift, dtype=np.float64)
+        cuts = np.zeros((E, 0)) if cuts is None else np.ascontiguousarray(cuts, dtype=np.float64)
+        if shift.shape != (E,) or cuts.ndim != 2 or cuts.shape[0] != E or cuts.shape[1] > POPULATION_MAX_CUTS:
+            raise ValueError("population_stats: one shift and at most 32 cut points per draw")
+        K = cuts.shape[1]
+        moments = np.empty((E, 6), dtype=np.float64)
+        above = np.zeros((E, K), dtype=np.int64)
+        self._ck(self._lib.fokl_population_stats(self._h, _ptr(s), s.shape[0], _ptr(betas), E, _ptr(shift),
+                                                 _ptr(cuts) if K else None, K, int(bool(with_data)), _ptr(moments),
+                                                 _ptr(above) if K else None))
+        return moments, above
+
+    def population_report(self):
+        """What the last ``population_stats`` on this context ran (fokl_population_report): ``coefficients`` ('registers':
+        a wavefront kept its draws' coefficients for the whole launch; 'table': read one k-step ahead, models wider than 128
+        columns), the ``grid`` of workgroups = ``chunks`` (rounded up to 8) x ``draw_blocks`` of 128 draws,
+        ``tiles_per_chunk`` of the ``row_tiles`` 16-row tiles, ``lds_bytes`` and the ``pieces`` the columns were walked in.
+        'none' and zeros after a refused call."""
+        out = np.zeros(8, dtype=np.int64)
+        self._ck(self._lib.fokl_population_report(self._h, _ptr(out)))
+        v = [int(x) for x in out]
+        return dict(coefficients=POPULATION_COEFFICIENTS[v[0]], grid=v[1], draw_blocks=v[2], chunks=v[3],
+                    tiles_per_chunk=v[4], row_tiles=v[5], lds_bytes=v[6], pieces=v[7])
 
     def _fit_report(self, which, count):
         out = np.zeros(count, dtype=np.int64)

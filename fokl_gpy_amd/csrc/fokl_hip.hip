@@ -93,6 +93,7 @@ struct fokl_ctx {
     hipEvent_t gram_done = nullptr;
     hipEvent_t resid_done = nullptr;     // behind the residual pass's result copy: its fetch waits for this, not for what was queued after it
     int64_t predict_report[6] = {0, 0, 0, 0, 0, 0};   // what the last fokl_predict call ran (fokl_predict_report)
+    int64_t population_report[FOKL_POPULATION_REPORT_LEN] = {};   // ... and the last fokl_population_stats call
     // what the last Gram block, residual pass and fokl_build_terms call ran (fokl_fit_report): host values noted while
     // enqueuing, zeros after a call that was refused or failed
     int64_t gram_report[FOKL_GRAM_REPORT_LEN] = {};
@@ -1923,6 +1924,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_chain_device.inc"
 #include "fokl_spectral_device.inc"
 #include "fokl_predict.inc"
+#include "fokl_population.inc"
 #include "fokl_integrate_device.inc"
 #include "fokl_probe.inc"
 #include "fokl_dgemm_device.inc"

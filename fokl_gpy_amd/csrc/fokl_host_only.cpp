@@ -74,6 +74,15 @@ extern "C" int fokl_embedded_hmc(fokl_ctx *, int, int, const int32_t *, int, con
     return FOKL_ERR_HIP;
 }
 
+// A population through every posterior draw runs on the device only (fokl_population.inc); its statement is
+// population.propagate_host.
+extern "C" int fokl_population_stats(fokl_ctx *, const int32_t *, int, const double *, int, const double *, const double *,
+                                     int, int, double *, int64_t *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_population_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // The device chain engine and page-locked memory do not exist in these builds: the native search (fokl_search.cpp) is
 // then created without an engine and falls back to ordinary memory for its tapes.
 extern "C" int fokl_host_alloc(size_t, void **out)

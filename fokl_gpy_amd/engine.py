@@ -214,6 +214,12 @@ class HipBackend:
     def predict(self, slots, betas, cut=None):
         return self.ctx.predict(slots, betas, cut)
 
+    def population_stats(self, slots, betas, shift, cuts=None, with_data=False):
+        return self.ctx.population_stats(slots, betas, shift, cuts, with_data)
+
+    def population_report(self):
+        return self.ctx.population_report()
+
 
 class SlotPool:
     """Free list of device column slots (slot 0 = ones, slot 1 = y are never handed out)."""

@@ -51,7 +51,8 @@ extern "C" {
 #define FOKL_K_BAND    8        /* ... and its mean / order-statistic launches (bytes = points read)                  */
 #define FOKL_K_OPTIMIZE 9       /* the multistart optimiser's launch (fokl_hip_internal.h: fokl_model_optimize)        */
 #define FOKL_K_OPTIMIZE_SYSTEM 10 /* the constrained system optimiser's launches (fokl_hip_internal.h: fokl_system_optimize) */
-#define FOKL_K_COUNT   11
+#define FOKL_K_POPULATION 11    /* propagate(): X * beta^T reduced over the rows per draw (fokl_hip_internal.h: fokl_population_stats) */
+#define FOKL_K_COUNT   12
 
 typedef struct fokl_ctx fokl_ctx;
 

@@ -15,6 +15,9 @@
  *   fokl_system_optimize       its constrained counterpart over a system of models (optimize.optimize_system)
  *   fokl_predict_report        which kernel the last fokl_predict call ran, over what grid, and how many of its tiles took
  *                              the exact fallback (the boundary's header is full)
+ *   fokl_population_stats / fokl_population_report
+ *                              a population of inputs through every posterior draw, reduced over the rows per draw
+ *                              (fokl_gpy_amd/population.py), and what its last launch ran
  *   fokl_fit_report            the same for the fit's kernels: which Gram instance, residual branch and basis kernels the
  *                              last launches ran, with their launch parameters
  *   fokl_embedded_hmc / fokl_embedded_rng
@@ -753,6 +756,48 @@ enum {
  * Host values and two device counters copied back with the results: no launch, no synchronisation of its own.
  */
 int fokl_predict_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* A population through every posterior draw (csrc/fokl_population.inc; fokl_gpy_amd/population.py)          */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/* out[0] of fokl_population_report: where a wavefront's draw coefficients lived */
+enum {
+    FOKL_POPULATION_NONE = 0,      /* no call yet, or the last one was refused or failed */
+    FOKL_POPULATION_REGISTERS = 1, /* in registers for the whole launch (at most 128 columns, padded to 4) */
+    FOKL_POPULATION_TABLE = 2      /* read from the transposed table one k-step ahead (wider models) */
+};
+#define FOKL_POPULATION_REPORT_LEN 8
+#define FOKL_POPULATION_MAX_CUTS 32
+
+/*
+ * The transpose of fokl_predict: y[row][d] = sum_k column(slots[k])[row] * betas[d][k] over the uploaded rows, reduced
+ * over the ROWS for every draw d (fokl_predict reduces over the draws for every row).  Host memory, row-major:
+ *   slots [nc], betas [draws, nc]   as for fokl_predict; any nc >= 1, any draws >= 1
+ *   shift [draws]                   c_d, a value near draw d's mean: the second moment is accumulated about it
+ *   cuts  [draws, n_cuts]           per-draw cut points, 0 <= n_cuts <= FOKL_POPULATION_MAX_CUTS (may be NULL if 0)
+ *   with_data                       non-zero: also the residuals e = data - y against the uploaded y (FOKL_SLOT_Y)
+ * Outputs:
+ *   moments_out [draws, 6]          sum(y - c), sum((y - c)^2), min y, max y, sum(e), sum(e^2) (the last two 0 without data)
+ *   above_out   [draws, n_cuts]     the number of rows with y > cuts[d][k], strictly (may be NULL if n_cuts is 0)
+ * One launch of population_kernel on v_mfma_f64_16x16x4_f64 (a lane keeps the accumulators of one draw in registers;
+ * each (row chunk, draw) leaves one record) and one of population_reduce_kernel, which adds the records in the order
+ * of the chunks: no floating-point atomics, the same arguments give the same bits.  y itself is never stored.
+ * Kernel time: FOKL_K_POPULATION (both launches).  Blocking.
+ */
+int fokl_population_stats(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, int draws,
+                          const double *shift, const double *cuts, int n_cuts, int with_data, double *moments_out,
+                          int64_t *above_out);
+
+/*
+ * The last fokl_population_stats call on `ctx`, out [FOKL_POPULATION_REPORT_LEN] (host):
+ *   out[0]  where the coefficients lived (above); zeros after a call that returned an error
+ *   out[1]  the grid (workgroups of 8 wavefronts = 128 draws): row chunks, rounded up to 8, x draw blocks
+ *   out[2]  draw blocks     out[3]  row chunks with rows     out[4]  16-row tiles per chunk     out[5]  row tiles
+ *   out[6]  dynamic LDS bytes     out[7]  pieces the columns were walked in per tile (above 1: more than 1024 columns)
+ * Host values noted while enqueuing: no launch, no synchronisation.
+ */
+int fokl_population_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* What the fit kernels ran: K1 basis build, K2 Gram block, K3 residual moments (csrc/fokl_hip.hip)          */
