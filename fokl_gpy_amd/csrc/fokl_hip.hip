@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -618,8 +619,27 @@ extern "C" int fokl_download_inputs(fokl_ctx *ctx, double *x_out)
 // Compute units of the device: every launch plan sizes its grid for this number.
 static int cu_count(fokl_ctx *ctx) { return ctx->cus > 0 ? ctx->cus : 256; }
 
-static int env_int(const char *name, int fallback);
-static int dev_int(const char *name, int fallback);
+static int env_int(const char *name, int fallback)
+{
+    const char *v = std::getenv(name);
+    return v && *v ? std::atoi(v) : fallback;
+}
+
+// Knobs that select between measured variants of a kernel (A/B runs: docs/LAB_NOTEBOOK.md).  The defaults are the product's
+// configuration, the one the `-m gpu` suite covers, and all the product library ever sees; a development build (make DEV=1)
+// lays the environment over them, anew for every call (fokl_gram_dev.inc).
+struct LaunchKnobs {
+    int path = 2, mfma4 = 0, dma = 2, half = 1, bufs = 2, loaders = 4, rb = 1, depth = 1, wgs = 3;     // FOKL_GRAM_<NAME>
+    int k1_wgs = INT_MAX;                     // FOKL_K1_WGS: cap on the basis kernel's workgroups per CU
+    int tiles4_nt = 0, tiles4_ct = 0;         // list limits of the 4x4x4 tile kernel (plan kind 1); 0: not in this build
+    // half-tile slots need the LDS-DMA kernel: asked for only where it runs every block
+    bool half_slots() const { return mfma4 != 2 && dma == 2 && half != 0; }
+};
+#ifdef FOKL_DEV_KERNELS
+static LaunchKnobs launch_knobs();
+#else
+static LaunchKnobs launch_knobs() { return LaunchKnobs(); }
+#endif
 
 // LDS available to one workgroup of the basis kernel; the factor table takes 4 KB per distinct factor.
 static constexpr size_t K1_LDS_BUDGET = 144 * 1024;
@@ -721,7 +741,7 @@ static int launch_basis(fokl_ctx *ctx, const int32_t *terms, const int32_t *slot
     const int64_t tile_rows = (int64_t)threads * K1_ROWS_PER_THREAD;
     const int64_t n_tiles = (ctx->n + tile_rows - 1) / tile_rows;
     int per_cu = (int)std::max<size_t>(1, std::min<size_t>(reg_table ? 5 : 16, (160 * 1024) / std::max<size_t>(lds_bytes, 1)));
-    per_cu = std::min(per_cu, std::max(1, dev_int("FOKL_K1_WGS", per_cu)));
+    per_cu = std::min(per_cu, launch_knobs().k1_wgs);
     const int grid = (int)std::min<int64_t>(n_tiles, (int64_t)cu_count(ctx) * per_cu);
     const BasisPlan *d_plan = reinterpret_cast<const BasisPlan *>(ctx->d_args);
     const int *d_arr = reinterpret_cast<const int *>(ctx->d_args + plan_bytes);
@@ -879,49 +899,6 @@ static int blocks_per_cu(F fn, int threads, size_t dyn_lds)
     return std::min(nb, 8);
 }
 
-#ifdef FOKL_DEV_KERNELS
-// One instantiation per tile configuration; the dispatcher below picks the smallest that covers the block.
-typedef void (*gram_mfma_fn)(double *const *, const int *, int, const int *, int, int64_t, double *, int, int,
-                             const double *);
-
-template <int TJ>
-static gram_mfma_fn pick_isplit()
-{
-    return gram_mfma_kernel<4, TJ, true>;
-}
-
-static gram_mfma_fn isplit_kernel(int tj)
-{
-    switch (tj) {
-        case 1: return pick_isplit<1>();
-        case 2: return pick_isplit<2>();
-        case 3: return pick_isplit<3>();
-        case 4: return pick_isplit<4>();
-        case 5: return pick_isplit<5>();
-        case 6: return pick_isplit<6>();
-        case 7: return pick_isplit<7>();
-        case 8: return pick_isplit<8>();
-        case 9: return pick_isplit<9>();
-        case 10: return pick_isplit<10>();
-        case 11: return pick_isplit<11>();
-        default: return pick_isplit<12>();
-    }
-}
-
-static gram_mfma_fn jsplit_kernel(int ti, int tj)
-{
-    if (ti == 1) {
-        if (tj == 1) return gram_mfma_kernel<1, 1, false>;
-        if (tj == 2) return gram_mfma_kernel<1, 2, false>;
-        return gram_mfma_kernel<1, 3, false>;
-    }
-    if (tj == 1) return gram_mfma_kernel<2, 1, false>;
-    if (tj == 2) return gram_mfma_kernel<2, 2, false>;
-    return gram_mfma_kernel<2, 3, false>;
-}
-
-#endif  // FOKL_DEV_KERNELS
-
 // ---- tile-list Gram (gram_tiles_kernel): launch planning ---------------------------------------------------
 
 struct GramPlan {
@@ -934,38 +911,15 @@ struct GramPlan {
     std::vector<GramGroup> groups;
 };
 
-static int env_int(const char *name, int fallback)
-{
-    const char *v = std::getenv(name);
-    return v && *v ? std::atoi(v) : fallback;
-}
-
-// Knobs that select between measured variants of a kernel (A/B runs: docs/LAB_NOTEBOOK.md) exist in development builds
-// only (make DEV=1): the product library runs one configuration, the one the `-m gpu` suite covers.
-static int dev_int(const char *name, int fallback)
-{
-#ifdef FOKL_DEV_KERNELS
-    return env_int(name, fallback);
-#else
-    (void)name;
-    return fallback;
-#endif
-}
-
 // Internal column order, tile groups and kernel parameters for an nr x nc block (see gram_tiles_kernel).  Pure host
 // arithmetic: fokl_gram_plan exposes it to the CPU tests, which replay the lists with numpy.
-static void plan_gram(const int32_t *row_slots, int nr, const int32_t *col_slots, int nc, int kind, GramPlan &pl,
-                      bool allow_half = false)
+static void plan_gram(const int32_t *row_slots, int nr, const int32_t *col_slots, int nc, int kind, const LaunchKnobs &knobs,
+                      GramPlan &pl)
 {
     pl.kind = kind;
     pl.waves = 4;
-#ifdef FOKL_DEV_KERNELS
-    const int nt_max = kind == 1 ? G4S_MAX_NT : GT_MAX_NT;
-    const int ct_max = kind == 1 ? G4S_MAX_CT : GT_MAX_CT;
-#else
-    const int nt_max = GT_MAX_NT, ct_max = GT_MAX_CT;
-    (void)kind;
-#endif
+    const int nt_max = kind == 1 ? knobs.tiles4_nt : GT_MAX_NT;
+    const int ct_max = kind == 1 ? knobs.tiles4_ct : GT_MAX_CT;
     pl.icols.assign(row_slots, row_slots + nr);
     pl.perm.resize(nc);
     {
@@ -1033,10 +987,9 @@ static void plan_gram(const int32_t *row_slots, int nr, const int32_t *col_slots
     pl.nt = (most_tiles + teams - 1) / teams;
     pl.ct = most_staged;
     // rows per chunk: as many sub-chunks of 32 rows as the 16 staging passes and FOKL_GRAM_RB allow
-    const int rb_cap = std::max(1, std::min(16, dev_int("FOKL_GRAM_RB", 1)));
     pl.rb_shift = 0;
-    while (kind == 0 && (pl.ct << (pl.rb_shift + 1)) <= GT_MAX_PASS && (2 << pl.rb_shift) <= rb_cap) ++pl.rb_shift;
-    pl.depth = kind == 0 && pl.nt <= 4 ? std::max(1, std::min(2, dev_int("FOKL_GRAM_DEPTH", 1))) : 1;
+    while (kind == 0 && (pl.ct << (pl.rb_shift + 1)) <= GT_MAX_PASS && (2 << pl.rb_shift) <= knobs.rb) ++pl.rb_shift;
+    pl.depth = kind == 0 && pl.nt <= 4 ? knobs.depth : 1;
 
     // Half-tile slots (gram_tiles_dma_kernel<NT, NBUF, true>): when 1 .. 8 of the 16 columns of the last row tile are
     // row-side columns, a tile of that row tile costs the matrix pipe half a tile if it is formed as 8 x 16.  Entries 0
@@ -1044,7 +997,7 @@ static void plan_gram(const int32_t *row_slots, int nr, const int32_t *col_slots
     // ordinary tiles follow from entry 2 and go to the list with the least work so far (ordinary tile = 2, half = 1).
     // Only if every group keeps within 8 ordinary entries per list; the caller says whether the kernel is the one to run.
     // (not for a single row tile: such blocks are HBM-bound and only pay for the extra slot: 8 x 40 measured 57 -> 65 us)
-    const int ragged = allow_half && kind == 0 && pl.ks == 1 && pl.it >= 2 && nr % 16 >= 1 && nr % 16 <= 8 ? pl.it - 1 : -1;
+    const int ragged = knobs.half_slots() && kind == 0 && pl.ks == 1 && pl.it >= 2 && nr % 16 >= 1 && nr % 16 <= 8 ? pl.it - 1 : -1;
     const int normal_cap = GT_MAX_NT - 2;
     pl.half = ragged >= 0;
     for (const Cut &c : cuts) {
@@ -1121,107 +1074,42 @@ static const double *slot_grid_base(fokl_ctx *ctx)
     return reinterpret_cast<const double *>(lo);
 }
 
-// Instantiations: NT = 1..4 (HBM-bound shapes) for P = 4, 8, 16 staging passes and one or two chunks in flight, the
-// k-split teams (NT = 1) likewise; NT = 5..10 (MFMA-bound) for P = 16, one chunk in flight.
-template <int NT, int P>
-static gram_tiles_fn tiles_kernel_np(int depth, int ks)
+// A launcher asked for an instantiation its table does not hold refuses the call; it never substitutes another one.
+static int no_instance(fokl_ctx *ctx, const char *kernel, const GramPlan &pl)
 {
-    if (NT == 1 && ks == 4) return depth == 2 ? gram_tiles_kernel<1, P, 2, 4> : gram_tiles_kernel<1, P, 1, 4>;
-    if (NT == 1 && ks == 2) return depth == 2 ? gram_tiles_kernel<1, P, 2, 2> : gram_tiles_kernel<1, P, 1, 2>;
-    if (depth == 2) return gram_tiles_kernel<NT, P, 2, 1>;
-    return gram_tiles_kernel<NT, P, 1, 1>;
+    return fail(ctx, FOKL_ERR_ARG, std::string("fokl_gram: this library holds no ") + kernel + " for nt " + std::to_string(pl.nt) +
+                                       ", ct " + std::to_string(pl.ct << pl.rb_shift) + ", depth " + std::to_string(pl.depth));
 }
 
-template <int NT>
-static gram_tiles_fn tiles_kernel_n(int passes, int depth, int ks)
+// gram_tiles_kernel as the product launches it: the k-split teams of a block of one tile (ks 4) or two (ks 2) -- one tile per
+// wavefront on at most four staged column tiles, 32 rows per chunk, one chunk in flight (tests/test_gram_plan.py sweeps the
+// planner for exactly this).  Every other form is an A/B route of development builds (fokl_gram_dev.inc).
+static gram_tiles_fn ksplit_kernel(const GramPlan &pl)
 {
-    if (passes <= 4) return tiles_kernel_np<NT, 4>(depth, ks);
-    if (passes <= 8) return tiles_kernel_np<NT, 8>(depth, ks);
-    return tiles_kernel_np<NT, 16>(depth, ks);
+    if (pl.nt != 1 || pl.ct > 4 || pl.rb_shift != 0 || pl.depth != 1) return nullptr;
+    return pl.ks == 4 ? gram_tiles_kernel<1, 4, 1, 4> : pl.ks == 2 ? gram_tiles_kernel<1, 4, 1, 2> : nullptr;
 }
-
-static gram_tiles_fn tiles_kernel(int nt, int passes, int depth, int ks)
-{
-    switch (nt) {
-        case 1: return tiles_kernel_n<1>(passes, depth, ks);
-        case 2: return tiles_kernel_n<2>(passes, depth, ks);
-        case 3: return tiles_kernel_n<3>(passes, depth, ks);
-        case 4: return tiles_kernel_n<4>(passes, depth, ks);
-        case 5: return gram_tiles_kernel<5, 16, 1, 1>;
-        case 6: return gram_tiles_kernel<6, 16, 1, 1>;
-        case 7: return gram_tiles_kernel<7, 16, 1, 1>;
-        case 8: return gram_tiles_kernel<8, 16, 1, 1>;
-        case 9: return gram_tiles_kernel<9, 16, 1, 1>;
-        default: return gram_tiles_kernel<10, 16, 1, 1>;
-    }
-}
-
-#ifdef FOKL_DEV_KERNELS
-typedef void (*gram_tiles4_fn)(double *const *, const int *, int, const GramGroup *, int, int64_t, double *, int, int,
-                               const double *, const double *);
-
-template <int NT>
-static gram_tiles4_fn tiles4s_kernel_n(int passes)
-{
-    if (passes <= 2) return gram_tiles4s_kernel<NT, 2>;
-    if (passes <= 4) return gram_tiles4s_kernel<NT, 4>;
-    if (passes <= 6) return gram_tiles4s_kernel<NT, 6>;
-    return gram_tiles4s_kernel<NT, 8>;
-}
-
-static gram_tiles4_fn tiles4s_kernel(int nt, int passes)
-{
-    switch (nt) {
-        case 1: return tiles4s_kernel_n<1>(passes);
-        case 2: return tiles4s_kernel_n<2>(passes);
-        case 3: return tiles4s_kernel_n<3>(passes);
-        default: return tiles4s_kernel_n<4>(passes);
-    }
-}
-
-#endif  // FOKL_DEV_KERNELS
 
 typedef void (*gram_dma_fn)(const GramGroup *, int, int, int64_t, double *, int, int, const double *, uint32_t);
+typedef gram_dma_fn (*gram_dma_picker)(int nt8, bool half, int nbuf, int loaders);
 
-// nt8: ordinary tiles per wavefront (1 .. 5; with half-tile slots 1 .. 4 + the slot); LW: loader wavefronts (0, 2, 4)
+// nt8: ordinary tiles per wavefront (1 .. 5; with half-tile slots 1 .. 4 + the slot); LW: loader wavefronts
 template <int NBUF, int LW>
 static gram_dma_fn tiles_dma_kernel_b(int nt8, bool half)
 {
-    if (half) {
-        switch (nt8) {
-            case 1: return gram_tiles_dma_kernel<1, NBUF, true, LW>;
-            case 2: return gram_tiles_dma_kernel<2, NBUF, true, LW>;
-            case 3: return gram_tiles_dma_kernel<3, NBUF, true, LW>;
-            default: return gram_tiles_dma_kernel<4, NBUF, true, LW>;
-        }
-    }
-    switch (nt8) {
-        case 1: return gram_tiles_dma_kernel<1, NBUF, false, LW>;
-        case 2: return gram_tiles_dma_kernel<2, NBUF, false, LW>;
-        case 3: return gram_tiles_dma_kernel<3, NBUF, false, LW>;
-        case 4: return gram_tiles_dma_kernel<4, NBUF, false, LW>;
-        default: return gram_tiles_dma_kernel<5, NBUF, false, LW>;
-    }
+    static const gram_dma_fn plain[5] = {gram_tiles_dma_kernel<1, NBUF, false, LW>, gram_tiles_dma_kernel<2, NBUF, false, LW>,
+                                         gram_tiles_dma_kernel<3, NBUF, false, LW>, gram_tiles_dma_kernel<4, NBUF, false, LW>,
+                                         gram_tiles_dma_kernel<5, NBUF, false, LW>};
+    static const gram_dma_fn slots[4] = {gram_tiles_dma_kernel<1, NBUF, true, LW>, gram_tiles_dma_kernel<2, NBUF, true, LW>,
+                                         gram_tiles_dma_kernel<3, NBUF, true, LW>, gram_tiles_dma_kernel<4, NBUF, true, LW>};
+    return nt8 < 1 || nt8 > (half ? 4 : 5) ? nullptr : half ? slots[nt8 - 1] : plain[nt8 - 1];
 }
 
-static gram_dma_fn tiles_dma_kernel(int nt8, int nbuf, bool half, int loaders = 0)
+// the product's: two LDS buffers, staged by the matrix wavefronts themselves or by four loader wavefronts
+static gram_dma_fn tiles_dma_kernel(int nt8, bool half, int nbuf, int loaders)
 {
-#ifdef FOKL_DEV_KERNELS
-    if (nbuf == 3) return tiles_dma_kernel_b<3, 0>(nt8, half);
-#endif
-    (void)nbuf;
-    if (loaders == 2) return tiles_dma_kernel_b<2, 2>(nt8, half);
-    if (loaders == 4) return tiles_dma_kernel_b<2, 4>(nt8, half);
-    return tiles_dma_kernel_b<2, 0>(nt8, half);
-}
-
-// Half-tile slots need the LDS-DMA kernel: asked for only where it runs every block (the default), FOKL_GRAM_HALF=0 for A/B
-static bool half_slots_wanted()
-{
-#ifdef FOKL_DEV_KERNELS
-    if (dev_int("FOKL_GRAM_MFMA4", 0) == 2) return false;
-#endif
-    return dev_int("FOKL_GRAM_DMA", 2) == 2 && dev_int("FOKL_GRAM_HALF", 1) != 0;
+    if (nbuf != 2) return nullptr;
+    return loaders == 4 ? tiles_dma_kernel_b<2, 4>(nt8, half) : loaders == 0 ? tiles_dma_kernel_b<2, 0>(nt8, half) : nullptr;
 }
 
 extern "C" int fokl_gram_plan(const int32_t *row_slots, int nr, const int32_t *col_slots, int nc, int kind, int32_t *info,
@@ -1229,11 +1117,11 @@ extern "C" int fokl_gram_plan(const int32_t *row_slots, int nr, const int32_t *c
 {
     if (!row_slots || !col_slots || !info || nr <= 0 || nc <= 0 || kind < 0 || kind > 1)
         return fail(nullptr, FOKL_ERR_ARG, "fokl_gram_plan: bad argument");
-#ifndef FOKL_DEV_KERNELS
-    if (kind == 1) return fail(nullptr, FOKL_ERR_ARG, "fokl_gram_plan: kind 1 (4x4x4 tile lists) needs a development build");
-#endif
+    const LaunchKnobs knobs = launch_knobs();
+    if (kind == 1 && !knobs.tiles4_nt)
+        return fail(nullptr, FOKL_ERR_ARG, "fokl_gram_plan: kind 1 (4x4x4 tile lists) needs a development build");
     GramPlan pl;
-    plan_gram(row_slots, nr, col_slots, nc, kind, pl, half_slots_wanted());
+    plan_gram(row_slots, nr, col_slots, nc, kind, knobs, pl);
     const int32_t head[10] = {pl.nci, pl.it, pl.jt, (int32_t)pl.groups.size(), pl.nt, pl.ct, pl.rb_shift, pl.ks, pl.depth,
                               pl.waves};
     std::memcpy(info, head, sizeof(head));
@@ -1256,13 +1144,228 @@ extern "C" int fokl_gram_plan(const int32_t *row_slots, int nr, const int32_t *c
     return FOKL_OK;
 }
 
+// ---- a Gram call: head (gram_enqueue), one launcher per kernel, tail (gram_enqueue) -------------------------
+
+// A Gram call once gram_enqueue has checked it.
+struct GramCall {
+    const int32_t *row_slots, *col_slots;
+    int nr, nc;
+    int slot;                          // FOKL_K_GRAM or FOKL_K_GRAM_MFMA: the roof the launch is booked under
+    double bytes, flops;               // algorithmic traffic and work of the block
+};
+
+// A Gram launch in the making: what stage_gram_tiles leaves for the tile-list launchers, what the tail needs from whichever
+// kernel ran.
+struct GramLaunch {
+    GramPlan plan;                     // path 2, with its descriptors on the device
+    const int *d_icols = nullptr;
+    const GramGroup *d_groups = nullptr;
+    const double *grid_base = nullptr;
+    const int *d_perm = nullptr;       // slabs in the plan's internal column order (symmetric reduction); nullptr: the caller's
+    int S = 0, slabs = 0;              // the row cut; partial blocks in d_slab (S per phase of a k-split)
+    int nr_pad = 0, nc_pad = 0;
+    int64_t rep[FOKL_GRAM_REPORT_LEN] = {};        // fokl_fit_report: the entries the launcher knows
+};
+
+static std::mutex lds_limit_mutex;
+static std::map<const void *, size_t> lds_limit_set;               // kernels whose dynamic LDS limit was raised already
+
+static int raise_lds_limit(fokl_ctx *ctx, const void *fn, size_t lds)
+{
+    std::lock_guard<std::mutex> lock(lds_limit_mutex);
+    size_t &have = lds_limit_set[fn];
+    if (have < lds) {
+        HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        have = 160 * 1024;
+    }
+    return FOKL_OK;
+}
+
+// The row cut S decides which rows meet in which partial sum, i.e. the last bits of the block.  It must move neither with a
+// compiler or an edit that changes a kernel's register count, nor with the device the fit happens to run on (a partition with
+// fewer CUs, another SKU), nor with what the occupancy query says today: it is the cut of 256 CUs hosting a PINNED number of
+// workgroups each -- by_registers: what the kernel could host when the goldens' margins were measured; under the 160 KB of
+// LDS counted by arithmetic -- so the same rows meet in the same partial sums everywhere and a golden measured on one device
+// holds on another.  Resident or queued, every workgroup has the same work.
+// wgs_cap: workgroups per CU that share the rows of a group: more of them hide more latency but every one writes a partial
+// block the reduction has to read back (3; FOKL_GRAM_WGS in development builds).
+static int pinned_row_cut(int wgs_cap, int by_registers, size_t lds, size_t groups, int64_t n_chunks, int cus = 256)
+{
+    const int lds_fit = (int)std::max<size_t>(1, (size_t)(160 * 1024) / std::max<size_t>(lds, 1));
+    const int target = std::max(1, (std::min({wgs_cap, by_registers, lds_fit}) * cus) / (int)groups);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(n_chunks, target));
+}
+
+// S workgroups share the chunks of rows of a group, each writes one partial block per phase of the k-split: room for them.
+static int size_slabs(fokl_ctx *ctx, GramLaunch &run, int S, int ks, int64_t n_chunks)
+{
+    run.S = S;
+    run.slabs = S * ks;
+    run.rep[14] = (n_chunks + S - 1) / S;
+    return ensure_slab(ctx, (size_t)run.slabs * run.nr_pad * run.nc_pad);
+}
+
+// The caller's slot lists on the device, rows first: for the kernels that take them as they are.
+static int push_slot_lists(fokl_ctx *ctx, const GramCall &c, const int *&d_rows, const int *&d_cols)
+{
+    const size_t arg_bytes = (size_t)(c.nr + c.nc) * sizeof(int);
+    int rc = begin_args(ctx, arg_bytes);
+    if (rc) return rc;
+    int *h = reinterpret_cast<int *>(ctx->h_args);
+    std::memcpy(h, c.row_slots, (size_t)c.nr * sizeof(int));
+    std::memcpy(h + c.nr, c.col_slots, (size_t)c.nc * sizeof(int));
+    d_rows = reinterpret_cast<const int *>(ctx->d_args);
+    d_cols = d_rows + c.nr;
+    return push_args(ctx, arg_bytes);
+}
+
+// Path 1, gram_valu_kernel: re-reads operands once per 4x4 register tile, fine while the block is small.
+static int launch_gram_valu(fokl_ctx *ctx, const GramCall &c, GramLaunch &run)
+{
+    const int *d_rows, *d_cols;
+    int rc = push_slot_lists(ctx, c, d_rows, d_cols);
+    if (rc) return rc;
+    const int gz = (c.nr + GV_TI - 1) / GV_TI, gy = (c.nc + GV_TJ - 1) / GV_TJ;
+    run.nr_pad = gz * GV_TI;
+    run.nc_pad = gy * GV_TJ;
+    const int64_t n_row_blocks = (ctx->n + GV_THREADS * 2 - 1) / (GV_THREADS * 2);
+    const int target = std::max(1, (8 * cu_count(ctx)) / (gz * gy));
+    rc = size_slabs(ctx, run, (int)std::max<int64_t>(1, std::min<int64_t>(n_row_blocks, target)), 1, n_row_blocks);
+    if (rc) return rc;
+    run.rep[0] = FOKL_GRAM_VALU, run.rep[5] = run.rep[6] = 1, run.rep[7] = GV_THREADS * 2, run.rep[8] = gy * gz;
+    run.rep[21] = GV_THREADS;
+    TimedRegion timed(ctx, c.slot, c.bytes, c.flops);      // brackets the Gram kernel only
+    hipLaunchKernelGGL(gram_valu_kernel, dim3(run.S, gy, gz), dim3(GV_THREADS), 0, ctx->stream, ctx->d_slot_ptr, d_rows, c.nr,
+                       d_cols, c.nc, ctx->n, ctx->d_slab, run.nr_pad, run.nc_pad);
+    return FOKL_OK;
+}
+
+// Path 2 in front of its launchers: tile lists over the internal column order (tiles below the diagonal of the row-side x
+// row-side part skipped), the groups' column addresses, the descriptors on the device; what the plan tells the tail.
+static int stage_gram_tiles(fokl_ctx *ctx, const GramCall &c, int kind, const LaunchKnobs &knobs, GramLaunch &run)
+{
+    GramPlan &pl = run.plan;
+    plan_gram(c.row_slots, c.nr, c.col_slots, c.nc, kind, knobs, pl);
+    // column addresses for the groups' descriptors (distances on the 256-byte slot grid)
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(run.grid_base);
+    const uint32_t zero_units = (uint32_t)((reinterpret_cast<uintptr_t>(ctx->d_zero) - lo) >> 8) | 0x80000000u;
+    for (GramGroup &g : pl.groups)
+        for (int p = 0; p < GT_MAX_CT; ++p)
+            for (int k = 0; k < 16; ++k) {
+                const int col = g.ct[p] >= 0 ? 16 * g.ct[p] + k : -1;
+                g.col_units[p][k] = col >= 0 && col < pl.nci
+                                        ? (uint32_t)((reinterpret_cast<uintptr_t>(ctx->slot_ptr[pl.icols[col]]) - lo) >> 8)
+                                        : zero_units;
+            }
+    const size_t ints = (size_t)pl.nci + (size_t)c.nc;
+    const size_t group_off = (ints * sizeof(int32_t) + 15) / 16 * 16;
+    const size_t arg_bytes = group_off + pl.groups.size() * sizeof(GramGroup);
+    int rc = begin_args(ctx, arg_bytes);
+    if (rc) return rc;
+    std::memcpy(ctx->h_args, pl.icols.data(), (size_t)pl.nci * sizeof(int32_t));
+    std::memcpy(ctx->h_args + (size_t)pl.nci * sizeof(int32_t), pl.perm.data(), (size_t)c.nc * sizeof(int32_t));
+    std::memcpy(ctx->h_args + group_off, pl.groups.data(), pl.groups.size() * sizeof(GramGroup));
+    run.d_icols = reinterpret_cast<const int *>(ctx->d_args);
+    run.d_perm = run.d_icols + pl.nci;
+    run.d_groups = reinterpret_cast<const GramGroup *>(ctx->d_args + group_off);
+    run.nr_pad = 16 * pl.it;
+    run.nc_pad = 16 * pl.jt;
+    run.rep[2] = pl.half ? 1 : 0, run.rep[5] = pl.ks, run.rep[6] = pl.depth, run.rep[8] = (int64_t)pl.groups.size();
+    run.rep[9] = pl.ct, run.rep[10] = pl.nt, run.rep[19] = pl.it, run.rep[20] = pl.jt;
+    return push_args(ctx, arg_bytes);
+}
+
+// gram_tiles_kernel (register staging).  The product's launches are the k-split teams of the blocks of one or two tiles --
+// every k-step of a chunk dealt over a team of wavefronts, one slab per phase -- at three workgroups per CU by registers.
+static int launch_gram_tiles(fokl_ctx *ctx, const GramCall &c, GramLaunch &run, gram_tiles_fn fn, int wgs_cap,
+                             int by_registers = 3, int cut_cus = 256)
+{
+    const GramPlan &pl = run.plan;
+    if (!fn) return no_instance(ctx, "gram_tiles_kernel", pl);
+    const int R = 32 << pl.rb_shift;
+    const size_t lds = (size_t)pl.ct * 16 * (R + 2) * sizeof(double);
+    int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(fn), lds);
+    if (rc) return rc;
+    const int64_t n_chunks = (ctx->n + R - 1) / R;
+    rc = size_slabs(ctx, run, pinned_row_cut(wgs_cap, by_registers, lds, pl.groups.size(), n_chunks, cut_cus), pl.ks, n_chunks);
+    if (rc) return rc;
+    run.rep[0] = FOKL_GRAM_TILES, run.rep[1] = pl.nt, run.rep[7] = R, run.rep[12] = (int64_t)lds, run.rep[21] = GT_THREADS;
+    TimedRegion timed(ctx, c.slot, c.bytes, c.flops);      // brackets the Gram kernel only
+    hipLaunchKernelGGL(fn, dim3(run.S, (unsigned)pl.groups.size()), dim3(GT_THREADS), lds, ctx->stream, ctx->d_slot_ptr,
+                       run.d_icols, pl.nci, run.d_groups, pl.ct, pl.rb_shift, ctx->n, ctx->d_slab, run.nr_pad, run.nc_pad,
+                       ctx->d_zero, run.grid_base);
+    return FOKL_OK;
+}
+
+// gram_tiles_dma_kernel: LDS-DMA staging, 8 matrix wavefronts per workgroup, nbuf LDS buffers: every block of three tiles or
+// more.  Three workgroups per CU by registers for one tile per wavefront, two beyond.
+static int launch_gram_dma(fokl_ctx *ctx, const GramCall &c, GramLaunch &run, gram_dma_picker pick, int wgs_cap, int nbuf,
+                           int loaders)
+{
+    const GramPlan &pl = run.plan;
+    const int nt8 = (pl.nt + 1) / 2, pieces = (pl.ct * 16 * 34 * 8 + 1023) / 1024;
+    const size_t lds = (size_t)nbuf * pieces * 1024;
+    gram_dma_fn fn = pick(nt8, pl.half, nbuf, 0);
+    if (!fn) return no_instance(ctx, "gram_tiles_dma_kernel", pl);
+    int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(fn), lds);
+    if (rc) return rc;
+    const int by_registers = nt8 == 1 ? 3 : 2;
+    if (loaders) {
+        // Loader wavefronts issue the LDS-DMA pieces instead of the matrix wavefronts (gram_tiles_dma_kernel<.., 4>) wherever
+        // a CU can host as many of the larger workgroups as the row cut puts on it -- fewer resident workgroups cost more than
+        // the loaders bring (56 x 98: 195 -> 216 us).  Same tiles, same order of summation: the block's bits do not depend on it.
+        gram_dma_fn with = pick(nt8, pl.half, nbuf, loaders);
+        if (!with) return no_instance(ctx, "gram_tiles_dma_kernel with loader wavefronts", pl);
+        rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(with), lds);
+        if (rc) return rc;
+        const int per_cu = std::min({wgs_cap, blocks_per_cu(fn, GD_THREADS, lds), by_registers});
+        if (blocks_per_cu(with, GD_THREADS + 64 * loaders, lds) >= per_cu)
+            fn = with;
+        else
+            loaders = 0;
+    }
+    const int64_t n_chunks = (ctx->n + 31) / 32;
+    rc = size_slabs(ctx, run, pinned_row_cut(wgs_cap, by_registers, lds, pl.groups.size(), n_chunks), 1, n_chunks);
+    if (rc) return rc;
+    const uint32_t zero_units =
+        (uint32_t)((reinterpret_cast<uintptr_t>(ctx->d_zero) - reinterpret_cast<uintptr_t>(run.grid_base)) >> 8);
+    run.rep[0] = FOKL_GRAM_DMA, run.rep[1] = nt8, run.rep[3] = loaders, run.rep[4] = nbuf, run.rep[7] = 32, run.rep[11] = pieces;
+    run.rep[12] = (int64_t)lds, run.rep[21] = GD_THREADS + 64 * loaders;
+    TimedRegion timed(ctx, c.slot, c.bytes, c.flops);      // brackets the Gram kernel only
+    hipLaunchKernelGGL(fn, dim3(run.S, (unsigned)pl.groups.size()), dim3(GD_THREADS + 64 * loaders), lds, ctx->stream,
+                       run.d_groups, pl.ct, pieces, ctx->n, ctx->d_slab, run.nr_pad, run.nc_pad, run.grid_base, zero_units);
+    return FOKL_OK;
+}
+
+#ifdef FOKL_DEV_KERNELS
+#include "fokl_gram_dev.inc"
+#endif
+
+// The kernel of a checked call.  path 1: the VALU kernel; 2: the tile lists, k-split teams for blocks of one or two tiles,
+// LDS-DMA staging (four loader wavefronts where they fit) for every other block; 3: development builds only.
+static int launch_gram(fokl_ctx *ctx, const GramCall &c, const LaunchKnobs &knobs, int path, GramLaunch &run)
+{
+    if (path == 1) return launch_gram_valu(ctx, c, run);
+    if (path == 2) {
+        const int rc = stage_gram_tiles(ctx, c, knobs.mfma4 == 2 ? 1 : 0, knobs, run);
+        if (rc) return rc;
+    }
+#ifdef FOKL_DEV_KERNELS
+    bool taken = false;           // fokl_gram_dev.inc: the routes only a knob reaches
+    const int rc = launch_gram_dev(ctx, c, knobs, path, run, taken);
+    if (taken) return rc;
+#endif
+    if (path == 3) return fail(ctx, FOKL_ERR_ARG, "fokl_gram: path 3 (round-1 panel kernel) needs a development build");
+    if (run.plan.ks > 1) return launch_gram_tiles(ctx, c, run, ksplit_kernel(run.plan), knobs.wgs);
+    return launch_gram_dma(ctx, c, run, tiles_dma_kernel, knobs.wgs, 2, knobs.loaders);
+}
+
 // Everything of a Gram block up to the copy into pinned host memory, enqueued on the context's stream.  aside: the
 // result goes to the d_gout / h_gout pair (fokl_gram_launch) instead of d_out / h_out.
 static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const int32_t *col_slots, int nc, int path,
                         int allreduce, bool aside)
 {
     std::memset(ctx->gram_report, 0, sizeof ctx->gram_report);     // fokl_fit_report: filled when everything is enqueued
-    int64_t rep[FOKL_GRAM_REPORT_LEN] = {};
     if (!ctx->have_data) return fail(ctx, FOKL_ERR_STATE, "fokl_gram: call fokl_upload first");
     if (nr <= 0 || nc <= 0) return fail(ctx, FOKL_ERR_ARG, "fokl_gram: empty block");
     if (path < 0 || path > 3) return fail(ctx, FOKL_ERR_ARG, "fokl_gram: path must be 0, 1, 2 or 3");
@@ -1272,13 +1375,13 @@ static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const i
     rc = check_slots(ctx, col_slots, nc, "fokl_gram");
     if (rc) return rc;
 
-    // path choice: the VALU kernel re-reads operands once per 4x4 register tile, fine while the block is small;
-    // the MFMA kernels read every column of a group of tiles once per row chunk.
-    if (path == 0) path = (int64_t)nr * nc > 64 ? dev_int("FOKL_GRAM_PATH", 2) : 1;
+    // path choice: the VALU kernel while the block is small; the MFMA kernels read every column of a group of tiles once
+    // per row chunk
+    const LaunchKnobs knobs = launch_knobs();
+    if (path == 0) path = (int64_t)nr * nc > 64 ? knobs.path : 1;
     if (path < 1 || path > 3) path = 2;
     const double *grid_base = path == 2 ? slot_grid_base(ctx) : nullptr;
     if (path == 2 && !grid_base) path = 3;                   // slots off the 256-byte grid (never seen): panel kernel
-    const int cus = cu_count(ctx);
     rc = aside ? ensure_gout(ctx, (size_t)nr * nc) : ensure_out(ctx, (size_t)nr * nc);
     if (rc) return rc;
     double *d_dst = aside ? ctx->d_gout : ctx->d_out;
@@ -1289,266 +1392,35 @@ static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const i
     uniq.insert(uniq.end(), col_slots, col_slots + nc);
     std::sort(uniq.begin(), uniq.end());
     const double distinct = (double)(std::unique(uniq.begin(), uniq.end()) - uniq.begin());
-    const double bytes = 8.0 * (double)ctx->n * distinct;
-    const double flops = 2.0 * (double)ctx->n * (double)nr * (double)nc;
+    GramCall call = {row_slots, col_slots, nr, nc, FOKL_K_GRAM, 8.0 * (double)ctx->n * distinct,
+                     2.0 * (double)ctx->n * (double)nr * (double)nc};
     // the launch is booked under the roof that binds it
-    const int gram_slot = flops / FOKL_PEAK_F64_FLOPS > bytes / FOKL_PEAK_HBM_BYTES_PER_S ? FOKL_K_GRAM_MFMA : FOKL_K_GRAM;
+    if (call.flops / FOKL_PEAK_F64_FLOPS > call.bytes / FOKL_PEAK_HBM_BYTES_PER_S) call.slot = FOKL_K_GRAM_MFMA;
     if (const char *trace = std::getenv("FOKL_GRAM_TRACE")) {   // profile runs: which class each launch was booked under
         if (FILE *fh = std::fopen(trace, "a")) {
-            std::fprintf(fh, "%d %d %d %s\n", nr, nc, (int)distinct, gram_slot == FOKL_K_GRAM_MFMA ? "gram_mfma" : "gram");
+            std::fprintf(fh, "%d %d %d %s\n", nr, nc, (int)distinct, call.slot == FOKL_K_GRAM_MFMA ? "gram_mfma" : "gram");
             std::fclose(fh);
         }
     }
-    const int total = nr * nc;
-    const int epb = reduce_elements_per_block(total);
 
-    if (path == 2) {
-        // tile lists over the internal column order; tiles below the diagonal of the row-side x row-side part skipped
-        // FOKL_GRAM_MFMA4=2: the 4x4x4 form of the fp64 MFMA instruction (A/B runs; slower beyond the smallest blocks)
-#ifdef FOKL_DEV_KERNELS
-        const int kind = dev_int("FOKL_GRAM_MFMA4", 0) == 2 ? 1 : 0;
-#else
-        const int kind = 0;
-#endif
-        GramPlan pl;
-        plan_gram(row_slots, nr, col_slots, nc, kind, pl, half_slots_wanted());
-        // column addresses for the groups' descriptors (distances on the 256-byte slot grid)
-        {
-            const uintptr_t lo = reinterpret_cast<uintptr_t>(grid_base);
-            const uint32_t zero_units = (uint32_t)((reinterpret_cast<uintptr_t>(ctx->d_zero) - lo) >> 8) | 0x80000000u;
-            for (GramGroup &g : pl.groups)
-                for (int p = 0; p < GT_MAX_CT; ++p)
-                    for (int c = 0; c < 16; ++c) {
-                        const int col = g.ct[p] >= 0 ? 16 * g.ct[p] + c : -1;
-                        g.col_units[p][c] = col >= 0 && col < pl.nci
-                                                ? (uint32_t)((reinterpret_cast<uintptr_t>(ctx->slot_ptr[pl.icols[col]]) - lo) >> 8)
-                                                : zero_units;
-                    }
-        }
-        const size_t ints = (size_t)pl.nci + (size_t)nc;
-        const size_t group_off = (ints * sizeof(int32_t) + 15) / 16 * 16;
-        const size_t arg_bytes = group_off + pl.groups.size() * sizeof(GramGroup);
-        rc = begin_args(ctx, arg_bytes);
-        if (rc) return rc;
-        std::memcpy(ctx->h_args, pl.icols.data(), (size_t)pl.nci * sizeof(int32_t));
-        std::memcpy(ctx->h_args + (size_t)pl.nci * sizeof(int32_t), pl.perm.data(), (size_t)nc * sizeof(int32_t));
-        std::memcpy(ctx->h_args + group_off, pl.groups.data(), pl.groups.size() * sizeof(GramGroup));
-        rc = push_args(ctx, arg_bytes);
-        if (rc) return rc;
-        const int *d_icols = reinterpret_cast<const int *>(ctx->d_args);
-        const int *d_perm = d_icols + pl.nci;
-        const GramGroup *d_groups = reinterpret_cast<const GramGroup *>(ctx->d_args + group_off);
+    GramLaunch run;
+    run.grid_base = grid_base;
+    rc = launch_gram(ctx, call, knobs, path, run);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipGetLastError());
 
-        static std::mutex attr_mutex;
-        static std::map<const void *, size_t> attr_set;            // kernels whose dynamic LDS limit was raised already
-        auto raise_lds_limit = [&](const void *fn, size_t lds) -> int {
-            std::lock_guard<std::mutex> lock(attr_mutex);
-            size_t &have = attr_set[fn];
-            if (have < lds) {
-                HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                have = 160 * 1024;
-            }
-            return FOKL_OK;
-        };
-        const int nr_pad = 16 * pl.it, nc_pad = 16 * pl.jt;
-        // workgroups per CU that share the rows of a group: more of them hide more latency but every one writes a
-        // partial block the reduction has to read back (FOKL_GRAM_WGS caps it)
-        const int wgs_cap = std::max(1, dev_int("FOKL_GRAM_WGS", 3));
-        // The row cut S decides which rows meet in which partial sum, i.e. the last bits of the block.  It must move neither
-        // with a compiler or an edit that changes a kernel's register count, nor with the device the fit happens to run on (a
-        // partition with fewer CUs, another SKU), nor with what the occupancy query says today: it is the cut of kCutCus CUs
-        // hosting a PINNED number of workgroups each -- what these kernels could host when the goldens' margins were
-        // measured, under the 160 KB of LDS counted by arithmetic -- so the same rows meet in the same partial sums
-        // everywhere and a golden measured on one device holds on another.  Resident or queued, every
-        // workgroup has the same work.
-        constexpr int kCutCus = 256;
-        auto lds_fit = [](size_t lds) { return (int)std::max<size_t>(1, (size_t)(160 * 1024) / std::max<size_t>(lds, 1)); };
-        int S;
-#ifdef FOKL_DEV_KERNELS
-        if (kind == 1) {
-            const int P = pl.ct <= 2 ? 2 : pl.ct <= 4 ? 4 : pl.ct <= 6 ? 6 : 8;
-            gram_tiles4_fn fn = tiles4s_kernel(pl.nt, pl.ct);
-            const size_t lds = (size_t)P * 16 * G4_PITCH * sizeof(double);
-            rc = raise_lds_limit(reinterpret_cast<const void *>(fn), lds);
-            if (rc) return rc;
-            const int64_t n_chunks = (ctx->n + 31) / 32;
-            const int per_cu = std::min(wgs_cap, blocks_per_cu(fn, G4S_THREADS, lds));
-            const int target = std::max(1, (per_cu * cus) / (int)pl.groups.size());      // (A/B kernel: no pinned row cut)
-            S = (int)std::max<int64_t>(1, std::min<int64_t>(n_chunks, target));
-            rc = ensure_slab(ctx, (size_t)S * nr_pad * nc_pad);
-            if (rc) return rc;
-            rep[0] = FOKL_GRAM_TILES4, rep[1] = pl.nt, rep[7] = 32, rep[12] = (int64_t)lds, rep[21] = G4S_THREADS;
-            rep[14] = (n_chunks + S - 1) / S;
-            TimedRegion timed(ctx, gram_slot, bytes, flops);      // brackets the Gram kernel only
-            hipLaunchKernelGGL(fn, dim3(S, (unsigned)pl.groups.size()), dim3(G4S_THREADS), lds, ctx->stream,
-                               ctx->d_slot_ptr, d_icols, pl.nci, d_groups, pl.ct, ctx->n, ctx->d_slab, nr_pad, nc_pad,
-                               ctx->d_zero, grid_base);
-        } else
-#endif
-        if (pl.ks == 1 && (dev_int("FOKL_GRAM_DMA", 2) == 2 ||
-                                  (dev_int("FOKL_GRAM_DMA", 2) == 1 && gram_slot == FOKL_K_GRAM_MFMA))) {
-            // LDS-DMA staging, 8 wavefronts per workgroup, two LDS buffers: every block of three tiles or more
-            // (FOKL_GRAM_DMA=1: only the launches the matrix pipe bounds, 0: gram_tiles_kernel for everything)
-            const int pieces = (pl.ct * 16 * 34 * 8 + 1023) / 1024;
-            // three LDS buffers (a chunk's pieces in flight across the barrier) where they fit, FOKL_GRAM_BUFS to force
-            int nbuf = 2;
-#ifdef FOKL_DEV_KERNELS
-            nbuf = dev_int("FOKL_GRAM_BUFS", 2);
-            if (nbuf == 3 && 3 * (size_t)pieces * 1024 > 160 * 1024) nbuf = 2;
-#endif
-            gram_dma_fn plain_fn = tiles_dma_kernel((pl.nt + 1) / 2, nbuf, pl.half);
-            const size_t lds = (size_t)nbuf * pieces * 1024;
-            rc = raise_lds_limit(reinterpret_cast<const void *>(plain_fn), lds);
-            if (rc) return rc;
-            const int64_t n_chunks = (ctx->n + 31) / 32;
-            // The row cut decides which rows meet in which partial sum, i.e. the last bits of the block: it must not move
-            // when a compiler or an edit changes the kernel's register count.  Pinned to what these kernels could host
-            // when the goldens' margins were measured (three workgroups per CU for one tile per wavefront, two beyond),
-            // under the LDS limit the occupancy query reports; resident or queued, every workgroup has the same work.
-            const int by_registers = (pl.nt + 1) / 2 == 1 ? 3 : 2;
-            const int per_cu = std::min({wgs_cap, blocks_per_cu(plain_fn, GD_THREADS, lds), by_registers});
-            // Four loader wavefronts issue the LDS-DMA pieces instead of the matrix wavefronts (gram_tiles_dma_kernel<.., 4>)
-            // wherever a CU can host as many of the larger workgroups as the row cut puts on it -- fewer resident
-            // workgroups cost more than the loaders bring (56 x 98: 195 -> 216 us).  FOKL_GRAM_LOADERS=0: never.  Same tiles,
-            // same order of summation: the block's bits do not depend on it.
-            int loaders = nbuf == 2 ? dev_int("FOKL_GRAM_LOADERS", 4) : 0;
-            if (loaders != 2 && loaders != 4) loaders = 0;
-            gram_dma_fn fn = plain_fn;
-            if (loaders) {
-                gram_dma_fn with = tiles_dma_kernel((pl.nt + 1) / 2, nbuf, pl.half, loaders);
-                rc = raise_lds_limit(reinterpret_cast<const void *>(with), lds);
-                if (rc) return rc;
-                if (blocks_per_cu(with, GD_THREADS + 64 * loaders, lds) >= per_cu)
-                    fn = with;
-                else
-                    loaders = 0;
-            }
-            const int cut_per_cu = std::min({wgs_cap, by_registers, lds_fit(lds)});
-            const int target = std::max(1, (cut_per_cu * kCutCus) / (int)pl.groups.size());
-            S = (int)std::max<int64_t>(1, std::min<int64_t>(n_chunks, target));
-            rc = ensure_slab(ctx, (size_t)S * nr_pad * nc_pad);
-            if (rc) return rc;
-            const uint32_t zero_units = (uint32_t)((reinterpret_cast<uintptr_t>(ctx->d_zero) - reinterpret_cast<uintptr_t>(grid_base)) >> 8);
-            rep[0] = FOKL_GRAM_DMA, rep[1] = (pl.nt + 1) / 2, rep[3] = loaders, rep[4] = nbuf, rep[7] = 32, rep[11] = pieces;
-            rep[12] = (int64_t)lds, rep[14] = (n_chunks + S - 1) / S, rep[21] = GD_THREADS + 64 * loaders;
-            TimedRegion timed(ctx, gram_slot, bytes, flops);      // brackets the Gram kernel only
-            hipLaunchKernelGGL(fn, dim3(S, (unsigned)pl.groups.size()), dim3(GD_THREADS + 64 * loaders), lds, ctx->stream,
-                               d_groups, pl.ct, pieces, ctx->n, ctx->d_slab, nr_pad, nc_pad, grid_base, zero_units);
-        } else {
-            gram_tiles_fn fn = tiles_kernel(pl.nt, pl.ct << pl.rb_shift, pl.depth, pl.ks);
-            const int R = 32 << pl.rb_shift;
-            const size_t lds = (size_t)pl.ct * 16 * (R + 2) * sizeof(double);
-            rc = raise_lds_limit(reinterpret_cast<const void *>(fn), lds);
-            if (rc) return rc;
-            const int64_t n_chunks = (ctx->n + R - 1) / R;
-            // the product's launches here are the k-split teams of the smallest blocks (ks = 2, 4: one tile per wavefront):
-            // three workgroups per CU by registers except with 16 staging passes and two chunks in flight (187 VGPRs: two);
-            // ks = 1 only runs here under FOKL_GRAM_DMA != 2 (A/B runs): the occupancy query, as before
-            const int passes = pl.ct << pl.rb_shift;
-            const int by_registers = pl.ks > 1 ? (passes > 8 && pl.depth == 2 ? 2 : 3) : blocks_per_cu(fn, GT_THREADS, lds);
-            const int cut_per_cu = std::min({wgs_cap, by_registers, lds_fit(lds)});
-            const int target = std::max(1, (cut_per_cu * (pl.ks > 1 ? kCutCus : cus)) / (int)pl.groups.size());
-            S = (int)std::max<int64_t>(1, std::min<int64_t>(n_chunks, target));
-            rc = ensure_slab(ctx, (size_t)S * pl.ks * nr_pad * nc_pad);
-            if (rc) return rc;
-            rep[0] = FOKL_GRAM_TILES, rep[1] = pl.nt, rep[7] = R, rep[12] = (int64_t)lds, rep[21] = GT_THREADS;
-            rep[14] = (n_chunks + S - 1) / S;
-            TimedRegion timed(ctx, gram_slot, bytes, flops);      // brackets the Gram kernel only
-            hipLaunchKernelGGL(fn, dim3(S, (unsigned)pl.groups.size()), dim3(GT_THREADS), lds, ctx->stream,
-                               ctx->d_slot_ptr, d_icols, pl.nci, d_groups, pl.ct, pl.rb_shift, ctx->n, ctx->d_slab,
-                               nr_pad, nc_pad, ctx->d_zero, grid_base);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-        {
-            // the reduction is a kernel of its own in the timing table (and in rocprofv3's): slabs read + block written
-            TimedRegion timed(ctx, FOKL_K_GRAM_REDUCE, 8.0 * ((double)S * pl.ks + 1.0) * total, 0.0);
+    const int total = nr * nc, epb = reduce_elements_per_block(total);
+    {
+        // the reduction is a kernel of its own in the timing table (and in rocprofv3's): slabs read + block written
+        TimedRegion timed(ctx, FOKL_K_GRAM_REDUCE, 8.0 * ((double)run.slabs + 1.0) * total, 0.0);
+        if (run.d_perm)
             hipLaunchKernelGGL(reduce_slabs_sym_kernel, dim3((total + epb - 1) / epb), dim3(RD_THREADS), 0, ctx->stream,
-                               ctx->d_slab, S * pl.ks, nr, nc, nr_pad, nc_pad, epb, d_perm, d_dst);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-        rep[2] = pl.half ? 1 : 0, rep[5] = pl.ks, rep[6] = pl.depth, rep[8] = (int64_t)pl.groups.size(), rep[9] = pl.ct;
-        rep[10] = pl.nt, rep[13] = S, rep[15] = nr_pad, rep[16] = nc_pad, rep[17] = (int64_t)S * pl.ks, rep[18] = epb;
-        rep[19] = pl.it, rep[20] = pl.jt;
-    } else {
-        const size_t arg_bytes = (size_t)(nr + nc) * sizeof(int);
-        rc = begin_args(ctx, arg_bytes);
-        if (rc) return rc;
-        int *h = reinterpret_cast<int *>(ctx->h_args);
-        std::memcpy(h, row_slots, (size_t)nr * sizeof(int));
-        std::memcpy(h + nr, col_slots, (size_t)nc * sizeof(int));
-        rc = push_args(ctx, arg_bytes);
-        if (rc) return rc;
-        const int *d_rows = reinterpret_cast<const int *>(ctx->d_args);
-        const int *d_cols = d_rows + nr;
-        int S, nr_pad, nc_pad;
-        dim3 grid;
-#ifndef FOKL_DEV_KERNELS
-        if (path == 3) return fail(ctx, FOKL_ERR_ARG, "fokl_gram: path 3 (round-1 panel kernel) needs a development build");
-        {
-#else
-        gram_mfma_fn mfma_fn = nullptr;
-        if (path == 3) {                                     // rectangular panels, one i-tile or j-tile set per wavefront
-            int BI, BJ;
-            const int j_tiles = (nc + 15) / 16;
-            if (nr > 32) {                                   // i-split: wave w <-> i-tile w, panel of TJ j-tiles
-                const int panels = (j_tiles + 11) / 12;
-                const int tj = (j_tiles + panels - 1) / panels;
-                mfma_fn = isplit_kernel(tj);
-                BI = 64;
-                BJ = 16 * tj;
-            } else {                                         // j-split: every wave all i-tiles, j-tiles dealt over waves
-                const int ti = nr > 16 ? 2 : 1;
-                const int per_wave = (j_tiles + 3) / 4;
-                const int panels = (per_wave + 2) / 3;
-                const int tj = (per_wave + panels - 1) / panels;
-                mfma_fn = jsplit_kernel(ti, tj);
-                BI = 16 * ti;
-                BJ = 64 * tj;
-            }
-            const int gz = (nr + BI - 1) / BI, gy = (nc + BJ - 1) / BJ;
-            nr_pad = gz * BI;
-            nc_pad = gy * BJ;
-            const int64_t n_chunks = (ctx->n + GM_R - 1) / GM_R;
-            const int per_cu = blocks_per_cu(mfma_fn, GM_THREADS, 0);
-            const int target = std::max(1, (per_cu * cus) / (gz * gy));
-            S = (int)std::max<int64_t>(1, std::min<int64_t>(n_chunks, target));
-            grid = dim3(S, gy, gz);
-            rep[0] = FOKL_GRAM_PANEL, rep[7] = GM_R, rep[8] = gy * gz, rep[14] = (n_chunks + S - 1) / S, rep[21] = GM_THREADS;
-        } else {
-#endif
-            const int gz = (nr + GV_TI - 1) / GV_TI, gy = (nc + GV_TJ - 1) / GV_TJ;
-            nr_pad = gz * GV_TI;
-            nc_pad = gy * GV_TJ;
-            const int64_t n_row_blocks = (ctx->n + GV_THREADS * 2 - 1) / (GV_THREADS * 2);
-            const int target = std::max(1, (8 * cus) / (gz * gy));
-            S = (int)std::max<int64_t>(1, std::min<int64_t>(n_row_blocks, target));
-            grid = dim3(S, gy, gz);
-            rep[0] = FOKL_GRAM_VALU, rep[7] = GV_THREADS * 2, rep[8] = gy * gz, rep[14] = (n_row_blocks + S - 1) / S;
-            rep[21] = GV_THREADS;
-        }
-        rep[5] = rep[6] = 1, rep[13] = rep[17] = S, rep[15] = nr_pad, rep[16] = nc_pad, rep[18] = epb;
-        rc = ensure_slab(ctx, (size_t)S * nr_pad * nc_pad);
-        if (rc) return rc;
-        {
-            TimedRegion timed(ctx, gram_slot, bytes, flops);      // brackets the Gram kernel only
-#ifdef FOKL_DEV_KERNELS
-            if (path == 3) {
-                hipLaunchKernelGGL(mfma_fn, grid, dim3(GM_THREADS), 0, ctx->stream, ctx->d_slot_ptr, d_rows, nr, d_cols,
-                                   nc, ctx->n, ctx->d_slab, nr_pad, nc_pad, ctx->d_zero);
-            } else
-#endif
-            {
-                hipLaunchKernelGGL(gram_valu_kernel, grid, dim3(GV_THREADS), 0, ctx->stream, ctx->d_slot_ptr, d_rows,
-                                   nr, d_cols, nc, ctx->n, ctx->d_slab, nr_pad, nc_pad);
-            }
-        }
-        {
-            TimedRegion timed(ctx, FOKL_K_GRAM_REDUCE, 8.0 * ((double)S + 1.0) * total, 0.0);
+                               ctx->d_slab, run.slabs, nr, nc, run.nr_pad, run.nc_pad, epb, run.d_perm, d_dst);
+        else
             hipLaunchKernelGGL(reduce_slabs_kernel, dim3((total + epb - 1) / epb), dim3(RD_THREADS), 0, ctx->stream,
-                               ctx->d_slab, S, nr, nc, nr_pad, nc_pad, epb, d_dst);
-        }
-        HIP_TRY(ctx, hipGetLastError());
+                               ctx->d_slab, run.slabs, nr, nc, run.nr_pad, run.nc_pad, epb, d_dst);
     }
+    HIP_TRY(ctx, hipGetLastError());
     // row-sharded fit: the block is summed over the ranks where it lies -- RCCL on the device, stream-ordered behind
     // the reduction kernel -- and crosses PCIe once
     if (allreduce && ctx->comm) {
@@ -1556,7 +1428,8 @@ static int gram_enqueue(fokl_ctx *ctx, const int32_t *row_slots, int nr, const i
         if (rc) return rc;
     }
     HIP_TRY(ctx, hipMemcpyAsync(h_dst, d_dst, (size_t)nr * nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    std::memcpy(ctx->gram_report, rep, sizeof rep);
+    run.rep[13] = run.S, run.rep[15] = run.nr_pad, run.rep[16] = run.nc_pad, run.rep[17] = run.slabs, run.rep[18] = epb;
+    std::memcpy(ctx->gram_report, run.rep, sizeof run.rep);
     return FOKL_OK;
 }
 

@@ -3,13 +3,15 @@
 //   K1  basis_build_reg_kernel  fused _inputs_to_phind + evaluate_basis + term products (HBM write bound);
 //       basis_build_kernel      the same with the factor table in LDS (terms with more than 16 factors)
 //   K2a gram_valu_kernel     Gram block with per-thread register tiles + wavefront reductions (tiny blocks)
-//   K2b gram_mfma_kernel     Gram block on v_mfma_f64_16x16x4_f64 tiles, rectangular panels (round 1; path 3)
 //   K2c gram_tiles_kernel    ... as lists of 16 x 16 tiles, symmetric half skipped, register staging (1-2 tile blocks)
 //       gram_tiles_dma_kernel  the same lists staged by LDS-DMA: what every larger block runs (HALF: + one 8 x 16
 //                              half tile per wavefront on v_mfma_f64_4x4x4_4b_f64, for a ragged last row tile)
-//   K2d gram_tiles4s_kernel  the lists on v_mfma_f64_4x4x4 (opt-in, A/B)
 //   K3  resid_kernel         residual moments for the BIC
 //       reduce_slabs_kernel  fixed-order combination of per-workgroup partial sums
+//
+// Retired paths (K2b gram_mfma_kernel, round-1 rectangular panels: `path` 3; K2d gram_tiles4s_kernel, the tile lists on
+// v_mfma_f64_4x4x4: FOKL_GRAM_MFMA4=2) are kept for A/B runs in fokl_gram_dev.inc, which only development builds (make DEV=1)
+// compile.
 //
 // Compiled with -ffp-contract=off: the reference rounds every product and sum separately
 // (FoKLRoutines.py:836, 843) and K1 reproduces those roundings; fma() is used only where it is wanted
@@ -583,152 +585,6 @@ __global__ __launch_bounds__(RD_THREADS) void reduce_slabs_kernel(const double *
         out[e] = s;
     }
 }
-
-// Retired paths (round-1 panel kernel: `path` 3; the 4x4x4 form of the tile lists: FOKL_GRAM_MFMA4=2; a third LDS-DMA
-// buffer: FOKL_GRAM_BUFS=3) are kept for A/B runs but compiled only into development builds (make DEV=1).
-#ifdef FOKL_DEV_KERNELS
-// ---------------------------------------------------------------------------------------------------------
-// K2b: Gram block on fp64 MFMA tiles (v_mfma_f64_16x16x4_f64)
-// ---------------------------------------------------------------------------------------------------------
-//
-// Workgroup = 4 wavefronts.  Per step a chunk of GM_R rows of every column of a row-side panel (16*TI columns)
-// and a column-side panel is staged in LDS as [column][GM_R + 2]; the 2-double pad makes the 16-column x 4-row
-// fragment reads conflict free (bank pair = 4*col + 2*row mod 64).  Two ways of splitting the 16x16 tiles:
-//   ISPLIT  (row side > 32 columns): TI == 4, wave w owns i-tile w and all TJ j-tiles (column panel 16*TJ wide)
-//   !ISPLIT (row side <= 32 columns): every wave owns all TI i-tiles and the j-tiles {w, w + 4, ...}
-//           (column panel 64*TJ wide)
-// so the padded MFMA work stays close to the real block (56 x 58 -> 64 x 64, not 64 x 128).
-// Staging uses one 16-byte load per lane (two consecutive rows of one column); the next chunk's loads are
-// issued before the MFMAs of the current one (register double buffering).
-//
-// Operand maps (cdna_hip_programming.md section 3, f64 form): lane l supplies A[m = l & 15][k = l >> 4] and
-// B[k = l >> 4][n = l & 15]; result register v of lane l is D[m = (l >> 4) + 4 v][n = l & 15].
-
-constexpr int GM_THREADS = 256;
-constexpr int GM_R = 32;
-constexpr int GM_PITCH = GM_R + 2;
-
-template <int TI, int TJ, bool ISPLIT>
-__global__ __launch_bounds__(GM_THREADS) void gram_mfma_kernel(double *const *__restrict__ slot_ptr,
-                                                               const int *__restrict__ row_slots, int nr,
-                                                               const int *__restrict__ col_slots, int nc, int64_t n,
-                                                               double *__restrict__ slab, int nr_pad, int nc_pad,
-                                                               const double *__restrict__ zero_col)
-{
-    static_assert(!ISPLIT || TI == 4, "i-split needs one i-tile per wavefront");
-    constexpr int BI = 16 * TI;
-    constexpr int BJ = ISPLIT ? 16 * TJ : 64 * TJ;
-    constexpr int NCOL = BI + BJ;
-    constexpr int PASSES = (NCOL + 15) / 16;              // 16 columns x 16 row pairs per pass of the block
-    constexpr int MI = ISPLIT ? 1 : TI;                    // i-tiles per wave
-    __shared__ __attribute__((aligned(16))) double tile[NCOL * GM_PITCH];
-
-    const int tid = threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
-    const int i0 = blockIdx.z * BI, j0 = blockIdx.y * BJ;
-
-    // Column pointers of this thread's staging passes live in registers for the whole kernel; columns beyond the
-    // block (padding) read a zero-filled column, so every pass is one unconditional 16-byte load and all of them
-    // are in flight together (a data-dependent fix-up or branch right after a load would serialise them).
-    constexpr int PCHUNK = (NCOL + 15) / 16;
-
-    d4 acc[MI][TJ];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
-
-    // staging map: thread t loads rows {2 (t & 15), 2 (t & 15) + 1} of column (t >> 4) + 16 * pass
-    const int spair = tid & 15, scol = tid >> 4;
-    const int64_t n_chunks = (n + GM_R - 1) / GM_R;
-    const double *cp[PCHUNK];
-    uint32_t padding = 0;                                  // bit p: pass p of this thread is a padding column, which re-reads
-#pragma unroll                                             // the first 16 bytes of the zero column (a cache hit) instead
-    for (int p = 0; p < PCHUNK; ++p) {                     // of streaming 8 N bytes of zeros per padded column
-        const int c = scol + 16 * p;                       // NCOL is a multiple of 16: always a valid panel column
-        const double *ptr = zero_col;
-        bool real = false;
-        if (c < BI) {
-            if (i0 + c < nr) {
-                ptr = slot_ptr[row_slots[i0 + c]];
-                real = true;
-            }
-        } else {
-            if (j0 + (c - BI) < nc) {
-                ptr = slot_ptr[col_slots[j0 + (c - BI)]];
-                real = true;
-            }
-        }
-        cp[p] = ptr;
-        if (!real) padding |= 1u << p;
-    }
-    d2 stage[PASSES];
-    int64_t staged_row = 0;
-
-    auto issue = [&](int64_t chunk) {
-        const int64_t r = chunk * GM_R + 2 * spair;
-        staged_row = r;
-        const int64_t rc = r < n ? r : 0;                  // rows past the end are masked at commit time
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) stage[p] = load_d2(cp[p] + ((padding >> p) & 1u ? 0 : rc));
-    };
-    auto commit = [&]() {
-        const bool ok0 = staged_row < n, ok1 = staged_row + 1 < n;
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            d2 v = stage[p];
-            if (!ok0) v.x = 0.0;
-            if (!ok1) v.y = 0.0;
-            *reinterpret_cast<d2 *>(&tile[(scol + 16 * p) * GM_PITCH + 2 * spair]) = v;
-        }
-    };
-
-    int64_t chunk = blockIdx.x;
-    if (chunk < n_chunks) issue(chunk);
-    const int fm = lane & 15, fk = lane >> 4;
-    while (chunk < n_chunks) {
-        commit();
-        __syncthreads();
-        const int64_t next = chunk + gridDim.x;
-        if (next < n_chunks) issue(next);
-#pragma unroll
-        for (int k0 = 0; k0 < GM_R; k0 += 4) {
-            double af[MI], bf[TJ];
-#pragma unroll
-            for (int i = 0; i < MI; ++i) {
-                const int it = ISPLIT ? wave : i;
-                af[i] = tile[(16 * it + fm) * GM_PITCH + k0 + fk];
-            }
-#pragma unroll
-            for (int j = 0; j < TJ; ++j) {
-                const int jt = ISPLIT ? j : wave + 4 * j;
-                bf[j] = tile[(BI + 16 * jt + fm) * GM_PITCH + k0 + fk];
-            }
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < TJ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-        chunk = next;
-    }
-
-    double *out = slab + (size_t)blockIdx.x * nr_pad * nc_pad;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int it = ISPLIT ? wave : i;
-                const int jt = ISPLIT ? j : wave + 4 * j;
-                const int gi = i0 + 16 * it + fk + 4 * v;
-                const int gj = j0 + 16 * jt + fm;
-                out[(size_t)gi * nc_pad + gj] = acc[i][j][v];
-            }
-}
-
-#endif  // FOKL_DEV_KERNELS
 
 // ---------------------------------------------------------------------------------------------------------
 // K2c: Gram block as lists of 16 x 16 MFMA tiles (round 2; the default MFMA path)
@@ -1309,168 +1165,6 @@ void gram_tiles_dma_kernel(const GramGroup *__restrict__ groups, int ct_count, i
         }
     }
 }
-
-#ifdef FOKL_DEV_KERNELS
-// ---------------------------------------------------------------------------------------------------------
-// K2d: the same tile lists on v_mfma_f64_4x4x4_4b_f64 (opt-in: FOKL_GRAM_MFMA4=2)
-// ---------------------------------------------------------------------------------------------------------
-//
-// v_mfma_f64_4x4x4_4b_f64: four independent 4 x 4 x 4 blocks, 512 flops; 71-75 TFLOP/s in a C++ loop on register
-// operands (tools/mfma_f64_peak.hip), where the same loop on the 16x16x4 form reads 47-49 -- an artefact of that loop, as
-// it turned out: written in assembly the 16x16x4 form issues every 64 cycles, 78 TFLOP/s (tools/mfma_f64_issue.hip), so
-// the premise of this kernel (a faster instruction) does not hold and neither did its result.  Lane maps of
-// the latter (tools/mfma_f64_4x4_map.hip, by experiment): A[blk][i][k] sits in lane i + 4 blk + 16 k, B[blk][k][j]
-// in lane j + 4 blk + 16 k, D[blk][i][j] in lane j + 4 blk + 16 i.  Here block blk takes the rows blk + 4 k of a
-// group of 16 rows, so one instruction multiplies 4 row-side by 4 column-side columns over 16 rows; a 16 x 16 tile
-// is 4 x 4 such instructions on 4 + 4 operand fragments per group of 16 rows, and its 16 accumulators hold four
-// partial sums each (one per block) that are added across lanes once, at the end.  The price is registers -- 32 per
-// tile instead of 8 -- so a wavefront has at most 4 tiles, a group 16 tiles on at most 8 staged column tiles (more
-// groups per launch, each re-staging the columns of its i-tiles), and the LDS pitch is 32 + 8: lanes
-// i + 4 blk + 16 k read element (column i, row blk + 4 k), conflict-free in both halves of a ds_read_b64 when
-// 2 * pitch = 16 (mod 64); the fragment reads are volatile LDS loads, because merged into ds_read2_b64 they run at
-// half the rate on 32 banks, where columns i and i + 2 of this pitch collide.
-// Result (N = 1e6, back to back, us; 16x16x4 lists / this kernel): 28 x 38: 92 / 77, 56 x 58: 132 / 127,
-// 56 x 80: 167 / 188, 56 x 128: 290 / 353, 56 x 176: 411 / 509, 28 x 120: 181 / 194 -- the faster instruction does
-// not pay beyond the smallest blocks.  A second form (8 wavefronts, 40 tiles per group, two LDS buffers and two or
-// three sets of staging registers with the loads and their s_waitcnt written by hand, the two wavefronts of a SIMD
-// committing at different steps) read 295 / 455 us on 56 x 128 / 56 x 176 whatever the depth of its pipeline, its
-// matrix pipe busy 55 % of the time (SQ_VALU_MFMA_BUSY_CYCLES) with the MFMAs alone worth 177 us and everything but
-// the MFMAs 185 us: the two do not overlap, for a reason the counters at hand did not name.  It was withdrawn; this
-// one stays for A/B runs.  The default is the 16x16x4 kernel for every launch.
-constexpr int G4_PITCH = 40;
-constexpr int G4S_THREADS = 256;
-constexpr int G4S_MAX_NT = 4;
-constexpr int G4S_MAX_CT = 8;
-
-template <int NT, int P>
-__global__ __launch_bounds__(G4S_THREADS, 2) void gram_tiles4s_kernel(double *const *__restrict__ slot_ptr,
-                                                                      const int *__restrict__ icols, int nci,
-                                                                      const GramGroup *__restrict__ groups, int ct_count,
-                                                                      int64_t n, double *__restrict__ slab, int nr_pad,
-                                                                      int nc_pad, const double *__restrict__ zero_col,
-                                                                      const double *__restrict__ base)
-{
-    extern __shared__ __attribute__((aligned(16))) double g4s_tile[];
-    constexpr int R = 32, pitch = G4_PITCH;
-    const GramGroup &g = groups[blockIdx.y];
-    const int tid = threadIdx.x, lane = tid % WAVE;
-    const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
-    const int spair = tid & 15, scol = tid >> 4;               // pass p: column scol of the group's p-th column tile
-
-    uint32_t cb[P];
-    uint32_t padding = 0;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const uint32_t u = p < ct_count ? g.col_units[p][scol] : 0x80000000u;
-        cb[p] = u & 0x7fffffffu;
-        padding |= (u >> 31) << p;
-    }
-
-    const int frag = (lane & 3) * pitch + ((lane >> 2) & 3) + 4 * (lane >> 4);
-    int aoff[NT], boff[NT];
-#pragma unroll
-    for (int k = 0; k < NT; ++k) {
-        aoff[k] = frag + 16 * (int)g.a[wave][k] * pitch;
-        boff[k] = frag + 16 * (int)g.b[wave][k] * pitch;
-    }
-    int real_tiles = 0;
-#pragma unroll
-    for (int k = 0; k < NT; ++k) real_tiles += g.oi[wave][k] != 0xFFFF ? 1 : 0;
-    real_tiles = __builtin_amdgcn_readfirstlane(real_tiles);
-    double acc[NT][4][4];
-#pragma unroll
-    for (int k = 0; k < NT; ++k)
-#pragma unroll
-        for (int ia = 0; ia < 4; ++ia)
-#pragma unroll
-            for (int jb = 0; jb < 4; ++jb) acc[k][ia][jb] = 0.0;
-
-    const int64_t n_chunks = (n + R - 1) / R;
-    const int64_t stride = gridDim.x;
-    d2 stage[P];
-
-    auto issue = [&](int64_t chunk) {
-        const int64_t r = chunk * R + 2 * spair;
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            const int64_t rc = ((padding >> p) & 1u) || r >= n ? 0 : r;
-            uint32_t units = cb[p];
-            asm volatile("" : "+v"(units));
-            stage[p] = load_d2(base + ((size_t)units << 5) + rc);
-        }
-    };
-    auto commit = [&](int64_t chunk) {
-        const int64_t r = chunk * R + 2 * spair;
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            d2 v = stage[p];
-            if (r >= n) v.x = 0.0;
-            if (r + 1 >= n) v.y = 0.0;
-            *reinterpret_cast<d2 *>(&g4s_tile[(16 * p + scol) * pitch + 2 * spair]) = v;
-        }
-    };
-    auto multiply = [&]() {
-        constexpr int STEPS = 2 * NT;
-        double af[2][4], bf[2][4];
-        typedef __attribute__((address_space(3))) const volatile double lds_cv_double;
-        lds_cv_double *lds_v = (lds_cv_double *)g4s_tile;
-        auto fetch = [&](int s, int buf) {
-            const int k = s % NT, rows = 16 * (s / NT);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                af[buf][q] = lds_v[aoff[k] + 4 * q * pitch + rows];      // (volatile: see above)
-                bf[buf][q] = lds_v[boff[k] + 4 * q * pitch + rows];
-            }
-        };
-        fetch(0, 0);
-#pragma unroll
-        for (int s = 0; s < STEPS; ++s) {
-            if (s + 1 < STEPS) fetch(s + 1, (s + 1) & 1);
-            __builtin_amdgcn_sched_barrier(0);
-            if (s % NT < real_tiles) {
-#pragma unroll
-                for (int ia = 0; ia < 4; ++ia)
-#pragma unroll
-                    for (int jb = 0; jb < 4; ++jb)
-                        acc[s % NT][ia][jb] = __builtin_amdgcn_mfma_f64_4x4x4f64(af[s & 1][ia], bf[s & 1][jb],
-                                                                                acc[s % NT][ia][jb], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-
-    int64_t chunk = blockIdx.x;
-    if (chunk < n_chunks) issue(chunk);
-    while (chunk < n_chunks) {
-        commit(chunk);
-        __syncthreads();
-        const int64_t next = chunk + stride;
-        if (next < n_chunks) issue(next);
-        multiply();
-        __syncthreads();
-        chunk = next;
-    }
-
-    double *out = slab + (size_t)blockIdx.x * nr_pad * nc_pad;
-    asm volatile("" ::: "memory");
-    const int dj = lane & 3, di = lane >> 4;
-#pragma unroll
-    for (int k = 0; k < NT; ++k) {
-        const int oi = g.oi[wave][k], oj = g.oj[wave][k];
-#pragma unroll
-        for (int ia = 0; ia < 4; ++ia)
-#pragma unroll
-            for (int jb = 0; jb < 4; ++jb) {
-                double v = acc[k][ia][jb];
-                v += __shfl_xor(v, 4, WAVE);
-                v += __shfl_xor(v, 8, WAVE);
-                if (oi != 0xFFFF && (lane & 12) == 0)
-                    out[(size_t)(16 * oi + 4 * ia + di) * nc_pad + 16 * oj + 4 * jb + dj] = v;
-            }
-    }
-}
-
-#endif  // FOKL_DEV_KERNELS
 
 // reduce_slabs_kernel for gram_tiles_kernel's slabs: element (i, j) of the caller's block sits at internal column
 // perm[j]; a position in a tile below the diagonal of the internal tile grid was not computed and is read from its

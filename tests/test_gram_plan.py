@@ -156,3 +156,37 @@ def test_narrow_blocks_split_the_k_steps_over_wavefronts():
     pl = _capi.gram_plan(np.arange(2, 10, dtype=np.int32), np.concatenate([[0], np.arange(2, 10), [1]]).astype(np.int32))
     assert pl['i_tiles'] == 1 and pl['j_tiles'] == 1 and pl['ks'] == 4 and pl['nt'] == 1
     assert np.all(pl['tiles'][0, :, 0, 2:] == 0)              # all four wavefronts work on the one tile
+
+
+# the (nr, nc) of tests/test_fit_kernels_device.py's table that the lists above do not have
+DEVICE_SHAPES = [(16, 30), (52, 120), (120, 122), (104, 300)]
+KNOBS = ['FOKL_GRAM_PATH', 'FOKL_GRAM_MFMA4', 'FOKL_GRAM_DMA', 'FOKL_GRAM_HALF', 'FOKL_GRAM_BUFS', 'FOKL_GRAM_LOADERS',
+         'FOKL_GRAM_RB', 'FOKL_GRAM_DEPTH', 'FOKL_GRAM_WGS']
+
+
+def test_every_plan_stays_within_the_kernels_the_product_instantiates(monkeypatch):
+    """The product library holds gram_tiles_kernel only as the k-split teams <NT 1, P 4, DEPTH 1, KS 2 | 4> and
+    gram_tiles_dma_kernel as <NT8 1 .. 5> plain and <NT8 1 .. 4> with half-tile slots (csrc/fokl_hip.hip: ksplit_kernel,
+    tiles_dma_kernel); a plan outside them is refused, not served by another instance.  The planner never makes one: every
+    nr up to 80 against every nc up to 200 and the shapes of the lists above, as the search's pattern and as disjoint lists."""
+    for name in KNOBS:                                    # a development build plans what its knobs say: none set
+        monkeypatch.delenv(name, raising=False)
+    seen = set()
+    shapes = [(nr, nc) for nr in range(1, 81) for nc in range(1, 201)] + SHAPES + WIDE_SHAPES + DEVICE_SHAPES
+    for nr, nc in shapes:
+        rs = np.arange(2, 2 + nr, dtype=np.int32)
+        model = np.arange(2 + nr, 2 + nr + max(nc - nr - 2, 0))
+        search = np.concatenate([[0], model, rs, [1]])[:nc] if nc >= nr + 2 else np.concatenate([rs, [0, 1]])[:nc]
+        for cs in (search.astype(np.int32), np.arange(2 + nr, 2 + nr + nc, dtype=np.int32)):
+            pl = _capi.gram_plan(rs, cs)
+            if pl['ks'] > 1:
+                assert pl['nt'] == 1 and pl['depth'] == 1 and pl['rows_per_chunk'] == 32, (nr, nc, pl['nt'], pl['depth'])
+                assert pl['ct'] <= 4, (nr, nc, pl['ks'], pl['ct'])                # P = 4 staging passes
+                seen.add(('tiles', pl['ks'], int(pl['ct'])))
+            else:
+                half = bool(pl['half'].any())
+                assert pl['depth'] == 1 and pl['rows_per_chunk'] == 32 and 1 <= pl['nt'] <= (8 if half else 10), (nr, nc, pl['nt'])
+                seen.add(('dma', (pl['nt'] + 1) // 2, half))
+    # and it reaches every one of them
+    assert {s for s in seen if s[0] == 'dma'} == {('dma', k, h) for k in (1, 2, 3, 4, 5) for h in (False, True)} - {('dma', 5, True)}
+    assert {s[1:] for s in seen if s[0] == 'tiles'} == {(4, 1), (2, 2)}       # one tile on one column tile, two tiles on two
