@@ -34,6 +34,7 @@ from . import engine as _engine
 from . import update as _update
 from . import optimize as _optimize
 from . import population as _population
+from . import resample as _resample
 
 
 def _column_min_max(a):
@@ -1305,6 +1306,32 @@ class FoKL:
             inputs = self.clean(inputs, kwargs_from_other=kwargs_to_clean)
         kwargs.setdefault('device', self._backend())
         return _population.propagate(phis=self.phis, kernel=self.kernel, inputs=inputs, data=data, **kwargs)
+
+    def resample(self, inputs=None, data=None, betas=None, mtx=None, **kwargs):
+        """Resample the fitted model's posterior on the device: many independent Gibbs chains of the model ``fit`` chose,
+        with sigma^2 and tau^2 kept and a split R-hat over the chains -- ``resample.resample`` with this model's ``mtx``,
+        ``phis``, ``kernel`` and the hyper-parameters the fit used (``a``, ``b``, ``atau``, ``btau`` as ``fit`` left them),
+        which documents the keywords -- chains, draws, burnin, thin, seed, init, keep -- and the result.  ``inputs`` /
+        ``data`` default to the model's own cleaned training set (pass another cleaned set, or ``mtx``, to override).
+        ``betas`` is accepted for symmetry with ``propagate`` / ``optimize`` and only checked against ``mtx``: the chains
+        start from the hyper-parameters, not from earlier draws.  ``fit``'s results, ``setnos`` and numpy's random stream
+        are left alone."""
+        known = ('chains', 'draws', 'burnin', 'thin', 'seed', 'init', 'keep', 'device')
+        unknown = [k for k in kwargs if k not in known]
+        if unknown:
+            raise ValueError(f"Unexpected keyword argument: {unknown[0]} (resample takes {', '.join(known)})")
+        if mtx is None:
+            mtx = getattr(self, 'mtx', None)
+        if mtx is None:
+            raise ValueError("resample needs a fitted model: call fit first (there is no interaction matrix mtx)")
+        if betas is not None and np.shape(betas)[-1] != np.atleast_2d(mtx).shape[0] * (np.size(mtx) > 0) + 1:
+            raise ValueError("betas do not belong to mtx: they need terms + 1 columns")
+        if inputs is None:
+            inputs = getattr(self, 'inputs', None)
+        if data is None:
+            data = getattr(self, 'data', None)
+        kwargs.setdefault('device', self._backend())
+        return _resample.resample(mtx, self.phis, self.kernel, inputs, data, self.a, self.b, self.atau, self.btau, **kwargs)
 
     def to_pyomo(self, *args, **kwargs):
         raise NotImplementedError("to_pyomo (FR:1796-1805) is outside the scope of this build")

@@ -19,6 +19,7 @@ K_INTEGRATE, K_BAND = 7, 8
 K_OPTIMIZE = 9
 K_OPTIMIZE_SYSTEM = 10
 K_POPULATION = 11
+K_RESAMPLE = 12
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
@@ -27,6 +28,11 @@ SLOT_ONES, SLOT_Y, SLOT_FIRST_FREE = 0, 1, 2
 PREDICT_NONE, PREDICT_VALU_LDS, PREDICT_VALU_GLOBAL, PREDICT_MFMA = 0, 1, 2, 3     # fokl_predict_report's kernel ids
 POPULATION_COEFFICIENTS = ('none', 'registers', 'table')      # fokl_population_report: where the draw coefficients lived
 POPULATION_MAX_CUTS = 32
+RESAMPLE_MAX_COLUMNS = 768                # fokl_resample_chains: 12 eigen-coordinates per lane
+RESAMPLE_ATTEMPT_CAP = 64                 # Marsaglia-Tsang attempts per gamma variate
+RESAMPLE_SEGMENTS = 3                     # per-chain sums: first half, second half, the odd last iteration
+# fokl_embedded_rng's purposes of the resampler (csrc/fokl_philox.h)
+RES_BETA, RES_SIG_NORMAL, RES_SIG_UNIFORM, RES_TAU_NORMAL, RES_TAU_UNIFORM, RES_START = 3, 4, 5, 6, 7, 8
 # fokl_fit_report's kernel names, by id: Gram / residual / basis launch
 GRAM_KERNELS = ('none', 'valu', 'tiles', 'dma', 'panel', 'tiles4')
 RESID_KERNELS = ('none', 'columns', 'matrix_free')
@@ -67,6 +73,9 @@ SIGNATURES = {
     'fokl_fit_report': (c_int, [c_vp, c_int, c_vp, c_int]),
     'fokl_population_stats': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     'fokl_population_report': (c_int, [c_vp, c_vp]),
+    'fokl_resample_chains': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_vp, c_vp, c_int,
+                                     c_int, c_int, ctypes.c_uint32, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_resample_report': (c_int, [c_vp, c_vp]),
     'fokl_read_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_write_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_timing_enable': (c_int, [c_vp, c_int]),
@@ -268,8 +277,8 @@ def _check(rc, ctx=None):
 
 
 def embedded_rng(seed, chain, draw, purpose, count):
-    """The numbers the embedded-GP sampler draws (fokl_embedded_rng: Philox 4x32-10 keyed by (seed, chain), counter
-    (draw, purpose, index)); host code, no device."""
+    """The numbers the embedded-GP sampler and the resampler draw (fokl_embedded_rng: Philox 4x32-10 keyed by (seed, chain),
+    counter (draw, purpose, index); purposes 0 .. 2 the embedded sampler's, RES_* the resampler's); host code, no device."""
     out = np.empty(int(count), dtype=np.float64)
     _check(load().fokl_embedded_rng(int(seed) & 0xFFFFFFFF, int(chain), int(draw), int(purpose), int(count), _ptr(out)))
     return out
@@ -1935,6 +1944,46 @@ class DeviceContext:
         v = [int(x) for x in out]
         return dict(coefficients=POPULATION_COEFFICIENTS[v[0]], grid=v[1], draw_blocks=v[2], chunks=v[3],
                     tiles_per_chunk=v[4], row_tiles=v[5], lds_bytes=v[6], pieces=v[7])
+
+    def resample_chains(self, lamb, qty, shift, astar, atau_star, b, btau, dtd, sigsqd0, tausqd0, burnin, draws, thin, seed,
+                        rows=True, chains_per_group=0, attempt_cap=0):
+        """fokl_resample_chains: one Gibbs chain per entry of ``sigsqd0`` / ``tausqd0`` in the eigenbasis (lamb, qty [P + 1]),
+        burnin + draws iterations each -> dict(w [chains, kept, P + 1], sigsqd, tausqd, attempts [chains, kept] -- None
+        without ``rows`` --, sums [chains, 3, 2, P + 3], counts [chains, 4]); resample.resample_host is its statement and
+        documents the fields.  ``chains_per_group`` / ``attempt_cap``: 0 the defaults; test hooks."""
+        lamb, qty, shift, sigsqd0, tausqd0 = (np.ascontiguousarray(np.reshape(v, -1), dtype=np.float64)
+                                              for v in (lamb, qty, shift, sigsqd0, tausqd0))
+        p1, chains = lamb.shape[0], sigsqd0.shape[0]
+        if qty.shape[0] != p1 or shift.shape[0] != p1 or tausqd0.shape[0] != chains:
+            raise ValueError("resample_chains: lamb, qty, shift [P + 1] and one start per chain")
+        burnin, draws, thin = int(burnin), int(draws), int(thin)
+        if draws < 1 or thin < 1:
+            raise ValueError("resample_chains: draws >= 1 and thin >= 1")
+        kept = -(-draws // thin)
+        w = sig = tau = att = None
+        if rows:
+            w = np.empty((chains, kept, p1), dtype=np.float64)
+            sig, tau = np.empty((chains, kept), dtype=np.float64), np.empty((chains, kept), dtype=np.float64)
+            att = np.empty((chains, kept), dtype=np.int32)
+        sums = np.empty((chains, RESAMPLE_SEGMENTS, 2, p1 + 2), dtype=np.float64)
+        counts = np.empty((chains, 4), dtype=np.int64)
+        self._ck(self._lib.fokl_resample_chains(self._h, p1, _ptr(lamb), _ptr(qty), _ptr(shift), float(astar), float(atau_star),
+                                                float(b), float(btau), float(dtd), chains, _ptr(sigsqd0), _ptr(tausqd0), burnin,
+                                                draws, thin, int(seed) & 0xFFFFFFFF, int(chains_per_group), int(attempt_cap),
+                                                _ptr(w), _ptr(sig), _ptr(tau), _ptr(att), _ptr(sums), _ptr(counts)))
+        return dict(w=w, sigsqd=sig, tausqd=tau, attempts=att, sums=sums, counts=counts)
+
+    def resample_report(self):
+        """What the last ``resample_chains`` on this context ran (fokl_resample_report): ``instance`` (the kernel's
+        eigen-coordinates per lane: 1, 2, 3, 4, 6, 8 or 12), ``chains``, ``iterations`` per chain (burn-in included),
+        ``chains_per_group`` (wavefronts per workgroup), the ``grid``, Marsaglia-Tsang ``attempts`` in all and
+        ``attempts_max`` (the most one gamma variate needed), ``kernel_ms``, ``flagged`` chains and the rows ``kept`` per
+        chain.  Zeros after a refused call."""
+        out = np.zeros(10, dtype=np.int64)
+        self._ck(self._lib.fokl_resample_report(self._h, _ptr(out)))
+        v = [int(x) for x in out]
+        return dict(instance=v[0], chains=v[1], iterations=v[2], chains_per_group=v[3], attempts=v[4], attempts_max=v[5],
+                    kernel_ms=v[6] / 1000.0, grid=v[7], flagged=v[8], kept=v[9])
 
     def _fit_report(self, which, count):
         out = np.zeros(count, dtype=np.int64)

@@ -7,10 +7,10 @@
 
 extern "C" int fokl_embedded_rng(uint32_t seed, uint32_t chain, uint32_t draw, int purpose, int count, double *out)
 {
-    if (count < 0 || (count > 0 && !out) || purpose < fokl::EMB_PURPOSE_MOMENTUM || purpose > fokl::EMB_PURPOSE_SEARCH)
+    if (count < 0 || (count > 0 && !out) || purpose < fokl::EMB_PURPOSE_MOMENTUM || purpose > fokl::EMB_PURPOSE_LAST)
         return FOKL_ERR_ARG;
     for (int j = 0; j < count; ++j)
-        out[j] = purpose == fokl::EMB_PURPOSE_ACCEPT ? fokl::emb_uniform(seed, chain, draw, (uint32_t)purpose, (uint32_t)j)
-                                                     : fokl::emb_normal(seed, chain, draw, (uint32_t)purpose, (uint32_t)j);
+        out[j] = fokl::emb_purpose_is_uniform(purpose) ? fokl::emb_uniform(seed, chain, draw, (uint32_t)purpose, (uint32_t)j)
+                                                       : fokl::emb_normal(seed, chain, draw, (uint32_t)purpose, (uint32_t)j);
     return FOKL_OK;
 }

@@ -83,6 +83,15 @@ extern "C" int fokl_population_stats(fokl_ctx *, const int32_t *, int, const dou
 }
 extern "C" int fokl_population_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Neither do the resampler's chains (fokl_resample_device.inc); their statement is resample.resample_host.
+extern "C" int fokl_resample_chains(fokl_ctx *, int, const double *, const double *, const double *, double, double, double,
+                                    double, double, int, const double *, const double *, int, int, int, uint32_t, int, int,
+                                    double *, double *, double *, int32_t *, double *, int64_t *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_resample_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // The device chain engine and page-locked memory do not exist in these builds: the native search (fokl_search.cpp) is
 // then created without an engine and falls back to ordinary memory for its tapes.
 extern "C" int fokl_host_alloc(size_t, void **out)

@@ -1,5 +1,6 @@
-// The random numbers of the embedded-GP sampler (fokl_embedded_device.inc, fokl_embedded.cpp): Philox 4x32-10, counter
-// based, so the kernel and the host statement draw the same numbers without sharing a state.  One header for both sides.
+// The random numbers of the embedded-GP sampler (fokl_embedded_device.inc, fokl_embedded.cpp) and of the posterior
+// resampler (fokl_resample_device.inc): Philox 4x32-10, counter based, so the kernel and the host statement draw the same
+// numbers without sharing a state.  One header for both sides.
 //
 //   key     = (seed, chain)                  counter = (draw, purpose, index, 0)
 //   words   = philox4x32_10(counter, key)    -> two uniforms of 53 bits, u_a from words 0-1 and u_b from words 2-3
@@ -24,6 +25,20 @@ namespace fokl {
 constexpr int EMB_PURPOSE_MOMENTUM = 0;   // the momentum of transition `draw`
 constexpr int EMB_PURPOSE_ACCEPT = 1;     // its accept uniform (index 0)
 constexpr int EMB_PURPOSE_SEARCH = 2;     // the momentum of the step search that runs at `draw` (0, or the mass update's)
+// fokl_resample_device.inc / resample.py: `draw` is the Gibbs iteration (burn-in included)
+constexpr int RES_PURPOSE_BETA = 3;       // the normal of eigen-coordinate `index`
+constexpr int RES_PURPOSE_SIG_NORMAL = 4; // sigma^2's gamma: the normal of Marsaglia-Tsang attempt `index` ...
+constexpr int RES_PURPOSE_SIG_UNIFORM = 5;   // ... and its uniform
+constexpr int RES_PURPOSE_TAU_NORMAL = 6; // tau^2's gamma: the same two
+constexpr int RES_PURPOSE_TAU_UNIFORM = 7;
+constexpr int RES_PURPOSE_START = 8;      // draw 0: the uniforms behind a dispersed start (index 0 sigma^2, 1 tau^2)
+constexpr int EMB_PURPOSE_LAST = RES_PURPOSE_START;
+
+FOKL_HD bool emb_purpose_is_uniform(int purpose)
+{
+    return purpose == EMB_PURPOSE_ACCEPT || purpose == RES_PURPOSE_SIG_UNIFORM || purpose == RES_PURPOSE_TAU_UNIFORM ||
+           purpose == RES_PURPOSE_START;
+}
 
 FOKL_HD void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
 {

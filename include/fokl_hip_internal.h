@@ -20,6 +20,9 @@
  *                              (fokl_gpy_amd/population.py), and what its last launch ran
  *   fokl_fit_report            the same for the fit's kernels: which Gram instance, residual branch and basis kernels the
  *                              last launches ran, with their launch parameters
+ *   fokl_resample_chains / fokl_resample_report
+ *                              many independent Gibbs chains of a fitted model, drawing their own counter-based numbers
+ *                              (fokl_gpy_amd/resample.py)
  *   fokl_embedded_hmc / fokl_embedded_rng
  *                              the HMC chains of GPs embedded in a user equation (fokl_gpy_amd/embedded.py) and their
  *                              counter-based random numbers as the host sees them
@@ -726,9 +729,56 @@ int fokl_embedded_hmc(fokl_ctx *ctx, int n_gps, int n_coef, const int32_t *term_
 /*
  * out[j], j < count: the numbers chain `chain` of a run seeded `seed` draws at `draw` for `purpose` -- 0 the momentum of
  * transition `draw` (standard normals, one per parameter), 1 its accept uniform (j = 0), 2 the momentum of the step
- * search that runs at `draw` (0 at the start, 500 after the mass update).  Host code, no device (csrc/fokl_philox.h).
+ * search that runs at `draw` (0 at the start, 500 after the mass update); and those of fokl_resample_chains, whose `draw`
+ * is the Gibbs iteration: 3 the normals of the eigen-coordinates j, 4 / 5 the normal / uniform of attempt j of sigma^2's
+ * gamma variate, 6 / 7 of tau^2's, 8 the uniforms behind a dispersed start (draw 0; j = 0 sigma^2, 1 tau^2).
+ * Host code, no device (csrc/fokl_philox.h).
  */
 int fokl_embedded_rng(uint32_t seed, uint32_t chain, uint32_t draw, int purpose, int count, double *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Resampling a fitted model's posterior (csrc/fokl_resample_device.inc; fokl_gpy_amd/resample.py)           */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_RESAMPLE_REPORT_LEN 10
+#define FOKL_RESAMPLE_MAX_COLUMNS 768      /* 12 eigen-coordinates per lane: FOKL_DCHAIN_MAX_COLUMNS' bar */
+#define FOKL_RESAMPLE_ATTEMPT_CAP 64       /* Marsaglia-Tsang attempts per gamma variate unless the call says otherwise */
+#define FOKL_RESAMPLE_SEGMENTS 3           /* per-chain sums: first half, second half, the odd last iteration */
+
+/*
+ * `chains` independent chains of the recursion fokl_gibbs_chain documents (include/fokl_hip.h), burnin + draws iterations
+ * each, in the eigenbasis (lamb, qty [p1]; astar, atau_star, b, btau, dtd as there), chain c started at sigsqd0[c],
+ * tausqd0[c].  Random numbers: Philox 4x32-10 keyed by (seed, c), counter (iteration, purpose, index) -- fokl_embedded_rng's
+ * purposes 3 .. 7; the gamma variates by Marsaglia-Tsang (shapes >= 1), at most `attempt_cap` attempts each (0: the default).
+ * One wavefront per chain, `chains_per_group` chains per workgroup (0: the default, 4; a test hook: the results do not
+ * depend on it), no atomics: the same arguments give the same bits.
+ * Outputs (host): with rows kept, iteration burnin + r thin of chain c is row c kept + r, kept = ceil(draws / thin), of
+ *   w_out [chains kept, p1], sig_out, tau_out [chains kept] (the iteration's new sigsqd, tausqd) and attempts_out
+ *   [chains kept] (attempts of its two gamma variates); all four NULL: no rows.
+ *   sums_out [chains, 3, 2, p1 + 2]: over the first half (draws / 2 iterations), the second half and the odd last of the
+ *   post-burn-in iterations, the sums and the sums of squares of w_i - shift[i] (i < p1), sigsqd (p1) and tausqd (p1 + 1),
+ *   each accumulated in iteration order.
+ *   counts_out [chains, 4]: the first flagged iteration or -1, why (1: bstar < 0, sigsqd is NaN as FR:1538-1541 leaves
+ *   it; 2: a gamma variate met the attempt cap and is NaN), attempts in all, the most attempts of one variate.  A flagged
+ *   chain runs on, NaN from there; the other chains are not affected.
+ * Refused (FOKL_ERR_ARG with a text, nothing is launched): p1 > FOKL_RESAMPLE_MAX_COLUMNS; a shape below 1; rows that do
+ * not fit the device's free memory.  The dataset, its slots and pending launches are left alone.  Blocking.
+ * The statement the kernel is tested against is resample.resample_host.  Kernel time: FOKL_K_RESAMPLE.
+ */
+int fokl_resample_chains(fokl_ctx *ctx, int p1, const double *lamb, const double *qty, const double *shift,
+                         double astar, double atau_star, double b, double btau, double dtd, int chains,
+                         const double *sigsqd0, const double *tausqd0, int burnin, int draws, int thin, uint32_t seed,
+                         int chains_per_group, int attempt_cap, double *w_out, double *sig_out, double *tau_out,
+                         int32_t *attempts_out, double *sums_out, int64_t *counts_out);
+
+/*
+ * The last fokl_resample_chains call on `ctx`, out [FOKL_RESAMPLE_REPORT_LEN] (host):
+ *   out[0]  the instance that ran: eigen-coordinates per lane (1, 2, 3, 4, 6, 8 or 12); zeros after a refused call
+ *   out[1]  chains     out[2]  iterations per chain (burn-in included)     out[3]  wavefronts (chains) per workgroup
+ *   out[4]  Marsaglia-Tsang attempts in all     out[5]  the most any variate needed     out[6]  kernel microseconds
+ *   out[7]  the grid     out[8]  flagged chains     out[9]  rows kept per chain (the call's kept, also without rows)
+ */
+int fokl_resample_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* What a prediction ran (csrc/fokl_predict.inc)                                                             */
