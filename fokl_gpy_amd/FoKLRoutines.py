@@ -34,6 +34,7 @@ from . import engine as _engine
 from . import update as _update
 from . import optimize as _optimize
 from . import population as _population
+from . import score as _score
 from . import resample as _resample
 
 
@@ -1332,6 +1333,47 @@ class FoKL:
             data = getattr(self, 'data', None)
         kwargs.setdefault('device', self._backend())
         return _resample.resample(mtx, self.phis, self.kernel, inputs, data, self.a, self.b, self.atau, self.btau, **kwargs)
+
+    def score(self, post=None, inputs=None, data=None, clean=False, betas=None, sigsqd=None, mtx=None, **kwargs):
+        """Score the fitted model pointwise over every posterior draw on the device: WAIC and PSIS-LOO of the training rows,
+        or the log predictive density of held-out rows -- ``score.score`` with this model's ``mtx``, ``phis`` and ``kernel``,
+        which documents the keywords -- method, draws -- and the result.  ``post`` is what ``resample`` returned (its
+        ``betas`` and ``sigsqd``), or pass ``betas=`` and ``sigsqd=``: the log density needs sigma^2 per draw, which a fit
+        does not keep.  ``inputs`` / ``data`` default to the model's own cleaned training set; ``clean=True`` normalises
+        other inputs with the model's ``minmax`` exactly as ``evaluate`` does.  Numpy's random stream and ``setnos`` are
+        left alone."""
+        if post is not None:
+            if betas is not None or sigsqd is not None:
+                raise ValueError("score takes a resample's result OR betas= and sigsqd=, not both")
+            try:
+                betas, sigsqd = post['betas'], post['sigsqd']
+            except (KeyError, TypeError, IndexError):
+                raise ValueError("score needs what resample returned (betas and sigsqd per draw) as its first argument") from None
+            if betas is None or sigsqd is None:
+                raise ValueError("this resample kept no rows (keep=...): score needs betas and sigsqd per draw")
+        if betas is None or sigsqd is None:
+            raise ValueError("score needs sigma^2 for every draw and a fit keeps the betas only: draw both with "
+                             "post = model.resample(...) and call model.score(post), or pass betas= and sigsqd=")
+        if mtx is None:
+            mtx = getattr(self, 'mtx', None)
+        if mtx is None:
+            raise ValueError("score needs a fitted model: call fit first (there is no interaction matrix mtx)")
+        if inputs is None:
+            if _str_to_bool(clean):
+                warnings.warn("Cleaning was already performed on default 'inputs', so overriding 'clean' to False.",
+                              category=UserWarning)
+            inputs = getattr(self, 'inputs', None)
+            if data is None:
+                data = getattr(self, 'data', None)
+        elif _str_to_bool(clean):
+            if not hasattr(self, 'minmax'):
+                raise ValueError("score(clean=True) needs the model's minmax (set by clean / fit, or model.minmax = "
+                                 "[[min, max], ...])")
+            kwargs_to_clean = dict(_CLEAN_DEFAULTS)
+            kwargs_to_clean['minmax'] = self.minmax
+            inputs = self.clean(inputs, kwargs_from_other=kwargs_to_clean)
+        kwargs.setdefault('device', self._backend())
+        return _score.score(betas, sigsqd, mtx, self.phis, self.kernel, inputs, data, **kwargs)
 
     def to_pyomo(self, *args, **kwargs):
         raise NotImplementedError("to_pyomo (FR:1796-1805) is outside the scope of this build")

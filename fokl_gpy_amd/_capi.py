@@ -20,6 +20,7 @@ K_OPTIMIZE = 9
 K_OPTIMIZE_SYSTEM = 10
 K_POPULATION = 11
 K_RESAMPLE = 12
+K_SCORE = 13
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
@@ -28,6 +29,8 @@ SLOT_ONES, SLOT_Y, SLOT_FIRST_FREE = 0, 1, 2
 PREDICT_NONE, PREDICT_VALU_LDS, PREDICT_VALU_GLOBAL, PREDICT_MFMA = 0, 1, 2, 3     # fokl_predict_report's kernel ids
 POPULATION_COEFFICIENTS = ('none', 'registers', 'table')      # fokl_population_report: where the draw coefficients lived
 POPULATION_MAX_CUTS = 32
+SCORE_INSTANCES = ('none', 'waic', 'waic_loo')                # fokl_score_report: the instance of score_kernel that ran
+SCORE_MAX_TAIL = 512                      # fokl_score_rows: entries (M + 1) of a row's list of largest log ratios in LDS
 RESAMPLE_MAX_COLUMNS = 768                # fokl_resample_chains: 12 eigen-coordinates per lane
 RESAMPLE_ATTEMPT_CAP = 64                 # Marsaglia-Tsang attempts per gamma variate
 RESAMPLE_SEGMENTS = 3                     # per-chain sums: first half, second half, the odd last iteration
@@ -76,6 +79,8 @@ SIGNATURES = {
     'fokl_resample_chains': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_vp, c_vp, c_int,
                                      c_int, c_int, ctypes.c_uint32, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_resample_report': (c_int, [c_vp, c_vp]),
+    'fokl_score_rows': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    'fokl_score_report': (c_int, [c_vp, c_vp]),
     'fokl_read_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_write_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_timing_enable': (c_int, [c_vp, c_int]),
@@ -1984,6 +1989,40 @@ class DeviceContext:
         v = [int(x) for x in out]
         return dict(instance=v[0], chains=v[1], iterations=v[2], chains_per_group=v[3], attempts=v[4], attempts_max=v[5],
                     kernel_ms=v[6] / 1000.0, grid=v[7], flagged=v[8], kept=v[9])
+
+    def score_rows(self, slots, betas, sigsqd, want_loo=True, want_tail=False):
+        """fokl_score_rows over the uploaded rows: ll[i, d] of the uploaded y against the columns ``slots`` times every row of
+        ``betas`` [E, nc] with ``sigsqd`` [E], reduced over the DRAWS per row -> stats [S, 8] = lppd, ll_mean, p_waic and, with
+        ``want_loo`` (else zeros), elpd_loo, khat, sigma, max r, M'; with ``want_tail`` also the sorted top M + 1 shifted
+        log ratios [S, M + 1].  score.score_rows_host is its statement.  Two calls with the same arguments return the same
+        bits."""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        if betas.ndim != 2 or betas.shape[1] != s.shape[0]:
+            raise ValueError("betas columns must match the slot list")
+        E = betas.shape[0]
+        sigsqd = np.ascontiguousarray(np.reshape(sigsqd, -1), dtype=np.float64)
+        if sigsqd.shape[0] != E:
+            raise ValueError("score_rows: one sigsqd per row of betas")
+        stats = np.empty((self.n, 8), dtype=np.float64)
+        tail = None
+        if want_tail:
+            M = int(min(E // 5, np.ceil(3.0 * np.sqrt(E))))
+            tail = np.empty((self.n, M + 1), dtype=np.float64)
+        self._ck(self._lib.fokl_score_rows(self._h, _ptr(s), s.shape[0], _ptr(betas), _ptr(sigsqd), E, int(bool(want_loo)),
+                                           _ptr(stats), _ptr(tail)))
+        return (stats, tail) if want_tail else stats
+
+    def score_report(self):
+        """What the last ``score_rows`` on this context ran (fokl_score_report): ``instance`` ('waic': no list, 'waic_loo'),
+        the ``grid`` of one-wavefront workgroups over ``row_tiles`` 16-row tiles, ``lds_bytes``, the ``tail_capacity`` used
+        (M + 1; 0 without want_loo), the ``raw_rows`` that took the khat = inf branch and ``kernel_ms``.  'none' and zeros
+        after a refused call."""
+        out = np.zeros(7, dtype=np.int64)
+        self._ck(self._lib.fokl_score_report(self._h, _ptr(out)))
+        v = [int(x) for x in out]
+        return dict(instance=SCORE_INSTANCES[v[0]], grid=v[1], row_tiles=v[2], lds_bytes=v[3], tail_capacity=v[4],
+                    raw_rows=v[5], kernel_ms=v[6] / 1000.0)
 
     def _fit_report(self, which, count):
         out = np.zeros(count, dtype=np.int64)

@@ -92,6 +92,13 @@ extern "C" int fokl_resample_chains(fokl_ctx *, int, const double *, const doubl
 }
 extern "C" int fokl_resample_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor does the pointwise score (fokl_score_device.inc); its statement is score.score_rows_host.
+extern "C" int fokl_score_rows(fokl_ctx *, const int32_t *, int, const double *, const double *, int, int, double *, double *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_score_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // The device chain engine and page-locked memory do not exist in these builds: the native search (fokl_search.cpp) is
 // then created without an engine and falls back to ordinary memory for its tapes.
 extern "C" int fokl_host_alloc(size_t, void **out)

@@ -220,6 +220,12 @@ class HipBackend:
     def population_report(self):
         return self.ctx.population_report()
 
+    def score_rows(self, slots, betas, sigsqd, want_loo=True, want_tail=False):
+        return self.ctx.score_rows(slots, betas, sigsqd, want_loo, want_tail)
+
+    def score_report(self):
+        return self.ctx.score_report()
+
 
 class SlotPool:
     """Free list of device column slots (slot 0 = ones, slot 1 = y are never handed out)."""

@@ -23,6 +23,9 @@
  *   fokl_resample_chains / fokl_resample_report
  *                              many independent Gibbs chains of a fitted model, drawing their own counter-based numbers
  *                              (fokl_gpy_amd/resample.py)
+ *   fokl_score_rows / fokl_score_report
+ *                              the log predictive density of every row over all draws: WAIC and PSIS-LOO
+ *                              (fokl_gpy_amd/score.py), and what its last launch ran
  *   fokl_embedded_hmc / fokl_embedded_rng
  *                              the HMC chains of GPs embedded in a user equation (fokl_gpy_amd/embedded.py) and their
  *                              counter-based random numbers as the host sees them
@@ -848,6 +851,56 @@ int fokl_population_stats(fokl_ctx *ctx, const int32_t *slots, int nc, const dou
  * Host values noted while enqueuing: no launch, no synchronisation.
  */
 int fokl_population_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Scoring a fitted model pointwise: WAIC and PSIS-LOO (csrc/fokl_score_device.inc; fokl_gpy_amd/score.py)   */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/* out[0] of fokl_score_report: the instance of score_kernel that ran */
+enum {
+    FOKL_SCORE_NONE = 0,      /* no call yet, or the last one was refused or failed */
+    FOKL_SCORE_WAIC = 1,      /* want_loo = 0: lppd, ll_mean, p_waic only, no list in LDS */
+    FOKL_SCORE_WAIC_LOO = 2   /* also the top-(M + 1) list, the Pareto fit and elpd_loo */
+};
+#define FOKL_SCORE_REPORT_LEN 7
+#define FOKL_SCORE_STATS 8
+#define FOKL_SCORE_MIN_DRAWS 25      /* PSIS needs a tail of at least 5 draws */
+/* Entries (M + 1) of a row's list of largest log ratios in LDS: 512 x 16 rows x 8 B = 64 KiB of the compute unit's 160 KiB,
+ * which leaves room for the basis values of a 16-row tile of a model of 750 columns next to it.  M = min(E / 5,
+ * ceil(3 sqrt(E))) <= 511 allows E <= 29 013 draws. */
+#define FOKL_SCORE_MAX_TAIL 512
+
+/*
+ * ll[i][d] = -log(2 pi sigsqd[d]) / 2 - (y_i - X_i . betas[d])^2 * (0.5 / sigsqd[d]) over the uploaded rows i (y: FOKL_SLOT_Y,
+ * X_i: the columns `slots`, nc of them, as for fokl_predict) and the draws d, reduced over the DRAWS for every row; ll is
+ * never stored.  Host memory, row-major: betas [draws, nc], sigsqd [draws] (all positive and finite).
+ *   stats_out [rows, 8]     lppd = logsumexp_d(ll) - log(draws); ll_mean; p_waic = the variance of ll over d (divisor
+ *                           draws - 1, accumulated about ll[i][0]); and with want_loo (else zeros) elpd_loo, khat, sigma of
+ *                           the generalised Pareto fit (0 where khat = +inf), max_d r with r = -ll, and M', the number of
+ *                           tail values strictly above the cutoff (M' <= 4, or a tail without a positive lower-quartile
+ *                           exceedance: khat = +inf and the raw weights are used)
+ *   tail_out  [rows, M + 1] or NULL: the M + 1 largest of r - max r, ascending, M = min(draws / 5, ceil(3 sqrt(draws))); a
+ *                           test and diagnostic output (needs want_loo)
+ * The estimator is PSIS (Vehtari et al.) with the Zhang-Stephens fit, stated in numpy by score.score_rows_host.  One launch
+ * of score_kernel on v_mfma_f64_16x16x4_f64, one wavefront per 16-row tile; merges across lanes in a fixed order, no
+ * floating-point atomics: the same arguments give the same bits.
+ * Refused (FOKL_ERR_ARG with a text, nothing is launched; the dataset, its slots and pending launches are left alone):
+ * want_loo with fewer than FOKL_SCORE_MIN_DRAWS draws or with M + 1 > FOKL_SCORE_MAX_TAIL; basis values and list beyond the
+ * LDS of a compute unit; tail_out, coefficient table and statistics together beyond the device's free memory (the message
+ * says which is the largest; the environment's FOKL_SCORE_FREE_BYTES, if set, caps what counts as free).
+ * Kernel time: FOKL_K_SCORE.  Blocking.
+ */
+int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sigsqd, int draws,
+                    int want_loo, double *stats_out, double *tail_out);
+
+/*
+ * The last fokl_score_rows call on `ctx`, out [FOKL_SCORE_REPORT_LEN] (host):
+ *   out[0]  the instance (above); zeros after a call that returned an error
+ *   out[1]  the grid (workgroups = wavefronts)     out[2]  16-row tiles (more than the grid: the tile loop went round)
+ *   out[3]  dynamic LDS bytes     out[4]  tail capacity used, M + 1 (0 without want_loo)
+ *   out[5]  rows that took the khat = +inf branch     out[6]  kernel microseconds
+ */
+int fokl_score_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* What the fit kernels ran: K1 basis build, K2 Gram block, K3 residual moments (csrc/fokl_hip.hip)          */
