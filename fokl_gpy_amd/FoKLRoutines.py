@@ -35,6 +35,7 @@ from . import update as _update
 from . import optimize as _optimize
 from . import population as _population
 from . import score as _score
+from . import infer as _infer
 from . import resample as _resample
 
 
@@ -1374,6 +1375,42 @@ class FoKL:
             inputs = self.clean(inputs, kwargs_from_other=kwargs_to_clean)
         kwargs.setdefault('device', self._backend())
         return _score.score(betas, sigsqd, mtx, self.phis, self.kernel, inputs, data, **kwargs)
+
+    def infer_inputs(self, post=None, unknown=None, known=None, data=None, clean=False, betas=None, sigsqd=None, mtx=None,
+                     **kwargs):
+        """Which inputs produced these observed outputs, and how sure can one be?  One ensemble sampler of 64 walkers over
+        the ``unknown`` inputs per posterior draw, on the device -- ``infer.infer_inputs`` with this model's ``mtx``, ``phis``,
+        ``minmax`` and ``kernel``, which documents the keywords -- prior, bounds, noise, starts, burnin, draws, thin,
+        jump_every, seed, keep, objective, posterior, xvars -- and the result.  ``post`` is what ``resample`` returned (its
+        ``betas`` and ``sigsqd``), or pass ``betas=`` and ``sigsqd=``; with ``noise=`` (the measurement's own standard
+        deviation) the fit's ``betas`` do.  ``known`` [K, m - d] holds the other inputs at every observation, normalised, or
+        in true scale with ``clean=True`` (normalised with the model's ``minmax``; the model's attributes are not touched).
+        'Bernoulli Polynomials' models only.  Numpy's random stream, ``setnos`` and everything ``fit`` set are left alone."""
+        if post is not None:
+            if betas is not None or sigsqd is not None:
+                raise ValueError("infer_inputs takes a resample's result OR betas= and sigsqd=, not both")
+            try:
+                betas, sigsqd = post['betas'], post['sigsqd']
+            except (KeyError, TypeError, IndexError):
+                raise ValueError("infer_inputs needs what resample returned (betas and sigsqd per draw) as its first "
+                                 "argument") from None
+            if betas is None or sigsqd is None:
+                raise ValueError("this resample kept no rows (keep=...): infer_inputs needs betas and sigsqd per draw")
+        if betas is None:
+            betas = getattr(self, 'betas', None)
+        if sigsqd is None and kwargs.get('noise') is None:
+            raise ValueError("infer_inputs needs sigma^2 for every draw and a fit keeps the betas only: draw both with "
+                             "post = model.resample(...) and call model.infer_inputs(post, ...), or give the measurement's "
+                             "own noise= (a standard deviation)")
+        if mtx is None:
+            mtx = getattr(self, 'mtx', None)
+        if mtx is None or betas is None:
+            raise ValueError("infer_inputs needs a fitted model: call fit first (there is no interaction matrix mtx)")
+        if not hasattr(self, 'minmax'):
+            raise ValueError("infer_inputs needs the model's minmax (set by clean / fit, or model.minmax = [[min, max], ...])")
+        kwargs.setdefault('device', self._backend())
+        return _infer.infer_inputs(betas, sigsqd, mtx, self.phis, self.minmax, self.kernel, unknown, known, data,
+                                   clean=_str_to_bool(clean), **kwargs)
 
     def to_pyomo(self, *args, **kwargs):
         raise NotImplementedError("to_pyomo (FR:1796-1805) is outside the scope of this build")

@@ -21,6 +21,7 @@ K_OPTIMIZE_SYSTEM = 10
 K_POPULATION = 11
 K_RESAMPLE = 12
 K_SCORE = 13
+K_INFER = 14
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
@@ -36,6 +37,10 @@ RESAMPLE_ATTEMPT_CAP = 64                 # Marsaglia-Tsang attempts per gamma v
 RESAMPLE_SEGMENTS = 3                     # per-chain sums: first half, second half, the odd last iteration
 # fokl_embedded_rng's purposes of the resampler (csrc/fokl_philox.h)
 RES_BETA, RES_SIG_NORMAL, RES_SIG_UNIFORM, RES_TAU_NORMAL, RES_TAU_UNIFORM, RES_START = 3, 4, 5, 6, 7, 8
+INFER_MAPPINGS = ('none', 'walker_per_lane')                  # fokl_infer_report: the lane mapping that ran
+INFER_WALKERS = 64                        # fokl_infer_inputs: one ensemble is one wavefront
+INFER_TERM_CAP = 1 << 33                  # ... and the term evaluations by a wavefront asked of one launch
+INFER_U1, INFER_U2, INFER_U3, INFER_JITTER = 0, 1, 2, 3      # fokl_infer_rng's purposes (csrc/fokl_philox.h)
 # fokl_fit_report's kernel names, by id: Gram / residual / basis launch
 GRAM_KERNELS = ('none', 'valu', 'tiles', 'dma', 'panel', 'tiles4')
 RESID_KERNELS = ('none', 'columns', 'matrix_free')
@@ -198,6 +203,11 @@ SIGNATURES = {
     'fokl_embedded_hmc': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
                                   ctypes.c_uint32, c_vp, c_dbl, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_embedded_rng': (c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int, c_int, c_vp]),
+    'fokl_infer_inputs': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
+                                  c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_uint32, c_i64, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp]),
+    'fokl_infer_report': (c_int, [c_vp, c_vp]),
+    'fokl_infer_rng': (c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int, c_int, c_vp]),
     'fokl_dchain_create': (c_int, [c_int, c_int, c_vp]),
     'fokl_dchain_destroy': (None, [c_vp]),
     'fokl_dchain_submit': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp,
@@ -286,6 +296,15 @@ def embedded_rng(seed, chain, draw, purpose, count):
     counter (draw, purpose, index); purposes 0 .. 2 the embedded sampler's, RES_* the resampler's); host code, no device."""
     out = np.empty(int(count), dtype=np.float64)
     _check(load().fokl_embedded_rng(int(seed) & 0xFFFFFFFF, int(chain), int(draw), int(purpose), int(count), _ptr(out)))
+    return out
+
+
+def infer_rng(seed, draw_id, iteration, purpose, count):
+    """The numbers the ensemble sampler over unknown inputs draws (fokl_infer_rng: Philox 4x32-10 keyed by (seed, draw_id),
+    counter (iteration, purpose, index, 1); purposes INFER_U1 .. INFER_U3 uniforms of walker ``index``, INFER_JITTER the
+    normal of index 64 i + w); host code, no device."""
+    out = np.empty(int(count), dtype=np.float64)
+    _check(load().fokl_infer_rng(int(seed) & 0xFFFFFFFF, int(draw_id), int(iteration), int(purpose), int(count), _ptr(out)))
     return out
 
 
@@ -2023,6 +2042,54 @@ class DeviceContext:
         v = [int(x) for x in out]
         return dict(instance=SCORE_INSTANCES[v[0]], grid=v[1], row_tiles=v[2], lds_bytes=v[3], tail_capacity=v[4],
                     raw_rows=v[5], kernel_ms=v[6] / 1000.0)
+
+    def infer_inputs(self, mtx_u, betas, h, table, lo, hi, prior_mean, prior_prec, y, known_prod, starts, burnin, draws,
+                     thin, jump_every, seed, draw_ids=None, rows=True, term_cap=0):
+        """fokl_infer_inputs (infer.infer_inputs assembles the arguments, all in normalised coordinates): mtx_u int32
+        [terms, d] the unknown columns of the interaction matrix, betas [E, terms + 1], h [E] = 0.5 / sigma^2, table
+        [n_basis, width], lo / hi / prior_mean / prior_prec [d], y [K], known_prod [K, terms + 1], starts [64, d] ->
+        (x [E, kept, 64, d], lp [E, kept, 64] -- both None without ``rows`` --, sums [E, 64, 2, 2, d], accepted [E, 64, 2],
+        evaluations [E]): what ``infer.sample_host`` returns.  ``draw_ids`` [E]: the stream of each ensemble (default its
+        index).  ``term_cap``: 0 the default launch bound; a test hook.  Needs no uploaded dataset and leaves one alone."""
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        mtx_u = np.ascontiguousarray(mtx_u, dtype=np.int32)
+        betas, h, table, lo, hi, prior_mean, prior_prec, y, known_prod, starts = (
+            f64(a) for a in (betas, h, table, lo, hi, prior_mean, prior_prec, y, known_prod, starts))
+        if mtx_u.ndim != 2 or betas.ndim != 2 or table.ndim != 2 or y.ndim != 1 or starts.ndim != 2 or lo.ndim != 1:
+            raise ValueError("infer_inputs: array shapes disagree")
+        n_terms, d = mtx_u.shape
+        E, K = betas.shape[0], y.shape[0]
+        if betas.shape[1] != n_terms + 1 or h.shape != (E,) or known_prod.shape != (K, n_terms + 1) or \
+                starts.shape != (INFER_WALKERS, d) or any(a.shape != (d,) for a in (lo, hi, prior_mean, prior_prec)):
+            raise ValueError("infer_inputs: array shapes disagree")
+        ids = None
+        if draw_ids is not None:
+            ids = np.ascontiguousarray(draw_ids, dtype=np.uint32)
+            if ids.shape != (E,):
+                raise ValueError("infer_inputs: one draw id per row of betas")
+        kept = -(-int(draws) // int(thin)) if int(thin) >= 1 and int(draws) >= 1 else 0
+        x = np.empty((E, kept, INFER_WALKERS, d), dtype=np.float64) if rows else None
+        lp = np.empty((E, kept, INFER_WALKERS), dtype=np.float64) if rows else None
+        sums = np.empty((E, INFER_WALKERS, 2, 2, d), dtype=np.float64)
+        accepted = np.empty((E, INFER_WALKERS, 2), dtype=np.int32)
+        evaluations = np.empty(E, dtype=np.int64)
+        self._ck(self._lib.fokl_infer_inputs(
+            self._h, int(d), int(n_terms), _ptr(mtx_u), int(E), _ptr(betas), _ptr(h), _ptr(ids), _ptr(table),
+            int(table.shape[0]), int(table.shape[1]), _ptr(lo), _ptr(hi), _ptr(prior_mean), _ptr(prior_prec), int(K), _ptr(y),
+            _ptr(known_prod), _ptr(starts), int(burnin), int(draws), int(thin), int(jump_every), int(seed) & 0xFFFFFFFF,
+            int(term_cap), _ptr(x), _ptr(lp), _ptr(sums), _ptr(accepted), _ptr(evaluations)))
+        return x, lp, sums, accepted, evaluations
+
+    def infer_report(self):
+        """What the last ``infer_inputs`` on this context ran (fokl_infer_report): the lane ``mapping`` ('walker_per_lane': one
+        draw per wavefront, lane = walker), ``lds_rows`` per lane and ``lds_bytes``, the ``grid`` of the largest launch, the
+        ``launches`` of ``draws_per_launch`` ensembles, ``kernel_us`` over all of them, the ``iterations`` of a chain and the
+        target ``evaluations`` in all.  'none' and zeros after a refused call."""
+        out = np.zeros(9, dtype=np.int64)
+        self._ck(self._lib.fokl_infer_report(self._h, _ptr(out)))
+        v = [int(x) for x in out]
+        return dict(mapping=INFER_MAPPINGS[v[0]], lds_rows=v[1], grid=v[2], launches=v[3], kernel_us=v[4], iterations=v[5],
+                    evaluations=v[6], draws_per_launch=v[7], lds_bytes=v[8])
 
     def _fit_report(self, which, count):
         out = np.zeros(count, dtype=np.int64)

@@ -97,6 +97,7 @@ struct fokl_ctx {
     int64_t population_report[FOKL_POPULATION_REPORT_LEN] = {};   // ... and the last fokl_population_stats call
     int64_t resample_report[FOKL_RESAMPLE_REPORT_LEN] = {};       // ... and the last fokl_resample_chains call
     int64_t score_report[FOKL_SCORE_REPORT_LEN] = {};             // ... and the last fokl_score_rows call
+    int64_t infer_report[FOKL_INFER_REPORT_LEN] = {};             // ... and the last fokl_infer_inputs call
     // what the last Gram block, residual pass and fokl_build_terms call ran (fokl_fit_report): host values noted while
     // enqueuing, zeros after a call that was refused or failed
     int64_t gram_report[FOKL_GRAM_REPORT_LEN] = {};
@@ -1806,6 +1807,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_optimize_core.inc"
 #include "fokl_optimize_device.inc"
 #include "fokl_optimize_system_device.inc"
+#include "fokl_infer_device.inc"
 #include "fokl_embedded_device.inc"
 #include "fokl_resample_device.inc"
 #include "fokl_score_device.inc"

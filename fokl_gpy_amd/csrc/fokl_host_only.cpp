@@ -99,6 +99,17 @@ extern "C" int fokl_score_rows(fokl_ctx *, const int32_t *, int, const double *,
 }
 extern "C" int fokl_score_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor does the ensemble sampler over unknown inputs (fokl_infer_device.inc); its statement is infer.sample_host, and its
+// random numbers (fokl_infer_rng) are host code and present here.
+extern "C" int fokl_infer_inputs(fokl_ctx *, int, int, const int32_t *, int, const double *, const double *, const uint32_t *,
+                                 const double *, int, int, const double *, const double *, const double *, const double *, int,
+                                 const double *, const double *, const double *, int, int, int, int, uint32_t, int64_t,
+                                 double *, double *, double *, int32_t *, int64_t *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_infer_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // The device chain engine and page-locked memory do not exist in these builds: the native search (fokl_search.cpp) is
 // then created without an engine and falls back to ordinary memory for its tapes.
 extern "C" int fokl_host_alloc(size_t, void **out)

@@ -7,6 +7,9 @@
 //   uniform = u_a                            in [0, 1)
 //   normal  = sqrt(-2 ln(1 - u_a)) cos(2 pi u_b)          (Box-Muller, one normal per counter: 1 - u_a is in (0, 1])
 //
+// The ensemble sampler over unknown inputs (fokl_infer_device.inc) draws from streams of its own: the same key and counter
+// layout with the fourth counter word 1 (inf_uniform, inf_normal below).
+//
 // Nothing here touches numpy's global stream or the fit's MT19937 machinery.
 #ifndef FOKL_PHILOX_H
 #define FOKL_PHILOX_H
@@ -62,6 +65,28 @@ FOKL_HD double emb_uniform(uint32_t seed, uint32_t chain, uint32_t draw, uint32_
     uint32_t w[4];
     philox4x32_10(draw, purpose, index, 0u, seed, chain, w);
     return emb_unit(w[0], w[1]);
+}
+
+// fokl_infer_device.inc / infer.py: the ensemble sampler over unknown inputs.  key = (seed, posterior draw), counter =
+// (iteration, purpose, index, 1): the fourth word keeps these streams apart from every one above, which all use 0.
+constexpr int INF_PURPOSE_PARTNER = 0;    // u1 of walker `index`: the partner (stretch), the first donor (jump)
+constexpr int INF_PURPOSE_STRETCH = 1;    // u2: the stretch factor, the second donor
+constexpr int INF_PURPOSE_ACCEPT = 2;     // u3: the accept uniform
+constexpr int INF_PURPOSE_JITTER = 3;     // the jump move's normal of coordinate i of walker w, index 64 i + w
+constexpr int INF_PURPOSE_LAST = INF_PURPOSE_JITTER;
+
+FOKL_HD double inf_uniform(uint32_t seed, uint32_t draw_id, uint32_t iteration, uint32_t purpose, uint32_t index)
+{
+    uint32_t w[4];
+    philox4x32_10(iteration, purpose, index, 1u, seed, draw_id, w);
+    return emb_unit(w[0], w[1]);
+}
+
+FOKL_HD double inf_normal(uint32_t seed, uint32_t draw_id, uint32_t iteration, uint32_t purpose, uint32_t index)
+{
+    uint32_t w[4];
+    philox4x32_10(iteration, purpose, index, 1u, seed, draw_id, w);
+    return sqrt(-2.0 * log(1.0 - emb_unit(w[0], w[1]))) * cos(6.283185307179586476925 * emb_unit(w[2], w[3]));
 }
 
 FOKL_HD double emb_normal(uint32_t seed, uint32_t chain, uint32_t draw, uint32_t purpose, uint32_t index)

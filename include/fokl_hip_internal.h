@@ -26,6 +26,10 @@
  *   fokl_score_rows / fokl_score_report
  *                              the log predictive density of every row over all draws: WAIC and PSIS-LOO
  *                              (fokl_gpy_amd/score.py), and what its last launch ran
+ *   fokl_infer_inputs / fokl_infer_report / fokl_infer_rng
+ *                              unknown inputs inferred from observed outputs: one affine-invariant ensemble of 64 walkers
+ *                              per posterior draw (fokl_gpy_amd/infer.py), what its last launches ran, and its
+ *                              counter-based random numbers as the host sees them
  *   fokl_embedded_hmc / fokl_embedded_rng
  *                              the HMC chains of GPs embedded in a user equation (fokl_gpy_amd/embedded.py) and their
  *                              counter-based random numbers as the host sees them
@@ -901,6 +905,79 @@ int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const double *b
  *   out[5]  rows that took the khat = +inf branch     out[6]  kernel microseconds
  */
 int fokl_score_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Unknown inputs from observed outputs (csrc/fokl_infer_device.inc; fokl_gpy_amd/infer.py)                  */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/* out[0] of fokl_infer_report: the lane mapping that ran */
+enum {
+    FOKL_INFER_NONE = 0,            /* no call yet, or the last one was refused or failed */
+    FOKL_INFER_WALKER_PER_LANE = 1  /* one draw per wavefront, lane = walker; the half that does not move idles */
+};
+#define FOKL_INFER_REPORT_LEN 9
+#define FOKL_INFER_WALKERS 64
+/* Term evaluations by a wavefront (one term of the model at one observation, for its 64 lanes) asked of ONE launch:
+ * the draws are sliced over launches so that draws x (2 (burnin + draws) + 1) x K x max(n_terms, 1) stays below it (a
+ * slice holds at least one draw).  At the roughly 40 ns a wavefront needs per term evaluation and with every SIMD of
+ * the part holding one ensemble, 2^33 is some hundreds of milliseconds of a full device: far below any watchdog, and
+ * long enough that the launch overhead is nothing.  `term_cap` of fokl_infer_inputs replaces it (a test hook). */
+#define FOKL_INFER_TERM_CAP ((int64_t)1 << 33)
+
+/*
+ * For every posterior draw e an ensemble of 64 walkers samples the d unknown inputs theta (normalised coordinates) from
+ *   lp_e(theta) = -h[e] sum_k (y[k] - f_ek(theta))^2 - 1/2 sum_i prior_prec[i] (theta_i - prior_mean[i])^2   inside lo < theta < hi,
+ *   f_ek(theta) = sum_t (betas[e][t] known_prod[k][t]) U_t(theta),  t = 0 .. n_terms ascending, U_0 = 1,
+ * U_t the product of term t's factors in the unknown inputs (row t - 1 of mtx_u, ascending input order), each factor by
+ * Horner from `table`.  The sampler -- stretch moves, a differential-evolution jump every `jump_every`-th iteration (0:
+ * never), half 0 of the walkers then half 1, a proposal outside the box rejected without an evaluation -- is stated in numpy
+ * by infer.sample_host (the module docstring is the statement).  Random numbers: Philox 4x32-10 keyed by (seed, draw_ids[e]
+ * or e), counter (iteration, purpose, index, 1) -- fokl_infer_rng below.
+ * Host memory, row-major:
+ *   mtx_u [n_terms, d] int32, betas [n_draws, n_terms + 1], h [n_draws] (0.5 / sigma^2: positive, finite), draw_ids
+ *   [n_draws] or NULL, table [n_basis, width] as for fokl_model_optimize, lo / hi / prior_mean / prior_prec [d],
+ *   y [K], known_prod [K, n_terms + 1], starts [64, d] strictly inside the box
+ *   x_out  [n_draws, kept, 64, d], lp_out [n_draws, kept, 64]   kept = ceil(draws / thin); row r is the state after both halves
+ *          of iteration burnin + r thin.  Both NULL: no rows are kept
+ *   sums_out [n_draws, 64, 2, 2, d]   per walker and half of the post-burn-in iterations (the first draws / 2, the rest): the
+ *          sum and the sum of squares of theta_i - (lo_i + hi_i) / 2, in iteration order
+ *   accept_out [n_draws, 64, 2] int32  accepted stretch moves, accepted jump moves (burn-in included)
+ *   evals_out [n_draws] int64          evaluations of the target (the 64 of the starts included)
+ * One wavefront per workgroup and draw, lane = walker; positions, proposals and factor values in LDS as [item][lane], a
+ * partner's position an LDS read at a computed lane; the draw's coefficients, premultiplied by known_prod on the host,
+ * are scalar loads.  The model is evaluated by fokl_optimize_core.inc's op_factors / op_terms.  No atomics: the same
+ * arguments give the same bits, and neither draw_ids' order, thin nor the slicing into launches (`term_cap`; 0:
+ * FOKL_INFER_TERM_CAP) changes a bit of a draw's chain.
+ * Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched; the dataset, its slots and pending launches
+ * are left alone): d outside 1 .. 16; lo >= hi or not finite; a start not strictly inside the box; h not positive and
+ * finite; K < 1; an order beyond the table; more than 288 values per lane in LDS (3 per distinct (input, order) factor +
+ * 4 d); thin < 1, draws < 1, burnin < 0, jump_every < 0; a negative or non-finite prior precision; NaN or infinity in
+ * betas x known_prod, y or the prior mean; outputs and coefficients beyond the device's free memory (the environment's
+ * FOKL_INFER_FREE_BYTES, if set, caps what counts as free).
+ * Kernel time: FOKL_K_INFER.  Blocking; everything uploaded is freed before it returns.
+ */
+int fokl_infer_inputs(fokl_ctx *ctx, int d, int n_terms, const int32_t *mtx_u, int n_draws, const double *betas,
+                      const double *h, const uint32_t *draw_ids, const double *table, int n_basis, int width,
+                      const double *lo, const double *hi, const double *prior_mean, const double *prior_prec, int K,
+                      const double *y, const double *known_prod, const double *starts, int burnin, int draws, int thin,
+                      int jump_every, uint32_t seed, int64_t term_cap, double *x_out, double *lp_out, double *sums_out,
+                      int32_t *accept_out, int64_t *evals_out);
+
+/*
+ * The last fokl_infer_inputs call on `ctx`, out [FOKL_INFER_REPORT_LEN] (host):
+ *   out[0]  the lane mapping (above); zeros after a call that returned an error
+ *   out[1]  LDS values per lane     out[2]  the grid of the largest launch (workgroups = wavefronts = draws)
+ *   out[3]  launches     out[4]  kernel microseconds over all launches     out[5]  iterations of a chain (burnin + draws)
+ *   out[6]  target evaluations over all draws     out[7]  draws per launch     out[8]  dynamic LDS bytes
+ */
+int fokl_infer_report(const fokl_ctx *ctx, int64_t *out);
+
+/*
+ * out[j], j < count: the number the sampler draws for `purpose` and index j at `iteration` of posterior draw `draw_id`:
+ * purposes 0, 1, 2 the uniforms u1, u2, u3 of walker j in [0, 1), 3 the jump move's normal of index 64 i + w.  Host code,
+ * no device.  FOKL_ERR_ARG for another purpose.
+ */
+int fokl_infer_rng(uint32_t seed, uint32_t draw_id, uint32_t iteration, int purpose, int count, double *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* What the fit kernels ran: K1 basis build, K2 Gram block, K3 residual moments (csrc/fokl_hip.hip)          */
