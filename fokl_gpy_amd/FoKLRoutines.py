@@ -35,6 +35,7 @@ from . import update as _update
 from . import optimize as _optimize
 from . import population as _population
 from . import score as _score
+from . import design as _design
 from . import infer as _infer
 from . import resample as _resample
 
@@ -1375,6 +1376,69 @@ class FoKL:
             inputs = self.clean(inputs, kwargs_from_other=kwargs_to_clean)
         kwargs.setdefault('device', self._backend())
         return _score.score(betas, sigsqd, mtx, self.phis, self.kernel, inputs, data, **kwargs)
+
+    def design(self, post=None, pool=None, clean=False, picks=64, criterion='variance', target=None, tausqd=None, inputs=None,
+               mtx=None, **kwargs):
+        """Which points should be measured next?  Greedy optimal design over a ``pool`` [S, m] of candidate inputs on the
+        device -- ``design.design`` with this model's ``mtx``, ``phis``, ``kernel`` and training ``inputs``, which documents the
+        keywords -- replicates, refresh_every, keep -- and the result.  ``criterion='variance'`` is greedy D-optimal (the
+        largest predictive variance), ``'ivr'`` the integrated variance reduction over ``target`` (default: the training
+        inputs).  ``post`` is what ``resample`` returned: 1 / tau^2 is the mean of 1 / post.tausqd and the mean of
+        post.sigsqd scales ``target_var``; or pass ``tausqd=`` as a number (a fit alone keeps no tau^2).  ``clean=True``
+        normalises ``pool`` and ``target`` with the model's ``minmax`` exactly as ``evaluate`` does, and ``res.x`` are the
+        chosen rows of ``pool`` as they were passed: measure there, then ``fitupdate``.  Nothing is drawn at random: numpy's
+        stream, ``setnos`` and everything ``fit`` set are left alone."""
+        if mtx is None:
+            mtx = getattr(self, 'mtx', None)
+        if mtx is None:
+            raise ValueError("design needs a fitted model: call fit first (there is no interaction matrix mtx)")
+        if inputs is None:
+            inputs = getattr(self, 'inputs', None)
+        inv_tausqd, sigsqd_mean = None, 1.0
+        if post is not None:
+            try:
+                tau, sig = post['tausqd'], post['sigsqd']
+            except (KeyError, TypeError, IndexError):
+                raise ValueError("design needs what resample returned (tausqd per draw) as its first argument, or tausqd= as a "
+                                 "number") from None
+            if tau is None and tausqd is None:
+                raise ValueError("this resample kept no rows (keep=...): design needs tausqd per draw, or tausqd= as a number")
+            if tau is not None:
+                tau = np.asarray(tau, dtype=np.float64).reshape(-1)
+                tau = tau[np.isfinite(tau) & (tau > 0.0)]
+                if tau.shape[0]:
+                    inv_tausqd = float(np.mean(1.0 / tau))
+            if sig is not None:
+                sig = np.asarray(sig, dtype=np.float64).reshape(-1)
+                sig = sig[np.isfinite(sig)]
+                if sig.shape[0]:
+                    sigsqd_mean = float(np.mean(sig))
+        if tausqd is not None:
+            if not np.isscalar(tausqd) or not float(tausqd) > 0.0:
+                raise ValueError("tausqd= must be a positive number")
+            inv_tausqd = 1.0 / float(tausqd)
+        if inv_tausqd is None:
+            raise ValueError("design needs tau^2, the prior scale of the coefficients, and a fit alone keeps none: pass what "
+                             "resample returned (post = model.resample(...); model.design(post, ...)) or tausqd= as a number")
+        raw_pool = pool
+        if _str_to_bool(clean) and pool is not None:
+            if not hasattr(self, 'minmax'):
+                raise ValueError("design(clean=True) needs the model's minmax (set by clean / fit, or model.minmax = "
+                                 "[[min, max], ...])")
+            kwargs_to_clean = dict(_CLEAN_DEFAULTS)
+            kwargs_to_clean['minmax'] = self.minmax
+            if not np.isfinite(np.asarray(pool, dtype=np.float64)).all():
+                raise ValueError("pool rows must be finite")
+            pool = self.clean(pool, kwargs_from_other=kwargs_to_clean)
+            if target is not None and np.size(target):
+                target = self.clean(target, kwargs_from_other=kwargs_to_clean)
+        kwargs.setdefault('device', self._backend())
+        res = _design.design(mtx, self.phis, self.kernel, inputs, pool, picks=picks, criterion=criterion, target=target,
+                             inv_tausqd=inv_tausqd, sigsqd_mean=sigsqd_mean, **kwargs)
+        if raw_pool is not pool:
+            raw = np.asarray(raw_pool, dtype=np.float64)
+            res['x_normalised'], res['x'] = res['x'], (raw[:, np.newaxis] if raw.ndim == 1 else raw)[res['index']]
+        return res
 
     def infer_inputs(self, post=None, unknown=None, known=None, data=None, clean=False, betas=None, sigsqd=None, mtx=None,
                      **kwargs):

@@ -22,6 +22,7 @@ K_POPULATION = 11
 K_RESAMPLE = 12
 K_SCORE = 13
 K_INFER = 14
+K_DESIGN = 15
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
@@ -37,6 +38,8 @@ RESAMPLE_ATTEMPT_CAP = 64                 # Marsaglia-Tsang attempts per gamma v
 RESAMPLE_SEGMENTS = 3                     # per-chain sums: first half, second half, the odd last iteration
 # fokl_embedded_rng's purposes of the resampler (csrc/fokl_philox.h)
 RES_BETA, RES_SIG_NORMAL, RES_SIG_UNIFORM, RES_TAU_NORMAL, RES_TAU_UNIFORM, RES_START = 3, 4, 5, 6, 7, 8
+DESIGN_INSTANCES = ('none', 'variance', 'ivr')                # fokl_design_report: the instance of the design kernels that ran
+DESIGN_MAX_COLUMNS = 768                  # fokl_design_select: a 16-row tile of basis values in LDS is 96 KiB
 INFER_MAPPINGS = ('none', 'walker_per_lane')                  # fokl_infer_report: the lane mapping that ran
 INFER_WALKERS = 64                        # fokl_infer_inputs: one ensemble is one wavefront
 INFER_TERM_CAP = 1 << 33                  # ... and the term evaluations by a wavefront asked of one launch
@@ -86,6 +89,9 @@ SIGNATURES = {
     'fokl_resample_report': (c_int, [c_vp, c_vp]),
     'fokl_score_rows': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     'fokl_score_report': (c_int, [c_vp, c_vp]),
+    'fokl_design_select': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp]),
+    'fokl_design_report': (c_int, [c_vp, c_vp]),
     'fokl_read_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_write_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_timing_enable': (c_int, [c_vp, c_int]),
@@ -2042,6 +2048,45 @@ class DeviceContext:
         v = [int(x) for x in out]
         return dict(instance=SCORE_INSTANCES[v[0]], grid=v[1], row_tiles=v[2], lds_bytes=v[3], tail_capacity=v[4],
                     raw_rows=v[5], kernel_ms=v[6] / 1000.0)
+
+    def design_select(self, slots, C0, CMC0=None, picks=1, replicates=False, refresh_every=64, keep=False, grid_cap=0):
+        """fokl_design_select over the uploaded rows (the pool): greedy selection of ``picks`` rows given C0 = (G + I / tau^2)^-1
+        [nc, nc] and, for integrated variance reduction, CMC0 = C0 M C0 (None: greedy D-optimal) -> dict(index [picks] int64,
+        gain [picks], vstar [picks], x [picks, nc] and, with ``keep``, v [S] (and w [S] with CMC0) after the last pick).
+        design.select_host is its statement.  ``grid_cap``: 0 the device's grids; a test hook.  Two calls with the same
+        arguments return the same bits."""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        nc = s.shape[0]
+        C0 = np.ascontiguousarray(C0, dtype=np.float64)
+        if C0.shape != (nc, nc):
+            raise ValueError("design_select: C0 must be [columns, columns] of the slot list")
+        if CMC0 is not None:
+            CMC0 = np.ascontiguousarray(CMC0, dtype=np.float64)
+            if CMC0.shape != (nc, nc):
+                raise ValueError("design_select: CMC0 must be [columns, columns] of the slot list")
+        picks = int(picks)
+        rows = max(picks, 0)
+        index = np.empty(rows, dtype=np.int64)
+        gain, vstar, x = np.empty(rows), np.empty(rows), np.empty((rows, nc))
+        v = np.empty(self.n, dtype=np.float64) if keep else None
+        w = np.empty(self.n, dtype=np.float64) if keep and CMC0 is not None else None
+        self._ck(self._lib.fokl_design_select(self._h, _ptr(s), nc, _ptr(C0), _ptr(CMC0), picks, int(bool(replicates)),
+                                              int(refresh_every), int(grid_cap), _ptr(index), _ptr(gain), _ptr(vstar), _ptr(x),
+                                              _ptr(v), _ptr(w)))
+        return dict(index=index, gain=gain, vstar=vstar, x=x, v=v, w=w)
+
+    def design_report(self):
+        """What the last ``design_select`` on this context ran (fokl_design_report): ``instance`` ('variance', 'ivr'), the
+        ``grid`` of one-wavefront workgroups of the quadratic-form kernel over ``row_tiles`` 16-row tiles and its
+        ``lds_bytes``, the ``step_grid``, the ``picks``, the ``refreshes`` (quadratic-form launches after the first), the
+        ``launches`` in all, ``kernel_us`` of the whole queue and ``quadform_us`` of the quadratic-form launches; ``step_us``
+        and ``pivot_us`` are measured while the context's timing is enabled (else 0).  'none' and zeros after a refused
+        call."""
+        out = np.zeros(12, dtype=np.int64)
+        self._ck(self._lib.fokl_design_report(self._h, _ptr(out)))
+        v = [int(x) for x in out]
+        return dict(instance=DESIGN_INSTANCES[v[0]], grid=v[1], step_grid=v[2], row_tiles=v[3], lds_bytes=v[4], picks=v[5],
+                    refreshes=v[6], launches=v[7], kernel_us=v[8], quadform_us=v[9], step_us=v[10], pivot_us=v[11])
 
     def infer_inputs(self, mtx_u, betas, h, table, lo, hi, prior_mean, prior_prec, y, known_prod, starts, burnin, draws,
                      thin, jump_every, seed, draw_ids=None, rows=True, term_cap=0):

@@ -98,6 +98,7 @@ struct fokl_ctx {
     int64_t resample_report[FOKL_RESAMPLE_REPORT_LEN] = {};       // ... and the last fokl_resample_chains call
     int64_t score_report[FOKL_SCORE_REPORT_LEN] = {};             // ... and the last fokl_score_rows call
     int64_t infer_report[FOKL_INFER_REPORT_LEN] = {};             // ... and the last fokl_infer_inputs call
+    int64_t design_report[FOKL_DESIGN_REPORT_LEN] = {};           // ... and the last fokl_design_select call
     // what the last Gram block, residual pass and fokl_build_terms call ran (fokl_fit_report): host values noted while
     // enqueuing, zeros after a call that was refused or failed
     int64_t gram_report[FOKL_GRAM_REPORT_LEN] = {};
@@ -1811,6 +1812,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_embedded_device.inc"
 #include "fokl_resample_device.inc"
 #include "fokl_score_device.inc"
+#include "fokl_design_device.inc"
 
 #if defined(FOKL_GT_STAMP) || defined(FOKL_GD_STAMP)
 // diagnostic builds only (tools/k2_clock.sh, tools/k2_phases.sh): the clock stamps of the last Gram launch

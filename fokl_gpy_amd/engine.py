@@ -226,6 +226,12 @@ class HipBackend:
     def score_report(self):
         return self.ctx.score_report()
 
+    def design_select(self, slots, C0, CMC0=None, picks=1, replicates=False, refresh_every=64, keep=False, grid_cap=0):
+        return self.ctx.design_select(slots, C0, CMC0, picks, replicates, refresh_every, keep, grid_cap)
+
+    def design_report(self):
+        return self.ctx.design_report()
+
 
 class SlotPool:
     """Free list of device column slots (slot 0 = ones, slot 1 = y are never handed out)."""

@@ -55,7 +55,8 @@ extern "C" {
 #define FOKL_K_RESAMPLE 12     /* resample(): independent Gibbs chains of a fitted model (fokl_hip_internal.h: fokl_resample_chains) */
 #define FOKL_K_SCORE   13       /* score(): pointwise log predictive density, WAIC and PSIS-LOO (fokl_hip_internal.h: fokl_score_rows) */
 #define FOKL_K_INFER   14       /* infer_inputs(): ensemble samplers over unknown inputs (fokl_hip_internal.h: fokl_infer_inputs) */
-#define FOKL_K_COUNT   15
+#define FOKL_K_DESIGN  15       /* design(): greedy optimal design over a candidate pool (fokl_hip_internal.h: fokl_design_select) */
+#define FOKL_K_COUNT   16
 
 typedef struct fokl_ctx fokl_ctx;
 

@@ -26,6 +26,9 @@
  *   fokl_score_rows / fokl_score_report
  *                              the log predictive density of every row over all draws: WAIC and PSIS-LOO
  *                              (fokl_gpy_amd/score.py), and what its last launch ran
+ *   fokl_design_select / fokl_design_report
+ *                              greedy D- / I-optimal selection from a candidate pool (fokl_gpy_amd/design.py), and what
+ *                              its last call ran
  *   fokl_infer_inputs / fokl_infer_report / fokl_infer_rng
  *                              unknown inputs inferred from observed outputs: one affine-invariant ensemble of 64 walkers
  *                              per posterior draw (fokl_gpy_amd/infer.py), what its last launches ran, and its
@@ -905,6 +908,62 @@ int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const double *b
  *   out[5]  rows that took the khat = +inf branch     out[6]  kernel microseconds
  */
 int fokl_score_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Which pool rows to measure next: greedy optimal design (csrc/fokl_design_device.inc; fokl_gpy_amd/design.py) */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/* out[0] of fokl_design_report: the instance of the three kernels that ran */
+enum {
+    FOKL_DESIGN_NONE = 0,      /* no call yet, or the last one was refused or failed */
+    FOKL_DESIGN_VARIANCE = 1,  /* CMC0 = NULL: greedy D-optimal, v alone */
+    FOKL_DESIGN_IVR = 2        /* integrated variance reduction: v and w, the second accumulator chain */
+};
+#define FOKL_DESIGN_REPORT_LEN 12
+/* Columns (ones first) of the pool: a 16-row tile of basis values in LDS is 768 x 16 x 8 B = 96 KiB of the compute unit's
+ * 160 KiB, and design_pivot_kernel keeps x*, u and a of that length in its own. */
+#define FOKL_DESIGN_MAX_COLUMNS 768
+
+/*
+ * Greedy selection of `picks` rows of the uploaded dataset (the pool; X_s: the columns `slots`, nc of them, ones first, as
+ * for fokl_predict) given C0 = (G + I / tau^2)^-1 [nc, nc] and, for integrated variance reduction, CMC0 = C0 M C0 [nc, nc]
+ * (NULL: greedy D-optimal); both symmetric, host memory, row-major.  With v_s = X_s' C X_s and w_s = X_s' CMC X_s the
+ * criterion of a row is v_s, or w_s / (1 + v_s); a pick takes the largest (compared with >: NaN never wins; on equal
+ * values the lowest row), and with u = C x*, a = CMC x*, v* = x*' u, w* = x*' a, d = 1 + v*:
+ *   C <- C - u u' / d,  CMC <- CMC - (u a' + a u') / d + u u' w* / d^2,
+ *   v_s <- v_s - p_s^2 / d,  w_s <- w_s - 2 p_s q_s / d + p_s^2 w* / d^2,   p_s = X_s' u, q_s = X_s' a.
+ * Before the first pick, and with refresh_every = r > 0 before the picks r, 2 r, ..., v and w are formed from the current
+ * matrices by design_quadform_kernel (v_mfma_f64_16x16x4_f64, one wavefront per 16-row tile) instead of downdated.
+ * replicates = 0 masks a picked row.  The statement in numpy is design.select_host.
+ *   index_out [picks] int64   the rows in pick order (-1: nothing could be taken, every criterion NaN or -inf)
+ *   gain_out  [picks]         the criterion of each pick when it was taken
+ *   vstar_out [picks]         v* of each pick (log det A grows by log1p(v*))
+ *   x_out     [picks, nc]     the picked rows' columns
+ *   v_out, w_out [rows] or NULL: v and w of every row after the last pick's downdate (w_out needs CMC0)
+ * All launches (design_quadform_kernel, then design_step_kernel and design_pivot_kernel per pick) are queued on the
+ * context's stream and synchronised once; nothing is accumulated with atomics and the best of two rows does not depend on
+ * the order they are met in, so the same arguments give the same bits whatever the grid.  grid_cap > 0 caps both grids (a
+ * test hook; 0: the device's).
+ * Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched; the dataset, its slots and pending launches
+ * are left alone): nc outside 1 .. FOKL_DESIGN_MAX_COLUMNS; picks < 1; picks above the rows without replicates; per-row
+ * values and matrices beyond the device's free memory (the environment's FOKL_DESIGN_FREE_BYTES, if set, caps what counts
+ * as free).
+ * Kernel time: FOKL_K_DESIGN.  Blocking; everything uploaded is freed before it returns.
+ */
+int fokl_design_select(fokl_ctx *ctx, const int32_t *slots, int nc, const double *C0, const double *CMC0, int picks,
+                       int replicates, int refresh_every, int grid_cap, int64_t *index_out, double *gain_out,
+                       double *vstar_out, double *x_out, double *v_out, double *w_out);
+
+/*
+ * The last fokl_design_select call on `ctx`, out [FOKL_DESIGN_REPORT_LEN] (host):
+ *   out[0]  the instance (above); zeros after a call that returned an error
+ *   out[1]  the grid of design_quadform_kernel (workgroups = wavefronts)     out[2]  the grid of design_step_kernel
+ *   out[3]  16-row tiles (more than out[1]: the tile loop went round)        out[4]  dynamic LDS bytes of a tile
+ *   out[5]  picks     out[6]  refreshes (quadratic-form launches after the first)     out[7]  launches in all
+ *   out[8]  kernel microseconds of the whole queue     out[9]  ... of the quadratic-form launches
+ *   out[10], out[11]  ... of the step and of the pivot launches (measured only while fokl_timing_enable is on, else 0)
+ */
+int fokl_design_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* Unknown inputs from observed outputs (csrc/fokl_infer_device.inc; fokl_gpy_amd/infer.py)                  */
