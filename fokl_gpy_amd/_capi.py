@@ -208,6 +208,7 @@ SIGNATURES = {
                                      c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_embedded_hmc': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
                                   ctypes.c_uint32, c_vp, c_dbl, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_embedded_plan': (c_int, [c_int, c_int, c_vp, c_vp]),
     'fokl_embedded_rng': (c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int, c_int, c_vp]),
     'fokl_infer_inputs': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
                                   c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, ctypes.c_uint32, c_i64, c_vp, c_vp, c_vp,
@@ -2283,6 +2284,13 @@ class DeviceContext:
         flags = out.pop('flags')
         out['status'], out['mass_updated'] = flags[:, 0].copy(), flags[:, 1].astype(bool)
         return out
+
+    def embedded_plan(self, n_gps, n_ops):
+        """fokl_embedded_plan: the launch ``embedded_hmc`` makes for a tape of n_ops operations over n_gps GPs -> dict of
+        threads (256 or 128 per workgroup) and lds_bytes (the dynamic LDS it asks for)."""
+        threads, lds_bytes = c_int(0), ctypes.c_size_t(0)
+        _check(self._lib.fokl_embedded_plan(int(n_gps), int(n_ops), ctypes.byref(threads), ctypes.byref(lds_bytes)))
+        return dict(threads=threads.value, lds_bytes=lds_bytes.value)
 
     def read_slot(self, slot, row0=0, nrows=None):
         nrows = self.n - row0 if nrows is None else nrows

@@ -393,10 +393,12 @@ __global__ __launch_bounds__(THREADS) void hmc_chain_kernel(EmbProblem p, const 
                     alive = eps > 0.0;
                 }
             }
-            if (tid == 0) eps_hist[(size_t)chain * p.n_windows + d / EMB_WINDOW - 1] = eps;
+            if (tid == 0) eps_hist[(size_t)chain * p.n_windows + d / EMB_WINDOW - 1] = alive ? eps : __builtin_nan("");
             if (!alive) {
-                // the rest of the chain is not sampled
+                // the rest of the chain is not sampled, and neither is its last proposal
                 const double nan = __builtin_nan("");
+                if (proposal)
+                    for (int j = tid; j < D + 1; j += THREADS) proposal[(size_t)chain * (D + 1) + j] = nan;
                 for (int r = d + 1; r <= p.draws; ++r) {
                     for (int j = tid; j < D; j += THREADS) st[(size_t)r * D + j] = nan;
                     if (tid == 0) {
@@ -438,6 +440,14 @@ static size_t emb_lds_bytes(int n_slots, int n_ops, int threads)
     return doubles * sizeof(double) + (size_t)3 * std::max(n_ops, 1) * sizeof(int);
 }
 
+// the launch plan of a tape: 256 threads where values and adjoints fit beside the rest, 128 for the largest tapes
+static size_t emb_plan(int n_gps, int n_ops, int *threads)
+{
+    const int n_slots = n_gps + n_ops;
+    *threads = emb_lds_bytes(n_slots, n_ops, 256) <= EMB_LDS_BUDGET ? 256 : 128;
+    return emb_lds_bytes(n_slots, n_ops, *threads);
+}
+
 // "" or why the tape cannot run
 static std::string emb_tape_refusal(int n_gps, int n_cols, int n_ops, const int32_t *ops, int n_consts, int result)
 {
@@ -467,6 +477,18 @@ static std::string emb_tape_refusal(int n_gps, int n_cols, int n_ops, const int3
 }
 
 }  // namespace fokl
+
+extern "C" int fokl_embedded_plan(int n_gps, int n_ops, int *threads, size_t *lds_bytes)
+{
+    using namespace fokl;
+    if (!threads || !lds_bytes) return fail(nullptr, FOKL_ERR_ARG, "fokl_embedded_plan: null pointer");
+    if (n_gps < 1 || n_gps > EMB_MAX_GPS || n_ops < 0 || n_ops > EMB_MAX_OPS)
+        return fail(nullptr, FOKL_ERR_ARG, "fokl_embedded_plan: " + std::to_string(n_gps) + " GPs and " + std::to_string(n_ops) +
+                                               " operations, 1 to " + std::to_string(EMB_MAX_GPS) + " and at most " +
+                                               std::to_string(EMB_MAX_OPS) + " expected");
+    *lds_bytes = emb_plan(n_gps, n_ops, threads);
+    return FOKL_OK;
+}
 
 extern "C" int fokl_embedded_hmc(fokl_ctx *ctx, int n_gps, int n_coef, const int32_t *term_slots, int n_cols,
                                  const int32_t *col_slots, int n_ops, const int32_t *ops, int n_consts, const double *consts,
@@ -523,10 +545,9 @@ extern "C" int fokl_embedded_hmc(fokl_ctx *ctx, int n_gps, int n_coef, const int
     p.n = ctx->n;
     p.ld = ctx->ld;
     p.eps0 = eps0;
-    const int n_slots = n_gps + n_ops, D = p.n_params;
-    // 256 threads where values and adjoints fit beside the rest, 128 for the largest tapes
-    const int threads = emb_lds_bytes(n_slots, n_ops, 256) <= EMB_LDS_BUDGET ? 256 : 128;
-    const size_t lds_bytes = emb_lds_bytes(n_slots, n_ops, threads);
+    const int D = p.n_params;
+    int threads = 0;
+    const size_t lds_bytes = emb_plan(n_gps, n_ops, &threads);
     if (lds_bytes > EMB_LDS_BUDGET) return fail(ctx, FOKL_ERR_ARG, who + "the tape's values do not fit the LDS of a compute unit");
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -73,6 +73,7 @@ extern "C" int fokl_embedded_hmc(fokl_ctx *, int, int, const int32_t *, int, con
 {
     return FOKL_ERR_HIP;
 }
+extern "C" int fokl_embedded_plan(int, int, int *, size_t *) { return FOKL_ERR_HIP; }
 
 // A population through every posterior draw runs on the device only (fokl_population.inc); its statement is
 // population.propagate_host.

@@ -737,6 +737,14 @@ int fokl_embedded_hmc(fokl_ctx *ctx, int n_gps, int n_coef, const int32_t *term_
                       double *eps_final, int32_t *status, double *grad0, double *proposal);
 
 /*
+ * The launch plan fokl_embedded_hmc chooses for a tape of n_ops operations over n_gps GPs, by the expression it launches
+ * with: *threads the workgroup's size -- 256 while the n_gps + n_ops value and adjoint slots of 256 threads fit the 160 KB
+ * of LDS beside the chain's state (up to 34 slots), 128 above that -- and *lds_bytes the dynamic LDS it asks for.  No
+ * device, no context; FOKL_ERR_ARG outside 1 .. 8 GPs or 0 .. 32 operations.
+ */
+int fokl_embedded_plan(int n_gps, int n_ops, int *threads, size_t *lds_bytes);
+
+/*
  * out[j], j < count: the numbers chain `chain` of a run seeded `seed` draws at `draw` for `purpose` -- 0 the momentum of
  * transition `draw` (standard normals, one per parameter), 1 its accept uniform (j = 0), 2 the momentum of the step
  * search that runs at `draw` (0 at the start, 500 after the mass update); and those of fokl_resample_chains, whose `draw`

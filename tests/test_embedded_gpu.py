@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+from embedded_reference import term_scales
 from helpers import GOLDEN
 from fokl_gpy_amd import _capi, embedded, engine, getKernels
 
@@ -55,10 +56,7 @@ def test_potential_and_gradient(device_ctx, equation, kernel):
             B = q0[c, :-1].reshape(K, T + 1)
             values = model.tape.forward(B @ X.T)
             e = model._data() - values[model.tape.result & 255]
-            prec = np.exp(-q0[c, -1])
-            scale_U = 0.5 * N * (np.log(2 * np.pi) + abs(q0[c, -1])) + 0.5 * prec * (e @ e) + 0.5 * (D - 1) * np.log(2000 * np.pi)
-            W = np.abs(model.tape.backward(values) * e)
-            scale_g = np.append((prec * (W @ np.abs(X)) + np.abs(B) / 1000).reshape(-1), 0.5 * N + 0.5 * prec * (e @ e))
+            scale_U, scale_g = term_scales(q0[c], X, e, model.tape.backward(values))
             assert abs(dev['potential'][c, 0] - U) <= 1e-11 * scale_U, (K, T, N, c)
             assert np.all(np.abs(dev['grad0'][c] - g) <= 1e-11 * scale_g + 1e-300), (K, T, N, c)
             assert np.array_equal(dev['states'][c, 0], q0[c])
