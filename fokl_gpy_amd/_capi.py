@@ -201,6 +201,10 @@ SIGNATURES = {
                                   c_dbl, c_vp, c_vp]),
     'fokl_gp_integrate_ensemble': (c_int, [c_vp, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_vp, c_vp, c_int, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
+    'fokl_simulate_ensemble': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
+                                       c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
+                                       c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_simulate_report': (c_int, [c_vp, c_vp]),
     'fokl_model_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_dbl,
                                     c_int, c_dbl, c_vp, c_vp, c_vp, c_vp]),
     'fokl_system_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int,
@@ -2194,6 +2198,47 @@ class DeviceContext:
             _ptr(cols), sources, _ptr(n_src), _ptr(forcing), _ptr(norms), _ptr(table), int(n_basis), int(width), float(h),
             _ptr(y0), int(y0.ndim == 2), int(cut or 0), _ptr(mean), _ptr(bounds), _ptr(members)))
         return mean, bounds, members
+
+    def simulate_ensemble(self, p):
+        """fokl_simulate_ensemble for a system prepared by ``dynamics._prepare`` -> (mean [n_states, P], bounds
+        [n_states, P, 2] or None, members [E, n_states, P] or None, first_saturation [E] int32).  Needs no uploaded
+        dataset and leaves one alone."""
+        K, E, P = int(p['K']), int(p['E']), int(p['n_steps']) + 1
+        mean = np.empty((K, P), dtype=np.float64)
+        bounds = np.empty((K, P, 2), dtype=np.float64) if p['want_bounds'] else None
+        members = np.empty((E, K, P), dtype=np.float64) if p['want_members'] else None
+        first = np.empty(E, dtype=np.int32)
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
+        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
+        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
+        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
+        coef, y0, box = f64(p['coef']), f64(p['y0']), f64(p['box'])
+        if coef.ndim != 2 or coef.shape[1] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
+                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
+                not (norm_src.shape == norm_lo.shape == norm_span.shape) or \
+                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
+                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21:
+            raise ValueError("simulate_ensemble: array shapes disagree")
+        self._ck(self._lib.fokl_simulate_ensemble(
+            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
+            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
+            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
+            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[0], _ptr(coef), _ptr(y0),
+            _ptr(box), int(p['cut']) if p['want_bounds'] else 0, _ptr(mean), _ptr(bounds), _ptr(members), _ptr(first)))
+        return mean, bounds, members, first
+
+    def simulate_report(self):
+        """What the last ``simulate_ensemble`` on this context ran (fokl_simulate_report; host values, no launch): ``NS``
+        (the kernel instance = states), ``members``, ``workgroups`` (= wavefronts = ceil(members / 64)), ``lds_bytes``,
+        ``launches`` of the integration kernel, ``spline_factors``, ``bernoulli_factors`` and ``steps_per_launch``.  Zeros
+        after a refused call."""
+        out = np.zeros(8, dtype=np.int64)
+        self._ck(self._lib.fokl_simulate_report(self._h, _ptr(out)))
+        keys = ('NS', 'members', 'workgroups', 'lds_bytes', 'launches', 'spline_factors', 'bernoulli_factors',
+                'steps_per_launch')
+        return dict(zip(keys, (int(v) for v in out)))
 
     def model_optimize(self, mtx, betas, table, lo, hi, starts, sign, max_iter, tol):
         """fokl_model_optimize (optimize.optimize assembles the arguments, all in normalised coordinates): mtx int32

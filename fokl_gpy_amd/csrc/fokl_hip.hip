@@ -99,6 +99,7 @@ struct fokl_ctx {
     int64_t score_report[FOKL_SCORE_REPORT_LEN] = {};             // ... and the last fokl_score_rows call
     int64_t infer_report[FOKL_INFER_REPORT_LEN] = {};             // ... and the last fokl_infer_inputs call
     int64_t design_report[FOKL_DESIGN_REPORT_LEN] = {};           // ... and the last fokl_design_select call
+    int64_t simulate_report[FOKL_SIMULATE_REPORT_LEN] = {};       // ... and the last fokl_simulate_ensemble call
     // what the last Gram block, residual pass and fokl_build_terms call ran (fokl_fit_report): host values noted while
     // enqueuing, zeros after a call that was refused or failed
     int64_t gram_report[FOKL_GRAM_REPORT_LEN] = {};
@@ -1803,6 +1804,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_predict.inc"
 #include "fokl_population.inc"
 #include "fokl_integrate_device.inc"
+#include "fokl_simulate_device.inc"
 #include "fokl_probe.inc"
 #include "fokl_dgemm_device.inc"
 #include "fokl_optimize_core.inc"

@@ -45,6 +45,17 @@ extern "C" int fokl_gp_integrate_ensemble(fokl_ctx *, int, int, int, int64_t, co
     return FOKL_ERR_HIP;
 }
 
+// Neither does dynamics.simulate (fokl_simulate_device.inc); its statement is dynamics.simulate_host.
+extern "C" int fokl_simulate_ensemble(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
+                                      const double *, const double *, int, int, const int32_t *, const int32_t *, const int32_t *,
+                                      const int32_t *, int, const double *, int, const double *, int, const int32_t *,
+                                      const int32_t *, const int32_t *, const int32_t *, int, const double *, const double *,
+                                      const double *, int, double *, double *, double *, int32_t *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_simulate_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // The multistart optimiser runs on the device only (fokl_optimize_device.inc on fokl_optimize_core.inc); its statement is
 // optimize.solve_host.
 extern "C" int fokl_model_optimize(fokl_ctx *, int, int, const int32_t *, int, const double *, const double *, int, int,

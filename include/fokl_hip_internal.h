@@ -33,6 +33,9 @@
  *                              unknown inputs inferred from observed outputs: one affine-invariant ensemble of 64 walkers
  *                              per posterior draw (fokl_gpy_amd/infer.py), what its last launches ran, and its
  *                              counter-based random numbers as the host sees them
+ *   fokl_simulate_ensemble / fokl_simulate_report
+ *                              a system of fitted models, wired by names, integrated for every posterior draw at once
+ *                              (fokl_gpy_amd/dynamics.py), and what its last call ran
  *   fokl_embedded_hmc / fokl_embedded_rng
  *                              the HMC chains of GPs embedded in a user equation (fokl_gpy_amd/embedded.py) and their
  *                              counter-based random numbers as the host sees them
@@ -1045,6 +1048,57 @@ int fokl_infer_report(const fokl_ctx *ctx, int64_t *out);
  * no device.  FOKL_ERR_ARG for another purpose.
  */
 int fokl_infer_rng(uint32_t seed, uint32_t draw_id, uint32_t iteration, int purpose, int count, double *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* A system of fitted models over every posterior draw (csrc/fokl_simulate_device.inc; fokl_gpy_amd/dynamics.py) */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_SIMULATE_REPORT_LEN 8
+#define FOKL_SIMULATE_MAX_STATES 8
+
+/*
+ * Classical Runge-Kutta integration of d(state k)/dt = model_k(its inputs), k < n_states <= 8, for n_members members at
+ * once, over n_steps steps of size h.  The plan is assembled by dynamics._prepare and the arithmetic is stated by
+ * dynamics.simulate_host (the module docstring of fokl_gpy_amd/dynamics.py): a member's trajectory equals the host
+ * statement's bit for bit.  Host memory, row-major:
+ *   forcing [n_steps, n_forcing_cols] true scale; row s serves the four stages of step s
+ *   norm_src / norm_lo / norm_span [n_norm]: the normalised inputs v = (x - lo) / span clamped to [0, 1]; the first
+ *          n_norm_forcing read forcing column -(src + 1), the others state src, in ascending order of src
+ *   fac_norm / fac_kind / fac_row / fac_degree [n_factors]: the distinct factors, the first n_forcing_factors on forcing
+ *          inputs, inside either group kind 0 (cubic splines) before kind 1 (Bernoulli); fac_row is the factor's row of
+ *          spline_table [n_spline_rows, 499, 4] (c0 .. c3 of every piece) or of bern_table [n_bern_rows, 21] (lowest
+ *          power first), fac_degree a Bernoulli factor's order (<= 20)
+ *   entries [n_entries, 4] int32 {slot, slot, slot, coefficient}: slot 0 is 1.0, slot f + 1 factor f; coefficient -1: the
+ *          product continues in the next entry.  Model k owns entries [entry_begin[k], entry_begin[k] + entry_count[k]) and
+ *          its constant is coefficient constant[k]
+ *   coef [n_coef, n_members], y0 [n_states, n_members], box [n_states, 2] (true scale: lower < upper)
+ *   mean [n_states, n_steps + 1]; bounds [n_states, n_steps + 1, 2] or NULL (sorted[cut], sorted[n_members - cut], at most
+ *   16 384 members); members [n_members, n_states, n_steps + 1] or NULL; first_saturation [n_members] int32: the first step
+ *   in which a clamp or the slope rule acted, -1 never.
+ * One lane per member, one wavefront per workgroup, (1 + n_factors + n_norm - n_norm_forcing + n_coef) values per lane in
+ * LDS (at most 144 KB).  The steps are cut into launches of FOKL_SIMULATE_STEPS_PER_LAUNCH (environment, default 512): the
+ * cut changes no bit.  Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched, the dataset and
+ * pending launches are left alone): more than 8 states, an index outside its table, an empty box, the LDS budget, bounds
+ * over fewer than 2 or more than 16 384 members.  Kernel times: FOKL_K_INTEGRATE, FOKL_K_BAND.  Blocking.
+ */
+int fokl_simulate_ensemble(fokl_ctx *ctx, int n_members, int n_states, int64_t n_steps, double h, int n_forcing_cols,
+                           const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
+                           const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
+                           const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
+                           const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
+                           const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
+                           const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
+                           const double *y0, const double *box, int cut, double *mean, double *bounds, double *members,
+                           int32_t *first_saturation);
+
+/*
+ * The last fokl_simulate_ensemble call on `ctx`, out [FOKL_SIMULATE_REPORT_LEN] (host values, no launch); zeros after a call
+ * that was refused or failed:
+ *   out[0]  NS: the kernel instance (states)     out[1]  members     out[2]  workgroups = wavefronts = ceil(members / 64)
+ *   out[3]  dynamic LDS bytes     out[4]  integration launches     out[5]  spline factors     out[6]  Bernoulli factors
+ *   out[7]  steps per launch
+ */
+int fokl_simulate_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* What the fit kernels ran: K1 basis build, K2 Gram block, K3 residual moments (csrc/fokl_hip.hip)          */
