@@ -44,6 +44,9 @@ INFER_MAPPINGS = ('none', 'walker_per_lane')                  # fokl_infer_repor
 INFER_WALKERS = 64                        # fokl_infer_inputs: one ensemble is one wavefront
 INFER_TERM_CAP = 1 << 33                  # ... and the term evaluations by a wavefront asked of one launch
 INFER_U1, INFER_U2, INFER_U3, INFER_JITTER = 0, 1, 2, 3      # fokl_infer_rng's purposes (csrc/fokl_philox.h)
+ASSIMILATE_PARTICLES = 64                 # fokl_assimilate_ensemble: the particles of one draw are one wavefront
+# fokl_assimilate_rng's purposes (csrc/fokl_philox.h); 0 .. 7 are the process-noise normals of state j
+ASSIMILATE_INIT, ASSIMILATE_RESAMPLE, ASSIMILATE_DRAW_INDEX = 8, 9, 10
 # fokl_fit_report's kernel names, by id: Gram / residual / basis launch
 GRAM_KERNELS = ('none', 'valu', 'tiles', 'dma', 'panel', 'tiles4')
 RESID_KERNELS = ('none', 'columns', 'matrix_free')
@@ -205,6 +208,12 @@ SIGNATURES = {
                                        c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
                                        c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     'fokl_simulate_report': (c_int, [c_vp, c_vp]),
+    'fokl_assimilate_ensemble': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
+                                         c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
+                                         c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
+                                         ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_assimilate_report': (c_int, [c_vp, c_vp]),
+    'fokl_assimilate_rng': (c_int, [ctypes.c_uint32, c_vp, c_int, ctypes.c_uint32, c_int, c_int, c_vp]),
     'fokl_model_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_dbl,
                                     c_int, c_dbl, c_vp, c_vp, c_vp, c_vp]),
     'fokl_system_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int,
@@ -307,6 +316,18 @@ def embedded_rng(seed, chain, draw, purpose, count):
     counter (draw, purpose, index); purposes 0 .. 2 the embedded sampler's, RES_* the resampler's); host code, no device."""
     out = np.empty(int(count), dtype=np.float64)
     _check(load().fokl_embedded_rng(int(seed) & 0xFFFFFFFF, int(chain), int(draw), int(purpose), int(count), _ptr(out)))
+    return out
+
+
+def assimilate_rng(seed, draw_ids, step, purpose, count):
+    """The numbers the particle filter draws (fokl_assimilate_rng: Philox 4x32-10 keyed by (seed, draw id), counter (step,
+    purpose, index, 2)) -> [len(draw_ids), count]; purposes 0 .. 7 the process-noise normal of that state (index = particle),
+    ASSIMILATE_INIT the start's normal (index 64 j + particle), ASSIMILATE_RESAMPLE and ASSIMILATE_DRAW_INDEX uniforms;
+    host code, no device."""
+    ids = np.ascontiguousarray(draw_ids, dtype=np.uint32)
+    out = np.empty((ids.shape[0], int(count)), dtype=np.float64)
+    _check(load().fokl_assimilate_rng(int(seed) & 0xFFFFFFFF, _ptr(ids), int(ids.shape[0]), int(step), int(purpose), int(count),
+                                      _ptr(out)))
     return out
 
 
@@ -2238,6 +2259,58 @@ class DeviceContext:
         self._ck(self._lib.fokl_simulate_report(self._h, _ptr(out)))
         keys = ('NS', 'members', 'workgroups', 'lds_bytes', 'launches', 'spline_factors', 'bernoulli_factors',
                 'steps_per_launch')
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def assimilate_ensemble(self, p):
+        """fokl_assimilate_ensemble for a system prepared by ``dynamics._prepare`` with the filter's entries added by
+        ``dynamics._prepare_assimilate`` -> (stats [E, n_obs, 2 n_states + 3], particles [E, n_obs, 64, n_states] or None,
+        weights [E, n_obs, 64] or None, first_saturation [E] int32, collapsed [E] int32).  Needs no uploaded dataset and
+        leaves one alone."""
+        K, E, P = int(p['K']), int(p['E']), int(p['n_steps']) + 1
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
+        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
+        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
+        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
+        coef, y0, box = f64(np.asarray(p['coef']).T), f64(p['y0']), f64(p['box'])
+        ids = np.ascontiguousarray(p['draw_ids'], dtype=np.uint32)
+        obs_state, obs_sd, obs_row = i32(p['obs_state']), f64(p['obs_sd']), i32(p['obs_row'])
+        data, obs_const, q, y0_sd = f64(p['data']), f64(p['obs_const']), f64(p['process_q']), f64(p['y0_sd'])
+        n_obs = data.shape[0] if data.ndim == 2 else -1
+        if coef.ndim != 2 or coef.shape[0] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
+                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
+                not (norm_src.shape == norm_lo.shape == norm_span.shape) or \
+                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
+                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21 or ids.shape != (E,) or \
+                obs_state.ndim != 1 or obs_sd.shape != obs_state.shape or data.ndim != 2 or \
+                data.shape[1] != obs_state.shape[0] or obs_row.shape != (P,) or obs_const.shape != (n_obs,) or \
+                q.shape != (K,) or y0_sd.shape != (K,):
+            raise ValueError("assimilate_ensemble: array shapes disagree")
+        stats = np.empty((E, n_obs, 2 * K + 3), dtype=np.float64)
+        keep = bool(p['want_particles'])
+        particles = np.empty((E, n_obs, ASSIMILATE_PARTICLES, K), dtype=np.float64) if keep else None
+        weights = np.empty((E, n_obs, ASSIMILATE_PARTICLES), dtype=np.float64) if keep else None
+        first, collapsed = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
+        self._ck(self._lib.fokl_assimilate_ensemble(
+            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
+            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
+            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
+            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[1], _ptr(coef), _ptr(y0),
+            _ptr(box), _ptr(ids), obs_state.shape[0], _ptr(obs_state), _ptr(obs_sd), n_obs, _ptr(obs_row), _ptr(data),
+            _ptr(obs_const), _ptr(q), _ptr(y0_sd), float(p['threshold']), int(p['seed']) & 0xFFFFFFFF, _ptr(stats),
+            _ptr(particles), _ptr(weights), _ptr(first), _ptr(collapsed)))
+        return stats, particles, weights, first, collapsed
+
+    def assimilate_report(self):
+        """What the last ``assimilate_ensemble`` on this context ran (fokl_assimilate_report; host values, no launch): ``NS``
+        (the kernel instance = states), ``draws``, ``grid`` (workgroups = wavefronts = draws), ``lds_bytes``, ``launches``
+        of ``steps_per_launch`` steps, ``observations``, ``spline_factors`` and ``bernoulli_factors``.  Zeros after a
+        refused call."""
+        out = np.zeros(9, dtype=np.int64)
+        self._ck(self._lib.fokl_assimilate_report(self._h, _ptr(out)))
+        keys = ('NS', 'draws', 'grid', 'lds_bytes', 'launches', 'steps_per_launch', 'observations', 'spline_factors',
+                'bernoulli_factors')
         return dict(zip(keys, (int(v) for v in out)))
 
     def model_optimize(self, mtx, betas, table, lo, hi, starts, sign, max_iter, tol):

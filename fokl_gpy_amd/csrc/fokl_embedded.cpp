@@ -25,3 +25,19 @@ extern "C" int fokl_infer_rng(uint32_t seed, uint32_t draw_id, uint32_t iteratio
                                                      : fokl::inf_uniform(seed, draw_id, iteration, (uint32_t)purpose, (uint32_t)j);
     return FOKL_OK;
 }
+
+// ... and of the particle filter over a fitted dynamic system (fokl_assimilate_device.inc; dynamics.assimilate_host draws
+// through this entry): out [n_draws][count], one row per draw id
+extern "C" int fokl_assimilate_rng(uint32_t seed, const uint32_t *draw_ids, int n_draws, uint32_t step, int purpose, int count,
+                                   double *out)
+{
+    if (count < 0 || n_draws < 0 || (n_draws > 0 && !draw_ids) || (count > 0 && n_draws > 0 && !out) || purpose < 0 ||
+        purpose > fokl::ASM_PURPOSE_LAST)
+        return FOKL_ERR_ARG;
+    const bool uniform = purpose == fokl::ASM_PURPOSE_RESAMPLE || purpose == fokl::ASM_PURPOSE_DRAW_INDEX;
+    for (int e = 0; e < n_draws; ++e)
+        for (int j = 0; j < count; ++j)
+            out[(size_t)e * count + j] = uniform ? fokl::asm_uniform(seed, draw_ids[e], step, (uint32_t)purpose, (uint32_t)j)
+                                                 : fokl::asm_normal(seed, draw_ids[e], step, (uint32_t)purpose, (uint32_t)j);
+    return FOKL_OK;
+}

@@ -56,6 +56,20 @@ extern "C" int fokl_simulate_ensemble(fokl_ctx *, int, int, int64_t, double, int
 }
 extern "C" int fokl_simulate_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor does the particle filter over such a system (fokl_assimilate_device.inc); its statement is dynamics.assimilate_host,
+// and its random numbers (fokl_assimilate_rng) are host code and present here.
+extern "C" int fokl_assimilate_ensemble(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
+                                        const double *, const double *, int, int, const int32_t *, const int32_t *,
+                                        const int32_t *, const int32_t *, int, const double *, int, const double *, int,
+                                        const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, const double *,
+                                        const double *, const double *, const uint32_t *, int, const int32_t *, const double *,
+                                        int, const int32_t *, const double *, const double *, const double *, const double *,
+                                        double, uint32_t, double *, double *, double *, int32_t *, int32_t *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_assimilate_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // The multistart optimiser runs on the device only (fokl_optimize_device.inc on fokl_optimize_core.inc); its statement is
 // optimize.solve_host.
 extern "C" int fokl_model_optimize(fokl_ctx *, int, int, const int32_t *, int, const double *, const double *, int, int,

@@ -10,6 +10,9 @@
 // The ensemble sampler over unknown inputs (fokl_infer_device.inc) draws from streams of its own: the same key and counter
 // layout with the fourth counter word 1 (inf_uniform, inf_normal below).
 //
+// The particle filter over a fitted dynamic system (fokl_assimilate_device.inc) draws from a third family: the same key and
+// counter layout with the fourth counter word 2 (asm_uniform, asm_normal below).
+//
 // Nothing here touches numpy's global stream or the fit's MT19937 machinery.
 #ifndef FOKL_PHILOX_H
 #define FOKL_PHILOX_H
@@ -86,6 +89,28 @@ FOKL_HD double inf_normal(uint32_t seed, uint32_t draw_id, uint32_t iteration, u
 {
     uint32_t w[4];
     philox4x32_10(iteration, purpose, index, 1u, seed, draw_id, w);
+    return sqrt(-2.0 * log(1.0 - emb_unit(w[0], w[1]))) * cos(6.283185307179586476925 * emb_unit(w[2], w[3]));
+}
+
+// fokl_assimilate_device.inc / dynamics.assimilate: the bootstrap particle filter.  key = (seed, posterior draw), counter =
+// (step, purpose, index, 2): the fourth word keeps these streams apart from every one above (0 and 1).  `step` is the point
+// of the time axis the number is drawn for; purposes 0 .. 7 are the process noise of state j (index = particle).
+constexpr int ASM_PURPOSE_INIT = 8;       // step 0: the normal that spreads particle i of state j at point 0, index 64 j + i
+constexpr int ASM_PURPOSE_RESAMPLE = 9;   // the uniform of the systematic resampling at point `step` (index 0)
+constexpr int ASM_PURPOSE_DRAW_INDEX = 10;   // draw id 0, step 0, index 0: the uniform behind the result's draw_index
+constexpr int ASM_PURPOSE_LAST = ASM_PURPOSE_DRAW_INDEX;
+
+FOKL_HD double asm_uniform(uint32_t seed, uint32_t draw_id, uint32_t step, uint32_t purpose, uint32_t index)
+{
+    uint32_t w[4];
+    philox4x32_10(step, purpose, index, 2u, seed, draw_id, w);
+    return emb_unit(w[0], w[1]);
+}
+
+FOKL_HD double asm_normal(uint32_t seed, uint32_t draw_id, uint32_t step, uint32_t purpose, uint32_t index)
+{
+    uint32_t w[4];
+    philox4x32_10(step, purpose, index, 2u, seed, draw_id, w);
     return sqrt(-2.0 * log(1.0 - emb_unit(w[0], w[1]))) * cos(6.283185307179586476925 * emb_unit(w[2], w[3]));
 }
 

@@ -85,8 +85,10 @@ struct SimTables {
     const double *spline, *bern;
 };
 
-// h * model_k(at) for every state k after the slope rule; true if a clamp or the rule acted for this lane
-template <int NS>
+// h * model_k(at) for every state k after the slope rule; true if a clamp or the rule acted for this lane.  CS is the
+// stride of the coefficients behind cf: SIM_LANES where every lane has its own ([coefficient][lane], cf offset by the lane),
+// 1 where the wavefront shares one set (fokl_assimilate_device.inc: lane = particle of one draw)
+template <int NS, int CS = SIM_LANES>
 __device__ __forceinline__ bool sim_stage(const SimSystem &sys, const SimTables &tab, double *xn, double *fac,
                                           const double *cf, const double (&at)[NS], double (&dy)[NS])
 {
@@ -123,11 +125,11 @@ __device__ __forceinline__ bool sim_stage(const SimSystem &sys, const SimTables 
             phi = phi * fac[d.y * SIM_LANES];
             phi = phi * fac[d.z * SIM_LANES];
             const bool ends = d.w >= 0;                                 // wave-uniform
-            const double with = delta + cf[max(d.w, 0) * SIM_LANES] * phi;
+            const double with = delta + cf[max(d.w, 0) * CS] * phi;
             delta = ends ? with : delta;
             phi = ends ? 1.0 : phi;
         }
-        double s = (delta + cf[sys.constant[k] * SIM_LANES]) * sys.h;
+        double s = (delta + cf[sys.constant[k] * CS]) * sys.h;
         const bool outwards = (at[k] >= sys.box_hi[k] && s > 0) || (at[k] <= sys.box_lo[k] && s < 0);
         if (outwards) s = 0;
         acted = acted || outwards;
@@ -221,48 +223,16 @@ hipError_t sim_launch(fokl_ctx *ctx, int grid, size_t lds_bytes, const SimSystem
     return hipGetLastError();
 }
 
-}  // namespace
-
-extern "C" int fokl_simulate_report(const fokl_ctx *ctx, int64_t *out)
+// Every index simulate_ensemble_kernel / assimilate_kernel follow, checked on the host (they read nothing outside their
+// tables), and the system as the kernels take it.  0, or the refusal's code with its text in the context.
+static int sim_plan(fokl_ctx *ctx, const std::string &who, int n_states, double h, int n_forcing_cols, int n_norm_forcing,
+                    int n_norm, const int32_t *norm_src, const double *norm_lo, const double *norm_span, int n_forcing_factors,
+                    int n_factors, const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
+                    const int32_t *fac_degree, int n_spline_rows, int n_bern_rows, int n_entries, const int32_t *entries,
+                    const int32_t *entry_begin, const int32_t *entry_count, const int32_t *constant, int n_coef,
+                    const double *box, SimSystem &sys, int &n_bern_factors)
 {
-    if (!ctx || !out) return fail(nullptr, FOKL_ERR_ARG, "fokl_simulate_report: null argument");
-    std::memcpy(out, ctx->simulate_report, sizeof ctx->simulate_report);
-    return FOKL_OK;
-}
-
-extern "C" int fokl_simulate_ensemble(fokl_ctx *ctx, int n_members, int n_states, int64_t n_steps, double h,
-                                      int n_forcing_cols, const double *forcing, int n_norm_forcing, int n_norm,
-                                      const int32_t *norm_src, const double *norm_lo, const double *norm_span,
-                                      int n_forcing_factors, int n_factors, const int32_t *fac_norm,
-                                      const int32_t *fac_kind, const int32_t *fac_row, const int32_t *fac_degree,
-                                      int n_spline_rows, const double *spline_table, int n_bern_rows,
-                                      const double *bern_table, int n_entries, const int32_t *entries,
-                                      const int32_t *entry_begin, const int32_t *entry_count, const int32_t *constant,
-                                      int n_coef, const double *coef, const double *y0, const double *box, int cut,
-                                      double *mean, double *bounds, double *members, int32_t *first_saturation)
-{
-    const std::string who = "fokl_simulate_ensemble: ";
-    if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
-    std::memset(ctx->simulate_report, 0, sizeof ctx->simulate_report);
-    if (n_members <= 0 || n_states <= 0 || n_steps < 0 || n_forcing_cols < 0 || n_norm_forcing < 0 || n_norm < n_norm_forcing ||
-        n_forcing_factors < 0 || n_factors < n_forcing_factors || n_spline_rows < 0 || n_bern_rows < 0 || n_entries < 0 ||
-        n_coef < n_states || !entry_begin || !entry_count || !constant || !coef || !y0 || !box || !mean || !first_saturation ||
-        (n_norm > 0 && (!norm_src || !norm_lo || !norm_span)) || (n_factors > 0 && (!fac_norm || !fac_kind || !fac_row || !fac_degree)) ||
-        (n_entries > 0 && !entries) || (n_spline_rows > 0 && !spline_table) || (n_bern_rows > 0 && !bern_table) ||
-        (n_forcing_cols > 0 && n_steps > 0 && !forcing))
-        return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
-    if (n_states > SIM_MAX_STATES)
-        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_states) + " states, the kernel is built for at most " +
-                                           std::to_string(SIM_MAX_STATES));
-    if (n_steps + 1 > (int64_t)1 << 30) return fail(ctx, FOKL_ERR_ARG, who + "too many steps");
-    if (!(h > 0) || !std::isfinite(h)) return fail(ctx, FOKL_ERR_ARG, who + "h must be positive and finite");
-    if (bounds && (cut < 1 || cut >= n_members)) return fail(ctx, FOKL_ERR_ARG, who + "bounds need 1 <= cut < n_members");
-    if (bounds && n_members > GI_BAND_MAX_MEMBERS)
-        return fail(ctx, FOKL_ERR_ARG, who + "bounds are formed over at most " + std::to_string(GI_BAND_MAX_MEMBERS) +
-                                           " members (mean and members have no limit)");
-
     // ---- every index the kernel follows, checked here: it reads nothing outside its tables ----
-    SimSystem sys{};
     for (int n = 0; n < n_norm; ++n) {
         const int src = norm_src[n];
         const bool ok = n < n_norm_forcing ? (src < 0 && -(int64_t)src - 1 < n_forcing_cols) : (src >= 0 && src < n_states);
@@ -272,7 +242,8 @@ extern "C" int fokl_simulate_ensemble(fokl_ctx *ctx, int n_members, int n_states
         if (!(norm_span[n] > 0) || !std::isfinite(norm_span[n]) || !std::isfinite(norm_lo[n]))
             return fail(ctx, FOKL_ERR_ARG, who + "a normalisation needs a finite lower end and a positive finite span");
     }
-    int n_forcing_splines = 0, n_state_splines = 0, n_bern_factors = 0;
+    int n_forcing_splines = 0, n_state_splines = 0;
+    n_bern_factors = 0;
     for (int f = 0; f < n_factors; ++f) {
         const bool is_forcing = f < n_forcing_factors, spline = fac_kind[f] == 0;
         if (fac_kind[f] != 0 && fac_kind[f] != 1) return fail(ctx, FOKL_ERR_ARG, who + "a factor's kernel is neither 0 (splines) nor 1 (Bernoulli)");
@@ -318,6 +289,56 @@ extern "C" int fokl_simulate_ensemble(fokl_ctx *ctx, int n_members, int n_states
     sys.n_coef = n_coef;
     sys.n_forcing_cols = n_forcing_cols;
     sys.h = h;
+    return FOKL_OK;
+}
+
+}  // namespace
+
+extern "C" int fokl_simulate_report(const fokl_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return fail(nullptr, FOKL_ERR_ARG, "fokl_simulate_report: null argument");
+    std::memcpy(out, ctx->simulate_report, sizeof ctx->simulate_report);
+    return FOKL_OK;
+}
+
+extern "C" int fokl_simulate_ensemble(fokl_ctx *ctx, int n_members, int n_states, int64_t n_steps, double h,
+                                      int n_forcing_cols, const double *forcing, int n_norm_forcing, int n_norm,
+                                      const int32_t *norm_src, const double *norm_lo, const double *norm_span,
+                                      int n_forcing_factors, int n_factors, const int32_t *fac_norm,
+                                      const int32_t *fac_kind, const int32_t *fac_row, const int32_t *fac_degree,
+                                      int n_spline_rows, const double *spline_table, int n_bern_rows,
+                                      const double *bern_table, int n_entries, const int32_t *entries,
+                                      const int32_t *entry_begin, const int32_t *entry_count, const int32_t *constant,
+                                      int n_coef, const double *coef, const double *y0, const double *box, int cut,
+                                      double *mean, double *bounds, double *members, int32_t *first_saturation)
+{
+    const std::string who = "fokl_simulate_ensemble: ";
+    if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
+    std::memset(ctx->simulate_report, 0, sizeof ctx->simulate_report);
+    if (n_members <= 0 || n_states <= 0 || n_steps < 0 || n_forcing_cols < 0 || n_norm_forcing < 0 || n_norm < n_norm_forcing ||
+        n_forcing_factors < 0 || n_factors < n_forcing_factors || n_spline_rows < 0 || n_bern_rows < 0 || n_entries < 0 ||
+        n_coef < n_states || !entry_begin || !entry_count || !constant || !coef || !y0 || !box || !mean || !first_saturation ||
+        (n_norm > 0 && (!norm_src || !norm_lo || !norm_span)) || (n_factors > 0 && (!fac_norm || !fac_kind || !fac_row || !fac_degree)) ||
+        (n_entries > 0 && !entries) || (n_spline_rows > 0 && !spline_table) || (n_bern_rows > 0 && !bern_table) ||
+        (n_forcing_cols > 0 && n_steps > 0 && !forcing))
+        return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
+    if (n_states > SIM_MAX_STATES)
+        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_states) + " states, the kernel is built for at most " +
+                                           std::to_string(SIM_MAX_STATES));
+    if (n_steps + 1 > (int64_t)1 << 30) return fail(ctx, FOKL_ERR_ARG, who + "too many steps");
+    if (!(h > 0) || !std::isfinite(h)) return fail(ctx, FOKL_ERR_ARG, who + "h must be positive and finite");
+    if (bounds && (cut < 1 || cut >= n_members)) return fail(ctx, FOKL_ERR_ARG, who + "bounds need 1 <= cut < n_members");
+    if (bounds && n_members > GI_BAND_MAX_MEMBERS)
+        return fail(ctx, FOKL_ERR_ARG, who + "bounds are formed over at most " + std::to_string(GI_BAND_MAX_MEMBERS) +
+                                           " members (mean and members have no limit)");
+
+    SimSystem sys{};
+    int n_bern_factors = 0;
+    if (const int refused = sim_plan(ctx, who, n_states, h, n_forcing_cols, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
+                                     n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows,
+                                     n_bern_rows, n_entries, entries, entry_begin, entry_count, constant, n_coef, box, sys,
+                                     n_bern_factors))
+        return refused;
     const size_t lds_rows = (size_t)1 + n_factors + (n_norm - n_norm_forcing) + n_coef;
     const size_t lds_bytes = lds_rows * SIM_LANES * sizeof(double);
     if (lds_bytes > SIM_LDS_BUDGET)

@@ -34,6 +34,7 @@
  *                              per posterior draw (fokl_gpy_amd/infer.py), what its last launches ran, and its
  *                              counter-based random numbers as the host sees them
  *   fokl_simulate_ensemble / fokl_simulate_report
+ *   fokl_assimilate_ensemble / fokl_assimilate_report / fokl_assimilate_rng
  *                              a system of fitted models, wired by names, integrated for every posterior draw at once
  *                              (fokl_gpy_amd/dynamics.py), and what its last call ran
  *   fokl_embedded_hmc / fokl_embedded_rng
@@ -1099,6 +1100,75 @@ int fokl_simulate_ensemble(fokl_ctx *ctx, int n_members, int n_states, int64_t n
  *   out[7]  steps per launch
  */
 int fokl_simulate_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* A particle filter of such a system against measurements (csrc/fokl_assimilate_device.inc; dynamics.py)    */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_ASSIMILATE_REPORT_LEN 9
+#define FOKL_ASSIMILATE_PARTICLES 64
+
+/*
+ * A bootstrap particle filter per posterior draw: 64 particles follow fokl_simulate_ensemble's Runge-Kutta step with the
+ * draw's coefficients, receive process noise, and are weighted and resampled at the observed points.  The plan of the system
+ * is dynamics._prepare's (the arguments up to `box` mean what they mean for fokl_simulate_ensemble, except coef), the
+ * arithmetic is stated by dynamics.assimilate_host (the module docstring of fokl_gpy_amd/dynamics.py).  Host memory,
+ * row-major:
+ *   coef [n_draws, n_coef] (a draw's coefficients are contiguous); y0 [n_states, n_draws]; draw_ids [n_draws]: the second
+ *          key word of a draw's random numbers (fokl_assimilate_rng)
+ *   obs_state [n_observed] the state every measured column reads (distinct), obs_sd [n_observed] > 0
+ *   obs_row [n_steps + 1] int32: the row of `data` measured at a point, -1 none; the rows appear as 0, 1, ... n_obs - 1
+ *   data [n_obs, n_observed] true scale, NaN = missing; obs_const [n_obs] = the sum over a row's present entries of
+ *          log(obs_sd sqrt(2 pi)), subtracted from the row's evidence increment
+ *   process_q [n_states] = process_sd sqrt(h) >= 0 (0: no number is drawn), y0_sd [n_states] >= 0
+ *   threshold = resample_below x 64 in [0, 64]: a row resamples where its ESS is below it
+ *   stats [n_draws, n_obs, 2 n_states + 3]: the weighted means of the states, their weighted variances, the ESS (all
+ *          before resampling), the increment of the log evidence (-inf: the draw collapsed here), 1.0 if it resampled
+ *   particles_out [n_draws, n_obs, 64, n_states] and weights_out [n_draws, n_obs, 64], before resampling; both or neither NULL
+ *   first_saturation [n_draws] int32: the first step in which a clamp or the slope rule acted for any particle, -1 never
+ *   collapsed [n_draws] int32: the first row at which no particle had a positive weight, -1 never
+ * One wavefront per workgroup and draw, lane = particle; LDS bytes = (1 + n_factors + n_norm - n_norm_forcing) x 64 x 8 +
+ * 64 x 8 (the exchange row) + n_coef x 8, at most 144 KB -- the coefficients are held once, so systems that
+ * fokl_simulate_ensemble refuses for LDS run here.  Sums and maxima over the particles are xor butterflies (offsets 32 .. 1),
+ * the prefix sum a Hillis-Steele scan (offsets 1 .. 32); no atomics: the same arguments give the same bits.  The steps are
+ * cut into launches of FOKL_ASSIMILATE_STEPS_PER_LAUNCH (environment, default 512): the cut changes no bit.
+ * Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched, the dataset and pending launches are left
+ * alone): what fokl_simulate_ensemble refuses of a system (its LDS bound excepted), the LDS bytes above, an observed column
+ * outside the states or twice the same, obs_sd not positive, negative noise, a threshold outside [0, 64], no observation,
+ * an observation table that is not 0, 1, ... in order or disagrees with n_obs.
+ * Kernel time: FOKL_K_INTEGRATE.  Blocking; everything uploaded is freed before it returns.
+ */
+int fokl_assimilate_ensemble(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
+                             const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
+                             const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
+                             const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
+                             const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
+                             const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
+                             const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
+                             const double *y0, const double *box, const uint32_t *draw_ids, int n_observed,
+                             const int32_t *obs_state, const double *obs_sd, int n_obs, const int32_t *obs_row,
+                             const double *data, const double *obs_const, const double *process_q, const double *y0_sd,
+                             double threshold, uint32_t seed, double *stats, double *particles_out, double *weights_out,
+                             int32_t *first_saturation, int32_t *collapsed);
+
+/*
+ * The last fokl_assimilate_ensemble call on `ctx`, out [FOKL_ASSIMILATE_REPORT_LEN] (host values, no launch); zeros after a
+ * call that was refused or failed:
+ *   out[0]  NS: the kernel instance (states)     out[1]  draws     out[2]  workgroups = wavefronts = draws
+ *   out[3]  dynamic LDS bytes     out[4]  launches     out[5]  steps per launch     out[6]  observations
+ *   out[7]  spline factors     out[8]  Bernoulli factors
+ */
+int fokl_assimilate_report(const fokl_ctx *ctx, int64_t *out);
+
+/*
+ * out[e * count + j], e < n_draws, j < count: the number the filter draws for draw id draw_ids[e] at point `step` of the
+ * time axis for `purpose` and index j.  Philox 4x32-10, key (seed, draw id), counter (step, purpose, index, 2).  Purposes
+ * 0 .. 7: the process-noise normal of state `purpose`, index = particle; 8: the normal that spreads the start (step 0,
+ * index 64 j + particle); 9: the uniform of the systematic resampling (index 0); 10: the uniform behind the result's
+ * draw_index (draw id 0, step 0, index 0).  Host code, no device.  FOKL_ERR_ARG for another purpose.
+ */
+int fokl_assimilate_rng(uint32_t seed, const uint32_t *draw_ids, int n_draws, uint32_t step, int purpose, int count,
+                        double *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* What the fit kernels ran: K1 basis build, K2 Gram block, K3 residual moments (csrc/fokl_hip.hip)          */
