@@ -213,6 +213,12 @@ SIGNATURES = {
                                          c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
                                          ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_assimilate_report': (c_int, [c_vp, c_vp]),
+    'fokl_control_solve': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp,
+                                   c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,
+                                   c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp,
+                                   c_int, c_int, c_vp, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp, c_vp]),
+    'fokl_control_report': (c_int, [c_vp, c_vp]),
     'fokl_assimilate_rng': (c_int, [ctypes.c_uint32, c_vp, c_int, ctypes.c_uint32, c_int, c_int, c_vp]),
     'fokl_model_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_dbl,
                                     c_int, c_dbl, c_vp, c_vp, c_vp, c_vp]),
@@ -2310,6 +2316,66 @@ class DeviceContext:
         out = np.zeros(9, dtype=np.int64)
         self._ck(self._lib.fokl_assimilate_report(self._h, _ptr(out)))
         keys = ('NS', 'draws', 'grid', 'lds_bytes', 'launches', 'steps_per_launch', 'observations', 'spline_factors',
+                'bernoulli_factors')
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def control_solve(self, p):
+        """fokl_control_solve for a system prepared by ``dynamics._prepare_control`` -> (solved, best_start [E] int32,
+        members [E, n_states, P], first_saturation [E] int32); ``solved`` holds z [E, S, D], cost, cost_start, status,
+        iterations, descent_steps [E, S] and, for max_iter == 0, ``first_pass`` (F [E, S], g [E, S, D], H [E, S, D, D]).  Needs no uploaded
+        dataset and leaves one alone."""
+        K, E, P, S, D = int(p['K']), int(p['E']), int(p['n_steps']) + 1, int(p['starts']), int(p['D'])
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
+        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
+        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
+        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
+        coef, y0, box = f64(np.asarray(p['coef']).T), f64(p['y0']), f64(p['box'])
+        seg_first, norm_control = i32(p['seg_first']), i32(p['norm_control'])
+        lo, width, ref, z0 = f64(p['ctl_lo']), f64(p['ctl_width']), f64(p['ref']), f64(p['z0'])
+        wt, term, lim_lo, lim_hi, move, prev = (f64(p[key]) for key in ('wt', 'term', 'lim_lo', 'lim_hi', 'move', 'prev'))
+        nc = int(p['n_controls'])
+        if coef.ndim != 2 or coef.shape[0] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
+                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
+                not (norm_src.shape == norm_lo.shape == norm_span.shape) or \
+                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
+                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21 or seg_first.ndim != 1 or \
+                D != nc * seg_first.shape[0] or norm_control.shape != (int(p['n_norm_forcing']),) or lo.shape != (nc,) or \
+                width.shape != (nc,) or move.shape != (nc,) or prev.shape != (nc,) or ref.shape != (K, P) or \
+                not (wt.shape == term.shape == lim_lo.shape == lim_hi.shape == (K,)) or z0.shape != (S, D):
+            raise ValueError("control_solve: array shapes disagree")
+        z = np.empty((E, S, D), dtype=np.float64)
+        cost, cost_start = np.empty((E, S), dtype=np.float64), np.empty((E, S), dtype=np.float64)
+        status, iterations = np.empty((E, S), dtype=np.int32), np.empty((E, S), dtype=np.int32)
+        descent = np.empty((E, S), dtype=np.int32)
+        best, first = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
+        members = np.empty((E, K, P), dtype=np.float64)
+        want_first = int(p['max_iter']) == 0
+        fF = np.empty((E, S), dtype=np.float64) if want_first else None
+        fg = np.empty((E, S, D), dtype=np.float64) if want_first else None
+        fH = np.empty((E, S, D, D), dtype=np.float64) if want_first else None
+        self._ck(self._lib.fokl_control_solve(
+            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
+            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
+            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
+            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[1], _ptr(coef), _ptr(y0),
+            _ptr(box), nc, seg_first.shape[0], _ptr(seg_first), _ptr(norm_control), _ptr(lo), _ptr(width), _ptr(ref), _ptr(wt),
+            _ptr(term), _ptr(lim_lo), _ptr(lim_hi), float(p['hl']), _ptr(move), _ptr(prev), int(bool(p['has_previous'])), S,
+            _ptr(z0), int(p['max_iter']), float(p['tol']), _ptr(z), _ptr(cost), _ptr(cost_start), _ptr(status), _ptr(iterations),
+            _ptr(descent), _ptr(best), _ptr(members), _ptr(first), _ptr(fF), _ptr(fg), _ptr(fH)))
+        solved = dict(z=z, cost=cost, cost_start=cost_start, status=status, iterations=iterations, descent_steps=descent)
+        if want_first:
+            solved['first_pass'] = dict(F=fF, g=fg, H=fH)
+        return solved, best, members, first
+
+    def control_report(self):
+        """What the last ``control_solve`` on this context ran (fokl_control_report; host values, no launch): ``NS`` (the
+        kernel instance = states), ``solves`` (= workgroups = wavefronts), ``D``, ``lds_bytes``, ``launches_queued``,
+        ``launches_with_work``, ``spline_factors`` and ``bernoulli_factors``.  Zeros after a refused call."""
+        out = np.zeros(8, dtype=np.int64)
+        self._ck(self._lib.fokl_control_report(self._h, _ptr(out)))
+        keys = ('NS', 'solves', 'D', 'lds_bytes', 'launches_queued', 'launches_with_work', 'spline_factors',
                 'bernoulli_factors')
         return dict(zip(keys, (int(v) for v in out)))
 

@@ -1,0 +1,799 @@
+// dynamics.control (textually included by fokl_hip.hip, after fokl_assimilate_device.inc): which inputs make the states of a
+// system of fitted models do what is wanted -- one bounded least-squares solve per (posterior draw, start), projected
+// Gauss-Newton with the Jacobian from forward sensitivities of the Runge-Kutta scheme as executed.
+//
+// The statement of the arithmetic is dynamics.control_host (fokl_gpy_amd/dynamics.py, module docstring); this file follows it
+// operation for operation and in its order: only + - * /, sqrt and comparisons, compiled under the tree's
+// -ffp-contract=off.  The values of a step are simulate_ensemble_kernel's (sim_clamp / sim_cubic / sim_horner / sim_stage of
+// fokl_simulate_device.inc; ctl_cubic / ctl_horner / ctl_stage are their twins that carry a tangent and form the value by
+// the same operations), so a trajectory under the returned controls is dynamics.simulate_host's bit for bit.
+//
+// control_iterate_kernel<NS>: one wavefront per workgroup and solve; one launch is one iteration of every solve that is
+// still running (a finished solve returns at once).  Iterate, status and counters live in device memory between launches.
+//   tangent pass   lane d < D carries the nominal trajectory (wave-uniform, computed in every lane) and direction d's
+//                  tangent; states and tangents are registers.  Per residual g_d += 2 w r t_d needs no other lane, and
+//                  H[d][d'] += (2 w t_d) t_d' reads the 64 tangents from the exchange row
+//   stop test      the projected-gradient maximum is the xor butterfly (asm_max)
+//   Cholesky       lane = row, in place in H; column entries and pivots are read from LDS at wave-uniform addresses
+//   trial pass     lane i < 31 tries P(z + 2^-i d), lane 32 + i tries P(z - 2^-i g): simulate's step (sim_stage with the
+//                  draw's coefficients once) with the controlled columns' forcing factors from the lane's own trial point;
+//                  each lane accumulates its own F; the first passing lane comes from a ballot
+// control_trajectory_kernel<NS> is the trial pass with every lane at the accepted point and lane 0 storing.
+// LDS, as [item][lane] unless noted: values of slot 0 (1.0), the factors and the stage's normalised states; their tangents;
+// four rows of 64 (exchange, z, g, direction); row d of H as [D][64] (after the factorisation: the trial points, lane =
+// trial); the draw's coefficients ONCE ([coefficient]).  bytes = (2 (1 + factors + normalised states) + 4 + D) x 64 x 8 +
+// n_coef x 8.  No atomics, plain stores: the same arguments give the same bits, and draw e alone is draw e of the full run.
+
+namespace fokl {
+
+constexpr int CTL_MAX_D = 32;
+constexpr int CTL_MAX_STEPS = 4096;
+constexpr int CTL_TRIALS = 31;                 // alpha = 1, 1/2, ..., 2^-30
+constexpr int CTL_MAX_SOLVES = 1 << 20;
+constexpr double CTL_ARMIJO = 1e-4, CTL_NOISE = 1e-13, CTL_PIVOT_FLOOR = 1e-8;
+enum { CTL_CONVERGED = 0, CTL_ITERATION_LIMIT = 1, CTL_NON_FINITE = 2, CTL_STALLED = 3 };
+
+struct CtlProblem {
+    int D, n_controls, segments, n_starts, n_draws, n_steps, has_previous, max_iter;
+    double lo[CTL_MAX_D], width[CTL_MAX_D], move[CTL_MAX_D], prev[CTL_MAX_D];
+    double wt[SIM_MAX_STATES], term[SIM_MAX_STATES], lim_lo[SIM_MAX_STATES], lim_hi[SIM_MAX_STATES];
+    double hl, tol;
+};
+
+struct CtlTables {
+    const int *norm_control;                   // [n_norm_forcing]: the control a forcing input reads, -1 a forcing column
+    const int *seg_first;                      // [segments]: the first step of every hold
+    const double *ref;                         // [NS][n_steps + 1], NaN: not tracked
+};
+
+// sim_cubic with d value / d v: the value by the same operations (dynamics._factor_dual)
+__device__ __forceinline__ double ctl_cubic(const double *__restrict__ table, int row, double v, double &slope)
+{
+    double p = ceil(v * 499.0);
+    p = p + (p == 0.0 ? 1.0 : 0.0);
+    p = p - 1.0;
+    const double s = 499.0 * v - p;
+    const int piece = (p >= 0.0 && p <= (double)(SIM_PIECES - 1)) ? (int)p : 0;
+    const double2 *c = reinterpret_cast<const double2 *>(table + ((size_t)row * SIM_PIECES + piece) * 4);
+    const double2 c01 = c[0], c23 = c[1];
+    const double q2 = c23.x + s * c23.y;
+    const double q1 = c01.y + s * q2;
+    const double d1 = q2 + s * c23.y;
+    const double d0 = q1 + s * d1;
+    slope = 499.0 * d0;
+    return c01.x + s * q1;
+}
+
+__device__ __forceinline__ double ctl_horner(const double *__restrict__ c, int degree, double v, double &slope)
+{
+    double value = c[degree], d = 0.0;
+    for (int k = degree - 1; k >= 0; --k) {
+        d = d * v + value;
+        value = value * v + c[k];
+    }
+    slope = d;
+    return value;
+}
+
+__device__ __forceinline__ double ctl_clip01(double x)
+{
+    x = x < 0.0 ? 0.0 : x;
+    return x > 1.0 ? 1.0 : x;
+}
+
+// sim_stage<NS, 1> with tangents: txn / tfac are laid out as xn / fac
+template <int NS>
+__device__ __forceinline__ void ctl_stage(const SimSystem &sys, const SimTables &tab, double *xn, double *fac, double *txn,
+                                          double *tfac, const double *cf, const double (&at)[NS], const double (&tat)[NS],
+                                          double (&dy)[NS], double (&tdy)[NS])
+{
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+        for (int n = sys.norm_begin[j]; n < sys.norm_begin[j + 1]; ++n) {
+            bool clamped = false;
+            const double v = sim_clamp((at[j] - tab.norm_lo[n]) / tab.norm_span[n], clamped);
+            xn[(n - sys.n_norm_forcing) * SIM_LANES] = v;
+            txn[(n - sys.n_norm_forcing) * SIM_LANES] = clamped ? 0.0 : tat[j] / tab.norm_span[n];
+        }
+    for (int f = sys.n_forcing_factors; f < sys.n_factors; ++f) {
+        const int n = (tab.fac_norm[f] - sys.n_norm_forcing) * SIM_LANES;
+        double slope;
+        fac[(f + 1) * SIM_LANES] = f < sys.n_state_splines_end
+                                       ? ctl_cubic(tab.spline, tab.fac_row[f], xn[n], slope)
+                                       : ctl_horner(tab.bern + tab.fac_row[f] * SIM_BERN_WIDTH, tab.fac_degree[f], xn[n], slope);
+        tfac[(f + 1) * SIM_LANES] = slope * txn[n];
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int4 *ent = tab.entries + sys.entry_begin[k];
+        double delta = 0.0, phi = 1.0, tdelta = 0.0, tphi = 0.0;
+        for (int t = 0; t < sys.entry_count[k]; ++t) {
+            const int4 d = ent[t];
+            tphi = tphi * fac[d.x * SIM_LANES] + phi * tfac[d.x * SIM_LANES];
+            phi = phi * fac[d.x * SIM_LANES];
+            tphi = tphi * fac[d.y * SIM_LANES] + phi * tfac[d.y * SIM_LANES];
+            phi = phi * fac[d.y * SIM_LANES];
+            tphi = tphi * fac[d.z * SIM_LANES] + phi * tfac[d.z * SIM_LANES];
+            phi = phi * fac[d.z * SIM_LANES];
+            const bool ends = d.w >= 0;                                 // wave-uniform
+            const double c = cf[max(d.w, 0)];
+            const double with = delta + c * phi, twith = tdelta + c * tphi;
+            delta = ends ? with : delta;
+            tdelta = ends ? twith : tdelta;
+            phi = ends ? 1.0 : phi;
+            tphi = ends ? 0.0 : tphi;
+        }
+        double s = (delta + cf[sys.constant[k]]) * sys.h, ts = tdelta * sys.h;
+        const bool outwards = (at[k] >= sys.box_hi[k] && s > 0) || (at[k] <= sys.box_lo[k] && s < 0);
+        if (outwards) {
+            s = 0;
+            ts = 0;
+        }
+        dy[k] = s;
+        tdy[k] = ts;
+    }
+}
+
+// One residual a - b of weight w with tangent t in this lane (`act`: wave-uniform; an idle limit adds nothing)
+__device__ __forceinline__ void ctl_residual(double weight, double a, double b, double t, bool act, int D, int lane, double *ex,
+                                             double *Hl, double &F, double &noise, double &g)
+{
+    if (!act) return;
+    const double r = a - b, mag = fabs(a) + fabs(b);
+    const double q = weight * r;
+    F = F + q * r;
+    noise = noise + weight * (mag * mag);
+    g = g + (2.0 * q) * t;
+    ex[lane] = t;
+    __syncthreads();
+    const double wt2 = (2.0 * weight) * t;
+    for (int d2 = 0; d2 < D; ++d2) Hl[d2 * SIM_LANES] = Hl[d2 * SIM_LANES] + wt2 * ex[d2];
+    __syncthreads();
+}
+
+// The cost of the lane's own point zt[d * 64] (zt is offset by the lane): simulate's step with the controlled columns read
+// from the point.  With `traj` (every lane at the same point) lane 0 stores the trajectory [NS][n_steps + 1]; `first` is
+// the first step in which a clamp or the slope rule acted.
+template <int NS>
+__device__ __forceinline__ double ctl_value_pass(const SimSystem &sys, const CtlProblem &cp, const SimTables &tab,
+                                                 const CtlTables &ct, const double *__restrict__ forcing, double *xn, double *fac,
+                                                 const double *cf, const double *zt, const double (&y0)[NS], int lane,
+                                                 double *__restrict__ traj, int &first)
+{
+    double y[NS], at[NS], dy[NS] = {}, sum[NS] = {};
+    const int P = cp.n_steps + 1;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        y[j] = y0[j];
+        if (traj && lane == 0) traj[(size_t)j * P] = y[j];
+    }
+    double F = 0.0;
+    int k = 0;
+    for (int s = 0; s < cp.n_steps; ++s) {
+        if (k + 1 < cp.segments && s >= ct.seg_first[k + 1]) ++k;
+        const double *row = forcing + (size_t)s * sys.n_forcing_cols;
+        bool acted = false;
+        for (int f = 0; f < sys.n_forcing_factors; ++f) {
+            const int n = tab.fac_norm[f];
+            const int c = ct.norm_control[n];
+            const double x = c < 0 ? row[-(tab.norm_src[n] + 1)] : cp.lo[c] + zt[(c * cp.segments + k) * SIM_LANES] * cp.width[c];
+            const double v = sim_clamp((x - tab.norm_lo[n]) / tab.norm_span[n], acted);
+            fac[(f + 1) * SIM_LANES] = f < sys.n_forcing_splines
+                                           ? sim_cubic(tab.spline, tab.fac_row[f], v)
+                                           : sim_horner(tab.bern + tab.fac_row[f] * SIM_BERN_WIDTH, tab.fac_degree[f], v);
+        }
+#pragma unroll 1
+        for (int st = 0; st < 4; ++st) {
+            const double reach = st == 3 ? 1.0 : 0.5, weight = (st == 1 || st == 2) ? 2.0 : 1.0;
+#pragma unroll
+            for (int j = 0; j < NS; ++j) at[j] = st == 0 ? y[j] : y[j] + dy[j] * reach;
+            const bool stage_acted = sim_stage<NS, 1>(sys, tab, xn, fac, cf, at, dy);
+            acted = acted || stage_acted;
+#pragma unroll
+            for (int j = 0; j < NS; ++j) sum[j] = st == 0 ? dy[j] : sum[j] + weight * dy[j];
+        }
+        const int point = s + 1;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            y[j] = y[j] + sum[j] / 6;
+            if (traj && lane == 0) traj[(size_t)j * P + point] = y[j];
+            const double target = ct.ref[(size_t)j * P + point];
+            if (cp.wt[j] > 0 && target == target) {
+                const double r = y[j] - target, q = cp.wt[j] * r;
+                F = F + q * r;
+            }
+            if (point == cp.n_steps && cp.term[j] > 0) {
+                const double r = y[j] - target, q = cp.term[j] * r;
+                F = F + q * r;
+            }
+            if (cp.hl > 0 && cp.lim_hi[j] < INFINITY && y[j] > cp.lim_hi[j]) {
+                const double r = y[j] - cp.lim_hi[j], q = cp.hl * r;
+                F = F + q * r;
+            }
+            if (cp.hl > 0 && cp.lim_lo[j] > -INFINITY && y[j] < cp.lim_lo[j]) {
+                const double r = cp.lim_lo[j] - y[j], q = cp.hl * r;
+                F = F + q * r;
+            }
+        }
+        if (first < 0 && acted) first = s;
+    }
+    for (int c = 0; c < cp.n_controls; ++c) {
+        if (!(cp.move[c] > 0)) continue;
+        for (int m = 0; m < cp.segments; ++m) {
+            if (m == 0 && !cp.has_previous) continue;
+            const int d = c * cp.segments + m;
+            const double now = cp.lo[c] + zt[d * SIM_LANES] * cp.width[c];
+            const double before = m == 0 ? cp.prev[c] : cp.lo[c] + zt[(d - 1) * SIM_LANES] * cp.width[c];
+            const double r = now - before, q = cp.move[c] * r;
+            F = F + q * r;
+        }
+    }
+    return F;
+}
+
+struct CtlLds {
+    double *fac, *xn, *tfac, *txn, *ex, *zs, *gs, *ds, *H, *cf;    // fac .. txn are offset by the lane; H is not
+};
+
+__device__ __forceinline__ CtlLds ctl_lds(double *lds, const SimSystem &sys, int D, int lane)
+{
+    const size_t n_state = (size_t)(sys.n_norm - sys.n_norm_forcing), n_fac = (size_t)1 + sys.n_factors;
+    CtlLds l;
+    l.fac = lds + lane;
+    l.xn = lds + n_fac * SIM_LANES + lane;
+    l.tfac = lds + (n_fac + n_state) * SIM_LANES + lane;
+    l.txn = lds + (2 * n_fac + n_state) * SIM_LANES + lane;
+    l.ex = lds + 2 * (n_fac + n_state) * SIM_LANES;
+    l.zs = l.ex + SIM_LANES;
+    l.gs = l.zs + SIM_LANES;
+    l.ds = l.gs + SIM_LANES;
+    l.H = l.ds + SIM_LANES;
+    l.cf = l.H + (size_t)D * SIM_LANES;
+    return l;
+}
+
+// Iteration `it` of every running solve b = draw * n_starts + start.  coef [draws][n_coef]; y0 [NS][draws]; z [solves][D];
+// status (-1: running), iterations, descent (steps taken in a steepest-descent lane), cost, cost_start [solves]; work [max_iter + 1]: launch `it` found a running solve;
+// first_F [solves], first_g [solves][D], first_H [solves][D][D] (or null): the tangent pass of iteration 0.
+template <int NS>
+__global__ __launch_bounds__(SIM_LANES) void control_iterate_kernel(
+    SimSystem sys, CtlProblem cp, const int *__restrict__ norm_src, const double *__restrict__ norm_lo,
+    const double *__restrict__ norm_span, const int *__restrict__ fac_norm, const int *__restrict__ fac_row,
+    const int *__restrict__ fac_degree, const int4 *__restrict__ entries, const double *__restrict__ spline,
+    const double *__restrict__ bern, const int *__restrict__ norm_control, const int *__restrict__ seg_first,
+    const double *__restrict__ ref, const double *__restrict__ coef, const double *__restrict__ forcing,
+    const double *__restrict__ y0, double *__restrict__ z, int *__restrict__ status, int *__restrict__ iterations,
+    int *__restrict__ descent, double *__restrict__ cost, double *__restrict__ cost_start, int *__restrict__ work,
+    double *__restrict__ first_F,
+    double *__restrict__ first_g, double *__restrict__ first_H, int it)
+{
+    const size_t b = blockIdx.x;
+    if (status[b] >= 0) return;                                        // a finished solve returns at once
+    const SimTables tab{norm_src, norm_lo, norm_span, fac_norm, fac_row, fac_degree, entries, spline, bern};
+    const CtlTables ct{norm_control, seg_first, ref};
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int lane = threadIdx.x, D = cp.D, P = cp.n_steps + 1;
+    const size_t e = b / (size_t)cp.n_starts;
+    const CtlLds l = ctl_lds(lds, sys, D, lane);
+    double *Hl = l.H + lane;                                           // Hl[d' * 64] = H[lane][d']
+    l.fac[0] = 1.0;
+    l.tfac[0] = 0.0;
+    for (int c = lane; c < sys.n_coef; c += SIM_LANES) l.cf[c] = coef[e * sys.n_coef + c];
+    l.zs[lane] = lane < D ? z[b * D + lane] : 0.0;
+    for (int d2 = 0; d2 < D; ++d2) Hl[d2 * SIM_LANES] = 0.0;
+    if (lane == 0) work[it] = 1;
+    __syncthreads();
+
+    // ---- the tangent pass: F, noise (wave-uniform), g of this lane's direction, row `lane` of H ----
+    double y0r[NS], y[NS], at[NS], dy[NS] = {}, sum[NS] = {}, ty[NS] = {}, tat[NS], tdy[NS] = {}, tsum[NS] = {};
+#pragma unroll
+    for (int j = 0; j < NS; ++j) y[j] = y0r[j] = y0[(size_t)j * cp.n_draws + e];
+    double F = 0.0, noise = 0.0, g = 0.0;
+    int k = 0;
+    for (int s = 0; s < cp.n_steps; ++s) {
+        if (k + 1 < cp.segments && s >= ct.seg_first[k + 1]) ++k;
+        const double *row = forcing + (size_t)s * sys.n_forcing_cols;
+        for (int f = 0; f < sys.n_forcing_factors; ++f) {
+            const int n = tab.fac_norm[f];
+            const int c = ct.norm_control[n];
+            const double x = c < 0 ? row[-(tab.norm_src[n] + 1)] : cp.lo[c] + l.zs[c * cp.segments + k] * cp.width[c];
+            bool clamped = false;
+            const double v = sim_clamp((x - tab.norm_lo[n]) / tab.norm_span[n], clamped);
+            const double tv = (c >= 0 && lane == c * cp.segments + k && !clamped) ? cp.width[c] / tab.norm_span[n] : 0.0;
+            double slope;
+            l.fac[(f + 1) * SIM_LANES] = f < sys.n_forcing_splines
+                                             ? ctl_cubic(tab.spline, tab.fac_row[f], v, slope)
+                                             : ctl_horner(tab.bern + tab.fac_row[f] * SIM_BERN_WIDTH, tab.fac_degree[f], v, slope);
+            l.tfac[(f + 1) * SIM_LANES] = slope * tv;
+        }
+#pragma unroll 1
+        for (int st = 0; st < 4; ++st) {
+            const double reach = st == 3 ? 1.0 : 0.5, weight = (st == 1 || st == 2) ? 2.0 : 1.0;
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                at[j] = st == 0 ? y[j] : y[j] + dy[j] * reach;
+                tat[j] = st == 0 ? ty[j] : ty[j] + tdy[j] * reach;
+            }
+            ctl_stage<NS>(sys, tab, l.xn, l.fac, l.txn, l.tfac, l.cf, at, tat, dy, tdy);
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                sum[j] = st == 0 ? dy[j] : sum[j] + weight * dy[j];
+                tsum[j] = st == 0 ? tdy[j] : tsum[j] + weight * tdy[j];
+            }
+        }
+        const int point = s + 1;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            y[j] = y[j] + sum[j] / 6;
+            ty[j] = ty[j] + tsum[j] / 6;
+            const double target = ct.ref[(size_t)j * P + point];
+            if (cp.wt[j] > 0 && target == target) ctl_residual(cp.wt[j], y[j], target, ty[j], true, D, lane, l.ex, Hl, F, noise, g);
+            if (point == cp.n_steps && cp.term[j] > 0)
+                ctl_residual(cp.term[j], y[j], target, ty[j], true, D, lane, l.ex, Hl, F, noise, g);
+            if (cp.hl > 0 && cp.lim_hi[j] < INFINITY)
+                ctl_residual(cp.hl, y[j], cp.lim_hi[j], ty[j], y[j] > cp.lim_hi[j], D, lane, l.ex, Hl, F, noise, g);
+            if (cp.hl > 0 && cp.lim_lo[j] > -INFINITY)
+                ctl_residual(cp.hl, cp.lim_lo[j], y[j], -ty[j], y[j] < cp.lim_lo[j], D, lane, l.ex, Hl, F, noise, g);
+        }
+    }
+    for (int c = 0; c < cp.n_controls; ++c) {
+        if (!(cp.move[c] > 0)) continue;
+        for (int m = 0; m < cp.segments; ++m) {
+            if (m == 0 && !cp.has_previous) continue;
+            const int d = c * cp.segments + m;
+            const double now = cp.lo[c] + l.zs[d] * cp.width[c];
+            const double before = m == 0 ? cp.prev[c] : cp.lo[c] + l.zs[d - 1] * cp.width[c];
+            const double t = lane == d ? cp.width[c] : (m > 0 && lane == d - 1) ? -cp.width[c] : 0.0;
+            ctl_residual(cp.move[c], now, before, t, true, D, lane, l.ex, Hl, F, noise, g);
+        }
+    }
+    if (lane >= D) g = 0.0;
+    if (it == 0) {
+        if (lane == 0) cost_start[b] = F;
+        if (first_F) {
+            if (lane == 0) first_F[b] = F;
+            if (lane < D) {
+                first_g[b * D + lane] = g;
+                for (int d2 = 0; d2 < D; ++d2) first_H[(b * D + lane) * D + d2] = Hl[d2 * SIM_LANES];
+            }
+        }
+    }
+    if (lane == 0) cost[b] = F;
+
+    // ---- the stop test ----
+    const double zl = l.zs[lane];
+    const bool finite = F - F == 0.0 && __all((int)(g - g == 0.0));
+    const double pg = asm_max(lane < D ? fabs(ctl_clip01(zl - g) - zl) : 0.0);
+    const int code = !finite ? CTL_NON_FINITE : pg <= cp.tol ? CTL_CONVERGED : it == cp.max_iter ? CTL_ITERATION_LIMIT : -1;
+    if (code >= 0) {
+        if (lane == 0) {
+            status[b] = code;
+            iterations[b] = it;
+        }
+        return;
+    }
+
+    // ---- active set and the modified Cholesky factor, in place: L[i][k] = l.H[k * 64 + i] ----
+    const bool active = lane < D && ((zl <= 0.0 && g > 0) || (zl >= 1.0 && g < 0));
+    const unsigned long long active_mask = __ballot((int)active);
+    const double free_diag = asm_max((lane < D && !active) ? fabs(Hl[lane * SIM_LANES]) : 0.0);
+    const double floor_ = CTL_PIVOT_FLOOR * fmax(1.0, free_diag);
+    for (int j = 0; j < D; ++j) {
+        double s = 0.0;
+        if (lane >= j && lane < D) {
+            const bool either = active || ((active_mask >> j) & 1ull);
+            s = either ? (lane == j ? 1.0 : 0.0) : l.H[j * SIM_LANES + lane];
+            for (int q = 0; q < j; ++q) s = s - l.H[q * SIM_LANES + lane] * l.H[q * SIM_LANES + j];
+            if (lane == j) {
+                s = s > floor_ ? s : fmax(fabs(s), floor_);
+                l.H[j * SIM_LANES + j] = sqrt(s);
+            }
+        }
+        __syncthreads();
+        if (lane > j && lane < D) l.H[j * SIM_LANES + lane] = s / l.H[j * SIM_LANES + j];
+        __syncthreads();
+    }
+    double s = active ? 0.0 : -g;
+    for (int q = 0; q < D; ++q) {                                      // forward
+        if (lane == q) {
+            s = s / l.H[q * SIM_LANES + q];
+            l.ex[q] = s;
+        }
+        __syncthreads();
+        if (lane > q && lane < D) s = s - l.H[q * SIM_LANES + lane] * l.ex[q];
+    }
+    for (int q = D - 1; q >= 0; --q) {                                 // back
+        if (lane == q) {
+            s = s / l.H[q * SIM_LANES + q];
+            l.ds[q] = s;
+        }
+        __syncthreads();
+        if (lane < q) s = s - l.H[lane * SIM_LANES + q] * l.ds[q];
+    }
+    l.gs[lane] = g;
+    __syncthreads();
+
+    // ---- every trial point at once: the lane's own in column `lane` of the H rows ----
+    const int halving = lane & 31;
+    const bool newton = lane < 32, valid = halving < CTL_TRIALS;
+    const double alpha = __longlong_as_double((long long)(1023 - halving) << 52);      // 2^-halving
+    double slope = 0.0;
+    bool moved = false;
+    for (int d = 0; d < D; ++d) {
+        const double base = newton ? l.ds[d] : -l.gs[d];
+        const double x = ctl_clip01(l.zs[d] + alpha * base);
+        Hl[d * SIM_LANES] = x;
+        const double step = x - l.zs[d];
+        slope = slope + l.gs[d] * step;
+        moved = moved || fabs(step) > 0;
+    }
+    int unused = 0;
+    const double Ft = ctl_value_pass<NS>(sys, cp, tab, ct, forcing, l.xn, l.fac, l.cf, Hl, y0r, lane, nullptr, unused);
+    const bool ok = valid && moved && Ft <= (F + CTL_ARMIJO * (slope < 0 ? slope : 0.0)) + CTL_NOISE * noise;
+    const unsigned long long passed = __ballot((int)ok);
+    const unsigned int by_newton = (unsigned int)(passed & 0x7FFFFFFFull), by_descent = (unsigned int)((passed >> 32) & 0x7FFFFFFFull);
+    if (by_newton == 0u && by_descent == 0u) {
+        if (lane == 0) {
+            status[b] = CTL_STALLED;
+            iterations[b] = it;
+        }
+        return;
+    }
+    const int taken = by_newton ? __builtin_ctz(by_newton) : 32 + __builtin_ctz(by_descent);
+    if (lane < D) z[b * D + lane] = l.H[lane * SIM_LANES + taken];
+    if (lane == 0 && taken >= 32) descent[b] = descent[b] + 1;
+}
+
+// The trajectory of draw e under z [draws][D]: members [draws][NS][n_steps + 1], first [draws]
+template <int NS>
+__global__ __launch_bounds__(SIM_LANES) void control_trajectory_kernel(
+    SimSystem sys, CtlProblem cp, const int *__restrict__ norm_src, const double *__restrict__ norm_lo,
+    const double *__restrict__ norm_span, const int *__restrict__ fac_norm, const int *__restrict__ fac_row,
+    const int *__restrict__ fac_degree, const int4 *__restrict__ entries, const double *__restrict__ spline,
+    const double *__restrict__ bern, const int *__restrict__ norm_control, const int *__restrict__ seg_first,
+    const double *__restrict__ ref, const double *__restrict__ coef, const double *__restrict__ forcing,
+    const double *__restrict__ y0, const double *__restrict__ z, double *__restrict__ members, int *__restrict__ first)
+{
+    const SimTables tab{norm_src, norm_lo, norm_span, fac_norm, fac_row, fac_degree, entries, spline, bern};
+    const CtlTables ct{norm_control, seg_first, ref};
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int lane = threadIdx.x, D = cp.D;
+    const size_t e = blockIdx.x;
+    const CtlLds l = ctl_lds(lds, sys, D, lane);
+    double *Hl = l.H + lane;
+    l.fac[0] = 1.0;
+    for (int c = lane; c < sys.n_coef; c += SIM_LANES) l.cf[c] = coef[e * sys.n_coef + c];
+    for (int d = 0; d < D; ++d) Hl[d * SIM_LANES] = z[e * D + d];
+    __syncthreads();
+    double y0r[NS];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) y0r[j] = y0[(size_t)j * cp.n_draws + e];
+    int saturated = -1;
+    (void)ctl_value_pass<NS>(sys, cp, tab, ct, forcing, l.xn, l.fac, l.cf, Hl, y0r, lane,
+                             members + e * (size_t)NS * (cp.n_steps + 1), saturated);
+    if (lane == 0) first[e] = saturated;
+}
+
+}  // namespace fokl
+
+namespace {
+
+template <int NS>
+hipError_t ctl_launch(fokl_ctx *ctx, int grid, size_t lds_bytes, const SimSystem &sys, const CtlProblem &cp, const SimTables &tab,
+                      const CtlTables &ct, const double *coef, const double *forcing, const double *y0, double *z, int *status,
+                      int *iterations, int *descent, double *cost, double *cost_start, int *work, double *first_F,
+                      double *first_g, double *first_H, int it)
+{
+    if (lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(control_iterate_kernel<NS>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS_BUDGET);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(control_iterate_kernel<NS>, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, tab.norm_src,
+                       tab.norm_lo, tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline, tab.bern,
+                       ct.norm_control, ct.seg_first, ct.ref, coef, forcing, y0, z, status, iterations, descent, cost, cost_start, work,
+                       first_F, first_g, first_H, it);
+    return hipGetLastError();
+}
+
+template <int NS>
+hipError_t ctl_trajectory(fokl_ctx *ctx, int grid, size_t lds_bytes, const SimSystem &sys, const CtlProblem &cp,
+                          const SimTables &tab, const CtlTables &ct, const double *coef, const double *forcing, const double *y0,
+                          const double *z, double *members, int *first)
+{
+    if (lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(control_trajectory_kernel<NS>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS_BUDGET);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(control_trajectory_kernel<NS>, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, tab.norm_src,
+                       tab.norm_lo, tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline, tab.bern,
+                       ct.norm_control, ct.seg_first, ct.ref, coef, forcing, y0, z, members, first);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int fokl_control_report(const fokl_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return fail(nullptr, FOKL_ERR_ARG, "fokl_control_report: null argument");
+    std::memcpy(out, ctx->control_report, sizeof ctx->control_report);
+    return FOKL_OK;
+}
+
+extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
+                                  const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
+                                  const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
+                                  const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
+                                  const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
+                                  const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
+                                  const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
+                                  const double *y0, const double *box, int n_controls, int n_segments,
+                                  const int32_t *seg_first, const int32_t *norm_control, const double *ctl_lo,
+                                  const double *ctl_width, const double *ref, const double *track_weight,
+                                  const double *terminal_weight, const double *limit_lo, const double *limit_hi,
+                                  double limit_weight, const double *move_weight, const double *previous, int has_previous,
+                                  int n_starts, const double *z0, int max_iter, double tol, double *z, double *cost,
+                                  double *cost_start, int32_t *status, int32_t *iterations, int32_t *descent_steps,
+                                  int32_t *best_start,
+                                  double *members, int32_t *first_saturation, double *first_F, double *first_g,
+                                  double *first_H)
+{
+    const std::string who = "fokl_control_solve: ";
+    if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
+    std::memset(ctx->control_report, 0, sizeof ctx->control_report);
+    if (n_draws <= 0 || n_states <= 0 || n_steps < 0 || n_forcing_cols < 0 || n_norm_forcing < 0 || n_norm < n_norm_forcing ||
+        n_forcing_factors < 0 || n_factors < n_forcing_factors || n_spline_rows < 0 || n_bern_rows < 0 || n_entries < 0 ||
+        n_coef < n_states || !entry_begin || !entry_count || !constant || !coef || !y0 || !box || !seg_first || !norm_control ||
+        !ctl_lo || !ctl_width || !ref || !track_weight || !terminal_weight || !limit_lo || !limit_hi || !move_weight ||
+        !previous || !z0 || !z || !cost || !cost_start || !status || !iterations || !descent_steps || !best_start || !members ||
+        !first_saturation || (first_F == nullptr) != (first_g == nullptr) || (first_F == nullptr) != (first_H == nullptr) ||
+        (n_norm > 0 && (!norm_src || !norm_lo || !norm_span)) || (n_factors > 0 && (!fac_norm || !fac_kind || !fac_row || !fac_degree)) ||
+        (n_entries > 0 && !entries) || (n_spline_rows > 0 && !spline_table) || (n_bern_rows > 0 && !bern_table) ||
+        (n_forcing_cols > 0 && n_steps > 0 && !forcing))
+        return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
+    if (n_states > SIM_MAX_STATES)
+        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_states) + " states, the kernel is built for at most " +
+                                           std::to_string(SIM_MAX_STATES));
+    if (n_steps < 1) return fail(ctx, FOKL_ERR_ARG, who + "no step at all: the horizon needs at least one step");
+    if (n_steps > CTL_MAX_STEPS)
+        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_steps) + " steps, a call handles at most " + std::to_string(CTL_MAX_STEPS));
+    if (!(h > 0) || !std::isfinite(h)) return fail(ctx, FOKL_ERR_ARG, who + "h must be positive and finite");
+
+    SimSystem sys{};
+    int n_bern_factors = 0;
+    if (const int refused = sim_plan(ctx, who, n_states, h, n_forcing_cols, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
+                                     n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows,
+                                     n_bern_rows, n_entries, entries, entry_begin, entry_count, constant, n_coef, box, sys,
+                                     n_bern_factors))
+        return refused;
+
+    // ---- the decision values, their box and the cost ----
+    if (n_controls < 1 || n_segments < 1 || (int64_t)n_controls * n_segments > CTL_MAX_D)
+        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_controls) + " controls x " + std::to_string(n_segments) +
+                                           " segments: at least one and at most " + std::to_string(CTL_MAX_D) + " decision values");
+    const int D = n_controls * n_segments;
+    if (seg_first[0] != 0) return fail(ctx, FOKL_ERR_ARG, who + "the first segment must begin with step 0");
+    for (int k = 1; k < n_segments; ++k)
+        if (seg_first[k] <= seg_first[k - 1] || seg_first[k] >= n_steps)
+            return fail(ctx, FOKL_ERR_ARG, who + "the segments' first steps must increase and lie below the number of steps");
+    CtlProblem cp{};
+    for (int c = 0; c < n_controls; ++c) {
+        if (!std::isfinite(ctl_lo[c]) || !std::isfinite(ctl_width[c]) || !(ctl_width[c] > 0))
+            return fail(ctx, FOKL_ERR_ARG, who + "a control's box is empty or not finite");
+        if (!(move_weight[c] >= 0) || !std::isfinite(move_weight[c]) || !std::isfinite(previous[c]))
+            return fail(ctx, FOKL_ERR_ARG, who + "move weights must be non-negative and finite, previous finite");
+        bool read = false;
+        for (int n = 0; n < n_norm_forcing; ++n) {
+            if (norm_control[n] != c) continue;
+            read = true;
+            const double a = (ctl_lo[c] - norm_lo[n]) / norm_span[n], b = (ctl_lo[c] + ctl_width[c] - norm_lo[n]) / norm_span[n];
+            if (a < -1e-9 || b > 1 + 1e-9)
+                return fail(ctx, FOKL_ERR_ARG, who + "a control's box reaches outside the training range of a column that reads it");
+        }
+        if (!read) return fail(ctx, FOKL_ERR_ARG, who + "a control is read by no model");
+        cp.lo[c] = ctl_lo[c];
+        cp.width[c] = ctl_width[c];
+        cp.move[c] = move_weight[c];
+        cp.prev[c] = previous[c];
+    }
+    for (int n = 0; n < n_norm_forcing; ++n)
+        if (norm_control[n] < -1 || norm_control[n] >= n_controls)
+            return fail(ctx, FOKL_ERR_ARG, who + "a forcing input reads outside the controls");
+    if (!(limit_weight >= 0) || !std::isfinite(limit_weight))
+        return fail(ctx, FOKL_ERR_ARG, who + "the limit weight must be non-negative and finite");
+    const int64_t n_points = n_steps + 1;
+    bool any_residual = false;
+    for (int j = 0; j < n_states; ++j) {
+        if (!(track_weight[j] >= 0) || !std::isfinite(track_weight[j]) || !(terminal_weight[j] >= 0) || !std::isfinite(terminal_weight[j]))
+            return fail(ctx, FOKL_ERR_ARG, who + "negative weights are refused: tracking and terminal weights must be non-negative and finite");
+        if (std::isnan(limit_lo[j]) || std::isnan(limit_hi[j]) || limit_lo[j] > limit_hi[j] || limit_lo[j] == INFINITY || limit_hi[j] == -INFINITY)
+            return fail(ctx, FOKL_ERR_ARG, who + "a state's limits must be lower <= upper (infinite: open)");
+        for (int64_t q = 0; q < n_points; ++q) {
+            const double r = ref[j * n_points + q];
+            if (std::isinf(r)) return fail(ctx, FOKL_ERR_ARG, who + "a target is infinite (NaN: not tracked)");
+            if (q > 0 && !std::isnan(r) && track_weight[j] > 0) any_residual = true;
+        }
+        if (terminal_weight[j] > 0) {
+            if (std::isnan(ref[j * n_points + n_steps]))
+                return fail(ctx, FOKL_ERR_ARG, who + "a terminal weight needs a target at the last point");
+            any_residual = true;
+        }
+        if (limit_weight > 0 && (std::isfinite(limit_lo[j]) || std::isfinite(limit_hi[j]))) any_residual = true;
+        cp.wt[j] = track_weight[j];
+        cp.term[j] = terminal_weight[j];
+        cp.lim_lo[j] = limit_lo[j];
+        cp.lim_hi[j] = limit_hi[j];
+    }
+    for (int c = 0; c < n_controls; ++c)
+        if (move_weight[c] > 0 && (n_segments > 1 || has_previous)) any_residual = true;
+    if (!any_residual) return fail(ctx, FOKL_ERR_ARG, who + "no residual at all: nothing is tracked, limited or penalised");
+    if (n_starts < 1) return fail(ctx, FOKL_ERR_ARG, who + "starts must be at least 1");
+    if ((int64_t)n_draws * n_starts > CTL_MAX_SOLVES)
+        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_draws) + " draws x " + std::to_string(n_starts) +
+                                           " starts: one call runs at most " + std::to_string(CTL_MAX_SOLVES) + " solves");
+    if (max_iter < 0 || !(tol >= 0)) return fail(ctx, FOKL_ERR_ARG, who + "max_iter and tol must be non-negative");
+    for (size_t i = 0; i < (size_t)n_starts * D; ++i)
+        if (!(z0[i] >= 0.0 && z0[i] <= 1.0)) return fail(ctx, FOKL_ERR_ARG, who + "a start lies outside the box [0, 1]");
+    for (size_t i = 0; i < (size_t)n_states * n_draws; ++i)
+        if (!std::isfinite(y0[i])) return fail(ctx, FOKL_ERR_ARG, who + "y0 is not finite");
+    const size_t lds_lane_rows = 2 * ((size_t)1 + n_factors + (n_norm - n_norm_forcing)) + 4 + D;
+    const size_t lds_bytes = lds_lane_rows * SIM_LANES * sizeof(double) + (size_t)n_coef * sizeof(double);
+    if (lds_bytes > SIM_LDS_BUDGET)
+        return fail(ctx, FOKL_ERR_ARG, who + "the system needs " + std::to_string(lds_bytes) + " bytes of LDS ((2 x (1 + " +
+                                           std::to_string(n_factors) + " factors + " + std::to_string(n_norm - n_norm_forcing) +
+                                           " normalised states) + 4 + " + std::to_string(D) + " decision values) x 64 x 8 + " +
+                                           std::to_string(n_coef) + " coefficients x 8), a wavefront has " +
+                                           std::to_string(SIM_LDS_BUDGET));
+    cp.D = D;
+    cp.n_controls = n_controls;
+    cp.segments = n_segments;
+    cp.n_starts = n_starts;
+    cp.n_draws = n_draws;
+    cp.n_steps = (int)n_steps;
+    cp.has_previous = has_previous ? 1 : 0;
+    cp.max_iter = max_iter;
+    cp.hl = limit_weight;
+    cp.tol = tol;
+
+    const size_t E = (size_t)n_draws, B = E * n_starts;
+    const int poll = std::max(0, env_int("FOKL_CONTROL_POLL", 8));    // read the statuses every `poll` launches; 0: never
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DeviceBuffers buf;
+    int *d_norm_src = nullptr, *d_fac_norm = nullptr, *d_fac_row = nullptr, *d_fac_degree = nullptr, *d_norm_control = nullptr,
+        *d_seg = nullptr, *d_status = nullptr, *d_iterations = nullptr, *d_descent = nullptr, *d_work = nullptr, *d_first = nullptr;
+    int4 *d_entries = nullptr;
+    double *d_norm_lo = nullptr, *d_norm_span = nullptr, *d_spline = nullptr, *d_bern = nullptr, *d_coef = nullptr,
+           *d_forcing = nullptr, *d_y0 = nullptr, *d_ref = nullptr, *d_z = nullptr, *d_cost = nullptr, *d_cost_start = nullptr,
+           *d_fF = nullptr, *d_fg = nullptr, *d_fH = nullptr, *d_zbest = nullptr, *d_members = nullptr;
+    std::vector<double> z_start(B * D);
+    for (size_t b = 0; b < B; ++b) std::memcpy(z_start.data() + b * D, z0 + (b % n_starts) * D, D * sizeof(double));
+    std::vector<int32_t> h_status(B, -1), h_zero((size_t)max_iter + 1, 0);
+    std::vector<double> h_nan(B, NAN);
+    HIP_TRY(ctx, buf.upload(&d_norm_src, norm_src, (size_t)n_norm));
+    HIP_TRY(ctx, buf.upload(&d_norm_lo, norm_lo, (size_t)n_norm));
+    HIP_TRY(ctx, buf.upload(&d_norm_span, norm_span, (size_t)n_norm));
+    HIP_TRY(ctx, buf.upload(&d_fac_norm, fac_norm, (size_t)n_factors));
+    HIP_TRY(ctx, buf.upload(&d_fac_row, fac_row, (size_t)n_factors));
+    HIP_TRY(ctx, buf.upload(&d_fac_degree, fac_degree, (size_t)n_factors));
+    HIP_TRY(ctx, buf.upload(&d_entries, entries, (size_t)n_entries));
+    HIP_TRY(ctx, buf.upload(&d_spline, spline_table, (size_t)n_spline_rows * SIM_PIECES * 4));
+    HIP_TRY(ctx, buf.upload(&d_bern, bern_table, (size_t)n_bern_rows * SIM_BERN_WIDTH));
+    HIP_TRY(ctx, buf.upload(&d_norm_control, norm_control, (size_t)n_norm_forcing));
+    HIP_TRY(ctx, buf.upload(&d_seg, seg_first, (size_t)n_segments));
+    HIP_TRY(ctx, buf.upload(&d_ref, ref, (size_t)n_states * n_points));
+    HIP_TRY(ctx, buf.upload(&d_coef, coef, E * n_coef));
+    HIP_TRY(ctx, buf.upload(&d_forcing, forcing, (size_t)n_steps * n_forcing_cols));
+    HIP_TRY(ctx, buf.upload(&d_y0, y0, E * n_states));
+    HIP_TRY(ctx, buf.upload(&d_z, z_start.data(), B * D));
+    HIP_TRY(ctx, buf.upload(&d_status, h_status.data(), B));
+    HIP_TRY(ctx, buf.upload(&d_iterations, h_status.data(), B));
+    std::vector<int32_t> h_none(B, 0);
+    HIP_TRY(ctx, buf.upload(&d_descent, h_none.data(), B));
+    HIP_TRY(ctx, buf.upload(&d_cost, h_nan.data(), B));
+    HIP_TRY(ctx, buf.upload(&d_cost_start, h_nan.data(), B));
+    HIP_TRY(ctx, buf.upload(&d_work, h_zero.data(), h_zero.size()));
+    if (first_F) {
+        HIP_TRY(ctx, buf.get(&d_fF, B));
+        HIP_TRY(ctx, buf.get(&d_fg, B * D));
+        HIP_TRY(ctx, buf.get(&d_fH, B * D * D));
+    }
+    HIP_TRY(ctx, buf.get(&d_zbest, E * D));
+    HIP_TRY(ctx, buf.get(&d_members, E * n_states * n_points));
+    HIP_TRY(ctx, buf.get(&d_first, E));
+    const SimTables tab{d_norm_src, d_norm_lo, d_norm_span, d_fac_norm, d_fac_row, d_fac_degree, d_entries, d_spline, d_bern};
+    const CtlTables ct{d_norm_control, d_seg, d_ref};
+
+    double terms_per_stage = 0.0;
+    for (int k = 0; k < n_states; ++k) terms_per_stage += sys.entry_count[k];
+    int64_t queued = 0;
+    for (int it = 0; it <= max_iter; ++it) {
+        {
+            TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)B * (D + 4.0),
+                              (double)B * SIM_LANES * (double)n_steps * 4.0 * 3.0 * (8.0 * terms_per_stage + 20.0 * n_factors));
+            hipError_t launched = hipSuccess;
+#define CTL_CASE(NS)                                                                                                         \
+    case NS:                                                                                                                 \
+        launched = ctl_launch<NS>(ctx, (int)B, lds_bytes, sys, cp, tab, ct, d_coef, d_forcing, d_y0, d_z, d_status,             \
+                                  d_iterations, d_descent, d_cost, d_cost_start, d_work, d_fF, d_fg, d_fH, it);                           \
+        break;
+            switch (n_states) {
+                CTL_CASE(1) CTL_CASE(2) CTL_CASE(3) CTL_CASE(4) CTL_CASE(5) CTL_CASE(6) CTL_CASE(7) CTL_CASE(8)
+            }
+#undef CTL_CASE
+            HIP_TRY(ctx, launched);
+            ++queued;
+        }
+        if (poll > 0 && (it + 1) % poll == 0 && it < max_iter) {      // may stop queuing early: a launch without work changes nothing
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(h_status.data(), d_status, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+            bool running = false;
+            for (size_t b = 0; b < B && !running; ++b) running = h_status[b] < 0;
+            if (!running) break;
+        }
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(z, d_z, B * D * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(cost, d_cost, B * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(cost_start, d_cost_start, B * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(status, d_status, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(iterations, d_iterations, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(descent_steps, d_descent, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(h_zero.data(), d_work, h_zero.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (first_F) {
+        HIP_TRY(ctx, hipMemcpy(first_F, d_fF, B * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(first_g, d_fg, B * D * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(first_H, d_fH, B * D * D * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    for (size_t b = 0; b < B; ++b)
+        if (status[b] < 0) return fail(ctx, FOKL_ERR_HIP, who + "a solve was left running");
+    int64_t worked = 0;
+    for (int32_t w : h_zero) worked += w;
+
+    // ---- the best start of every draw (a non-finite solve is never the best), and its trajectory ----
+    std::vector<double> z_best(E * D);
+    for (size_t e = 0; e < E; ++e) {
+        int best = 0;
+        double best_key = INFINITY;
+        for (int s = 0; s < n_starts; ++s) {
+            const size_t b = e * n_starts + s;
+            const double key = (std::isfinite(cost[b]) && status[b] != CTL_NON_FINITE) ? cost[b] : INFINITY;
+            if (key < best_key) {
+                best_key = key;
+                best = s;
+            }
+        }
+        best_start[e] = best;
+        std::memcpy(z_best.data() + e * D, z + (e * n_starts + best) * D, D * sizeof(double));
+    }
+    HIP_TRY(ctx, hipMemcpy(d_zbest, z_best.data(), E * D * sizeof(double), hipMemcpyHostToDevice));
+    {
+        TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)E * n_states * n_points,
+                          (double)E * SIM_LANES * (double)n_steps * 4.0 * (8.0 * terms_per_stage + 20.0 * n_factors));
+        hipError_t launched = hipSuccess;
+#define CTL_CASE(NS)                                                                                                         \
+    case NS:                                                                                                                 \
+        launched = ctl_trajectory<NS>(ctx, n_draws, lds_bytes, sys, cp, tab, ct, d_coef, d_forcing, d_y0, d_zbest, d_members,  \
+                                      d_first);                                                                              \
+        break;
+        switch (n_states) {
+            CTL_CASE(1) CTL_CASE(2) CTL_CASE(3) CTL_CASE(4) CTL_CASE(5) CTL_CASE(6) CTL_CASE(7) CTL_CASE(8)
+        }
+#undef CTL_CASE
+        HIP_TRY(ctx, launched);
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(members, d_members, E * n_states * n_points * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(first_saturation, d_first, E * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int64_t *rep = ctx->control_report;
+    rep[0] = n_states;
+    rep[1] = (int64_t)B;
+    rep[2] = D;
+    rep[3] = (int64_t)lds_bytes;
+    rep[4] = queued;
+    rep[5] = worked;
+    rep[6] = n_factors - n_bern_factors;
+    rep[7] = n_bern_factors;
+    return FOKL_OK;
+}

@@ -70,6 +70,20 @@ extern "C" int fokl_assimilate_ensemble(fokl_ctx *, int, int, int64_t, double, i
 }
 extern "C" int fokl_assimilate_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor does the optimal control of such a system (fokl_control_device.inc); its statement is dynamics.control_host.
+extern "C" int fokl_control_solve(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
+                                  const double *, const double *, int, int, const int32_t *, const int32_t *, const int32_t *,
+                                  const int32_t *, int, const double *, int, const double *, int, const int32_t *,
+                                  const int32_t *, const int32_t *, const int32_t *, int, const double *, const double *,
+                                  const double *, int, int, const int32_t *, const int32_t *, const double *, const double *,
+                                  const double *, const double *, const double *, const double *, const double *, double,
+                                  const double *, const double *, int, int, const double *, int, double, double *, double *,
+                                  double *, int32_t *, int32_t *, int32_t *, int32_t *, double *, int32_t *, double *, double *, double *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_control_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // The multistart optimiser runs on the device only (fokl_optimize_device.inc on fokl_optimize_core.inc); its statement is
 // optimize.solve_host.
 extern "C" int fokl_model_optimize(fokl_ctx *, int, int, const int32_t *, int, const double *, const double *, int, int,

@@ -70,6 +70,62 @@ device and this host to the two maths libraries' last bits.
 Pooling over the draws at observation k: draw e weighs exp(log_evidence[e, k]) normalised over the draws (uniform if all
 are -inf); ``mean`` is the weighted mean of ``draw_mean``, ``sd`` the root of the weighted within-draw variance plus
 the weighted squared distance of ``draw_mean`` to ``mean``.
+
+``control(models, states, inputs, controls=[...], ..., targets, limits, move_weight, ...)`` answers what such a system is
+fitted for: which inputs, held piecewise constant over the coming horizon, make the states do what is wanted -- one bounded
+least-squares solve per posterior draw and start, every solve at once on the device, so the answer comes with its
+uncertainty as ``optimize``'s does.  ``control_host`` is its statement in numpy.  ``assimilate`` returns what a controller
+starts from (``draw_mean[:, :, -1]`` as ``y0`` [E, n_states], ``draw_index`` as ``draws=``), so the loop assimilate ->
+control -> apply -> assimilate closes inside the package.
+
+The cost is a sum of weighted squares of residuals a - b, listed by point: with y the trajectory of ``simulate``'s scheme
+(clamps and slope rule included) under u_ck = lo_c + z_ck (hi_c - lo_c), control c on segment k, decision value d = c K + k,
+
+  at point p = 1 .. P - 1, per state j in order:
+      tracking    weight h w_j,          y_j(p) - ref_j(p)         where w_j > 0 and ref_j(p) is not NaN
+      terminal    weight terminal_j,     y_j(P - 1) - ref_j(P - 1) at the last point, where terminal_j > 0
+      upper limit weight h limit_weight, y_j(p) - hi_j             where y_j(p) > hi_j (otherwise it adds nothing)
+      lower limit weight h limit_weight, lo_j - y_j(p)             where y_j(p) < lo_j
+  then per control c, per segment k (k = 0 only with ``previous``):
+      move        weight move_c,         u_ck - u_c,k-1            (u_c,-1 = previous_c)
+
+  F = sum weight (a - b)^2 accumulated as F = F + (weight r) r; S = sum weight (|a| + |b|)^2 is the rounding scale of F.
+
+One solve, operation for operation (only + - * /, sqrt, ceil and comparisons, in fixed orders, nothing fused):
+
+  1. Tangent pass.  Direction d (a lane of the wavefront) carries, next to every value of ``simulate``'s step, its
+     derivative with respect to z_d:
+       a controlled column   v = ((lo_c + z_ck (hi_c - lo_c)) - lo) / span, clamped as any input; t_v = (hi_c - lo_c) / span
+                             for d = c K + k (k the segment of the step), else 0; a state's input has t_v = t_y / span;
+                             a clamp that acts (v > 1 or v < 0; a value exactly on 0 or 1 is not clamped) sets t_v = 0
+       Bernoulli factor      value = c_o, slope = 0; for k = o - 1 .. 0: slope = slope v + value; value = value v + c_k
+       spline factor         the value's piece and s: q2 = c2 + s c3; q1 = c1 + s q2; value = c0 + s q1; d1 = q2 + s c3;
+                             d0 = q1 + s d1; slope = 499 d0
+       factor tangent        slope t_v
+       term                  over its entry's slots in order: t_phi = t_phi fac + phi t_fac; phi = phi fac (from 1, 0)
+       model                 delta = delta + beta phi, t_delta = t_delta + beta t_phi; the slope (delta + beta_0) h has
+                             tangent t_delta h; a slope the slope rule zeroes has tangent 0
+       step                  the stage points and the sum of the stages carry their tangents through the same formulas
+     Per residual with tangent t (of y_j: t_y; of lo_j - y_j: -t_y; of a move: hi_c - lo_c in d = c K + k, -(hi_c - lo_c)
+     in d - 1): g_d = g_d + (2 (weight r)) t_d and H[d][d'] = H[d][d'] + ((2 weight) t_d) t_d'.  So g = 2 J' r, H = 2 J' J,
+     the derivative of the scheme as executed.
+  2. Stop test: non-finite F or g ends the solve (status 2); max_d |P(z - g)_d - z_d| <= tol ends it converged (0), P the
+     clip to [0, 1] by comparisons; iteration ``max_iter`` ends it at the limit (1).  (``optimize``'s codes.)
+  3. Active set: coordinate d is active where z_d <= 0 and g_d > 0, or z_d >= 1 and g_d < 0.
+  4. Modified Cholesky of the lower triangle, column by column, row i >= j: s = H[i][j] (1 on the diagonal and 0 off it
+     where i or j is active) - L[i][0] L[j][0] - ... - L[i][j-1] L[j][j-1]; the pivot s is replaced by max(|s|, floor)
+     unless s > floor = 1e-8 max(1, largest |H[d][d]| over the free d); L[j][j] = sqrt(s), L[i][j] = s / L[j][j].  Forward
+     substitution from -g (0 where active) for k = 0 .. D - 1: s_k = s_k / L[k][k], then s_i = s_i - L[i][k] s_k for i > k;
+     back substitution for k = D - 1 .. 0: s_k = s_k / L[k][k], then s_i = s_i - L[k][i] s_k for i < k.
+  5. Arc search, every trial point in one pass: lane i < 31 tries P(z + 2^-i d), lane 32 + i tries P(z + 2^-i (-g)).  A
+     lane passes if its point moves z (some |step_d| > 0) and F_trial <= (F + 1e-4 min(slope, 0)) + 1e-13 S with
+     slope = g_0 step_0 + g_1 step_1 + ... in order.  The first passing Newton lane is taken, else the first passing
+     steepest-descent lane, else the solve ends stalled (3).  The trial F is formed by the value operations above alone.
+
+One iteration is one tangent pass and one trial pass.  The returned cost is F of the tangent pass at the returned point; the
+best start of a draw has the smallest finite cost; every draw's trajectory under its own controls (``mean``, ``bounds``,
+``members``, ``first_saturation``) is ``simulate_host``'s under ``expand_controls(res, e)``, bit for bit.  The device follows
+the statement operation for operation: the tangent pass agrees bit for bit, whole solves in status, iterations and 1e-9.
 """
 import numpy as np
 
@@ -365,6 +421,7 @@ def _prepare(models, states, inputs, forcing, y0, t, draws, bounds, ReturnBounds
         norm_src=np.array([norms[n][0] for n in norm_order], dtype=np.int32),
         norm_lo=np.array([norms[n][1] for n in norm_order], dtype=np.float64),
         norm_span=np.array([norms[n][2] - norms[n][1] for n in norm_order], dtype=np.float64),
+        norm_hi=np.array([norms[n][2] for n in norm_order], dtype=np.float64), forcing_cols=list(forcing_cols),
         n_norm_forcing=n_norm_forcing, n_forcing_factors=n_forcing_factors, fac_norm=fac_norm, fac_kind=fac_kind,
         fac_row=fac_row, fac_degree=fac_degree, spline_table=np.ascontiguousarray(spline_table),
         bern_table=np.ascontiguousarray(bern_table),
@@ -822,3 +879,584 @@ def assimilate_host(models, states, inputs, forcing=None, y0=None, t=None, draws
 
 assimilate.__doc__ += _ASSIMILATE_SIGNATURE
 assimilate_host.__doc__ += _ASSIMILATE_SIGNATURE
+
+
+# ---------------------------------------------------------------------------------------------------------
+# control: projected Gauss-Newton on a least-squares cost, per posterior draw (module docstring)
+# ---------------------------------------------------------------------------------------------------------
+
+from .optimize import (start_points, CONVERGED, ITERATION_LIMIT, NON_FINITE, STALLED, STATUS_TEXT,   # noqa: E402,F401
+                       ARMIJO, NOISE, PIVOT_FLOOR, MAX_SOLVES)
+
+CONTROL_MAX_DECISIONS = 32                # D = controls x segments: one direction lane each, the Newton trials fill lanes 0 .. 30
+CONTROL_MAX_STEPS = 4096                  # two passes over the horizon are one launch
+CONTROL_TRIALS = 31                       # alpha = 1, 1/2, ..., 2**-30 in lanes i (Newton) and 32 + i (steepest descent)
+_TRIAL_ALPHA = np.ldexp(1.0, -np.arange(CONTROL_TRIALS))
+
+
+def control_lds_bytes(n_factors, n_norm_state, n_coef, D):
+    """LDS bytes of a solve's wavefront: values and tangents of slot 0, the factors and the normalised states as
+    [item][lane], four rows of 64 (exchange, z, g, direction), row d of H (afterwards the trial points) as [D][64], and
+    the draw's coefficients once."""
+    return (2 * (1 + n_factors + n_norm_state) + 4 + D) * LANES * 8 + n_coef * 8
+
+
+def _named(name, given, states, what, default):
+    out = np.full(len(states), float(default))
+    for key, value in dict(given or {}).items():
+        if str(key) not in states:
+            raise ValueError(f"{name}: '{key}' is not a state ({states})")
+        out[states.index(str(key))] = what(key, value)
+    return out
+
+
+def _prepare_control(models, states, inputs, controls, forcing, y0, t, draws, bounds, segments, control_bounds, targets,
+                     weights, terminal, limits, limit_weight, move_weight, previous, init, starts, max_iter, tol, keep):
+    """``_prepare`` with the controls as forcing columns, and what the solver adds; touches no device."""
+    wanted = {keep} if isinstance(keep, str) else set(keep or ())
+    if not wanted <= {'members', 'all'}:
+        raise ValueError("keep must be None, 'members', 'all' or a list of the two")
+    controls = [str(name) for name in (controls if controls is not None else [])]
+    if not controls:
+        raise ValueError("controls must name at least one input column the solver chooses")
+    if len(set(controls)) != len(controls):
+        raise ValueError(f"controls names a column twice: {controls}")
+    forcing = dict(forcing or {})
+    state_names = [str(name) for name in states]
+    for name in controls:
+        if name in state_names:
+            raise ValueError(f"controls: '{name}' is a state")
+        if name in [str(key) for key in forcing]:
+            raise ValueError(f"controls: '{name}' is a forcing key")
+    start, stop, h = (float(v) for v in t)
+    if not (np.isfinite([start, stop, h]).all() and h > 0):
+        raise ValueError("t = (start, stop, h) needs finite numbers and h > 0")
+    n_steps = len(np.arange(start, stop + h, h)) - 1
+    if n_steps < 1:
+        raise ValueError("control needs at least one step: t = (start, stop, h) holds no step at all")
+    if n_steps > CONTROL_MAX_STEPS:
+        raise ValueError(f"control handles at most {CONTROL_MAX_STEPS} steps per call, t holds {n_steps}: shorten the horizon "
+                         f"or recede it")
+    placeholder = np.zeros(n_steps)
+    p = _prepare(models, states, inputs, {**forcing, **{name: placeholder for name in controls}}, y0, t, draws, bounds, False,
+                 None, lds_per_member=False)
+    NS, E, P = p['K'], p['E'], n_steps + 1
+    states = p['states']
+    nc = len(controls)
+    col_control = np.full(len(p['forcing_cols']), -1, dtype=np.int32)
+    for c, name in enumerate(controls):
+        if name not in p['forcing_cols']:
+            raise ValueError(f"controls: no model reads '{name}' (no term of any model has an order on it)")
+        col_control[p['forcing_cols'].index(name)] = c
+
+    # ---- segments ----
+    if np.ndim(segments) == 0:
+        if int(segments) != segments or int(segments) < 1:
+            raise ValueError("segments must be a positive count or an increasing array of first steps that begins with 0")
+        hold = -(-n_steps // int(segments))
+        seg_first = np.arange(0, n_steps, hold)
+        if len(seg_first) != int(segments):
+            raise ValueError(f"segments={int(segments)} holds of ceil({n_steps} / {int(segments)}) = {hold} steps cover the "
+                             f"{n_steps} steps in {len(seg_first)}: ask for at most that many")
+    else:
+        seg_first = np.asarray(segments)
+        if seg_first.ndim != 1 or seg_first.size == 0 or not np.issubdtype(seg_first.dtype, np.integer) or seg_first[0] != 0 \
+                or np.any(np.diff(seg_first) <= 0) or seg_first[-1] >= n_steps:
+            raise ValueError(f"segments as an array must hold increasing first steps, beginning with 0 and below {n_steps}")
+    Kseg = int(len(seg_first))
+    D = nc * Kseg
+    if D > CONTROL_MAX_DECISIONS:
+        raise ValueError(f"{nc} controls x {Kseg} segments = {D} decision values, the solver handles at most "
+                         f"{CONTROL_MAX_DECISIONS}")
+    seg_of = (np.searchsorted(seg_first, np.arange(n_steps), side='right') - 1).astype(np.int32)
+
+    # ---- the control box: inside the training range of every column that reads the control ----
+    norm_control = np.array([col_control[-(src + 1)] for src in p['norm_src'][:p['n_norm_forcing']]], dtype=np.int32)
+    given = {str(key): value for key, value in dict(control_bounds or {}).items()}
+    for name in given:
+        if name not in controls:
+            raise ValueError(f"control_bounds: '{name}' is not a control ({controls})")
+    lo, hi = np.empty(nc), np.empty(nc)
+    for c, name in enumerate(controls):
+        readers = np.flatnonzero(norm_control == c)
+        range_lo, range_hi = np.max(p['norm_lo'][readers]), np.min(p['norm_hi'][readers])
+        if name in given:
+            pair = np.asarray(given[name], dtype=np.float64)
+            if pair.shape != (2,) or not np.isfinite(pair).all():
+                raise ValueError(f"control_bounds['{name}'] must be two finite numbers (lo, hi) in true scale")
+            lo[c], hi[c] = pair
+            if not lo[c] < hi[c]:
+                raise ValueError(f"control_bounds['{name}'] is empty (lower {lo[c]}, upper {hi[c]})")
+            for n in readers:
+                if (lo[c] - p['norm_lo'][n]) / p['norm_span'][n] < -1e-12 or (hi[c] - p['norm_lo'][n]) / p['norm_span'][n] > 1 + 1e-12:
+                    raise ValueError(f"control_bounds['{name}'] reaches outside the training range [{range_lo}, {range_hi}] "
+                                     f"of the columns that read it: the models are not extrapolated")
+        else:
+            lo[c], hi[c] = range_lo, range_hi
+            if not lo[c] < hi[c]:
+                raise ValueError(f"control '{name}': its box is empty, the training ranges of the columns that read it have "
+                                 f"no interval in common")
+    width = hi - lo
+
+    # ---- the cost ----
+    def number(name):
+        def check(key, value):
+            if np.ndim(value) != 0 or not np.isfinite(value) or float(value) < 0:
+                raise ValueError(f"{name}['{key}'] must be a non-negative finite number (negative weights are refused)")
+            return float(value)
+        return check
+    ref = np.full((NS, P), np.nan)
+    for key, value in dict(targets or {}).items():
+        if str(key) not in states:
+            raise ValueError(f"targets: '{key}' is not a state ({states})")
+        value = np.asarray(value, dtype=np.float64)
+        if value.ndim == 0:
+            value = np.full(P, float(value))
+        if value.shape != (P,):
+            raise ValueError(f"targets['{key}'] must be a number or one value per point of t ({P}), got shape {list(value.shape)}")
+        if np.isinf(value).any():
+            raise ValueError(f"targets['{key}'] holds an infinite value (a point that is not tracked is NaN)")
+        ref[states.index(str(key))] = value
+    targeted = ~np.isnan(ref).all(axis=1)
+    w = _named('weights', weights, states, number('weights'), np.nan)
+    w = np.where(np.isnan(w), np.where(targeted, 1.0, 0.0), w)
+    term = _named('terminal', terminal, states, number('terminal'), 0.0)
+    for j in np.flatnonzero(term > 0):
+        if np.isnan(ref[j, P - 1]):
+            raise ValueError(f"terminal['{states[j]}'] needs a target at the last point")
+    lim_lo, lim_hi = np.full(NS, -np.inf), np.full(NS, np.inf)
+    for key, pair in dict(limits or {}).items():
+        if str(key) not in states:
+            raise ValueError(f"limits: '{key}' is not a state ({states})")
+        if np.ndim(pair) != 1 or len(pair) != 2:
+            raise ValueError(f"limits['{key}'] must be (lower, upper); None leaves a side open")
+        low, high = (None if v is None else float(v) for v in pair)
+        if (low is not None and not np.isfinite(low)) or (high is not None and not np.isfinite(high)) or \
+                (low is not None and high is not None and not low <= high):
+            raise ValueError(f"limits['{key}'] must be finite with lower <= upper; None leaves a side open")
+        j = states.index(str(key))
+        lim_lo[j], lim_hi[j] = (-np.inf if low is None else low), (np.inf if high is None else high)
+    if np.ndim(limit_weight) != 0 or not np.isfinite(limit_weight) or limit_weight < 0:
+        raise ValueError("limit_weight must be a non-negative finite number (negative weights are refused)")
+    move = np.zeros(nc)
+    for key, value in dict(move_weight or {}).items():
+        if str(key) not in controls:
+            raise ValueError(f"move_weight: '{key}' is not a control ({controls})")
+        move[controls.index(str(key))] = number('move_weight')(key, value)
+    has_previous = previous is not None
+    prev = np.zeros(nc)
+    if has_previous:
+        prev = np.asarray(previous, dtype=np.float64)
+        if prev.shape != (nc,) or not np.isfinite(prev).all():
+            raise ValueError(f"previous must be [{nc}] finite numbers (one value per control, true scale), got shape "
+                             f"{list(np.shape(previous))}")
+    wt = p['h'] * w
+    hl = p['h'] * float(limit_weight)
+    tracked = np.any((wt[:, np.newaxis] > 0) & ~np.isnan(ref[:, 1:]))
+    limited = hl > 0 and (np.isfinite(lim_lo).any() or np.isfinite(lim_hi).any())
+    penalised = np.any(move > 0) and (Kseg > 1 or has_previous)
+    if not (tracked or np.any(term > 0) or limited or penalised):
+        raise ValueError("the cost has no residual at all: nothing is tracked, limited or penalised")
+
+    # ---- starts ----
+    if np.ndim(starts) != 0 or int(starts) != starts or int(starts) < 1:
+        raise ValueError("starts must be a count >= 1")
+    S = int(starts)
+    if E * S > MAX_SOLVES:
+        raise ValueError(f"{E} draws x {S} starts: one call runs at most {MAX_SOLVES} solves")
+    z0 = np.full((S, nc, Kseg), 0.5)
+    if init is not None:
+        first = np.asarray(init, dtype=np.float64)
+        if first.shape != (nc, Kseg) or not np.isfinite(first).all():
+            raise ValueError(f"init must be [{nc}, {Kseg}] finite numbers (controls x segments, true scale), got shape "
+                             f"{list(np.shape(init))}")
+        z0[0] = (first - lo[:, np.newaxis]) / width[:, np.newaxis]
+    if S > 1:
+        z0[1:] = ((start_points(S - 1, lo, hi) - lo) / width)[:, :, np.newaxis]
+    z0 = np.minimum(np.maximum(z0, 0.0), 1.0).reshape(S, D)
+    if int(max_iter) != max_iter or int(max_iter) < 0:
+        raise ValueError("max_iter must be a non-negative integer")
+    if not (tol >= 0):
+        raise ValueError("tol must be >= 0")
+    n_norm_state = p['norm_src'].shape[0] - p['n_norm_forcing']
+    lds_bytes = control_lds_bytes(p['fac_norm'].shape[0], n_norm_state, p['coef'].shape[0], D)
+    if lds_bytes > LDS_BUDGET:
+        raise ValueError(f"the system needs {lds_bytes} bytes of LDS ((2 x (1 + {p['fac_norm'].shape[0]} factors + {n_norm_state} "
+                         f"normalised states) + 4 + {D} decision values) x {LANES} x 8 + {p['coef'].shape[0]} coefficients x 8), "
+                         f"a wavefront has {LDS_BUDGET}")
+    p.update(controls=controls, n_controls=nc, segments=Kseg, D=D, seg_first=seg_first.astype(np.int32), seg_of=seg_of,
+             col_control=col_control, norm_control=norm_control, ctl_lo=lo, ctl_width=width, ref=np.ascontiguousarray(ref),
+             wt=wt, term=term, lim_lo=lim_lo, lim_hi=lim_hi, hl=hl, move=move, prev=prev, has_previous=bool(has_previous),
+             z0=np.ascontiguousarray(z0), starts=S, max_iter=int(max_iter), tol=float(tol), want_members='members' in wanted,
+             want_all='all' in wanted, lds_bytes=lds_bytes)
+    return p
+
+
+def _clip01(x):
+    x = np.where(x < 0.0, 0.0, x)
+    return np.where(x > 1.0, 1.0, x)
+
+
+def _factor_dual(p, f, v):
+    """Factor f at normalised v [M] -> (value as ``_factor_values`` forms it, d value / d v)."""
+    if p['fac_kind'][f] == SPLINE:
+        pieces = p['spline_table'][p['fac_row'][f]]
+        q = np.ceil(v * 499.0)
+        q = q + (q == 0)
+        q = q - 1
+        s = 499.0 * v - q
+        c = pieces[np.clip(np.where(np.isfinite(q), q, 0.0), 0, PIECES - 1).astype(np.intp)]
+        q2 = c[..., 2] + s * c[..., 3]
+        q1 = c[..., 1] + s * q2
+        d1 = q2 + s * c[..., 3]
+        d0 = q1 + s * d1
+        return c[..., 0] + s * q1, 499.0 * d0
+    c = p['bern_table'][p['fac_row'][f]]
+    degree = int(p['fac_degree'][f])
+    value, slope = np.full(v.shape, float(c[degree])), np.zeros(v.shape)
+    for k in range(degree - 1, -1, -1):
+        slope = slope * v + value
+        value = value * v + float(c[k])
+    return value, slope
+
+
+def _control_pass(p, z, member, tangents=False, record=False):
+    """One pass over the horizon for M solves / trial points: z [D, M], ``member`` [M] the draw of each.  Returns a dict with
+    F and noise [M]; with ``tangents`` also g [D, M] and H [D, D, M] (entry [d, d'] as lane d forms it); with ``record``
+    members [M, n_states, P] and first [M].  The module docstring states every operation."""
+    NS, S, M, D, Kseg = p['K'], p['n_steps'], z.shape[1], p['D'], p['segments']
+    h, nF, nN, nNF, nFF = p['h'], p['fac_norm'].shape[0], p['norm_src'].shape[0], p['n_norm_forcing'], p['n_forcing_factors']
+    cf, y = p['coef'][:, member], p['y0'][:, member].copy()
+    fac, xn = np.ones((1 + nF, M)), np.zeros((nN, M))
+    F, noise = np.zeros(M), np.zeros(M)
+    first = np.full(M, -1, dtype=np.int32)
+    members = np.empty((M, NS, S + 1)) if record else None
+    if record:
+        members[:, :, 0] = y.T
+    if tangents:
+        tfac, txn, ty = np.zeros((1 + nF, D, M)), np.zeros((nN, D, M)), np.zeros((NS, D, M))
+        g, H = np.zeros((D, M)), np.zeros((D, D, M))
+    zero = np.zeros((D, M)) if tangents else None
+
+    def residual(weight, a, b, t, act=None):
+        nonlocal F, noise, g, H
+        r, mag = a - b, np.abs(a) + np.abs(b)
+        if act is not None:
+            r, mag = np.where(act, r, 0.0), np.where(act, mag, 0.0)
+        q = weight * r
+        F = F + q * r
+        noise = noise + weight * (mag * mag)
+        if tangents:
+            if act is not None:
+                t = np.where(act, t, 0.0)
+            g = g + (2.0 * q) * t
+            H = H + ((2.0 * weight) * t)[:, np.newaxis, :] * t[np.newaxis, :, :]
+
+    def factors(begin, end):
+        for f in range(begin, end):
+            n = p['fac_norm'][f]
+            if tangents:
+                fac[f + 1], slope = _factor_dual(p, f, xn[n])
+                tfac[f + 1] = slope * txn[n]
+            elif p['fac_kind'][f] == SPLINE:
+                fac[f + 1] = spline_value(p['spline_table'][p['fac_row'][f]], xn[n])
+            else:
+                fac[f + 1] = bernoulli_value(p['bern_table'][p['fac_row'][f], :p['fac_degree'][f] + 1], xn[n])
+
+    def stage(at, tat):
+        acted = np.zeros(M, dtype=bool)
+        for n in range(nNF, nN):
+            j = p['norm_src'][n]
+            xn[n], clamp = _clamped((at[j] - p['norm_lo'][n]) / p['norm_span'][n])
+            acted |= clamp
+            if tangents:
+                txn[n] = np.where(clamp, 0.0, tat[j] / p['norm_span'][n])
+        factors(nFF, nF)
+        dy = np.empty((NS, M))
+        tdy = np.empty((NS, D, M)) if tangents else None
+        for k in range(NS):
+            delta, phi = np.zeros(M), np.ones(M)
+            tdelta, tphi = zero, zero
+            for a, b, c, w in p['entries'][p['entry_begin'][k]:p['entry_begin'][k] + p['entry_count'][k]]:
+                for slot in (a, b, c):
+                    if tangents:
+                        tphi = tphi * fac[slot] + phi * tfac[slot]
+                    phi = phi * fac[slot]
+                if w >= 0:
+                    delta = delta + cf[w] * phi
+                    phi = np.ones(M)
+                    if tangents:
+                        tdelta = tdelta + cf[w] * tphi
+                        tphi = zero
+            s = (delta + cf[p['constant'][k]]) * h
+            out = ((at[k] >= p['box'][k, 1]) & (s > 0)) | ((at[k] <= p['box'][k, 0]) & (s < 0))
+            dy[k] = np.where(out, 0.0, s)
+            if tangents:
+                tdy[k] = np.where(out, 0.0, tdelta * h)
+            acted |= out
+        return dy, tdy, acted
+
+    with np.errstate(all='ignore'):
+        for s in range(S):
+            k = p['seg_of'][s]
+            acted = np.zeros(M, dtype=bool)
+            for n in range(nNF):
+                col = -(p['norm_src'][n] + 1)
+                c = p['col_control'][col]
+                x = np.full(M, p['forcing'][s, col]) if c < 0 else p['ctl_lo'][c] + z[c * Kseg + k] * p['ctl_width'][c]
+                xn[n], clamp = _clamped((x - p['norm_lo'][n]) / p['norm_span'][n])
+                acted |= clamp
+                if tangents:
+                    txn[n] = 0.0
+                    if c >= 0:
+                        txn[n, c * Kseg + k] = np.where(clamp, 0.0, p['ctl_width'][c] / p['norm_span'][n])
+            factors(0, nFF)
+            dy = tdy = total = ttotal = None
+            for st in range(4):
+                reach, weight = (1.0 if st == 3 else 0.5), (2.0 if st in (1, 2) else 1.0)
+                at = y if st == 0 else y + dy * reach
+                tat = None if not tangents else ty if st == 0 else ty + tdy * reach
+                dy, tdy, stage_acted = stage(at, tat)
+                total = dy if st == 0 else total + weight * dy
+                if tangents:
+                    ttotal = tdy if st == 0 else ttotal + weight * tdy
+                acted |= stage_acted
+            y = y + total / 6
+            if tangents:
+                ty = ty + ttotal / 6
+            if record:
+                members[:, :, s + 1] = y.T
+                first = np.where((first < 0) & acted, np.int32(s), first).astype(np.int32)
+            point = s + 1
+            for j in range(NS):
+                t = ty[j] if tangents else None
+                target = p['ref'][j, point]
+                if p['wt'][j] > 0 and not np.isnan(target):
+                    residual(p['wt'][j], y[j], target, t)
+                if point == S and p['term'][j] > 0:
+                    residual(p['term'][j], y[j], target, t)
+                if p['hl'] > 0 and p['lim_hi'][j] < np.inf:
+                    residual(p['hl'], y[j], p['lim_hi'][j], t, y[j] > p['lim_hi'][j])
+                if p['hl'] > 0 and p['lim_lo'][j] > -np.inf:
+                    residual(p['hl'], p['lim_lo'][j], y[j], -t if tangents else None, y[j] < p['lim_lo'][j])
+        for c in range(p['n_controls']):
+            if not p['move'][c] > 0:
+                continue
+            for k in range(Kseg):
+                if k == 0 and not p['has_previous']:
+                    continue
+                d = c * Kseg + k
+                t = None
+                if tangents:
+                    t = np.zeros((D, M))
+                    t[d] = p['ctl_width'][c]
+                    if k > 0:
+                        t[d - 1] = -p['ctl_width'][c]
+                now = p['ctl_lo'][c] + z[d] * p['ctl_width'][c]
+                before = np.full(M, p['prev'][c]) if k == 0 else p['ctl_lo'][c] + z[d - 1] * p['ctl_width'][c]
+                residual(p['move'][c], now, before, t)
+    out = dict(F=F, noise=noise)
+    if tangents:
+        out.update(g=g, H=H)
+    if record:
+        out.update(members=members, first=first)
+    return out
+
+
+def _control_direction(H, g, active):
+    """Step 4: the modified-Cholesky direction of every solve, lane = row.  H [D, D, B] (its lower triangle is read)."""
+    D, B = g.shape
+    with np.errstate(all='ignore'):
+        free = np.zeros(B)
+        for j in range(D):
+            free = np.where(active[j], free, np.fmax(free, np.abs(H[j, j])))
+        floor = PIVOT_FLOOR * np.fmax(1.0, free)
+        L = np.zeros((D, D, B))
+        for j in range(D):
+            for i in range(j, D):
+                s = np.where(active[i] | active[j], 1.0 if i == j else 0.0, H[i, j])
+                for k in range(j):
+                    s = s - L[i, k] * L[j, k]
+                if i == j:
+                    s = np.where(s > floor, s, np.fmax(np.abs(s), floor))
+                    L[j, j] = np.sqrt(s)
+                else:
+                    L[i, j] = s / L[j, j]
+        s = np.where(active, 0.0, -g)
+        for k in range(D):                                            # forward: row k is final once rows 0 .. k - 1 are taken off
+            s[k] = s[k] / L[k, k]
+            for i in range(k + 1, D):
+                s[i] = s[i] - L[i, k] * s[k]
+        for k in range(D - 1, -1, -1):                                # back: row k is final once rows D - 1 .. k + 1 are taken off
+            s[k] = s[k] / L[k, k]
+            for i in range(k):
+                s[i] = s[i] - L[k, i] * s[k]
+    return s
+
+
+def _control_solve_host(p):
+    """Every (draw, start) solve -> dict(z [E, S, D], cost, cost_start, status, iterations [E, S] and, with max_iter == 0,
+    the first tangent pass F [E, S], g [E, S, D], H [E, S, D, D])."""
+    E, S, D, max_iter, tol = p['E'], p['starts'], p['D'], p['max_iter'], p['tol']
+    B = E * S
+    member = np.repeat(np.arange(E), S)
+    z = np.ascontiguousarray(np.tile(p['z0'], (E, 1)).T)              # [D, B], solve b = e S + s
+    status = np.full(B, -1, dtype=np.int32)
+    iterations, descent = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    cost, cost_start = np.full(B, np.nan), np.full(B, np.nan)
+    first_pass = None
+    lanes = np.arange(CONTROL_TRIALS)
+    for it in range(max_iter + 1):
+        idx = np.flatnonzero(status < 0)
+        if idx.size == 0:
+            break
+        zi = z[:, idx]
+        out = _control_pass(p, zi, member[idx], tangents=True)
+        F, g, H, noise = out['F'], out['g'], out['H'], out['noise']
+        if it == 0:
+            cost_start[idx] = F
+            first_pass = dict(F=F.reshape(E, S), g=g.T.reshape(E, S, D), H=H.transpose(2, 0, 1).reshape(E, S, D, D))
+        cost[idx] = F
+        with np.errstate(all='ignore'):
+            finite = np.isfinite(F) & np.isfinite(g).all(axis=0)
+            pg = np.zeros(idx.size)
+            for d in range(D):
+                pg = np.fmax(pg, np.abs(_clip01(zi[d] - g[d]) - zi[d]))
+        code = np.where(~finite, NON_FINITE, np.where(pg <= tol, CONVERGED, ITERATION_LIMIT if it == max_iter else -1))
+        stopped = code >= 0
+        status[idx[stopped]], iterations[idx[stopped]] = code[stopped], it
+        go = np.flatnonzero(~stopped)
+        if go.size == 0:
+            continue
+        idx, zi, F, g, H, noise = idx[go], zi[:, go], F[go], g[:, go], H[:, :, go], noise[go]
+        with np.errstate(all='ignore'):
+            active = ((zi <= 0.0) & (g > 0)) | ((zi >= 1.0) & (g < 0))
+            direction = _control_direction(H, g, active)
+            # lane i: P(z + 2^-i d); lane 31 + i here (32 + i of the wavefront): P(z + 2^-i (-g))
+            both = np.stack([direction, -g], axis=1)                                              # [D, 2, n]
+            trial = _clip01(zi[:, np.newaxis, np.newaxis, :] + _TRIAL_ALPHA[np.newaxis, np.newaxis, :, np.newaxis] *
+                            both[:, :, np.newaxis, :])                                            # [D, 2, 31, n]
+            n = idx.size
+            flat = np.ascontiguousarray(trial.reshape(D, 2 * CONTROL_TRIALS * n))
+            Ft = _control_pass(p, flat, np.tile(member[idx], 2 * CONTROL_TRIALS))['F'].reshape(2, CONTROL_TRIALS, n)
+            step = trial - zi[:, np.newaxis, np.newaxis, :]
+            slope, moved = np.zeros((2, CONTROL_TRIALS, n)), np.zeros((2, CONTROL_TRIALS, n), dtype=bool)
+            for d in range(D):
+                slope = slope + g[d] * step[d]
+                moved |= np.abs(step[d]) > 0
+            ok = moved & (Ft <= (F + ARMIJO * np.where(slope < 0, slope, 0.0)) + NOISE * noise)
+        ok = ok.reshape(2 * CONTROL_TRIALS, n)
+        any_ok = ok.any(axis=0)
+        chosen = np.argmax(ok, axis=0)                                # the first Newton lane, else the first steepest-descent lane
+        taken = trial.reshape(D, 2 * CONTROL_TRIALS, n)[:, chosen, np.arange(n)]
+        z[:, idx[any_ok]] = taken[:, any_ok]
+        descent[idx[any_ok & (chosen >= CONTROL_TRIALS)]] += 1
+        status[idx[~any_ok]], iterations[idx[~any_ok]] = STALLED, it
+    res = dict(z=z.T.reshape(E, S, D).copy(), cost=cost.reshape(E, S), cost_start=cost_start.reshape(E, S),
+               status=status.reshape(E, S), iterations=iterations.reshape(E, S), descent_steps=descent.reshape(E, S))
+    if max_iter == 0:
+        res['first_pass'] = first_pass
+    return res
+
+
+def _best_start(cost, status):
+    key = np.where(np.isfinite(cost) & (status != NON_FINITE), cost, np.inf)
+    return np.argmin(key, axis=1)
+
+
+def _run_control_host(p):
+    solved = _control_solve_host(p)
+    best = _best_start(solved['cost'], solved['status'])
+    zb = np.ascontiguousarray(solved['z'][np.arange(p['E']), best].T)
+    out = _control_pass(p, zb, np.arange(p['E']), record=True)
+    return solved, best.astype(np.int32), out['members'], out['first']
+
+
+def _assemble_control(p, solved, best, members, first):
+    E, nc, Kseg = p['E'], p['n_controls'], p['segments']
+    rows = np.arange(E)
+    true_scale = lambda zz: p['ctl_lo'][:, np.newaxis] + zz.reshape(zz.shape[:-1] + (nc, Kseg)) * p['ctl_width'][:, np.newaxis]
+    z = solved['z'][rows, best]
+    u = true_scale(z)
+    res = SimulateResult(u=u, z=z.reshape(E, nc, Kseg), cost=solved['cost'][rows, best], status=solved['status'][rows, best],
+                         iterations=solved['iterations'][rows, best], descent_steps=solved['descent_steps'][rows, best], cost_start=solved['cost_start'][rows, best],
+                         best_start=best.astype(np.int64), u_mean=u.mean(axis=0), t=p['T'], mean=np.mean(members, axis=0),
+                         first_saturation=first, controls=list(p['controls']), states=list(p['states']),
+                         segment_first=p['seg_first'].astype(np.int64))
+    if E >= 2:
+        cut = bounds_cut(E)
+        us, ms = np.sort(u, axis=0), np.sort(members, axis=0)
+        res['u_bounds'] = np.stack([us[cut], us[E - cut]], axis=-1)
+        res['bounds'] = np.stack([ms[cut], ms[E - cut]], axis=-1)
+    if p['want_members']:
+        res['members'] = members
+    if p['want_all']:
+        res.update(u_all=true_scale(solved['z']), cost_all=solved['cost'], status_all=solved['status'],
+                   iterations_all=solved['iterations'], descent_steps_all=solved['descent_steps'])
+    if 'first_pass' in solved:
+        res['first_pass'] = solved['first_pass']
+    return res
+
+
+def expand_controls(res, e=None):
+    """The controls of a result as ``forcing`` arrays [steps]: draw e's own (``res.u[e]``), or ``u_mean`` if e is None."""
+    u = res['u_mean'] if e is None else res['u'][e]
+    n_steps = len(res['t']) - 1
+    seg_of = np.searchsorted(res['segment_first'], np.arange(n_steps), side='right') - 1
+    return {name: u[c][seg_of] for c, name in enumerate(res['controls'])}
+
+
+_CONTROL_SIGNATURE = """
+    models, states, inputs, forcing, y0, t, draws, bounds : as for ``simulate``; ``y0`` [E, n_states] and ``draws=`` take
+                  ``assimilate``'s ``draw_mean[:, :, -1]`` and ``draw_index``
+    controls    : names of input columns that are neither states nor keys of ``forcing``: the solver chooses their values
+    segments    : K, for K holds of ceil(steps / K) steps (the last may be shorter), or an increasing array of first steps
+                  that begins with 0
+    control_bounds : {control: (lo, hi)} in true scale; default and outer limit: the intersection of the training ranges of
+                  the columns that read the control
+    targets     : {state: a number or [points]}; NaN: that point is not tracked.  weights {state: w >= 0} (default 1 for a
+                  targeted state), terminal {state: w >= 0} on the last point
+    limits      : {state: (lower, upper)}, None leaves a side open; soft, weighted by ``limit_weight``
+    move_weight : {control: w >= 0} on u_k - u_(k-1); ``previous`` [n_controls] is u before step 0 (without it the first
+                  move is free)
+    init        : [n_controls, K] start 0 in true scale (default: the box centre); ``starts`` - 1 further starts hold every
+                  control constant at the points of ``optimize.start_points``.  Nothing is drawn at random
+    max_iter, tol : iteration limit of a solve; projected-gradient tolerance in z.  max_iter=0 evaluates the first tangent
+                  pass only and returns it as ``first_pass`` (F [E, S], g [E, S, D], H [E, S, D, D], lower triangle)
+    keep        : 'members' also returns every draw's trajectory under its own controls, 'all' every start's solve; a list
+                  of both is accepted
+
+    Returns a ``SimulateResult``: u [E, n_controls, K] (true scale, = lo + z (hi - lo)), z, cost, status, iterations,
+    cost_start, best_start, descent_steps (iterations whose accepted trial was a steepest-descent lane) [E] of each
+    draw's best start (status: ``optimize.STATUS_TEXT``); u_mean [n_controls, K] and, for
+    E >= 2, u_bounds [n_controls, K, 2] and bounds [n_states, P, 2] (``evaluate``'s order statistics over the draws); t,
+    mean [n_states, P] and first_saturation [E] of the trajectories under each draw's OWN controls; members [E, n_states,
+    P] with keep='members'; u_all, cost_all, status_all, iterations_all [E, S, ...] with keep='all'.
+    ``expand_controls(res, e)`` gives the controls as ``forcing`` arrays for ``simulate``."""
+
+
+def control(models, states, inputs, controls=None, forcing=None, y0=None, t=None, draws=None, bounds=None, segments=8,
+            control_bounds=None, targets=None, weights=None, terminal=None, limits=None, limit_weight=1e3, move_weight=None,
+            previous=None, init=None, starts=1, max_iter=60, tol=1e-10, keep=None, device=None):
+    """Which inputs make the states of a fitted system do what is wanted?  One bounded least-squares solve per posterior
+    draw and start, every solve a wavefront on the device (module docstring).
+
+    device      : device index (default: the process's device, as for ``fit``), a backend or a ``_capi.DeviceContext``"""
+    p = _prepare_control(models, states, inputs, controls, forcing, y0, t, draws, bounds, segments, control_bounds, targets,
+                         weights, terminal, limits, limit_weight, move_weight, previous, init, starts, max_iter, tol, keep)
+    ctx = _device_context(device)
+    return _assemble_control(p, *ctx.control_solve(p))
+
+
+def control_host(models, states, inputs, controls=None, forcing=None, y0=None, t=None, draws=None, bounds=None, segments=8,
+                 control_bounds=None, targets=None, weights=None, terminal=None, limits=None, limit_weight=1e3,
+                 move_weight=None, previous=None, init=None, starts=1, max_iter=60, tol=1e-10, keep=None):
+    """``control`` in numpy on this host, vectorised over solves and trial points: the statement the kernel is tested
+    against (module docstring), not a fallback.  Same arguments, same result fields."""
+    p = _prepare_control(models, states, inputs, controls, forcing, y0, t, draws, bounds, segments, control_bounds, targets,
+                         weights, terminal, limits, limit_weight, move_weight, previous, init, starts, max_iter, tol, keep)
+    return _assemble_control(p, *_run_control_host(p))
+
+
+control.__doc__ += _CONTROL_SIGNATURE
+control_host.__doc__ += _CONTROL_SIGNATURE

@@ -35,6 +35,7 @@
  *                              counter-based random numbers as the host sees them
  *   fokl_simulate_ensemble / fokl_simulate_report
  *   fokl_assimilate_ensemble / fokl_assimilate_report / fokl_assimilate_rng
+ *   fokl_control_solve / fokl_control_report
  *                              a system of fitted models, wired by names, integrated for every posterior draw at once
  *                              (fokl_gpy_amd/dynamics.py), and what its last call ran
  *   fokl_embedded_hmc / fokl_embedded_rng
@@ -1169,6 +1170,66 @@ int fokl_assimilate_report(const fokl_ctx *ctx, int64_t *out);
  */
 int fokl_assimilate_rng(uint32_t seed, const uint32_t *draw_ids, int n_draws, uint32_t step, int purpose, int count,
                         double *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Optimal control of such a system, per posterior draw (csrc/fokl_control_device.inc; dynamics.py)          */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_CONTROL_REPORT_LEN 8
+#define FOKL_CONTROL_MAX_DECISIONS 32
+#define FOKL_CONTROL_MAX_STEPS 4096
+
+/*
+ * One bounded least-squares solve per (posterior draw, start): projected Gauss-Newton on the cost of dynamics.control, the
+ * Jacobian from forward sensitivities of fokl_simulate_ensemble's Runge-Kutta step as executed.  The plan of the system is
+ * dynamics._prepare's with the controls as forcing columns (the arguments up to `box` mean what they mean for
+ * fokl_assimilate_ensemble), the arithmetic is stated by dynamics.control_host (the module docstring of
+ * fokl_gpy_amd/dynamics.py).  Host memory, row-major:
+ *   seg_first [n_segments] int32: the first step of every hold (0 first, increasing, below n_steps)
+ *   norm_control [n_norm_forcing] int32: the control a forcing input reads, -1: a column of `forcing`
+ *   ctl_lo / ctl_width [n_controls]: u = lo + z width, z in [0, 1]; decision value d = control x n_segments + segment
+ *   ref [n_states, n_steps + 1] targets, NaN: not tracked; track_weight [n_states] = h w_j, terminal_weight [n_states],
+ *          limit_lo / limit_hi [n_states] (-inf / +inf: open), limit_weight = h x the soft limits' weight
+ *   move_weight / previous [n_controls]; the move of segment 0 counts only with has_previous
+ *   z0 [n_starts, D] in [0, 1]; max_iter (0: the first tangent pass only), tol on the projected gradient in z
+ *   z [n_draws, n_starts, D], cost / cost_start [n_draws, n_starts], status (0 converged, 1 iteration limit, 2 non-finite,
+ *          3 stalled) / iterations / descent_steps (iterations whose accepted trial was a steepest-descent lane)
+ *          [n_draws, n_starts] int32; best_start [n_draws] int32
+ *   members [n_draws, n_states, n_steps + 1]: every draw's trajectory under its best start's controls, first_saturation
+ *          [n_draws] int32 of that trajectory
+ *   first_F [n_draws, n_starts], first_g [.., D], first_H [.., D, D] (entry [d][d'] as lane d forms it): the tangent pass
+ *          of iteration 0; all three or none NULL
+ * One wavefront per workgroup and solve, one launch per iteration of every solve (a finished solve returns at once); the
+ * statuses are read back every FOKL_CONTROL_POLL launches (environment, default 8; 0: never) to stop queuing early, which
+ * changes no result.  LDS bytes = (2 (1 + n_factors + n_norm - n_norm_forcing) + 4 + D) x 64 x 8 + n_coef x 8, at most 144 KB.
+ * No atomics: the same arguments give the same bits.
+ * Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched): what fokl_simulate_ensemble refuses of a
+ * system (its LDS bound excepted), D above 32, no step or more than 4 096, a control no input reads, an empty or non-finite
+ * control box or one outside the training range, negative weights, no residual at all, n_starts < 1, n_draws x n_starts
+ * above 1 048 576, a start outside [0, 1], the LDS bytes above.  Kernel time: FOKL_K_INTEGRATE.  Blocking.
+ */
+int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
+                       const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src, const double *norm_lo,
+                       const double *norm_span, int n_forcing_factors, int n_factors, const int32_t *fac_norm,
+                       const int32_t *fac_kind, const int32_t *fac_row, const int32_t *fac_degree, int n_spline_rows,
+                       const double *spline_table, int n_bern_rows, const double *bern_table, int n_entries,
+                       const int32_t *entries, const int32_t *entry_begin, const int32_t *entry_count, const int32_t *constant,
+                       int n_coef, const double *coef, const double *y0, const double *box, int n_controls, int n_segments,
+                       const int32_t *seg_first, const int32_t *norm_control, const double *ctl_lo, const double *ctl_width,
+                       const double *ref, const double *track_weight, const double *terminal_weight, const double *limit_lo,
+                       const double *limit_hi, double limit_weight, const double *move_weight, const double *previous,
+                       int has_previous, int n_starts, const double *z0, int max_iter, double tol, double *z, double *cost,
+                       double *cost_start, int32_t *status, int32_t *iterations, int32_t *descent_steps, int32_t *best_start,
+                       double *members, int32_t *first_saturation, double *first_F, double *first_g, double *first_H);
+
+/*
+ * The last fokl_control_solve call on `ctx`, out [FOKL_CONTROL_REPORT_LEN] (host values, no launch); zeros after a call
+ * that was refused or failed:
+ *   out[0]  NS: the kernel instance (states)     out[1]  solves = workgroups = wavefronts     out[2]  D
+ *   out[3]  dynamic LDS bytes     out[4]  launches queued     out[5]  launches that found a running solve
+ *   out[6]  spline factors     out[7]  Bernoulli factors
+ */
+int fokl_control_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* What the fit kernels ran: K1 basis build, K2 Gram block, K3 residual moments (csrc/fokl_hip.hip)          */
