@@ -40,6 +40,8 @@ RESAMPLE_SEGMENTS = 3                     # per-chain sums: first half, second h
 RES_BETA, RES_SIG_NORMAL, RES_SIG_UNIFORM, RES_TAU_NORMAL, RES_TAU_UNIFORM, RES_START = 3, 4, 5, 6, 7, 8
 DESIGN_INSTANCES = ('none', 'variance', 'ivr')                # fokl_design_report: the instance of the design kernels that ran
 DESIGN_MAX_COLUMNS = 768                  # fokl_design_select: a 16-row tile of basis values in LDS is 96 KiB
+OPTIMIZE_INSTANCES = ('none', 'uniform', 'per_lane')          # fokl_optimize_report / fokl_system_optimize_report
+OPTIMIZE_TRIALS = 31                                          # trial points of one arc search (optimize.MAX_HALVINGS + 1)
 INFER_MAPPINGS = ('none', 'walker_per_lane')                  # fokl_infer_report: the lane mapping that ran
 INFER_WALKERS = 64                        # fokl_infer_inputs: one ensemble is one wavefront
 INFER_TERM_CAP = 1 << 33                  # ... and the term evaluations by a wavefront asked of one launch
@@ -225,6 +227,13 @@ SIGNATURES = {
     'fokl_system_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int,
                                      c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl, c_dbl, c_dbl, c_int, c_vp, c_vp, c_vp,
                                      c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_model_optimize_trace': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp,
+                                          c_dbl, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
+    'fokl_system_optimize_trace': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int,
+                                           c_int, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_dbl, c_dbl, c_dbl, c_int, c_vp, c_vp,
+                                           c_vp, c_int, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
+    'fokl_optimize_report': (c_int, [c_vp, c_vp]),
+    'fokl_system_optimize_report': (c_int, [c_vp, c_vp]),
     'fokl_embedded_hmc': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
                                   ctypes.c_uint32, c_vp, c_dbl, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_embedded_plan': (c_int, [c_int, c_int, c_vp, c_vp]),
@@ -2379,11 +2388,58 @@ class DeviceContext:
                 'bernoulli_factors')
         return dict(zip(keys, (int(v) for v in out)))
 
-    def model_optimize(self, mtx, betas, table, lo, hi, starts, sign, max_iter, tol):
+    @staticmethod
+    def _step_trace(rows, m, K=0, C=0):
+        """The fields of a trace [E, S, stride] (fokl_hip_internal.h: fokl_model_optimize_trace) by name; flags as bool,
+        counts and statuses as int64 (a status that was never written: -9)."""
+        h = m * (m + 1) // 2
+        flag = lambda a: np.nan_to_num(a, nan=0.0) != 0
+        whole = lambda a: np.nan_to_num(a, nan=-9.0).astype(np.int64)
+        out = dict(running=flag(rows[..., 0]), F=rows[..., 1], noise=rows[..., 2], pg=rows[..., 3],
+                   active=(whole(rows[..., 4])[..., None] >> np.arange(m)) & 1 == 1, status_tests=whole(rows[..., 5]),
+                   stepping=flag(rows[..., 6]), use_steepest=flag(rows[..., 7]), trials=whole(rows[..., 8]),
+                   alpha=rows[..., 9], failed=flag(rows[..., 10]), steepest=flag(rows[..., 11]), status=whole(rows[..., 12]))
+        at = 13
+        for name, width in (('x_in', m), ('g', m), ('H', h), ('factor', h), ('d', m), ('Ft', OPTIMIZE_TRIALS), ('x_out', m)):
+            out[name] = rows[..., at:at + width]
+            at += width
+        if K:
+            for name, width in (('ev', K), ('nz', K), ('lam', 2 * C), ('rho', 1), ('inner', 1), ('target', 1), ('viol', 1),
+                                ('measure', 1), ('update', 1), ('good', 1), ('lam_out', 2 * C), ('rho_out', 1),
+                                ('inner_out', 1), ('target_out', 1)):
+                out[name] = rows[..., at:at + width] if name in ('ev', 'nz', 'lam', 'lam_out') else rows[..., at]
+                at += width
+            out['update'], out['good'] = flag(out['update']), flag(out['good'])
+        assert at == rows.shape[-1]
+        return out
+
+    def _optimize_report(self, call):
+        out = np.zeros(9, dtype=np.int64)
+        self._ck(call(self._h, _ptr(out)))
+        keys = ('instance', 'grid', 'lds_bytes', 'lds_raised', 'slots', 'side_list', 'solves', 'launches', 'traced')
+        rep = dict(zip(keys, (int(v) for v in out)))
+        rep['instance'] = OPTIMIZE_INSTANCES[rep['instance']]
+        return rep
+
+    def optimize_report(self):
+        """What the last ``model_optimize`` on this context ran (fokl_optimize_report; host values, no launch):
+        ``instance`` ('uniform': a wavefront belongs to one draw, 'per_lane'), ``grid`` (workgroups = wavefronts),
+        ``lds_bytes``, ``lds_raised`` (1: the attribute that allows more than 64 KB was set), ``slots`` (distinct (input,
+        order) factors), ``side_list`` (entries), ``solves``, ``launches``, ``traced``.  'none' and zeros after a refused
+        call."""
+        return self._optimize_report(self._lib.fokl_optimize_report)
+
+    def system_optimize_report(self):
+        """``optimize_report`` for the last ``system_optimize`` (fokl_system_optimize_report): ``grid`` is the first
+        launch's, ``slots`` the largest model's."""
+        return self._optimize_report(self._lib.fokl_system_optimize_report)
+
+    def model_optimize(self, mtx, betas, table, lo, hi, starts, sign, max_iter, tol, trace_iteration=None):
         """fokl_model_optimize (optimize.optimize assembles the arguments, all in normalised coordinates): mtx int32
         [terms, m], betas [E, terms + 1], table [n_basis, width], lo / hi [m], starts [S, m], sign +1 (minimise) or -1
         -> (x [E, S, m], model value [E, S], iterations [E, S], status [E, S]).  Needs no uploaded dataset and leaves
-        one alone."""
+        one alone.  trace_iteration=k (fokl_model_optimize_trace): a fifth result, the dict of what iteration k of every
+        solve saw and decided ([E, S, ...] each; ``_step_trace`` names the fields)."""
         mtx = np.ascontiguousarray(mtx, dtype=np.int32)
         betas, table, starts = (np.ascontiguousarray(a, dtype=np.float64) for a in (betas, table, starts))
         lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
@@ -2396,17 +2452,22 @@ class DeviceContext:
         f = np.empty((E, S), dtype=np.float64)
         iterations = np.empty((E, S), dtype=np.int32)
         status = np.empty((E, S), dtype=np.int32)
-        self._ck(self._lib.fokl_model_optimize(
-            self._h, int(m), int(n_terms), _ptr(mtx), int(E), _ptr(betas), _ptr(table), int(table.shape[0]),
-            int(table.shape[1]), _ptr(lo), _ptr(hi), int(S), _ptr(starts), float(sign), int(max_iter), float(tol), _ptr(x),
-            _ptr(f), _ptr(iterations), _ptr(status)))
-        return x, f, iterations, status
+        args = (self._h, int(m), int(n_terms), _ptr(mtx), int(E), _ptr(betas), _ptr(table), int(table.shape[0]),
+                int(table.shape[1]), _ptr(lo), _ptr(hi), int(S), _ptr(starts), float(sign), int(max_iter), float(tol), _ptr(x),
+                _ptr(f), _ptr(iterations), _ptr(status))
+        if trace_iteration is None:
+            self._ck(self._lib.fokl_model_optimize(*args))
+            return x, f, iterations, status
+        rows = np.empty((E, S, 13 + 4 * m + m * (m + 1) + OPTIMIZE_TRIALS), dtype=np.float64)
+        self._ck(self._lib.fokl_model_optimize_trace(*args, int(trace_iteration), _ptr(rows)))
+        return x, f, iterations, status, self._step_trace(rows, m)
 
-    def system_optimize(self, p):
+    def system_optimize(self, p, trace_iteration=None):
         """fokl_system_optimize for a system prepared by ``optimize._prepare_system`` (common normalised coordinates)
         -> (x [E, S, n], objective [E, S], violation [E, S], model values [E, S, K], multipliers [E, S, C], iterations
         [E, S], status [E, S]): what ``optimize.solve_system_host`` returns.  Needs no uploaded dataset and leaves one
-        alone."""
+        alone.  trace_iteration=k (fokl_system_optimize_trace): one more result, the dict of what iteration k of every
+        solve saw and decided (``_step_trace``)."""
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
         n, K, cons = int(p['n']), int(p['K']), p['cons']
@@ -2429,13 +2490,17 @@ class DeviceContext:
         f, violation = np.empty((E, S), dtype=np.float64), np.empty((E, S), dtype=np.float64)
         y, mu = np.empty((E, S, K), dtype=np.float64), np.empty((E, S, C), dtype=np.float64)
         iterations, status = np.empty((E, S), dtype=np.int32), np.empty((E, S), dtype=np.int32)
-        self._ck(self._lib.fokl_system_optimize(
-            self._h, n, K, _ptr(n_inputs), _ptr(n_terms), _ptr(mtx), _ptr(var_of), _ptr(shift), _ptr(slope), int(E),
-            _ptr(betas), _ptr(table), int(table.shape[0]), int(table.shape[1]), _ptr(lo), _ptr(hi), int(S), _ptr(starts),
-            int(p['obj_model']), obj_var, offset, span, float(p['sign']), C, _ptr(con_model), _ptr(con_var), _ptr(con_par),
-            int(p['max_iter']), float(p['tol']), float(p['ctol']), _ptr(x), _ptr(f), _ptr(violation), _ptr(y), _ptr(mu),
-            _ptr(iterations), _ptr(status)))
-        return x, f, violation, y, mu, iterations, status
+        args = (self._h, n, K, _ptr(n_inputs), _ptr(n_terms), _ptr(mtx), _ptr(var_of), _ptr(shift), _ptr(slope), int(E),
+                _ptr(betas), _ptr(table), int(table.shape[0]), int(table.shape[1]), _ptr(lo), _ptr(hi), int(S), _ptr(starts),
+                int(p['obj_model']), obj_var, offset, span, float(p['sign']), C, _ptr(con_model), _ptr(con_var), _ptr(con_par),
+                int(p['max_iter']), float(p['tol']), float(p['ctol']), _ptr(x), _ptr(f), _ptr(violation), _ptr(y), _ptr(mu),
+                _ptr(iterations), _ptr(status))
+        if trace_iteration is None:
+            self._ck(self._lib.fokl_system_optimize(*args))
+            return x, f, violation, y, mu, iterations, status
+        rows = np.empty((E, S, 13 + 4 * n + n * (n + 1) + OPTIMIZE_TRIALS + 2 * K + 4 * C + 10), dtype=np.float64)
+        self._ck(self._lib.fokl_system_optimize_trace(*args, int(trace_iteration), _ptr(rows)))
+        return x, f, violation, y, mu, iterations, status, self._step_trace(rows, n, K, C)
 
     def embedded_hmc(self, n_gps, term_slots, col_slots, ops, consts, result, chains, draws, leapfrog, seed, q0=None,
                      eps0=0.0, adapt=True, want_grad0=False, want_proposal=False):

@@ -119,6 +119,11 @@ struct fokl_ctx {
     int rank = 0, world = 1;
     double *d_comm = nullptr;
     size_t comm_doubles = 0;
+
+    // what the last fokl_model_optimize(_trace) / fokl_system_optimize(_trace) call ran (fokl_optimize_report,
+    // fokl_system_optimize_report); behind everything a fit touches
+    int64_t optimize_report[FOKL_OPTIMIZE_REPORT_LEN] = {};
+    int64_t system_optimize_report[FOKL_OPTIMIZE_REPORT_LEN] = {};
 };
 
 static int fail(fokl_ctx *ctx, int code, const std::string &msg)

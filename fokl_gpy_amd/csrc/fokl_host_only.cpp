@@ -93,6 +93,14 @@ extern "C" int fokl_model_optimize(fokl_ctx *, int, int, const int32_t *, int, c
     return FOKL_ERR_HIP;
 }
 
+extern "C" int fokl_model_optimize_trace(fokl_ctx *, int, int, const int32_t *, int, const double *, const double *, int, int,
+                                         const double *, const double *, int, const double *, double, int, double, double *,
+                                         double *, int32_t *, int32_t *, int, double *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_optimize_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // Neither does the constrained optimiser over a system of models (fokl_optimize_system_device.inc;
 // optimize.solve_system_host).
 extern "C" int fokl_system_optimize(fokl_ctx *, int, int, const int32_t *, const int32_t *, const int32_t *, const int32_t *,
@@ -103,6 +111,16 @@ extern "C" int fokl_system_optimize(fokl_ctx *, int, int, const int32_t *, const
 {
     return FOKL_ERR_HIP;
 }
+extern "C" int fokl_system_optimize_trace(fokl_ctx *, int, int, const int32_t *, const int32_t *, const int32_t *,
+                                          const int32_t *, const double *, const double *, int, const double *, const double *,
+                                          int, int, const double *, const double *, int, const double *, int, int, double,
+                                          double, double, int, const int32_t *, const int32_t *, const double *, int, double,
+                                          double, double *, double *, double *, double *, double *, int32_t *, int32_t *, int,
+                                          double *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_system_optimize_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
 // The embedded-GP sampler's chains run on the device only (fokl_embedded_device.inc); its statement is
 // embedded.full_sample_host, and its random numbers (fokl_embedded_rng) are host code and present here.

@@ -30,6 +30,70 @@ constexpr int64_t OP_MAX_SOLVES = (int64_t)1 << 20;
 constexpr double OP_ARMIJO = 1e-4, OP_NOISE = 1e-13, OP_PIVOT_FLOOR = 1e-8;
 constexpr int OP_CONVERGED = 0, OP_ITERATION_LIMIT = 1, OP_NON_FINITE = 2, OP_STALLED = 3;
 
+// The trace of ONE iteration of every solve (fokl_model_optimize_trace, fokl_system_optimize_trace): a row of doubles per
+// solve, written by the product kernels' TRACE instantiations.  Flags and counts are stored as doubles too (exact).
+//   head    running (1: the solve was running when iteration k began; 0: it had stopped before, or its wavefront had),
+//           F, noise, pg, active (the mask as a number), status after the tests of iteration k (-1: still running),
+//           stepping, use_steepest, trial points, alpha, failed, steepest for the next iteration, status at the exit
+//   x_in [m], g [m], H [m (m + 1) / 2] before the factorisation, factor [m (m + 1) / 2], d [m] after the select and the
+//   scaling, trial [31] (NaN where the lane evaluated none), x_out [m]; the system kernel appends its own (SysTraceAt).
+// The host fills every row with NaN and running = 0.  x_in and x_out are written for every real lane whose wavefront
+// reaches iteration k, running or not.
+constexpr int OP_TR_RUNNING = 0, OP_TR_F = 1, OP_TR_NOISE = 2, OP_TR_PG = 3, OP_TR_ACTIVE = 4, OP_TR_STATUS_TESTS = 5,
+              OP_TR_STEPPING = 6, OP_TR_USE_STEEPEST = 7, OP_TR_TRIALS = 8, OP_TR_ALPHA = 9, OP_TR_FAILED = 10,
+              OP_TR_STEEPEST_NEXT = 11, OP_TR_STATUS = 12, OP_TR_HEAD = 13;
+
+struct OpTraceAt {                                                    // offsets into a row
+    int flags, x_in, g, H, factor, d, trial, x_out, end;
+    __host__ __device__ static OpTraceAt of(int m)
+    {
+        const int nh = m * (m + 1) / 2;
+        OpTraceAt a;
+        a.flags = 0;
+        a.x_in = OP_TR_HEAD;
+        a.g = a.x_in + m;
+        a.H = a.g + m;
+        a.factor = a.H + nh;
+        a.d = a.factor + nh;
+        a.trial = a.d + m;
+        a.x_out = a.trial + OP_MAX_HALVINGS + 1;
+        a.end = a.x_out + m;
+        return a;
+    }
+};
+
+struct OpTrace {
+    double *row = nullptr;                                            // this lane's row while iteration k runs, else nullptr
+    OpTraceAt at = {};
+};
+
+// What a TRACE kernel writes of iteration k before the step: the entry values and the status after the tests
+__device__ __forceinline__ void op_trace_entry(const OpTrace &tr, int m, bool running, double F, double noise, double pg,
+                                               unsigned active, int status, const double *xs, const double *g,
+                                               const double *H)
+{
+    if (!tr.row) return;
+    for (int j = 0; j < m; ++j) tr.row[tr.at.x_in + j] = tr.row[tr.at.x_out + j] = xs[j * OP_LANES];
+    tr.row[OP_TR_RUNNING] = running;
+    tr.row[OP_TR_STATUS_TESTS] = tr.row[OP_TR_STATUS] = status;
+    if (!running) return;
+    tr.row[OP_TR_F] = F;
+    tr.row[OP_TR_NOISE] = noise;
+    tr.row[OP_TR_PG] = pg;
+    tr.row[OP_TR_ACTIVE] = active;
+    for (int j = 0; j < m; ++j) tr.row[tr.at.g + j] = g[j * OP_LANES];
+    for (int h = 0; h < m * (m + 1) / 2; ++h) tr.row[tr.at.H + h] = H[h * OP_LANES];
+}
+
+// ... and after it: where the solve is now, what it carries to the next iteration, its status
+__device__ __forceinline__ void op_trace_exit(const OpTrace &tr, int m, const double *xs, bool steepest, int status)
+{
+    if (!tr.row) return;
+    for (int j = 0; j < m; ++j) tr.row[tr.at.x_out + j] = xs[j * OP_LANES];
+    tr.row[OP_TR_STEEPEST_NEXT] = steepest;
+    tr.row[OP_TR_STATUS] = status;
+}
+
 // coordinate j of the iterate, or of the trial point P(x + alpha d); box [2][m] (lower bounds, upper bounds)
 template <bool TRIAL>
 __device__ __forceinline__ double op_point(int m, const double *box, const double *xs, const double *dv, double alpha, int j)
@@ -211,12 +275,17 @@ __device__ __forceinline__ void op_newton(int m, unsigned active, double *H, con
 // may overwrite whatever else the caller gives it.  A solve whose search passes moves to that point.  One whose search
 // fails takes steepest descent from the same point next time (`steepest`); when this already was steepest descent the
 // function returns true for it: stalled.  Every lane runs every loop; what a lane that is not stepping computes is dropped.
-template <typename MeritAt>
+// TRACE (the *_trace entry points; compiled away otherwise): a lane whose `tr.row` is set writes what this step decided
+// into its row of the trace -- see OpTrace.
+template <bool TRACE = false, typename MeritAt>
 __device__ __forceinline__ bool op_step(int m, const double *box, unsigned active, bool stepping, double F, double noise,
                                         double *H, const double *g, double *dv, double *xs, bool &steepest,
-                                        MeritAt &&merit_at)
+                                        MeritAt &&merit_at, const OpTrace &tr = OpTrace())
 {
     op_newton(m, active, H, g, dv);
+    if constexpr (TRACE)
+        if (tr.row)
+            for (int h = 0; h < m * (m + 1) / 2; ++h) tr.row[tr.at.factor + h] = H[h * OP_LANES];
     double reach = 0.0;
     bool use_steepest = steepest;
     for (int j = 0; j < m; ++j) {
@@ -234,10 +303,23 @@ __device__ __forceinline__ bool op_step(int m, const double *box, unsigned activ
     }
     if (reach > 1.0)
         for (int j = 0; j < m; ++j) dv[j * OP_LANES] = dv[j * OP_LANES] / reach;
+    int trials = 0;                                                    // trial points this lane evaluated (TRACE only)
+    (void)trials;
+    if constexpr (TRACE)
+        if (tr.row) {
+            for (int j = 0; j < m; ++j) tr.row[tr.at.d + j] = dv[j * OP_LANES];
+            tr.row[tr.at.flags + OP_TR_USE_STEEPEST] = use_steepest;
+            tr.row[tr.at.flags + OP_TR_STEPPING] = stepping;
+        }
     double alpha = 1.0;
     bool searching = stepping;
     for (int h = 0; h <= OP_MAX_HALVINGS && __any(searching); ++h) {
         const double Ft = merit_at(alpha);
+        if constexpr (TRACE)
+            if (tr.row && searching) {
+                tr.row[tr.at.trial + h] = Ft;
+                ++trials;
+            }
         double slope = 0.0, moved = 0.0;
         for (int j = 0; j < m; ++j) {
             const double step = op_point<true>(m, box, xs, dv, alpha, j) - xs[j * OP_LANES];
@@ -252,6 +334,12 @@ __device__ __forceinline__ bool op_step(int m, const double *box, unsigned activ
     if (stepping && !failed)
         for (int j = 0; j < m; ++j) xs[j * OP_LANES] = op_point<true>(m, box, xs, dv, alpha, j);
     steepest = failed && !use_steepest;
+    if constexpr (TRACE)
+        if (tr.row) {
+            tr.row[tr.at.flags + OP_TR_TRIALS] = trials;
+            tr.row[tr.at.flags + OP_TR_ALPHA] = alpha;
+            tr.row[tr.at.flags + OP_TR_FAILED] = failed;
+        }
     return failed && use_steepest;
 }
 
@@ -318,11 +406,13 @@ std::string op_refusal(double sign, bool limits_ok, const char *limits, int n, c
 }
 
 // The instantiation for this number of starts -- UNIFORM when a wavefront belongs to one draw --, allowed its LDS
+// (`raised`: the attribute that lifts the 64 KB default was set)
 template <typename Kernel>
-hipError_t op_pick(Kernel *uniform, Kernel *per_lane, int n_starts, size_t lds_bytes, Kernel **kernel)
+hipError_t op_pick(Kernel *uniform, Kernel *per_lane, int n_starts, size_t lds_bytes, Kernel **kernel, bool *raised)
 {
     *kernel = n_starts % fokl::OP_LANES == 0 ? uniform : per_lane;
-    if (lds_bytes <= 64 * 1024) return hipSuccess;
+    *raised = lds_bytes > 64 * 1024;
+    if (!*raised) return hipSuccess;
     return hipFuncSetAttribute(reinterpret_cast<const void *>(*kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)fokl::OP_LDS_BUDGET);
 }

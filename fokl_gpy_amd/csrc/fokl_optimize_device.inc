@@ -21,8 +21,10 @@ struct OpProblem {
 };
 
 // box [2][m] (lower bounds, upper bounds), starts [n_starts][m], betas [draws][n_coef]; x_out [n_solves][m], the others
-// [n_solves].  Lanes beyond n_solves (the last wavefront) solve nothing and write nothing.
-template <bool UNIFORM>
+// [n_solves].  Lanes beyond n_solves (the last wavefront) solve nothing and write nothing.  TRACE: iteration trace_it of
+// every solve also goes into its row of trace [n_solves][OpTraceAt::of(m).end] (fokl_optimize_core.inc: OpTrace); the
+// product instantiations never read those two arguments.
+template <bool UNIFORM, bool TRACE>
 __global__ __launch_bounds__(OP_LANES) void model_optimize_kernel(OpProblem p, const int *__restrict__ slot_src,
                                                                   const int *__restrict__ slot_ord,
                                                                   const int4 *__restrict__ entries,
@@ -32,7 +34,8 @@ __global__ __launch_bounds__(OP_LANES) void model_optimize_kernel(OpProblem p, c
                                                                   const double *__restrict__ starts,
                                                                   const double *__restrict__ betas,
                                                                   double *__restrict__ x_out, double *__restrict__ f_out,
-                                                                  int *__restrict__ it_out, int *__restrict__ st_out)
+                                                                  int *__restrict__ it_out, int *__restrict__ st_out,
+                                                                  double *__restrict__ trace, int trace_it)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int lane = threadIdx.x;
@@ -54,10 +57,14 @@ __global__ __launch_bounds__(OP_LANES) void model_optimize_kernel(OpProblem p, c
     int status = real ? -1 : OP_CONVERGED, iterations = 0;             // -1: running
     double f_end = NAN;
     bool steepest = false;
+    OpTrace tr;
+    if constexpr (TRACE) tr.at = OpTraceAt::of(m);
     for (int it = 0; __any(status < 0); ++it) {
         double F, noise, pg;
         unsigned active;
         bool finite;
+        const bool running = status < 0;
+        if constexpr (TRACE) tr.row = real && it == trace_it ? trace + (size_t)n * tr.at.end : nullptr;
         op_factors<2, false, false>(p.n_slots, slot_src, slot_ord, nullptr, table, p.width, m, box, xs, dv, 0.0, fac);
         for (int j = 0; j < m; ++j) g[j * OP_LANES] = 0.0;
         for (int h = 0; h < p.n_hess; ++h) H[h * OP_LANES] = 0.0;
@@ -68,18 +75,20 @@ __global__ __launch_bounds__(OP_LANES) void model_optimize_kernel(OpProblem p, c
             iterations = it;
             f_end = F;
         }
+        if constexpr (TRACE) op_trace_entry(tr, m, running, F, noise, pg, active, status, xs, g, H);
         if (!__any(status < 0)) break;
-        const bool stalled = op_step(m, box, active, status < 0, F, noise, H, g, dv, xs, steepest, [&](double alpha) {
+        const bool stalled = op_step<TRACE>(m, box, active, status < 0, F, noise, H, g, dv, xs, steepest, [&](double alpha) {
             double Ft, noise_t;
             op_factors<0, true, false>(p.n_slots, slot_src, slot_ord, nullptr, table, p.width, m, box, xs, dv, alpha, fac);
             op_terms<0>(p.n_entries, slot_src, entries, long_slots, coef, p.sign, p.sign, fac, g, H, Ft, noise_t);
             return Ft;
-        });
+        }, tr);
         if (stalled) {
             status = OP_STALLED;
             iterations = it;
             f_end = F;
         }
+        if constexpr (TRACE) op_trace_exit(tr, m, xs, steepest, status);
     }
     if (real) {
         for (int j = 0; j < m; ++j) x_out[(size_t)n * m + j] = xs[j * OP_LANES];
@@ -91,14 +100,16 @@ __global__ __launch_bounds__(OP_LANES) void model_optimize_kernel(OpProblem p, c
 
 }  // namespace fokl
 
-extern "C" int fokl_model_optimize(fokl_ctx *ctx, int n_inputs, int n_terms, const int32_t *mtx, int n_draws,
-                                   const double *betas, const double *table, int n_basis, int width, const double *lo,
-                                   const double *hi, int n_starts, const double *starts, double sign, int max_iter,
-                                   double tol, double *x, double *f, int32_t *iterations, int32_t *status)
+// fokl_model_optimize and fokl_model_optimize_trace (trace != nullptr: iteration trace_it into trace [N][stride])
+static int model_optimize_run(const std::string &who, fokl_ctx *ctx, int n_inputs, int n_terms, const int32_t *mtx,
+                              int n_draws, const double *betas, const double *table, int n_basis, int width,
+                              const double *lo, const double *hi, int n_starts, const double *starts, double sign,
+                              int max_iter, double tol, double *x, double *f, int32_t *iterations, int32_t *status,
+                              int trace_it, double *trace)
 {
     using namespace fokl;
-    const std::string who = "fokl_model_optimize: ";
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
+    std::memset(ctx->optimize_report, 0, sizeof ctx->optimize_report);
     if (n_inputs <= 0 || n_terms < 0 || n_draws <= 0 || n_starts <= 0 || n_basis <= 0 || width <= 0 ||
         (n_terms > 0 && !mtx) || !betas || !table || !lo || !hi || !starts || !x || !f || !iterations || !status)
         return fail(ctx, FOKL_ERR_ARG, who + "null pointer or empty problem");
@@ -151,16 +162,29 @@ extern "C" int fokl_model_optimize(fokl_ctx *ctx, int n_inputs, int n_terms, con
     HIP_TRY(ctx, buf.get(&d_f, N));
     HIP_TRY(ctx, buf.get(&d_it, N));
     HIP_TRY(ctx, buf.get(&d_st, N));
+    double *d_trace = nullptr;
+    const size_t stride = (size_t)OpTraceAt::of(n_inputs).end;
+    if (trace) {                                                       // NaN everywhere, running = 0
+        std::fill(trace, trace + N * stride, std::nan(""));
+        for (size_t i = 0; i < N; ++i) trace[i * stride + OP_TR_RUNNING] = 0.0;
+        HIP_TRY(ctx, buf.upload(&d_trace, trace, N * stride));
+    }
 
-    decltype(&model_optimize_kernel<true>) kernel = nullptr;
-    HIP_TRY(ctx, op_pick(model_optimize_kernel<true>, model_optimize_kernel<false>, n_starts, lds_bytes, &kernel));
+    decltype(&model_optimize_kernel<true, false>) kernel = nullptr;
+    bool raised = false;
+    if (trace)
+        HIP_TRY(ctx, op_pick(model_optimize_kernel<true, true>, model_optimize_kernel<false, true>, n_starts, lds_bytes,
+                             &kernel, &raised));
+    else
+        HIP_TRY(ctx, op_pick(model_optimize_kernel<true, false>, model_optimize_kernel<false, false>, n_starts, lds_bytes,
+                             &kernel, &raised));
     const int grid = (int)((N + OP_LANES - 1) / OP_LANES);
     {
         // per iterate and solve roughly: 40 flops and 9 + 18 LDS accesses per term, 6 flops per factor and degree
         TimedRegion timed(ctx, FOKL_K_OPTIMIZE, 8.0 * (double)N * (m + 3.0) + 8.0 * (double)n_draws * p.n_coef,
                           (double)N * 40.0 * std::max(1, n_terms));
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(OP_LANES), lds_bytes, ctx->stream, p, d_src, d_ord, d_entries, d_long,
-                           d_table, d_box, d_starts, d_betas, d_x, d_f, d_it, d_st);
+                           d_table, d_box, d_starts, d_betas, d_x, d_f, d_it, d_st, d_trace, trace_it);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -168,5 +192,45 @@ extern "C" int fokl_model_optimize(fokl_ctx *ctx, int n_inputs, int n_terms, con
     HIP_TRY(ctx, hipMemcpy(f, d_f, N * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(iterations, d_it, N * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(status, d_st, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (trace) HIP_TRY(ctx, hipMemcpy(trace, d_trace, N * stride * sizeof(double), hipMemcpyDeviceToHost));
+    int64_t *rep = ctx->optimize_report;
+    rep[0] = n_starts % OP_LANES == 0 ? FOKL_OPTIMIZE_UNIFORM : FOKL_OPTIMIZE_PER_LANE;
+    rep[1] = grid;
+    rep[2] = (int64_t)lds_bytes;
+    rep[3] = raised;
+    rep[4] = p.n_slots;
+    rep[5] = (int64_t)tables.long_slots.size();
+    rep[6] = p.n_solves;
+    rep[7] = 1;
+    rep[8] = trace != nullptr;
+    return FOKL_OK;
+}
+
+extern "C" int fokl_model_optimize(fokl_ctx *ctx, int n_inputs, int n_terms, const int32_t *mtx, int n_draws,
+                                   const double *betas, const double *table, int n_basis, int width, const double *lo,
+                                   const double *hi, int n_starts, const double *starts, double sign, int max_iter,
+                                   double tol, double *x, double *f, int32_t *iterations, int32_t *status)
+{
+    return model_optimize_run("fokl_model_optimize: ", ctx, n_inputs, n_terms, mtx, n_draws, betas, table, n_basis, width, lo,
+                              hi, n_starts, starts, sign, max_iter, tol, x, f, iterations, status, 0, nullptr);
+}
+
+extern "C" int fokl_model_optimize_trace(fokl_ctx *ctx, int n_inputs, int n_terms, const int32_t *mtx, int n_draws,
+                                         const double *betas, const double *table, int n_basis, int width,
+                                         const double *lo, const double *hi, int n_starts, const double *starts,
+                                         double sign, int max_iter, double tol, double *x, double *f,
+                                         int32_t *iterations, int32_t *status, int trace_iteration, double *trace)
+{
+    const std::string who = "fokl_model_optimize_trace: ";
+    if (ctx) std::memset(ctx->optimize_report, 0, sizeof ctx->optimize_report);
+    if (!trace || trace_iteration < 0) return fail(ctx, FOKL_ERR_ARG, who + "null trace or negative iteration");
+    return model_optimize_run(who, ctx, n_inputs, n_terms, mtx, n_draws, betas, table, n_basis, width, lo, hi, n_starts,
+                              starts, sign, max_iter, tol, x, f, iterations, status, trace_iteration, trace);
+}
+
+extern "C" int fokl_optimize_report(const fokl_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return fail(nullptr, FOKL_ERR_ARG, "fokl_optimize_report: null argument");
+    std::memcpy(out, ctx->optimize_report, sizeof ctx->optimize_report);
     return FOKL_OK;
 }

@@ -52,6 +52,28 @@ struct SysCon {
     double psi, slope, curve, viol, measure, new_lo, new_hi;
 };
 
+// What the system kernel appends to a row of the trace (fokl_optimize_core.inc: OpTrace) behind OpTraceAt::of(n).end:
+// ev [K], nz [K] and lam [2 C] at the entry, then rho, inner, target, viol, measure, update, good at the entry, then
+// lam [2 C], rho, inner, target at the exit (after the update, if the iteration was one)
+constexpr int SYS_TR_RHO = 0, SYS_TR_INNER = 1, SYS_TR_TARGET = 2, SYS_TR_VIOL = 3, SYS_TR_MEASURE = 4, SYS_TR_UPDATE = 5,
+              SYS_TR_GOOD = 6, SYS_TR_HEAD = 7;
+
+struct SysTraceAt {
+    int ev, nz, lam_in, head, lam_out, tail, end;
+    __host__ __device__ static SysTraceAt of(int n, int K, int C)
+    {
+        SysTraceAt a;
+        a.ev = OpTraceAt::of(n).end;
+        a.nz = a.ev + K;
+        a.lam_in = a.nz + K;
+        a.head = a.lam_in + 2 * C;
+        a.lam_out = a.head + SYS_TR_HEAD;
+        a.tail = a.lam_out + 2 * C;
+        a.end = a.tail + 3;
+        return a;
+    }
+};
+
 // max(a, b) that keeps a NaN in either (numpy.maximum)
 __device__ __forceinline__ double sys_max(double a, double b) { return a != a ? a : !(b <= a) ? b : a; }
 
@@ -206,15 +228,18 @@ __device__ __forceinline__ void sys_derivatives(const SysProblem &p, const SysDa
 }
 
 // box [2][n], starts [n_starts][n], betas [draws][n_coef]; x_out [solves][n], y_out [solves][K], mu_out [solves][C], the
-// others [solves].  Lanes beyond p.end (the launch's last wavefront) solve nothing and write nothing.
-template <bool UNIFORM>
+// others [solves].  Lanes beyond p.end (the launch's last wavefront) solve nothing and write nothing.  TRACE: iteration
+// trace_it of every solve also goes into its row of trace [solves][SysTraceAt::of(n, K, C).end]; the product
+// instantiations never read those two arguments.
+template <bool UNIFORM, bool TRACE>
 __global__ __launch_bounds__(OP_LANES) void system_optimize_kernel(SysProblem p, SysData s,
                                                                    const double *__restrict__ starts,
                                                                    const double *__restrict__ betas,
                                                                    double *__restrict__ x_out, double *__restrict__ f_out,
                                                                    double *__restrict__ viol_out,
                                                                    double *__restrict__ y_out, double *__restrict__ mu_out,
-                                                                   int *__restrict__ it_out, int *__restrict__ st_out)
+                                                                   int *__restrict__ it_out, int *__restrict__ st_out,
+                                                                   double *__restrict__ trace, int trace_it)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int lane = threadIdx.x;
@@ -242,8 +267,17 @@ __global__ __launch_bounds__(OP_LANES) void system_optimize_kernel(SysProblem p,
     bool steepest = false;
     double rho = SYS_RHO_START, inner = p.n_con ? fmax(p.tol, SYS_INNER_START) : p.tol;
     double target = fmax(p.ctol, SYS_FEASIBLE_START);
+    OpTrace tr;
+    SysTraceAt ts = {};
+    if constexpr (TRACE) {
+        tr.at = OpTraceAt::of(n);
+        ts = SysTraceAt::of(n, p.n_models, p.n_con);
+    }
+    (void)ts;
     for (int it = 0; __any(status < 0); ++it) {
         double F, noise, viol, measure;
+        const bool running = status < 0;
+        if constexpr (TRACE) tr.row = real && it == trace_it ? trace + (size_t)solve * ts.end : nullptr;
         sys_values<false>(p, s, coef, xs, dv, 0.0, fac, ev, nz);
         sys_merit<false>(p, s, xs, dv, 0.0, ev, nz, lam, rho, F, noise, viol, measure);
         sys_derivatives(p, s, coef, xs, ev, nz, lam, rho, fac, g, H, dv);
@@ -255,6 +289,21 @@ __global__ __launch_bounds__(OP_LANES) void system_optimize_kernel(SysProblem p,
         if (status < 0 && (!finite || settled || it == p.max_iter)) {
             status = !finite ? OP_NON_FINITE : settled ? OP_CONVERGED : OP_ITERATION_LIMIT;
             iterations = it;
+        }
+        if constexpr (TRACE) {
+            op_trace_entry(tr, n, running, F, noise, pg, active, status, xs, g, H);
+            if (tr.row && running) {
+                for (int k = 0; k < p.n_models; ++k) {
+                    tr.row[ts.ev + k] = ev[k * OP_LANES];
+                    tr.row[ts.nz + k] = nz[k * OP_LANES];
+                }
+                for (int i = 0; i < 2 * p.n_con; ++i) tr.row[ts.lam_in + i] = tr.row[ts.lam_out + i] = lam[i * OP_LANES];
+                tr.row[ts.head + SYS_TR_RHO] = tr.row[ts.tail] = rho;
+                tr.row[ts.head + SYS_TR_INNER] = tr.row[ts.tail + 1] = inner;
+                tr.row[ts.head + SYS_TR_TARGET] = tr.row[ts.tail + 2] = target;
+                tr.row[ts.head + SYS_TR_VIOL] = viol;
+                tr.row[ts.head + SYS_TR_MEASURE] = measure;
+            }
         }
         if (!__any(status < 0)) break;
         // the inner problem is solved to its tolerance: multipliers or penalty move, the iterate does not
@@ -279,16 +328,26 @@ __global__ __launch_bounds__(OP_LANES) void system_optimize_kernel(SysProblem p,
             target = fmax(p.ctol, SYS_FEASIBLE_SHRINK * target);
         }
         if (update && !good) rho = fmin(SYS_RHO_GROWTH * rho, SYS_RHO_MAX);
-        const bool stalled = op_step(n, box, active, status < 0 && !update, F, noise, H, g, dv, xs, steepest, [&](double alpha) {
+        if constexpr (TRACE)
+            if (tr.row && running) {
+                tr.row[ts.head + SYS_TR_UPDATE] = update;
+                tr.row[ts.head + SYS_TR_GOOD] = good;
+                for (int i = 0; i < 2 * p.n_con; ++i) tr.row[ts.lam_out + i] = lam[i * OP_LANES];
+                tr.row[ts.tail] = rho;
+                tr.row[ts.tail + 1] = inner;
+                tr.row[ts.tail + 2] = target;
+            }
+        const bool stalled = op_step<TRACE>(n, box, active, status < 0 && !update, F, noise, H, g, dv, xs, steepest, [&](double alpha) {
             double Ft, noise_t, viol_t, measure_t;
             sys_values<true>(p, s, coef, xs, dv, alpha, fac, ev, nz);
             sys_merit<true>(p, s, xs, dv, alpha, ev, nz, lam, rho, Ft, noise_t, viol_t, measure_t);
             return Ft;
-        });
+        }, tr);
         if (stalled) {
             status = OP_STALLED;
             iterations = it;
         }
+        if constexpr (TRACE) op_trace_exit(tr, n, xs, steepest, status);
     }
     // the results at the end point: objective, violation, every model's value, first-order multipliers
     double F, noise, viol, measure;
@@ -312,18 +371,19 @@ __global__ __launch_bounds__(OP_LANES) void system_optimize_kernel(SysProblem p,
 
 }  // namespace fokl
 
-extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, const int32_t *n_inputs, const int32_t *n_terms,
-                                    const int32_t *mtx, const int32_t *var_of, const double *shift, const double *slope,
-                                    int n_draws, const double *betas, const double *table, int n_basis, int width,
-                                    const double *lo, const double *hi, int n_starts, const double *starts, int obj_model,
-                                    int obj_var, double obj_offset, double obj_span, double sign, int n_con,
-                                    const int32_t *con_model, const int32_t *con_var, const double *con_par, int max_iter,
-                                    double tol, double ctol, double *x, double *f, double *violation, double *y,
-                                    double *multipliers, int32_t *iterations, int32_t *status)
+// fokl_system_optimize and fokl_system_optimize_trace (trace != nullptr: iteration trace_it into trace [N][stride])
+static int system_optimize_run(const std::string &who, fokl_ctx *ctx, int n_vars, int n_models, const int32_t *n_inputs,
+                               const int32_t *n_terms, const int32_t *mtx, const int32_t *var_of, const double *shift,
+                               const double *slope, int n_draws, const double *betas, const double *table, int n_basis,
+                               int width, const double *lo, const double *hi, int n_starts, const double *starts,
+                               int obj_model, int obj_var, double obj_offset, double obj_span, double sign, int n_con,
+                               const int32_t *con_model, const int32_t *con_var, const double *con_par, int max_iter,
+                               double tol, double ctol, double *x, double *f, double *violation, double *y,
+                               double *multipliers, int32_t *iterations, int32_t *status, int trace_it, double *trace)
 {
     using namespace fokl;
-    const std::string who = "fokl_system_optimize: ";
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
+    std::memset(ctx->system_optimize_report, 0, sizeof ctx->system_optimize_report);
     if (n_vars <= 0 || n_models <= 0 || n_draws <= 0 || n_starts <= 0 || n_basis <= 0 || width <= 0 || n_con < 0 ||
         !n_inputs || !n_terms || !mtx || !var_of || !shift || !slope || !betas || !table || !lo || !hi || !starts ||
         (n_con > 0 && (!con_model || !con_var || !con_par || !multipliers)) || !x || !f || !violation || !y || !iterations ||
@@ -457,6 +517,13 @@ extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, con
     HIP_TRY(ctx, buf.get(&d_mu, N * C));
     HIP_TRY(ctx, buf.get(&d_it, N));
     HIP_TRY(ctx, buf.get(&d_st, N));
+    double *d_trace = nullptr;
+    const size_t stride = (size_t)SysTraceAt::of(n_vars, n_models, n_con).end;
+    if (trace) {                                                       // NaN everywhere, running = 0
+        std::fill(trace, trace + N * stride, std::nan(""));
+        for (size_t i = 0; i < N; ++i) trace[i * stride + OP_TR_RUNNING] = 0.0;
+        HIP_TRY(ctx, buf.upload(&d_trace, trace, N * stride));
+    }
     SysData s{};
     s.models = d_models;
     s.slot_var = d_var;
@@ -470,8 +537,15 @@ extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, con
     s.box = d_box;
     s.con_par = d_par;
 
-    decltype(&system_optimize_kernel<true>) kernel = nullptr;
-    HIP_TRY(ctx, op_pick(system_optimize_kernel<true>, system_optimize_kernel<false>, n_starts, lds_bytes, &kernel));
+    decltype(&system_optimize_kernel<true, false>) kernel = nullptr;
+    bool raised = false;
+    if (trace)
+        HIP_TRY(ctx, op_pick(system_optimize_kernel<true, true>, system_optimize_kernel<false, true>, n_starts, lds_bytes,
+                             &kernel, &raised));
+    else
+        HIP_TRY(ctx, op_pick(system_optimize_kernel<true, false>, system_optimize_kernel<false, false>, n_starts, lds_bytes,
+                             &kernel, &raised));
+    int launches = 0, first_grid = 0;
     // a launch is asked for at most SYS_ITERATION_CAP solve-iterations (solves x max_iter), in whole wavefronts
     const int64_t per_launch = std::max<int64_t>(OP_LANES, SYS_ITERATION_CAP / std::max(1, max_iter) / OP_LANES * OP_LANES);
     for (int64_t first = 0; first < (int64_t)N; first += per_launch) {
@@ -483,8 +557,9 @@ extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, con
         TimedRegion timed(ctx, FOKL_K_OPTIMIZE_SYSTEM, 8.0 * count * (n + K + C + 4.0) + 8.0 * (double)n_draws * n_coef,
                           count * 50.0 * std::max(1, total_terms));
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(OP_LANES), lds_bytes, ctx->stream, p, s, d_starts, d_betas, d_x, d_f,
-                           d_viol, d_y, d_mu, d_it, d_st);
+                           d_viol, d_y, d_mu, d_it, d_st, d_trace, trace_it);
         HIP_TRY(ctx, hipGetLastError());
+        if (!launches++) first_grid = grid;
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(x, d_x, N * n * sizeof(double), hipMemcpyDeviceToHost));
@@ -494,5 +569,58 @@ extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, con
     if (C) HIP_TRY(ctx, hipMemcpy(multipliers, d_mu, N * C * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(iterations, d_it, N * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(status, d_st, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (trace) HIP_TRY(ctx, hipMemcpy(trace, d_trace, N * stride * sizeof(double), hipMemcpyDeviceToHost));
+    int64_t *rep = ctx->system_optimize_report;
+    rep[0] = n_starts % OP_LANES == 0 ? FOKL_OPTIMIZE_UNIFORM : FOKL_OPTIMIZE_PER_LANE;
+    rep[1] = first_grid;
+    rep[2] = (int64_t)lds_bytes;
+    rep[3] = raised;
+    rep[4] = max_slots;
+    rep[5] = (int64_t)tables.long_slots.size();
+    rep[6] = (int64_t)N;
+    rep[7] = launches;
+    rep[8] = trace != nullptr;
+    return FOKL_OK;
+}
+
+extern "C" int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, const int32_t *n_inputs, const int32_t *n_terms,
+                                    const int32_t *mtx, const int32_t *var_of, const double *shift, const double *slope,
+                                    int n_draws, const double *betas, const double *table, int n_basis, int width,
+                                    const double *lo, const double *hi, int n_starts, const double *starts, int obj_model,
+                                    int obj_var, double obj_offset, double obj_span, double sign, int n_con,
+                                    const int32_t *con_model, const int32_t *con_var, const double *con_par, int max_iter,
+                                    double tol, double ctol, double *x, double *f, double *violation, double *y,
+                                    double *multipliers, int32_t *iterations, int32_t *status)
+{
+    return system_optimize_run("fokl_system_optimize: ", ctx, n_vars, n_models, n_inputs, n_terms, mtx, var_of, shift, slope,
+                               n_draws, betas, table, n_basis, width, lo, hi, n_starts, starts, obj_model, obj_var, obj_offset,
+                               obj_span, sign, n_con, con_model, con_var, con_par, max_iter, tol, ctol, x, f, violation, y,
+                               multipliers, iterations, status, 0, nullptr);
+}
+
+extern "C" int fokl_system_optimize_trace(fokl_ctx *ctx, int n_vars, int n_models, const int32_t *n_inputs,
+                                          const int32_t *n_terms, const int32_t *mtx, const int32_t *var_of,
+                                          const double *shift, const double *slope, int n_draws, const double *betas,
+                                          const double *table, int n_basis, int width, const double *lo, const double *hi,
+                                          int n_starts, const double *starts, int obj_model, int obj_var, double obj_offset,
+                                          double obj_span, double sign, int n_con, const int32_t *con_model,
+                                          const int32_t *con_var, const double *con_par, int max_iter, double tol,
+                                          double ctol, double *x, double *f, double *violation, double *y,
+                                          double *multipliers, int32_t *iterations, int32_t *status, int trace_iteration,
+                                          double *trace)
+{
+    const std::string who = "fokl_system_optimize_trace: ";
+    if (ctx) std::memset(ctx->system_optimize_report, 0, sizeof ctx->system_optimize_report);
+    if (!trace || trace_iteration < 0) return fail(ctx, FOKL_ERR_ARG, who + "null trace or negative iteration");
+    return system_optimize_run(who, ctx, n_vars, n_models, n_inputs, n_terms, mtx, var_of, shift, slope, n_draws, betas, table,
+                               n_basis, width, lo, hi, n_starts, starts, obj_model, obj_var, obj_offset, obj_span, sign, n_con,
+                               con_model, con_var, con_par, max_iter, tol, ctol, x, f, violation, y, multipliers, iterations,
+                               status, trace_iteration, trace);
+}
+
+extern "C" int fokl_system_optimize_report(const fokl_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return fail(nullptr, FOKL_ERR_ARG, "fokl_system_optimize_report: null argument");
+    std::memcpy(out, ctx->system_optimize_report, sizeof ctx->system_optimize_report);
     return FOKL_OK;
 }

@@ -31,7 +31,13 @@ STATEMENT the kernel is tested against.  Step 1 is ``_model_parts`` and steps 3-
 and for the system solver below alike -- as both kernels have them from ``csrc/fokl_optimize_core.inc``.  It carries a batch of solves through every numpy operation (each solve sees
 exactly the element-wise arithmetic it would see alone) because a Python loop over 32 000 solves is of no use to a test.
 The device and the host may differ in the last bits of a sum (the order of the terms differs), which can flip a
-line-search test: compare results, not iterates.
+line-search test, so whole solves are compared by their results.  Iterates are compared one iteration at a time
+(``DeviceContext.model_optimize(..., trace_iteration=k)`` / ``system_optimize(p, trace_iteration=k)``: the product kernels
+write what iteration k saw and decided): the values against exact references -- integer data, where the order of a sum
+does not matter, bit for bit; the real table against rational arithmetic within a derived rounding bound -- and the
+decisions against the traced values themselves: ``_step_direction``, ``_armijo`` and ``_constraint`` on the device's own
+F, g, H and trial values must give the device's factor, direction, trial count, step and update bit for bit
+(tests/optimize_step_cases.py).
 
 Limits, checked before anything is launched: at most 16 inputs; 3 x distinct factors + m (m + 1) / 2 + 3 m values per
 solve within the 144 KB of LDS a wavefront of 64 solves gets (the 16-input, 32-factor models fit: 280 of 288); orders
@@ -424,22 +430,45 @@ def _direction(H, g, active):
     return d
 
 
-def _newton_step(x, F, noise, g, H, lo, hi, stepping, steepest, merit_at):
-    """Steps 3-5 for the solves ``stepping`` [B] at the iterates x [B, m], where the merit is F [B] (sum of magnitudes
-    ``noise``) with gradient g [m, B] and Hessian triangle H (factored in place); ``merit_at(points)`` is the merit at
-    trial points [B, m].  x moves in place where a trial point passes.  Returns (failed, use_steepest): no trial point
-    passed; the direction was projected steepest descent (asked for by ``steepest``, or the Newton one was not finite)."""
-    B, m = x.shape
+def _active_set(xt, g, lo_c, hi_c):
+    """Step 3: the fixed coordinates and those on a bound whose descent direction points outwards; xt, g [m, B]."""
+    with np.errstate(invalid='ignore'):
+        return (lo_c == hi_c) | ((xt <= lo_c) & (g > 0)) | ((xt >= hi_c) & (g < 0))
+
+
+def _step_direction(x, g, H, lo, hi, steepest):
+    """Steps 3 and 4 at the iterates x [B, m]: the active set [m, B], the direction d [m, B] -- the modified-Cholesky
+    Newton direction (H is factored in place), projected steepest descent where ``steepest`` asks for it or the Newton
+    direction is not finite, scaled to at most one box width -- and which of the two it is."""
     xt = x.T                                                         # [m, B]
     lo_c, hi_c = lo[:, None], hi[:, None]
     with np.errstate(invalid='ignore', over='ignore'):
-        active = (lo_c == hi_c) | ((xt <= lo_c) & (g > 0)) | ((xt >= hi_c) & (g < 0))
+        active = _active_set(xt, g, lo_c, hi_c)
         d = _direction(H, g, active)
         reach = np.max(np.abs(d), axis=0)
         use_steepest = steepest | ~(reach <= np.finfo(np.float64).max)
         d = np.where(use_steepest, np.where(active, 0.0, -g), d)
         reach = np.max(np.abs(d), axis=0)
         d = np.where(reach > 1.0, d / reach, d)
+    return active, d, use_steepest
+
+
+def _armijo(Ft, F, noise, g, step):
+    """Step 5's test of the trial points x + step (step [m, B], already projected): the decrease with its rounding
+    allowance, and that the point moved at all."""
+    slope = np.zeros(F.shape[0])
+    for j in range(step.shape[0]):
+        slope = slope + g[j] * step[j]
+    return (Ft <= F + ARMIJO * np.minimum(slope, 0.0) + NOISE * noise) & (np.max(np.abs(step), axis=0) > 0)
+
+
+def _arc_search(x, F, noise, g, d, lo, hi, stepping, merit_at):
+    """Step 5 for the solves ``stepping``: halving along the projection arc; x moves in place where a trial point
+    passes.  Returns which solves found none."""
+    B, m = x.shape
+    xt = x.T
+    lo_c, hi_c = lo[:, None], hi[:, None]
+    with np.errstate(invalid='ignore', over='ignore'):
         alpha = np.ones(B)
         searching = stepping.copy()
         for _ in range(MAX_HALVINGS + 1):
@@ -447,16 +476,21 @@ def _newton_step(x, F, noise, g, H, lo, hi, stepping, steepest, merit_at):
                 break
             trial = np.minimum(np.maximum(xt + alpha * d, lo_c), hi_c)
             Ft = merit_at(np.ascontiguousarray(trial.T))
-            step = trial - xt
-            slope = np.zeros(B)
-            for j in range(m):
-                slope = slope + g[j] * step[j]
-            ok = (Ft <= F + ARMIJO * np.minimum(slope, 0.0) + NOISE * noise) & (np.max(np.abs(step), axis=0) > 0)
+            ok = _armijo(Ft, F, noise, g, trial - xt)
             take = searching & ok
             x[take] = trial.T[take]
             searching = searching & ~ok
             alpha = np.where(searching, alpha * 0.5, alpha)
-    return searching, use_steepest
+    return searching
+
+
+def _newton_step(x, F, noise, g, H, lo, hi, stepping, steepest, merit_at):
+    """Steps 3-5 for the solves ``stepping`` [B] at the iterates x [B, m], where the merit is F [B] (sum of magnitudes
+    ``noise``) with gradient g [m, B] and Hessian triangle H (factored in place); ``merit_at(points)`` is the merit at
+    trial points [B, m].  x moves in place where a trial point passes.  Returns (failed, use_steepest): no trial point
+    passed; the direction was projected steepest descent (asked for by ``steepest``, or the Newton one was not finite)."""
+    _, d, use_steepest = _step_direction(x, g, H, lo, hi, steepest)
+    return _arc_search(x, F, noise, g, d, lo, hi, stepping, merit_at), use_steepest
 
 
 def _solve_block(tt, table, coef, lo, hi, x, sign, max_iter, tol):

@@ -13,6 +13,8 @@
  *                              a host chain's recursion in verified segments (the boundary's header is full)
  *   fokl_model_optimize        the multistart optimiser behind fokl_gpy_amd/optimize.py (the boundary's header is full)
  *   fokl_system_optimize       its constrained counterpart over a system of models (optimize.optimize_system)
+ *   fokl_model_optimize_trace / fokl_system_optimize_trace / fokl_optimize_report / fokl_system_optimize_report
+ *                              one iteration of every solve as the product kernels saw it, and what they launched
  *   fokl_predict_report        which kernel the last fokl_predict call ran, over what grid, and how many of its tiles took
  *                              the exact fallback (the boundary's header is full)
  *   fokl_population_stats / fokl_population_report
@@ -702,6 +704,63 @@ int fokl_system_optimize(fokl_ctx *ctx, int n_vars, int n_models, const int32_t 
                          const int32_t *con_var, const double *con_par, int max_iter, double tol, double ctol, double *x,
                          double *f, double *violation, double *y, double *multipliers, int32_t *iterations,
                          int32_t *status);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* The optimisers' Newton step, one iteration at a time: traces and launch reports (tests; optimize.py)       */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_OPTIMIZE_REPORT_LEN 9
+/* out[0] of fokl_optimize_report / fokl_system_optimize_report: the instantiation that ran */
+enum {
+    FOKL_OPTIMIZE_NONE = 0,       /* no call yet, or the last one was refused or failed: nothing to report */
+    FOKL_OPTIMIZE_UNIFORM = 1,    /* n_starts a multiple of 64: a wavefront belongs to one draw, scalar coefficient loads */
+    FOKL_OPTIMIZE_PER_LANE = 2    /* every lane reads its own draw's row */
+};
+
+/*
+ * fokl_model_optimize / fokl_system_optimize with one more result: what iteration `trace_iteration` (0 = the first pass)
+ * of every solve saw and decided, written by the TRACE instantiation of the SAME kernel body the product launches
+ * (the tracing statements are compiled away in the product's instantiations).  Everything else -- arguments, checks,
+ * results, launches -- is the product entry point's: both run one host function.
+ * trace [n_draws * n_starts, stride] doubles, host memory; flags and counts are stored as doubles.  With m = n_inputs (or
+ * n_vars), h = m (m + 1) / 2, a row is
+ *   [0]  running: 1 the solve was running when the iteration began, 0 it had stopped before (or its whole wavefront had)
+ *   [1] F  [2] noise  [3] pg  [4] active (bit j: coordinate j)  [5] status after the iteration's tests (-1: runs on)
+ *   [6] stepping  [7] use_steepest  [8] trial points evaluated while searching  [9] alpha  [10] failed
+ *   [11] steepest for the next iteration  [12] status at the iteration's exit (-1: runs on)
+ *   then x_in [m], g [m], H [h] before the factorisation, the factor [h], d [m] after the fall-back select and the
+ *   scaling, Ft [31] of the trial points (NaN beyond those evaluated), x_out [m]:  stride = 13 + 4 m + 2 h + 31;
+ *   the system's rows go on with ev [K], nz [K], lam [2 C], rho, inner, target, viol, measure, update, good at the entry
+ *   and lam [2 C], rho, inner, target at the exit:  stride = 13 + 4 n + 2 h + 31 + 2 K + 4 C + 10.
+ * What a row does not get stays NaN: everything but running for a solve whose wavefront ended before the iteration;
+ * everything but running, both statuses, x_in and x_out (= x_in) for a solve that had stopped; the step's values when
+ * the wavefront ended at this iteration's tests.  Values of a lane that is not `stepping` are what the kernel computed
+ * and dropped.
+ */
+int fokl_model_optimize_trace(fokl_ctx *ctx, int n_inputs, int n_terms, const int32_t *mtx, int n_draws,
+                              const double *betas, const double *table, int n_basis, int width, const double *lo,
+                              const double *hi, int n_starts, const double *starts, double sign, int max_iter, double tol,
+                              double *x, double *f, int32_t *iterations, int32_t *status, int trace_iteration,
+                              double *trace);
+int fokl_system_optimize_trace(fokl_ctx *ctx, int n_vars, int n_models, const int32_t *n_inputs, const int32_t *n_terms,
+                               const int32_t *mtx, const int32_t *var_of, const double *shift, const double *slope,
+                               int n_draws, const double *betas, const double *table, int n_basis, int width,
+                               const double *lo, const double *hi, int n_starts, const double *starts, int obj_model,
+                               int obj_var, double obj_offset, double obj_span, double sign, int n_con,
+                               const int32_t *con_model, const int32_t *con_var, const double *con_par, int max_iter,
+                               double tol, double ctol, double *x, double *f, double *violation, double *y,
+                               double *multipliers, int32_t *iterations, int32_t *status, int trace_iteration,
+                               double *trace);
+
+/*
+ * What the last fokl_model_optimize(_trace) / fokl_system_optimize(_trace) call on `ctx` ran, out [9] (host values, no
+ * launch): the instantiation (FOKL_OPTIMIZE_*), the grid (workgroups = wavefronts; the system's: of its first launch),
+ * lds_bytes, whether the attribute that allows more than 64 KB of LDS was set, slots (distinct (input, order) factors;
+ * the system's: of its largest model), side-list entries, solves, launches, 1 if it was a trace.  All zeros after a call
+ * that was refused or failed.
+ */
+int fokl_optimize_report(const fokl_ctx *ctx, int64_t *out);
+int fokl_system_optimize_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* Embedded GPs: HMC chains of GPs inside a traced equation (csrc/fokl_embedded_device.inc; embedded.py)     */

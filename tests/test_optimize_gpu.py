@@ -62,7 +62,8 @@ def projected_gradient(mtx, betas, x, sign, lo, hi):
 
 
 def check_against_host(dev, host, mtx, betas, sign, lo, hi, label=''):
-    """Results, not iterates: the orders of the sums differ, which may flip a line-search test."""
+    """Whole solves by their results: the orders of the sums differ, which may flip a line-search test.  The iterates
+    are compared one iteration at a time in test_optimize_step_gpu.py and test_optimize_system_step_gpu.py."""
     x, f, it, st = dev
     hx, hf, hit, hst = host
     assert x.shape == hx.shape and f.shape == hf.shape and st.dtype == np.int32 and it.dtype == np.int32
@@ -191,6 +192,8 @@ def test_native_refusals_launch_nothing(device_ctx):
         with pytest.raises(_capi.FoklNativeError) as err:
             device_ctx.model_optimize(*args)
         assert err.value.code == -2 and text in str(err.value), str(err.value)
+        report = device_ctx.optimize_report()
+        assert report.pop('instance') == 'none' and set(report.values()) == {0}
 
     wide = np.zeros((1, 17), dtype=np.int32)
     wide[0, 0] = 1

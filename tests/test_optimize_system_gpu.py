@@ -76,7 +76,8 @@ def system(name, draws):
 
 
 def check_against_host(dev, host, label):
-    """Results, not iterates: the orders of the sums differ, which may flip a line-search test."""
+    """Whole solves by their results: the orders of the sums differ, which may flip a line-search test.  The iterates
+    are compared one iteration at a time in test_optimize_step_gpu.py and test_optimize_system_step_gpu.py."""
     x, f, viol, y, mu, it, st = dev
     hx, hf, hviol, hy, hmu, hit, hst = host
     assert x.shape == hx.shape and y.shape == hy.shape and mu.shape == hmu.shape and st.dtype == np.int32
@@ -225,6 +226,8 @@ def test_native_refusals_launch_nothing(device_ctx):
         with pytest.raises(_capi.FoklNativeError) as err:
             device_ctx.system_optimize(dict(p, **changes))
         assert err.value.code == -2 and text in str(err.value), str(err.value)
+        report = device_ctx.system_optimize_report()
+        assert report.pop('instance') == 'none' and set(report.values()) == {0}
 
     refused('sign must be', sign=0.5)
     refused('sign must be', ctol=-1.0)
