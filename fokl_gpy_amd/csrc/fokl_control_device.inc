@@ -19,6 +19,8 @@
 //                  draw's coefficients once) with the controlled columns' forcing factors from the lane's own trial point;
 //                  each lane accumulates its own F; the first passing lane comes from a ballot
 // control_trajectory_kernel<NS> is the trial pass with every lane at the accepted point and lane 0 storing.
+// The parts of an iteration are __device__ functions (ctl_tangent_pass, ctl_stop_code, ctl_newton_direction, ctl_trial_points,
+// ctl_first_passing) that the kernels of dynamics.control_pooled (fokl_control_pooled_device.inc) call as well.
 // LDS, as [item][lane] unless noted: values of slot 0 (1.0), the factors and the stage's normalised states; their tangents;
 // four rows of 64 (exchange, z, g, direction); row d of H as [D][64] (after the factorisation: the trial points, lane =
 // trial); the draw's coefficients ONCE ([coefficient]).  bytes = (2 (1 + factors + normalised states) + 4 + D) x 64 x 8 +
@@ -252,43 +254,34 @@ __device__ __forceinline__ CtlLds ctl_lds(double *lds, const SimSystem &sys, int
     return l;
 }
 
-// Iteration `it` of every running solve b = draw * n_starts + start.  coef [draws][n_coef]; y0 [NS][draws]; z [solves][D];
-// status (-1: running), iterations, descent (steps taken in a steepest-descent lane), cost, cost_start [solves]; work [max_iter + 1]: launch `it` found a running solve;
-// first_F [solves], first_g [solves][D], first_H [solves][D][D] (or null): the tangent pass of iteration 0.
-template <int NS>
-__global__ __launch_bounds__(SIM_LANES) void control_iterate_kernel(
-    SimSystem sys, CtlProblem cp, const int *__restrict__ norm_src, const double *__restrict__ norm_lo,
-    const double *__restrict__ norm_span, const int *__restrict__ fac_norm, const int *__restrict__ fac_row,
-    const int *__restrict__ fac_degree, const int4 *__restrict__ entries, const double *__restrict__ spline,
-    const double *__restrict__ bern, const int *__restrict__ norm_control, const int *__restrict__ seg_first,
-    const double *__restrict__ ref, const double *__restrict__ coef, const double *__restrict__ forcing,
-    const double *__restrict__ y0, double *__restrict__ z, int *__restrict__ status, int *__restrict__ iterations,
-    int *__restrict__ descent, double *__restrict__ cost, double *__restrict__ cost_start, int *__restrict__ work,
-    double *__restrict__ first_F,
-    double *__restrict__ first_g, double *__restrict__ first_H, int it)
+// ---- what control_iterate_kernel and the pooled kernels (fokl_control_pooled_device.inc) share: one text, inlined ----
+
+// Before a tangent pass: slot 0, the draw's coefficients `coef` [n_coef], the iterate `z` [D] into the z row, H = 0
+__device__ __forceinline__ void ctl_tangent_load(const SimSystem &sys, const CtlLds &l, double *Hl, int D, int lane,
+                                                 const double *__restrict__ coef, const double *__restrict__ z)
 {
-    const size_t b = blockIdx.x;
-    if (status[b] >= 0) return;                                        // a finished solve returns at once
-    const SimTables tab{norm_src, norm_lo, norm_span, fac_norm, fac_row, fac_degree, entries, spline, bern};
-    const CtlTables ct{norm_control, seg_first, ref};
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int lane = threadIdx.x, D = cp.D, P = cp.n_steps + 1;
-    const size_t e = b / (size_t)cp.n_starts;
-    const CtlLds l = ctl_lds(lds, sys, D, lane);
-    double *Hl = l.H + lane;                                           // Hl[d' * 64] = H[lane][d']
     l.fac[0] = 1.0;
     l.tfac[0] = 0.0;
-    for (int c = lane; c < sys.n_coef; c += SIM_LANES) l.cf[c] = coef[e * sys.n_coef + c];
-    l.zs[lane] = lane < D ? z[b * D + lane] : 0.0;
+    for (int c = lane; c < sys.n_coef; c += SIM_LANES) l.cf[c] = coef[c];
+    l.zs[lane] = lane < D ? z[lane] : 0.0;
     for (int d2 = 0; d2 < D; ++d2) Hl[d2 * SIM_LANES] = 0.0;
-    if (lane == 0) work[it] = 1;
     __syncthreads();
+}
 
-    // ---- the tangent pass: F, noise (wave-uniform), g of this lane's direction, row `lane` of H ----
-    double y0r[NS], y[NS], at[NS], dy[NS] = {}, sum[NS] = {}, ty[NS] = {}, tat[NS], tdy[NS] = {}, tsum[NS] = {};
+// The tangent pass at the z row: F, noise (wave-uniform), g of this lane's direction (0 for lane >= D), row `lane` of H in Hl
+template <int NS>
+__device__ __forceinline__ void ctl_tangent_pass(const SimSystem &sys, const CtlProblem &cp, const SimTables &tab,
+                                                 const CtlTables &ct, const double *__restrict__ forcing, const CtlLds &l,
+                                                 double *Hl, const double (&y0r)[NS], int lane, double &F, double &noise,
+                                                 double &g)
+{
+    const int D = cp.D, P = cp.n_steps + 1;
+    double y[NS], at[NS], dy[NS] = {}, sum[NS] = {}, ty[NS] = {}, tat[NS], tdy[NS] = {}, tsum[NS] = {};
 #pragma unroll
-    for (int j = 0; j < NS; ++j) y[j] = y0r[j] = y0[(size_t)j * cp.n_draws + e];
-    double F = 0.0, noise = 0.0, g = 0.0;
+    for (int j = 0; j < NS; ++j) y[j] = y0r[j];
+    F = 0.0;
+    noise = 0.0;
+    g = 0.0;
     int k = 0;
     for (int s = 0; s < cp.n_steps; ++s) {
         if (k + 1 < cp.segments && s >= ct.seg_first[k + 1]) ++k;
@@ -348,6 +341,125 @@ __global__ __launch_bounds__(SIM_LANES) void control_iterate_kernel(
         }
     }
     if (lane >= D) g = 0.0;
+}
+
+// The stop test of iteration `it` at z_lane = zl: a status, or -1 to go on (wave-uniform)
+__device__ __forceinline__ int ctl_stop_code(const CtlProblem &cp, double F, double g, double zl, int lane, int it)
+{
+    const bool finite = F - F == 0.0 && __all((int)(g - g == 0.0));
+    const double pg = asm_max(lane < cp.D ? fabs(ctl_clip01(zl - g) - zl) : 0.0);
+    return !finite ? CTL_NON_FINITE : pg <= cp.tol ? CTL_CONVERGED : it == cp.max_iter ? CTL_ITERATION_LIMIT : -1;
+}
+
+// Active set, the modified Cholesky factor in place (L[i][k] = H[k * 64 + i], H[d' * 64 + d] = H[d][d'] on entry) and the two
+// solves: the Newton direction is left in ds [D] and g in gs [64].  Uses ex.
+__device__ __forceinline__ void ctl_newton_direction(double *H, double *ex, double *gs, double *ds, int D, int lane, double zl,
+                                                     double g)
+{
+    const bool active = lane < D && ((zl <= 0.0 && g > 0) || (zl >= 1.0 && g < 0));
+    const unsigned long long active_mask = __ballot((int)active);
+    const double free_diag = asm_max((lane < D && !active) ? fabs(H[lane * SIM_LANES + lane]) : 0.0);
+    const double floor_ = CTL_PIVOT_FLOOR * fmax(1.0, free_diag);
+    for (int j = 0; j < D; ++j) {
+        double s = 0.0;
+        if (lane >= j && lane < D) {
+            const bool either = active || ((active_mask >> j) & 1ull);
+            s = either ? (lane == j ? 1.0 : 0.0) : H[j * SIM_LANES + lane];
+            for (int q = 0; q < j; ++q) s = s - H[q * SIM_LANES + lane] * H[q * SIM_LANES + j];
+            if (lane == j) {
+                s = s > floor_ ? s : fmax(fabs(s), floor_);
+                H[j * SIM_LANES + j] = sqrt(s);
+            }
+        }
+        __syncthreads();
+        if (lane > j && lane < D) H[j * SIM_LANES + lane] = s / H[j * SIM_LANES + j];
+        __syncthreads();
+    }
+    double s = active ? 0.0 : -g;
+    for (int q = 0; q < D; ++q) {                                      // forward
+        if (lane == q) {
+            s = s / H[q * SIM_LANES + q];
+            ex[q] = s;
+        }
+        __syncthreads();
+        if (lane > q && lane < D) s = s - H[q * SIM_LANES + lane] * ex[q];
+    }
+    for (int q = D - 1; q >= 0; --q) {                                 // back
+        if (lane == q) {
+            s = s / H[q * SIM_LANES + q];
+            ds[q] = s;
+        }
+        __syncthreads();
+        if (lane < q) s = s - H[lane * SIM_LANES + q] * ds[q];
+    }
+    gs[lane] = g;
+    __syncthreads();
+}
+
+// Every trial point at once, the lane's own in column `lane` of the H rows (Hl[d * 64]); its slope and whether it moves z.
+// Returns whether the lane is a trial at all (lanes 31 and 63 are not).
+__device__ __forceinline__ bool ctl_trial_points(const double *zs, const double *gs, const double *ds, double *Hl, int D, int lane,
+                                                 double &slope, bool &moved)
+{
+    const int halving = lane & 31;
+    const bool newton = lane < 32, valid = halving < CTL_TRIALS;
+    const double alpha = __longlong_as_double((long long)(1023 - halving) << 52);      // 2^-halving
+    slope = 0.0;
+    moved = false;
+    for (int d = 0; d < D; ++d) {
+        const double base = newton ? ds[d] : -gs[d];
+        const double x = ctl_clip01(zs[d] + alpha * base);
+        Hl[d * SIM_LANES] = x;
+        const double step = x - zs[d];
+        slope = slope + gs[d] * step;
+        moved = moved || fabs(step) > 0;
+    }
+    return valid;
+}
+
+// The Armijo test of every lane's trial cost Ft and the first passing lane: Newton lanes first, -1 if none passes
+__device__ __forceinline__ int ctl_first_passing(bool valid, bool moved, double Ft, double F, double slope, double noise)
+{
+    const bool ok = valid && moved && Ft <= (F + CTL_ARMIJO * (slope < 0 ? slope : 0.0)) + CTL_NOISE * noise;
+    const unsigned long long passed = __ballot((int)ok);
+    const unsigned int by_newton = (unsigned int)(passed & 0x7FFFFFFFull), by_descent = (unsigned int)((passed >> 32) & 0x7FFFFFFFull);
+    if (by_newton == 0u && by_descent == 0u) return -1;
+    return by_newton ? __builtin_ctz(by_newton) : 32 + __builtin_ctz(by_descent);
+}
+
+// Iteration `it` of every running solve b = draw * n_starts + start.  coef [draws][n_coef]; y0 [NS][draws]; z [solves][D];
+// status (-1: running), iterations, descent (steps taken in a steepest-descent lane), cost, cost_start [solves]; work [max_iter + 1]: launch `it` found a running solve;
+// first_F [solves], first_g [solves][D], first_H [solves][D][D] (or null): the tangent pass of iteration 0.
+template <int NS>
+__global__ __launch_bounds__(SIM_LANES) void control_iterate_kernel(
+    SimSystem sys, CtlProblem cp, const int *__restrict__ norm_src, const double *__restrict__ norm_lo,
+    const double *__restrict__ norm_span, const int *__restrict__ fac_norm, const int *__restrict__ fac_row,
+    const int *__restrict__ fac_degree, const int4 *__restrict__ entries, const double *__restrict__ spline,
+    const double *__restrict__ bern, const int *__restrict__ norm_control, const int *__restrict__ seg_first,
+    const double *__restrict__ ref, const double *__restrict__ coef, const double *__restrict__ forcing,
+    const double *__restrict__ y0, double *__restrict__ z, int *__restrict__ status, int *__restrict__ iterations,
+    int *__restrict__ descent, double *__restrict__ cost, double *__restrict__ cost_start, int *__restrict__ work,
+    double *__restrict__ first_F,
+    double *__restrict__ first_g, double *__restrict__ first_H, int it)
+{
+    const size_t b = blockIdx.x;
+    if (status[b] >= 0) return;                                        // a finished solve returns at once
+    const SimTables tab{norm_src, norm_lo, norm_span, fac_norm, fac_row, fac_degree, entries, spline, bern};
+    const CtlTables ct{norm_control, seg_first, ref};
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int lane = threadIdx.x, D = cp.D;
+    const size_t e = b / (size_t)cp.n_starts;
+    const CtlLds l = ctl_lds(lds, sys, D, lane);
+    double *Hl = l.H + lane;                                           // Hl[d' * 64] = H[lane][d']
+    if (lane == 0) work[it] = 1;
+    ctl_tangent_load(sys, l, Hl, D, lane, coef + e * sys.n_coef, z + b * D);
+
+    // ---- the tangent pass: F, noise (wave-uniform), g of this lane's direction, row `lane` of H ----
+    double y0r[NS];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) y0r[j] = y0[(size_t)j * cp.n_draws + e];
+    double F, noise, g;
+    ctl_tangent_pass<NS>(sys, cp, tab, ct, forcing, l, Hl, y0r, lane, F, noise, g);
     if (it == 0) {
         if (lane == 0) cost_start[b] = F;
         if (first_F) {
@@ -362,9 +474,7 @@ __global__ __launch_bounds__(SIM_LANES) void control_iterate_kernel(
 
     // ---- the stop test ----
     const double zl = l.zs[lane];
-    const bool finite = F - F == 0.0 && __all((int)(g - g == 0.0));
-    const double pg = asm_max(lane < D ? fabs(ctl_clip01(zl - g) - zl) : 0.0);
-    const int code = !finite ? CTL_NON_FINITE : pg <= cp.tol ? CTL_CONVERGED : it == cp.max_iter ? CTL_ITERATION_LIMIT : -1;
+    const int code = ctl_stop_code(cp, F, g, zl, lane, it);
     if (code >= 0) {
         if (lane == 0) {
             status[b] = code;
@@ -373,73 +483,21 @@ __global__ __launch_bounds__(SIM_LANES) void control_iterate_kernel(
         return;
     }
 
-    // ---- active set and the modified Cholesky factor, in place: L[i][k] = l.H[k * 64 + i] ----
-    const bool active = lane < D && ((zl <= 0.0 && g > 0) || (zl >= 1.0 && g < 0));
-    const unsigned long long active_mask = __ballot((int)active);
-    const double free_diag = asm_max((lane < D && !active) ? fabs(Hl[lane * SIM_LANES]) : 0.0);
-    const double floor_ = CTL_PIVOT_FLOOR * fmax(1.0, free_diag);
-    for (int j = 0; j < D; ++j) {
-        double s = 0.0;
-        if (lane >= j && lane < D) {
-            const bool either = active || ((active_mask >> j) & 1ull);
-            s = either ? (lane == j ? 1.0 : 0.0) : l.H[j * SIM_LANES + lane];
-            for (int q = 0; q < j; ++q) s = s - l.H[q * SIM_LANES + lane] * l.H[q * SIM_LANES + j];
-            if (lane == j) {
-                s = s > floor_ ? s : fmax(fabs(s), floor_);
-                l.H[j * SIM_LANES + j] = sqrt(s);
-            }
-        }
-        __syncthreads();
-        if (lane > j && lane < D) l.H[j * SIM_LANES + lane] = s / l.H[j * SIM_LANES + j];
-        __syncthreads();
-    }
-    double s = active ? 0.0 : -g;
-    for (int q = 0; q < D; ++q) {                                      // forward
-        if (lane == q) {
-            s = s / l.H[q * SIM_LANES + q];
-            l.ex[q] = s;
-        }
-        __syncthreads();
-        if (lane > q && lane < D) s = s - l.H[q * SIM_LANES + lane] * l.ex[q];
-    }
-    for (int q = D - 1; q >= 0; --q) {                                 // back
-        if (lane == q) {
-            s = s / l.H[q * SIM_LANES + q];
-            l.ds[q] = s;
-        }
-        __syncthreads();
-        if (lane < q) s = s - l.H[lane * SIM_LANES + q] * l.ds[q];
-    }
-    l.gs[lane] = g;
-    __syncthreads();
-
-    // ---- every trial point at once: the lane's own in column `lane` of the H rows ----
-    const int halving = lane & 31;
-    const bool newton = lane < 32, valid = halving < CTL_TRIALS;
-    const double alpha = __longlong_as_double((long long)(1023 - halving) << 52);      // 2^-halving
-    double slope = 0.0;
-    bool moved = false;
-    for (int d = 0; d < D; ++d) {
-        const double base = newton ? l.ds[d] : -l.gs[d];
-        const double x = ctl_clip01(l.zs[d] + alpha * base);
-        Hl[d * SIM_LANES] = x;
-        const double step = x - l.zs[d];
-        slope = slope + l.gs[d] * step;
-        moved = moved || fabs(step) > 0;
-    }
+    // ---- active set, modified Cholesky and the two solves; then every trial point at once ----
+    ctl_newton_direction(l.H, l.ex, l.gs, l.ds, D, lane, zl, g);
+    double slope;
+    bool moved;
+    const bool valid = ctl_trial_points(l.zs, l.gs, l.ds, Hl, D, lane, slope, moved);
     int unused = 0;
     const double Ft = ctl_value_pass<NS>(sys, cp, tab, ct, forcing, l.xn, l.fac, l.cf, Hl, y0r, lane, nullptr, unused);
-    const bool ok = valid && moved && Ft <= (F + CTL_ARMIJO * (slope < 0 ? slope : 0.0)) + CTL_NOISE * noise;
-    const unsigned long long passed = __ballot((int)ok);
-    const unsigned int by_newton = (unsigned int)(passed & 0x7FFFFFFFull), by_descent = (unsigned int)((passed >> 32) & 0x7FFFFFFFull);
-    if (by_newton == 0u && by_descent == 0u) {
+    const int taken = ctl_first_passing(valid, moved, Ft, F, slope, noise);
+    if (taken < 0) {
         if (lane == 0) {
             status[b] = CTL_STALLED;
             iterations[b] = it;
         }
         return;
     }
-    const int taken = by_newton ? __builtin_ctz(by_newton) : 32 + __builtin_ctz(by_descent);
     if (lane < D) z[b * D + lane] = l.H[lane * SIM_LANES + taken];
     if (lane == 0 && taken >= 32) descent[b] = descent[b] + 1;
 }
@@ -512,42 +570,60 @@ hipError_t ctl_trajectory(fokl_ctx *ctx, int grid, size_t lds_bytes, const SimSy
     return hipGetLastError();
 }
 
-}  // namespace
+// The inputs fokl_control_solve and fokl_control_pooled_solve share, as their argument lists name them
+struct CtlArgs {
+    int n_draws, n_states;
+    int64_t n_steps;
+    double h;
+    int n_forcing_cols;
+    const double *forcing;
+    int n_norm_forcing, n_norm;
+    const int32_t *norm_src;
+    const double *norm_lo, *norm_span;
+    int n_forcing_factors, n_factors;
+    const int32_t *fac_norm, *fac_kind, *fac_row, *fac_degree;
+    int n_spline_rows;
+    const double *spline_table;
+    int n_bern_rows;
+    const double *bern_table;
+    int n_entries;
+    const int32_t *entries, *entry_begin, *entry_count, *constant;
+    int n_coef;
+    const double *coef, *y0, *box;
+    int n_controls, n_segments;
+    const int32_t *seg_first, *norm_control;
+    const double *ctl_lo, *ctl_width, *ref, *track_weight, *terminal_weight, *limit_lo, *limit_hi;
+    double limit_weight;
+    const double *move_weight, *previous;
+    int has_previous, n_starts;
+    const double *z0;
+    int max_iter;
+    double tol;
+};
 
-extern "C" int fokl_control_report(const fokl_ctx *ctx, int64_t *out)
+// Everything both entry points refuse of their inputs (the outputs are the caller's to check), and the plan: sys, cp, the
+// LDS bytes of a wavefront that runs a tangent or a value pass.
+int ctl_plan(fokl_ctx *ctx, const std::string &who, const CtlArgs &in, SimSystem &sys, CtlProblem &cp,
+             size_t &lds_bytes, int &n_bern_factors)
 {
-    if (!ctx || !out) return fail(nullptr, FOKL_ERR_ARG, "fokl_control_report: null argument");
-    std::memcpy(out, ctx->control_report, sizeof ctx->control_report);
-    return FOKL_OK;
-}
-
-extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
-                                  const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
-                                  const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
-                                  const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
-                                  const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
-                                  const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
-                                  const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
-                                  const double *y0, const double *box, int n_controls, int n_segments,
-                                  const int32_t *seg_first, const int32_t *norm_control, const double *ctl_lo,
-                                  const double *ctl_width, const double *ref, const double *track_weight,
-                                  const double *terminal_weight, const double *limit_lo, const double *limit_hi,
-                                  double limit_weight, const double *move_weight, const double *previous, int has_previous,
-                                  int n_starts, const double *z0, int max_iter, double tol, double *z, double *cost,
-                                  double *cost_start, int32_t *status, int32_t *iterations, int32_t *descent_steps,
-                                  int32_t *best_start,
-                                  double *members, int32_t *first_saturation, double *first_F, double *first_g,
-                                  double *first_H)
-{
-    const std::string who = "fokl_control_solve: ";
-    if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
-    std::memset(ctx->control_report, 0, sizeof ctx->control_report);
+    const int n_draws = in.n_draws, n_states = in.n_states, n_forcing_cols = in.n_forcing_cols, n_norm_forcing = in.n_norm_forcing,
+              n_norm = in.n_norm, n_forcing_factors = in.n_forcing_factors, n_factors = in.n_factors, n_spline_rows = in.n_spline_rows,
+              n_bern_rows = in.n_bern_rows, n_entries = in.n_entries, n_coef = in.n_coef, n_controls = in.n_controls,
+              n_segments = in.n_segments, has_previous = in.has_previous, n_starts = in.n_starts, max_iter = in.max_iter;
+    const int64_t n_steps = in.n_steps;
+    const double h = in.h, limit_weight = in.limit_weight, tol = in.tol;
+    const int32_t *norm_src = in.norm_src, *fac_norm = in.fac_norm, *fac_kind = in.fac_kind, *fac_row = in.fac_row,
+                  *fac_degree = in.fac_degree, *entries = in.entries, *entry_begin = in.entry_begin, *entry_count = in.entry_count,
+                  *constant = in.constant, *seg_first = in.seg_first, *norm_control = in.norm_control;
+    const double *forcing = in.forcing, *norm_lo = in.norm_lo, *norm_span = in.norm_span, *spline_table = in.spline_table,
+                 *bern_table = in.bern_table, *coef = in.coef, *y0 = in.y0, *box = in.box, *ctl_lo = in.ctl_lo, *ctl_width = in.ctl_width,
+                 *ref = in.ref, *track_weight = in.track_weight, *terminal_weight = in.terminal_weight, *limit_lo = in.limit_lo,
+                 *limit_hi = in.limit_hi, *move_weight = in.move_weight, *previous = in.previous, *z0 = in.z0;
     if (n_draws <= 0 || n_states <= 0 || n_steps < 0 || n_forcing_cols < 0 || n_norm_forcing < 0 || n_norm < n_norm_forcing ||
         n_forcing_factors < 0 || n_factors < n_forcing_factors || n_spline_rows < 0 || n_bern_rows < 0 || n_entries < 0 ||
         n_coef < n_states || !entry_begin || !entry_count || !constant || !coef || !y0 || !box || !seg_first || !norm_control ||
         !ctl_lo || !ctl_width || !ref || !track_weight || !terminal_weight || !limit_lo || !limit_hi || !move_weight ||
-        !previous || !z0 || !z || !cost || !cost_start || !status || !iterations || !descent_steps || !best_start || !members ||
-        !first_saturation || (first_F == nullptr) != (first_g == nullptr) || (first_F == nullptr) != (first_H == nullptr) ||
+        !previous || !z0 ||
         (n_norm > 0 && (!norm_src || !norm_lo || !norm_span)) || (n_factors > 0 && (!fac_norm || !fac_kind || !fac_row || !fac_degree)) ||
         (n_entries > 0 && !entries) || (n_spline_rows > 0 && !spline_table) || (n_bern_rows > 0 && !bern_table) ||
         (n_forcing_cols > 0 && n_steps > 0 && !forcing))
@@ -560,8 +636,8 @@ extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int6
         return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_steps) + " steps, a call handles at most " + std::to_string(CTL_MAX_STEPS));
     if (!(h > 0) || !std::isfinite(h)) return fail(ctx, FOKL_ERR_ARG, who + "h must be positive and finite");
 
-    SimSystem sys{};
-    int n_bern_factors = 0;
+    sys = SimSystem{};
+    n_bern_factors = 0;
     if (const int refused = sim_plan(ctx, who, n_states, h, n_forcing_cols, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
                                      n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows,
                                      n_bern_rows, n_entries, entries, entry_begin, entry_count, constant, n_coef, box, sys,
@@ -577,7 +653,7 @@ extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int6
     for (int k = 1; k < n_segments; ++k)
         if (seg_first[k] <= seg_first[k - 1] || seg_first[k] >= n_steps)
             return fail(ctx, FOKL_ERR_ARG, who + "the segments' first steps must increase and lie below the number of steps");
-    CtlProblem cp{};
+    cp = CtlProblem{};
     for (int c = 0; c < n_controls; ++c) {
         if (!std::isfinite(ctl_lo[c]) || !std::isfinite(ctl_width[c]) || !(ctl_width[c] > 0))
             return fail(ctx, FOKL_ERR_ARG, who + "a control's box is empty or not finite");
@@ -638,7 +714,7 @@ extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int6
     for (size_t i = 0; i < (size_t)n_states * n_draws; ++i)
         if (!std::isfinite(y0[i])) return fail(ctx, FOKL_ERR_ARG, who + "y0 is not finite");
     const size_t lds_lane_rows = 2 * ((size_t)1 + n_factors + (n_norm - n_norm_forcing)) + 4 + D;
-    const size_t lds_bytes = lds_lane_rows * SIM_LANES * sizeof(double) + (size_t)n_coef * sizeof(double);
+    lds_bytes = lds_lane_rows * SIM_LANES * sizeof(double) + (size_t)n_coef * sizeof(double);
     if (lds_bytes > SIM_LDS_BUDGET)
         return fail(ctx, FOKL_ERR_ARG, who + "the system needs " + std::to_string(lds_bytes) + " bytes of LDS ((2 x (1 + " +
                                            std::to_string(n_factors) + " factors + " + std::to_string(n_norm - n_norm_forcing) +
@@ -655,37 +731,109 @@ extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int6
     cp.max_iter = max_iter;
     cp.hl = limit_weight;
     cp.tol = tol;
+    return FOKL_OK;
+}
+
+// The system's tables, the problem's and the draws' on the device
+struct CtlDevice {
+    SimTables tab;
+    CtlTables ct;
+    double *coef, *forcing, *y0;
+};
+
+hipError_t ctl_upload(DeviceBuffers &buf, const CtlArgs &in, CtlDevice &d)
+{
+    int *norm_src = nullptr, *fac_norm = nullptr, *fac_row = nullptr, *fac_degree = nullptr, *norm_control = nullptr, *seg = nullptr;
+    int4 *entries = nullptr;
+    double *norm_lo = nullptr, *norm_span = nullptr, *spline = nullptr, *bern = nullptr, *ref = nullptr;
+    const size_t E = (size_t)in.n_draws;
+    hipError_t e;
+#define CTL_UP(call)                                                                                                          \
+    if ((e = (call)) != hipSuccess) return e;
+    CTL_UP(buf.upload(&norm_src, in.norm_src, (size_t)in.n_norm))
+    CTL_UP(buf.upload(&norm_lo, in.norm_lo, (size_t)in.n_norm))
+    CTL_UP(buf.upload(&norm_span, in.norm_span, (size_t)in.n_norm))
+    CTL_UP(buf.upload(&fac_norm, in.fac_norm, (size_t)in.n_factors))
+    CTL_UP(buf.upload(&fac_row, in.fac_row, (size_t)in.n_factors))
+    CTL_UP(buf.upload(&fac_degree, in.fac_degree, (size_t)in.n_factors))
+    CTL_UP(buf.upload(&entries, in.entries, (size_t)in.n_entries))
+    CTL_UP(buf.upload(&spline, in.spline_table, (size_t)in.n_spline_rows * SIM_PIECES * 4))
+    CTL_UP(buf.upload(&bern, in.bern_table, (size_t)in.n_bern_rows * SIM_BERN_WIDTH))
+    CTL_UP(buf.upload(&norm_control, in.norm_control, (size_t)in.n_norm_forcing))
+    CTL_UP(buf.upload(&seg, in.seg_first, (size_t)in.n_segments))
+    CTL_UP(buf.upload(&ref, in.ref, (size_t)in.n_states * (in.n_steps + 1)))
+    CTL_UP(buf.upload(&d.coef, in.coef, E * in.n_coef))
+    CTL_UP(buf.upload(&d.forcing, in.forcing, (size_t)in.n_steps * in.n_forcing_cols))
+    CTL_UP(buf.upload(&d.y0, in.y0, E * in.n_states))
+#undef CTL_UP
+    d.tab = SimTables{norm_src, norm_lo, norm_span, fac_norm, fac_row, fac_degree, entries, spline, bern};
+    d.ct = CtlTables{norm_control, seg, ref};
+    return hipSuccess;
+}
+
+}  // namespace
+
+extern "C" int fokl_control_report(const fokl_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return fail(nullptr, FOKL_ERR_ARG, "fokl_control_report: null argument");
+    std::memcpy(out, ctx->control_report, sizeof ctx->control_report);
+    return FOKL_OK;
+}
+
+extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
+                                  const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
+                                  const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
+                                  const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
+                                  const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
+                                  const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
+                                  const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
+                                  const double *y0, const double *box, int n_controls, int n_segments,
+                                  const int32_t *seg_first, const int32_t *norm_control, const double *ctl_lo,
+                                  const double *ctl_width, const double *ref, const double *track_weight,
+                                  const double *terminal_weight, const double *limit_lo, const double *limit_hi,
+                                  double limit_weight, const double *move_weight, const double *previous, int has_previous,
+                                  int n_starts, const double *z0, int max_iter, double tol, double *z, double *cost,
+                                  double *cost_start, int32_t *status, int32_t *iterations, int32_t *descent_steps,
+                                  int32_t *best_start,
+                                  double *members, int32_t *first_saturation, double *first_F, double *first_g,
+                                  double *first_H)
+{
+    const std::string who = "fokl_control_solve: ";
+    if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
+    std::memset(ctx->control_report, 0, sizeof ctx->control_report);
+    if (!z || !cost || !cost_start || !status || !iterations || !descent_steps || !best_start || !members || !first_saturation ||
+        (first_F == nullptr) != (first_g == nullptr) || (first_F == nullptr) != (first_H == nullptr))
+        return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
+    const CtlArgs args{n_draws, n_states, n_steps, h, n_forcing_cols, forcing, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
+                       n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows, spline_table,
+                       n_bern_rows, bern_table, n_entries, entries, entry_begin, entry_count, constant, n_coef, coef, y0, box,
+                       n_controls, n_segments, seg_first, norm_control, ctl_lo, ctl_width, ref, track_weight, terminal_weight,
+                       limit_lo, limit_hi, limit_weight, move_weight, previous, has_previous, n_starts, z0, max_iter, tol};
+    SimSystem sys{};
+    CtlProblem cp{};
+    size_t lds_bytes = 0;
+    int n_bern_factors = 0;
+    if (const int refused = ctl_plan(ctx, who, args, sys, cp, lds_bytes, n_bern_factors)) return refused;
+    const int D = cp.D;
+    const int64_t n_points = n_steps + 1;
 
     const size_t E = (size_t)n_draws, B = E * n_starts;
     const int poll = std::max(0, env_int("FOKL_CONTROL_POLL", 8));    // read the statuses every `poll` launches; 0: never
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DeviceBuffers buf;
-    int *d_norm_src = nullptr, *d_fac_norm = nullptr, *d_fac_row = nullptr, *d_fac_degree = nullptr, *d_norm_control = nullptr,
-        *d_seg = nullptr, *d_status = nullptr, *d_iterations = nullptr, *d_descent = nullptr, *d_work = nullptr, *d_first = nullptr;
-    int4 *d_entries = nullptr;
-    double *d_norm_lo = nullptr, *d_norm_span = nullptr, *d_spline = nullptr, *d_bern = nullptr, *d_coef = nullptr,
-           *d_forcing = nullptr, *d_y0 = nullptr, *d_ref = nullptr, *d_z = nullptr, *d_cost = nullptr, *d_cost_start = nullptr,
-           *d_fF = nullptr, *d_fg = nullptr, *d_fH = nullptr, *d_zbest = nullptr, *d_members = nullptr;
+    int *d_status = nullptr, *d_iterations = nullptr, *d_descent = nullptr, *d_work = nullptr, *d_first = nullptr;
+    double *d_z = nullptr, *d_cost = nullptr, *d_cost_start = nullptr, *d_fF = nullptr, *d_fg = nullptr, *d_fH = nullptr,
+           *d_zbest = nullptr, *d_members = nullptr;
+    CtlDevice dev{};
+    HIP_TRY(ctx, ctl_upload(buf, args, dev));
+    const SimTables &tab = dev.tab;
+    const CtlTables &ct = dev.ct;
+    double *d_coef = dev.coef, *d_forcing = dev.forcing, *d_y0 = dev.y0;
     std::vector<double> z_start(B * D);
     for (size_t b = 0; b < B; ++b) std::memcpy(z_start.data() + b * D, z0 + (b % n_starts) * D, D * sizeof(double));
     std::vector<int32_t> h_status(B, -1), h_zero((size_t)max_iter + 1, 0);
     std::vector<double> h_nan(B, NAN);
-    HIP_TRY(ctx, buf.upload(&d_norm_src, norm_src, (size_t)n_norm));
-    HIP_TRY(ctx, buf.upload(&d_norm_lo, norm_lo, (size_t)n_norm));
-    HIP_TRY(ctx, buf.upload(&d_norm_span, norm_span, (size_t)n_norm));
-    HIP_TRY(ctx, buf.upload(&d_fac_norm, fac_norm, (size_t)n_factors));
-    HIP_TRY(ctx, buf.upload(&d_fac_row, fac_row, (size_t)n_factors));
-    HIP_TRY(ctx, buf.upload(&d_fac_degree, fac_degree, (size_t)n_factors));
-    HIP_TRY(ctx, buf.upload(&d_entries, entries, (size_t)n_entries));
-    HIP_TRY(ctx, buf.upload(&d_spline, spline_table, (size_t)n_spline_rows * SIM_PIECES * 4));
-    HIP_TRY(ctx, buf.upload(&d_bern, bern_table, (size_t)n_bern_rows * SIM_BERN_WIDTH));
-    HIP_TRY(ctx, buf.upload(&d_norm_control, norm_control, (size_t)n_norm_forcing));
-    HIP_TRY(ctx, buf.upload(&d_seg, seg_first, (size_t)n_segments));
-    HIP_TRY(ctx, buf.upload(&d_ref, ref, (size_t)n_states * n_points));
-    HIP_TRY(ctx, buf.upload(&d_coef, coef, E * n_coef));
-    HIP_TRY(ctx, buf.upload(&d_forcing, forcing, (size_t)n_steps * n_forcing_cols));
-    HIP_TRY(ctx, buf.upload(&d_y0, y0, E * n_states));
     HIP_TRY(ctx, buf.upload(&d_z, z_start.data(), B * D));
     HIP_TRY(ctx, buf.upload(&d_status, h_status.data(), B));
     HIP_TRY(ctx, buf.upload(&d_iterations, h_status.data(), B));
@@ -702,8 +850,6 @@ extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int6
     HIP_TRY(ctx, buf.get(&d_zbest, E * D));
     HIP_TRY(ctx, buf.get(&d_members, E * n_states * n_points));
     HIP_TRY(ctx, buf.get(&d_first, E));
-    const SimTables tab{d_norm_src, d_norm_lo, d_norm_span, d_fac_norm, d_fac_row, d_fac_degree, d_entries, d_spline, d_bern};
-    const CtlTables ct{d_norm_control, d_seg, d_ref};
 
     double terms_per_stage = 0.0;
     for (int k = 0; k < n_states; ++k) terms_per_stage += sys.entry_count[k];

@@ -84,6 +84,21 @@ extern "C" int fokl_control_solve(fokl_ctx *, int, int, int64_t, double, int, co
 }
 extern "C" int fokl_control_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor does the pooled solve over all draws (fokl_control_pooled_device.inc); its statement is dynamics.control_pooled_host.
+extern "C" int fokl_control_pooled_solve(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
+                                         const double *, const double *, int, int, const int32_t *, const int32_t *,
+                                         const int32_t *, const int32_t *, int, const double *, int, const double *, int,
+                                         const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, const double *,
+                                         const double *, const double *, int, int, const int32_t *, const int32_t *,
+                                         const double *, const double *, const double *, const double *, const double *,
+                                         const double *, const double *, double, const double *, const double *, int, int,
+                                         const double *, int, double, const double *, double *, double *, double *, int32_t *,
+                                         int32_t *, int32_t *, int32_t *, double *, int32_t *, double *, double *, double *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_control_pooled_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // The multistart optimiser runs on the device only (fokl_optimize_device.inc on fokl_optimize_core.inc); its statement is
 // optimize.solve_host.
 extern "C" int fokl_model_optimize(fokl_ctx *, int, int, const int32_t *, int, const double *, const double *, int, int,

@@ -126,6 +126,27 @@ One iteration is one tangent pass and one trial pass.  The returned cost is F of
 best start of a draw has the smallest finite cost; every draw's trajectory under its own controls (``mean``, ``bounds``,
 ``members``, ``first_saturation``) is ``simulate_host``'s under ``expand_controls(res, e)``, bit for bit.  The device follows
 the statement operation for operation: the tangent pass agrees bit for bit, whole solves in status, iterations and 1e-9.
+
+``control_pooled(..., draw_weights=None, ...)`` finds ONE control sequence for the whole posterior: it minimises the expected
+cost F(z) = sum_e w_e F_e(z) over the one decision vector z, F_e being exactly ``control``'s cost of draw e and w the
+normalised draw weights (uniform, or for example ``assimilate``'s ``weights``).  A weighted sum of sums of squares is a sum
+of squares again, so projected Gauss-Newton stays exact with g = sum_e w_e g_e and H = sum_e w_e H_e; there is one solve per
+start, not per (draw, start).  ``control_pooled_host`` is its statement in numpy.
+
+  pooled sum      ``pooled_sum(X, w)``, used for F, S (the rounding scale), g, H and the trial costs alike: the draws are cut
+                  into chunks of ``POOL_CHUNK`` = 64 consecutive indices; inside a chunk acc = acc + w_e X_e runs in index
+                  order from 0.0; the chunk sums are then added in chunk order from the first.  A draw with w_e == 0 is
+                  skipped entirely (no multiply, no add), so a collapsed draw of ``assimilate`` (weight 0, possibly NaN
+                  states) cannot poison the sum.  Only + and *, in an order no launch shape changes: the device reproduces
+                  it bit for bit
+  one iteration   steps 1 .. 5 of ``control`` with the pooled F, S, g, H in place of one draw's: the tangent pass of every
+                  draw at the shared z, the pooled sum, the same stop test (a non-finite pooled F or g: status 2), active
+                  set, modified Cholesky and 31 + 31 trial points, the value pass of every draw at every trial point, the
+                  pooled sum of the trial costs, the same Armijo test, the first passing lane
+
+The returned cost is the pooled F of the tangent pass at the returned point, ``cost_draws`` the draws' own costs there
+(cost == pooled_sum(cost_draws, w)); every draw's trajectory under the shared controls is ``simulate_host``'s under
+``expand_controls(res)``, bit for bit.  With one draw the solve is ``control``'s, bit for bit (0.0 + 1.0 X is X).
 """
 import numpy as np
 
@@ -1399,7 +1420,10 @@ def _assemble_control(p, solved, best, members, first):
 
 
 def expand_controls(res, e=None):
-    """The controls of a result as ``forcing`` arrays [steps]: draw e's own (``res.u[e]``), or ``u_mean`` if e is None."""
+    """The controls of a result as ``forcing`` arrays [steps]: draw e's own (``res.u[e]``), or ``u_mean`` if e is None.  A
+    result of ``control_pooled`` has one sequence for all draws (``u_mean`` = ``u``) and none per draw."""
+    if e is not None and res.get('pooled', False):
+        raise ValueError("expand_controls: a pooled result holds one control sequence for all draws (e=None), none per draw")
     u = res['u_mean'] if e is None else res['u'][e]
     n_steps = len(res['t']) - 1
     seg_of = np.searchsorted(res['segment_first'], np.arange(n_steps), side='right') - 1
@@ -1460,3 +1484,230 @@ def control_host(models, states, inputs, controls=None, forcing=None, y0=None, t
 
 control.__doc__ += _CONTROL_SIGNATURE
 control_host.__doc__ += _CONTROL_SIGNATURE
+
+
+# ---------------------------------------------------------------------------------------------------------
+# control_pooled: one control sequence for the whole posterior, the expected cost over the draws (module docstring)
+# ---------------------------------------------------------------------------------------------------------
+
+POOL_CHUNK = 64                           # draws per chunk of the pooled sum
+
+
+def pooled_sum(X, w):
+    """sum_e w[e] X[e] over the first axis in the one order the module docstring states: chunks of ``POOL_CHUNK``
+    consecutive draws, inside a chunk acc = acc + w_e X_e in index order from 0.0, the chunk sums added in chunk order from
+    the first; a draw with w_e == 0 is skipped entirely.  X [E, ...], w [E] -> [...]."""
+    X, w = np.asarray(X, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    if w.ndim != 1 or X.ndim < 1 or X.shape[0] != w.shape[0]:
+        raise ValueError(f"pooled_sum: X must hold one row per weight ({list(w.shape)}), got shape {list(X.shape)}")
+    total = None
+    with np.errstate(all='ignore'):
+        for begin in range(0, w.shape[0], POOL_CHUNK):
+            acc = np.zeros(X.shape[1:])
+            for e in range(begin, min(begin + POOL_CHUNK, w.shape[0])):
+                if w[e] == 0:
+                    continue
+                acc = acc + w[e] * X[e]
+            total = acc if total is None else total + acc
+    return np.zeros(X.shape[1:]) if total is None else total
+
+
+def _pool_weights(draw_weights, E):
+    """The normalised draw weights [E] (w / w.sum(); uniform for None) or a refusal that names the limit."""
+    if draw_weights is None:
+        w = np.ones(E)
+    else:
+        w = np.asarray(draw_weights, dtype=np.float64)
+        if w.shape != (E,):
+            raise ValueError(f"draw_weights must be [{E}] numbers, one per draw, got shape {list(w.shape)}")
+        if not np.isfinite(w).all() or np.any(w < 0):
+            raise ValueError("draw_weights must be non-negative finite numbers (a negative or non-finite weight is refused)")
+        if not np.any(w > 0):
+            raise ValueError("draw_weights are all zero: at least one draw must weigh something")
+    return np.ascontiguousarray(w / w.sum())
+
+
+def _prepare_control_pooled(models, states, inputs, controls, forcing, y0, t, draws, bounds, segments, control_bounds, targets,
+                            weights, terminal, limits, limit_weight, move_weight, previous, init, starts, max_iter, tol,
+                            draw_weights, keep):
+    p = _prepare_control(models, states, inputs, controls, forcing, y0, t, draws, bounds, segments, control_bounds, targets,
+                         weights, terminal, limits, limit_weight, move_weight, previous, init, starts, max_iter, tol, keep)
+    p.update(pool_w=_pool_weights(draw_weights, p['E']), pool_given=draw_weights is not None)
+    return p
+
+
+def _control_pooled_solve_host(p):
+    """Every start's pooled solve -> dict(z [S, D], cost, cost_start, status, iterations, descent_steps [S] and, with
+    max_iter == 0, the first tangent pass: pooled F [S], g [S, D], H [S, D, D] and the draws' own F_draws [S, E], g_draws
+    [S, E, D], H_draws [S, E, D, D]; NaN for a draw of weight 0, which is never evaluated)."""
+    E, S, D, max_iter, tol, w = p['E'], p['starts'], p['D'], p['max_iter'], p['tol'], p['pool_w']
+    live = np.flatnonzero(w != 0)
+    z = np.ascontiguousarray(p['z0'].T)                               # [D, S]
+    status = np.full(S, -1, dtype=np.int32)
+    iterations, descent = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+    cost, cost_start = np.full(S, np.nan), np.full(S, np.nan)
+    first_pass = None
+
+    def per_draw(values, n):
+        """[..., live x n] as _control_pass returns it (draw-major) -> [E, ..., n], NaN where the draw weighs nothing"""
+        out = np.full((E,) + values.shape[:-1] + (n,), np.nan)
+        out[live] = np.moveaxis(values.reshape(values.shape[:-1] + (live.size, n)), -2, 0)
+        return out
+
+    for it in range(max_iter + 1):
+        idx = np.flatnonzero(status < 0)
+        n = idx.size
+        if n == 0:
+            break
+        zi = z[:, idx]
+        out = _control_pass(p, np.ascontiguousarray(np.tile(zi, (1, live.size))), np.repeat(live, n), tangents=True)
+        parts = {key: per_draw(out[key], n) for key in ('F', 'noise', 'g', 'H')}
+        F, noise, g, H = (pooled_sum(parts[key], w) for key in ('F', 'noise', 'g', 'H'))
+        if it == 0:
+            cost_start[idx] = F
+            first_pass = dict(F=F.copy(), g=g.T.copy(), H=H.transpose(2, 0, 1).copy(), F_draws=parts['F'].T.copy(),
+                              g_draws=parts['g'].transpose(2, 0, 1).copy(), H_draws=parts['H'].transpose(3, 0, 1, 2).copy())
+        cost[idx] = F
+        with np.errstate(all='ignore'):
+            finite = np.isfinite(F) & np.isfinite(g).all(axis=0)
+            pg = np.zeros(n)
+            for d in range(D):
+                pg = np.fmax(pg, np.abs(_clip01(zi[d] - g[d]) - zi[d]))
+        code = np.where(~finite, NON_FINITE, np.where(pg <= tol, CONVERGED, ITERATION_LIMIT if it == max_iter else -1))
+        stopped = code >= 0
+        status[idx[stopped]], iterations[idx[stopped]] = code[stopped], it
+        go = np.flatnonzero(~stopped)
+        if go.size == 0:
+            continue
+        idx, zi, F, g, H, noise = idx[go], zi[:, go], F[go], g[:, go], H[:, :, go], noise[go]
+        n = idx.size
+        with np.errstate(all='ignore'):
+            active = ((zi <= 0.0) & (g > 0)) | ((zi >= 1.0) & (g < 0))
+            direction = _control_direction(H, g, active)
+            both = np.stack([direction, -g], axis=1)                                              # [D, 2, n]
+            trial = _clip01(zi[:, np.newaxis, np.newaxis, :] + _TRIAL_ALPHA[np.newaxis, np.newaxis, :, np.newaxis] *
+                            both[:, :, np.newaxis, :])                                            # [D, 2, 31, n]
+            m = 2 * CONTROL_TRIALS * n
+            flat = trial.reshape(D, m)
+            Ft_draws = per_draw(_control_pass(p, np.ascontiguousarray(np.tile(flat, (1, live.size))), np.repeat(live, m))['F'], m)
+            Ft = pooled_sum(Ft_draws, w).reshape(2, CONTROL_TRIALS, n)
+            step = trial - zi[:, np.newaxis, np.newaxis, :]
+            slope, moved = np.zeros((2, CONTROL_TRIALS, n)), np.zeros((2, CONTROL_TRIALS, n), dtype=bool)
+            for d in range(D):
+                slope = slope + g[d] * step[d]
+                moved |= np.abs(step[d]) > 0
+            ok = moved & (Ft <= (F + ARMIJO * np.where(slope < 0, slope, 0.0)) + NOISE * noise)
+        ok = ok.reshape(2 * CONTROL_TRIALS, n)
+        any_ok = ok.any(axis=0)
+        chosen = np.argmax(ok, axis=0)                                # the first Newton lane, else the first steepest-descent lane
+        taken = trial.reshape(D, 2 * CONTROL_TRIALS, n)[:, chosen, np.arange(n)]
+        z[:, idx[any_ok]] = taken[:, any_ok]
+        descent[idx[any_ok & (chosen >= CONTROL_TRIALS)]] += 1
+        status[idx[~any_ok]], iterations[idx[~any_ok]] = STALLED, it
+    res = dict(z=z.T.copy(), cost=cost, cost_start=cost_start, status=status, iterations=iterations, descent_steps=descent)
+    if max_iter == 0:
+        res['first_pass'] = first_pass
+    return res
+
+
+def _run_control_pooled_host(p):
+    solved = _control_pooled_solve_host(p)
+    best = int(_best_start(solved['cost'][np.newaxis], solved['status'][np.newaxis])[0])
+    zb = np.ascontiguousarray(np.repeat(solved['z'][best][:, np.newaxis], p['E'], axis=1))
+    out = _control_pass(p, zb, np.arange(p['E']), record=True)
+    return solved, best, out['members'], out['first'], out['F']
+
+
+def _weighted_band(values, w):
+    """The weighted 2.5 % / 97.5 % quantiles of values [E, ...] over the draws, by ``_assemble_assimilate``'s rule."""
+    live = np.flatnonzero(w > 0)
+    flat = values[live].reshape(live.size, -1)
+    band = np.empty((flat.shape[1], 2))
+    for k in range(flat.shape[1]):
+        order = np.argsort(flat[:, k], kind='stable')
+        cumulative = np.cumsum(w[live][order])
+        cumulative = cumulative / cumulative[-1]
+        for side, level in enumerate((0.025, 0.975)):
+            band[k, side] = flat[order[min(int(np.searchsorted(cumulative, level)), live.size - 1)], k]
+    return band.reshape(values.shape[1:] + (2,))
+
+
+def _assemble_control_pooled(p, solved, best, members, first, cost_draws):
+    E, nc, Kseg, w = p['E'], p['n_controls'], p['segments'], p['pool_w']
+    true_scale = lambda zz: p['ctl_lo'][:, np.newaxis] + zz.reshape(zz.shape[:-1] + (nc, Kseg)) * p['ctl_width'][:, np.newaxis]
+    z = solved['z'][best]
+    u = true_scale(z)
+    with np.errstate(all='ignore'):
+        outside = (members > p['lim_hi'][np.newaxis, :, np.newaxis]) | (members < p['lim_lo'][np.newaxis, :, np.newaxis])
+    violated = outside[:, :, 1:].any(axis=2)                          # the points the cost sees: 1 .. P - 1
+    res = SimulateResult(u=u, z=z.reshape(nc, Kseg), cost=float(solved['cost'][best]), status=int(solved['status'][best]),
+                         iterations=int(solved['iterations'][best]), descent_steps=int(solved['descent_steps'][best]),
+                         cost_start=float(solved['cost_start'][best]), best_start=int(best), u_mean=u, cost_draws=cost_draws,
+                         draw_weights=w, t=p['T'], mean=pooled_sum(members, w), first_saturation=first, violated=violated,
+                         violation_share=pooled_sum(violated.astype(np.float64), w), controls=list(p['controls']),
+                         states=list(p['states']), segment_first=p['seg_first'].astype(np.int64), pooled=True)
+    if p['pool_given']:
+        res['bounds'] = _weighted_band(members, w)
+    elif E >= 2:
+        cut = bounds_cut(E)
+        ms = np.sort(members, axis=0)
+        res['bounds'] = np.stack([ms[cut], ms[E - cut]], axis=-1)
+    if p['want_members']:
+        res['members'] = members
+    if p['want_all']:
+        res.update(u_all=true_scale(solved['z']), cost_all=solved['cost'], status_all=solved['status'],
+                   iterations_all=solved['iterations'], descent_steps_all=solved['descent_steps'])
+    if 'first_pass' in solved:
+        res['first_pass'] = solved['first_pass']
+    return res
+
+
+_CONTROL_POOLED_SIGNATURE = """
+    Every argument shared with ``control`` means what it means there (its docstring).
+    draw_weights : None (uniform) or [E] non-negative numbers, for example ``assimilate``'s ``weights``; normalised as
+                  w / w.sum().  A draw of weight 0 is never evaluated by the solver.  A wrong length, a negative or non-finite
+                  weight and all weights zero are refused
+    starts      : ``control``'s starts; there are ``starts`` solves in all
+    max_iter=0  : returns ``first_pass``: the pooled F [S], g [S, D], H [S, D, D] and the draws' own F_draws [S, E], g_draws
+                  [S, E, D], H_draws [S, E, D, D] (NaN for a draw of weight 0)
+
+    Returns a ``SimulateResult``: of the best start u [n_controls, K] (true scale), z, cost, cost_start, status, iterations,
+    descent_steps and best_start (scalars; the best start has the smallest finite cost); u_mean = u, so
+    ``expand_controls(res)`` gives the ``forcing`` arrays (``expand_controls(res, e)`` is refused: there is no per-draw
+    sequence); cost_draws [E], every draw's own cost F_e at u; draw_weights [E] as normalised; t, first_saturation [E] and
+    with keep='members' members [E, n_states, P]: every draw's trajectory under the shared u; mean [n_states, P] =
+    ``pooled_sum(members, w)``; bounds [n_states, P, 2]: ``evaluate``'s order statistics for uniform weights (E >= 2), else
+    the weighted 2.5 % / 97.5 % quantiles over the draws of positive weight; violated [E, n_states] bool: some point 1 .. P - 1
+    of the trajectory lies outside ``limits``; violation_share [n_states]: the weight of those draws; u_all, cost_all,
+    status_all, iterations_all, descent_steps_all [S, ...] with keep='all'."""
+
+
+def control_pooled(models, states, inputs, controls=None, forcing=None, y0=None, t=None, draws=None, bounds=None, segments=8,
+                   control_bounds=None, targets=None, weights=None, terminal=None, limits=None, limit_weight=1e3,
+                   move_weight=None, previous=None, init=None, starts=1, max_iter=60, tol=1e-10, draw_weights=None, keep=None,
+                   device=None):
+    """One control sequence for the whole posterior: the expected cost sum_e w_e F_e(z) of ``control``'s cost over the draws,
+    minimised over one decision vector, on the device (module docstring).
+
+    device      : device index (default: the process's device, as for ``fit``), a backend or a ``_capi.DeviceContext``"""
+    p = _prepare_control_pooled(models, states, inputs, controls, forcing, y0, t, draws, bounds, segments, control_bounds,
+                                targets, weights, terminal, limits, limit_weight, move_weight, previous, init, starts, max_iter,
+                                tol, draw_weights, keep)
+    ctx = _device_context(device)
+    return _assemble_control_pooled(p, *ctx.control_pooled_solve(p))
+
+
+def control_pooled_host(models, states, inputs, controls=None, forcing=None, y0=None, t=None, draws=None, bounds=None,
+                        segments=8, control_bounds=None, targets=None, weights=None, terminal=None, limits=None,
+                        limit_weight=1e3, move_weight=None, previous=None, init=None, starts=1, max_iter=60, tol=1e-10,
+                        draw_weights=None, keep=None):
+    """``control_pooled`` in numpy on this host, vectorised over starts, draws and trial points: the statement the kernels are
+    tested against (module docstring), not a fallback.  Same arguments, same result fields."""
+    p = _prepare_control_pooled(models, states, inputs, controls, forcing, y0, t, draws, bounds, segments, control_bounds,
+                                targets, weights, terminal, limits, limit_weight, move_weight, previous, init, starts, max_iter,
+                                tol, draw_weights, keep)
+    return _assemble_control_pooled(p, *_run_control_pooled_host(p))
+
+
+control_pooled.__doc__ += _CONTROL_POOLED_SIGNATURE
+control_pooled_host.__doc__ += _CONTROL_POOLED_SIGNATURE

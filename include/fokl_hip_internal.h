@@ -38,6 +38,7 @@
  *   fokl_simulate_ensemble / fokl_simulate_report
  *   fokl_assimilate_ensemble / fokl_assimilate_report / fokl_assimilate_rng
  *   fokl_control_solve / fokl_control_report
+ *   fokl_control_pooled_solve / fokl_control_pooled_report
  *                              a system of fitted models, wired by names, integrated for every posterior draw at once
  *                              (fokl_gpy_amd/dynamics.py), and what its last call ran
  *   fokl_embedded_hmc / fokl_embedded_rng
@@ -1289,6 +1290,62 @@ int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps
  *   out[6]  spline factors     out[7]  Bernoulli factors
  */
 int fokl_control_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* One control sequence for the whole posterior (csrc/fokl_control_pooled_device.inc; dynamics.py)           */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_CONTROL_POOLED_REPORT_LEN 15
+#define FOKL_CONTROL_POOL_CHUNK 64
+
+/*
+ * One bounded least-squares solve per start over ALL draws: the expected cost sum_e w_e F_e(z) of fokl_control_solve's cost,
+ * minimised over one decision vector by the same projected Gauss-Newton iteration with the pooled F, noise, g and H in place
+ * of one draw's.  The arithmetic is stated by dynamics.control_pooled_host; every argument up to `tol` means what it means
+ * for fokl_control_solve.  Host memory, row-major:
+ *   draw_weights [n_draws]: used as given (the caller normalises them to sum 1); a draw of weight 0 is never evaluated
+ *   z [n_starts, D], cost / cost_start [n_starts], status / iterations / descent_steps [n_starts] int32; best_start [1] int32
+ *   members [n_draws, n_states, n_steps + 1], first_saturation [n_draws] int32: every draw's trajectory under the best
+ *          start's controls; cost_draws [n_draws]: every draw's own cost there (one value pass, weight 0 included)
+ *   first_pooled [n_starts, n], first_rows [n_starts, n_draws, n] with n = 2 + D + D D: the pooled tangent pass of iteration
+ *          0 and the draws' own, each row F, noise, g [D], H [D, D] (entry [d][d'] as lane d forms it); the row of a draw of
+ *          weight 0 is NaN; both or none NULL
+ * The pooled sum (dynamics.pooled_sum): chunks of FOKL_CONTROL_POOL_CHUNK consecutive draws, inside a chunk
+ * acc = acc + w_e x_e in index order from 0.0, the chunk sums added in chunk order from the first, a draw of weight 0
+ * skipped.  One iteration is six launches on the context's stream (tangent pass per (draw, start), chunk sums, Newton step
+ * per start, value pass per (draw, start) with lane = trial point, chunk sums, Armijo decision per start); a finished start
+ * returns at once in each.  The statuses are read back every FOKL_CONTROL_POLL iterations (environment, default 8; 0:
+ * never), which changes no result.  No atomics: the same arguments give the same bits.
+ * Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched): everything fokl_control_solve refuses (the
+ * LDS bytes of the per-draw kernels are its formula); a weight that is negative or not finite, weights that sum to zero;
+ * a workspace of n_draws x n_starts x (n + 64) x 8 bytes plus (n + 64) x 8 per (start, chunk) beyond the device's free
+ * memory, of which FOKL_CONTROL_POOLED_FREE_BYTES (environment) caps what counts.  Kernel time: FOKL_K_INTEGRATE.  Blocking.
+ */
+int fokl_control_pooled_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
+                              const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
+                              const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
+                              const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
+                              const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
+                              const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
+                              const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
+                              const double *y0, const double *box, int n_controls, int n_segments, const int32_t *seg_first,
+                              const int32_t *norm_control, const double *ctl_lo, const double *ctl_width, const double *ref,
+                              const double *track_weight, const double *terminal_weight, const double *limit_lo,
+                              const double *limit_hi, double limit_weight, const double *move_weight, const double *previous,
+                              int has_previous, int n_starts, const double *z0, int max_iter, double tol,
+                              const double *draw_weights, double *z, double *cost, double *cost_start, int32_t *status,
+                              int32_t *iterations, int32_t *descent_steps, int32_t *best_start, double *members,
+                              int32_t *first_saturation, double *cost_draws, double *first_pooled, double *first_rows);
+
+/*
+ * The last fokl_control_pooled_solve call on `ctx`, out [FOKL_CONTROL_POOLED_REPORT_LEN] (host values, no launch); zeros
+ * after a call that was refused or failed:
+ *   out[0]  NS: the kernel instance (states)     out[1]  draws     out[2]  starts     out[3]  D     out[4]  chunks
+ *   out[5]  dynamic LDS bytes of the per-draw kernels     out[6]  ... of the step kernel
+ *   out[7]  iterations queued     out[8]  iterations that found a running start     out[9]  launches per iteration (6)
+ *   out[10 .. 14]  with kernel timing enabled, nanoseconds in the tangent, chunk-sum (both), step, trial and accept launches
+ */
+int fokl_control_pooled_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* What the fit kernels ran: K1 basis build, K2 Gram block, K3 residual moments (csrc/fokl_hip.hip)          */
