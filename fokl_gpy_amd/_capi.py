@@ -227,6 +227,12 @@ SIGNATURES = {
                                           c_vp, c_int, c_int, c_vp, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                           c_vp, c_vp, c_vp, c_vp]),
     'fokl_control_pooled_report': (c_int, [c_vp, c_vp]),
+    'fokl_control_cvar_solve': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
+                                        c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
+                                        c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp,
+                                        c_vp, c_int, c_int, c_vp, c_int, c_dbl, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_control_cvar_report': (c_int, [c_vp, c_vp]),
     'fokl_assimilate_rng': (c_int, [ctypes.c_uint32, c_vp, c_int, ctypes.c_uint32, c_int, c_int, c_vp]),
     'fokl_model_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_dbl,
                                     c_int, c_dbl, c_vp, c_vp, c_vp, c_vp]),
@@ -2456,6 +2462,82 @@ class DeviceContext:
         self._ck(self._lib.fokl_control_pooled_report(self._h, _ptr(out)))
         keys = ('NS', 'draws', 'starts', 'D', 'chunks', 'lds_bytes', 'step_lds_bytes', 'iterations_queued', 'iterations_with_work',
                 'launches_per_iteration', 'tangent_ns', 'chunk_ns', 'step_ns', 'trial_ns', 'accept_ns')
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def control_cvar_solve(self, p):
+        """fokl_control_cvar_solve for a system prepared as for ``control_pooled_solve`` with ``alpha``, ``smoothing`` and
+        ``epsilon`` (None: relative) -> what ``control_pooled_solve`` returns, ``solved`` also holding ``epsilon`` (as used)
+        and, for max_iter == 0, ``first_pass``: phi, a [S], g [S, D], H [S, D, D], q, c [S, E] and the draws' own F_draws,
+        g_draws, H_draws -- for alpha == 0 ``control_pooled_solve``'s."""
+        K, E, P, S, D = int(p['K']), int(p['E']), int(p['n_steps']) + 1, int(p['starts']), int(p['D'])
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
+        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
+        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
+        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
+        coef, y0, box = f64(np.asarray(p['coef']).T), f64(p['y0']), f64(p['box'])
+        seg_first, norm_control = i32(p['seg_first']), i32(p['norm_control'])
+        lo, width, ref, z0, w = f64(p['ctl_lo']), f64(p['ctl_width']), f64(p['ref']), f64(p['z0']), f64(p['pool_w'])
+        wt, term, lim_lo, lim_hi, move, prev = (f64(p[key]) for key in ('wt', 'term', 'lim_lo', 'lim_hi', 'move', 'prev'))
+        nc = int(p['n_controls'])
+        if coef.ndim != 2 or coef.shape[0] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
+                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
+                not (norm_src.shape == norm_lo.shape == norm_span.shape) or \
+                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
+                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21 or seg_first.ndim != 1 or \
+                D != nc * seg_first.shape[0] or norm_control.shape != (int(p['n_norm_forcing']),) or lo.shape != (nc,) or \
+                width.shape != (nc,) or move.shape != (nc,) or prev.shape != (nc,) or ref.shape != (K, P) or \
+                not (wt.shape == term.shape == lim_lo.shape == lim_hi.shape == (K,)) or z0.shape != (S, D) or w.shape != (E,):
+            raise ValueError("control_cvar_solve: array shapes disagree")
+        n = 2 + D + D * D
+        alpha = float(p['alpha'])
+        epsilon = float('nan') if p['epsilon'] is None else float(p['epsilon'])
+        z = np.empty((S, D), dtype=np.float64)
+        cost, cost_start = np.empty(S, dtype=np.float64), np.empty(S, dtype=np.float64)
+        status, iterations, descent = (np.empty(S, dtype=np.int32) for _ in range(3))
+        best, first = np.empty(1, dtype=np.int32), np.empty(E, dtype=np.int32)
+        members, cost_draws = np.empty((E, K, P), dtype=np.float64), np.empty(E, dtype=np.float64)
+        used = np.full(1, np.nan)
+        want_first = int(p['max_iter']) == 0
+        pooled = np.empty((S, n), dtype=np.float64) if want_first else None
+        rows = np.empty((S, E, n), dtype=np.float64) if want_first else None
+        fa = np.empty(S, dtype=np.float64) if want_first else None
+        fq = np.empty((S, E), dtype=np.float64) if want_first else None
+        fc = np.empty((S, E), dtype=np.float64) if want_first else None
+        self._ck(self._lib.fokl_control_cvar_solve(
+            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
+            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
+            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
+            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[1], _ptr(coef), _ptr(y0),
+            _ptr(box), nc, seg_first.shape[0], _ptr(seg_first), _ptr(norm_control), _ptr(lo), _ptr(width), _ptr(ref), _ptr(wt),
+            _ptr(term), _ptr(lim_lo), _ptr(lim_hi), float(p['hl']), _ptr(move), _ptr(prev), int(bool(p['has_previous'])), S,
+            _ptr(z0), int(p['max_iter']), float(p['tol']), _ptr(w), alpha, float(p['smoothing']), epsilon, _ptr(z), _ptr(cost),
+            _ptr(cost_start), _ptr(status), _ptr(iterations), _ptr(descent), _ptr(best), _ptr(members), _ptr(first),
+            _ptr(cost_draws), _ptr(used), _ptr(pooled), _ptr(rows), _ptr(fa), _ptr(fq), _ptr(fc)))
+        solved = dict(z=z, cost=cost, cost_start=cost_start, status=status, iterations=iterations, descent_steps=descent,
+                      epsilon=float(used[0]))
+        if want_first:
+            parts = dict(g=pooled[:, 2:2 + D].copy(), H=pooled[:, 2 + D:].reshape(S, D, D).copy(), F_draws=rows[:, :, 0].copy(),
+                         g_draws=rows[:, :, 2:2 + D].copy(), H_draws=rows[:, :, 2 + D:].reshape(S, E, D, D).copy())
+            if alpha == 0:
+                solved['first_pass'] = dict(F=pooled[:, 0].copy(), **parts)
+            else:
+                solved['first_pass'] = dict(phi=pooled[:, 0].copy(), a=fa, q=fq, c=fc, **parts)
+        return solved, int(best[0]), members, first, cost_draws
+
+    def control_cvar_report(self):
+        """What the last ``control_cvar_solve`` with alpha > 0 on this context ran (fokl_control_cvar_report; host values, no
+        launch): ``NS``, ``draws``, ``starts``, ``D``, ``chunks`` (of 64 draws), ``lds_bytes`` of the per-draw kernels,
+        ``step_lds_bytes``, ``risk_lds_bytes`` and ``risk_threads`` of the risk kernel, ``iterations_queued``,
+        ``iterations_with_work``, ``launches_per_iteration`` (7) and, with kernel timing enabled, the nanoseconds spent in the
+        launches of each kind (``tangent_ns``, ``risk_ns``, ``chunk_ns``, ``step_ns``, ``trial_ns``, ``accept_ns``).  Zeros
+        after a refused call and after alpha == 0 (``control_pooled_report`` has that call)."""
+        out = np.zeros(18, dtype=np.int64)
+        self._ck(self._lib.fokl_control_cvar_report(self._h, _ptr(out)))
+        keys = ('NS', 'draws', 'starts', 'D', 'chunks', 'lds_bytes', 'step_lds_bytes', 'risk_lds_bytes', 'risk_threads',
+                'iterations_queued', 'iterations_with_work', 'launches_per_iteration', 'tangent_ns', 'risk_ns', 'chunk_ns',
+                'step_ns', 'trial_ns', 'accept_ns')
         return dict(zip(keys, (int(v) for v in out)))
 
     @staticmethod

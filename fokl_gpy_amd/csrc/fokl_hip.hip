@@ -103,6 +103,7 @@ struct fokl_ctx {
     int64_t assimilate_report[FOKL_ASSIMILATE_REPORT_LEN] = {};   // ... and the last fokl_assimilate_ensemble call
     int64_t control_report[FOKL_CONTROL_REPORT_LEN] = {};         // ... and the last fokl_control_solve call
     int64_t control_pooled_report[FOKL_CONTROL_POOLED_REPORT_LEN] = {};   // ... and the last fokl_control_pooled_solve call
+    int64_t control_cvar_report[FOKL_CONTROL_CVAR_REPORT_LEN] = {};       // ... and the last fokl_control_cvar_solve call
     // what the last Gram block, residual pass and fokl_build_terms call ran (fokl_fit_report): host values noted while
     // enqueuing, zeros after a call that was refused or failed
     int64_t gram_report[FOKL_GRAM_REPORT_LEN] = {};
@@ -1816,6 +1817,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_assimilate_device.inc"
 #include "fokl_control_device.inc"
 #include "fokl_control_pooled_device.inc"
+#include "fokl_control_cvar_device.inc"
 #include "fokl_probe.inc"
 #include "fokl_dgemm_device.inc"
 #include "fokl_optimize_core.inc"

@@ -99,6 +99,22 @@ extern "C" int fokl_control_pooled_solve(fokl_ctx *, int, int, int64_t, double, 
 }
 extern "C" int fokl_control_pooled_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor does the CVaR solve over all draws (fokl_control_cvar_device.inc); its statement is dynamics.control_cvar_host.
+extern "C" int fokl_control_cvar_solve(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
+                                       const double *, const double *, int, int, const int32_t *, const int32_t *,
+                                       const int32_t *, const int32_t *, int, const double *, int, const double *, int,
+                                       const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, const double *,
+                                       const double *, const double *, int, int, const int32_t *, const int32_t *,
+                                       const double *, const double *, const double *, const double *, const double *,
+                                       const double *, const double *, double, const double *, const double *, int, int,
+                                       const double *, int, double, const double *, double, double, double, double *, double *,
+                                       double *, int32_t *, int32_t *, int32_t *, int32_t *, double *, int32_t *, double *,
+                                       double *, double *, double *, double *, double *, double *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_control_cvar_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // The multistart optimiser runs on the device only (fokl_optimize_device.inc on fokl_optimize_core.inc); its statement is
 // optimize.solve_host.
 extern "C" int fokl_model_optimize(fokl_ctx *, int, int, const int32_t *, int, const double *, const double *, int, int,

@@ -147,6 +147,39 @@ start, not per (draw, start).  ``control_pooled_host`` is its statement in numpy
 The returned cost is the pooled F of the tangent pass at the returned point, ``cost_draws`` the draws' own costs there
 (cost == pooled_sum(cost_draws, w)); every draw's trajectory under the shared controls is ``simulate_host``'s under
 ``expand_controls(res)``, bit for bit.  With one draw the solve is ``control``'s, bit for bit (0.0 + 1.0 X is X).
+
+``control_cvar(..., alpha=0.9, smoothing=0.01, epsilon=None, ...)`` finds ONE control sequence that protects the bad tail of
+the posterior: in place of the expected cost it minimises the smoothed conditional value at risk at level alpha of the
+draws' costs (Rockafellar and Uryasev), with m = 1 - alpha and live draws those with w_e != 0,
+
+    phi(z) = min_a  a + (1 / m) sum_e w_e s_eps(F_e(z) - a),
+    s_eps(t) = 0 for t <= 0,  t^2 / (2 eps) for 0 < t < eps,  t - eps / 2 for t >= eps        (C1)
+
+so cvar - eps / (2 m) <= phi <= cvar.  ``control_cvar_host`` is its statement in numpy; ``cvar_smooth`` is the risk and
+``cvar_exact`` the exact CVaR that is reported.  alpha = 0 IS ``control_pooled`` (q = w, no a, no covariance term), bit for bit.
+
+  finding a       64 bisections, nothing else: lo = min_e F_e - eps and hi = max_e F_e over the live draws; each step
+                  mid = lo + 0.5 (hi - lo), h = pooled_sum(clip((F - mid) / eps, 0, 1), w), lo = mid if h > m, else hi = mid;
+                  a = hi.  The clip is two comparisons
+  soft weights    r_e = clip((F_e - a) / eps, 0, 1); q_e = (w_e r_e) / m (they sum to 1 up to the bisection's resolution);
+                  c_e = w_e / (m eps) where 0 < F_e - a < eps, else 0; a draw of weight 0 has q_e = c_e = 0
+  pooled values   phi = a + pooled_sum(s_eps(F - a), w) / m with s_eps's middle piece as (t t) / (2 eps) and its last as
+                  t - 0.5 eps; S = pooled_sum(S_e, q); g = pooled_sum(g_e, q);
+                  H = pooled_sum(H_e, q) + [Scgg - (Scg Scg') / Sc] with Sc = pooled_sum(1, c), Scg = pooled_sum(g_e, c),
+                  Scgg[d][d'] = pooled_sum(g_ed g_ed', c): the Schur complement of a, the band draws' covariance of gradients
+                  (positive semi-definite), dropped where Sc == 0.  A draw with q_e == 0 (c_e == 0) is skipped in the q-sums
+                  (c-sums), as a draw of weight 0 is.  A live draw with a non-finite F_e makes phi and a NaN and q = c = 0: at z
+                  that is status 2, and a trial lane with such a draw fails its test
+  one iteration   ``control_pooled``'s with phi, S, g, H in place of the pooled F, S, g, H: the same stop test, active set,
+                  modified Cholesky, 31 + 31 trial points, Armijo test (on phi of each trial lane, found with the same
+                  bisection per lane), first passing lane, status codes and best start
+  eps             ``epsilon`` in cost units, or ``smoothing`` x pooled_sum(F_e(z0 of start 0), w); fixed for the whole call and
+                  all starts, so the starts' costs stay comparable
+
+The returned cost is phi of the tangent pass at the returned point; cvar, var, expected_cost, tail_weights and a are formed
+from ``cost_draws`` by ``cvar_exact``, ``pooled_sum`` and ``cvar_smooth``.  Ranking the draws and descending on the
+tail-weighted sum instead (the subgradient route) zigzags across the kinks where draws enter and leave the tail and ends at
+the iteration limit; without the covariance term the smooth iteration does too.
 """
 import numpy as np
 
@@ -1711,3 +1744,282 @@ def control_pooled_host(models, states, inputs, controls=None, forcing=None, y0=
 
 control_pooled.__doc__ += _CONTROL_POOLED_SIGNATURE
 control_pooled_host.__doc__ += _CONTROL_POOLED_SIGNATURE
+
+
+# ---------------------------------------------------------------------------------------------------------
+# control_cvar: one control sequence that protects the bad tail of the posterior (module docstring)
+# ---------------------------------------------------------------------------------------------------------
+
+CVAR_BISECTIONS = 64
+
+
+def cvar_exact(F, w, alpha):
+    """The exact CVaR at level alpha of the costs F [E] under the weights w [E], and the VaR -> (cvar, var).  The live
+    draws (w_e != 0) are ranked by F descending, ties to the lower index; the mass is accumulated sequentially in that
+    order; a draw strictly inside the mass m = 1 - alpha counts fully, the boundary draw (its cost is the VaR) gets m minus
+    the mass before it; the sum is divided by m.  A non-finite live cost gives (NaN, NaN)."""
+    F, w, m = np.asarray(F, dtype=np.float64), np.asarray(w, dtype=np.float64), 1.0 - float(alpha)
+    if F.ndim != 1 or F.shape != w.shape:
+        raise ValueError(f"cvar_exact: F and w must be [E] numbers, got shapes {list(F.shape)} and {list(w.shape)}")
+    if not 0.0 <= float(alpha) < 1.0:
+        raise ValueError(f"alpha must lie in [0, 1), got {alpha}")
+    live = np.flatnonzero(w != 0)
+    if live.size == 0 or not np.isfinite(F[live]).all():
+        return np.nan, np.nan
+    order = live[np.argsort(-F[live], kind='stable')]
+    before, total, var = 0.0, 0.0, F[order[-1]]
+    for e in order:
+        if before + w[e] < m:
+            total = total + w[e] * F[e]
+            before = before + w[e]
+        else:
+            total = total + (m - before) * F[e]
+            var = F[e]
+            break
+    return float(total / m), float(var)
+
+
+def _smooth_plus(t, eps):
+    """s_eps(t): 0 for t <= 0, t^2 / (2 eps) for 0 < t < eps, t - eps / 2 from eps on (C1)"""
+    return np.where(t <= 0.0, 0.0, np.where(t < eps, (t * t) / (2.0 * eps), t - 0.5 * eps))
+
+
+def cvar_smooth(F, w, alpha, eps):
+    """The smoothed Rockafellar-Uryasev risk of the costs F [E, ...] under the weights w [E] (every trailing index is a
+    risk of its own) -> (phi [...], a [...], q [E, ...], c [E, ...]):
+
+        phi = min_a  a + (1 / m) sum_e w_e s_eps(F_e - a),   m = 1 - alpha
+
+    ``a`` by ``CVAR_BISECTIONS`` = 64 bisections of h(a) = pooled_sum(clip((F - a) / eps, 0, 1), w) = m from
+    [min F - eps, max F] over the live draws (mid = lo + 0.5 (hi - lo); lo = mid if h > m, else hi = mid; a = hi);
+    r = clip((F - a) / eps, 0, 1), the soft tail weights q_e = (w_e r_e) / m and the band weights c_e = w_e / (m eps) where
+    0 < F_e - a < eps (else 0).  A draw of weight 0 has q = c = 0 and may hold anything.  A non-finite live cost gives
+    phi = a = NaN and q = c = 0.  Only + - * /, comparisons and ``pooled_sum``."""
+    F, w = np.asarray(F, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    m, eps = 1.0 - float(alpha), float(eps)
+    if w.ndim != 1 or F.ndim < 1 or F.shape[0] != w.shape[0]:
+        raise ValueError(f"cvar_smooth: F must hold one row per weight ({list(w.shape)}), got shape {list(F.shape)}")
+    if not 0.0 < float(alpha) < 1.0:
+        raise ValueError(f"cvar_smooth: alpha must lie in (0, 1), got {alpha} (alpha = 0 is the plain pooled sum)")
+    if not (eps > 0 and np.isfinite(eps)):
+        raise ValueError(f"epsilon must be positive and finite, got {eps}")
+    live = w != 0
+    if not live.any():
+        raise ValueError("cvar_smooth: the weights are all zero")
+    wide = live.reshape((-1,) + (1,) * (F.ndim - 1))
+    with np.errstate(all='ignore'):
+        bad = (wide & ~np.isfinite(F)).any(axis=0)
+        Fs = np.where(wide & ~bad, F, 0.0)                             # what is not live, or sits in a non-finite risk: 0
+        lo = np.min(np.where(wide, Fs, np.inf), axis=0) - eps
+        hi = np.max(np.where(wide, Fs, -np.inf), axis=0)
+        for _ in range(CVAR_BISECTIONS):
+            mid = lo + 0.5 * (hi - lo)
+            above = pooled_sum(_clip01((Fs - mid) / eps), w) > m
+            lo, hi = np.where(above, mid, lo), np.where(above, hi, mid)
+        a = hi
+        t = Fs - a
+        q = np.where(wide & ~bad, (w.reshape(wide.shape) * _clip01(t / eps)) / m, 0.0)
+        c = np.where(wide & ~bad & (t > 0.0) & (t < eps), w.reshape(wide.shape) / (m * eps), 0.0) + np.zeros_like(Fs)
+        phi = a + pooled_sum(_smooth_plus(t, eps), w) / m
+    return np.where(bad, np.nan, phi), np.where(bad, np.nan, a), q, c
+
+
+def _pooled_sum_each(X, q):
+    """``pooled_sum`` with weights of their own per last index: X [E, ..., n], q [E, n] -> [..., n]; where q[e, k] == 0 the
+    draw is skipped for index k (its X may hold anything)."""
+    total = None
+    with np.errstate(all='ignore'):
+        for begin in range(0, q.shape[0], POOL_CHUNK):
+            acc = np.zeros(X.shape[1:])
+            for e in range(begin, min(begin + POOL_CHUNK, q.shape[0])):
+                acc = np.where(q[e] != 0, acc + q[e] * X[e], acc)
+            total = acc if total is None else total + acc
+    return total
+
+
+def _cvar_pooled(parts, w, alpha, eps):
+    """phi, noise, g, H of one tangent pass from the draws' own parts (F, noise [E, n], g [E, D, n], H [E, D, D, n]), and
+    a, q, c (module docstring: the pooled quantities)."""
+    phi, a, q, c = cvar_smooth(parts['F'], w, alpha, eps)
+    noise, g, Hq = (_pooled_sum_each(parts[key], q) for key in ('noise', 'g', 'H'))
+    ge = parts['g']
+    with np.errstate(all='ignore'):
+        sc = _pooled_sum_each(np.ones_like(parts['F']), c)
+        scg = _pooled_sum_each(ge, c)
+        scgg = _pooled_sum_each(ge[:, :, np.newaxis, :] * ge[:, np.newaxis, :, :], c)
+        bracket = scgg - (scg[:, np.newaxis, :] * scg[np.newaxis, :, :]) / sc
+        H = np.where(sc != 0, Hq + bracket, Hq)
+    return phi, noise, g, H, a, q, c
+
+
+def _check_cvar(alpha, smoothing, epsilon):
+    alpha = float(alpha)
+    if not 0.0 <= alpha < 1.0:
+        raise ValueError(f"alpha must lie in [0, 1), got {alpha}")
+    smoothing = float(smoothing)
+    if not (smoothing > 0 and np.isfinite(smoothing)):
+        raise ValueError(f"smoothing must be positive and finite, got {smoothing}")
+    if epsilon is not None:
+        epsilon = float(epsilon)
+        if not (epsilon > 0 and np.isfinite(epsilon)):
+            raise ValueError(f"epsilon must be positive and finite, got {epsilon}")
+    return alpha, smoothing, epsilon
+
+
+def _relative_epsilon(smoothing, cost):
+    """eps = smoothing x the pooled cost of start 0 at its z0, or the refusal"""
+    if not (np.isfinite(cost) and cost != 0):
+        raise ValueError(f"smoothing is relative to the pooled cost at the start, which is {cost}: with a cost of 0 or a "
+                         "non-finite cost there give epsilon= in cost units")
+    return float(smoothing * cost)
+
+
+def _control_cvar_solve_host(p):
+    """Every start's CVaR solve -> ``_control_pooled_solve_host``'s dict with cost = phi, ``epsilon`` and, with
+    max_iter == 0, the first pass: phi, a [S], g [S, D], H [S, D, D], q, c [S, E] and the draws' own parts."""
+    E, S, D, max_iter, tol, w = p['E'], p['starts'], p['D'], p['max_iter'], p['tol'], p['pool_w']
+    alpha, eps = p['alpha'], p['epsilon']
+    live = np.flatnonzero(w != 0)
+    z = np.ascontiguousarray(p['z0'].T)                               # [D, S]
+    status = np.full(S, -1, dtype=np.int32)
+    iterations, descent = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+    cost, cost_start = np.full(S, np.nan), np.full(S, np.nan)
+    first_pass = None
+
+    def per_draw(values, n):
+        out = np.full((E,) + values.shape[:-1] + (n,), np.nan)
+        out[live] = np.moveaxis(values.reshape(values.shape[:-1] + (live.size, n)), -2, 0)
+        return out
+
+    for it in range(max_iter + 1):
+        idx = np.flatnonzero(status < 0)
+        n = idx.size
+        if n == 0:
+            break
+        zi = z[:, idx]
+        out = _control_pass(p, np.ascontiguousarray(np.tile(zi, (1, live.size))), np.repeat(live, n), tangents=True)
+        parts = {key: per_draw(out[key], n) for key in ('F', 'noise', 'g', 'H')}
+        if it == 0 and eps is None:
+            eps = _relative_epsilon(p['smoothing'], float(pooled_sum(parts['F'][:, 0], w)))
+        F, noise, g, H, a, q, c = _cvar_pooled(parts, w, alpha, eps)
+        if it == 0:
+            cost_start[idx] = F
+            first_pass = dict(phi=F.copy(), a=a.copy(), g=g.T.copy(), H=H.transpose(2, 0, 1).copy(), q=q.T.copy(), c=c.T.copy(),
+                              F_draws=parts['F'].T.copy(), g_draws=parts['g'].transpose(2, 0, 1).copy(),
+                              H_draws=parts['H'].transpose(3, 0, 1, 2).copy())
+        cost[idx] = F
+        with np.errstate(all='ignore'):
+            finite = np.isfinite(F) & np.isfinite(g).all(axis=0)
+            pg = np.zeros(n)
+            for d in range(D):
+                pg = np.fmax(pg, np.abs(_clip01(zi[d] - g[d]) - zi[d]))
+        code = np.where(~finite, NON_FINITE, np.where(pg <= tol, CONVERGED, ITERATION_LIMIT if it == max_iter else -1))
+        stopped = code >= 0
+        status[idx[stopped]], iterations[idx[stopped]] = code[stopped], it
+        go = np.flatnonzero(~stopped)
+        if go.size == 0:
+            continue
+        idx, zi, F, g, H, noise = idx[go], zi[:, go], F[go], g[:, go], H[:, :, go], noise[go]
+        n = idx.size
+        with np.errstate(all='ignore'):
+            active = ((zi <= 0.0) & (g > 0)) | ((zi >= 1.0) & (g < 0))
+            direction = _control_direction(H, g, active)
+            both = np.stack([direction, -g], axis=1)                                              # [D, 2, n]
+            trial = _clip01(zi[:, np.newaxis, np.newaxis, :] + _TRIAL_ALPHA[np.newaxis, np.newaxis, :, np.newaxis] *
+                            both[:, :, np.newaxis, :])                                            # [D, 2, 31, n]
+            m = 2 * CONTROL_TRIALS * n
+            flat = trial.reshape(D, m)
+            Ft_draws = per_draw(_control_pass(p, np.ascontiguousarray(np.tile(flat, (1, live.size))), np.repeat(live, m))['F'], m)
+            Ft = cvar_smooth(Ft_draws, w, alpha, eps)[0].reshape(2, CONTROL_TRIALS, n)           # phi of every trial lane
+            step = trial - zi[:, np.newaxis, np.newaxis, :]
+            slope, moved = np.zeros((2, CONTROL_TRIALS, n)), np.zeros((2, CONTROL_TRIALS, n), dtype=bool)
+            for d in range(D):
+                slope = slope + g[d] * step[d]
+                moved |= np.abs(step[d]) > 0
+            ok = moved & (Ft <= (F + ARMIJO * np.where(slope < 0, slope, 0.0)) + NOISE * noise)
+        ok = ok.reshape(2 * CONTROL_TRIALS, n)
+        any_ok = ok.any(axis=0)
+        chosen = np.argmax(ok, axis=0)
+        taken = trial.reshape(D, 2 * CONTROL_TRIALS, n)[:, chosen, np.arange(n)]
+        z[:, idx[any_ok]] = taken[:, any_ok]
+        descent[idx[any_ok & (chosen >= CONTROL_TRIALS)]] += 1
+        status[idx[~any_ok]], iterations[idx[~any_ok]] = STALLED, it
+    res = dict(z=z.T.copy(), cost=cost, cost_start=cost_start, status=status, iterations=iterations, descent_steps=descent,
+               epsilon=eps)
+    if max_iter == 0:
+        res['first_pass'] = first_pass
+    return res
+
+
+def _run_control_cvar_host(p):
+    if p['alpha'] == 0:
+        return _run_control_pooled_host(p)
+    solved = _control_cvar_solve_host(p)
+    best = int(_best_start(solved['cost'][np.newaxis], solved['status'][np.newaxis])[0])
+    zb = np.ascontiguousarray(np.repeat(solved['z'][best][:, np.newaxis], p['E'], axis=1))
+    out = _control_pass(p, zb, np.arange(p['E']), record=True)
+    return solved, best, out['members'], out['first'], out['F']
+
+
+def _assemble_control_cvar(p, solved, best, members, first, cost_draws):
+    res = _assemble_control_pooled(p, solved, best, members, first, cost_draws)
+    w, alpha = p['pool_w'], p['alpha']
+    cvar, var = cvar_exact(cost_draws, w, alpha)
+    if alpha == 0:
+        eps, a, q = (np.nan if p['epsilon'] is None else p['epsilon']), np.nan, w.copy()
+    else:
+        eps = float(solved['epsilon'])
+        _, a, q, _ = cvar_smooth(cost_draws, w, alpha, eps)
+        a = float(a)
+    res.update(cvar=cvar, var=var, expected_cost=float(pooled_sum(cost_draws, w)), tail_weights=q, a=a, epsilon=eps, alpha=alpha)
+    return res
+
+
+_CONTROL_CVAR_SIGNATURE = """
+    Every argument shared with ``control_pooled`` means what it means there (its docstring).
+    alpha       : the level in [0, 1): the plan minimises the mean cost of the worst 1 - alpha of the posterior's weight.
+                  alpha = 0 IS ``control_pooled``, bit for bit in every field
+    smoothing   : epsilon=None takes eps = smoothing x the pooled cost of start 0 at its starting point (refused where that
+                  cost is 0 or not finite); eps is fixed for the whole call and all starts
+    epsilon     : the width of the smoothed kink in cost units, instead of ``smoothing``
+    max_iter=0  : returns ``first_pass``: phi, a [S], g [S, D], H [S, D, D], q, c [S, E] and the draws' own F_draws [S, E],
+                  g_draws [S, E, D], H_draws [S, E, D, D] (NaN for a draw of weight 0); for alpha = 0 ``control_pooled``'s
+
+    Returns ``control_pooled``'s ``SimulateResult`` with cost = phi at the plan (cvar - eps / (2 (1 - alpha)) <= phi <= cvar)
+    and cvar, var: the exact CVaR and VaR of cost_draws (``cvar_exact``); expected_cost = ``pooled_sum(cost_draws, w)``;
+    tail_weights [E]: q at the plan; a; epsilon (NaN for alpha = 0 without ``epsilon=``); alpha."""
+
+
+def control_cvar(models, states, inputs, controls=None, forcing=None, y0=None, t=None, draws=None, bounds=None, segments=8,
+                 control_bounds=None, targets=None, weights=None, terminal=None, limits=None, limit_weight=1e3,
+                 move_weight=None, previous=None, init=None, starts=1, max_iter=60, tol=1e-10, draw_weights=None, alpha=0.9,
+                 smoothing=0.01, epsilon=None, keep=None, device=None):
+    """One control sequence for the whole posterior that protects its bad tail: the smoothed conditional value at risk at
+    level alpha of ``control``'s cost over the draws, minimised over one decision vector, on the device (module docstring).
+
+    device      : device index (default: the process's device, as for ``fit``), a backend or a ``_capi.DeviceContext``"""
+    alpha, smoothing, epsilon = _check_cvar(alpha, smoothing, epsilon)
+    p = _prepare_control_pooled(models, states, inputs, controls, forcing, y0, t, draws, bounds, segments, control_bounds,
+                                targets, weights, terminal, limits, limit_weight, move_weight, previous, init, starts, max_iter,
+                                tol, draw_weights, keep)
+    p.update(alpha=alpha, smoothing=smoothing, epsilon=epsilon)
+    ctx = _device_context(device)
+    return _assemble_control_cvar(p, *ctx.control_cvar_solve(p))
+
+
+def control_cvar_host(models, states, inputs, controls=None, forcing=None, y0=None, t=None, draws=None, bounds=None,
+                      segments=8, control_bounds=None, targets=None, weights=None, terminal=None, limits=None,
+                      limit_weight=1e3, move_weight=None, previous=None, init=None, starts=1, max_iter=60, tol=1e-10,
+                      draw_weights=None, alpha=0.9, smoothing=0.01, epsilon=None, keep=None):
+    """``control_cvar`` in numpy on this host: the statement the kernels are tested against (module docstring), not a
+    fallback.  Same arguments, same result fields."""
+    alpha, smoothing, epsilon = _check_cvar(alpha, smoothing, epsilon)
+    p = _prepare_control_pooled(models, states, inputs, controls, forcing, y0, t, draws, bounds, segments, control_bounds,
+                                targets, weights, terminal, limits, limit_weight, move_weight, previous, init, starts, max_iter,
+                                tol, draw_weights, keep)
+    p.update(alpha=alpha, smoothing=smoothing, epsilon=epsilon)
+    return _assemble_control_cvar(p, *_run_control_cvar_host(p))
+
+
+control_cvar.__doc__ += _CONTROL_CVAR_SIGNATURE
+control_cvar_host.__doc__ += _CONTROL_CVAR_SIGNATURE

@@ -39,6 +39,7 @@
  *   fokl_assimilate_ensemble / fokl_assimilate_report / fokl_assimilate_rng
  *   fokl_control_solve / fokl_control_report
  *   fokl_control_pooled_solve / fokl_control_pooled_report
+ *   fokl_control_cvar_solve / fokl_control_cvar_report
  *                              a system of fitted models, wired by names, integrated for every posterior draw at once
  *                              (fokl_gpy_amd/dynamics.py), and what its last call ran
  *   fokl_embedded_hmc / fokl_embedded_rng
@@ -1346,6 +1347,65 @@ int fokl_control_pooled_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t 
  *   out[10 .. 14]  with kernel timing enabled, nanoseconds in the tangent, chunk-sum (both), step, trial and accept launches
  */
 int fokl_control_pooled_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* One control sequence that protects the posterior's bad tail (csrc/fokl_control_cvar_device.inc; dynamics.py) */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_CONTROL_CVAR_REPORT_LEN 18
+
+/*
+ * fokl_control_pooled_solve with the smoothed conditional value at risk at level `alpha` of the draws' costs in place of
+ * their weighted mean: phi(z) = min_a a + sum_e w_e s_eps(F_e(z) - a) / (1 - alpha).  The arithmetic is stated by
+ * dynamics.control_cvar_host (the risk: dynamics.cvar_smooth); every argument up to `draw_weights`, and every output up to
+ * `cost_draws`, means what it means for fokl_control_pooled_solve, `cost` being phi.  Further, host memory:
+ *   alpha in [0, 1); alpha == 0 IS fokl_control_pooled_solve (which is called: first_a reads NaN, first_q the weights,
+ *          first_c 0, this call's report stays zero and the pooled call's is written)
+ *   epsilon: the width of the smoothed kink in cost units, or NaN for smoothing x the pooled cost of start 0 at its z0 (one
+ *          host read after the first tangent launch); fixed for all starts and iterations; epsilon_used [1] returns it
+ *   first_pooled [n_starts, n]: phi, noise, g [D], H [D, D] of iteration 0; first_rows as for the pooled solve; first_a
+ *          [n_starts]; first_q, first_c [n_starts, n_draws]: the soft tail weights and the band weights; all or none NULL
+ * One iteration is seven launches: tangent pass per (draw, start), risk per start (min and max, 64 bisections, phi, q, c; one
+ * thread per chunk of FOKL_CONTROL_POOL_CHUNK draws), chunk sums under q and c, Newton step per start (adds the band draws'
+ * covariance of gradients to H), value pass per (draw, start) with lane = trial point, risk per (start, lane), Armijo
+ * decision per start.  Every sum over the draws runs in dynamics.pooled_sum's order.  FOKL_CONTROL_POLL as for the pooled
+ * solve; it changes no result.  No atomics: the same arguments give the same bits.
+ * Refused (FOKL_ERR_ARG with a text that names the limit): everything fokl_control_pooled_solve refuses; alpha outside
+ * [0, 1); a smoothing or an epsilon that is not positive and finite; a relative smoothing where the pooled cost at the start
+ * is 0 or not finite (found after the first tangent launch); more draws than the risk kernel's LDS holds ((2 x 64 x chunks +
+ * 2 x threads) x 8 bytes within 144 KiB and at most 256 chunks); a workspace of n_draws x n_starts x (n + 66) x 8 bytes plus
+ * (3 + 2 D + 2 D D) x 8 per (start, chunk) plus 64 x (4 + D) x 8 per start beyond the device's free memory, of which
+ * FOKL_CONTROL_CVAR_FREE_BYTES (environment) caps what counts.  Kernel time: FOKL_K_INTEGRATE.  Blocking.
+ */
+int fokl_control_cvar_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
+                            const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
+                            const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
+                            const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
+                            const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
+                            const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
+                            const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
+                            const double *y0, const double *box, int n_controls, int n_segments, const int32_t *seg_first,
+                            const int32_t *norm_control, const double *ctl_lo, const double *ctl_width, const double *ref,
+                            const double *track_weight, const double *terminal_weight, const double *limit_lo,
+                            const double *limit_hi, double limit_weight, const double *move_weight, const double *previous,
+                            int has_previous, int n_starts, const double *z0, int max_iter, double tol,
+                            const double *draw_weights, double alpha, double smoothing, double epsilon, double *z,
+                            double *cost, double *cost_start, int32_t *status, int32_t *iterations, int32_t *descent_steps,
+                            int32_t *best_start, double *members, int32_t *first_saturation, double *cost_draws,
+                            double *epsilon_used, double *first_pooled, double *first_rows, double *first_a, double *first_q,
+                            double *first_c);
+
+/*
+ * The last fokl_control_cvar_solve call on `ctx` with alpha > 0, out [FOKL_CONTROL_CVAR_REPORT_LEN] (host values, no
+ * launch); zeros after a call that was refused, failed or had alpha == 0:
+ *   out[0]  NS: the kernel instance (states)     out[1]  draws     out[2]  starts     out[3]  D     out[4]  chunks
+ *   out[5]  dynamic LDS bytes of the per-draw kernels     out[6]  ... of the step kernel     out[7]  ... of the risk kernel
+ *   out[8]  threads of a risk workgroup     out[9]  iterations queued     out[10]  iterations that found a running start
+ *   out[11]  launches per iteration (7)
+ *   out[12 .. 17]  with kernel timing enabled, nanoseconds in the tangent, risk (both), chunk-sum, step, trial and accept
+ *           launches
+ */
+int fokl_control_cvar_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* What the fit kernels ran: K1 basis build, K2 Gram block, K3 residual moments (csrc/fokl_hip.hip)          */
