@@ -225,13 +225,13 @@ SIGNATURES = {
                                           c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
                                           c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp,
                                           c_vp, c_int, c_int, c_vp, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                          c_vp, c_vp, c_vp, c_vp]),
+                                          c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_control_pooled_report': (c_int, [c_vp, c_vp]),
     'fokl_control_cvar_solve': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
                                         c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
                                         c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp,
                                         c_vp, c_int, c_int, c_vp, c_int, c_dbl, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp,
-                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_control_cvar_report': (c_int, [c_vp, c_vp]),
     'fokl_assimilate_rng': (c_int, [ctypes.c_uint32, c_vp, c_int, ctypes.c_uint32, c_int, c_int, c_vp]),
     'fokl_model_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_dbl,
@@ -1813,6 +1813,59 @@ class NativeRun:
             pass
 
 
+class _FirstTrialStruct(ctypes.Structure):
+    """fokl_control_first_trial (include/fokl_hip_internal.h)"""
+    _fields_ = [(name, ctypes.c_void_p) for name in ('trial', 'slope', 'moved', 'pooled', 'ft', 'ft_sums', 'phi_t', 'a_t', 'z',
+                                                      'status', 'descent')]
+
+
+class _FirstTrial:
+    """The host buffers behind a fokl_control_first_trial, and what they hold as ``dynamics``' ``first_trial`` dict."""
+
+    def __init__(self, S, E, D):
+        chunks = -(-E // 64)
+        f64 = lambda *shape: np.full(shape, np.nan, dtype=np.float64)
+        self.arrays = dict(trial=f64(S, D, 64), slope=f64(S, 64), moved=np.zeros((S, 64), dtype=np.int32), pooled=f64(S, 2 + D),
+                           ft=f64(S, E, 64), ft_sums=f64(S, chunks, 64), phi_t=f64(S, 64), a_t=f64(S, 64), z=f64(S, D),
+                           status=np.full(S, -1, dtype=np.int32), descent=np.zeros(S, dtype=np.int32))
+        self.struct = _FirstTrialStruct(**{name: a.ctypes.data for name, a in self.arrays.items()})
+
+    def ref(self):
+        return ctypes.byref(self.struct)
+
+    def result(self, pooled):
+        """Lanes 31 and 63 of the wavefront are no trials: [..., 64] -> [..., 2, 31], their ``moved`` apart as
+        ``idle_moved`` [S, 2].  ``reached`` [S]: iteration 0 got to its trial pass (it went on, or it stalled there).  ``lane``
+        [S]: the wavefront lane whose point became z (0-30 a Newton trial, 32-62 a steepest-descent trial), -1 where none
+        passed or the start never got there -- the first moved lane of the half the descent count names whose trial point is
+        the new z, bit for bit (an earlier lane at the same point would have the same cost and slope, and would have passed)."""
+        a = self.arrays
+        halves = lambda x: x.reshape(x.shape[:-1] + (2, 32))[..., :31].copy()
+        S, D = a['z'].shape
+        status = a['status']
+        reached = ~np.isnan(a['pooled'][:, 0])                         # the step kernel writes F only past its stop test
+        trial, moved = halves(a['trial']), halves(a['moved']) != 0
+        lane = np.full(S, -1, dtype=np.int64)
+        for s in np.flatnonzero(reached & (status < 0)):
+            half = int(a['descent'][s] > 0)
+            same = moved[s, half] & np.all(trial[s, :, half, :] == a['z'][s][:, np.newaxis], axis=0)
+            if same.any():
+                lane[s] = 32 * half + int(np.argmax(same))
+        out = dict(trial=trial, slope=halves(a['slope']), moved=moved, idle_moved=a['moved'][:, [31, 63]].copy(),
+                   Ft_draws=halves(a['ft']), F=a['pooled'][:, 0].copy(), noise=a['pooled'][:, 1].copy(), g=a['pooled'][:, 2:].copy(),
+                   z=a['z'], status=status, descent_steps=a['descent'], reached=reached, lane=lane)
+        if pooled:
+            chunk_sums = halves(a['ft_sums'])
+            total = chunk_sums[:, 0]
+            with np.errstate(all='ignore'):
+                for k in range(1, chunk_sums.shape[1]):
+                    total = total + chunk_sums[:, k]
+            out.update(Ft_chunks=chunk_sums, Ft=total)
+        else:
+            out.update(phi_t=halves(a['phi_t']), a_t=halves(a['a_t']))
+        return out
+
+
 class DeviceContext:
     """One HIP stream on one MI355X plus the resident dataset and column slots."""
 
@@ -2400,12 +2453,15 @@ class DeviceContext:
                 'bernoulli_factors')
         return dict(zip(keys, (int(v) for v in out)))
 
-    def control_pooled_solve(self, p):
+    def control_pooled_solve(self, p, first_trial=False):
         """fokl_control_pooled_solve for a system prepared by ``dynamics._prepare_control_pooled`` -> (solved, best_start,
         members [E, n_states, P], first_saturation [E] int32, cost_draws [E]); ``solved`` holds z [S, D], cost, cost_start,
         status, iterations, descent_steps [S] and, for max_iter == 0, ``first_pass`` (the pooled F [S], g [S, D], H [S, D, D]
-        and the draws' own F_draws [S, E], g_draws [S, E, D], H_draws [S, E, D, D]; NaN for a draw of weight 0).  Needs no
-        uploaded dataset and leaves one alone."""
+        and the draws' own F_draws [S, E], g_draws [S, E, D], H_draws [S, E, D, D]; NaN for a draw of weight 0).  With
+        ``first_trial=True`` ``solved`` also holds ``first_trial``: the trial half of iteration 0 as the device left it, in
+        the layout of ``dynamics._control_pooled_solve_host``'s ``first_trial`` (``_first_trial_dict`` below), with
+        ``Ft_chunks`` [S, chunks, 2, 31], the chunk sums the accept launch adds, and ``Ft`` their sum in chunk order formed
+        here.  Needs no uploaded dataset and leaves one alone."""
         K, E, P, S, D = int(p['K']), int(p['E']), int(p['n_steps']) + 1, int(p['starts']), int(p['D'])
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
@@ -2436,6 +2492,7 @@ class DeviceContext:
         want_first = int(p['max_iter']) == 0
         pooled = np.empty((S, n), dtype=np.float64) if want_first else None
         rows = np.empty((S, E, n), dtype=np.float64) if want_first else None
+        trace = _FirstTrial(S, E, D) if first_trial else None
         self._ck(self._lib.fokl_control_pooled_solve(
             self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
             _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
@@ -2444,8 +2501,11 @@ class DeviceContext:
             _ptr(box), nc, seg_first.shape[0], _ptr(seg_first), _ptr(norm_control), _ptr(lo), _ptr(width), _ptr(ref), _ptr(wt),
             _ptr(term), _ptr(lim_lo), _ptr(lim_hi), float(p['hl']), _ptr(move), _ptr(prev), int(bool(p['has_previous'])), S,
             _ptr(z0), int(p['max_iter']), float(p['tol']), _ptr(w), _ptr(z), _ptr(cost), _ptr(cost_start), _ptr(status),
-            _ptr(iterations), _ptr(descent), _ptr(best), _ptr(members), _ptr(first), _ptr(cost_draws), _ptr(pooled), _ptr(rows)))
+            _ptr(iterations), _ptr(descent), _ptr(best), _ptr(members), _ptr(first), _ptr(cost_draws), _ptr(pooled), _ptr(rows),
+            trace.ref() if trace else None))
         solved = dict(z=z, cost=cost, cost_start=cost_start, status=status, iterations=iterations, descent_steps=descent)
+        if trace:
+            solved['first_trial'] = trace.result(pooled=True)
         if want_first:
             solved['first_pass'] = dict(F=pooled[:, 0].copy(), g=pooled[:, 2:2 + D].copy(), H=pooled[:, 2 + D:].reshape(S, D, D).copy(),
                                         F_draws=rows[:, :, 0].copy(), g_draws=rows[:, :, 2:2 + D].copy(),
@@ -2464,11 +2524,13 @@ class DeviceContext:
                 'launches_per_iteration', 'tangent_ns', 'chunk_ns', 'step_ns', 'trial_ns', 'accept_ns')
         return dict(zip(keys, (int(v) for v in out)))
 
-    def control_cvar_solve(self, p):
+    def control_cvar_solve(self, p, first_trial=False):
         """fokl_control_cvar_solve for a system prepared as for ``control_pooled_solve`` with ``alpha``, ``smoothing`` and
         ``epsilon`` (None: relative) -> what ``control_pooled_solve`` returns, ``solved`` also holding ``epsilon`` (as used)
         and, for max_iter == 0, ``first_pass``: phi, a [S], g [S, D], H [S, D, D], q, c [S, E] and the draws' own F_draws,
-        g_draws, H_draws -- for alpha == 0 ``control_pooled_solve``'s."""
+        g_draws, H_draws -- for alpha == 0 ``control_pooled_solve``'s.  With ``first_trial=True`` ``solved`` also holds
+        ``first_trial`` in the layout of ``dynamics._control_cvar_solve_host``'s: ``phi_t`` and ``a_t`` [S, 2, 31] of the
+        trial-side risk launch in place of the pooled ``Ft`` (for alpha == 0 ``control_pooled_solve``'s)."""
         K, E, P, S, D = int(p['K']), int(p['E']), int(p['n_steps']) + 1, int(p['starts']), int(p['D'])
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
@@ -2505,6 +2567,7 @@ class DeviceContext:
         fa = np.empty(S, dtype=np.float64) if want_first else None
         fq = np.empty((S, E), dtype=np.float64) if want_first else None
         fc = np.empty((S, E), dtype=np.float64) if want_first else None
+        trace = _FirstTrial(S, E, D) if first_trial else None
         self._ck(self._lib.fokl_control_cvar_solve(
             self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
             _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
@@ -2514,9 +2577,12 @@ class DeviceContext:
             _ptr(term), _ptr(lim_lo), _ptr(lim_hi), float(p['hl']), _ptr(move), _ptr(prev), int(bool(p['has_previous'])), S,
             _ptr(z0), int(p['max_iter']), float(p['tol']), _ptr(w), alpha, float(p['smoothing']), epsilon, _ptr(z), _ptr(cost),
             _ptr(cost_start), _ptr(status), _ptr(iterations), _ptr(descent), _ptr(best), _ptr(members), _ptr(first),
-            _ptr(cost_draws), _ptr(used), _ptr(pooled), _ptr(rows), _ptr(fa), _ptr(fq), _ptr(fc)))
+            _ptr(cost_draws), _ptr(used), _ptr(pooled), _ptr(rows), _ptr(fa), _ptr(fq), _ptr(fc),
+            trace.ref() if trace else None))
         solved = dict(z=z, cost=cost, cost_start=cost_start, status=status, iterations=iterations, descent_steps=descent,
                       epsilon=float(used[0]))
+        if trace:
+            solved['first_trial'] = trace.result(pooled=alpha == 0)
         if want_first:
             parts = dict(g=pooled[:, 2:2 + D].copy(), H=pooled[:, 2 + D:].reshape(S, D, D).copy(), F_draws=rows[:, :, 0].copy(),
                          g_draws=rows[:, :, 2:2 + D].copy(), H_draws=rows[:, :, 2 + D:].reshape(S, E, D, D).copy())

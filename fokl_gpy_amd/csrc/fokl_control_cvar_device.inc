@@ -23,7 +23,9 @@
 //   6  control_cvar_risk_kernel           grid starts x 64: F_e = ft[s][e][lane] -> phi_t [s][lane] (and a_t, unused)
 //   7  control_pooled_accept_kernel       with one chunk: the Armijo test on phi_t per lane, the first passing lane
 // LDS of 2 and 6: (2 x 64 x ceil(draws / 64) + 2 x threads) x 8 bytes (F and w by [position in chunk][chunk], the exchange
-// twice); of 4: (4 + D) x 64 x 8 bytes.
+// twice); of 4: (4 + D) x 64 x 8 bytes.  The LDS of 2 and 6 is the limit on the draws: 141 chunks = 9 024 draws with 192
+// threads take exactly SIM_LDS_BUDGET, so the kernel's launch bound of 256 threads (256 chunks) is never reached.
+// fokl_control_first_trial: as for the pooled solve, with phi_t and a_t of launch 6 in place of the launch-5 chunk sums.
 
 namespace fokl {
 
@@ -302,7 +304,7 @@ extern "C" int fokl_control_cvar_solve(
     const double *z0, int max_iter, double tol, const double *draw_weights, double alpha, double smoothing, double epsilon,
     double *z, double *cost, double *cost_start, int32_t *status, int32_t *iterations, int32_t *descent_steps, int32_t *best_start,
     double *members, int32_t *first_saturation, double *cost_draws, double *epsilon_used, double *first_pooled, double *first_rows,
-    double *first_a, double *first_q, double *first_c)
+    double *first_a, double *first_q, double *first_c, const fokl_control_first_trial *first_trial)
 {
     const std::string who = "fokl_control_cvar_solve: ";
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
@@ -310,7 +312,10 @@ extern "C" int fokl_control_cvar_solve(
     const bool want_first = first_pooled != nullptr;
     if (!draw_weights || !z || !cost || !cost_start || !status || !iterations || !descent_steps || !best_start || !members ||
         !first_saturation || !cost_draws || !epsilon_used || want_first != (first_rows != nullptr) ||
-        want_first != (first_a != nullptr) || want_first != (first_q != nullptr) || want_first != (first_c != nullptr))
+        want_first != (first_a != nullptr) || want_first != (first_q != nullptr) || want_first != (first_c != nullptr) ||
+        (first_trial && alpha != 0.0 &&
+         (!first_trial->trial || !first_trial->slope || !first_trial->moved || !first_trial->pooled || !first_trial->ft ||
+          !first_trial->phi_t || !first_trial->a_t || !first_trial->z || !first_trial->status || !first_trial->descent)))
         return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
     if (!(alpha >= 0.0 && alpha < 1.0)) return fail(ctx, FOKL_ERR_ARG, who + "alpha must lie in [0, 1), got " + std::to_string(alpha));
     const bool relative = std::isnan(epsilon);                        // NaN: eps = smoothing x the pooled cost of start 0 at z0
@@ -335,7 +340,7 @@ extern "C" int fokl_control_cvar_solve(
                                          ctl_lo, ctl_width, ref, track_weight, terminal_weight, limit_lo, limit_hi, limit_weight,
                                          move_weight, previous, has_previous, n_starts, z0, max_iter, tol, draw_weights, z, cost,
                                          cost_start, status, iterations, descent_steps, best_start, members, first_saturation,
-                                         cost_draws, first_pooled, first_rows);
+                                         cost_draws, first_pooled, first_rows, first_trial);
     }
     const CtlArgs args{n_draws, n_states, n_steps, h, n_forcing_cols, forcing, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
                        n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows, spline_table,
@@ -422,6 +427,15 @@ extern "C" int fokl_control_cvar_solve(
         HIP_TRY(ctx, hipMemcpy(d_rows, h_rows.data(), h_rows.size() * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(ctx, buf.get(&d_fpool, S * n));
     }
+    if (first_trial) {                                                // what iteration 0 does not write reads NaN, moved 0
+        HIP_TRY(ctx, pooled_fill_nan(d_trial, S * D * SIM_LANES));
+        HIP_TRY(ctx, pooled_fill_nan(d_slope, S * SIM_LANES));
+        HIP_TRY(ctx, pooled_fill_nan(d_pooled, S * (2 + D)));
+        HIP_TRY(ctx, pooled_fill_nan(d_ft, B * SIM_LANES));
+        HIP_TRY(ctx, pooled_fill_nan(d_phi_t, S * SIM_LANES));
+        HIP_TRY(ctx, pooled_fill_nan(d_a_t, S * SIM_LANES));
+        HIP_TRY(ctx, hipMemset(d_moved, 0, S * SIM_LANES * sizeof(int)));
+    }
     HIP_TRY(ctx, buf.get(&d_zbest, E * D));
     HIP_TRY(ctx, buf.get(&d_members, E * n_states * n_points));
     HIP_TRY(ctx, buf.get(&d_first, E));
@@ -501,6 +515,19 @@ extern "C" int fokl_control_cvar_solve(
             clock.after();
             HIP_TRY(ctx, launched);
             ++queued;
+        }
+        if (it == 0 && first_trial) {                                 // iteration 0's trial half, before a later one overwrites it
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(first_trial->trial, d_trial, S * D * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->slope, d_slope, S * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->moved, d_moved, S * SIM_LANES * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->pooled, d_pooled, S * (2 + D) * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->ft, d_ft, B * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->phi_t, d_phi_t, S * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->a_t, d_a_t, S * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->z, d_z, S * D * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->status, d_status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->descent, d_descent, S * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
         if (poll > 0 && (it + 1) % poll == 0 && it < max_iter) {      // may stop queuing early: an iteration without work changes nothing
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

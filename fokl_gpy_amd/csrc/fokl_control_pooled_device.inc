@@ -23,6 +23,8 @@
 //                                         the new z, the descent count, or status 3
 // A finished start (status >= 0) and, in 1 and 4, a draw of weight 0 return at once.  LDS of 1 and 4: control's formula;
 // of 3: (4 + D) x 64 x 8 bytes (exchange, z, g, direction, H as [D][64]).
+// For tests the host half can hand out what iteration 0 left in these buffers after launch 6 (fokl_control_first_trial in
+// fokl_hip_internal.h): one more stream synchronisation and host copies, no other launch and no change to a kernel.
 
 namespace fokl {
 
@@ -289,6 +291,13 @@ hipError_t pooled_trial(fokl_ctx *ctx, int grid, size_t lds_bytes, const SimSyst
     return hipGetLastError();
 }
 
+// For the first_trial outputs: NaN into a buffer that iteration 0 may leave unwritten in places
+hipError_t pooled_fill_nan(double *d, size_t count)
+{
+    const std::vector<double> h(count, NAN);
+    return hipMemcpy(d, h.data(), count * sizeof(double), hipMemcpyHostToDevice);
+}
+
 hipError_t pooled_chunks(fokl_ctx *ctx, const double *rows, const double *w, const int *status, double *sums, int n_draws,
                          int n_starts, int n, int n_chunks)
 {
@@ -330,13 +339,15 @@ extern "C" int fokl_control_pooled_solve(
     const double *limit_hi, double limit_weight, const double *move_weight, const double *previous, int has_previous, int n_starts,
     const double *z0, int max_iter, double tol, const double *draw_weights, double *z, double *cost, double *cost_start,
     int32_t *status, int32_t *iterations, int32_t *descent_steps, int32_t *best_start, double *members, int32_t *first_saturation,
-    double *cost_draws, double *first_pooled, double *first_rows)
+    double *cost_draws, double *first_pooled, double *first_rows, const fokl_control_first_trial *first_trial)
 {
     const std::string who = "fokl_control_pooled_solve: ";
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
     std::memset(ctx->control_pooled_report, 0, sizeof ctx->control_pooled_report);
     if (!draw_weights || !z || !cost || !cost_start || !status || !iterations || !descent_steps || !best_start || !members ||
-        !first_saturation || !cost_draws || (first_pooled == nullptr) != (first_rows == nullptr))
+        !first_saturation || !cost_draws || (first_pooled == nullptr) != (first_rows == nullptr) ||
+        (first_trial && (!first_trial->trial || !first_trial->slope || !first_trial->moved || !first_trial->pooled || !first_trial->ft ||
+                         !first_trial->ft_sums || !first_trial->z || !first_trial->status || !first_trial->descent)))
         return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
     const CtlArgs args{n_draws, n_states, n_steps, h, n_forcing_cols, forcing, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
                        n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows, spline_table,
@@ -408,6 +419,14 @@ extern "C" int fokl_control_pooled_solve(
         HIP_TRY(ctx, hipMemcpy(d_rows, h_rows.data(), h_rows.size() * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(ctx, buf.get(&d_fpool, S * n));
     }
+    if (first_trial) {                                                // what iteration 0 does not write reads NaN, moved 0
+        HIP_TRY(ctx, pooled_fill_nan(d_trial, S * D * SIM_LANES));
+        HIP_TRY(ctx, pooled_fill_nan(d_slope, S * SIM_LANES));
+        HIP_TRY(ctx, pooled_fill_nan(d_pooled, S * (2 + D)));
+        HIP_TRY(ctx, pooled_fill_nan(d_ft, B * SIM_LANES));
+        HIP_TRY(ctx, pooled_fill_nan(d_ft_sums, S * n_chunks * SIM_LANES));
+        HIP_TRY(ctx, hipMemset(d_moved, 0, S * SIM_LANES * sizeof(int)));
+    }
     HIP_TRY(ctx, buf.get(&d_zbest, E * D));
     HIP_TRY(ctx, buf.get(&d_members, E * n_states * n_points));
     HIP_TRY(ctx, buf.get(&d_first, E));
@@ -451,6 +470,18 @@ extern "C" int fokl_control_pooled_solve(
             clock.after();
             HIP_TRY(ctx, launched);
             ++queued;
+        }
+        if (it == 0 && first_trial) {                                 // iteration 0's trial half, before a later one overwrites it
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy(first_trial->trial, d_trial, S * D * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->slope, d_slope, S * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->moved, d_moved, S * SIM_LANES * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->pooled, d_pooled, S * (2 + D) * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->ft, d_ft, B * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->ft_sums, d_ft_sums, S * n_chunks * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->z, d_z, S * D * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->status, d_status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(first_trial->descent, d_descent, S * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
         if (poll > 0 && (it + 1) % poll == 0 && it < max_iter) {      // may stop queuing early: an iteration without work changes nothing
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

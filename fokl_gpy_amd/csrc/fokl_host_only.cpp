@@ -93,7 +93,8 @@ extern "C" int fokl_control_pooled_solve(fokl_ctx *, int, int, int64_t, double, 
                                          const double *, const double *, const double *, const double *, const double *,
                                          const double *, const double *, double, const double *, const double *, int, int,
                                          const double *, int, double, const double *, double *, double *, double *, int32_t *,
-                                         int32_t *, int32_t *, int32_t *, double *, int32_t *, double *, double *, double *)
+                                         int32_t *, int32_t *, int32_t *, double *, int32_t *, double *, double *, double *,
+                                         const fokl_control_first_trial *)
 {
     return FOKL_ERR_HIP;
 }
@@ -109,7 +110,8 @@ extern "C" int fokl_control_cvar_solve(fokl_ctx *, int, int, int64_t, double, in
                                        const double *, const double *, double, const double *, const double *, int, int,
                                        const double *, int, double, const double *, double, double, double, double *, double *,
                                        double *, int32_t *, int32_t *, int32_t *, int32_t *, double *, int32_t *, double *,
-                                       double *, double *, double *, double *, double *, double *)
+                                       double *, double *, double *, double *, double *, double *,
+                                       const fokl_control_first_trial *)
 {
     return FOKL_ERR_HIP;
 }

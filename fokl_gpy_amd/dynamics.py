@@ -1569,17 +1569,71 @@ def _prepare_control_pooled(models, states, inputs, controls, forcing, y0, t, dr
     return p
 
 
+def _trial_step(zi, g, trial):
+    """slope [2, 31, n] = sum_d g_d (trial_d - z_d) in index order from 0.0, and moved [2, 31, n]: some trial_d != z_d.
+    zi, g [D, n]; trial [D, 2, 31, n]."""
+    slope, moved = np.zeros(trial.shape[1:]), np.zeros(trial.shape[1:], dtype=bool)
+    with np.errstate(all='ignore'):
+        step = trial - zi[:, np.newaxis, np.newaxis, :]
+        for d in range(zi.shape[0]):
+            slope = slope + g[d] * step[d]
+            moved |= np.abs(step[d]) > 0
+    return slope, moved
+
+
+def _armijo(Ft, F, noise, slope, moved):
+    """The Armijo decision of every solve: Ft, slope, moved [2, 31, n]; F, noise [n] -> (chosen [n], any_ok [n]).  chosen
+    counts the 62 trials, the 31 Newton trials first; the first passing one is taken."""
+    with np.errstate(all='ignore'):
+        ok = moved & (Ft <= (F + ARMIJO * np.where(slope < 0, slope, 0.0)) + NOISE * noise)
+    ok = ok.reshape(2 * CONTROL_TRIALS, -1)
+    return np.argmax(ok, axis=0), ok.any(axis=0)
+
+
+def _first_trial(S, E, D, idx, trial, slope, moved, Ft_draws, F, noise, g, **risk):
+    """The trial half of iteration 0 for the starts idx that reached it, over all S starts (NaN, moved False elsewhere):
+    trial [S, D, 2, 31], slope, moved [S, 2, 31], Ft_draws [S, E, 2, 31] (NaN for a draw of weight 0), F, noise [S] and g
+    [S, D] as the decision reads them, the risk's own arrays [S, 2, 31] (``Ft``, or ``phi_t`` and ``a_t``), idle_moved [S, 2]
+    (lanes 31 and 63 of the device's wavefront are no trials: 0), reached [S].  ``_first_trial_decision`` adds the rest."""
+    n = idx.size
+    full = lambda shape, values: _scatter(np.full((S,) + shape, np.nan), idx, values)
+    out = dict(trial=full((D, 2, CONTROL_TRIALS), np.moveaxis(trial, -1, 0)), slope=full((2, CONTROL_TRIALS), np.moveaxis(slope, -1, 0)),
+               moved=_scatter(np.zeros((S, 2, CONTROL_TRIALS), dtype=bool), idx, np.moveaxis(moved, -1, 0)),
+               idle_moved=np.zeros((S, 2), dtype=np.int32),
+               Ft_draws=full((E, 2, CONTROL_TRIALS), np.moveaxis(Ft_draws.reshape(E, 2, CONTROL_TRIALS, n), -1, 0)),
+               F=full((), F), noise=full((), noise), g=full((D,), g.T), reached=_scatter(np.zeros(S, dtype=bool), idx, True))
+    for key, value in risk.items():
+        out[key] = full((2, CONTROL_TRIALS), np.moveaxis(value.reshape(2, CONTROL_TRIALS, n), -1, 0))
+    return out
+
+
+def _scatter(into, idx, values):
+    into[idx] = values
+    return into
+
+
+def _first_trial_decision(first_trial, idx, chosen, any_ok, z, status, descent):
+    """lane [S]: the trial taken, numbered as the device's wavefront lane (0-30 a Newton trial, 32-62 a steepest-descent
+    trial), -1 where none passed or the start never got there; z [S, D], status (-1: the start goes on) and descent_steps
+    [S] after iteration 0."""
+    lane = np.full(status.shape[0], -1, dtype=np.int64)
+    lane[idx] = np.where(any_ok, chosen + (chosen >= CONTROL_TRIALS), -1)
+    first_trial.update(lane=lane, z=z.T.copy(), status=status.copy(), descent_steps=descent.copy())
+
+
 def _control_pooled_solve_host(p):
     """Every start's pooled solve -> dict(z [S, D], cost, cost_start, status, iterations, descent_steps [S] and, with
     max_iter == 0, the first tangent pass: pooled F [S], g [S, D], H [S, D, D] and the draws' own F_draws [S, E], g_draws
-    [S, E, D], H_draws [S, E, D, D]; NaN for a draw of weight 0, which is never evaluated)."""
+    [S, E, D], H_draws [S, E, D, D]; NaN for a draw of weight 0, which is never evaluated).  Where iteration 0 reached its
+    trial pass in some start, ``first_trial``: that pass (``_first_trial``, with the pooled ``Ft`` [S, 2, 31], and
+    ``_first_trial_decision``)."""
     E, S, D, max_iter, tol, w = p['E'], p['starts'], p['D'], p['max_iter'], p['tol'], p['pool_w']
     live = np.flatnonzero(w != 0)
-    z = np.ascontiguousarray(p['z0'].T)                               # [D, S]
+    z = np.array(p['z0'].T, order='C')                                # [D, S]; a copy: p['z0'] stays the start (for D == 1 .T is contiguous)
     status = np.full(S, -1, dtype=np.int32)
     iterations, descent = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
     cost, cost_start = np.full(S, np.nan), np.full(S, np.nan)
-    first_pass = None
+    first_pass = first_trial = None
 
     def per_draw(values, n):
         """[..., live x n] as _control_pass returns it (draw-major) -> [E, ..., n], NaN where the draw weighs nothing"""
@@ -1624,22 +1678,20 @@ def _control_pooled_solve_host(p):
             flat = trial.reshape(D, m)
             Ft_draws = per_draw(_control_pass(p, np.ascontiguousarray(np.tile(flat, (1, live.size))), np.repeat(live, m))['F'], m)
             Ft = pooled_sum(Ft_draws, w).reshape(2, CONTROL_TRIALS, n)
-            step = trial - zi[:, np.newaxis, np.newaxis, :]
-            slope, moved = np.zeros((2, CONTROL_TRIALS, n)), np.zeros((2, CONTROL_TRIALS, n), dtype=bool)
-            for d in range(D):
-                slope = slope + g[d] * step[d]
-                moved |= np.abs(step[d]) > 0
-            ok = moved & (Ft <= (F + ARMIJO * np.where(slope < 0, slope, 0.0)) + NOISE * noise)
-        ok = ok.reshape(2 * CONTROL_TRIALS, n)
-        any_ok = ok.any(axis=0)
-        chosen = np.argmax(ok, axis=0)                                # the first Newton lane, else the first steepest-descent lane
+            slope, moved = _trial_step(zi, g, trial)
+        chosen, any_ok = _armijo(Ft, F, noise, slope, moved)          # the first Newton lane, else the first steepest-descent lane
         taken = trial.reshape(D, 2 * CONTROL_TRIALS, n)[:, chosen, np.arange(n)]
         z[:, idx[any_ok]] = taken[:, any_ok]
         descent[idx[any_ok & (chosen >= CONTROL_TRIALS)]] += 1
         status[idx[~any_ok]], iterations[idx[~any_ok]] = STALLED, it
+        if it == 0:
+            first_trial = _first_trial(S, E, D, idx, trial, slope, moved, Ft_draws, F, noise, g, Ft=Ft)
+            _first_trial_decision(first_trial, idx, chosen, any_ok, z, status, descent)
     res = dict(z=z.T.copy(), cost=cost, cost_start=cost_start, status=status, iterations=iterations, descent_steps=descent)
     if max_iter == 0:
         res['first_pass'] = first_pass
+    if first_trial is not None:
+        res['first_trial'] = first_trial
     return res
 
 
@@ -1876,15 +1928,17 @@ def _relative_epsilon(smoothing, cost):
 
 def _control_cvar_solve_host(p):
     """Every start's CVaR solve -> ``_control_pooled_solve_host``'s dict with cost = phi, ``epsilon`` and, with
-    max_iter == 0, the first pass: phi, a [S], g [S, D], H [S, D, D], q, c [S, E] and the draws' own parts."""
+    max_iter == 0, the first pass: phi, a [S], g [S, D], H [S, D, D], q, c [S, E] and the draws' own parts; ``first_trial``
+    holds ``phi_t`` and ``a_t`` [S, 2, 31] (``cvar_smooth`` of every trial point's costs) in place of the pooled ``Ft``, and
+    F is phi."""
     E, S, D, max_iter, tol, w = p['E'], p['starts'], p['D'], p['max_iter'], p['tol'], p['pool_w']
     alpha, eps = p['alpha'], p['epsilon']
     live = np.flatnonzero(w != 0)
-    z = np.ascontiguousarray(p['z0'].T)                               # [D, S]
+    z = np.array(p['z0'].T, order='C')                                # [D, S]; a copy: p['z0'] stays the start (for D == 1 .T is contiguous)
     status = np.full(S, -1, dtype=np.int32)
     iterations, descent = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
     cost, cost_start = np.full(S, np.nan), np.full(S, np.nan)
-    first_pass = None
+    first_pass = first_trial = None
 
     def per_draw(values, n):
         out = np.full((E,) + values.shape[:-1] + (n,), np.nan)
@@ -1930,24 +1984,22 @@ def _control_cvar_solve_host(p):
             m = 2 * CONTROL_TRIALS * n
             flat = trial.reshape(D, m)
             Ft_draws = per_draw(_control_pass(p, np.ascontiguousarray(np.tile(flat, (1, live.size))), np.repeat(live, m))['F'], m)
-            Ft = cvar_smooth(Ft_draws, w, alpha, eps)[0].reshape(2, CONTROL_TRIALS, n)           # phi of every trial lane
-            step = trial - zi[:, np.newaxis, np.newaxis, :]
-            slope, moved = np.zeros((2, CONTROL_TRIALS, n)), np.zeros((2, CONTROL_TRIALS, n), dtype=bool)
-            for d in range(D):
-                slope = slope + g[d] * step[d]
-                moved |= np.abs(step[d]) > 0
-            ok = moved & (Ft <= (F + ARMIJO * np.where(slope < 0, slope, 0.0)) + NOISE * noise)
-        ok = ok.reshape(2 * CONTROL_TRIALS, n)
-        any_ok = ok.any(axis=0)
-        chosen = np.argmax(ok, axis=0)
+            Ft, a_t = (x.reshape(2, CONTROL_TRIALS, n) for x in cvar_smooth(Ft_draws, w, alpha, eps)[:2])   # phi of every trial lane
+            slope, moved = _trial_step(zi, g, trial)
+        chosen, any_ok = _armijo(Ft, F, noise, slope, moved)
         taken = trial.reshape(D, 2 * CONTROL_TRIALS, n)[:, chosen, np.arange(n)]
         z[:, idx[any_ok]] = taken[:, any_ok]
         descent[idx[any_ok & (chosen >= CONTROL_TRIALS)]] += 1
         status[idx[~any_ok]], iterations[idx[~any_ok]] = STALLED, it
+        if it == 0:
+            first_trial = _first_trial(S, E, D, idx, trial, slope, moved, Ft_draws, F, noise, g, phi_t=Ft, a_t=a_t)
+            _first_trial_decision(first_trial, idx, chosen, any_ok, z, status, descent)
     res = dict(z=z.T.copy(), cost=cost, cost_start=cost_start, status=status, iterations=iterations, descent_steps=descent,
                epsilon=eps)
     if max_iter == 0:
         res['first_pass'] = first_pass
+    if first_trial is not None:
+        res['first_trial'] = first_trial
     return res
 
 

@@ -1300,6 +1300,26 @@ int fokl_control_report(const fokl_ctx *ctx, int64_t *out);
 #define FOKL_CONTROL_POOL_CHUNK 64
 
 /*
+ * What iteration 0 of fokl_control_pooled_solve / fokl_control_cvar_solve left in device memory after its last launch, for
+ * tests: the trial half of the iteration, which no result shows.  Host memory, row-major, lane = the wavefront's lane (0-30
+ * Newton trials, 32-62 steepest-descent trials, 31 and 63 are no trials).  Where the struct is given every pointer that the
+ * call uses must be set; a start that stopped before its trial pass (and, in ft, a draw of weight 0) reads NaN, moved 0.
+ */
+typedef struct fokl_control_first_trial {
+    double *trial;    /* [n_starts, D, 64]: the trial points */
+    double *slope;    /* [n_starts, 64]: g . (trial - z) */
+    int32_t *moved;   /* [n_starts, 64]: the lane is a trial and moves z */
+    double *pooled;   /* [n_starts, 2 + D]: F (the CVaR solve: phi), noise and g as the Armijo decision reads them */
+    double *ft;       /* [n_starts, n_draws, 64]: every draw's own cost at every trial point */
+    double *ft_sums;  /* [n_starts, chunks, 64]: the chunk sums of ft the accept launch adds (pooled solve, alpha == 0) */
+    double *phi_t;    /* [n_starts, 64]: phi of every trial point (CVaR solve with alpha > 0) */
+    double *a_t;      /* [n_starts, 64]: its a */
+    double *z;        /* [n_starts, D]: z after iteration 0 */
+    int32_t *status;  /* [n_starts]: after iteration 0; -1 is a start that goes on */
+    int32_t *descent; /* [n_starts]: the descent count after iteration 0 */
+} fokl_control_first_trial;
+
+/*
  * One bounded least-squares solve per start over ALL draws: the expected cost sum_e w_e F_e(z) of fokl_control_solve's cost,
  * minimised over one decision vector by the same projected Gauss-Newton iteration with the pooled F, noise, g and H in place
  * of one draw's.  The arithmetic is stated by dynamics.control_pooled_host; every argument up to `tol` means what it means
@@ -1311,6 +1331,9 @@ int fokl_control_report(const fokl_ctx *ctx, int64_t *out);
  *   first_pooled [n_starts, n], first_rows [n_starts, n_draws, n] with n = 2 + D + D D: the pooled tangent pass of iteration
  *          0 and the draws' own, each row F, noise, g [D], H [D, D] (entry [d][d'] as lane d forms it); the row of a draw of
  *          weight 0 is NaN; both or none NULL
+ *   first_trial: NULL, or what iteration 0 wrote (fokl_control_first_trial above).  NULL changes nothing; otherwise the
+ *          buffers it names are filled with NaN before the first launch and the stream is synchronised once after iteration
+ *          0's last launch for the copies: the same launches, the same report, the same bits in every other output
  * The pooled sum (dynamics.pooled_sum): chunks of FOKL_CONTROL_POOL_CHUNK consecutive draws, inside a chunk
  * acc = acc + w_e x_e in index order from 0.0, the chunk sums added in chunk order from the first, a draw of weight 0
  * skipped.  One iteration is six launches on the context's stream (tangent pass per (draw, start), chunk sums, Newton step
@@ -1336,7 +1359,8 @@ int fokl_control_pooled_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t 
                               int has_previous, int n_starts, const double *z0, int max_iter, double tol,
                               const double *draw_weights, double *z, double *cost, double *cost_start, int32_t *status,
                               int32_t *iterations, int32_t *descent_steps, int32_t *best_start, double *members,
-                              int32_t *first_saturation, double *cost_draws, double *first_pooled, double *first_rows);
+                              int32_t *first_saturation, double *cost_draws, double *first_pooled, double *first_rows,
+                              const fokl_control_first_trial *first_trial);
 
 /*
  * The last fokl_control_pooled_solve call on `ctx`, out [FOKL_CONTROL_POOLED_REPORT_LEN] (host values, no launch); zeros
@@ -1365,6 +1389,7 @@ int fokl_control_pooled_report(const fokl_ctx *ctx, int64_t *out);
  *          host read after the first tangent launch); fixed for all starts and iterations; epsilon_used [1] returns it
  *   first_pooled [n_starts, n]: phi, noise, g [D], H [D, D] of iteration 0; first_rows as for the pooled solve; first_a
  *          [n_starts]; first_q, first_c [n_starts, n_draws]: the soft tail weights and the band weights; all or none NULL
+ *   first_trial: as for fokl_control_pooled_solve, with phi_t and a_t in place of ft_sums; alpha == 0 passes it through
  * One iteration is seven launches: tangent pass per (draw, start), risk per start (min and max, 64 bisections, phi, q, c; one
  * thread per chunk of FOKL_CONTROL_POOL_CHUNK draws), chunk sums under q and c, Newton step per start (adds the band draws'
  * covariance of gradients to H), value pass per (draw, start) with lane = trial point, risk per (start, lane), Armijo
@@ -1373,7 +1398,7 @@ int fokl_control_pooled_report(const fokl_ctx *ctx, int64_t *out);
  * Refused (FOKL_ERR_ARG with a text that names the limit): everything fokl_control_pooled_solve refuses; alpha outside
  * [0, 1); a smoothing or an epsilon that is not positive and finite; a relative smoothing where the pooled cost at the start
  * is 0 or not finite (found after the first tangent launch); more draws than the risk kernel's LDS holds ((2 x 64 x chunks +
- * 2 x threads) x 8 bytes within 144 KiB and at most 256 chunks); a workspace of n_draws x n_starts x (n + 66) x 8 bytes plus
+ * 2 x threads) x 8 bytes within 144 KiB: 141 chunks = 9 024 draws; the kernel's 256 threads are never the limit); a workspace of n_draws x n_starts x (n + 66) x 8 bytes plus
  * (3 + 2 D + 2 D D) x 8 per (start, chunk) plus 64 x (4 + D) x 8 per start beyond the device's free memory, of which
  * FOKL_CONTROL_CVAR_FREE_BYTES (environment) caps what counts.  Kernel time: FOKL_K_INTEGRATE.  Blocking.
  */
@@ -1393,7 +1418,7 @@ int fokl_control_cvar_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_
                             double *cost, double *cost_start, int32_t *status, int32_t *iterations, int32_t *descent_steps,
                             int32_t *best_start, double *members, int32_t *first_saturation, double *cost_draws,
                             double *epsilon_used, double *first_pooled, double *first_rows, double *first_a, double *first_q,
-                            double *first_c);
+                            double *first_c, const fokl_control_first_trial *first_trial);
 
 /*
  * The last fokl_control_cvar_solve call on `ctx` with alpha > 0, out [FOKL_CONTROL_CVAR_REPORT_LEN] (host values, no

@@ -330,3 +330,38 @@ def test_refusals_name_their_limit():
         dynamics.cvar_smooth(np.ones(3), np.ones(3) / 3, 0.5, 0.0)
     with pytest.raises(ValueError, match="alpha must lie in \\[0, 1\\)"):
         dynamics.cvar_exact(np.ones(3), np.ones(3) / 3, 1.0)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# first_trial: the trial half of iteration 0, spelled out
+# ---------------------------------------------------------------------------------------------------------
+
+def test_first_trial_is_the_trial_half_of_iteration_0():
+    args = product(65, 20, spread=0.3)
+    w = 0.25 + np.random.default_rng(3).random(65)
+    w[32] = 0.0
+    kw = dict(**args, **NONLINEAR, starts=2, draw_weights=w, forcing=None, draws=None, bounds=None, control_bounds=None, weights=None,
+              terminal=None, limits=None, limit_weight=1e3, previous=None, init=None, tol=1e-10, keep=None)
+    risk = dict(alpha=0.8, smoothing=0.01, epsilon=2e-3)
+    p = {**dynamics._prepare_control_pooled(**kw, max_iter=1), **risk}
+    solved = dynamics._control_cvar_solve_host(p)
+    first = dynamics._control_cvar_solve_host({**dynamics._prepare_control_pooled(**kw, max_iter=0), **risk})
+    assert 'first_trial' not in first
+    ft, w = solved['first_trial'], p['pool_w']
+    assert ft['phi_t'].shape == ft['a_t'].shape == (2, 2, 31) and 'Ft' not in ft and ft['reached'].all()
+    assert np.array_equal(ft['F'], first['first_pass']['phi']) and np.array_equal(ft['g'], first['first_pass']['g'])
+    for s in range(2):
+        for half in range(2):
+            for i in range(31):                                        # every trial point's risk is cvar_smooth of its own costs
+                phi, a, _, _ = dynamics.cvar_smooth(ft['Ft_draws'][s, :, half, i], w, 0.8, 2e-3)
+                assert phi == ft['phi_t'][s, half, i] and a == ft['a_t'][s, half, i]
+        bound = (ft['F'][s] + dynamics.ARMIJO * np.where(ft['slope'][s] < 0, ft['slope'][s], 0.0)) + dynamics.NOISE * ft['noise'][s]
+        ok = (ft['moved'][s] & (ft['phi_t'][s] <= bound)).ravel()
+        lane = int(np.argmax(ok)) + int(np.argmax(ok) >= 31)
+        assert ok.any() and lane == ft['lane'][s] and np.array_equal(ft['z'][s], ft['trial'][s, :, lane // 32, lane % 32])
+        assert np.isnan(ft['Ft_draws'][s, 32]).all() and ft['status'][s] == -1
+    assert np.array_equal(solved['z'], ft['z'])
+    # alpha = 0 is the pooled solve's first_trial
+    zero = dynamics._run_control_cvar_host({**p, 'alpha': 0.0})[0]['first_trial']
+    pooled = dynamics._control_pooled_solve_host(p)['first_trial']
+    assert set(zero) == set(pooled) and all(np.array_equal(zero[key], pooled[key], equal_nan=True) for key in pooled)

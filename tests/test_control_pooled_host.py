@@ -282,3 +282,54 @@ def test_refusals_name_their_limit():
         dynamics.control_pooled_host(**args, segments=4, targets={'q': 0.0})
     one = dynamics.control_pooled_host(**args, **NONLINEAR, draws='mean', max_iter=2)
     assert one.cost_draws.shape == (1,) and one.draw_weights.tolist() == [1.0]
+
+
+# ---------------------------------------------------------------------------------------------------------
+# 10. first_trial: the trial half of iteration 0, spelled out
+# ---------------------------------------------------------------------------------------------------------
+
+def _first_passing(Ft, F, noise, slope, moved):
+    """The Armijo decision lane by lane, numbered as the device's wavefront lanes: 0-30 Newton, 32-62 steepest descent."""
+    for half in range(2):
+        for i in range(31):
+            bound = (F + dynamics.ARMIJO * (slope[half, i] if slope[half, i] < 0 else 0.0)) + dynamics.NOISE * noise
+            if moved[half, i] and Ft[half, i] <= bound:
+                return 32 * half + i
+    return -1
+
+
+def test_first_trial_is_the_trial_half_of_iteration_0():
+    args = product(65, 20, spread=0.3)
+    w = 0.25 + np.random.default_rng(3).random(65)
+    w[32] = 0.0
+    kw = dict(**args, **NONLINEAR, starts=2, draw_weights=w, forcing=None, draws=None, bounds=None, control_bounds=None, weights=None,
+              terminal=None, limits=None, limit_weight=1e3, previous=None, init=None, tol=1e-10, keep=None)
+    p = dynamics._prepare_control_pooled(**kw, max_iter=1)
+    z0 = p['z0'].copy()
+    solved = dynamics._control_pooled_solve_host(p)
+    first = dynamics._control_pooled_solve_host(dynamics._prepare_control_pooled(**kw, max_iter=0))
+    assert 'first_trial' not in first and np.array_equal(p['z0'], z0)  # nothing reaches a trial pass; the start is left alone
+    ft, w = solved['first_trial'], p['pool_w']
+    S, E, D = 2, 65, 4
+    assert ft['trial'].shape == (S, D, 2, 31) and ft['Ft_draws'].shape == (S, E, 2, 31) and ft['Ft'].shape == (S, 2, 31)
+    assert ft['reached'].all() and not ft['idle_moved'].any() and np.array_equal(ft['F'], first['first_pass']['F'])
+    assert np.array_equal(ft['g'], first['first_pass']['g'])
+    for s in range(S):
+        for i in range(31):                                            # the steepest-descent half: P(z - 2^-i g)
+            assert np.array_equal(ft['trial'][s, :, 1, i], np.clip(z0[s] + 2.0 ** -i * -ft['g'][s], 0.0, 1.0))
+        step = ft['trial'][s] - z0[s][:, np.newaxis, np.newaxis]
+        slope = np.zeros((2, 31))
+        for d in range(D):
+            slope = slope + ft['g'][s, d] * step[d]
+        assert np.array_equal(ft['slope'][s], slope) and np.array_equal(ft['moved'][s], (step != 0).any(axis=0))
+        assert np.isnan(ft['Ft_draws'][s, 32]).all() and np.isfinite(np.delete(ft['Ft_draws'][s], 32, axis=0)).all()
+        assert np.array_equal(ft['Ft'][s], dynamics.pooled_sum(ft['Ft_draws'][s], w))
+        for half, i, e in ((0, 0, 0), (0, 7, 64), (1, 3, 31), (1, 30, 33)):     # a draw's own cost at a trial point is control's
+            own = dynamics._control_pass(p, np.ascontiguousarray(ft['trial'][s, :, half, i][:, np.newaxis]), np.array([e]))['F'][0]
+            assert own == ft['Ft_draws'][s, e, half, i]
+        lane = _first_passing(ft['Ft'][s], ft['F'][s], ft['noise'][s], ft['slope'][s], ft['moved'][s])
+        assert lane == ft['lane'][s] and lane >= 0 and ft['status'][s] == -1 and ft['descent_steps'][s] == (lane >= 32)
+        assert np.array_equal(ft['z'][s], ft['trial'][s, :, lane // 32, lane % 32])
+    assert np.array_equal(solved['z'], ft['z'])                        # iteration 1 only looks
+    public = dynamics.control_pooled_host(**args, **NONLINEAR, starts=2, draw_weights=w, max_iter=1)
+    assert 'first_trial' not in public and np.array_equal(public.z.ravel(), ft['z'][public.best_start])
