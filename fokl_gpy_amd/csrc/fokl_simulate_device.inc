@@ -87,10 +87,11 @@ struct SimTables {
 
 // h * model_k(at) for every state k after the slope rule; true if a clamp or the rule acted for this lane.  CS is the
 // stride of the coefficients behind cf: SIM_LANES where every lane has its own ([coefficient][lane], cf offset by the lane),
-// 1 where the wavefront shares one set (fokl_assimilate_device.inc: lane = particle of one draw)
-template <int NS, int CS = SIM_LANES>
+// 1 where the wavefront shares one set (fokl_assimilate_device.inc: lane = particle of one draw).  OWN_STEP: the slope is
+// scaled by the lane's own `step` in the place of the wave-uniform sys.h (fokl_simulate_adaptive_device.inc)
+template <int NS, int CS = SIM_LANES, bool OWN_STEP = false>
 __device__ __forceinline__ bool sim_stage(const SimSystem &sys, const SimTables &tab, double *xn, double *fac,
-                                          const double *cf, const double (&at)[NS], double (&dy)[NS])
+                                          const double *cf, const double (&at)[NS], double (&dy)[NS], double step = 0.0)
 {
     bool acted = false;
     // the normalised inputs of state j are [norm_begin[j], norm_begin[j + 1]): j is a compile-time index into the registers
@@ -129,7 +130,7 @@ __device__ __forceinline__ bool sim_stage(const SimSystem &sys, const SimTables 
             delta = ends ? with : delta;
             phi = ends ? 1.0 : phi;
         }
-        double s = (delta + cf[sys.constant[k] * CS]) * sys.h;
+        double s = (delta + cf[sys.constant[k] * CS]) * (OWN_STEP ? step : sys.h);
         const bool outwards = (at[k] >= sys.box_hi[k] && s > 0) || (at[k] <= sys.box_lo[k] && s < 0);
         if (outwards) s = 0;
         acted = acted || outwards;

@@ -33,6 +33,42 @@ The arithmetic (``simulate_host`` is its statement in numpy, the device kernel f
 Step s takes point s of ``t`` to point s + 1.  ``first_saturation[e]`` is the first s in which, for member e, a
 normalised input (a state's or a forcing value's) was clamped or the slope rule changed a slope; -1 if none did.
 
+``simulate_adaptive(..., rtol=1e-6, atol=None, min_halvings=0, max_halvings=10)`` integrates the same system on the same
+output grid with an error statement per member: inside every output step a member takes as many substeps of the scheme above
+as ITS fitted model needs, chosen by step doubling on a dyadic grid.  ``simulate_adaptive_host`` is its statement in numpy;
+only + - * /, ceil, comparisons and integer bookkeeping, in fixed orders (no pow, no sqrt), so the device agrees bit for bit.
+
+Per member, carried over the whole run: the state y and the level k (it starts at ``min_halvings``).  With K =
+``max_halvings`` and FULL = 2^K, output step s takes point s of ``t`` to point s + 1:
+
+  1. forcing      row s serves the whole step (zero-order hold); the forcing factors are formed once, as ``simulate`` forms
+                  them; a forcing clamp counts for ``first_saturation``.  pos = 0
+  2. while pos < FULL:
+       substep    g = h 2^-(k + 1) (an exact scaling of h)
+       full       y1 = one step of ``simulate``'s scheme from y with 2 g in the place of h (stage, clamps, the slope rule on
+                  the scaled slope and the sum (((d1 + 2 d2) + 2 d3) + d4) / 6 unchanged)
+       halves     ya = one such step from y with g; y2 = one such step from ya with g
+       estimate   per state j in order, |.| and max by comparison: d_j = |y2_j - y1_j|,
+                  sc_j = atol_j + rtol max(|y_j|, |y2_j|)
+       ok         d_j <= 15 sc_j for every j: the Richardson estimate d / 15 of y2's local error within tolerance
+       easy       64 d_j <= 15 sc_j for every j: a step twice as long has 32 times the local error, and a factor 2 of safety
+                  (a NaN fails both tests)
+       accept     if ok or k == K: y = y2; pos += FULL >> k; pairs += 1; if not ok the step is forced and
+                  ``first_unresolved`` takes s if it is still -1; if a clamp or the slope rule acted in either half step
+                  ``first_saturation`` takes s if it is still -1; error = r where r > error, r = max_j d_j / (15 sc_j) formed
+                  from 0.0 by r = q where q > r (a NaN is never taken); levels[s] = max(levels[s], k); max_level likewise.
+                  Then, if easy and k > min_halvings and pos mod 2^(K - k + 1) == 0: k -= 1 (pos == FULL is aligned, so a
+                  level can relax at the end of a step)
+       reject     otherwise: k += 1; rejected += 1
+  3. point s + 1 is y
+
+Every iteration advances pos or raises k, and k cannot pass K: the loop ends for any input, NaN coefficients included.  pos
+stays a multiple of FULL >> k, so a pair never crosses an output point.  y2 is accepted as it is (no local extrapolation).
+With ``min_halvings`` = ``max_halvings`` = L every member takes pairs of half steps of h / 2^(L + 1) throughout: the members
+equal ``simulate_host``'s on the grid (start, stop, h / 2^(L + 1)) with every forcing row repeated 2^(L + 1) times, at every
+2^(L + 1)-th point, bit for bit, and ``first_saturation`` equals that run's integer-divided by 2^(L + 1).  A member that meets
+the wall of the box sits on a kink of the right-hand side, which no step size resolves: ``first_unresolved`` says so.
+
 ``assimilate(models, states, inputs, ..., observe, data, ...)`` filters the same system against measurements: a bootstrap
 particle filter of 64 particles per posterior draw, every draw at once on the device.  It returns the filtered states
 (per draw and pooled over the draws), and per draw the log marginal likelihood of the measurements, which normalised
@@ -539,6 +575,14 @@ def _step(p, fac, xn, y, s):
         xn[n], clamp = _clamped((x - p['norm_lo'][n]) / p['norm_span'][n])
         acted |= clamp
     _factor_values(p, fac, xn, 0, p['n_forcing_factors'])
+    y, stages_acted = _stages(p, fac, xn, y)
+    return y, acted | stages_acted
+
+
+def _stages(p, fac, xn, y):
+    """The four stages of one step of size p['h'] (a number, or one per member) from y [K, E], the forcing factors being in
+    ``fac``: -> (y after the step, per member whether a clamp or the slope rule acted)."""
+    acted = np.zeros(y.shape[1], dtype=bool)
     dy = total = None
     for st in range(4):
         reach, weight = (1.0 if st == 3 else 0.5), (2.0 if st in (1, 2) else 1.0)
@@ -625,6 +669,189 @@ def simulate_host(models, states, inputs, forcing=None, y0=None, t=None, draws=N
 
 simulate.__doc__ += _SIGNATURE
 simulate_host.__doc__ += _SIGNATURE
+
+
+# ---------------------------------------------------------------------------------------------------------
+# simulate_adaptive: step doubling on simulate's scheme, on a dyadic grid (module docstring)
+# ---------------------------------------------------------------------------------------------------------
+
+MAX_HALVINGS = 12
+_KEEP_ADAPTIVE = ('members', 'levels')
+
+
+def _prepare_adaptive(models, states, inputs, forcing, y0, t, draws, bounds, ReturnBounds, keep, rtol, atol, min_halvings,
+                      max_halvings):
+    """``_prepare`` and what the error control adds; touches no device."""
+    kept = (keep,) if isinstance(keep, str) else keep
+    if kept is not None and (not isinstance(kept, (tuple, list)) or not 1 <= len(kept) <= 2 or
+                             (len(kept) == 2 and kept[0] == kept[1]) or
+                             any(not isinstance(name, str) or name not in _KEEP_ADAPTIVE for name in kept)):
+        raise ValueError("keep must be None, 'members', 'levels' or a tuple of the two names")
+    kept = tuple(kept or ())
+    p = _prepare(models, states, inputs, forcing, y0, t, draws, bounds, ReturnBounds, 'members' if 'members' in kept else None)
+    K = p['K']
+    try:
+        rtol = float(rtol)
+    except (TypeError, ValueError):
+        rtol = np.nan
+    if not (np.isfinite(rtol) and rtol >= 0):
+        raise ValueError(f"rtol must be finite and not negative, got {rtol}")
+    if atol is None:
+        width = p['box'][:, 1] - p['box'][:, 0]
+        for k, name in enumerate(p['states']):
+            if not np.isfinite(width[k]):
+                raise ValueError(f"state '{name}': its box is unbounded, so the default atol (1e-9 x the box's width) does "
+                                 f"not exist: pass atol")
+        atol = 1e-9 * width
+    else:
+        atol = _per('atol', atol, K, 'state')
+    if not np.all(np.isfinite(atol) & (atol >= 0)):
+        raise ValueError(f"atol must be finite and not negative, got {atol.tolist()}")
+    if rtol == 0 and np.any(atol == 0):
+        raise ValueError(f"rtol == 0 needs a positive atol for every state (the tolerance of a state would be zero), got atol "
+                         f"{atol.tolist()}")
+    levels = []
+    for value in (min_halvings, max_halvings):
+        if isinstance(value, (bool, np.bool_)) or np.ndim(value) != 0 or not isinstance(value, (int, np.integer, float, np.floating)) \
+                or int(value) != value:
+            raise ValueError(f"min_halvings and max_halvings must be integers with 0 <= min_halvings <= max_halvings <= "
+                             f"{MAX_HALVINGS}, got {min_halvings!r} and {max_halvings!r}")
+        levels.append(int(value))
+    if not 0 <= levels[0] <= levels[1] <= MAX_HALVINGS:
+        raise ValueError(f"min_halvings and max_halvings need 0 <= min_halvings <= max_halvings <= {MAX_HALVINGS}, got "
+                         f"{levels[0]} and {levels[1]}")
+    p.update(rtol=rtol, atol=np.ascontiguousarray(atol, dtype=np.float64), min_halvings=levels[0], max_halvings=levels[1],
+             want_levels='levels' in kept)
+    return p
+
+
+def _abs(x):
+    return np.where(x < 0, -x, x)
+
+
+def _run_adaptive_host(p):
+    """-> (members [E, K, P], first_saturation, pairs, rejected, max_level, error, first_unresolved, levels [E, steps])"""
+    K, E, S = p['K'], p['E'], p['n_steps']
+    low, top = p['min_halvings'], p['max_halvings']
+    FULL = 1 << top
+    rtol, atol, h = p['rtol'], p['atol'], p['h']
+    y = p['y0'].copy()
+    members = np.empty((E, K, S + 1))
+    members[:, :, 0] = y.T
+    level = np.full(E, low, dtype=np.int64)
+    pairs, rejected = np.zeros(E, dtype=np.int64), np.zeros(E, dtype=np.int64)
+    max_level, error = np.zeros(E, dtype=np.int32), np.zeros(E)
+    first, unresolved = np.full(E, -1, dtype=np.int32), np.full(E, -1, dtype=np.int32)
+    levels = np.zeros((E, S), dtype=np.int8)
+    fac = np.ones((1 + p['fac_norm'].shape[0], E))
+    n_norms = p['norm_src'].shape[0]
+    for s in range(S):
+        acted = np.zeros(E, dtype=bool)
+        xn = np.zeros((n_norms, E))
+        for n in range(p['n_norm_forcing']):
+            x = np.full(E, p['forcing'][s, -(p['norm_src'][n] + 1)])
+            xn[n], clamp = _clamped((x - p['norm_lo'][n]) / p['norm_span'][n])
+            acted |= clamp
+        _factor_values(p, fac, xn, 0, p['n_forcing_factors'])
+        first[(first < 0) & acted] = s
+        pos = np.zeros(E, dtype=np.int64)
+        while True:
+            live = np.flatnonzero(pos < FULL)                         # the members still inside the step: a mask
+            if live.size == 0:
+                break
+            k = level[live]
+            g = h * np.ldexp(1.0, -(k + 1))                           # an exact scaling
+            q = dict(p, coef=p['coef'][:, live], h=g)
+            qfac, qxn, at = np.ascontiguousarray(fac[:, live]), np.zeros((n_norms, live.size)), y[:, live]
+            with np.errstate(all='ignore'):
+                y1, _ = _stages(dict(q, h=2.0 * g), qfac, qxn, at)
+                ya, acted_a = _stages(q, qfac, qxn, at)
+                y2, acted_b = _stages(q, qfac, qxn, ya)
+                ok, easy = np.ones(live.size, dtype=bool), np.ones(live.size, dtype=bool)
+                r = np.zeros(live.size)
+                for j in range(K):
+                    d = _abs(y2[j] - y1[j])
+                    a, b = _abs(at[j]), _abs(y2[j])
+                    sc = atol[j] + rtol * np.where(b > a, b, a)
+                    ok &= d <= 15.0 * sc
+                    easy &= 64.0 * d <= 15.0 * sc
+                    ratio = d / (15.0 * sc)
+                    r = np.where(ratio > r, ratio, r)
+            accept = ok | (k == top)
+            took = live[accept]
+            ka = k[accept]
+            y[:, took] = y2[:, accept]
+            pos[took] += FULL >> ka
+            pairs[took] += 1
+            forced = took[~ok[accept]]
+            unresolved[forced[unresolved[forced] < 0]] = s
+            hit = took[(acted_a | acted_b)[accept]]
+            first[hit[first[hit] < 0]] = s
+            ra = r[accept]
+            error[took] = np.where(ra > error[took], ra, error[took])
+            levels[took, s] = np.maximum(levels[took, s], ka)
+            max_level[took] = np.maximum(max_level[took], ka)
+            relax = easy[accept] & (ka > low) & (pos[took] % (1 << (top - ka + 1)) == 0)
+            level[took[relax]] -= 1
+            refused = live[~accept]
+            level[refused] += 1
+            rejected[refused] += 1
+        members[:, :, s + 1] = y.T
+    return members, first, pairs, rejected, max_level, error, unresolved, levels
+
+
+def _assemble_adaptive(p, mean, bounds, members, first, pairs, rejected, max_level, error, unresolved, levels):
+    res = _assemble(p, mean, bounds, members, first)
+    res.update(pairs=pairs, rejected=rejected, max_level=max_level, error=error, first_unresolved=unresolved,
+               unresolved_fraction=float(np.mean(unresolved >= 0)), rtol=p['rtol'], atol=p['atol'])
+    if p['want_levels']:
+        res['levels'] = levels
+    return res
+
+
+_SIGNATURE_ADAPTIVE = _SIGNATURE.replace("keep        : 'members' also returns every member's trajectory", """\
+keep        : None, 'members' (also every member's trajectory), 'levels' (also the deepest level accepted inside each
+                  step, [E, steps] int8) or a tuple of the two names
+    rtol, atol  : a pair of half steps is accepted where |y2 - y1| / 15 <= atol_j + rtol max(|y_j|, |y2_j|) for every state
+                  j; atol is a number or one per state, default per state 1e-9 x (box_hi - box_lo) (a state whose box is
+                  unbounded needs an explicit atol)
+    min_halvings, max_halvings : the levels k a member may use, 0 <= min <= max <= 12: its substep is h / 2^(k + 1); at
+                  k == max_halvings a pair is taken whatever its estimate (``first_unresolved`` records the step)""") + """
+    and pairs, rejected [E] int64 (accepted pairs of half steps, rejected trials), max_level [E] int32 (the deepest level
+    of an accepted pair), error [E] (the largest accepted |y2 - y1| / (15 sc); <= 1 unless a step was forced),
+    first_unresolved [E] int32 (the first step in which the finest level still missed the tolerance, -1: never),
+    unresolved_fraction."""
+
+
+def simulate_adaptive(models, states, inputs, forcing=None, y0=None, t=None, draws=None, bounds=None, ReturnBounds=True,
+                      keep=None, rtol=1e-6, atol=None, min_halvings=0, max_halvings=10, device=None):
+    """``simulate`` with an error statement: every member chooses its own substeps inside each output step by step doubling
+    on a dyadic grid, on the device (module docstring).
+
+    device      : device index (default: the process's device, as for ``fit``), a backend or a ``_capi.DeviceContext``"""
+    p = _prepare_adaptive(models, states, inputs, forcing, y0, t, draws, bounds, ReturnBounds, keep, rtol, atol, min_halvings,
+                          max_halvings)
+    ctx = _device_context(device)
+    return _assemble_adaptive(p, *ctx.simulate_adaptive(p))
+
+
+def simulate_adaptive_host(models, states, inputs, forcing=None, y0=None, t=None, draws=None, bounds=None, ReturnBounds=True,
+                           keep=None, rtol=1e-6, atol=None, min_halvings=0, max_halvings=10):
+    """``simulate_adaptive`` in numpy on this host, vectorised over members with masks: the statement the kernel is tested
+    against (module docstring), not a fallback.  Same arguments, same result fields."""
+    p = _prepare_adaptive(models, states, inputs, forcing, y0, t, draws, bounds, ReturnBounds, keep, rtol, atol, min_halvings,
+                          max_halvings)
+    members, *record = _run_adaptive_host(p)
+    mean = np.mean(members, axis=0)
+    band = None
+    if p['want_bounds']:
+        srt = np.sort(members, axis=0)
+        band = np.stack([srt[p['cut']], srt[p['E'] - p['cut']]], axis=-1)
+    return _assemble_adaptive(p, mean, band, members, *record)
+
+
+simulate_adaptive.__doc__ += _SIGNATURE_ADAPTIVE
+simulate_adaptive_host.__doc__ += _SIGNATURE_ADAPTIVE
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -36,6 +36,7 @@
  *                              per posterior draw (fokl_gpy_amd/infer.py), what its last launches ran, and its
  *                              counter-based random numbers as the host sees them
  *   fokl_simulate_ensemble / fokl_simulate_report
+ *   fokl_simulate_adaptive / fokl_simulate_adaptive_report
  *   fokl_assimilate_ensemble / fokl_assimilate_report / fokl_assimilate_rng
  *   fokl_control_solve / fokl_control_report
  *   fokl_control_pooled_solve / fokl_control_pooled_report
@@ -1162,6 +1163,54 @@ int fokl_simulate_ensemble(fokl_ctx *ctx, int n_members, int n_states, int64_t n
  *   out[7]  steps per launch
  */
 int fokl_simulate_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* The same system integrated under an error tolerance (csrc/fokl_simulate_adaptive_device.inc; dynamics.py) */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_SIMULATE_ADAPTIVE_REPORT_LEN 12
+#define FOKL_SIMULATE_ADAPTIVE_MAX_HALVINGS 12
+
+/*
+ * fokl_simulate_ensemble's system, plan and Runge-Kutta step on the same output grid, every member choosing its own substeps
+ * inside each output step by step doubling on a dyadic grid: at level k a trial is one step of 2 g and two steps of
+ * g = h / 2^(k + 1), accepted where |y2 - y1| <= 15 (atol_j + rtol max(|y_j|, |y2_j|)) for every state j or k == max_halvings.
+ * The arithmetic is stated by dynamics.simulate_adaptive_host (the module docstring of fokl_gpy_amd/dynamics.py): every
+ * output equals the host statement's bit for bit.  The arguments up to `cut` are fokl_simulate_ensemble's; then
+ *   rtol, atol [n_states]; min_halvings <= max_halvings: the levels a member may use
+ *   mean, bounds, members, first_saturation: as fokl_simulate_ensemble's
+ *   pairs, rejected [n_members] int64: accepted pairs of half steps, rejected trials
+ *   max_level [n_members] int32: the deepest level of an accepted pair; error [n_members]: the largest accepted
+ *   |y2 - y1| / (15 sc); first_unresolved [n_members] int32: the first step in which a pair was accepted at max_halvings
+ *   outside the tolerance, -1 never; levels [n_members, n_steps] int8 or NULL: the deepest level accepted inside each step.
+ * One lane per member, one wavefront per workgroup, fokl_simulate_ensemble's LDS layout and bound; a lane that has finished
+ * an output step waits for the slowest lane of its wavefront.  The steps are cut into launches of
+ * max(1, FOKL_SIMULATE_ADAPTIVE_PAIRS_PER_LAUNCH >> max_halvings) steps (environment, default 65 536): the cut changes no bit.
+ * No atomics: member e of a large run equals member e run alone.  Refused (FOKL_ERR_ARG with a text that names the limit,
+ * nothing is launched): what fokl_simulate_ensemble refuses, rtol or an atol that is negative or not finite, rtol == 0 with
+ * a zero atol, levels outside 0 <= min_halvings <= max_halvings <= 12.  Kernel times: FOKL_K_INTEGRATE, FOKL_K_BAND.  Blocking.
+ */
+int fokl_simulate_adaptive(fokl_ctx *ctx, int n_members, int n_states, int64_t n_steps, double h, int n_forcing_cols,
+                           const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
+                           const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
+                           const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
+                           const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
+                           const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
+                           const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
+                           const double *y0, const double *box, int cut, double rtol, const double *atol, int min_halvings,
+                           int max_halvings, double *mean, double *bounds, double *members, int32_t *first_saturation,
+                           int64_t *pairs, int64_t *rejected, int32_t *max_level, double *error, int32_t *first_unresolved,
+                           int8_t *levels);
+
+/*
+ * The last fokl_simulate_adaptive call on `ctx`, out [FOKL_SIMULATE_ADAPTIVE_REPORT_LEN] (host values, no launch); zeros
+ * after a call that was refused or failed:
+ *   out[0]  NS: the kernel instance (states)     out[1]  members     out[2]  workgroups = wavefronts = ceil(members / 64)
+ *   out[3]  integration launches     out[4]  steps per launch     out[5]  dynamic LDS bytes     out[6]  spline factors
+ *   out[7]  Bernoulli factors     out[8]  min_halvings     out[9]  max_halvings     out[10] accepted pairs, all members
+ *   out[11] rejected trials, all members
+ */
+int fokl_simulate_adaptive_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* A particle filter of such a system against measurements (csrc/fokl_assimilate_device.inc; dynamics.py)    */
