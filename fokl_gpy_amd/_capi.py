@@ -215,6 +215,11 @@ SIGNATURES = {
                                        c_vp, c_vp, c_vp, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        c_vp, c_vp, c_vp, c_vp]),
     'fokl_simulate_adaptive_report': (c_int, [c_vp, c_vp]),
+    'fokl_simulate_stiff': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
+                                    c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
+                                    c_vp, c_vp, c_vp, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_simulate_stiff_report': (c_int, [c_vp, c_vp]),
     'fokl_assimilate_ensemble': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
                                          c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
                                          c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
@@ -2391,6 +2396,53 @@ class DeviceContext:
         self._ck(self._lib.fokl_simulate_adaptive_report(self._h, _ptr(out)))
         keys = ('NS', 'members', 'workgroups', 'launches', 'steps_per_launch', 'lds_bytes', 'spline_factors',
                 'bernoulli_factors', 'min_halvings', 'max_halvings', 'pairs', 'rejected')
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def simulate_stiff(self, p):
+        """fokl_simulate_stiff for a system prepared by ``dynamics._prepare_stiff`` -> (mean [n_states, P], bounds
+        [n_states, P, 2] or None, members [E, n_states, P] or None, first_saturation [E] int32, steps [E] int64, rejected [E]
+        int64, swaps [E] int64, max_level [E] int32, error [E], first_unresolved [E] int32, levels [E, steps] int8 or None).
+        Needs no uploaded dataset and leaves one alone."""
+        K, E, P = int(p['K']), int(p['E']), int(p['n_steps']) + 1
+        mean = np.empty((K, P), dtype=np.float64)
+        bounds = np.empty((K, P, 2), dtype=np.float64) if p['want_bounds'] else None
+        members = np.empty((E, K, P), dtype=np.float64) if p['want_members'] else None
+        first, unresolved, max_level = (np.empty(E, dtype=np.int32) for _ in range(3))
+        steps, rejected, swaps = (np.empty(E, dtype=np.int64) for _ in range(3))
+        error = np.empty(E, dtype=np.float64)
+        levels = np.zeros((E, P - 1), dtype=np.int8) if p['want_levels'] else None
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
+        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
+        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
+        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
+        coef, y0, box, atol = f64(p['coef']), f64(p['y0']), f64(p['box']), f64(p['atol'])
+        if coef.ndim != 2 or coef.shape[1] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
+                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
+                not (norm_src.shape == norm_lo.shape == norm_span.shape) or atol.shape != (K,) or \
+                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
+                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21:
+            raise ValueError("simulate_stiff: array shapes disagree")
+        self._ck(self._lib.fokl_simulate_stiff(
+            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
+            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
+            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
+            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[0], _ptr(coef), _ptr(y0),
+            _ptr(box), int(p['cut']) if p['want_bounds'] else 0, float(p['rtol']), _ptr(atol), int(p['min_halvings']),
+            int(p['max_halvings']), _ptr(mean), _ptr(bounds), _ptr(members), _ptr(first), _ptr(steps), _ptr(rejected),
+            _ptr(swaps), _ptr(max_level), _ptr(error), _ptr(unresolved), _ptr(levels)))
+        return mean, bounds, members, first, steps, rejected, swaps, max_level, error, unresolved, levels
+
+    def simulate_stiff_report(self):
+        """What the last ``simulate_stiff`` on this context ran (fokl_simulate_stiff_report; host values, no launch): ``NS``
+        (the kernel instance = states), ``members``, ``workgroups`` (= wavefronts = ceil(members / 64)), ``launches`` of the
+        integration kernel, ``steps_per_launch`` (output steps), ``lds_bytes``, ``min_halvings``, ``max_halvings`` and the
+        totals ``steps``, ``rejected`` and ``swaps`` over the members.  Zeros after a refused call."""
+        out = np.zeros(11, dtype=np.int64)
+        self._ck(self._lib.fokl_simulate_stiff_report(self._h, _ptr(out)))
+        keys = ('NS', 'members', 'workgroups', 'launches', 'steps_per_launch', 'lds_bytes', 'min_halvings', 'max_halvings',
+                'steps', 'rejected', 'swaps')
         return dict(zip(keys, (int(v) for v in out)))
 
     def assimilate_ensemble(self, p):

@@ -101,6 +101,7 @@ struct fokl_ctx {
     int64_t design_report[FOKL_DESIGN_REPORT_LEN] = {};           // ... and the last fokl_design_select call
     int64_t simulate_report[FOKL_SIMULATE_REPORT_LEN] = {};       // ... and the last fokl_simulate_ensemble call
     int64_t simulate_adaptive_report[FOKL_SIMULATE_ADAPTIVE_REPORT_LEN] = {};     // ... and the last fokl_simulate_adaptive call
+    int64_t simulate_stiff_report[FOKL_SIMULATE_STIFF_REPORT_LEN] = {};   // ... and the last fokl_simulate_stiff call
     int64_t assimilate_report[FOKL_ASSIMILATE_REPORT_LEN] = {};   // ... and the last fokl_assimilate_ensemble call
     int64_t control_report[FOKL_CONTROL_REPORT_LEN] = {};         // ... and the last fokl_control_solve call
     int64_t control_pooled_report[FOKL_CONTROL_POOLED_REPORT_LEN] = {};   // ... and the last fokl_control_pooled_solve call
@@ -1816,6 +1817,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_integrate_device.inc"
 #include "fokl_simulate_device.inc"
 #include "fokl_simulate_adaptive_device.inc"
+#include "fokl_simulate_stiff_device.inc"
 #include "fokl_assimilate_device.inc"
 #include "fokl_control_device.inc"
 #include "fokl_control_pooled_device.inc"

@@ -68,6 +68,18 @@ extern "C" int fokl_simulate_adaptive(fokl_ctx *, int, int, int64_t, double, int
 }
 extern "C" int fokl_simulate_adaptive_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor the stiff sibling (fokl_simulate_stiff_device.inc); its statement is dynamics.simulate_stiff_host.
+extern "C" int fokl_simulate_stiff(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
+                                   const double *, const double *, int, int, const int32_t *, const int32_t *, const int32_t *,
+                                   const int32_t *, int, const double *, int, const double *, int, const int32_t *,
+                                   const int32_t *, const int32_t *, const int32_t *, int, const double *, const double *,
+                                   const double *, int, double, const double *, int, int, double *, double *, double *,
+                                   int32_t *, int64_t *, int64_t *, int64_t *, int32_t *, double *, int32_t *, int8_t *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_simulate_stiff_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // Nor does the particle filter over such a system (fokl_assimilate_device.inc); its statement is dynamics.assimilate_host,
 // and its random numbers (fokl_assimilate_rng) are host code and present here.
 extern "C" int fokl_assimilate_ensemble(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,

@@ -69,6 +69,43 @@ equal ``simulate_host``'s on the grid (start, stop, h / 2^(L + 1)) with every fo
 2^(L + 1)-th point, bit for bit, and ``first_saturation`` equals that run's integer-divided by 2^(L + 1).  A member that meets
 the wall of the box sits on a kink of the right-hand side, which no step size resolves: ``first_unresolved`` says so.
 
+``simulate_stiff(..., rtol=1e-4, atol=None, min_halvings=0, max_halvings=10)`` is the linearly implicit sibling for members
+whose fitted model is stiff: Rodas3 (four stages, order 3 with an embedded order 2, gamma = 1 / 2, A- and L-stable) under the
+same per-member dyadic controller, so a decayed fast mode no longer chooses the step.  ``simulate_stiff_host`` is its statement
+in numpy; only + - * /, ceil, comparisons and integer bookkeeping, in fixed orders, so the device agrees bit for bit.  On
+dy/dt = b (y - y*) a step of size g multiplies y - y* by R(z) = 8 (z^3 - 6 z + 6) / (3 (z - 2)^4), z = b g.
+
+Per member, carried over the whole run: y and the level k (from ``min_halvings``).  Output step s, K = ``max_halvings``,
+FULL = 2^K; the forcing factors of row s are formed once as above (the system is autonomous inside the step), pos = 0:
+
+  while pos < FULL:
+    step size     g = h 2^-k (an exact scaling); c2 = 2.0 / g, c4 = 4.0 / g, ig = 1.0 / g, c83 = 8.0 / 3.0
+    F(x)          the stage above with a step of 1: clamps, the model, the slope rule on the unscaled slope
+    F0, J         F(y) and J[r][d] = d F_r / d y_d by ``control``'s tangent rules, one direction d at a time: the input of
+                  state j has tangent (1.0 if j == d else 0.0) / span, 0 where its clamp acted; a factor's tangent is its
+                  slope (``_factor_dual``) times its input's tangent, a forcing factor's is 0; a term's
+                  t_phi = t_phi fac + phi t_fac over its slots in order (from 1, 0); t_delta = t_delta + beta t_phi; row r of
+                  J is 0 where the slope rule acted on state r
+    W             W[r][r] = c2 - J[r][r]; W[r][d] = -J[r][d] elsewhere
+    LU            ``stiff_lu``: for column c = 0 .. NS - 1: best = |W[c][c]|, row = c; for r = c + 1 ..: row = r and
+                  best = |W[r][c]| where |W[r][c]| > best (ties and NaN keep the lower row); rows c and row are exchanged
+                  from column c on (the multipliers left of it stay; the exchange is counted); then for r > c: l = W[r][c] / W[c][c], stored in W[r][c], and
+                  W[r][j] = W[r][j] - l W[c][j] for j = c + 1 .. in order.  |x| is -x where x < 0
+    solve(b)      ``stiff_solve``: for c = 0 ..: exchange b[c] and b[row_c]; then for r > c: b[r] = b[r] - W[r][c] b[c];
+                  then for c = NS - 1 .. 0: b[c] = b[c] / W[c][c]; for r = 0 .. c - 1: b[r] = b[r] - W[r][c] b[c]
+    stages        K1 = solve(F0); K2 = solve(F0 + c4 K1); y3 = y + 2.0 K1; K3 = solve(F(y3) + (K1 - K2) ig); y4 = y3 + K3;
+                  K4 = solve(F(y4) + ((K1 - K2) - c83 K3) ig); y_new = y4 + K4; the estimate is K4
+    test          per state j in order: e_j = |K4_j|, sc_j = atol_j + rtol max(|y_j|, |y_new_j|); ok: e_j <= sc_j for every
+                  j; easy: 16.0 e_j <= sc_j for every j (the estimate falls by 8 when g halves, and a factor 2 of safety); a
+                  NaN fails both; r = max_j e_j / sc_j formed from 0.0 by r = q where q > r
+    accept        if ok or k == K: y = y_new; pos += FULL >> k; steps += 1; swaps += the trial's exchanges; forced (not ok)
+                  sets ``first_unresolved``; a clamp or the slope rule in F(y), F(y3) or F(y4) sets ``first_saturation``;
+                  error, levels[s], max_level and the relaxation of k (easy, k > min_halvings, pos aligned) as above
+    reject        otherwise: k += 1; rejected += 1
+
+A zero pivot is not special: the division gives inf or NaN, the trial fails, and at k == K the member takes the NaN as a NaN
+coefficient's member does above.  Three evaluations of F, one Jacobian and one factorisation per trial.
+
 ``assimilate(models, states, inputs, ..., observe, data, ...)`` filters the same system against measurements: a bootstrap
 particle filter of 64 particles per posterior draw, every draw at once on the device.  It returns the filtered states
 (per draw and pooled over the draws), and per draw the log marginal likelihood of the measurements, which normalised
@@ -852,6 +889,265 @@ def simulate_adaptive_host(models, states, inputs, forcing=None, y0=None, t=None
 
 simulate_adaptive.__doc__ += _SIGNATURE_ADAPTIVE
 simulate_adaptive_host.__doc__ += _SIGNATURE_ADAPTIVE
+
+
+# ---------------------------------------------------------------------------------------------------------
+# simulate_stiff: Rodas3 under simulate_adaptive's dyadic controller (module docstring)
+# ---------------------------------------------------------------------------------------------------------
+
+def stiff_lds_rows(n_factors, n_norm_state, n_coef):
+    """Values per member the stiff kernel holds in LDS: ``simulate``'s and one set of tangent rows."""
+    return 2 * (1 + n_factors + n_norm_state) + n_coef
+
+
+def _prepare_stiff(models, states, inputs, forcing, y0, t, draws, bounds, ReturnBounds, keep, rtol, atol, min_halvings,
+                   max_halvings):
+    """``_prepare_adaptive`` and the LDS need of the tangent rows; touches no device."""
+    p = _prepare_adaptive(models, states, inputs, forcing, y0, t, draws, bounds, ReturnBounds, keep, rtol, atol, min_halvings,
+                          max_halvings)
+    n_factors, n_norm_state, n_coef = p['fac_norm'].shape[0], p['norm_src'].shape[0] - p['n_norm_forcing'], p['coef'].shape[0]
+    need = stiff_lds_rows(n_factors, n_norm_state, n_coef)
+    if need > LDS_ROWS:
+        raise ValueError(f"the system needs {need} values per member in LDS (2 x (1 + {n_factors} factors + {n_norm_state} "
+                         f"normalised states) + {n_coef} coefficients: simulate's and one set of tangent rows), a wavefront's "
+                         f"{LDS_BUDGET // 1024} KB hold {LDS_ROWS}")
+    p['lds_rows'] = need
+    return p
+
+
+def _stage_dual(p, fac, xn, at):
+    """F(at) [K, M] (the stage with a step of 1), J [K, K, M] with J[r, d] = d F_r / d y_d, and per member whether a clamp or
+    the slope rule acted.  Direction d is axis 1 of every tangent; each is formed as if it were alone."""
+    K, M = at.shape
+    nF, nN, nNF, nFF = p['fac_norm'].shape[0], p['norm_src'].shape[0], p['n_norm_forcing'], p['n_forcing_factors']
+    cf = p['coef']
+    acted = np.zeros(M, dtype=bool)
+    txn, tfac = np.zeros((nN, K, M)), np.zeros((1 + nF, K, M))
+    unit = np.eye(K)
+    for n in range(nNF, nN):
+        j = p['norm_src'][n]
+        xn[n], clamp = _clamped((at[j] - p['norm_lo'][n]) / p['norm_span'][n])
+        acted |= clamp
+        txn[n] = np.where(clamp, 0.0, np.broadcast_to(unit[j][:, np.newaxis], (K, M)) / p['norm_span'][n])
+    for f in range(nFF, nF):
+        n = p['fac_norm'][f]
+        fac[f + 1], slope = _factor_dual(p, f, xn[n])
+        tfac[f + 1] = slope * txn[n]
+    F, J = np.empty((K, M)), np.empty((K, K, M))
+    zero = np.zeros((K, M))
+    for k in range(K):
+        delta, phi = np.zeros(M), np.ones(M)
+        tdelta, tphi = zero, zero
+        for a, b, c, w in p['entries'][p['entry_begin'][k]:p['entry_begin'][k] + p['entry_count'][k]]:
+            for slot in (a, b, c):
+                tphi = tphi * fac[slot] + phi * tfac[slot]
+                phi = phi * fac[slot]
+            if w >= 0:
+                delta = delta + cf[w] * phi
+                tdelta = tdelta + cf[w] * tphi
+                phi, tphi = np.ones(M), zero
+        s = delta + cf[p['constant'][k]]
+        out = ((at[k] >= p['box'][k, 1]) & (s > 0)) | ((at[k] <= p['box'][k, 0]) & (s < 0))
+        F[k] = np.where(out, 0.0, s)
+        J[k] = np.where(out, 0.0, tdelta)
+        acted |= out
+    return F, J, acted
+
+
+def stiff_lu(W):
+    """LU with partial pivoting of W [K, K, M], one matrix per member, in the statement's order (module docstring) ->
+    (LU [K, K, M]: U on and above the diagonal, the multipliers below it; rows [K, M]: the row exchanged with row c in
+    column c; exchanges [M])."""
+    W = np.array(W, dtype=np.float64)
+    K, M = W.shape[0], W.shape[2]
+    rows, exchanges = np.empty((K, M), dtype=np.int64), np.zeros(M, dtype=np.int64)
+    for c in range(K):
+        best, row = _abs(W[c, c]), np.full(M, c, dtype=np.int64)
+        for r in range(c + 1, K):
+            a = _abs(W[r, c])
+            take = a > best
+            best, row = np.where(take, a, best), np.where(take, r, row)
+        rows[c] = row
+        exchanges += row != c
+        for r in range(c + 1, K):
+            here = row == r
+            upper = W[c, c:].copy()
+            W[c, c:] = np.where(here, W[r, c:], upper)
+            W[r, c:] = np.where(here, upper, W[r, c:])
+        for r in range(c + 1, K):
+            l = W[r, c] / W[c, c]
+            W[r, c] = l
+            for j in range(c + 1, K):
+                W[r, j] = W[r, j] - l * W[c, j]
+    return W, rows, exchanges
+
+
+def stiff_solve(LU, rows, b):
+    """``stiff_lu``'s factors applied to b [K, M] -> W^-1 b, in the statement's order."""
+    b = np.array(b, dtype=np.float64)
+    K = b.shape[0]
+    for c in range(K):
+        for r in range(c + 1, K):
+            here = rows[c] == r
+            upper = b[c].copy()
+            b[c] = np.where(here, b[r], upper)
+            b[r] = np.where(here, upper, b[r])
+        for r in range(c + 1, K):
+            b[r] = b[r] - LU[r, c] * b[c]
+    for c in range(K - 1, -1, -1):
+        b[c] = b[c] / LU[c, c]
+        for r in range(c):
+            b[r] = b[r] - LU[r, c] * b[c]
+    return b
+
+
+def _stiff_trial(q, qfac, qxn, y, g):
+    """One Rodas3 trial of size g [M] from y [K, M] with the forcing factors in ``qfac`` -> (y_new, K4, exchanges, acted,
+    W, LU, rows, F0, K1)."""
+    K = y.shape[0]
+    c2, c4, ig, c83 = 2.0 / g, 4.0 / g, 1.0 / g, 8.0 / 3.0
+    F0, J, acted = _stage_dual(q, qfac, qxn, y)
+    W = -J
+    for r in range(K):
+        W[r, r] = c2 - J[r, r]
+    LU, rows, exchanges = stiff_lu(W)
+    K1 = stiff_solve(LU, rows, F0)
+    K2 = stiff_solve(LU, rows, F0 + c4 * K1)
+    y3 = y + 2.0 * K1
+    F3, acted3 = _stage(q, qfac, qxn, y3)
+    K3 = stiff_solve(LU, rows, F3 + (K1 - K2) * ig)
+    y4 = y3 + K3
+    F4, acted4 = _stage(q, qfac, qxn, y4)
+    K4 = stiff_solve(LU, rows, F4 + ((K1 - K2) - c83 * K3) * ig)
+    return y4 + K4, K4, exchanges, acted | acted3 | acted4, W, LU, rows, F0, K1
+
+
+def _run_stiff_host(p, trial_hook=None):
+    """-> (members [E, K, P], first_saturation, steps, rejected, swaps, max_level, error, first_unresolved, levels [E, steps]).
+    ``trial_hook(s, live, W, LU, rows, F0, K1)`` sees every trial (tests)."""
+    K, E, S = p['K'], p['E'], p['n_steps']
+    low, top = p['min_halvings'], p['max_halvings']
+    FULL = 1 << top
+    rtol, atol, h = p['rtol'], p['atol'], p['h']
+    y = p['y0'].copy()
+    members = np.empty((E, K, S + 1))
+    members[:, :, 0] = y.T
+    level = np.full(E, low, dtype=np.int64)
+    steps, rejected, swaps = (np.zeros(E, dtype=np.int64) for _ in range(3))
+    max_level, error = np.zeros(E, dtype=np.int32), np.zeros(E)
+    first, unresolved = np.full(E, -1, dtype=np.int32), np.full(E, -1, dtype=np.int32)
+    levels = np.zeros((E, S), dtype=np.int8)
+    fac = np.ones((1 + p['fac_norm'].shape[0], E))
+    n_norms = p['norm_src'].shape[0]
+    for s in range(S):
+        acted = np.zeros(E, dtype=bool)
+        xn = np.zeros((n_norms, E))
+        for n in range(p['n_norm_forcing']):
+            x = np.full(E, p['forcing'][s, -(p['norm_src'][n] + 1)])
+            xn[n], clamp = _clamped((x - p['norm_lo'][n]) / p['norm_span'][n])
+            acted |= clamp
+        _factor_values(p, fac, xn, 0, p['n_forcing_factors'])
+        first[(first < 0) & acted] = s
+        pos = np.zeros(E, dtype=np.int64)
+        while True:
+            live = np.flatnonzero(pos < FULL)                         # the members still inside the step: a mask
+            if live.size == 0:
+                break
+            k = level[live]
+            g = h * np.ldexp(1.0, -k)                                 # an exact scaling
+            q = dict(p, coef=p['coef'][:, live], h=1.0)
+            qfac, qxn, at = np.ascontiguousarray(fac[:, live]), np.zeros((n_norms, live.size)), y[:, live]
+            with np.errstate(all='ignore'):
+                y_new, est, exchanges, trial_acted, *seen = _stiff_trial(q, qfac, qxn, at, g)
+                ok, easy = np.ones(live.size, dtype=bool), np.ones(live.size, dtype=bool)
+                r = np.zeros(live.size)
+                for j in range(K):
+                    d = _abs(est[j])
+                    a, b = _abs(at[j]), _abs(y_new[j])
+                    sc = atol[j] + rtol * np.where(b > a, b, a)
+                    ok &= d <= sc
+                    easy &= 16.0 * d <= sc
+                    ratio = d / sc
+                    r = np.where(ratio > r, ratio, r)
+            if trial_hook is not None:
+                trial_hook(s, live, *seen)
+            accept = ok | (k == top)
+            took = live[accept]
+            ka = k[accept]
+            y[:, took] = y_new[:, accept]
+            pos[took] += FULL >> ka
+            steps[took] += 1
+            swaps[took] += exchanges[accept]
+            forced = took[~ok[accept]]
+            unresolved[forced[unresolved[forced] < 0]] = s
+            hit = took[trial_acted[accept]]
+            first[hit[first[hit] < 0]] = s
+            ra = r[accept]
+            error[took] = np.where(ra > error[took], ra, error[took])
+            levels[took, s] = np.maximum(levels[took, s], ka)
+            max_level[took] = np.maximum(max_level[took], ka)
+            relax = easy[accept] & (ka > low) & (pos[took] % (1 << (top - ka + 1)) == 0)
+            level[took[relax]] -= 1
+            refused = live[~accept]
+            level[refused] += 1
+            rejected[refused] += 1
+        members[:, :, s + 1] = y.T
+    return members, first, steps, rejected, swaps, max_level, error, unresolved, levels
+
+
+def _assemble_stiff(p, mean, bounds, members, first, steps, rejected, swaps, max_level, error, unresolved, levels):
+    res = _assemble(p, mean, bounds, members, first)
+    res.update(steps=steps, rejected=rejected, swaps=swaps, max_level=max_level, error=error, first_unresolved=unresolved,
+               unresolved_fraction=float(np.mean(unresolved >= 0)), rtol=p['rtol'], atol=p['atol'])
+    if p['want_levels']:
+        res['levels'] = levels
+    return res
+
+
+_SIGNATURE_STIFF = _SIGNATURE.replace("keep        : 'members' also returns every member's trajectory", """\
+keep        : None, 'members' (also every member's trajectory), 'levels' (also the deepest level accepted inside each
+                  step, [E, steps] int8) or a tuple of the two names
+    rtol, atol  : a step is accepted where the embedded estimate |K4_j| <= atol_j + rtol max(|y_j|, |y_new_j|) for every state
+                  j; atol is a number or one per state, default per state 1e-9 x (box_hi - box_lo) (a state whose box is
+                  unbounded needs an explicit atol)
+    min_halvings, max_halvings : the levels k a member may use, 0 <= min <= max <= 12: its step is h / 2^k; at
+                  k == max_halvings a step is taken whatever its estimate (``first_unresolved`` records the output step)""") + """
+    and steps, rejected, swaps [E] int64 (accepted steps, rejected trials, row exchanges of the accepted steps' factorisations),
+    max_level [E] int32 (the deepest level of an accepted step), error [E] (the largest accepted |K4| / sc; <= 1 unless a
+    step was forced), first_unresolved [E] int32 (the first output step in which the finest level still missed the tolerance,
+    -1: never), unresolved_fraction."""
+
+
+def simulate_stiff(models, states, inputs, forcing=None, y0=None, t=None, draws=None, bounds=None, ReturnBounds=True,
+                   keep=None, rtol=1e-4, atol=None, min_halvings=0, max_halvings=10, device=None):
+    """``simulate_adaptive`` for stiff members: the linearly implicit Rodas3 step (order 3, L-stable) under the same per-member
+    dyadic step control, on the device (module docstring).
+
+    device      : device index (default: the process's device, as for ``fit``), a backend or a ``_capi.DeviceContext``"""
+    p = _prepare_stiff(models, states, inputs, forcing, y0, t, draws, bounds, ReturnBounds, keep, rtol, atol, min_halvings,
+                       max_halvings)
+    ctx = _device_context(device)
+    return _assemble_stiff(p, *ctx.simulate_stiff(p))
+
+
+def simulate_stiff_host(models, states, inputs, forcing=None, y0=None, t=None, draws=None, bounds=None, ReturnBounds=True,
+                        keep=None, rtol=1e-4, atol=None, min_halvings=0, max_halvings=10, trial_hook=None):
+    """``simulate_stiff`` in numpy on this host, vectorised over members with masks: the statement the kernel is tested
+    against (module docstring), not a fallback.  Same arguments, same result fields.  ``trial_hook(s, live, W, LU, rows,
+    F0, K1)`` is called with every trial's matrix, its factors, F(y) and the first stage, for the members ``live`` of output step s."""
+    p = _prepare_stiff(models, states, inputs, forcing, y0, t, draws, bounds, ReturnBounds, keep, rtol, atol, min_halvings,
+                       max_halvings)
+    members, *record = _run_stiff_host(p, trial_hook)
+    mean = np.mean(members, axis=0)
+    band = None
+    if p['want_bounds']:
+        srt = np.sort(members, axis=0)
+        band = np.stack([srt[p['cut']], srt[p['E'] - p['cut']]], axis=-1)
+    return _assemble_stiff(p, mean, band, members, *record)
+
+
+simulate_stiff.__doc__ += _SIGNATURE_STIFF
+simulate_stiff_host.__doc__ += _SIGNATURE_STIFF
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -37,6 +37,7 @@
  *                              counter-based random numbers as the host sees them
  *   fokl_simulate_ensemble / fokl_simulate_report
  *   fokl_simulate_adaptive / fokl_simulate_adaptive_report
+ *   fokl_simulate_stiff / fokl_simulate_stiff_report
  *   fokl_assimilate_ensemble / fokl_assimilate_report / fokl_assimilate_rng
  *   fokl_control_solve / fokl_control_report
  *   fokl_control_pooled_solve / fokl_control_pooled_report
@@ -1211,6 +1212,51 @@ int fokl_simulate_adaptive(fokl_ctx *ctx, int n_members, int n_states, int64_t n
  *   out[11] rejected trials, all members
  */
 int fokl_simulate_adaptive_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* The same system for stiff members: Rodas3 (csrc/fokl_simulate_stiff_device.inc; dynamics.py)             */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_SIMULATE_STIFF_REPORT_LEN 11
+
+/*
+ * fokl_simulate_adaptive's system, plan, output grid and per-member dyadic step control with a linearly implicit step: at
+ * level k a trial is one Rodas3 step of g = h / 2^k (four stages, order 3 with an embedded order 2, gamma = 1 / 2, L-stable):
+ * the Jacobian of the right-hand side by forward tangents, W = (2 / g) I - J factorised once by LU with partial pivoting,
+ * four solves; accepted where the estimate |K4_j| <= atol_j + rtol max(|y_j|, |y_new_j|) for every state j or
+ * k == max_halvings.  The arithmetic is stated by dynamics.simulate_stiff_host (the module docstring of
+ * fokl_gpy_amd/dynamics.py): every output equals the host statement's bit for bit.  The arguments are
+ * fokl_simulate_adaptive's, except
+ *   steps, rejected, swaps [n_members] int64: accepted steps, rejected trials, row exchanges in the factorisations of the
+ *   accepted steps; error [n_members]: the largest accepted |K4| / sc.
+ * One lane per member, one wavefront per workgroup; W, the pivot rows and the stages are per-lane registers; LDS holds
+ * fokl_simulate_ensemble's rows and one set of tangent rows: (2 (1 + factors + normalised states) + coefficients) x 64 x 8
+ * bytes.  The steps are cut into launches of max(1, FOKL_SIMULATE_STIFF_SUBSTEPS_PER_LAUNCH >> max_halvings) output steps
+ * (environment, default 65 536): the cut changes no bit.  No atomics: member e of a large run equals member e run alone.
+ * Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched): what fokl_simulate_adaptive refuses, and a
+ * system whose LDS need exceeds the 144 KB of a wavefront.  Kernel times: FOKL_K_INTEGRATE, FOKL_K_BAND.  Blocking.
+ */
+int fokl_simulate_stiff(fokl_ctx *ctx, int n_members, int n_states, int64_t n_steps, double h, int n_forcing_cols,
+                        const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
+                        const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
+                        const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
+                        const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
+                        const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
+                        const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
+                        const double *y0, const double *box, int cut, double rtol, const double *atol, int min_halvings,
+                        int max_halvings, double *mean, double *bounds, double *members, int32_t *first_saturation,
+                        int64_t *steps, int64_t *rejected, int64_t *swaps, int32_t *max_level, double *error,
+                        int32_t *first_unresolved, int8_t *levels);
+
+/*
+ * The last fokl_simulate_stiff call on `ctx`, out [FOKL_SIMULATE_STIFF_REPORT_LEN] (host values, no launch); zeros after a
+ * call that was refused or failed:
+ *   out[0]  NS: the kernel instance (states)     out[1]  members     out[2]  workgroups = wavefronts = ceil(members / 64)
+ *   out[3]  integration launches     out[4]  output steps per launch     out[5]  dynamic LDS bytes     out[6]  min_halvings
+ *   out[7]  max_halvings     out[8]  accepted steps, all members     out[9]  rejected trials, all members
+ *   out[10] row exchanges of the accepted steps, all members
+ */
+int fokl_simulate_stiff_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* A particle filter of such a system against measurements (csrc/fokl_assimilate_device.inc; dynamics.py)    */
