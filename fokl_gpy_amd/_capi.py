@@ -206,42 +206,24 @@ SIGNATURES = {
                                   c_dbl, c_vp, c_vp]),
     'fokl_gp_integrate_ensemble': (c_int, [c_vp, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_vp, c_vp, c_int, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
-    'fokl_simulate_ensemble': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
-                                       c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
-                                       c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_simulate_ensemble': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     'fokl_simulate_report': (c_int, [c_vp, c_vp]),
-    'fokl_simulate_adaptive': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
-                                       c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
-                                       c_vp, c_vp, c_vp, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                       c_vp, c_vp, c_vp, c_vp]),
+    'fokl_simulate_adaptive': (c_int, [c_vp, c_vp, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp]),
     'fokl_simulate_adaptive_report': (c_int, [c_vp, c_vp]),
-    'fokl_simulate_stiff': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
-                                    c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
-                                    c_vp, c_vp, c_vp, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                    c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_simulate_stiff': (c_int, [c_vp, c_vp, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp]),
     'fokl_simulate_stiff_report': (c_int, [c_vp, c_vp]),
-    'fokl_assimilate_ensemble': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
-                                         c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
-                                         c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl,
-                                         ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_assimilate_ensemble': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, ctypes.c_uint32,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_assimilate_report': (c_int, [c_vp, c_vp]),
-    'fokl_control_solve': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp,
-                                   c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,
-                                   c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp,
-                                   c_int, c_int, c_vp, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                   c_vp, c_vp]),
+    'fokl_control_solve': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_control_report': (c_int, [c_vp, c_vp]),
-    'fokl_control_pooled_solve': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
-                                          c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
-                                          c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp,
-                                          c_vp, c_int, c_int, c_vp, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                          c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_control_pooled_solve': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp]),
     'fokl_control_pooled_report': (c_int, [c_vp, c_vp]),
-    'fokl_control_cvar_solve': (c_int, [c_vp, c_int, c_int, c_i64, c_dbl, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int,
-                                        c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
-                                        c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp,
-                                        c_vp, c_int, c_int, c_vp, c_int, c_dbl, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp,
-                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_control_cvar_solve': (c_int, [c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_control_cvar_report': (c_int, [c_vp, c_vp]),
     'fokl_assimilate_rng': (c_int, [ctypes.c_uint32, c_vp, c_int, ctypes.c_uint32, c_int, c_int, c_vp]),
     'fokl_model_optimize': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_dbl,
@@ -1829,6 +1811,71 @@ class _FirstTrialStruct(ctypes.Structure):
                                                       'status', 'descent')]
 
 
+class _SystemStruct(ctypes.Structure):
+    """fokl_system (include/fokl_hip_internal.h)"""
+    _fields_ = [('n_members', c_int), ('n_states', c_int), ('n_steps', c_i64), ('h', c_dbl), ('n_forcing_cols', c_int),
+                ('forcing', c_vp), ('n_norm_forcing', c_int), ('n_norm', c_int), ('norm_src', c_vp), ('norm_lo', c_vp),
+                ('norm_span', c_vp), ('n_forcing_factors', c_int), ('n_factors', c_int), ('fac_norm', c_vp), ('fac_kind', c_vp),
+                ('fac_row', c_vp), ('fac_degree', c_vp), ('n_spline_rows', c_int), ('spline_table', c_vp), ('n_bern_rows', c_int),
+                ('bern_table', c_vp), ('n_entries', c_int), ('entries', c_vp), ('entry_begin', c_vp), ('entry_count', c_vp),
+                ('constant', c_vp), ('n_coef', c_int), ('coef', c_vp), ('y0', c_vp), ('box', c_vp)]
+
+
+class _ControlProblemStruct(ctypes.Structure):
+    """fokl_control_problem (include/fokl_hip_internal.h)"""
+    _fields_ = [('n_controls', c_int), ('n_segments', c_int), ('seg_first', c_vp), ('norm_control', c_vp), ('ctl_lo', c_vp),
+                ('ctl_width', c_vp), ('ref', c_vp), ('track_weight', c_vp), ('terminal_weight', c_vp), ('limit_lo', c_vp),
+                ('limit_hi', c_vp), ('limit_weight', c_dbl), ('move_weight', c_vp), ('previous', c_vp), ('has_previous', c_int),
+                ('n_starts', c_int), ('z0', c_vp), ('max_iter', c_int), ('tol', c_dbl)]
+
+
+_i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+_f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _system_struct(p, who, coef_by_draw):
+    """The fokl_system of a prepared ``p`` -> (struct, the arrays it points into: the caller keeps them referenced until the
+    call has returned).  ``coef_by_draw``: coef goes as [E, n_coef] (assimilate, control), otherwise as [n_coef, E]."""
+    K, E, steps = int(p['K']), int(p['E']), int(p['n_steps'])
+    a = dict(forcing=_f64(p['forcing']), norm_src=_i32(p['norm_src']), norm_lo=_f64(p['norm_lo']), norm_span=_f64(p['norm_span']),
+             fac_norm=_i32(p['fac_norm']), fac_kind=_i32(p['fac_kind']), fac_row=_i32(p['fac_row']), fac_degree=_i32(p['fac_degree']),
+             spline_table=_f64(p['spline_table']), bern_table=_f64(p['bern_table']), entries=_i32(p['entries']).reshape(-1, 4),
+             entry_begin=_i32(p['entry_begin']), entry_count=_i32(p['entry_count']), constant=_i32(p['constant']),
+             coef=_f64(np.asarray(p['coef']).T if coef_by_draw else p['coef']), y0=_f64(p['y0']), box=_f64(p['box']))
+    coef, forcing, bern = a['coef'], a['forcing'], a['bern_table']
+    if coef.ndim != 2 or coef.shape[0 if coef_by_draw else 1] != E or a['y0'].shape != (K, E) or a['box'].shape != (K, 2) or \
+            a['entry_begin'].shape != (K,) or a['entry_count'].shape != (K,) or a['constant'].shape != (K,) or \
+            forcing.ndim != 2 or forcing.shape[0] != steps or \
+            not (a['norm_src'].shape == a['norm_lo'].shape == a['norm_span'].shape) or \
+            not (a['fac_norm'].shape == a['fac_kind'].shape == a['fac_row'].shape == a['fac_degree'].shape) or \
+            a['spline_table'].shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21:
+        raise ValueError(f"{who}: array shapes disagree")
+    struct = _SystemStruct(n_members=E, n_states=K, n_steps=steps, h=float(p['h']), n_forcing_cols=forcing.shape[1],
+                           n_norm_forcing=int(p['n_norm_forcing']), n_norm=a['norm_src'].shape[0],
+                           n_forcing_factors=int(p['n_forcing_factors']), n_factors=a['fac_norm'].shape[0],
+                           n_spline_rows=a['spline_table'].shape[0], n_bern_rows=bern.shape[0], n_entries=a['entries'].shape[0],
+                           n_coef=coef.shape[1 if coef_by_draw else 0], **{name: _ptr(arr) for name, arr in a.items()})
+    return struct, a
+
+
+def _control_problem_struct(p, who):
+    """The fokl_control_problem of a ``p`` prepared by ``dynamics._prepare_control`` -> (struct, the arrays it points into)."""
+    K, P, S, D, nc = int(p['K']), int(p['n_steps']) + 1, int(p['starts']), int(p['D']), int(p['n_controls'])
+    a = dict(seg_first=_i32(p['seg_first']), norm_control=_i32(p['norm_control']), ctl_lo=_f64(p['ctl_lo']),
+             ctl_width=_f64(p['ctl_width']), ref=_f64(p['ref']), track_weight=_f64(p['wt']), terminal_weight=_f64(p['term']),
+             limit_lo=_f64(p['lim_lo']), limit_hi=_f64(p['lim_hi']), move_weight=_f64(p['move']), previous=_f64(p['prev']),
+             z0=_f64(p['z0']))
+    if a['seg_first'].ndim != 1 or D != nc * a['seg_first'].shape[0] or a['norm_control'].shape != (int(p['n_norm_forcing']),) or \
+            any(a[key].shape != (nc,) for key in ('ctl_lo', 'ctl_width', 'move_weight', 'previous')) or a['ref'].shape != (K, P) or \
+            any(a[key].shape != (K,) for key in ('track_weight', 'terminal_weight', 'limit_lo', 'limit_hi')) or \
+            a['z0'].shape != (S, D):
+        raise ValueError(f"{who}: array shapes disagree")
+    struct = _ControlProblemStruct(n_controls=nc, n_segments=a['seg_first'].shape[0], limit_weight=float(p['hl']),
+                                   has_previous=int(bool(p['has_previous'])), n_starts=S, max_iter=int(p['max_iter']),
+                                   tol=float(p['tol']), **{name: _ptr(arr) for name, arr in a.items()})
+    return struct, a
+
+
 class _FirstTrial:
     """The host buffers behind a fokl_control_first_trial, and what they hold as ``dynamics``' ``first_trial`` dict."""
 
@@ -2319,25 +2366,10 @@ class DeviceContext:
         bounds = np.empty((K, P, 2), dtype=np.float64) if p['want_bounds'] else None
         members = np.empty((E, K, P), dtype=np.float64) if p['want_members'] else None
         first = np.empty(E, dtype=np.int32)
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
-        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
-        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
-        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
-        coef, y0, box = f64(p['coef']), f64(p['y0']), f64(p['box'])
-        if coef.ndim != 2 or coef.shape[1] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
-                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
-                not (norm_src.shape == norm_lo.shape == norm_span.shape) or \
-                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
-                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21:
-            raise ValueError("simulate_ensemble: array shapes disagree")
-        self._ck(self._lib.fokl_simulate_ensemble(
-            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
-            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
-            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
-            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[0], _ptr(coef), _ptr(y0),
-            _ptr(box), int(p['cut']) if p['want_bounds'] else 0, _ptr(mean), _ptr(bounds), _ptr(members), _ptr(first)))
+        system, held = _system_struct(p, 'simulate_ensemble', coef_by_draw=False)
+        self._ck(self._lib.fokl_simulate_ensemble(self._h, ctypes.byref(system), int(p['cut']) if p['want_bounds'] else 0,
+                                                  _ptr(mean), _ptr(bounds), _ptr(members), _ptr(first)))
+        del held
         return mean, bounds, members, first
 
     def simulate_report(self):
@@ -2363,27 +2395,15 @@ class DeviceContext:
         first, unresolved, max_level = (np.empty(E, dtype=np.int32) for _ in range(3))
         pairs, rejected, error = np.empty(E, dtype=np.int64), np.empty(E, dtype=np.int64), np.empty(E, dtype=np.float64)
         levels = np.zeros((E, P - 1), dtype=np.int8) if p['want_levels'] else None
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
-        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
-        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
-        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
-        coef, y0, box, atol = f64(p['coef']), f64(p['y0']), f64(p['box']), f64(p['atol'])
-        if coef.ndim != 2 or coef.shape[1] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
-                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
-                not (norm_src.shape == norm_lo.shape == norm_span.shape) or atol.shape != (K,) or \
-                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
-                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21:
+        system, held = _system_struct(p, 'simulate_adaptive', coef_by_draw=False)
+        atol = _f64(p['atol'])
+        if atol.shape != (K,):
             raise ValueError("simulate_adaptive: array shapes disagree")
         self._ck(self._lib.fokl_simulate_adaptive(
-            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
-            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
-            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
-            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[0], _ptr(coef), _ptr(y0),
-            _ptr(box), int(p['cut']) if p['want_bounds'] else 0, float(p['rtol']), _ptr(atol), int(p['min_halvings']),
-            int(p['max_halvings']), _ptr(mean), _ptr(bounds), _ptr(members), _ptr(first), _ptr(pairs), _ptr(rejected),
-            _ptr(max_level), _ptr(error), _ptr(unresolved), _ptr(levels)))
+            self._h, ctypes.byref(system), int(p['cut']) if p['want_bounds'] else 0, float(p['rtol']), _ptr(atol),
+            int(p['min_halvings']), int(p['max_halvings']), _ptr(mean), _ptr(bounds), _ptr(members), _ptr(first), _ptr(pairs),
+            _ptr(rejected), _ptr(max_level), _ptr(error), _ptr(unresolved), _ptr(levels)))
+        del held
         return mean, bounds, members, first, pairs, rejected, max_level, error, unresolved, levels
 
     def simulate_adaptive_report(self):
@@ -2411,27 +2431,15 @@ class DeviceContext:
         steps, rejected, swaps = (np.empty(E, dtype=np.int64) for _ in range(3))
         error = np.empty(E, dtype=np.float64)
         levels = np.zeros((E, P - 1), dtype=np.int8) if p['want_levels'] else None
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
-        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
-        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
-        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
-        coef, y0, box, atol = f64(p['coef']), f64(p['y0']), f64(p['box']), f64(p['atol'])
-        if coef.ndim != 2 or coef.shape[1] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
-                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
-                not (norm_src.shape == norm_lo.shape == norm_span.shape) or atol.shape != (K,) or \
-                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
-                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21:
+        system, held = _system_struct(p, 'simulate_stiff', coef_by_draw=False)
+        atol = _f64(p['atol'])
+        if atol.shape != (K,):
             raise ValueError("simulate_stiff: array shapes disagree")
         self._ck(self._lib.fokl_simulate_stiff(
-            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
-            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
-            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
-            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[0], _ptr(coef), _ptr(y0),
-            _ptr(box), int(p['cut']) if p['want_bounds'] else 0, float(p['rtol']), _ptr(atol), int(p['min_halvings']),
-            int(p['max_halvings']), _ptr(mean), _ptr(bounds), _ptr(members), _ptr(first), _ptr(steps), _ptr(rejected),
-            _ptr(swaps), _ptr(max_level), _ptr(error), _ptr(unresolved), _ptr(levels)))
+            self._h, ctypes.byref(system), int(p['cut']) if p['want_bounds'] else 0, float(p['rtol']), _ptr(atol),
+            int(p['min_halvings']), int(p['max_halvings']), _ptr(mean), _ptr(bounds), _ptr(members), _ptr(first), _ptr(steps),
+            _ptr(rejected), _ptr(swaps), _ptr(max_level), _ptr(error), _ptr(unresolved), _ptr(levels)))
+        del held
         return mean, bounds, members, first, steps, rejected, swaps, max_level, error, unresolved, levels
 
     def simulate_stiff_report(self):
@@ -2451,23 +2459,12 @@ class DeviceContext:
         weights [E, n_obs, 64] or None, first_saturation [E] int32, collapsed [E] int32).  Needs no uploaded dataset and
         leaves one alone."""
         K, E, P = int(p['K']), int(p['E']), int(p['n_steps']) + 1
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
-        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
-        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
-        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
-        coef, y0, box = f64(np.asarray(p['coef']).T), f64(p['y0']), f64(p['box'])
+        system, held = _system_struct(p, 'assimilate_ensemble', coef_by_draw=True)
         ids = np.ascontiguousarray(p['draw_ids'], dtype=np.uint32)
-        obs_state, obs_sd, obs_row = i32(p['obs_state']), f64(p['obs_sd']), i32(p['obs_row'])
-        data, obs_const, q, y0_sd = f64(p['data']), f64(p['obs_const']), f64(p['process_q']), f64(p['y0_sd'])
+        obs_state, obs_sd, obs_row = _i32(p['obs_state']), _f64(p['obs_sd']), _i32(p['obs_row'])
+        data, obs_const, q, y0_sd = _f64(p['data']), _f64(p['obs_const']), _f64(p['process_q']), _f64(p['y0_sd'])
         n_obs = data.shape[0] if data.ndim == 2 else -1
-        if coef.ndim != 2 or coef.shape[0] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
-                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
-                not (norm_src.shape == norm_lo.shape == norm_span.shape) or \
-                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
-                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21 or ids.shape != (E,) or \
-                obs_state.ndim != 1 or obs_sd.shape != obs_state.shape or data.ndim != 2 or \
+        if ids.shape != (E,) or obs_state.ndim != 1 or obs_sd.shape != obs_state.shape or data.ndim != 2 or \
                 data.shape[1] != obs_state.shape[0] or obs_row.shape != (P,) or obs_const.shape != (n_obs,) or \
                 q.shape != (K,) or y0_sd.shape != (K,):
             raise ValueError("assimilate_ensemble: array shapes disagree")
@@ -2477,13 +2474,10 @@ class DeviceContext:
         weights = np.empty((E, n_obs, ASSIMILATE_PARTICLES), dtype=np.float64) if keep else None
         first, collapsed = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
         self._ck(self._lib.fokl_assimilate_ensemble(
-            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
-            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
-            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
-            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[1], _ptr(coef), _ptr(y0),
-            _ptr(box), _ptr(ids), obs_state.shape[0], _ptr(obs_state), _ptr(obs_sd), n_obs, _ptr(obs_row), _ptr(data),
-            _ptr(obs_const), _ptr(q), _ptr(y0_sd), float(p['threshold']), int(p['seed']) & 0xFFFFFFFF, _ptr(stats),
+            self._h, ctypes.byref(system), _ptr(ids), obs_state.shape[0], _ptr(obs_state), _ptr(obs_sd), n_obs, _ptr(obs_row),
+            _ptr(data), _ptr(obs_const), _ptr(q), _ptr(y0_sd), float(p['threshold']), int(p['seed']) & 0xFFFFFFFF, _ptr(stats),
             _ptr(particles), _ptr(weights), _ptr(first), _ptr(collapsed)))
+        del held
         return stats, particles, weights, first, collapsed
 
     def assimilate_report(self):
@@ -2503,26 +2497,8 @@ class DeviceContext:
         iterations, descent_steps [E, S] and, for max_iter == 0, ``first_pass`` (F [E, S], g [E, S, D], H [E, S, D, D]).  Needs no uploaded
         dataset and leaves one alone."""
         K, E, P, S, D = int(p['K']), int(p['E']), int(p['n_steps']) + 1, int(p['starts']), int(p['D'])
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
-        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
-        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
-        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
-        coef, y0, box = f64(np.asarray(p['coef']).T), f64(p['y0']), f64(p['box'])
-        seg_first, norm_control = i32(p['seg_first']), i32(p['norm_control'])
-        lo, width, ref, z0 = f64(p['ctl_lo']), f64(p['ctl_width']), f64(p['ref']), f64(p['z0'])
-        wt, term, lim_lo, lim_hi, move, prev = (f64(p[key]) for key in ('wt', 'term', 'lim_lo', 'lim_hi', 'move', 'prev'))
-        nc = int(p['n_controls'])
-        if coef.ndim != 2 or coef.shape[0] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
-                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
-                not (norm_src.shape == norm_lo.shape == norm_span.shape) or \
-                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
-                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21 or seg_first.ndim != 1 or \
-                D != nc * seg_first.shape[0] or norm_control.shape != (int(p['n_norm_forcing']),) or lo.shape != (nc,) or \
-                width.shape != (nc,) or move.shape != (nc,) or prev.shape != (nc,) or ref.shape != (K, P) or \
-                not (wt.shape == term.shape == lim_lo.shape == lim_hi.shape == (K,)) or z0.shape != (S, D):
-            raise ValueError("control_solve: array shapes disagree")
+        system, held = _system_struct(p, 'control_solve', coef_by_draw=True)
+        problem, held_problem = _control_problem_struct(p, 'control_solve')
         z = np.empty((E, S, D), dtype=np.float64)
         cost, cost_start = np.empty((E, S), dtype=np.float64), np.empty((E, S), dtype=np.float64)
         status, iterations = np.empty((E, S), dtype=np.int32), np.empty((E, S), dtype=np.int32)
@@ -2534,14 +2510,9 @@ class DeviceContext:
         fg = np.empty((E, S, D), dtype=np.float64) if want_first else None
         fH = np.empty((E, S, D, D), dtype=np.float64) if want_first else None
         self._ck(self._lib.fokl_control_solve(
-            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
-            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
-            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
-            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[1], _ptr(coef), _ptr(y0),
-            _ptr(box), nc, seg_first.shape[0], _ptr(seg_first), _ptr(norm_control), _ptr(lo), _ptr(width), _ptr(ref), _ptr(wt),
-            _ptr(term), _ptr(lim_lo), _ptr(lim_hi), float(p['hl']), _ptr(move), _ptr(prev), int(bool(p['has_previous'])), S,
-            _ptr(z0), int(p['max_iter']), float(p['tol']), _ptr(z), _ptr(cost), _ptr(cost_start), _ptr(status), _ptr(iterations),
-            _ptr(descent), _ptr(best), _ptr(members), _ptr(first), _ptr(fF), _ptr(fg), _ptr(fH)))
+            self._h, ctypes.byref(system), ctypes.byref(problem), _ptr(z), _ptr(cost), _ptr(cost_start), _ptr(status),
+            _ptr(iterations), _ptr(descent), _ptr(best), _ptr(members), _ptr(first), _ptr(fF), _ptr(fg), _ptr(fH)))
+        del held, held_problem
         solved = dict(z=z, cost=cost, cost_start=cost_start, status=status, iterations=iterations, descent_steps=descent)
         if want_first:
             solved['first_pass'] = dict(F=fF, g=fg, H=fH)
@@ -2567,25 +2538,10 @@ class DeviceContext:
         ``Ft_chunks`` [S, chunks, 2, 31], the chunk sums the accept launch adds, and ``Ft`` their sum in chunk order formed
         here.  Needs no uploaded dataset and leaves one alone."""
         K, E, P, S, D = int(p['K']), int(p['E']), int(p['n_steps']) + 1, int(p['starts']), int(p['D'])
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
-        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
-        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
-        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
-        coef, y0, box = f64(np.asarray(p['coef']).T), f64(p['y0']), f64(p['box'])
-        seg_first, norm_control = i32(p['seg_first']), i32(p['norm_control'])
-        lo, width, ref, z0, w = f64(p['ctl_lo']), f64(p['ctl_width']), f64(p['ref']), f64(p['z0']), f64(p['pool_w'])
-        wt, term, lim_lo, lim_hi, move, prev = (f64(p[key]) for key in ('wt', 'term', 'lim_lo', 'lim_hi', 'move', 'prev'))
-        nc = int(p['n_controls'])
-        if coef.ndim != 2 or coef.shape[0] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
-                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
-                not (norm_src.shape == norm_lo.shape == norm_span.shape) or \
-                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
-                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21 or seg_first.ndim != 1 or \
-                D != nc * seg_first.shape[0] or norm_control.shape != (int(p['n_norm_forcing']),) or lo.shape != (nc,) or \
-                width.shape != (nc,) or move.shape != (nc,) or prev.shape != (nc,) or ref.shape != (K, P) or \
-                not (wt.shape == term.shape == lim_lo.shape == lim_hi.shape == (K,)) or z0.shape != (S, D) or w.shape != (E,):
+        system, held = _system_struct(p, 'control_pooled_solve', coef_by_draw=True)
+        problem, held_problem = _control_problem_struct(p, 'control_pooled_solve')
+        w = _f64(p['pool_w'])
+        if w.shape != (E,):
             raise ValueError("control_pooled_solve: array shapes disagree")
         n = 2 + D + D * D
         z = np.empty((S, D), dtype=np.float64)
@@ -2598,15 +2554,10 @@ class DeviceContext:
         rows = np.empty((S, E, n), dtype=np.float64) if want_first else None
         trace = _FirstTrial(S, E, D) if first_trial else None
         self._ck(self._lib.fokl_control_pooled_solve(
-            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
-            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
-            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
-            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[1], _ptr(coef), _ptr(y0),
-            _ptr(box), nc, seg_first.shape[0], _ptr(seg_first), _ptr(norm_control), _ptr(lo), _ptr(width), _ptr(ref), _ptr(wt),
-            _ptr(term), _ptr(lim_lo), _ptr(lim_hi), float(p['hl']), _ptr(move), _ptr(prev), int(bool(p['has_previous'])), S,
-            _ptr(z0), int(p['max_iter']), float(p['tol']), _ptr(w), _ptr(z), _ptr(cost), _ptr(cost_start), _ptr(status),
+            self._h, ctypes.byref(system), ctypes.byref(problem), _ptr(w), _ptr(z), _ptr(cost), _ptr(cost_start), _ptr(status),
             _ptr(iterations), _ptr(descent), _ptr(best), _ptr(members), _ptr(first), _ptr(cost_draws), _ptr(pooled), _ptr(rows),
             trace.ref() if trace else None))
+        del held, held_problem
         solved = dict(z=z, cost=cost, cost_start=cost_start, status=status, iterations=iterations, descent_steps=descent)
         if trace:
             solved['first_trial'] = trace.result(pooled=True)
@@ -2636,25 +2587,10 @@ class DeviceContext:
         ``first_trial`` in the layout of ``dynamics._control_cvar_solve_host``'s: ``phi_t`` and ``a_t`` [S, 2, 31] of the
         trial-side risk launch in place of the pooled ``Ft`` (for alpha == 0 ``control_pooled_solve``'s)."""
         K, E, P, S, D = int(p['K']), int(p['E']), int(p['n_steps']) + 1, int(p['starts']), int(p['D'])
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        forcing, norm_src, norm_lo, norm_span = f64(p['forcing']), i32(p['norm_src']), f64(p['norm_lo']), f64(p['norm_span'])
-        fac_norm, fac_kind, fac_row, fac_degree = (i32(p[key]) for key in ('fac_norm', 'fac_kind', 'fac_row', 'fac_degree'))
-        spline, bern, entries = f64(p['spline_table']), f64(p['bern_table']), i32(p['entries']).reshape(-1, 4)
-        begin, count, constant = i32(p['entry_begin']), i32(p['entry_count']), i32(p['constant'])
-        coef, y0, box = f64(np.asarray(p['coef']).T), f64(p['y0']), f64(p['box'])
-        seg_first, norm_control = i32(p['seg_first']), i32(p['norm_control'])
-        lo, width, ref, z0, w = f64(p['ctl_lo']), f64(p['ctl_width']), f64(p['ref']), f64(p['z0']), f64(p['pool_w'])
-        wt, term, lim_lo, lim_hi, move, prev = (f64(p[key]) for key in ('wt', 'term', 'lim_lo', 'lim_hi', 'move', 'prev'))
-        nc = int(p['n_controls'])
-        if coef.ndim != 2 or coef.shape[0] != E or y0.shape != (K, E) or box.shape != (K, 2) or begin.shape != (K,) or \
-                count.shape != (K,) or constant.shape != (K,) or forcing.ndim != 2 or forcing.shape[0] != P - 1 or \
-                not (norm_src.shape == norm_lo.shape == norm_span.shape) or \
-                not (fac_norm.shape == fac_kind.shape == fac_row.shape == fac_degree.shape) or \
-                spline.shape[1:] != (499, 4) or bern.ndim != 2 or bern.shape[1] != 21 or seg_first.ndim != 1 or \
-                D != nc * seg_first.shape[0] or norm_control.shape != (int(p['n_norm_forcing']),) or lo.shape != (nc,) or \
-                width.shape != (nc,) or move.shape != (nc,) or prev.shape != (nc,) or ref.shape != (K, P) or \
-                not (wt.shape == term.shape == lim_lo.shape == lim_hi.shape == (K,)) or z0.shape != (S, D) or w.shape != (E,):
+        system, held = _system_struct(p, 'control_cvar_solve', coef_by_draw=True)
+        problem, held_problem = _control_problem_struct(p, 'control_cvar_solve')
+        w = _f64(p['pool_w'])
+        if w.shape != (E,):
             raise ValueError("control_cvar_solve: array shapes disagree")
         n = 2 + D + D * D
         alpha = float(p['alpha'])
@@ -2673,16 +2609,11 @@ class DeviceContext:
         fc = np.empty((S, E), dtype=np.float64) if want_first else None
         trace = _FirstTrial(S, E, D) if first_trial else None
         self._ck(self._lib.fokl_control_cvar_solve(
-            self._h, E, K, P - 1, float(p['h']), forcing.shape[1], _ptr(forcing), int(p['n_norm_forcing']), norm_src.shape[0],
-            _ptr(norm_src), _ptr(norm_lo), _ptr(norm_span), int(p['n_forcing_factors']), fac_norm.shape[0], _ptr(fac_norm),
-            _ptr(fac_kind), _ptr(fac_row), _ptr(fac_degree), spline.shape[0], _ptr(spline), bern.shape[0], _ptr(bern),
-            entries.shape[0], _ptr(entries), _ptr(begin), _ptr(count), _ptr(constant), coef.shape[1], _ptr(coef), _ptr(y0),
-            _ptr(box), nc, seg_first.shape[0], _ptr(seg_first), _ptr(norm_control), _ptr(lo), _ptr(width), _ptr(ref), _ptr(wt),
-            _ptr(term), _ptr(lim_lo), _ptr(lim_hi), float(p['hl']), _ptr(move), _ptr(prev), int(bool(p['has_previous'])), S,
-            _ptr(z0), int(p['max_iter']), float(p['tol']), _ptr(w), alpha, float(p['smoothing']), epsilon, _ptr(z), _ptr(cost),
-            _ptr(cost_start), _ptr(status), _ptr(iterations), _ptr(descent), _ptr(best), _ptr(members), _ptr(first),
+            self._h, ctypes.byref(system), ctypes.byref(problem), _ptr(w), alpha, float(p['smoothing']), epsilon, _ptr(z),
+            _ptr(cost), _ptr(cost_start), _ptr(status), _ptr(iterations), _ptr(descent), _ptr(best), _ptr(members), _ptr(first),
             _ptr(cost_draws), _ptr(used), _ptr(pooled), _ptr(rows), _ptr(fa), _ptr(fq), _ptr(fc),
             trace.ref() if trace else None))
+        del held, held_problem
         solved = dict(z=z, cost=cost, cost_start=cost_start, status=status, iterations=iterations, descent_steps=descent,
                       epsilon=float(used[0]))
         if trace:

@@ -233,28 +233,6 @@ __global__ __launch_bounds__(SIM_LANES) void assimilate_kernel(
 
 }  // namespace fokl
 
-namespace {
-
-template <int NS>
-hipError_t asm_launch(fokl_ctx *ctx, int grid, size_t lds_bytes, const SimSystem &sys, const AsmProblem &ap, const SimTables &tab,
-                      const double *coef, const double *forcing, const double *y0, const uint32_t *draw_ids, const int *obs_row,
-                      const double *data, const double *obs_const, double *particles, double *weights, int *flags, double *stats,
-                      double *particles_out, double *weights_out, int64_t t0, int steps, int first)
-{
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(assimilate_kernel<NS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS_BUDGET);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(assimilate_kernel<NS>, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, ap, tab.norm_src,
-                       tab.norm_lo, tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline, tab.bern,
-                       coef, forcing, y0, draw_ids, obs_row, data, obs_const, particles, weights, flags, stats, particles_out,
-                       weights_out, t0, steps, first);
-    return hipGetLastError();
-}
-
-}  // namespace
-
 extern "C" int fokl_assimilate_report(const fokl_ctx *ctx, int64_t *out)
 {
     if (!ctx || !out) return fail(nullptr, FOKL_ERR_ARG, "fokl_assimilate_report: null argument");
@@ -262,44 +240,27 @@ extern "C" int fokl_assimilate_report(const fokl_ctx *ctx, int64_t *out)
     return FOKL_OK;
 }
 
-extern "C" int fokl_assimilate_ensemble(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
-                                        const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
-                                        const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
-                                        const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
-                                        const int32_t *fac_degree, int n_spline_rows, const double *spline_table,
-                                        int n_bern_rows, const double *bern_table, int n_entries, const int32_t *entries,
-                                        const int32_t *entry_begin, const int32_t *entry_count, const int32_t *constant,
-                                        int n_coef, const double *coef, const double *y0, const double *box,
-                                        const uint32_t *draw_ids, int n_observed, const int32_t *obs_state, const double *obs_sd,
-                                        int n_obs, const int32_t *obs_row, const double *data, const double *obs_const,
-                                        const double *process_q, const double *y0_sd, double threshold, uint32_t seed,
-                                        double *stats, double *particles_out, double *weights_out, int32_t *first_saturation,
+extern "C" int fokl_assimilate_ensemble(fokl_ctx *ctx, const fokl_system *system, const uint32_t *draw_ids, int n_observed,
+                                        const int32_t *obs_state, const double *obs_sd, int n_obs, const int32_t *obs_row,
+                                        const double *data, const double *obs_const, const double *process_q,
+                                        const double *y0_sd, double threshold, uint32_t seed, double *stats,
+                                        double *particles_out, double *weights_out, int32_t *first_saturation,
                                         int32_t *collapsed)
 {
     const std::string who = "fokl_assimilate_ensemble: ";
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
     std::memset(ctx->assimilate_report, 0, sizeof ctx->assimilate_report);
-    if (n_draws <= 0 || n_states <= 0 || n_steps < 0 || n_forcing_cols < 0 || n_norm_forcing < 0 || n_norm < n_norm_forcing ||
-        n_forcing_factors < 0 || n_factors < n_forcing_factors || n_spline_rows < 0 || n_bern_rows < 0 || n_entries < 0 ||
-        n_coef < n_states || !entry_begin || !entry_count || !constant || !coef || !y0 || !box || !draw_ids || !obs_state ||
-        !obs_sd || !obs_row || !data || !obs_const || !process_q || !y0_sd || !stats || !first_saturation || !collapsed ||
-        (particles_out == nullptr) != (weights_out == nullptr) || (n_norm > 0 && (!norm_src || !norm_lo || !norm_span)) ||
-        (n_factors > 0 && (!fac_norm || !fac_kind || !fac_row || !fac_degree)) || (n_entries > 0 && !entries) ||
-        (n_spline_rows > 0 && !spline_table) || (n_bern_rows > 0 && !bern_table) || (n_forcing_cols > 0 && n_steps > 0 && !forcing))
-        return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
-    if (n_states > SIM_MAX_STATES)
-        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_states) + " states, the kernel is built for at most " +
-                                           std::to_string(SIM_MAX_STATES));
-    if (n_steps + 1 > (int64_t)1 << 30) return fail(ctx, FOKL_ERR_ARG, who + "too many steps");
-    if (!(h > 0) || !std::isfinite(h)) return fail(ctx, FOKL_ERR_ARG, who + "h must be positive and finite");
+    const bool own_ok = draw_ids && obs_state && obs_sd && obs_row && data && obs_const && process_q && y0_sd && stats &&
+                        first_saturation && collapsed && (particles_out == nullptr) == (weights_out == nullptr);
+    if (const int refused = sim_check(ctx, who, system, own_ok, sim_steps_fit)) return refused;
+    const fokl_system &s = *system;
+    const int n_draws = s.n_members, n_states = s.n_states, n_factors = s.n_factors, n_coef = s.n_coef;
+    const int64_t n_steps = s.n_steps;
+    const double *y0 = s.y0;
 
     SimSystem sys{};
     int n_bern_factors = 0;
-    if (const int refused = sim_plan(ctx, who, n_states, h, n_forcing_cols, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
-                                     n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows,
-                                     n_bern_rows, n_entries, entries, entry_begin, entry_count, constant, n_coef, box, sys,
-                                     n_bern_factors))
-        return refused;
+    if (const int refused = sim_plan(ctx, who, s, sys, n_bern_factors)) return refused;
 
     // ---- the observations: every index and every scale the kernel follows ----
     const int64_t n_points = n_steps + 1;
@@ -348,11 +309,11 @@ extern "C" int fokl_assimilate_ensemble(fokl_ctx *ctx, int n_draws, int n_states
     ap.threshold = threshold;
     ap.seed = seed;
 
-    const size_t lds_lane_rows = (size_t)1 + n_factors + (n_norm - n_norm_forcing);
+    const size_t lds_lane_rows = (size_t)1 + n_factors + (s.n_norm - s.n_norm_forcing);
     const size_t lds_bytes = (lds_lane_rows + 1) * SIM_LANES * sizeof(double) + (size_t)n_coef * sizeof(double);
     if (lds_bytes > SIM_LDS_BUDGET)
         return fail(ctx, FOKL_ERR_ARG, who + "the system needs " + std::to_string(lds_bytes) + " bytes of LDS ((1 + " +
-                                           std::to_string(n_factors) + " factors + " + std::to_string(n_norm - n_norm_forcing) +
+                                           std::to_string(n_factors) + " factors + " + std::to_string(s.n_norm - s.n_norm_forcing) +
                                            " normalised states + the exchange row) x 64 x 8 + " + std::to_string(n_coef) +
                                            " coefficients x 8), a wavefront has " + std::to_string(SIM_LDS_BUDGET));
 
@@ -361,25 +322,14 @@ extern "C" int fokl_assimilate_ensemble(fokl_ctx *ctx, int n_draws, int n_states
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DeviceBuffers buf;
-    int *d_norm_src = nullptr, *d_fac_norm = nullptr, *d_fac_row = nullptr, *d_fac_degree = nullptr, *d_flags = nullptr,
-        *d_obs_row = nullptr;
-    int4 *d_entries = nullptr;
+    SimTables tab{};
+    int *d_flags = nullptr, *d_obs_row = nullptr;
     uint32_t *d_ids = nullptr;
-    double *d_norm_lo = nullptr, *d_norm_span = nullptr, *d_spline = nullptr, *d_bern = nullptr, *d_coef = nullptr,
-           *d_forcing = nullptr, *d_y0 = nullptr, *d_data = nullptr, *d_const = nullptr, *d_particles = nullptr,
+    double *d_coef = nullptr, *d_forcing = nullptr, *d_y0 = nullptr, *d_data = nullptr, *d_const = nullptr, *d_particles = nullptr,
            *d_weights = nullptr, *d_stats = nullptr, *d_pout = nullptr, *d_wout = nullptr;
     std::vector<int32_t> never(2 * E, -1);
-    HIP_TRY(ctx, buf.upload(&d_norm_src, norm_src, (size_t)n_norm));
-    HIP_TRY(ctx, buf.upload(&d_norm_lo, norm_lo, (size_t)n_norm));
-    HIP_TRY(ctx, buf.upload(&d_norm_span, norm_span, (size_t)n_norm));
-    HIP_TRY(ctx, buf.upload(&d_fac_norm, fac_norm, (size_t)n_factors));
-    HIP_TRY(ctx, buf.upload(&d_fac_row, fac_row, (size_t)n_factors));
-    HIP_TRY(ctx, buf.upload(&d_fac_degree, fac_degree, (size_t)n_factors));
-    HIP_TRY(ctx, buf.upload(&d_entries, entries, (size_t)n_entries));
-    HIP_TRY(ctx, buf.upload(&d_spline, spline_table, (size_t)n_spline_rows * SIM_PIECES * 4));
-    HIP_TRY(ctx, buf.upload(&d_bern, bern_table, (size_t)n_bern_rows * SIM_BERN_WIDTH));
-    HIP_TRY(ctx, buf.upload(&d_coef, coef, E * n_coef));
-    HIP_TRY(ctx, buf.upload(&d_forcing, forcing, (size_t)n_steps * n_forcing_cols));
+    HIP_TRY(ctx, sim_upload(buf, s, tab, d_forcing));
+    HIP_TRY(ctx, buf.upload(&d_coef, s.coef, E * n_coef));
     HIP_TRY(ctx, buf.upload(&d_y0, y0, E * n_states));
     HIP_TRY(ctx, buf.upload(&d_ids, draw_ids, E));
     HIP_TRY(ctx, buf.upload(&d_obs_row, obs_row, (size_t)n_points));
@@ -393,27 +343,26 @@ extern "C" int fokl_assimilate_ensemble(fokl_ctx *ctx, int n_draws, int n_states
         HIP_TRY(ctx, buf.get(&d_pout, E * n_obs * SIM_LANES * n_states));
         HIP_TRY(ctx, buf.get(&d_wout, E * n_obs * SIM_LANES));
     }
-    const SimTables tab{d_norm_src, d_norm_lo, d_norm_span, d_fac_norm, d_fac_row, d_fac_degree, d_entries, d_spline, d_bern};
 
-    double terms_per_stage = 0.0;
-    for (int k = 0; k < n_states; ++k) terms_per_stage += sys.entry_count[k];
+    const double stage_flops = 8.0 * sim_terms_per_stage(sys, n_states) + 20.0 * (n_factors - s.n_forcing_factors);
     int64_t launches = 0, t0 = 0;
     do {
         const int first = t0 == 0;
         const int steps = (int)std::min<int64_t>(per_launch, n_steps - t0);
         {
             TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)E * SIM_LANES * (n_states + 1.0) * 2.0,
-                              (double)E * SIM_LANES * steps * 4.0 * (8.0 * terms_per_stage + 20.0 * (n_factors - n_forcing_factors)));
-            hipError_t launched = hipSuccess;
-#define ASM_CASE(NS)                                                                                                         \
-    case NS:                                                                                                                 \
-        launched = asm_launch<NS>(ctx, n_draws, lds_bytes, sys, ap, tab, d_coef, d_forcing, d_y0, d_ids, d_obs_row, d_data,     \
-                                  d_const, d_particles, d_weights, d_flags, d_stats, d_pout, d_wout, t0, steps, first);        \
-        break;
-            switch (n_states) {
-                ASM_CASE(1) ASM_CASE(2) ASM_CASE(3) ASM_CASE(4) ASM_CASE(5) ASM_CASE(6) ASM_CASE(7) ASM_CASE(8)
-            }
-#undef ASM_CASE
+                              (double)E * SIM_LANES * steps * 4.0 * stage_flops);
+            const hipError_t launched = sim_dispatch(n_states, [&](auto ns) {
+                const auto kernel = assimilate_kernel<decltype(ns)::value>;
+                if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+                hipLaunchKernelGGL(kernel, dim3(n_draws), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, ap, tab.norm_src,
+                                   tab.norm_lo, tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline,
+                                   tab.bern, (const double *)d_coef, (const double *)d_forcing, (const double *)d_y0,
+                                   (const uint32_t *)d_ids, (const int *)d_obs_row, (const double *)d_data,
+                                   (const double *)d_const, d_particles, d_weights, d_flags, d_stats, d_pout, d_wout, t0, steps,
+                                   first);
+                return hipGetLastError();
+            });
             HIP_TRY(ctx, launched);
             ++launches;
         }

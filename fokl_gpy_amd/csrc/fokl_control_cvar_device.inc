@@ -194,8 +194,7 @@ __global__ __launch_bounds__(SIM_LANES) void control_cvar_step_kernel(
     if (status[s] >= 0) return;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int lane = threadIdx.x, D = cp.D, n = 2 + D + D * D, total = n + 1 + D + D * D;
-    double *ex = lds, *zs = ex + SIM_LANES, *gs = zs + SIM_LANES, *ds = gs + SIM_LANES, *H = ds + SIM_LANES;
-    double *Hl = H + lane;                                             // Hl[d' * 64] = H[lane][d']
+    double *zs = lds + SIM_LANES, *Hl = lds + 4 * SIM_LANES + lane;    // ctl_pooled_step's layout: Hl[d' * 64] = H[lane][d']
     if (lane == 0) work[it] = 1;
     const double zl = lane < D ? z[s * D + lane] : 0.0;
     zs[lane] = zl;
@@ -226,43 +225,8 @@ __global__ __launch_bounds__(SIM_LANES) void control_cvar_step_kernel(
         }
         Hl[d2 * SIM_LANES] = h;
     }
-    if (it == 0) {
-        if (lane == 0) cost_start[s] = F;
-        if (first) {
-            double *row = first + s * (size_t)n;
-            if (lane == 0) {
-                row[0] = F;
-                row[1] = noise;
-            }
-            if (lane < D) {
-                row[2 + lane] = g;
-                for (int d2 = 0; d2 < D; ++d2) row[2 + D + lane * D + d2] = Hl[d2 * SIM_LANES];
-            }
-        }
-    }
-    if (lane == 0) cost[s] = F;
-    __syncthreads();
-
-    const int code = ctl_stop_code(cp, F, g, zl, lane, it);
-    if (code >= 0) {
-        if (lane == 0) {
-            status[s] = code;
-            iterations[s] = it;
-        }
-        return;
-    }
-    ctl_newton_direction(H, ex, gs, ds, D, lane, zl, g);
-    double slope;
-    bool moved;
-    const bool valid = ctl_trial_points(zs, gs, ds, Hl, D, lane, slope, moved);
-    for (int d = 0; d < D; ++d) trial[(s * D + d) * SIM_LANES + lane] = Hl[d * SIM_LANES];
-    slope_out[s * SIM_LANES + lane] = slope;
-    moved_out[s * SIM_LANES + lane] = (valid && moved) ? 1 : 0;
-    if (lane == 0) {
-        pooled[s * (2 + D)] = F;
-        pooled[s * (2 + D) + 1] = noise;
-    }
-    if (lane < D) pooled[s * (2 + D) + 2 + lane] = g;
+    ctl_pooled_step(cp, s, lane, it, F, noise, g, zl, lds, status, iterations, cost, cost_start, trial, slope_out, moved_out, pooled,
+                    first);
 }
 
 }  // namespace fokl
@@ -270,18 +234,6 @@ __global__ __launch_bounds__(SIM_LANES) void control_cvar_step_kernel(
 namespace {
 
 enum { CVAR_TANGENT = 0, CVAR_RISK = 1, CVAR_CHUNK = 2, CVAR_STEP = 3, CVAR_TRIAL = 4, CVAR_ACCEPT = 5, CVAR_KINDS = 6 };
-
-#define CVAR_NS_SWITCH(call, ...)                                                                                             \
-    switch (n_states) {                                                                                                       \
-        case 1: launched = call<1>(__VA_ARGS__); break;                                                                       \
-        case 2: launched = call<2>(__VA_ARGS__); break;                                                                       \
-        case 3: launched = call<3>(__VA_ARGS__); break;                                                                       \
-        case 4: launched = call<4>(__VA_ARGS__); break;                                                                       \
-        case 5: launched = call<5>(__VA_ARGS__); break;                                                                       \
-        case 6: launched = call<6>(__VA_ARGS__); break;                                                                       \
-        case 7: launched = call<7>(__VA_ARGS__); break;                                                                       \
-        case 8: launched = call<8>(__VA_ARGS__); break;                                                                       \
-    }
 
 }  // namespace
 
@@ -292,27 +244,22 @@ extern "C" int fokl_control_cvar_report(const fokl_ctx *ctx, int64_t *out)
     return FOKL_OK;
 }
 
-extern "C" int fokl_control_cvar_solve(
-    fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols, const double *forcing,
-    int n_norm_forcing, int n_norm, const int32_t *norm_src, const double *norm_lo, const double *norm_span, int n_forcing_factors,
-    int n_factors, const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row, const int32_t *fac_degree,
-    int n_spline_rows, const double *spline_table, int n_bern_rows, const double *bern_table, int n_entries, const int32_t *entries,
-    const int32_t *entry_begin, const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef, const double *y0,
-    const double *box, int n_controls, int n_segments, const int32_t *seg_first, const int32_t *norm_control, const double *ctl_lo,
-    const double *ctl_width, const double *ref, const double *track_weight, const double *terminal_weight, const double *limit_lo,
-    const double *limit_hi, double limit_weight, const double *move_weight, const double *previous, int has_previous, int n_starts,
-    const double *z0, int max_iter, double tol, const double *draw_weights, double alpha, double smoothing, double epsilon,
-    double *z, double *cost, double *cost_start, int32_t *status, int32_t *iterations, int32_t *descent_steps, int32_t *best_start,
-    double *members, int32_t *first_saturation, double *cost_draws, double *epsilon_used, double *first_pooled, double *first_rows,
-    double *first_a, double *first_q, double *first_c, const fokl_control_first_trial *first_trial)
+extern "C" int fokl_control_cvar_solve(fokl_ctx *ctx, const fokl_system *system, const fokl_control_problem *problem,
+                                       const double *draw_weights, double alpha, double smoothing, double epsilon, double *z,
+                                       double *cost, double *cost_start, int32_t *status, int32_t *iterations,
+                                       int32_t *descent_steps, int32_t *best_start, double *members, int32_t *first_saturation,
+                                       double *cost_draws, double *epsilon_used, double *first_pooled, double *first_rows,
+                                       double *first_a, double *first_q, double *first_c,
+                                       const fokl_control_first_trial *first_trial)
 {
     const std::string who = "fokl_control_cvar_solve: ";
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
     std::memset(ctx->control_cvar_report, 0, sizeof ctx->control_cvar_report);
     const bool want_first = first_pooled != nullptr;
-    if (!draw_weights || !z || !cost || !cost_start || !status || !iterations || !descent_steps || !best_start || !members ||
-        !first_saturation || !cost_draws || !epsilon_used || want_first != (first_rows != nullptr) ||
-        want_first != (first_a != nullptr) || want_first != (first_q != nullptr) || want_first != (first_c != nullptr) ||
+    const PooledOutputs out{z, cost, cost_start, status, iterations, descent_steps, best_start, members, first_saturation,
+                            cost_draws, first_pooled, first_rows};
+    if (!system || !problem || !draw_weights || !out.complete() || !epsilon_used || want_first != (first_a != nullptr) ||
+        want_first != (first_q != nullptr) || want_first != (first_c != nullptr) ||
         (first_trial && alpha != 0.0 &&
          (!first_trial->trial || !first_trial->slope || !first_trial->moved || !first_trial->pooled || !first_trial->ft ||
           !first_trial->phi_t || !first_trial->a_t || !first_trial->z || !first_trial->status || !first_trial->descent)))
@@ -326,43 +273,29 @@ extern "C" int fokl_control_cvar_solve(
                                            std::to_string(epsilon));
     if (alpha == 0.0) {                                                // q = w, no a, no covariance term: control_pooled itself
         if (want_first) {
-            for (size_t k = 0; k < (size_t)std::max(n_starts, 0); ++k) first_a[k] = NAN;
-            for (size_t k = 0; k < (size_t)std::max(n_starts, 0) * (size_t)std::max(n_draws, 0); ++k) {
-                first_q[k] = draw_weights[k % (size_t)n_draws];
+            const size_t starts = (size_t)std::max(problem->n_starts, 0), draws = (size_t)std::max(system->n_members, 0);
+            for (size_t k = 0; k < starts; ++k) first_a[k] = NAN;
+            for (size_t k = 0; k < starts * draws; ++k) {
+                first_q[k] = draw_weights[k % draws];
                 first_c[k] = 0.0;
             }
         }
         *epsilon_used = epsilon;
-        return fokl_control_pooled_solve(ctx, n_draws, n_states, n_steps, h, n_forcing_cols, forcing, n_norm_forcing, n_norm, norm_src,
-                                         norm_lo, norm_span, n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree,
-                                         n_spline_rows, spline_table, n_bern_rows, bern_table, n_entries, entries, entry_begin,
-                                         entry_count, constant, n_coef, coef, y0, box, n_controls, n_segments, seg_first, norm_control,
-                                         ctl_lo, ctl_width, ref, track_weight, terminal_weight, limit_lo, limit_hi, limit_weight,
-                                         move_weight, previous, has_previous, n_starts, z0, max_iter, tol, draw_weights, z, cost,
-                                         cost_start, status, iterations, descent_steps, best_start, members, first_saturation,
-                                         cost_draws, first_pooled, first_rows, first_trial);
+        return fokl_control_pooled_solve(ctx, system, problem, draw_weights, z, cost, cost_start, status, iterations, descent_steps,
+                                         best_start, members, first_saturation, cost_draws, first_pooled, first_rows, first_trial);
     }
-    const CtlArgs args{n_draws, n_states, n_steps, h, n_forcing_cols, forcing, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
-                       n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows, spline_table,
-                       n_bern_rows, bern_table, n_entries, entries, entry_begin, entry_count, constant, n_coef, coef, y0, box,
-                       n_controls, n_segments, seg_first, norm_control, ctl_lo, ctl_width, ref, track_weight, terminal_weight,
-                       limit_lo, limit_hi, limit_weight, move_weight, previous, has_previous, n_starts, z0, max_iter, tol};
     SimSystem sys{};
     CtlProblem cp{};
     size_t lds_bytes = 0;
     int n_bern_factors = 0;
-    if (const int refused = ctl_plan(ctx, who, args, sys, cp, lds_bytes, n_bern_factors)) return refused;
-    double weight_sum = 0.0;
-    for (int e = 0; e < n_draws; ++e) {
-        if (!(draw_weights[e] >= 0) || !std::isfinite(draw_weights[e]))
-            return fail(ctx, FOKL_ERR_ARG, who + "draw weights must be non-negative and finite");
-        weight_sum += draw_weights[e];
-    }
-    if (!(weight_sum > 0)) return fail(ctx, FOKL_ERR_ARG, who + "the draw weights sum to zero: at least one draw must weigh something");
+    if (const int refused = ctl_plan(ctx, who, system, problem, true, sys, cp, lds_bytes, n_bern_factors)) return refused;
+    const fokl_system &s = *system;
+    const int n_draws = s.n_members, n_states = s.n_states, n_starts = cp.n_starts, max_iter = cp.max_iter;
+    if (const int refused = pooled_weights_check(ctx, who, n_draws, draw_weights)) return refused;
 
-    const int D = cp.D, n = 2 + D + D * D, n2 = 1 + D + D * D, n_chunks = (n_draws + CTL_POOL_CHUNK - 1) / CTL_POOL_CHUNK;
-    const int64_t n_points = n_steps + 1;
-    const size_t E = (size_t)n_draws, S = (size_t)n_starts, B = E * S;
+    PooledWork k(cp);
+    const int D = k.D, n = k.n, n2 = 1 + D + D * D, n_chunks = k.n_chunks;
+    const size_t S = k.S, B = k.B;
     const size_t step_lds = (size_t)(4 + D) * SIM_LANES * sizeof(double);
     const int risk_threads = ((n_chunks + SIM_LANES - 1) / SIM_LANES) * SIM_LANES;
     const size_t risk_lds = ((size_t)2 * CTL_POOL_CHUNK * n_chunks + 2 * (size_t)risk_threads) * sizeof(double);
@@ -371,83 +304,40 @@ extern "C" int fokl_control_cvar_solve(
                     who + "the risk kernel keeps every draw's cost and weight in LDS: (2 x 64 x ceil(draws / 64) + 2 x threads) x 8 = " +
                         std::to_string(risk_lds) + " bytes for " + std::to_string(n_draws) + " draws, the limit is " +
                         std::to_string(SIM_LDS_BUDGET) + " (solve over fewer draws)");
-    const int poll = std::max(0, env_int("FOKL_CONTROL_POLL", 8));    // read the statuses every `poll` iterations; 0: never
     const double m = 1.0 - alpha;
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // ---- the workspace against the device's free memory (FOKL_CONTROL_CVAR_FREE_BYTES caps what counts as free) ----
     const size_t workspace =
         (B * (size_t)(n + SIM_LANES + 2) + S * n_chunks * (size_t)(n + n2) + S * SIM_LANES * (size_t)(4 + D)) * sizeof(double);
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    if (const char *cap = std::getenv("FOKL_CONTROL_CVAR_FREE_BYTES"))
-        free_bytes = std::min<size_t>(free_bytes, std::strtoull(cap, nullptr, 10));
-    if (workspace > free_bytes)
-        return fail(ctx, FOKL_ERR_ARG,
-                    who + "the workspace needs " + std::to_string(workspace) + " bytes (" + std::to_string(n_draws) + " draws x " +
-                        std::to_string(n_starts) + " starts x (2 + D + D x D + 64 + 2 = " + std::to_string(n + SIM_LANES + 2) +
-                        ") x 8, (3 + 2 D + 2 D x D = " + std::to_string(n + n2) + ") x 8 per start and chunk of 64 draws: " +
-                        std::to_string(n_chunks) + " chunks, and 64 x (4 + D) x 8 per start), the device has " +
-                        std::to_string(free_bytes) + " free (FOKL_CONTROL_CVAR_FREE_BYTES caps what counts; solve over fewer draws or starts)");
+    if (const int refused = pooled_workspace_fits(
+            ctx, who, workspace, "FOKL_CONTROL_CVAR_FREE_BYTES",
+            std::to_string(n_draws) + " draws x " + std::to_string(n_starts) + " starts x (2 + D + D x D + 64 + 2 = " +
+                std::to_string(n + SIM_LANES + 2) + ") x 8, (3 + 2 D + 2 D x D = " + std::to_string(n + n2) +
+                ") x 8 per start and chunk of 64 draws: " + std::to_string(n_chunks) + " chunks, and 64 x (4 + D) x 8 per start"))
+        return refused;
 
     DeviceBuffers buf;
     CtlDevice dev{};
-    HIP_TRY(ctx, ctl_upload(buf, args, dev));
-    int *d_status = nullptr, *d_iterations = nullptr, *d_descent = nullptr, *d_work = nullptr, *d_first = nullptr, *d_moved = nullptr,
-        *d_running = nullptr;
-    double *d_w = nullptr, *d_z = nullptr, *d_cost = nullptr, *d_cost_start = nullptr, *d_rows = nullptr, *d_sums = nullptr,
-           *d_ft = nullptr, *d_trial = nullptr, *d_slope = nullptr, *d_pooled = nullptr, *d_fpool = nullptr, *d_zbest = nullptr,
-           *d_members = nullptr, *d_phi = nullptr, *d_a = nullptr, *d_phi_t = nullptr, *d_a_t = nullptr, *d_q = nullptr, *d_c = nullptr;
-    std::vector<int32_t> h_status(S, -1), h_none(S, 0), h_zero((size_t)max_iter + 1, 0);
-    std::vector<double> h_nan(S, NAN);
-    HIP_TRY(ctx, buf.upload(&d_w, draw_weights, E));
-    HIP_TRY(ctx, buf.upload(&d_z, z0, S * D));
-    HIP_TRY(ctx, buf.upload(&d_status, h_status.data(), S));
-    HIP_TRY(ctx, buf.upload(&d_iterations, h_status.data(), S));
-    HIP_TRY(ctx, buf.upload(&d_descent, h_none.data(), S));
-    HIP_TRY(ctx, buf.upload(&d_cost, h_nan.data(), S));
-    HIP_TRY(ctx, buf.upload(&d_cost_start, h_nan.data(), S));
-    HIP_TRY(ctx, buf.upload(&d_work, h_zero.data(), h_zero.size()));
-    HIP_TRY(ctx, buf.upload(&d_running, h_status.data(), 1));
-    HIP_TRY(ctx, buf.get(&d_rows, B * n));
-    HIP_TRY(ctx, buf.get(&d_sums, S * n_chunks * (size_t)(n + n2)));
-    HIP_TRY(ctx, buf.get(&d_ft, B * SIM_LANES));
-    HIP_TRY(ctx, buf.get(&d_trial, S * D * SIM_LANES));
-    HIP_TRY(ctx, buf.get(&d_slope, S * SIM_LANES));
-    HIP_TRY(ctx, buf.get(&d_moved, S * SIM_LANES));
-    HIP_TRY(ctx, buf.get(&d_pooled, S * (2 + D)));
+    HIP_TRY(ctx, ctl_upload(buf, s, *problem, dev));
+    if (const int failed = k.alloc(ctx, buf, s, draw_weights, problem->z0, (size_t)(n + n2), want_first, first_trial != nullptr))
+        return failed;
+    double *d_phi = nullptr, *d_a = nullptr, *d_phi_t = nullptr, *d_a_t = nullptr, *d_q = nullptr, *d_c = nullptr;
     HIP_TRY(ctx, buf.get(&d_phi, S));
     HIP_TRY(ctx, buf.get(&d_a, S));
     HIP_TRY(ctx, buf.get(&d_phi_t, S * SIM_LANES));
     HIP_TRY(ctx, buf.get(&d_a_t, S * SIM_LANES));
     HIP_TRY(ctx, buf.get(&d_q, B));
     HIP_TRY(ctx, buf.get(&d_c, B));
-    if (want_first) {                                                 // a draw of weight 0 writes no row: its row reads NaN
-        std::vector<double> h_rows(B * n, NAN);
-        HIP_TRY(ctx, hipMemcpy(d_rows, h_rows.data(), h_rows.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, buf.get(&d_fpool, S * n));
-    }
-    if (first_trial) {                                                // what iteration 0 does not write reads NaN, moved 0
-        HIP_TRY(ctx, pooled_fill_nan(d_trial, S * D * SIM_LANES));
-        HIP_TRY(ctx, pooled_fill_nan(d_slope, S * SIM_LANES));
-        HIP_TRY(ctx, pooled_fill_nan(d_pooled, S * (2 + D)));
-        HIP_TRY(ctx, pooled_fill_nan(d_ft, B * SIM_LANES));
+    if (first_trial) {
         HIP_TRY(ctx, pooled_fill_nan(d_phi_t, S * SIM_LANES));
         HIP_TRY(ctx, pooled_fill_nan(d_a_t, S * SIM_LANES));
-        HIP_TRY(ctx, hipMemset(d_moved, 0, S * SIM_LANES * sizeof(int)));
     }
-    HIP_TRY(ctx, buf.get(&d_zbest, E * D));
-    HIP_TRY(ctx, buf.get(&d_members, E * n_states * n_points));
-    HIP_TRY(ctx, buf.get(&d_first, E));
-    if (risk_lds > 64 * 1024)
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(control_cvar_risk_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS_BUDGET));
+    HIP_TRY(ctx, sim_lds_attribute(control_cvar_risk_kernel, risk_lds));
 
-    double terms_per_stage = 0.0;
-    for (int k = 0; k < n_states; ++k) terms_per_stage += sys.entry_count[k];
-    const double pass_flops = (double)B * SIM_LANES * (double)n_steps * 4.0 * (8.0 * terms_per_stage + 20.0 * n_factors);
+    const double pass_flops = (double)B * SIM_LANES * (double)s.n_steps * 4.0 * (8.0 * sim_terms_per_stage(sys, n_states) + 20.0 * s.n_factors);
     const int chunk_blocks = (n + n2 + CTL_POOL_BLOCK - 1) / CTL_POOL_BLOCK;
     PooledClock clock(ctx);
+    CtlPoll poll;
     int64_t queued = 0;
     hipError_t launched = hipSuccess;
     double eps = epsilon;
@@ -455,17 +345,17 @@ extern "C" int fokl_control_cvar_solve(
         {
             TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (2.0 * (double)B * (n + SIM_LANES)), 3.0 * pass_flops);
             clock.before(CVAR_TANGENT);
-            CVAR_NS_SWITCH(pooled_tangent, ctx, (int)B, lds_bytes, sys, cp, dev, d_z, d_status, d_w, d_rows)
+            launched = pooled_tangent(ctx, n_states, (int)B, lds_bytes, sys, cp, dev, k.z, k.status, k.w, k.rows);
             clock.after();
             HIP_TRY(ctx, launched);
             if (it == 0 && relative) {
                 // the one host read: the pooled cost of start 0 at its z0, in pooled_sum's order, fixes eps for the whole call
-                HIP_TRY(ctx, pooled_chunks(ctx, d_rows, d_w, d_status, d_sums, n_draws, 1, n, n_chunks));
+                HIP_TRY(ctx, pooled_chunks(ctx, k.rows, k.w, k.status, k.sums, n_draws, 1, n, n_chunks));
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
                 std::vector<double> h_sums((size_t)n_chunks * n);
-                HIP_TRY(ctx, hipMemcpy(h_sums.data(), d_sums, h_sums.size() * sizeof(double), hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(h_sums.data(), k.sums, h_sums.size() * sizeof(double), hipMemcpyDeviceToHost));
                 double at_start = h_sums[0];
-                for (int k = 1; k < n_chunks; ++k) at_start = at_start + h_sums[(size_t)k * n];
+                for (int c = 1; c < n_chunks; ++c) at_start = at_start + h_sums[(size_t)c * n];
                 if (!std::isfinite(at_start) || at_start == 0.0)
                     return fail(ctx, FOKL_ERR_ARG,
                                 who + "smoothing is relative to the pooled cost at the start, which is " + std::to_string(at_start) +
@@ -473,14 +363,14 @@ extern "C" int fokl_control_cvar_solve(
                 eps = smoothing * at_start;
             }
             clock.before(CVAR_RISK);
-            hipLaunchKernelGGL(control_cvar_risk_kernel, dim3((unsigned)S), dim3(risk_threads), risk_lds, ctx->stream, d_rows, d_w,
-                               d_status, n_draws, n_chunks, n, 1, m, eps, d_phi, d_a, d_q, d_c);
+            hipLaunchKernelGGL(control_cvar_risk_kernel, dim3((unsigned)S), dim3(risk_threads), risk_lds, ctx->stream, k.rows, k.w,
+                               k.status, n_draws, n_chunks, n, 1, m, eps, d_phi, d_a, d_q, d_c);
             launched = hipGetLastError();
             clock.after();
             HIP_TRY(ctx, launched);
             clock.before(CVAR_CHUNK);
             hipLaunchKernelGGL(control_cvar_chunk_kernel, dim3((unsigned)(S * n_chunks * chunk_blocks)), dim3(CTL_POOL_BLOCK), 0,
-                               ctx->stream, d_rows, d_q, d_c, d_status, d_sums, n_draws, D, n_chunks, chunk_blocks);
+                               ctx->stream, k.rows, d_q, d_c, k.status, k.sums, n_draws, D, n_chunks, chunk_blocks);
             launched = hipGetLastError();
             clock.after();
             HIP_TRY(ctx, launched);
@@ -491,117 +381,45 @@ extern "C" int fokl_control_cvar_solve(
                 HIP_TRY(ctx, hipMemcpy(first_c, d_c, B * sizeof(double), hipMemcpyDeviceToHost));
             }
             clock.before(CVAR_STEP);
-            hipLaunchKernelGGL(control_cvar_step_kernel, dim3((unsigned)S), dim3(SIM_LANES), step_lds, ctx->stream, cp, d_sums,
-                               n_chunks, d_phi, d_z, d_status, d_iterations, d_cost, d_cost_start, d_work, d_trial, d_slope, d_moved,
-                               d_pooled, d_fpool, it);
+            hipLaunchKernelGGL(control_cvar_step_kernel, dim3((unsigned)S), dim3(SIM_LANES), step_lds, ctx->stream, cp, k.sums,
+                               n_chunks, d_phi, k.z, k.status, k.iterations, k.cost, k.cost_start, k.work, k.trial, k.slope, k.moved,
+                               k.pooled, k.fpool, it);
             launched = hipGetLastError();
             clock.after();
             HIP_TRY(ctx, launched);
             clock.before(CVAR_TRIAL);
-            CVAR_NS_SWITCH(pooled_trial, ctx, (int)B, lds_bytes, sys, cp, dev, d_trial, d_status, d_w, d_ft)
+            launched = pooled_trial(ctx, n_states, (int)B, lds_bytes, sys, cp, dev, k.trial, k.status, k.w, k.ft);
             clock.after();
             HIP_TRY(ctx, launched);
             clock.before(CVAR_RISK);
             hipLaunchKernelGGL(control_cvar_risk_kernel, dim3((unsigned)(S * SIM_LANES)), dim3(risk_threads), risk_lds, ctx->stream,
-                               d_ft, d_w, d_status, n_draws, n_chunks, SIM_LANES, SIM_LANES, m, eps, d_phi_t, d_a_t,
+                               k.ft, k.w, k.status, n_draws, n_chunks, SIM_LANES, SIM_LANES, m, eps, d_phi_t, d_a_t,
                                (double *)nullptr, (double *)nullptr);
             launched = hipGetLastError();
             clock.after();
             HIP_TRY(ctx, launched);
             clock.before(CVAR_ACCEPT);
             hipLaunchKernelGGL(control_pooled_accept_kernel, dim3((unsigned)S), dim3(SIM_LANES), 0, ctx->stream, D, d_phi_t, 1,
-                               d_trial, d_slope, d_moved, d_pooled, d_z, d_status, d_iterations, d_descent, it);
+                               k.trial, k.slope, k.moved, k.pooled, k.z, k.status, k.iterations, k.descent, it);
             launched = hipGetLastError();
             clock.after();
             HIP_TRY(ctx, launched);
             ++queued;
         }
-        if (it == 0 && first_trial) {                                 // iteration 0's trial half, before a later one overwrites it
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(first_trial->trial, d_trial, S * D * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->slope, d_slope, S * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->moved, d_moved, S * SIM_LANES * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->pooled, d_pooled, S * (2 + D) * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->ft, d_ft, B * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+        if (it == 0 && first_trial) {
+            if (const int failed = k.first_trial_out(ctx, *first_trial)) return failed;
             HIP_TRY(ctx, hipMemcpy(first_trial->phi_t, d_phi_t, S * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
             HIP_TRY(ctx, hipMemcpy(first_trial->a_t, d_a_t, S * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->z, d_z, S * D * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->status, d_status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->descent, d_descent, S * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
-        if (poll > 0 && (it + 1) % poll == 0 && it < max_iter) {      // may stop queuing early: an iteration without work changes nothing
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(h_status.data(), d_status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-            bool running = false;
-            for (size_t s = 0; s < S && !running; ++s) running = h_status[s] < 0;
-            if (!running) break;
-        }
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(z, d_z, S * D * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(cost, d_cost, S * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(cost_start, d_cost_start, S * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(status, d_status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(iterations, d_iterations, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(descent_steps, d_descent, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(h_zero.data(), d_work, h_zero.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (want_first) {
-        HIP_TRY(ctx, hipMemcpy(first_pooled, d_fpool, S * n * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(first_rows, d_rows, B * n * sizeof(double), hipMemcpyDeviceToHost));
+        bool stopped = false;
+        if (const int failed = poll(ctx, it, max_iter, k.status, S, stopped)) return failed;
+        if (stopped) break;
     }
     *epsilon_used = eps;
-    for (size_t s = 0; s < S; ++s)
-        if (status[s] < 0) return fail(ctx, FOKL_ERR_HIP, who + "a solve was left running");
     int64_t worked = 0;
-    for (int32_t found : h_zero) worked += found;
-
-    // ---- the best start (a non-finite solve is never the best); every draw's trajectory and own cost under its controls ----
-    int best = 0;
-    double best_key = INFINITY;
-    for (int s = 0; s < n_starts; ++s) {
-        const double key = (std::isfinite(cost[s]) && status[s] != CTL_NON_FINITE) ? cost[s] : INFINITY;
-        if (key < best_key) {
-            best_key = key;
-            best = s;
-        }
-    }
-    *best_start = best;
-    std::vector<double> z_best(E * D), point((size_t)D * SIM_LANES);
-    for (size_t e = 0; e < E; ++e) std::memcpy(z_best.data() + e * D, z + (size_t)best * D, D * sizeof(double));
-    for (int d = 0; d < D; ++d)
-        for (int lane = 0; lane < SIM_LANES; ++lane) point[(size_t)d * SIM_LANES + lane] = z[(size_t)best * D + d];
-    HIP_TRY(ctx, hipMemcpy(d_zbest, z_best.data(), E * D * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_trial, point.data(), point.size() * sizeof(double), hipMemcpyHostToDevice));
-    {
-        TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)E * n_states * n_points, 2.0 * pass_flops / (double)S);
-#define CTL_CASE(NS)                                                                                                         \
-    case NS:                                                                                                                 \
-        launched = ctl_trajectory<NS>(ctx, n_draws, lds_bytes, sys, cp, dev.tab, dev.ct, dev.coef, dev.forcing, dev.y0, d_zbest,  \
-                                      d_members, d_first);                                                                   \
-        break;
-        switch (n_states) {
-            CTL_CASE(1) CTL_CASE(2) CTL_CASE(3) CTL_CASE(4) CTL_CASE(5) CTL_CASE(6) CTL_CASE(7) CTL_CASE(8)
-        }
-#undef CTL_CASE
-        HIP_TRY(ctx, launched);
-        // one start (d_running holds -1), no weights: every draw's value pass at the returned point, lane 0 is read
-        CVAR_NS_SWITCH(pooled_trial, ctx, n_draws, lds_bytes, sys, cp, dev, d_trial, d_running, nullptr, d_ft)
-        HIP_TRY(ctx, launched);
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(members, d_members, E * n_states * n_points * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(first_saturation, d_first, E * sizeof(int32_t), hipMemcpyDeviceToHost));
-    std::vector<double> h_ft(E * SIM_LANES);
-    HIP_TRY(ctx, hipMemcpy(h_ft.data(), d_ft, h_ft.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < E; ++e) cost_draws[e] = h_ft[e * SIM_LANES];
+    if (const int failed = k.finish(ctx, who, s, sys, cp, lds_bytes, dev, pass_flops, out, worked)) return failed;
     int64_t *rep = ctx->control_cvar_report;
-    rep[0] = n_states;
-    rep[1] = n_draws;
-    rep[2] = n_starts;
-    rep[3] = D;
-    rep[4] = n_chunks;
-    rep[5] = (int64_t)lds_bytes;
-    rep[6] = (int64_t)step_lds;
+    k.report_head(rep, n_states, lds_bytes, step_lds);
     rep[7] = (int64_t)risk_lds;
     rep[8] = risk_threads;
     rep[9] = queued;
@@ -610,5 +428,3 @@ extern "C" int fokl_control_cvar_solve(
     clock.read(rep + 12);
     return FOKL_OK;
 }
-
-#undef CVAR_NS_SWITCH

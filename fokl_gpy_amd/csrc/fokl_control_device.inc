@@ -536,201 +536,120 @@ __global__ __launch_bounds__(SIM_LANES) void control_trajectory_kernel(
 
 namespace {
 
-template <int NS>
-hipError_t ctl_launch(fokl_ctx *ctx, int grid, size_t lds_bytes, const SimSystem &sys, const CtlProblem &cp, const SimTables &tab,
-                      const CtlTables &ct, const double *coef, const double *forcing, const double *y0, double *z, int *status,
-                      int *iterations, int *descent, double *cost, double *cost_start, int *work, double *first_F,
-                      double *first_g, double *first_H, int it)
+// What the control calls refuse of n_steps (sim_check's steps_test)
+int ctl_steps_fit(fokl_ctx *ctx, const std::string &who, const fokl_system &s)
 {
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(control_iterate_kernel<NS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS_BUDGET);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(control_iterate_kernel<NS>, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, tab.norm_src,
-                       tab.norm_lo, tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline, tab.bern,
-                       ct.norm_control, ct.seg_first, ct.ref, coef, forcing, y0, z, status, iterations, descent, cost, cost_start, work,
-                       first_F, first_g, first_H, it);
-    return hipGetLastError();
+    if (s.n_steps < 1) return fail(ctx, FOKL_ERR_ARG, who + "no step at all: the horizon needs at least one step");
+    if (s.n_steps > CTL_MAX_STEPS)
+        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(s.n_steps) + " steps, a call handles at most " + std::to_string(CTL_MAX_STEPS));
+    return FOKL_OK;
 }
 
-template <int NS>
-hipError_t ctl_trajectory(fokl_ctx *ctx, int grid, size_t lds_bytes, const SimSystem &sys, const CtlProblem &cp,
-                          const SimTables &tab, const CtlTables &ct, const double *coef, const double *forcing, const double *y0,
-                          const double *z, double *members, int *first)
+// Everything the three entry points refuse of their inputs (outputs_ok: the caller's test of its outputs, the first refusal),
+// and the plan: sys, cp, the LDS bytes of a wavefront that runs a tangent or a value pass.
+int ctl_plan(fokl_ctx *ctx, const std::string &who, const fokl_system *system, const fokl_control_problem *problem, bool outputs_ok,
+             SimSystem &sys, CtlProblem &cp, size_t &lds_bytes, int &n_bern_factors)
 {
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(control_trajectory_kernel<NS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS_BUDGET);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(control_trajectory_kernel<NS>, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, tab.norm_src,
-                       tab.norm_lo, tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline, tab.bern,
-                       ct.norm_control, ct.seg_first, ct.ref, coef, forcing, y0, z, members, first);
-    return hipGetLastError();
-}
-
-// The inputs fokl_control_solve and fokl_control_pooled_solve share, as their argument lists name them
-struct CtlArgs {
-    int n_draws, n_states;
-    int64_t n_steps;
-    double h;
-    int n_forcing_cols;
-    const double *forcing;
-    int n_norm_forcing, n_norm;
-    const int32_t *norm_src;
-    const double *norm_lo, *norm_span;
-    int n_forcing_factors, n_factors;
-    const int32_t *fac_norm, *fac_kind, *fac_row, *fac_degree;
-    int n_spline_rows;
-    const double *spline_table;
-    int n_bern_rows;
-    const double *bern_table;
-    int n_entries;
-    const int32_t *entries, *entry_begin, *entry_count, *constant;
-    int n_coef;
-    const double *coef, *y0, *box;
-    int n_controls, n_segments;
-    const int32_t *seg_first, *norm_control;
-    const double *ctl_lo, *ctl_width, *ref, *track_weight, *terminal_weight, *limit_lo, *limit_hi;
-    double limit_weight;
-    const double *move_weight, *previous;
-    int has_previous, n_starts;
-    const double *z0;
-    int max_iter;
-    double tol;
-};
-
-// Everything both entry points refuse of their inputs (the outputs are the caller's to check), and the plan: sys, cp, the
-// LDS bytes of a wavefront that runs a tangent or a value pass.
-int ctl_plan(fokl_ctx *ctx, const std::string &who, const CtlArgs &in, SimSystem &sys, CtlProblem &cp,
-             size_t &lds_bytes, int &n_bern_factors)
-{
-    const int n_draws = in.n_draws, n_states = in.n_states, n_forcing_cols = in.n_forcing_cols, n_norm_forcing = in.n_norm_forcing,
-              n_norm = in.n_norm, n_forcing_factors = in.n_forcing_factors, n_factors = in.n_factors, n_spline_rows = in.n_spline_rows,
-              n_bern_rows = in.n_bern_rows, n_entries = in.n_entries, n_coef = in.n_coef, n_controls = in.n_controls,
-              n_segments = in.n_segments, has_previous = in.has_previous, n_starts = in.n_starts, max_iter = in.max_iter;
-    const int64_t n_steps = in.n_steps;
-    const double h = in.h, limit_weight = in.limit_weight, tol = in.tol;
-    const int32_t *norm_src = in.norm_src, *fac_norm = in.fac_norm, *fac_kind = in.fac_kind, *fac_row = in.fac_row,
-                  *fac_degree = in.fac_degree, *entries = in.entries, *entry_begin = in.entry_begin, *entry_count = in.entry_count,
-                  *constant = in.constant, *seg_first = in.seg_first, *norm_control = in.norm_control;
-    const double *forcing = in.forcing, *norm_lo = in.norm_lo, *norm_span = in.norm_span, *spline_table = in.spline_table,
-                 *bern_table = in.bern_table, *coef = in.coef, *y0 = in.y0, *box = in.box, *ctl_lo = in.ctl_lo, *ctl_width = in.ctl_width,
-                 *ref = in.ref, *track_weight = in.track_weight, *terminal_weight = in.terminal_weight, *limit_lo = in.limit_lo,
-                 *limit_hi = in.limit_hi, *move_weight = in.move_weight, *previous = in.previous, *z0 = in.z0;
-    if (n_draws <= 0 || n_states <= 0 || n_steps < 0 || n_forcing_cols < 0 || n_norm_forcing < 0 || n_norm < n_norm_forcing ||
-        n_forcing_factors < 0 || n_factors < n_forcing_factors || n_spline_rows < 0 || n_bern_rows < 0 || n_entries < 0 ||
-        n_coef < n_states || !entry_begin || !entry_count || !constant || !coef || !y0 || !box || !seg_first || !norm_control ||
-        !ctl_lo || !ctl_width || !ref || !track_weight || !terminal_weight || !limit_lo || !limit_hi || !move_weight ||
-        !previous || !z0 ||
-        (n_norm > 0 && (!norm_src || !norm_lo || !norm_span)) || (n_factors > 0 && (!fac_norm || !fac_kind || !fac_row || !fac_degree)) ||
-        (n_entries > 0 && !entries) || (n_spline_rows > 0 && !spline_table) || (n_bern_rows > 0 && !bern_table) ||
-        (n_forcing_cols > 0 && n_steps > 0 && !forcing))
-        return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
-    if (n_states > SIM_MAX_STATES)
-        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_states) + " states, the kernel is built for at most " +
-                                           std::to_string(SIM_MAX_STATES));
-    if (n_steps < 1) return fail(ctx, FOKL_ERR_ARG, who + "no step at all: the horizon needs at least one step");
-    if (n_steps > CTL_MAX_STEPS)
-        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_steps) + " steps, a call handles at most " + std::to_string(CTL_MAX_STEPS));
-    if (!(h > 0) || !std::isfinite(h)) return fail(ctx, FOKL_ERR_ARG, who + "h must be positive and finite");
-
-    sys = SimSystem{};
-    n_bern_factors = 0;
-    if (const int refused = sim_plan(ctx, who, n_states, h, n_forcing_cols, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
-                                     n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows,
-                                     n_bern_rows, n_entries, entries, entry_begin, entry_count, constant, n_coef, box, sys,
-                                     n_bern_factors))
-        return refused;
+    const bool own_ok = outputs_ok && problem && problem->seg_first && problem->norm_control && problem->ctl_lo &&
+                        problem->ctl_width && problem->ref && problem->track_weight && problem->terminal_weight &&
+                        problem->limit_lo && problem->limit_hi && problem->move_weight && problem->previous && problem->z0;
+    if (const int refused = sim_check(ctx, who, system, own_ok, ctl_steps_fit)) return refused;
+    const fokl_system &s = *system;
+    const fokl_control_problem &c = *problem;
+    if (const int refused = sim_plan(ctx, who, s, sys, n_bern_factors)) return refused;
 
     // ---- the decision values, their box and the cost ----
+    const int n_states = s.n_states, n_controls = c.n_controls, n_segments = c.n_segments;
+    const int64_t n_steps = s.n_steps;
     if (n_controls < 1 || n_segments < 1 || (int64_t)n_controls * n_segments > CTL_MAX_D)
         return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_controls) + " controls x " + std::to_string(n_segments) +
                                            " segments: at least one and at most " + std::to_string(CTL_MAX_D) + " decision values");
     const int D = n_controls * n_segments;
-    if (seg_first[0] != 0) return fail(ctx, FOKL_ERR_ARG, who + "the first segment must begin with step 0");
+    if (c.seg_first[0] != 0) return fail(ctx, FOKL_ERR_ARG, who + "the first segment must begin with step 0");
     for (int k = 1; k < n_segments; ++k)
-        if (seg_first[k] <= seg_first[k - 1] || seg_first[k] >= n_steps)
+        if (c.seg_first[k] <= c.seg_first[k - 1] || c.seg_first[k] >= n_steps)
             return fail(ctx, FOKL_ERR_ARG, who + "the segments' first steps must increase and lie below the number of steps");
     cp = CtlProblem{};
-    for (int c = 0; c < n_controls; ++c) {
-        if (!std::isfinite(ctl_lo[c]) || !std::isfinite(ctl_width[c]) || !(ctl_width[c] > 0))
+    for (int u = 0; u < n_controls; ++u) {
+        if (!std::isfinite(c.ctl_lo[u]) || !std::isfinite(c.ctl_width[u]) || !(c.ctl_width[u] > 0))
             return fail(ctx, FOKL_ERR_ARG, who + "a control's box is empty or not finite");
-        if (!(move_weight[c] >= 0) || !std::isfinite(move_weight[c]) || !std::isfinite(previous[c]))
+        if (!(c.move_weight[u] >= 0) || !std::isfinite(c.move_weight[u]) || !std::isfinite(c.previous[u]))
             return fail(ctx, FOKL_ERR_ARG, who + "move weights must be non-negative and finite, previous finite");
         bool read = false;
-        for (int n = 0; n < n_norm_forcing; ++n) {
-            if (norm_control[n] != c) continue;
+        for (int n = 0; n < s.n_norm_forcing; ++n) {
+            if (c.norm_control[n] != u) continue;
             read = true;
-            const double a = (ctl_lo[c] - norm_lo[n]) / norm_span[n], b = (ctl_lo[c] + ctl_width[c] - norm_lo[n]) / norm_span[n];
+            const double a = (c.ctl_lo[u] - s.norm_lo[n]) / s.norm_span[n],
+                         b = (c.ctl_lo[u] + c.ctl_width[u] - s.norm_lo[n]) / s.norm_span[n];
             if (a < -1e-9 || b > 1 + 1e-9)
                 return fail(ctx, FOKL_ERR_ARG, who + "a control's box reaches outside the training range of a column that reads it");
         }
         if (!read) return fail(ctx, FOKL_ERR_ARG, who + "a control is read by no model");
-        cp.lo[c] = ctl_lo[c];
-        cp.width[c] = ctl_width[c];
-        cp.move[c] = move_weight[c];
-        cp.prev[c] = previous[c];
+        cp.lo[u] = c.ctl_lo[u];
+        cp.width[u] = c.ctl_width[u];
+        cp.move[u] = c.move_weight[u];
+        cp.prev[u] = c.previous[u];
     }
-    for (int n = 0; n < n_norm_forcing; ++n)
-        if (norm_control[n] < -1 || norm_control[n] >= n_controls)
+    for (int n = 0; n < s.n_norm_forcing; ++n)
+        if (c.norm_control[n] < -1 || c.norm_control[n] >= n_controls)
             return fail(ctx, FOKL_ERR_ARG, who + "a forcing input reads outside the controls");
-    if (!(limit_weight >= 0) || !std::isfinite(limit_weight))
+    if (!(c.limit_weight >= 0) || !std::isfinite(c.limit_weight))
         return fail(ctx, FOKL_ERR_ARG, who + "the limit weight must be non-negative and finite");
     const int64_t n_points = n_steps + 1;
     bool any_residual = false;
     for (int j = 0; j < n_states; ++j) {
-        if (!(track_weight[j] >= 0) || !std::isfinite(track_weight[j]) || !(terminal_weight[j] >= 0) || !std::isfinite(terminal_weight[j]))
+        if (!(c.track_weight[j] >= 0) || !std::isfinite(c.track_weight[j]) || !(c.terminal_weight[j] >= 0) ||
+            !std::isfinite(c.terminal_weight[j]))
             return fail(ctx, FOKL_ERR_ARG, who + "negative weights are refused: tracking and terminal weights must be non-negative and finite");
-        if (std::isnan(limit_lo[j]) || std::isnan(limit_hi[j]) || limit_lo[j] > limit_hi[j] || limit_lo[j] == INFINITY || limit_hi[j] == -INFINITY)
+        if (std::isnan(c.limit_lo[j]) || std::isnan(c.limit_hi[j]) || c.limit_lo[j] > c.limit_hi[j] || c.limit_lo[j] == INFINITY ||
+            c.limit_hi[j] == -INFINITY)
             return fail(ctx, FOKL_ERR_ARG, who + "a state's limits must be lower <= upper (infinite: open)");
         for (int64_t q = 0; q < n_points; ++q) {
-            const double r = ref[j * n_points + q];
+            const double r = c.ref[j * n_points + q];
             if (std::isinf(r)) return fail(ctx, FOKL_ERR_ARG, who + "a target is infinite (NaN: not tracked)");
-            if (q > 0 && !std::isnan(r) && track_weight[j] > 0) any_residual = true;
+            if (q > 0 && !std::isnan(r) && c.track_weight[j] > 0) any_residual = true;
         }
-        if (terminal_weight[j] > 0) {
-            if (std::isnan(ref[j * n_points + n_steps]))
+        if (c.terminal_weight[j] > 0) {
+            if (std::isnan(c.ref[j * n_points + n_steps]))
                 return fail(ctx, FOKL_ERR_ARG, who + "a terminal weight needs a target at the last point");
             any_residual = true;
         }
-        if (limit_weight > 0 && (std::isfinite(limit_lo[j]) || std::isfinite(limit_hi[j]))) any_residual = true;
-        cp.wt[j] = track_weight[j];
-        cp.term[j] = terminal_weight[j];
-        cp.lim_lo[j] = limit_lo[j];
-        cp.lim_hi[j] = limit_hi[j];
+        if (c.limit_weight > 0 && (std::isfinite(c.limit_lo[j]) || std::isfinite(c.limit_hi[j]))) any_residual = true;
+        cp.wt[j] = c.track_weight[j];
+        cp.term[j] = c.terminal_weight[j];
+        cp.lim_lo[j] = c.limit_lo[j];
+        cp.lim_hi[j] = c.limit_hi[j];
     }
-    for (int c = 0; c < n_controls; ++c)
-        if (move_weight[c] > 0 && (n_segments > 1 || has_previous)) any_residual = true;
+    for (int u = 0; u < n_controls; ++u)
+        if (c.move_weight[u] > 0 && (n_segments > 1 || c.has_previous)) any_residual = true;
     if (!any_residual) return fail(ctx, FOKL_ERR_ARG, who + "no residual at all: nothing is tracked, limited or penalised");
-    if (n_starts < 1) return fail(ctx, FOKL_ERR_ARG, who + "starts must be at least 1");
-    if ((int64_t)n_draws * n_starts > CTL_MAX_SOLVES)
-        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_draws) + " draws x " + std::to_string(n_starts) +
+    if (c.n_starts < 1) return fail(ctx, FOKL_ERR_ARG, who + "starts must be at least 1");
+    if ((int64_t)s.n_members * c.n_starts > CTL_MAX_SOLVES)
+        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(s.n_members) + " draws x " + std::to_string(c.n_starts) +
                                            " starts: one call runs at most " + std::to_string(CTL_MAX_SOLVES) + " solves");
-    if (max_iter < 0 || !(tol >= 0)) return fail(ctx, FOKL_ERR_ARG, who + "max_iter and tol must be non-negative");
-    for (size_t i = 0; i < (size_t)n_starts * D; ++i)
-        if (!(z0[i] >= 0.0 && z0[i] <= 1.0)) return fail(ctx, FOKL_ERR_ARG, who + "a start lies outside the box [0, 1]");
-    for (size_t i = 0; i < (size_t)n_states * n_draws; ++i)
-        if (!std::isfinite(y0[i])) return fail(ctx, FOKL_ERR_ARG, who + "y0 is not finite");
-    const size_t lds_lane_rows = 2 * ((size_t)1 + n_factors + (n_norm - n_norm_forcing)) + 4 + D;
-    lds_bytes = lds_lane_rows * SIM_LANES * sizeof(double) + (size_t)n_coef * sizeof(double);
+    if (c.max_iter < 0 || !(c.tol >= 0)) return fail(ctx, FOKL_ERR_ARG, who + "max_iter and tol must be non-negative");
+    for (size_t i = 0; i < (size_t)c.n_starts * D; ++i)
+        if (!(c.z0[i] >= 0.0 && c.z0[i] <= 1.0)) return fail(ctx, FOKL_ERR_ARG, who + "a start lies outside the box [0, 1]");
+    for (size_t i = 0; i < (size_t)n_states * s.n_members; ++i)
+        if (!std::isfinite(s.y0[i])) return fail(ctx, FOKL_ERR_ARG, who + "y0 is not finite");
+    const size_t lds_lane_rows = 2 * ((size_t)1 + s.n_factors + (s.n_norm - s.n_norm_forcing)) + 4 + D;
+    lds_bytes = lds_lane_rows * SIM_LANES * sizeof(double) + (size_t)s.n_coef * sizeof(double);
     if (lds_bytes > SIM_LDS_BUDGET)
         return fail(ctx, FOKL_ERR_ARG, who + "the system needs " + std::to_string(lds_bytes) + " bytes of LDS ((2 x (1 + " +
-                                           std::to_string(n_factors) + " factors + " + std::to_string(n_norm - n_norm_forcing) +
+                                           std::to_string(s.n_factors) + " factors + " + std::to_string(s.n_norm - s.n_norm_forcing) +
                                            " normalised states) + 4 + " + std::to_string(D) + " decision values) x 64 x 8 + " +
-                                           std::to_string(n_coef) + " coefficients x 8), a wavefront has " +
+                                           std::to_string(s.n_coef) + " coefficients x 8), a wavefront has " +
                                            std::to_string(SIM_LDS_BUDGET));
     cp.D = D;
     cp.n_controls = n_controls;
     cp.segments = n_segments;
-    cp.n_starts = n_starts;
-    cp.n_draws = n_draws;
+    cp.n_starts = c.n_starts;
+    cp.n_draws = s.n_members;
     cp.n_steps = (int)n_steps;
-    cp.has_previous = has_previous ? 1 : 0;
-    cp.max_iter = max_iter;
-    cp.hl = limit_weight;
-    cp.tol = tol;
+    cp.has_previous = c.has_previous ? 1 : 0;
+    cp.max_iter = c.max_iter;
+    cp.hl = c.limit_weight;
+    cp.tol = c.tol;
     return FOKL_OK;
 }
 
@@ -741,34 +660,83 @@ struct CtlDevice {
     double *coef, *forcing, *y0;
 };
 
-hipError_t ctl_upload(DeviceBuffers &buf, const CtlArgs &in, CtlDevice &d)
+hipError_t ctl_upload(DeviceBuffers &buf, const fokl_system &s, const fokl_control_problem &c, CtlDevice &d)
 {
-    int *norm_src = nullptr, *fac_norm = nullptr, *fac_row = nullptr, *fac_degree = nullptr, *norm_control = nullptr, *seg = nullptr;
-    int4 *entries = nullptr;
-    double *norm_lo = nullptr, *norm_span = nullptr, *spline = nullptr, *bern = nullptr, *ref = nullptr;
-    const size_t E = (size_t)in.n_draws;
+    int *norm_control = nullptr, *seg = nullptr;
+    double *ref = nullptr;
+    const size_t E = (size_t)s.n_members;
     hipError_t e;
-#define CTL_UP(call)                                                                                                          \
-    if ((e = (call)) != hipSuccess) return e;
-    CTL_UP(buf.upload(&norm_src, in.norm_src, (size_t)in.n_norm))
-    CTL_UP(buf.upload(&norm_lo, in.norm_lo, (size_t)in.n_norm))
-    CTL_UP(buf.upload(&norm_span, in.norm_span, (size_t)in.n_norm))
-    CTL_UP(buf.upload(&fac_norm, in.fac_norm, (size_t)in.n_factors))
-    CTL_UP(buf.upload(&fac_row, in.fac_row, (size_t)in.n_factors))
-    CTL_UP(buf.upload(&fac_degree, in.fac_degree, (size_t)in.n_factors))
-    CTL_UP(buf.upload(&entries, in.entries, (size_t)in.n_entries))
-    CTL_UP(buf.upload(&spline, in.spline_table, (size_t)in.n_spline_rows * SIM_PIECES * 4))
-    CTL_UP(buf.upload(&bern, in.bern_table, (size_t)in.n_bern_rows * SIM_BERN_WIDTH))
-    CTL_UP(buf.upload(&norm_control, in.norm_control, (size_t)in.n_norm_forcing))
-    CTL_UP(buf.upload(&seg, in.seg_first, (size_t)in.n_segments))
-    CTL_UP(buf.upload(&ref, in.ref, (size_t)in.n_states * (in.n_steps + 1)))
-    CTL_UP(buf.upload(&d.coef, in.coef, E * in.n_coef))
-    CTL_UP(buf.upload(&d.forcing, in.forcing, (size_t)in.n_steps * in.n_forcing_cols))
-    CTL_UP(buf.upload(&d.y0, in.y0, E * in.n_states))
-#undef CTL_UP
-    d.tab = SimTables{norm_src, norm_lo, norm_span, fac_norm, fac_row, fac_degree, entries, spline, bern};
+    if ((e = sim_upload(buf, s, d.tab, d.forcing)) || (e = buf.upload(&norm_control, c.norm_control, (size_t)s.n_norm_forcing)) ||
+        (e = buf.upload(&seg, c.seg_first, (size_t)c.n_segments)) ||
+        (e = buf.upload(&ref, c.ref, (size_t)s.n_states * (s.n_steps + 1))) || (e = buf.upload(&d.coef, s.coef, E * s.n_coef)) ||
+        (e = buf.upload(&d.y0, s.y0, E * s.n_states)))
+        return e;
     d.ct = CtlTables{norm_control, seg, ref};
     return hipSuccess;
+}
+
+// Iteration `it` of every solve that is still running
+hipError_t ctl_iterate(fokl_ctx *ctx, int n_states, int grid, size_t lds_bytes, const SimSystem &sys, const CtlProblem &cp,
+                       const CtlDevice &d, double *z, int *status, int *iterations, int *descent, double *cost, double *cost_start,
+                       int *work, double *first_F, double *first_g, double *first_H, int it)
+{
+    return sim_dispatch(n_states, [&](auto ns) {
+        const auto kernel = control_iterate_kernel<decltype(ns)::value>;
+        if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, d.tab.norm_src, d.tab.norm_lo,
+                           d.tab.norm_span, d.tab.fac_norm, d.tab.fac_row, d.tab.fac_degree, d.tab.entries, d.tab.spline, d.tab.bern,
+                           d.ct.norm_control, d.ct.seg_first, d.ct.ref, (const double *)d.coef, (const double *)d.forcing,
+                           (const double *)d.y0, z, status, iterations, descent, cost, cost_start, work, first_F, first_g, first_H,
+                           it);
+        return hipGetLastError();
+    });
+}
+
+// Every draw's trajectory under z [grid][D], and the first step in which it saturated
+hipError_t ctl_trajectory(fokl_ctx *ctx, int n_states, int grid, size_t lds_bytes, const SimSystem &sys, const CtlProblem &cp,
+                          const CtlDevice &d, const double *z, double *members, int *first)
+{
+    return sim_dispatch(n_states, [&](auto ns) {
+        const auto kernel = control_trajectory_kernel<decltype(ns)::value>;
+        if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, d.tab.norm_src, d.tab.norm_lo,
+                           d.tab.norm_span, d.tab.fac_norm, d.tab.fac_row, d.tab.fac_degree, d.tab.entries, d.tab.spline, d.tab.bern,
+                           d.ct.norm_control, d.ct.seg_first, d.ct.ref, (const double *)d.coef, (const double *)d.forcing,
+                           (const double *)d.y0, z, members, first);
+        return hipGetLastError();
+    });
+}
+
+// The statuses are read back every FOKL_CONTROL_POLL iterations (0: never) so that a call may stop queuing early: an
+// iteration without work changes nothing.  stopped: iteration `it` was polled and left no status running.
+struct CtlPoll {
+    const int every = std::max(0, env_int("FOKL_CONTROL_POLL", 8));
+    std::vector<int32_t> seen;
+    int operator()(fokl_ctx *ctx, int it, int max_iter, const int *d_status, size_t count, bool &stopped)
+    {
+        stopped = false;
+        if (every == 0 || (it + 1) % every != 0 || it >= max_iter) return FOKL_OK;
+        seen.resize(count);
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(seen.data(), d_status, count * sizeof(int32_t), hipMemcpyDeviceToHost));
+        stopped = std::none_of(seen.begin(), seen.end(), [](int32_t status) { return status < 0; });
+        return FOKL_OK;
+    }
+};
+
+// The start with the lowest finite cost among cost / status [n_starts] (a non-finite solve is never the best; none: 0)
+int ctl_best_start(const double *cost, const int32_t *status, int n_starts)
+{
+    int best = 0;
+    double best_key = INFINITY;
+    for (int s = 0; s < n_starts; ++s) {
+        const double key = (std::isfinite(cost[s]) && status[s] != CTL_NON_FINITE) ? cost[s] : INFINITY;
+        if (key < best_key) {
+            best_key = key;
+            best = s;
+        }
+    }
+    return best;
 }
 
 }  // namespace
@@ -780,45 +748,26 @@ extern "C" int fokl_control_report(const fokl_ctx *ctx, int64_t *out)
     return FOKL_OK;
 }
 
-extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
-                                  const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
-                                  const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
-                                  const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
-                                  const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
-                                  const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
-                                  const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
-                                  const double *y0, const double *box, int n_controls, int n_segments,
-                                  const int32_t *seg_first, const int32_t *norm_control, const double *ctl_lo,
-                                  const double *ctl_width, const double *ref, const double *track_weight,
-                                  const double *terminal_weight, const double *limit_lo, const double *limit_hi,
-                                  double limit_weight, const double *move_weight, const double *previous, int has_previous,
-                                  int n_starts, const double *z0, int max_iter, double tol, double *z, double *cost,
-                                  double *cost_start, int32_t *status, int32_t *iterations, int32_t *descent_steps,
-                                  int32_t *best_start,
-                                  double *members, int32_t *first_saturation, double *first_F, double *first_g,
-                                  double *first_H)
+extern "C" int fokl_control_solve(fokl_ctx *ctx, const fokl_system *system, const fokl_control_problem *problem, double *z,
+                                  double *cost, double *cost_start, int32_t *status, int32_t *iterations,
+                                  int32_t *descent_steps, int32_t *best_start, double *members, int32_t *first_saturation,
+                                  double *first_F, double *first_g, double *first_H)
 {
     const std::string who = "fokl_control_solve: ";
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
     std::memset(ctx->control_report, 0, sizeof ctx->control_report);
-    if (!z || !cost || !cost_start || !status || !iterations || !descent_steps || !best_start || !members || !first_saturation ||
-        (first_F == nullptr) != (first_g == nullptr) || (first_F == nullptr) != (first_H == nullptr))
-        return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
-    const CtlArgs args{n_draws, n_states, n_steps, h, n_forcing_cols, forcing, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
-                       n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows, spline_table,
-                       n_bern_rows, bern_table, n_entries, entries, entry_begin, entry_count, constant, n_coef, coef, y0, box,
-                       n_controls, n_segments, seg_first, norm_control, ctl_lo, ctl_width, ref, track_weight, terminal_weight,
-                       limit_lo, limit_hi, limit_weight, move_weight, previous, has_previous, n_starts, z0, max_iter, tol};
+    const bool outputs_ok = z && cost && cost_start && status && iterations && descent_steps && best_start && members &&
+                            first_saturation && (first_F == nullptr) == (first_g == nullptr) &&
+                            (first_F == nullptr) == (first_H == nullptr);
     SimSystem sys{};
     CtlProblem cp{};
     size_t lds_bytes = 0;
     int n_bern_factors = 0;
-    if (const int refused = ctl_plan(ctx, who, args, sys, cp, lds_bytes, n_bern_factors)) return refused;
-    const int D = cp.D;
-    const int64_t n_points = n_steps + 1;
-
-    const size_t E = (size_t)n_draws, B = E * n_starts;
-    const int poll = std::max(0, env_int("FOKL_CONTROL_POLL", 8));    // read the statuses every `poll` launches; 0: never
+    if (const int refused = ctl_plan(ctx, who, system, problem, outputs_ok, sys, cp, lds_bytes, n_bern_factors)) return refused;
+    const fokl_system &s = *system;
+    const int D = cp.D, n_states = s.n_states, n_starts = cp.n_starts, max_iter = cp.max_iter;
+    const int64_t n_steps = s.n_steps, n_points = n_steps + 1;
+    const size_t E = (size_t)s.n_members, B = E * n_starts;
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DeviceBuffers buf;
@@ -826,12 +775,9 @@ extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int6
     double *d_z = nullptr, *d_cost = nullptr, *d_cost_start = nullptr, *d_fF = nullptr, *d_fg = nullptr, *d_fH = nullptr,
            *d_zbest = nullptr, *d_members = nullptr;
     CtlDevice dev{};
-    HIP_TRY(ctx, ctl_upload(buf, args, dev));
-    const SimTables &tab = dev.tab;
-    const CtlTables &ct = dev.ct;
-    double *d_coef = dev.coef, *d_forcing = dev.forcing, *d_y0 = dev.y0;
+    HIP_TRY(ctx, ctl_upload(buf, s, *problem, dev));
     std::vector<double> z_start(B * D);
-    for (size_t b = 0; b < B; ++b) std::memcpy(z_start.data() + b * D, z0 + (b % n_starts) * D, D * sizeof(double));
+    for (size_t b = 0; b < B; ++b) std::memcpy(z_start.data() + b * D, problem->z0 + (b % n_starts) * D, D * sizeof(double));
     std::vector<int32_t> h_status(B, -1), h_zero((size_t)max_iter + 1, 0);
     std::vector<double> h_nan(B, NAN);
     HIP_TRY(ctx, buf.upload(&d_z, z_start.data(), B * D));
@@ -851,33 +797,19 @@ extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int6
     HIP_TRY(ctx, buf.get(&d_members, E * n_states * n_points));
     HIP_TRY(ctx, buf.get(&d_first, E));
 
-    double terms_per_stage = 0.0;
-    for (int k = 0; k < n_states; ++k) terms_per_stage += sys.entry_count[k];
+    const double pass_flops = (double)SIM_LANES * (double)n_steps * 4.0 * (8.0 * sim_terms_per_stage(sys, n_states) + 20.0 * s.n_factors);
+    CtlPoll poll;
     int64_t queued = 0;
     for (int it = 0; it <= max_iter; ++it) {
         {
-            TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)B * (D + 4.0),
-                              (double)B * SIM_LANES * (double)n_steps * 4.0 * 3.0 * (8.0 * terms_per_stage + 20.0 * n_factors));
-            hipError_t launched = hipSuccess;
-#define CTL_CASE(NS)                                                                                                         \
-    case NS:                                                                                                                 \
-        launched = ctl_launch<NS>(ctx, (int)B, lds_bytes, sys, cp, tab, ct, d_coef, d_forcing, d_y0, d_z, d_status,             \
-                                  d_iterations, d_descent, d_cost, d_cost_start, d_work, d_fF, d_fg, d_fH, it);                           \
-        break;
-            switch (n_states) {
-                CTL_CASE(1) CTL_CASE(2) CTL_CASE(3) CTL_CASE(4) CTL_CASE(5) CTL_CASE(6) CTL_CASE(7) CTL_CASE(8)
-            }
-#undef CTL_CASE
-            HIP_TRY(ctx, launched);
+            TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)B * (D + 4.0), (double)B * pass_flops * 3.0);
+            HIP_TRY(ctx, ctl_iterate(ctx, n_states, (int)B, lds_bytes, sys, cp, dev, d_z, d_status, d_iterations, d_descent, d_cost,
+                                     d_cost_start, d_work, d_fF, d_fg, d_fH, it));
             ++queued;
         }
-        if (poll > 0 && (it + 1) % poll == 0 && it < max_iter) {      // may stop queuing early: a launch without work changes nothing
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(h_status.data(), d_status, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-            bool running = false;
-            for (size_t b = 0; b < B && !running; ++b) running = h_status[b] < 0;
-            if (!running) break;
-        }
+        bool stopped = false;
+        if (const int failed = poll(ctx, it, max_iter, d_status, B, stopped)) return failed;
+        if (stopped) break;
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(z, d_z, B * D * sizeof(double), hipMemcpyDeviceToHost));
@@ -897,37 +829,16 @@ extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int6
     int64_t worked = 0;
     for (int32_t w : h_zero) worked += w;
 
-    // ---- the best start of every draw (a non-finite solve is never the best), and its trajectory ----
+    // ---- the best start of every draw, and its trajectory ----
     std::vector<double> z_best(E * D);
     for (size_t e = 0; e < E; ++e) {
-        int best = 0;
-        double best_key = INFINITY;
-        for (int s = 0; s < n_starts; ++s) {
-            const size_t b = e * n_starts + s;
-            const double key = (std::isfinite(cost[b]) && status[b] != CTL_NON_FINITE) ? cost[b] : INFINITY;
-            if (key < best_key) {
-                best_key = key;
-                best = s;
-            }
-        }
-        best_start[e] = best;
-        std::memcpy(z_best.data() + e * D, z + (e * n_starts + best) * D, D * sizeof(double));
+        best_start[e] = ctl_best_start(cost + e * n_starts, status + e * n_starts, n_starts);
+        std::memcpy(z_best.data() + e * D, z + (e * n_starts + best_start[e]) * D, D * sizeof(double));
     }
     HIP_TRY(ctx, hipMemcpy(d_zbest, z_best.data(), E * D * sizeof(double), hipMemcpyHostToDevice));
     {
-        TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)E * n_states * n_points,
-                          (double)E * SIM_LANES * (double)n_steps * 4.0 * (8.0 * terms_per_stage + 20.0 * n_factors));
-        hipError_t launched = hipSuccess;
-#define CTL_CASE(NS)                                                                                                         \
-    case NS:                                                                                                                 \
-        launched = ctl_trajectory<NS>(ctx, n_draws, lds_bytes, sys, cp, tab, ct, d_coef, d_forcing, d_y0, d_zbest, d_members,  \
-                                      d_first);                                                                              \
-        break;
-        switch (n_states) {
-            CTL_CASE(1) CTL_CASE(2) CTL_CASE(3) CTL_CASE(4) CTL_CASE(5) CTL_CASE(6) CTL_CASE(7) CTL_CASE(8)
-        }
-#undef CTL_CASE
-        HIP_TRY(ctx, launched);
+        TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)E * n_states * n_points, (double)E * pass_flops);
+        HIP_TRY(ctx, ctl_trajectory(ctx, n_states, (int)E, lds_bytes, sys, cp, dev, d_zbest, d_members, d_first));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(members, d_members, E * n_states * n_points * sizeof(double), hipMemcpyDeviceToHost));
@@ -939,7 +850,7 @@ extern "C" int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int6
     rep[3] = (int64_t)lds_bytes;
     rep[4] = queued;
     rep[5] = worked;
-    rep[6] = n_factors - n_bern_factors;
+    rep[6] = s.n_factors - n_bern_factors;
     rep[7] = n_bern_factors;
     return FOKL_OK;
 }

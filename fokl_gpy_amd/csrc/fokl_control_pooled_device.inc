@@ -88,39 +88,19 @@ __global__ __launch_bounds__(CTL_POOL_BLOCK) void control_pooled_chunk_kernel(co
     sums[sc * (size_t)n + i] = acc;
 }
 
-// Launch 3.  sums [starts][chunks][n]; trial [starts][D][64]; slope [starts][64]; moved [starts][64] (the lane is a trial
-// AND moves z); pooled [starts][2 + D] = F, noise, g; first [starts][n] (or null): the pooled row of iteration 0
-__global__ __launch_bounds__(SIM_LANES) void control_pooled_step_kernel(
-    CtlProblem cp, const double *__restrict__ sums, int n_chunks, const double *__restrict__ z, int *__restrict__ status,
-    int *__restrict__ iterations, double *__restrict__ cost, double *__restrict__ cost_start, int *__restrict__ work,
-    double *__restrict__ trial, double *__restrict__ slope_out, int *__restrict__ moved_out, double *__restrict__ pooled,
-    double *__restrict__ first, int it)
+// What control_pooled_step_kernel and control_cvar_step_kernel do for start s once its F, noise, g (lane d: g[d]) and H (lane
+// d: row d, in the LDS layout below) are formed: iteration 0's record, the stop test, the Newton direction, the trial points.
+// lds: exchange, z, g, direction [64] each, then H as [D][64]; z is there already.
+__device__ __forceinline__ void ctl_pooled_step(const CtlProblem &cp, size_t s, int lane, int it, double F, double noise, double g,
+                                                double zl, double *lds, int *__restrict__ status, int *__restrict__ iterations,
+                                                double *__restrict__ cost, double *__restrict__ cost_start,
+                                                double *__restrict__ trial, double *__restrict__ slope_out,
+                                                int *__restrict__ moved_out, double *__restrict__ pooled,
+                                                double *__restrict__ first)
 {
-    const size_t s = blockIdx.x;
-    if (status[s] >= 0) return;
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int lane = threadIdx.x, D = cp.D, n = 2 + D + D * D;
+    const int D = cp.D, n = 2 + D + D * D;
     double *ex = lds, *zs = ex + SIM_LANES, *gs = zs + SIM_LANES, *ds = gs + SIM_LANES, *H = ds + SIM_LANES;
     double *Hl = H + lane;                                             // Hl[d' * 64] = H[lane][d']
-    if (lane == 0) work[it] = 1;
-    const double zl = lane < D ? z[s * D + lane] : 0.0;
-    zs[lane] = zl;
-    // ---- the chunk sums in chunk order from the first ----
-    const double *cs = sums + s * (size_t)n_chunks * n;
-    double F = cs[0], noise = cs[1], g = lane < D ? cs[2 + lane] : 0.0;
-    for (int c = 1; c < n_chunks; ++c) {
-        F = F + cs[(size_t)c * n];
-        noise = noise + cs[(size_t)c * n + 1];
-        if (lane < D) g = g + cs[(size_t)c * n + 2 + lane];
-    }
-    for (int d2 = 0; d2 < D; ++d2) {
-        double h = 0.0;
-        if (lane < D) {
-            h = cs[2 + D + lane * D + d2];
-            for (int c = 1; c < n_chunks; ++c) h = h + cs[(size_t)c * n + 2 + D + lane * D + d2];
-        }
-        Hl[d2 * SIM_LANES] = h;
-    }
     if (it == 0) {
         if (lane == 0) cost_start[s] = F;
         if (first) {
@@ -158,6 +138,42 @@ __global__ __launch_bounds__(SIM_LANES) void control_pooled_step_kernel(
         pooled[s * (2 + D) + 1] = noise;
     }
     if (lane < D) pooled[s * (2 + D) + 2 + lane] = g;
+}
+
+// Launch 3.  sums [starts][chunks][n]; trial [starts][D][64]; slope [starts][64]; moved [starts][64] (the lane is a trial
+// AND moves z); pooled [starts][2 + D] = F, noise, g; first [starts][n] (or null): the pooled row of iteration 0
+__global__ __launch_bounds__(SIM_LANES) void control_pooled_step_kernel(
+    CtlProblem cp, const double *__restrict__ sums, int n_chunks, const double *__restrict__ z, int *__restrict__ status,
+    int *__restrict__ iterations, double *__restrict__ cost, double *__restrict__ cost_start, int *__restrict__ work,
+    double *__restrict__ trial, double *__restrict__ slope_out, int *__restrict__ moved_out, double *__restrict__ pooled,
+    double *__restrict__ first, int it)
+{
+    const size_t s = blockIdx.x;
+    if (status[s] >= 0) return;
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int lane = threadIdx.x, D = cp.D, n = 2 + D + D * D;
+    double *zs = lds + SIM_LANES, *Hl = lds + 4 * SIM_LANES + lane;    // ctl_pooled_step's layout: Hl[d' * 64] = H[lane][d']
+    if (lane == 0) work[it] = 1;
+    const double zl = lane < D ? z[s * D + lane] : 0.0;
+    zs[lane] = zl;
+    // ---- the chunk sums in chunk order from the first ----
+    const double *cs = sums + s * (size_t)n_chunks * n;
+    double F = cs[0], noise = cs[1], g = lane < D ? cs[2 + lane] : 0.0;
+    for (int c = 1; c < n_chunks; ++c) {
+        F = F + cs[(size_t)c * n];
+        noise = noise + cs[(size_t)c * n + 1];
+        if (lane < D) g = g + cs[(size_t)c * n + 2 + lane];
+    }
+    for (int d2 = 0; d2 < D; ++d2) {
+        double h = 0.0;
+        if (lane < D) {
+            h = cs[2 + D + lane * D + d2];
+            for (int c = 1; c < n_chunks; ++c) h = h + cs[(size_t)c * n + 2 + D + lane * D + d2];
+        }
+        Hl[d2 * SIM_LANES] = h;
+    }
+    ctl_pooled_step(cp, s, lane, it, F, noise, g, zl, lds, status, iterations, cost, cost_start, trial, slope_out, moved_out, pooled,
+                    first);
 }
 
 // Launch 4 (and, with w null, one start and every lane at the same point, the draws' own costs at the returned controls).
@@ -260,35 +276,32 @@ struct PooledClock {
     }
 };
 
-template <typename Kernel>
-hipError_t pooled_lds(Kernel kernel, size_t lds_bytes)
+hipError_t pooled_tangent(fokl_ctx *ctx, int n_states, int grid, size_t lds_bytes, const SimSystem &sys, const CtlProblem &cp,
+                          const CtlDevice &d, const double *z, const int *status, const double *w, double *rows)
 {
-    if (lds_bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS_BUDGET);
+    return sim_dispatch(n_states, [&](auto ns) {
+        const auto kernel = control_pooled_tangent_kernel<decltype(ns)::value>;
+        if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, d.tab.norm_src, d.tab.norm_lo,
+                           d.tab.norm_span, d.tab.fac_norm, d.tab.fac_row, d.tab.fac_degree, d.tab.entries, d.tab.spline, d.tab.bern,
+                           d.ct.norm_control, d.ct.seg_first, d.ct.ref, (const double *)d.coef, (const double *)d.forcing,
+                           (const double *)d.y0, z, status, w, rows);
+        return hipGetLastError();
+    });
 }
 
-template <int NS>
-hipError_t pooled_tangent(fokl_ctx *ctx, int grid, size_t lds_bytes, const SimSystem &sys, const CtlProblem &cp, const CtlDevice &d,
-                          const double *z, const int *status, const double *w, double *rows)
+hipError_t pooled_trial(fokl_ctx *ctx, int n_states, int grid, size_t lds_bytes, const SimSystem &sys, const CtlProblem &cp,
+                        const CtlDevice &d, const double *trial, const int *status, const double *w, double *ft)
 {
-    if (hipError_t e = pooled_lds(control_pooled_tangent_kernel<NS>, lds_bytes)) return e;
-    hipLaunchKernelGGL(control_pooled_tangent_kernel<NS>, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp,
-                       d.tab.norm_src, d.tab.norm_lo, d.tab.norm_span, d.tab.fac_norm, d.tab.fac_row, d.tab.fac_degree, d.tab.entries,
-                       d.tab.spline, d.tab.bern, d.ct.norm_control, d.ct.seg_first, d.ct.ref, d.coef, d.forcing, d.y0, z, status, w,
-                       rows);
-    return hipGetLastError();
-}
-
-template <int NS>
-hipError_t pooled_trial(fokl_ctx *ctx, int grid, size_t lds_bytes, const SimSystem &sys, const CtlProblem &cp, const CtlDevice &d,
-                        const double *trial, const int *status, const double *w, double *ft)
-{
-    if (hipError_t e = pooled_lds(control_pooled_trial_kernel<NS>, lds_bytes)) return e;
-    hipLaunchKernelGGL(control_pooled_trial_kernel<NS>, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp,
-                       d.tab.norm_src, d.tab.norm_lo, d.tab.norm_span, d.tab.fac_norm, d.tab.fac_row, d.tab.fac_degree, d.tab.entries,
-                       d.tab.spline, d.tab.bern, d.ct.norm_control, d.ct.seg_first, d.ct.ref, d.coef, d.forcing, d.y0, trial, status, w,
-                       ft);
-    return hipGetLastError();
+    return sim_dispatch(n_states, [&](auto ns) {
+        const auto kernel = control_pooled_trial_kernel<decltype(ns)::value>;
+        if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, d.tab.norm_src, d.tab.norm_lo,
+                           d.tab.norm_span, d.tab.fac_norm, d.tab.fac_row, d.tab.fac_degree, d.tab.entries, d.tab.spline, d.tab.bern,
+                           d.ct.norm_control, d.ct.seg_first, d.ct.ref, (const double *)d.coef, (const double *)d.forcing,
+                           (const double *)d.y0, trial, status, w, ft);
+        return hipGetLastError();
+    });
 }
 
 // For the first_trial outputs: NaN into a buffer that iteration 0 may leave unwritten in places
@@ -307,17 +320,176 @@ hipError_t pooled_chunks(fokl_ctx *ctx, const double *rows, const double *w, con
     return hipGetLastError();
 }
 
-#define POOLED_NS_SWITCH(call, ...)                                                                                           \
-    switch (n_states) {                                                                                                       \
-        case 1: launched = call<1>(__VA_ARGS__); break;                                                                       \
-        case 2: launched = call<2>(__VA_ARGS__); break;                                                                       \
-        case 3: launched = call<3>(__VA_ARGS__); break;                                                                       \
-        case 4: launched = call<4>(__VA_ARGS__); break;                                                                       \
-        case 5: launched = call<5>(__VA_ARGS__); break;                                                                       \
-        case 6: launched = call<6>(__VA_ARGS__); break;                                                                       \
-        case 7: launched = call<7>(__VA_ARGS__); break;                                                                       \
-        case 8: launched = call<8>(__VA_ARGS__); break;                                                                       \
+// The outputs fokl_control_pooled_solve and fokl_control_cvar_solve share
+struct PooledOutputs {
+    double *z, *cost, *cost_start;
+    int32_t *status, *iterations, *descent_steps, *best_start;
+    double *members;
+    int32_t *first_saturation;
+    double *cost_draws, *first_pooled, *first_rows;
+    bool complete() const
+    {
+        return z && cost && cost_start && status && iterations && descent_steps && best_start && members && first_saturation &&
+               cost_draws && (first_pooled == nullptr) == (first_rows == nullptr);
     }
+};
+
+int pooled_weights_check(fokl_ctx *ctx, const std::string &who, int n_draws, const double *draw_weights)
+{
+    double weight_sum = 0.0;
+    for (int e = 0; e < n_draws; ++e) {
+        if (!(draw_weights[e] >= 0) || !std::isfinite(draw_weights[e]))
+            return fail(ctx, FOKL_ERR_ARG, who + "draw weights must be non-negative and finite");
+        weight_sum += draw_weights[e];
+    }
+    if (!(weight_sum > 0)) return fail(ctx, FOKL_ERR_ARG, who + "the draw weights sum to zero: at least one draw must weigh something");
+    return FOKL_OK;
+}
+
+// What both solves keep on the device (S starts, E draws, B = E S, n = 2 + D + D D): the state of the starts, the draws'
+// rows and trial costs, the step kernel's outputs, and the buffers of the closing trajectory.  sums is [S][chunks][sums_width].
+struct PooledWork {
+    int D, n, n_chunks;
+    size_t E, S, B;
+    int *status = nullptr, *iterations = nullptr, *descent = nullptr, *work = nullptr, *first = nullptr, *moved = nullptr,
+        *running = nullptr;
+    double *w = nullptr, *z = nullptr, *cost = nullptr, *cost_start = nullptr, *rows = nullptr, *sums = nullptr, *ft = nullptr,
+           *trial = nullptr, *slope = nullptr, *pooled = nullptr, *fpool = nullptr, *zbest = nullptr, *members = nullptr;
+    std::vector<int32_t> h_work;
+
+    PooledWork(const CtlProblem &cp)
+        : D(cp.D), n(2 + cp.D + cp.D * cp.D), n_chunks((cp.n_draws + CTL_POOL_CHUNK - 1) / CTL_POOL_CHUNK), E((size_t)cp.n_draws),
+          S((size_t)cp.n_starts), B(E * S), h_work((size_t)cp.max_iter + 1, 0)
+    {
+    }
+
+    // want_first: rows and the pooled row of iteration 0 are read back (a draw of weight 0 writes no row: it reads NaN);
+    // fill_trial: what iteration 0 does not write of the first_trial fields kept here reads NaN, moved 0
+    int alloc(fokl_ctx *ctx, DeviceBuffers &buf, const fokl_system &s, const double *draw_weights, const double *z0,
+              size_t sums_width, bool want_first, bool fill_trial)
+    {
+        const std::vector<int32_t> h_status(S, -1), h_none(S, 0);
+        const std::vector<double> h_nan(S, NAN);
+        HIP_TRY(ctx, buf.upload(&w, draw_weights, E));
+        HIP_TRY(ctx, buf.upload(&z, z0, S * D));
+        HIP_TRY(ctx, buf.upload(&status, h_status.data(), S));
+        HIP_TRY(ctx, buf.upload(&iterations, h_status.data(), S));
+        HIP_TRY(ctx, buf.upload(&descent, h_none.data(), S));
+        HIP_TRY(ctx, buf.upload(&cost, h_nan.data(), S));
+        HIP_TRY(ctx, buf.upload(&cost_start, h_nan.data(), S));
+        HIP_TRY(ctx, buf.upload(&work, h_work.data(), h_work.size()));
+        HIP_TRY(ctx, buf.upload(&running, h_status.data(), 1));
+        HIP_TRY(ctx, buf.get(&rows, B * n));
+        HIP_TRY(ctx, buf.get(&sums, S * n_chunks * sums_width));
+        HIP_TRY(ctx, buf.get(&ft, B * SIM_LANES));
+        HIP_TRY(ctx, buf.get(&trial, S * D * SIM_LANES));
+        HIP_TRY(ctx, buf.get(&slope, S * SIM_LANES));
+        HIP_TRY(ctx, buf.get(&moved, S * SIM_LANES));
+        HIP_TRY(ctx, buf.get(&pooled, S * (2 + D)));
+        if (want_first) {
+            HIP_TRY(ctx, pooled_fill_nan(rows, B * n));
+            HIP_TRY(ctx, buf.get(&fpool, S * n));
+        }
+        if (fill_trial) {
+            HIP_TRY(ctx, pooled_fill_nan(trial, S * D * SIM_LANES));
+            HIP_TRY(ctx, pooled_fill_nan(slope, S * SIM_LANES));
+            HIP_TRY(ctx, pooled_fill_nan(pooled, S * (2 + D)));
+            HIP_TRY(ctx, pooled_fill_nan(ft, B * SIM_LANES));
+            HIP_TRY(ctx, hipMemset(moved, 0, S * SIM_LANES * sizeof(int)));
+        }
+        HIP_TRY(ctx, buf.get(&zbest, E * D));
+        HIP_TRY(ctx, buf.get(&members, E * s.n_states * (s.n_steps + 1)));
+        HIP_TRY(ctx, buf.get(&first, E));
+        return FOKL_OK;
+    }
+
+    // Iteration 0's trial half, before a later one overwrites it: the fields both solves fill
+    int first_trial_out(fokl_ctx *ctx, const fokl_control_first_trial &t) const
+    {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(t.trial, trial, S * D * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(t.slope, slope, S * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(t.moved, moved, S * SIM_LANES * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(t.pooled, pooled, S * (2 + D) * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(t.ft, ft, B * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(t.z, z, S * D * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(t.status, status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(t.descent, descent, S * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return FOKL_OK;
+    }
+
+    // After the last iteration: the starts' results, the best start, every draw's trajectory and own cost under its controls
+    // (one start -- `running` holds -1 -- and no weights: every draw's value pass at the returned point, lane 0 is read).
+    // worked: the iterations that found a running start.
+    int finish(fokl_ctx *ctx, const std::string &who, const fokl_system &s, const SimSystem &sys, const CtlProblem &cp,
+               size_t lds_bytes, const CtlDevice &dev, double pass_flops, const PooledOutputs &out, int64_t &worked)
+    {
+        const int64_t n_points = s.n_steps + 1;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(out.z, z, S * D * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.cost, cost, S * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.cost_start, cost_start, S * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.status, status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.iterations, iterations, S * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.descent_steps, descent, S * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(h_work.data(), work, h_work.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (out.first_pooled) {
+            HIP_TRY(ctx, hipMemcpy(out.first_pooled, fpool, S * n * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(out.first_rows, rows, B * n * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        for (size_t k = 0; k < S; ++k)
+            if (out.status[k] < 0) return fail(ctx, FOKL_ERR_HIP, who + "a solve was left running");
+        worked = 0;
+        for (int32_t found : h_work) worked += found;
+
+        const int best = ctl_best_start(out.cost, out.status, (int)S);
+        *out.best_start = best;
+        std::vector<double> z_best(E * D), point((size_t)D * SIM_LANES);
+        for (size_t e = 0; e < E; ++e) std::memcpy(z_best.data() + e * D, out.z + (size_t)best * D, D * sizeof(double));
+        for (int d = 0; d < D; ++d)
+            for (int lane = 0; lane < SIM_LANES; ++lane) point[(size_t)d * SIM_LANES + lane] = out.z[(size_t)best * D + d];
+        HIP_TRY(ctx, hipMemcpy(zbest, z_best.data(), E * D * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(trial, point.data(), point.size() * sizeof(double), hipMemcpyHostToDevice));
+        {
+            TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)E * s.n_states * n_points, 2.0 * pass_flops / (double)S);
+            HIP_TRY(ctx, ctl_trajectory(ctx, s.n_states, (int)E, lds_bytes, sys, cp, dev, zbest, members, first));
+            HIP_TRY(ctx, pooled_trial(ctx, s.n_states, (int)E, lds_bytes, sys, cp, dev, trial, running, nullptr, ft));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(out.members, members, E * s.n_states * n_points * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(out.first_saturation, first, E * sizeof(int32_t), hipMemcpyDeviceToHost));
+        std::vector<double> h_ft(E * SIM_LANES);
+        HIP_TRY(ctx, hipMemcpy(h_ft.data(), ft, h_ft.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t e = 0; e < E; ++e) out.cost_draws[e] = h_ft[e * SIM_LANES];
+        return FOKL_OK;
+    }
+
+    // out[0 .. 6] of both reports
+    void report_head(int64_t *rep, int n_states, size_t lds_bytes, size_t step_lds) const
+    {
+        rep[0] = n_states;
+        rep[1] = (int64_t)E;
+        rep[2] = (int64_t)S;
+        rep[3] = D;
+        rep[4] = n_chunks;
+        rep[5] = (int64_t)lds_bytes;
+        rep[6] = (int64_t)step_lds;
+    }
+};
+
+// The workspace against the device's free memory, of which the environment variable `cap_env` caps what counts;
+// `what` spells the workspace out for the refusal
+int pooled_workspace_fits(fokl_ctx *ctx, const std::string &who, size_t workspace, const char *cap_env, const std::string &what)
+{
+    size_t free_bytes = 0, total_bytes = 0;
+    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
+    if (const char *cap = std::getenv(cap_env)) free_bytes = std::min<size_t>(free_bytes, std::strtoull(cap, nullptr, 10));
+    if (workspace > free_bytes)
+        return fail(ctx, FOKL_ERR_ARG, who + "the workspace needs " + std::to_string(workspace) + " bytes (" + what + "), the device has " +
+                                           std::to_string(free_bytes) + " free (" + cap_env +
+                                           " caps what counts; solve over fewer draws or starts)");
+    return FOKL_OK;
+}
 
 }  // namespace
 
@@ -328,238 +500,106 @@ extern "C" int fokl_control_pooled_report(const fokl_ctx *ctx, int64_t *out)
     return FOKL_OK;
 }
 
-extern "C" int fokl_control_pooled_solve(
-    fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols, const double *forcing,
-    int n_norm_forcing, int n_norm, const int32_t *norm_src, const double *norm_lo, const double *norm_span, int n_forcing_factors,
-    int n_factors, const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row, const int32_t *fac_degree,
-    int n_spline_rows, const double *spline_table, int n_bern_rows, const double *bern_table, int n_entries, const int32_t *entries,
-    const int32_t *entry_begin, const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef, const double *y0,
-    const double *box, int n_controls, int n_segments, const int32_t *seg_first, const int32_t *norm_control, const double *ctl_lo,
-    const double *ctl_width, const double *ref, const double *track_weight, const double *terminal_weight, const double *limit_lo,
-    const double *limit_hi, double limit_weight, const double *move_weight, const double *previous, int has_previous, int n_starts,
-    const double *z0, int max_iter, double tol, const double *draw_weights, double *z, double *cost, double *cost_start,
-    int32_t *status, int32_t *iterations, int32_t *descent_steps, int32_t *best_start, double *members, int32_t *first_saturation,
-    double *cost_draws, double *first_pooled, double *first_rows, const fokl_control_first_trial *first_trial)
+extern "C" int fokl_control_pooled_solve(fokl_ctx *ctx, const fokl_system *system, const fokl_control_problem *problem,
+                                         const double *draw_weights, double *z, double *cost, double *cost_start,
+                                         int32_t *status, int32_t *iterations, int32_t *descent_steps, int32_t *best_start,
+                                         double *members, int32_t *first_saturation, double *cost_draws, double *first_pooled,
+                                         double *first_rows, const fokl_control_first_trial *first_trial)
 {
     const std::string who = "fokl_control_pooled_solve: ";
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
     std::memset(ctx->control_pooled_report, 0, sizeof ctx->control_pooled_report);
-    if (!draw_weights || !z || !cost || !cost_start || !status || !iterations || !descent_steps || !best_start || !members ||
-        !first_saturation || !cost_draws || (first_pooled == nullptr) != (first_rows == nullptr) ||
-        (first_trial && (!first_trial->trial || !first_trial->slope || !first_trial->moved || !first_trial->pooled || !first_trial->ft ||
-                         !first_trial->ft_sums || !first_trial->z || !first_trial->status || !first_trial->descent)))
-        return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
-    const CtlArgs args{n_draws, n_states, n_steps, h, n_forcing_cols, forcing, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
-                       n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows, spline_table,
-                       n_bern_rows, bern_table, n_entries, entries, entry_begin, entry_count, constant, n_coef, coef, y0, box,
-                       n_controls, n_segments, seg_first, norm_control, ctl_lo, ctl_width, ref, track_weight, terminal_weight,
-                       limit_lo, limit_hi, limit_weight, move_weight, previous, has_previous, n_starts, z0, max_iter, tol};
+    const PooledOutputs out{z, cost, cost_start, status, iterations, descent_steps, best_start, members, first_saturation,
+                            cost_draws, first_pooled, first_rows};
+    const bool outputs_ok =
+        draw_weights && out.complete() &&
+        (!first_trial || (first_trial->trial && first_trial->slope && first_trial->moved && first_trial->pooled && first_trial->ft &&
+                          first_trial->ft_sums && first_trial->z && first_trial->status && first_trial->descent));
     SimSystem sys{};
     CtlProblem cp{};
     size_t lds_bytes = 0;
     int n_bern_factors = 0;
-    if (const int refused = ctl_plan(ctx, who, args, sys, cp, lds_bytes, n_bern_factors)) return refused;
-    double weight_sum = 0.0;
-    for (int e = 0; e < n_draws; ++e) {
-        if (!(draw_weights[e] >= 0) || !std::isfinite(draw_weights[e]))
-            return fail(ctx, FOKL_ERR_ARG, who + "draw weights must be non-negative and finite");
-        weight_sum += draw_weights[e];
-    }
-    if (!(weight_sum > 0)) return fail(ctx, FOKL_ERR_ARG, who + "the draw weights sum to zero: at least one draw must weigh something");
+    if (const int refused = ctl_plan(ctx, who, system, problem, outputs_ok, sys, cp, lds_bytes, n_bern_factors)) return refused;
+    const fokl_system &s = *system;
+    const int n_draws = s.n_members, n_states = s.n_states, n_starts = cp.n_starts, max_iter = cp.max_iter;
+    if (const int refused = pooled_weights_check(ctx, who, n_draws, draw_weights)) return refused;
 
-    const int D = cp.D, n = 2 + D + D * D, n_chunks = (n_draws + CTL_POOL_CHUNK - 1) / CTL_POOL_CHUNK;
-    const int64_t n_points = n_steps + 1;
-    const size_t E = (size_t)n_draws, S = (size_t)n_starts, B = E * S;
+    PooledWork k(cp);
+    const int D = k.D, n = k.n, n_chunks = k.n_chunks;
+    const size_t S = k.S, B = k.B;
     const size_t step_lds = (size_t)(4 + D) * SIM_LANES * sizeof(double);
-    const int poll = std::max(0, env_int("FOKL_CONTROL_POLL", 8));    // read the statuses every `poll` iterations; 0: never
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // ---- the workspace against the device's free memory (FOKL_CONTROL_POOLED_FREE_BYTES caps what counts as free) ----
     const size_t workspace = (B * (size_t)(n + SIM_LANES) + S * n_chunks * (size_t)(n + SIM_LANES)) * sizeof(double);
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    if (const char *cap = std::getenv("FOKL_CONTROL_POOLED_FREE_BYTES"))
-        free_bytes = std::min<size_t>(free_bytes, std::strtoull(cap, nullptr, 10));
-    if (workspace > free_bytes)
-        return fail(ctx, FOKL_ERR_ARG,
-                    who + "the workspace needs " + std::to_string(workspace) + " bytes (" + std::to_string(n_draws) + " draws x " +
-                        std::to_string(n_starts) + " starts x (2 + D + D x D + 64 = " + std::to_string(n + SIM_LANES) +
-                        ") x 8, and as much per chunk of 64 draws: " + std::to_string(n_chunks) + " chunks), the device has " +
-                        std::to_string(free_bytes) + " free (FOKL_CONTROL_POOLED_FREE_BYTES caps what counts; solve over fewer draws or starts)");
+    if (const int refused = pooled_workspace_fits(
+            ctx, who, workspace, "FOKL_CONTROL_POOLED_FREE_BYTES",
+            std::to_string(n_draws) + " draws x " + std::to_string(n_starts) + " starts x (2 + D + D x D + 64 = " +
+                std::to_string(n + SIM_LANES) + ") x 8, and as much per chunk of 64 draws: " + std::to_string(n_chunks) + " chunks"))
+        return refused;
 
     DeviceBuffers buf;
     CtlDevice dev{};
-    HIP_TRY(ctx, ctl_upload(buf, args, dev));
-    int *d_status = nullptr, *d_iterations = nullptr, *d_descent = nullptr, *d_work = nullptr, *d_first = nullptr, *d_moved = nullptr,
-        *d_running = nullptr;
-    double *d_w = nullptr, *d_z = nullptr, *d_cost = nullptr, *d_cost_start = nullptr, *d_rows = nullptr, *d_sums = nullptr,
-           *d_ft = nullptr, *d_ft_sums = nullptr, *d_trial = nullptr, *d_slope = nullptr, *d_pooled = nullptr, *d_fpool = nullptr,
-           *d_zbest = nullptr, *d_members = nullptr;
-    std::vector<int32_t> h_status(S, -1), h_none(S, 0), h_zero((size_t)max_iter + 1, 0);
-    std::vector<double> h_nan(S, NAN);
-    HIP_TRY(ctx, buf.upload(&d_w, draw_weights, E));
-    HIP_TRY(ctx, buf.upload(&d_z, z0, S * D));
-    HIP_TRY(ctx, buf.upload(&d_status, h_status.data(), S));
-    HIP_TRY(ctx, buf.upload(&d_iterations, h_status.data(), S));
-    HIP_TRY(ctx, buf.upload(&d_descent, h_none.data(), S));
-    HIP_TRY(ctx, buf.upload(&d_cost, h_nan.data(), S));
-    HIP_TRY(ctx, buf.upload(&d_cost_start, h_nan.data(), S));
-    HIP_TRY(ctx, buf.upload(&d_work, h_zero.data(), h_zero.size()));
-    HIP_TRY(ctx, buf.upload(&d_running, h_status.data(), 1));
-    HIP_TRY(ctx, buf.get(&d_rows, B * n));
-    HIP_TRY(ctx, buf.get(&d_sums, S * n_chunks * n));
-    HIP_TRY(ctx, buf.get(&d_ft, B * SIM_LANES));
+    HIP_TRY(ctx, ctl_upload(buf, s, *problem, dev));
+    if (const int failed = k.alloc(ctx, buf, s, draw_weights, problem->z0, (size_t)n, first_pooled != nullptr, first_trial != nullptr))
+        return failed;
+    double *d_ft_sums = nullptr;
     HIP_TRY(ctx, buf.get(&d_ft_sums, S * n_chunks * SIM_LANES));
-    HIP_TRY(ctx, buf.get(&d_trial, S * D * SIM_LANES));
-    HIP_TRY(ctx, buf.get(&d_slope, S * SIM_LANES));
-    HIP_TRY(ctx, buf.get(&d_moved, S * SIM_LANES));
-    HIP_TRY(ctx, buf.get(&d_pooled, S * (2 + D)));
-    if (first_pooled) {                                               // a draw of weight 0 writes no row: its row reads NaN
-        std::vector<double> h_rows(B * n, NAN);
-        HIP_TRY(ctx, hipMemcpy(d_rows, h_rows.data(), h_rows.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, buf.get(&d_fpool, S * n));
-    }
-    if (first_trial) {                                                // what iteration 0 does not write reads NaN, moved 0
-        HIP_TRY(ctx, pooled_fill_nan(d_trial, S * D * SIM_LANES));
-        HIP_TRY(ctx, pooled_fill_nan(d_slope, S * SIM_LANES));
-        HIP_TRY(ctx, pooled_fill_nan(d_pooled, S * (2 + D)));
-        HIP_TRY(ctx, pooled_fill_nan(d_ft, B * SIM_LANES));
-        HIP_TRY(ctx, pooled_fill_nan(d_ft_sums, S * n_chunks * SIM_LANES));
-        HIP_TRY(ctx, hipMemset(d_moved, 0, S * SIM_LANES * sizeof(int)));
-    }
-    HIP_TRY(ctx, buf.get(&d_zbest, E * D));
-    HIP_TRY(ctx, buf.get(&d_members, E * n_states * n_points));
-    HIP_TRY(ctx, buf.get(&d_first, E));
+    if (first_trial) HIP_TRY(ctx, pooled_fill_nan(d_ft_sums, S * n_chunks * SIM_LANES));
 
-    double terms_per_stage = 0.0;
-    for (int k = 0; k < n_states; ++k) terms_per_stage += sys.entry_count[k];
-    const double pass_flops = (double)B * SIM_LANES * (double)n_steps * 4.0 * (8.0 * terms_per_stage + 20.0 * n_factors);
+    const double pass_flops = (double)B * SIM_LANES * (double)s.n_steps * 4.0 * (8.0 * sim_terms_per_stage(sys, n_states) + 20.0 * s.n_factors);
     PooledClock clock(ctx);
+    CtlPoll poll;
     int64_t queued = 0;
     hipError_t launched = hipSuccess;
     for (int it = 0; it <= max_iter; ++it) {
         {
             TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (2.0 * (double)B * (n + SIM_LANES)), 3.0 * pass_flops);
             clock.before(POOLED_TANGENT);
-            POOLED_NS_SWITCH(pooled_tangent, ctx, (int)B, lds_bytes, sys, cp, dev, d_z, d_status, d_w, d_rows)
+            launched = pooled_tangent(ctx, n_states, (int)B, lds_bytes, sys, cp, dev, k.z, k.status, k.w, k.rows);
             clock.after();
             HIP_TRY(ctx, launched);
             clock.before(POOLED_CHUNK);
-            launched = pooled_chunks(ctx, d_rows, d_w, d_status, d_sums, n_draws, n_starts, n, n_chunks);
+            launched = pooled_chunks(ctx, k.rows, k.w, k.status, k.sums, n_draws, n_starts, n, n_chunks);
             clock.after();
             HIP_TRY(ctx, launched);
             clock.before(POOLED_STEP);
-            hipLaunchKernelGGL(control_pooled_step_kernel, dim3((unsigned)S), dim3(SIM_LANES), step_lds, ctx->stream, cp, d_sums,
-                               n_chunks, d_z, d_status, d_iterations, d_cost, d_cost_start, d_work, d_trial, d_slope, d_moved,
-                               d_pooled, d_fpool, it);
+            hipLaunchKernelGGL(control_pooled_step_kernel, dim3((unsigned)S), dim3(SIM_LANES), step_lds, ctx->stream, cp, k.sums,
+                               n_chunks, k.z, k.status, k.iterations, k.cost, k.cost_start, k.work, k.trial, k.slope, k.moved,
+                               k.pooled, k.fpool, it);
             launched = hipGetLastError();
             clock.after();
             HIP_TRY(ctx, launched);
             clock.before(POOLED_TRIAL);
-            POOLED_NS_SWITCH(pooled_trial, ctx, (int)B, lds_bytes, sys, cp, dev, d_trial, d_status, d_w, d_ft)
+            launched = pooled_trial(ctx, n_states, (int)B, lds_bytes, sys, cp, dev, k.trial, k.status, k.w, k.ft);
             clock.after();
             HIP_TRY(ctx, launched);
             clock.before(POOLED_CHUNK);
-            launched = pooled_chunks(ctx, d_ft, d_w, d_status, d_ft_sums, n_draws, n_starts, SIM_LANES, n_chunks);
+            launched = pooled_chunks(ctx, k.ft, k.w, k.status, d_ft_sums, n_draws, n_starts, SIM_LANES, n_chunks);
             clock.after();
             HIP_TRY(ctx, launched);
             clock.before(POOLED_ACCEPT);
             hipLaunchKernelGGL(control_pooled_accept_kernel, dim3((unsigned)S), dim3(SIM_LANES), 0, ctx->stream, D, d_ft_sums,
-                               n_chunks, d_trial, d_slope, d_moved, d_pooled, d_z, d_status, d_iterations, d_descent, it);
+                               n_chunks, k.trial, k.slope, k.moved, k.pooled, k.z, k.status, k.iterations, k.descent, it);
             launched = hipGetLastError();
             clock.after();
             HIP_TRY(ctx, launched);
             ++queued;
         }
-        if (it == 0 && first_trial) {                                 // iteration 0's trial half, before a later one overwrites it
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(first_trial->trial, d_trial, S * D * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->slope, d_slope, S * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->moved, d_moved, S * SIM_LANES * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->pooled, d_pooled, S * (2 + D) * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->ft, d_ft, B * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
+        if (it == 0 && first_trial) {
+            if (const int failed = k.first_trial_out(ctx, *first_trial)) return failed;
             HIP_TRY(ctx, hipMemcpy(first_trial->ft_sums, d_ft_sums, S * n_chunks * SIM_LANES * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->z, d_z, S * D * sizeof(double), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->status, d_status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(first_trial->descent, d_descent, S * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
-        if (poll > 0 && (it + 1) % poll == 0 && it < max_iter) {      // may stop queuing early: an iteration without work changes nothing
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy(h_status.data(), d_status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-            bool running = false;
-            for (size_t s = 0; s < S && !running; ++s) running = h_status[s] < 0;
-            if (!running) break;
-        }
+        bool stopped = false;
+        if (const int failed = poll(ctx, it, max_iter, k.status, S, stopped)) return failed;
+        if (stopped) break;
     }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(z, d_z, S * D * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(cost, d_cost, S * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(cost_start, d_cost_start, S * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(status, d_status, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(iterations, d_iterations, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(descent_steps, d_descent, S * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(h_zero.data(), d_work, h_zero.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (first_pooled) {
-        HIP_TRY(ctx, hipMemcpy(first_pooled, d_fpool, S * n * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(first_rows, d_rows, B * n * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    for (size_t s = 0; s < S; ++s)
-        if (status[s] < 0) return fail(ctx, FOKL_ERR_HIP, who + "a solve was left running");
     int64_t worked = 0;
-    for (int32_t found : h_zero) worked += found;
-
-    // ---- the best start (a non-finite solve is never the best); every draw's trajectory and own cost under its controls ----
-    int best = 0;
-    double best_key = INFINITY;
-    for (int s = 0; s < n_starts; ++s) {
-        const double key = (std::isfinite(cost[s]) && status[s] != CTL_NON_FINITE) ? cost[s] : INFINITY;
-        if (key < best_key) {
-            best_key = key;
-            best = s;
-        }
-    }
-    *best_start = best;
-    std::vector<double> z_best(E * D), point((size_t)D * SIM_LANES);
-    for (size_t e = 0; e < E; ++e) std::memcpy(z_best.data() + e * D, z + (size_t)best * D, D * sizeof(double));
-    for (int d = 0; d < D; ++d)
-        for (int lane = 0; lane < SIM_LANES; ++lane) point[(size_t)d * SIM_LANES + lane] = z[(size_t)best * D + d];
-    HIP_TRY(ctx, hipMemcpy(d_zbest, z_best.data(), E * D * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_trial, point.data(), point.size() * sizeof(double), hipMemcpyHostToDevice));
-    {
-        TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)E * n_states * n_points, 2.0 * pass_flops / (double)S);
-#define CTL_CASE(NS)                                                                                                         \
-    case NS:                                                                                                                 \
-        launched = ctl_trajectory<NS>(ctx, n_draws, lds_bytes, sys, cp, dev.tab, dev.ct, dev.coef, dev.forcing, dev.y0, d_zbest,  \
-                                      d_members, d_first);                                                                   \
-        break;
-        switch (n_states) {
-            CTL_CASE(1) CTL_CASE(2) CTL_CASE(3) CTL_CASE(4) CTL_CASE(5) CTL_CASE(6) CTL_CASE(7) CTL_CASE(8)
-        }
-#undef CTL_CASE
-        HIP_TRY(ctx, launched);
-        // one start (d_running holds -1), no weights: every draw's value pass at the returned point, lane 0 is read
-        POOLED_NS_SWITCH(pooled_trial, ctx, n_draws, lds_bytes, sys, cp, dev, d_trial, d_running, nullptr, d_ft)
-        HIP_TRY(ctx, launched);
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(members, d_members, E * n_states * n_points * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(first_saturation, d_first, E * sizeof(int32_t), hipMemcpyDeviceToHost));
-    std::vector<double> h_ft(E * SIM_LANES);
-    HIP_TRY(ctx, hipMemcpy(h_ft.data(), d_ft, h_ft.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < E; ++e) cost_draws[e] = h_ft[e * SIM_LANES];
+    if (const int failed = k.finish(ctx, who, s, sys, cp, lds_bytes, dev, pass_flops, out, worked)) return failed;
     int64_t *rep = ctx->control_pooled_report;
-    rep[0] = n_states;
-    rep[1] = n_draws;
-    rep[2] = n_starts;
-    rep[3] = D;
-    rep[4] = n_chunks;
-    rep[5] = (int64_t)lds_bytes;
-    rep[6] = (int64_t)step_lds;
+    k.report_head(rep, n_states, lds_bytes, step_lds);
     rep[7] = queued;
     rep[8] = worked;
     rep[9] = 6;
     clock.read(rep + 10);
     return FOKL_OK;
 }
-
-#undef POOLED_NS_SWITCH

@@ -46,22 +46,14 @@ extern "C" int fokl_gp_integrate_ensemble(fokl_ctx *, int, int, int, int64_t, co
 }
 
 // Neither does dynamics.simulate (fokl_simulate_device.inc); its statement is dynamics.simulate_host.
-extern "C" int fokl_simulate_ensemble(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
-                                      const double *, const double *, int, int, const int32_t *, const int32_t *, const int32_t *,
-                                      const int32_t *, int, const double *, int, const double *, int, const int32_t *,
-                                      const int32_t *, const int32_t *, const int32_t *, int, const double *, const double *,
-                                      const double *, int, double *, double *, double *, int32_t *)
+extern "C" int fokl_simulate_ensemble(fokl_ctx *, const fokl_system *, int, double *, double *, double *, int32_t *)
 {
     return FOKL_ERR_HIP;
 }
 extern "C" int fokl_simulate_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
 // Nor its error-controlled sibling (fokl_simulate_adaptive_device.inc); its statement is dynamics.simulate_adaptive_host.
-extern "C" int fokl_simulate_adaptive(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
-                                      const double *, const double *, int, int, const int32_t *, const int32_t *, const int32_t *,
-                                      const int32_t *, int, const double *, int, const double *, int, const int32_t *,
-                                      const int32_t *, const int32_t *, const int32_t *, int, const double *, const double *,
-                                      const double *, int, double, const double *, int, int, double *, double *, double *,
+extern "C" int fokl_simulate_adaptive(fokl_ctx *, const fokl_system *, int, double, const double *, int, int, double *, double *, double *,
                                       int32_t *, int64_t *, int64_t *, int32_t *, double *, int32_t *, int8_t *)
 {
     return FOKL_ERR_HIP;
@@ -69,11 +61,7 @@ extern "C" int fokl_simulate_adaptive(fokl_ctx *, int, int, int64_t, double, int
 extern "C" int fokl_simulate_adaptive_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
 // Nor the stiff sibling (fokl_simulate_stiff_device.inc); its statement is dynamics.simulate_stiff_host.
-extern "C" int fokl_simulate_stiff(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
-                                   const double *, const double *, int, int, const int32_t *, const int32_t *, const int32_t *,
-                                   const int32_t *, int, const double *, int, const double *, int, const int32_t *,
-                                   const int32_t *, const int32_t *, const int32_t *, int, const double *, const double *,
-                                   const double *, int, double, const double *, int, int, double *, double *, double *,
+extern "C" int fokl_simulate_stiff(fokl_ctx *, const fokl_system *, int, double, const double *, int, int, double *, double *, double *,
                                    int32_t *, int64_t *, int64_t *, int64_t *, int32_t *, double *, int32_t *, int8_t *)
 {
     return FOKL_ERR_HIP;
@@ -82,12 +70,8 @@ extern "C" int fokl_simulate_stiff_report(const fokl_ctx *, int64_t *) { return 
 
 // Nor does the particle filter over such a system (fokl_assimilate_device.inc); its statement is dynamics.assimilate_host,
 // and its random numbers (fokl_assimilate_rng) are host code and present here.
-extern "C" int fokl_assimilate_ensemble(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
-                                        const double *, const double *, int, int, const int32_t *, const int32_t *,
-                                        const int32_t *, const int32_t *, int, const double *, int, const double *, int,
-                                        const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, const double *,
-                                        const double *, const double *, const uint32_t *, int, const int32_t *, const double *,
-                                        int, const int32_t *, const double *, const double *, const double *, const double *,
+extern "C" int fokl_assimilate_ensemble(fokl_ctx *, const fokl_system *, const uint32_t *, int, const int32_t *, const double *, int,
+                                        const int32_t *, const double *, const double *, const double *, const double *,
                                         double, uint32_t, double *, double *, double *, int32_t *, int32_t *)
 {
     return FOKL_ERR_HIP;
@@ -95,46 +79,26 @@ extern "C" int fokl_assimilate_ensemble(fokl_ctx *, int, int, int64_t, double, i
 extern "C" int fokl_assimilate_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
 // Nor does the optimal control of such a system (fokl_control_device.inc); its statement is dynamics.control_host.
-extern "C" int fokl_control_solve(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
-                                  const double *, const double *, int, int, const int32_t *, const int32_t *, const int32_t *,
-                                  const int32_t *, int, const double *, int, const double *, int, const int32_t *,
-                                  const int32_t *, const int32_t *, const int32_t *, int, const double *, const double *,
-                                  const double *, int, int, const int32_t *, const int32_t *, const double *, const double *,
-                                  const double *, const double *, const double *, const double *, const double *, double,
-                                  const double *, const double *, int, int, const double *, int, double, double *, double *,
-                                  double *, int32_t *, int32_t *, int32_t *, int32_t *, double *, int32_t *, double *, double *, double *)
+extern "C" int fokl_control_solve(fokl_ctx *, const fokl_system *, const fokl_control_problem *, double *, double *, double *,
+                                  int32_t *, int32_t *, int32_t *, int32_t *, double *, int32_t *, double *, double *, double *)
 {
     return FOKL_ERR_HIP;
 }
 extern "C" int fokl_control_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
 // Nor does the pooled solve over all draws (fokl_control_pooled_device.inc); its statement is dynamics.control_pooled_host.
-extern "C" int fokl_control_pooled_solve(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
-                                         const double *, const double *, int, int, const int32_t *, const int32_t *,
-                                         const int32_t *, const int32_t *, int, const double *, int, const double *, int,
-                                         const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, const double *,
-                                         const double *, const double *, int, int, const int32_t *, const int32_t *,
-                                         const double *, const double *, const double *, const double *, const double *,
-                                         const double *, const double *, double, const double *, const double *, int, int,
-                                         const double *, int, double, const double *, double *, double *, double *, int32_t *,
-                                         int32_t *, int32_t *, int32_t *, double *, int32_t *, double *, double *, double *,
-                                         const fokl_control_first_trial *)
+extern "C" int fokl_control_pooled_solve(fokl_ctx *, const fokl_system *, const fokl_control_problem *, const double *, double *,
+                                         double *, double *, int32_t *, int32_t *, int32_t *, int32_t *, double *, int32_t *,
+                                         double *, double *, double *, const fokl_control_first_trial *)
 {
     return FOKL_ERR_HIP;
 }
 extern "C" int fokl_control_pooled_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
 // Nor does the CVaR solve over all draws (fokl_control_cvar_device.inc); its statement is dynamics.control_cvar_host.
-extern "C" int fokl_control_cvar_solve(fokl_ctx *, int, int, int64_t, double, int, const double *, int, int, const int32_t *,
-                                       const double *, const double *, int, int, const int32_t *, const int32_t *,
-                                       const int32_t *, const int32_t *, int, const double *, int, const double *, int,
-                                       const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, const double *,
-                                       const double *, const double *, int, int, const int32_t *, const int32_t *,
-                                       const double *, const double *, const double *, const double *, const double *,
-                                       const double *, const double *, double, const double *, const double *, int, int,
-                                       const double *, int, double, const double *, double, double, double, double *, double *,
-                                       double *, int32_t *, int32_t *, int32_t *, int32_t *, double *, int32_t *, double *,
-                                       double *, double *, double *, double *, double *, double *,
+extern "C" int fokl_control_cvar_solve(fokl_ctx *, const fokl_system *, const fokl_control_problem *, const double *, double, double,
+                                       double, double *, double *, double *, int32_t *, int32_t *, int32_t *, int32_t *, double *,
+                                       int32_t *, double *, double *, double *, double *, double *, double *, double *,
                                        const fokl_control_first_trial *)
 {
     return FOKL_ERR_HIP;

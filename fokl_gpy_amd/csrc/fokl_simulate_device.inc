@@ -208,88 +208,241 @@ __global__ __launch_bounds__(SIM_LANES) void simulate_ensemble_kernel(
 
 namespace {
 
-template <int NS>
-hipError_t sim_launch(fokl_ctx *ctx, int grid, size_t lds_bytes, const SimSystem &sys, const SimTables &tab,
-                      const double *coef, const double *forcing, double *state, int *saturation, double *points, int64_t ld,
-                      int64_t t0, int steps, int chunk_points, int write_first)
+// The kernel instance of a system: f(std::integral_constant<int, NS>) with NS = n_states, 1 .. SIM_MAX_STATES
+template <class F>
+hipError_t sim_dispatch(int n_states, F &&f)
 {
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(simulate_ensemble_kernel<NS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SIM_LDS_BUDGET);
-        if (e != hipSuccess) return e;
+    switch (n_states) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 8: return f(std::integral_constant<int, 8>{});
     }
-    hipLaunchKernelGGL(simulate_ensemble_kernel<NS>, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, tab.norm_src,
-                       tab.norm_lo, tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline, tab.bern,
-                       coef, forcing, state, saturation, points, ld, t0, steps, chunk_points, write_first);
-    return hipGetLastError();
+    return hipErrorInvalidValue;
+}
+
+// A kernel that wants more than 64 KB of dynamic LDS has to be told so
+template <class Kernel>
+hipError_t sim_lds_attribute(Kernel kernel, size_t lds_bytes, size_t limit = SIM_LDS_BUDGET)
+{
+    if (lds_bytes <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit);
+}
+
+// What the simulate calls and the filter refuse of n_steps (sim_check's steps_test; control has its own)
+int sim_steps_fit(fokl_ctx *ctx, const std::string &who, const fokl_system &s)
+{
+    if (s.n_steps + 1 > (int64_t)1 << 30) return fail(ctx, FOKL_ERR_ARG, who + "too many steps");
+    return FOKL_OK;
+}
+
+// What every entry point refuses first, in this order: a null pointer or a size that cannot be (own_ok: the caller's own
+// pointers, the same refusal), too many states, the caller's test of n_steps, h.  0, or the refusal's code.
+int sim_check(fokl_ctx *ctx, const std::string &who, const fokl_system *system, bool own_ok,
+              int (*steps_test)(fokl_ctx *, const std::string &, const fokl_system &))
+{
+    if (!system || !own_ok) return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
+    const fokl_system &s = *system;
+    if (s.n_members <= 0 || s.n_states <= 0 || s.n_steps < 0 || s.n_forcing_cols < 0 || s.n_norm_forcing < 0 ||
+        s.n_norm < s.n_norm_forcing || s.n_forcing_factors < 0 || s.n_factors < s.n_forcing_factors || s.n_spline_rows < 0 ||
+        s.n_bern_rows < 0 || s.n_entries < 0 || s.n_coef < s.n_states || !s.entry_begin || !s.entry_count || !s.constant ||
+        !s.coef || !s.y0 || !s.box || (s.n_norm > 0 && (!s.norm_src || !s.norm_lo || !s.norm_span)) ||
+        (s.n_factors > 0 && (!s.fac_norm || !s.fac_kind || !s.fac_row || !s.fac_degree)) || (s.n_entries > 0 && !s.entries) ||
+        (s.n_spline_rows > 0 && !s.spline_table) || (s.n_bern_rows > 0 && !s.bern_table) ||
+        (s.n_forcing_cols > 0 && s.n_steps > 0 && !s.forcing))
+        return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
+    if (s.n_states > SIM_MAX_STATES)
+        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(s.n_states) + " states, the kernel is built for at most " +
+                                           std::to_string(SIM_MAX_STATES));
+    if (const int refused = steps_test(ctx, who, s)) return refused;
+    if (!(s.h > 0) || !std::isfinite(s.h)) return fail(ctx, FOKL_ERR_ARG, who + "h must be positive and finite");
+    return FOKL_OK;
 }
 
 // Every index simulate_ensemble_kernel / assimilate_kernel follow, checked on the host (they read nothing outside their
 // tables), and the system as the kernels take it.  0, or the refusal's code with its text in the context.
-static int sim_plan(fokl_ctx *ctx, const std::string &who, int n_states, double h, int n_forcing_cols, int n_norm_forcing,
-                    int n_norm, const int32_t *norm_src, const double *norm_lo, const double *norm_span, int n_forcing_factors,
-                    int n_factors, const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
-                    const int32_t *fac_degree, int n_spline_rows, int n_bern_rows, int n_entries, const int32_t *entries,
-                    const int32_t *entry_begin, const int32_t *entry_count, const int32_t *constant, int n_coef,
-                    const double *box, SimSystem &sys, int &n_bern_factors)
+int sim_plan(fokl_ctx *ctx, const std::string &who, const fokl_system &s, SimSystem &sys, int &n_bern_factors)
 {
     // ---- every index the kernel follows, checked here: it reads nothing outside its tables ----
-    for (int n = 0; n < n_norm; ++n) {
-        const int src = norm_src[n];
-        const bool ok = n < n_norm_forcing ? (src < 0 && -(int64_t)src - 1 < n_forcing_cols) : (src >= 0 && src < n_states);
+    for (int n = 0; n < s.n_norm; ++n) {
+        const int src = s.norm_src[n];
+        const bool ok = n < s.n_norm_forcing ? (src < 0 && -(int64_t)src - 1 < s.n_forcing_cols) : (src >= 0 && src < s.n_states);
         if (!ok) return fail(ctx, FOKL_ERR_ARG, who + "a normalised input reads outside the states / the forcing columns");
-        if (n > n_norm_forcing && src < norm_src[n - 1])
+        if (n > s.n_norm_forcing && src < s.norm_src[n - 1])
             return fail(ctx, FOKL_ERR_ARG, who + "the normalised inputs of the states must be ordered by state");
-        if (!(norm_span[n] > 0) || !std::isfinite(norm_span[n]) || !std::isfinite(norm_lo[n]))
+        if (!(s.norm_span[n] > 0) || !std::isfinite(s.norm_span[n]) || !std::isfinite(s.norm_lo[n]))
             return fail(ctx, FOKL_ERR_ARG, who + "a normalisation needs a finite lower end and a positive finite span");
     }
     int n_forcing_splines = 0, n_state_splines = 0;
     n_bern_factors = 0;
-    for (int f = 0; f < n_factors; ++f) {
-        const bool is_forcing = f < n_forcing_factors, spline = fac_kind[f] == 0;
-        if (fac_kind[f] != 0 && fac_kind[f] != 1) return fail(ctx, FOKL_ERR_ARG, who + "a factor's kernel is neither 0 (splines) nor 1 (Bernoulli)");
-        if (spline && f > 0 && fac_kind[f - 1] == 1 && f != n_forcing_factors)
+    for (int f = 0; f < s.n_factors; ++f) {
+        const bool is_forcing = f < s.n_forcing_factors, spline = s.fac_kind[f] == 0;
+        if (s.fac_kind[f] != 0 && s.fac_kind[f] != 1)
+            return fail(ctx, FOKL_ERR_ARG, who + "a factor's kernel is neither 0 (splines) nor 1 (Bernoulli)");
+        if (spline && f > 0 && s.fac_kind[f - 1] == 1 && f != s.n_forcing_factors)
             return fail(ctx, FOKL_ERR_ARG, who + "the factors must be ordered splines before Bernoulli, forcing before states");
-        const int n = fac_norm[f];
-        if (is_forcing ? (n < 0 || n >= n_norm_forcing) : (n < n_norm_forcing || n >= n_norm))
+        const int n = s.fac_norm[f];
+        if (is_forcing ? (n < 0 || n >= s.n_norm_forcing) : (n < s.n_norm_forcing || n >= s.n_norm))
             return fail(ctx, FOKL_ERR_ARG, who + "a factor reads outside the normalised inputs of its kind");
-        if (fac_row[f] < 0 || fac_row[f] >= (spline ? n_spline_rows : n_bern_rows))
+        if (s.fac_row[f] < 0 || s.fac_row[f] >= (spline ? s.n_spline_rows : s.n_bern_rows))
             return fail(ctx, FOKL_ERR_ARG, who + "a factor's order lies outside its coefficient table");
-        if (!spline && (fac_degree[f] < 0 || fac_degree[f] >= SIM_BERN_WIDTH))
+        if (!spline && (s.fac_degree[f] < 0 || s.fac_degree[f] >= SIM_BERN_WIDTH))
             return fail(ctx, FOKL_ERR_ARG, who + "Bernoulli orders above " + std::to_string(SIM_BERN_WIDTH - 1) + " are not handled");
         n_forcing_splines += is_forcing && spline;
         n_state_splines += !is_forcing && spline;
         n_bern_factors += !spline;
     }
-    for (int t = 0; t < n_entries; ++t) {
-        const int32_t *d = entries + 4 * (size_t)t;
-        if (d[0] < 0 || d[0] > n_factors || d[1] < 0 || d[1] > n_factors || d[2] < 0 || d[2] > n_factors || d[3] < -1 || d[3] >= n_coef)
+    for (int t = 0; t < s.n_entries; ++t) {
+        const int32_t *d = s.entries + 4 * (size_t)t;
+        if (d[0] < 0 || d[0] > s.n_factors || d[1] < 0 || d[1] > s.n_factors || d[2] < 0 || d[2] > s.n_factors || d[3] < -1 ||
+            d[3] >= s.n_coef)
             return fail(ctx, FOKL_ERR_ARG, who + "a term entry points outside the factors / the coefficients");
     }
-    for (int k = 0; k < n_states; ++k) {
-        if (entry_begin[k] < 0 || entry_count[k] < 0 || (int64_t)entry_begin[k] + entry_count[k] > n_entries || constant[k] < 0 ||
-            constant[k] >= n_coef)
+    sys = SimSystem{};
+    for (int k = 0; k < s.n_states; ++k) {
+        if (s.entry_begin[k] < 0 || s.entry_count[k] < 0 || (int64_t)s.entry_begin[k] + s.entry_count[k] > s.n_entries ||
+            s.constant[k] < 0 || s.constant[k] >= s.n_coef)
             return fail(ctx, FOKL_ERR_ARG, who + "a model's term list or constant lies outside the tables");
-        if (!(box[2 * k] < box[2 * k + 1])) return fail(ctx, FOKL_ERR_ARG, who + "a state's box is empty");
-        sys.entry_begin[k] = entry_begin[k];
-        sys.entry_count[k] = entry_count[k];
-        sys.constant[k] = constant[k];
-        sys.box_lo[k] = box[2 * k];
-        sys.box_hi[k] = box[2 * k + 1];
+        if (!(s.box[2 * k] < s.box[2 * k + 1])) return fail(ctx, FOKL_ERR_ARG, who + "a state's box is empty");
+        sys.entry_begin[k] = s.entry_begin[k];
+        sys.entry_count[k] = s.entry_count[k];
+        sys.constant[k] = s.constant[k];
+        sys.box_lo[k] = s.box[2 * k];
+        sys.box_hi[k] = s.box[2 * k + 1];
     }
-    sys.n_norm_forcing = n_norm_forcing;
-    sys.n_norm = n_norm;
-    for (int j = 0, n = n_norm_forcing; j <= SIM_MAX_STATES; ++j) {
-        while (n < n_norm && norm_src[n] < j) ++n;
+    sys.n_norm_forcing = s.n_norm_forcing;
+    sys.n_norm = s.n_norm;
+    for (int j = 0, n = s.n_norm_forcing; j <= SIM_MAX_STATES; ++j) {
+        while (n < s.n_norm && s.norm_src[n] < j) ++n;
         sys.norm_begin[j] = n;
     }
     sys.n_forcing_splines = n_forcing_splines;
-    sys.n_forcing_factors = n_forcing_factors;
-    sys.n_state_splines_end = n_forcing_factors + n_state_splines;
-    sys.n_factors = n_factors;
-    sys.n_coef = n_coef;
-    sys.n_forcing_cols = n_forcing_cols;
-    sys.h = h;
+    sys.n_forcing_factors = s.n_forcing_factors;
+    sys.n_state_splines_end = s.n_forcing_factors + n_state_splines;
+    sys.n_factors = s.n_factors;
+    sys.n_coef = s.n_coef;
+    sys.n_forcing_cols = s.n_forcing_cols;
+    sys.h = s.h;
+    return FOKL_OK;
+}
+
+// The term entries of every state over one stage, for the kernel timers' work estimates
+double sim_terms_per_stage(const SimSystem &sys, int n_states)
+{
+    double terms = 0.0;
+    for (int k = 0; k < n_states; ++k) terms += sys.entry_count[k];
+    return terms;
+}
+
+// The system's nine tables and its forcing on the device
+hipError_t sim_upload(DeviceBuffers &buf, const fokl_system &s, SimTables &tab, double *&forcing)
+{
+    int *norm_src = nullptr, *fac_norm = nullptr, *fac_row = nullptr, *fac_degree = nullptr;
+    int4 *entries = nullptr;
+    double *norm_lo = nullptr, *norm_span = nullptr, *spline = nullptr, *bern = nullptr;
+    hipError_t e;
+    if ((e = buf.upload(&norm_src, s.norm_src, (size_t)s.n_norm)) || (e = buf.upload(&norm_lo, s.norm_lo, (size_t)s.n_norm)) ||
+        (e = buf.upload(&norm_span, s.norm_span, (size_t)s.n_norm)) || (e = buf.upload(&fac_norm, s.fac_norm, (size_t)s.n_factors)) ||
+        (e = buf.upload(&fac_row, s.fac_row, (size_t)s.n_factors)) || (e = buf.upload(&fac_degree, s.fac_degree, (size_t)s.n_factors)) ||
+        (e = buf.upload(&entries, s.entries, (size_t)s.n_entries)) ||
+        (e = buf.upload(&spline, s.spline_table, (size_t)s.n_spline_rows * SIM_PIECES * 4)) ||
+        (e = buf.upload(&bern, s.bern_table, (size_t)s.n_bern_rows * SIM_BERN_WIDTH)) ||
+        (e = buf.upload(&forcing, s.forcing, (size_t)s.n_steps * s.n_forcing_cols)))
+        return e;
+    tab = SimTables{norm_src, norm_lo, norm_span, fac_norm, fac_row, fac_degree, entries, spline, bern};
+    return hipSuccess;
+}
+
+// host [rows][members] -> device [rows][ld], ld = the members rounded up to whole wavefronts; the padding members hold zeros
+hipError_t sim_upload_padded(DeviceBuffers &buf, double **out, const double *host, size_t rows, size_t members, size_t ld)
+{
+    std::vector<double> padded(rows * ld, 0.0);
+    for (size_t r = 0; r < rows; ++r) std::memcpy(padded.data() + r * ld, host + r * members, members * sizeof(double));
+    return buf.upload(out, padded.data(), padded.size());
+}
+
+// The outputs the three simulate calls share, and what they refuse of them after sim_check
+struct SimOutputs {
+    int cut;
+    double *mean, *bounds, *members;
+};
+
+int sim_outputs_check(fokl_ctx *ctx, const std::string &who, const fokl_system &s, const SimOutputs &out)
+{
+    if (out.bounds && (out.cut < 1 || out.cut >= s.n_members)) return fail(ctx, FOKL_ERR_ARG, who + "bounds need 1 <= cut < n_members");
+    if (out.bounds && s.n_members > GI_BAND_MAX_MEMBERS)
+        return fail(ctx, FOKL_ERR_ARG, who + "bounds are formed over at most " + std::to_string(GI_BAND_MAX_MEMBERS) +
+                                           " members (mean and members have no limit)");
+    return FOKL_OK;
+}
+
+// The time axis of a simulate call: launches of at most `bound` steps (and of what stays resident: the points of one launch),
+// each followed by the band and, where the members are wanted, the transpose with its strided copy; then mean and bounds.
+// launch(points, t0, steps, chunk_points, write_first) queues the caller's integration kernel for one chunk;
+// flops_per_step: its work per member and step for the kernel timer (0: not known beforehand).
+template <class Launch>
+int sim_run(fokl_ctx *ctx, const fokl_system &s, size_t ld, int64_t bound, const SimOutputs &out, double flops_per_step,
+            DeviceBuffers &buf, Launch launch, int64_t &per_launch, int64_t &launches)
+{
+    const int n_states = s.n_states, n_members = s.n_members;
+    const int64_t n_steps = s.n_steps, n_points = n_steps + 1;
+    const size_t E = (size_t)n_members;
+    const int64_t resident = ((int64_t)256 << 20) / (int64_t)((size_t)n_states * ld * sizeof(double));
+    per_launch = std::max<int64_t>(1, std::min(bound, resident - 1));
+    const int chunk_cap = (int)std::min<int64_t>(per_launch + 1, n_points);
+
+    double *d_points = nullptr, *d_mean = nullptr, *d_bounds = nullptr, *d_members = nullptr;
+    HIP_TRY(ctx, buf.get(&d_points, (size_t)n_states * chunk_cap * ld));
+    HIP_TRY(ctx, buf.get(&d_mean, (size_t)n_states * n_points));
+    if (out.bounds) HIP_TRY(ctx, buf.get(&d_bounds, (size_t)n_states * n_points * 2));
+    if (out.members) HIP_TRY(ctx, buf.get(&d_members, E * n_states * chunk_cap));
+
+    int npow2 = 2;
+    while (npow2 < n_members) npow2 <<= 1;
+    const size_t band_lds = out.bounds ? (size_t)npow2 * sizeof(double) : 0;
+    HIP_TRY(ctx, sim_lds_attribute(ensemble_band_kernel, band_lds, GI_BAND_MAX_MEMBERS * sizeof(double)));
+
+    launches = 0;
+    for (int64_t t0 = 0, p_first = 0; p_first < n_points;) {
+        const int write_first = t0 == 0;
+        const int steps = (int)std::min<int64_t>(per_launch, n_steps - t0);
+        const int chunk_points = steps + write_first;
+        {
+            TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)ld * n_states * (chunk_points + 2.0),
+                              (double)ld * steps * flops_per_step);
+            HIP_TRY(ctx, launch(d_points, t0, steps, chunk_points, write_first));
+            ++launches;
+        }
+        {
+            const int rows = n_states * chunk_points;
+            const int band_grid = std::min(rows, cu_count(ctx) * (band_lds > 32 * 1024 ? 1 : 4));
+            TimedRegion timed(ctx, FOKL_K_BAND, 8.0 * (double)rows * (E + 3.0), (double)rows * E);
+            hipLaunchKernelGGL(ensemble_band_kernel, dim3(band_grid), dim3(GI_BAND_THREADS), band_lds, ctx->stream,
+                               d_points, (int64_t)ld, n_members, n_states, chunk_points, n_points, p_first, npow2, out.cut,
+                               d_mean, d_bounds);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        if (out.members) {
+            hipLaunchKernelGGL(ensemble_transpose_kernel, dim3((n_members + 31) / 32, (chunk_points + 31) / 32, n_states),
+                               dim3(256), 0, ctx->stream, d_points, (int64_t)ld, n_members, n_states, chunk_points,
+                               d_members);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            HIP_TRY(ctx, hipMemcpy2D(out.members + p_first, (size_t)n_points * sizeof(double), d_members,
+                                     (size_t)chunk_points * sizeof(double), (size_t)chunk_points * sizeof(double),
+                                     E * n_states, hipMemcpyDeviceToHost));
+        }
+        t0 += steps;
+        p_first += chunk_points;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(out.mean, d_mean, (size_t)n_states * n_points * sizeof(double), hipMemcpyDeviceToHost));
+    if (out.bounds)
+        HIP_TRY(ctx, hipMemcpy(out.bounds, d_bounds, (size_t)n_states * n_points * 2 * sizeof(double), hipMemcpyDeviceToHost));
     return FOKL_OK;
 }
 
@@ -302,156 +455,67 @@ extern "C" int fokl_simulate_report(const fokl_ctx *ctx, int64_t *out)
     return FOKL_OK;
 }
 
-extern "C" int fokl_simulate_ensemble(fokl_ctx *ctx, int n_members, int n_states, int64_t n_steps, double h,
-                                      int n_forcing_cols, const double *forcing, int n_norm_forcing, int n_norm,
-                                      const int32_t *norm_src, const double *norm_lo, const double *norm_span,
-                                      int n_forcing_factors, int n_factors, const int32_t *fac_norm,
-                                      const int32_t *fac_kind, const int32_t *fac_row, const int32_t *fac_degree,
-                                      int n_spline_rows, const double *spline_table, int n_bern_rows,
-                                      const double *bern_table, int n_entries, const int32_t *entries,
-                                      const int32_t *entry_begin, const int32_t *entry_count, const int32_t *constant,
-                                      int n_coef, const double *coef, const double *y0, const double *box, int cut,
-                                      double *mean, double *bounds, double *members, int32_t *first_saturation)
+extern "C" int fokl_simulate_ensemble(fokl_ctx *ctx, const fokl_system *system, int cut, double *mean, double *bounds,
+                                      double *members, int32_t *first_saturation)
 {
     const std::string who = "fokl_simulate_ensemble: ";
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + "null context");
     std::memset(ctx->simulate_report, 0, sizeof ctx->simulate_report);
-    if (n_members <= 0 || n_states <= 0 || n_steps < 0 || n_forcing_cols < 0 || n_norm_forcing < 0 || n_norm < n_norm_forcing ||
-        n_forcing_factors < 0 || n_factors < n_forcing_factors || n_spline_rows < 0 || n_bern_rows < 0 || n_entries < 0 ||
-        n_coef < n_states || !entry_begin || !entry_count || !constant || !coef || !y0 || !box || !mean || !first_saturation ||
-        (n_norm > 0 && (!norm_src || !norm_lo || !norm_span)) || (n_factors > 0 && (!fac_norm || !fac_kind || !fac_row || !fac_degree)) ||
-        (n_entries > 0 && !entries) || (n_spline_rows > 0 && !spline_table) || (n_bern_rows > 0 && !bern_table) ||
-        (n_forcing_cols > 0 && n_steps > 0 && !forcing))
-        return fail(ctx, FOKL_ERR_ARG, who + "null pointer, negative size or empty system");
-    if (n_states > SIM_MAX_STATES)
-        return fail(ctx, FOKL_ERR_ARG, who + std::to_string(n_states) + " states, the kernel is built for at most " +
-                                           std::to_string(SIM_MAX_STATES));
-    if (n_steps + 1 > (int64_t)1 << 30) return fail(ctx, FOKL_ERR_ARG, who + "too many steps");
-    if (!(h > 0) || !std::isfinite(h)) return fail(ctx, FOKL_ERR_ARG, who + "h must be positive and finite");
-    if (bounds && (cut < 1 || cut >= n_members)) return fail(ctx, FOKL_ERR_ARG, who + "bounds need 1 <= cut < n_members");
-    if (bounds && n_members > GI_BAND_MAX_MEMBERS)
-        return fail(ctx, FOKL_ERR_ARG, who + "bounds are formed over at most " + std::to_string(GI_BAND_MAX_MEMBERS) +
-                                           " members (mean and members have no limit)");
+    if (const int refused = sim_check(ctx, who, system, mean && first_saturation, sim_steps_fit)) return refused;
+    const fokl_system &s = *system;
+    const SimOutputs out{cut, mean, bounds, members};
+    if (const int refused = sim_outputs_check(ctx, who, s, out)) return refused;
 
     SimSystem sys{};
     int n_bern_factors = 0;
-    if (const int refused = sim_plan(ctx, who, n_states, h, n_forcing_cols, n_norm_forcing, n_norm, norm_src, norm_lo, norm_span,
-                                     n_forcing_factors, n_factors, fac_norm, fac_kind, fac_row, fac_degree, n_spline_rows,
-                                     n_bern_rows, n_entries, entries, entry_begin, entry_count, constant, n_coef, box, sys,
-                                     n_bern_factors))
-        return refused;
-    const size_t lds_rows = (size_t)1 + n_factors + (n_norm - n_norm_forcing) + n_coef;
+    if (const int refused = sim_plan(ctx, who, s, sys, n_bern_factors)) return refused;
+    const size_t lds_rows = (size_t)1 + s.n_factors + (s.n_norm - s.n_norm_forcing) + s.n_coef;
     const size_t lds_bytes = lds_rows * SIM_LANES * sizeof(double);
     if (lds_bytes > SIM_LDS_BUDGET)
         return fail(ctx, FOKL_ERR_ARG, who + "the system needs " + std::to_string(lds_rows) + " values per member in LDS (1 + factors + "
                                            "normalised states + coefficients), a wavefront's " + std::to_string(SIM_LDS_BUDGET / 1024) +
                                            " KB hold " + std::to_string(SIM_LDS_BUDGET / (SIM_LANES * sizeof(double))));
 
-    const int64_t n_points = n_steps + 1;
-    const size_t E = (size_t)n_members, ld = (E + SIM_LANES - 1) / SIM_LANES * SIM_LANES;
-    std::vector<double> coef_ld((size_t)n_coef * ld, 0.0), state((size_t)n_states * ld, 0.0);
-    for (size_t c = 0; c < (size_t)n_coef; ++c) std::memcpy(coef_ld.data() + c * ld, coef + c * E, E * sizeof(double));
-    for (size_t k = 0; k < (size_t)n_states; ++k) std::memcpy(state.data() + k * ld, y0 + k * E, E * sizeof(double));
-    std::vector<int32_t> never(ld, -1);
-
-    // steps per launch: bounded (no launch of this call runs long, the points of one launch are what is resident);
-    // FOKL_SIMULATE_STEPS_PER_LAUNCH overrides (tests: the cut changes no bit of the result)
-    int64_t per_launch = env_int("FOKL_SIMULATE_STEPS_PER_LAUNCH", 512);
-    const int64_t resident = ((int64_t)256 << 20) / (int64_t)((size_t)n_states * ld * sizeof(double));
-    per_launch = std::max<int64_t>(1, std::min(per_launch, resident - 1));
-    const int chunk_cap = (int)std::min<int64_t>(per_launch + 1, n_points);
+    const size_t E = (size_t)s.n_members, ld = (E + SIM_LANES - 1) / SIM_LANES * SIM_LANES;
+    const std::vector<int32_t> never(ld, -1);
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DeviceBuffers buf;
-    int *d_norm_src = nullptr, *d_fac_norm = nullptr, *d_fac_row = nullptr, *d_fac_degree = nullptr, *d_sat = nullptr;
-    int4 *d_entries = nullptr;
-    double *d_norm_lo = nullptr, *d_norm_span = nullptr, *d_spline = nullptr, *d_bern = nullptr, *d_coef = nullptr,
-           *d_forcing = nullptr, *d_state = nullptr, *d_points = nullptr, *d_mean = nullptr, *d_bounds = nullptr,
-           *d_members = nullptr;
-    HIP_TRY(ctx, buf.upload(&d_norm_src, norm_src, (size_t)n_norm));
-    HIP_TRY(ctx, buf.upload(&d_norm_lo, norm_lo, (size_t)n_norm));
-    HIP_TRY(ctx, buf.upload(&d_norm_span, norm_span, (size_t)n_norm));
-    HIP_TRY(ctx, buf.upload(&d_fac_norm, fac_norm, (size_t)n_factors));
-    HIP_TRY(ctx, buf.upload(&d_fac_row, fac_row, (size_t)n_factors));
-    HIP_TRY(ctx, buf.upload(&d_fac_degree, fac_degree, (size_t)n_factors));
-    HIP_TRY(ctx, buf.upload(&d_entries, entries, (size_t)n_entries));
-    HIP_TRY(ctx, buf.upload(&d_spline, spline_table, (size_t)n_spline_rows * SIM_PIECES * 4));
-    HIP_TRY(ctx, buf.upload(&d_bern, bern_table, (size_t)n_bern_rows * SIM_BERN_WIDTH));
-    HIP_TRY(ctx, buf.upload(&d_coef, coef_ld.data(), coef_ld.size()));
-    HIP_TRY(ctx, buf.upload(&d_forcing, forcing, (size_t)n_steps * n_forcing_cols));
-    HIP_TRY(ctx, buf.upload(&d_state, state.data(), state.size()));
+    SimTables tab{};
+    int *d_sat = nullptr;
+    double *d_coef = nullptr, *d_forcing = nullptr, *d_state = nullptr;
+    HIP_TRY(ctx, sim_upload(buf, s, tab, d_forcing));
+    HIP_TRY(ctx, sim_upload_padded(buf, &d_coef, s.coef, (size_t)s.n_coef, E, ld));
+    HIP_TRY(ctx, sim_upload_padded(buf, &d_state, s.y0, (size_t)s.n_states, E, ld));
     HIP_TRY(ctx, buf.upload(&d_sat, never.data(), never.size()));
-    HIP_TRY(ctx, buf.get(&d_points, (size_t)n_states * chunk_cap * ld));
-    HIP_TRY(ctx, buf.get(&d_mean, (size_t)n_states * n_points));
-    if (bounds) HIP_TRY(ctx, buf.get(&d_bounds, (size_t)n_states * n_points * 2));
-    if (members) HIP_TRY(ctx, buf.get(&d_members, E * n_states * chunk_cap));
-    const SimTables tab{d_norm_src, d_norm_lo, d_norm_span, d_fac_norm, d_fac_row, d_fac_degree, d_entries, d_spline, d_bern};
 
-    int npow2 = 2;
-    while (npow2 < n_members) npow2 <<= 1;
-    const size_t band_lds = bounds ? (size_t)npow2 * sizeof(double) : 0;
-    if (band_lds > 64 * 1024)
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(ensemble_band_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, GI_BAND_MAX_MEMBERS * (int)sizeof(double)));
-
+    // steps per launch: bounded (no launch of this call runs long); FOKL_SIMULATE_STEPS_PER_LAUNCH overrides (tests: the cut
+    // changes no bit of the result)
     const int grid = (int)(ld / SIM_LANES);
-    double terms_per_stage = 0.0;
-    for (int k = 0; k < n_states; ++k) terms_per_stage += sys.entry_count[k];
-    int64_t launches = 0;
-    for (int64_t t0 = 0, p_first = 0; p_first < n_points;) {
-        const int write_first = t0 == 0;
-        const int steps = (int)std::min<int64_t>(per_launch, n_steps - t0);
-        const int chunk_points = steps + write_first;
-        {
-            TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)ld * n_states * (chunk_points + 2.0),
-                              (double)ld * steps * 4.0 * (8.0 * terms_per_stage + 20.0 * (n_factors - n_forcing_factors)));
-            hipError_t launched = hipSuccess;
-#define SIM_CASE(NS)                                                                                                       \
-    case NS:                                                                                                               \
-        launched = sim_launch<NS>(ctx, grid, lds_bytes, sys, tab, d_coef, d_forcing, d_state, d_sat, d_points, (int64_t)ld, \
-                                  t0, steps, chunk_points, write_first);                                                   \
-        break;
-            switch (n_states) {
-                SIM_CASE(1) SIM_CASE(2) SIM_CASE(3) SIM_CASE(4) SIM_CASE(5) SIM_CASE(6) SIM_CASE(7) SIM_CASE(8)
-            }
-#undef SIM_CASE
-            HIP_TRY(ctx, launched);
-            ++launches;
-        }
-        {
-            const int rows = n_states * chunk_points;
-            const int band_grid = std::min(rows, cu_count(ctx) * (band_lds > 32 * 1024 ? 1 : 4));
-            TimedRegion timed(ctx, FOKL_K_BAND, 8.0 * (double)rows * (E + 3.0), (double)rows * E);
-            hipLaunchKernelGGL(ensemble_band_kernel, dim3(band_grid), dim3(GI_BAND_THREADS), band_lds, ctx->stream,
-                               d_points, (int64_t)ld, n_members, n_states, chunk_points, n_points, p_first, npow2, cut,
-                               d_mean, d_bounds);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        if (members) {
-            hipLaunchKernelGGL(ensemble_transpose_kernel, dim3((n_members + 31) / 32, (chunk_points + 31) / 32, n_states),
-                               dim3(256), 0, ctx->stream, d_points, (int64_t)ld, n_members, n_states, chunk_points,
-                               d_members);
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            HIP_TRY(ctx, hipMemcpy2D(members + p_first, (size_t)n_points * sizeof(double), d_members,
-                                     (size_t)chunk_points * sizeof(double), (size_t)chunk_points * sizeof(double),
-                                     E * n_states, hipMemcpyDeviceToHost));
-        }
-        t0 += steps;
-        p_first += chunk_points;
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(mean, d_mean, (size_t)n_states * n_points * sizeof(double), hipMemcpyDeviceToHost));
-    if (bounds)
-        HIP_TRY(ctx, hipMemcpy(bounds, d_bounds, (size_t)n_states * n_points * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    const double flops_per_step = 4.0 * (8.0 * sim_terms_per_stage(sys, s.n_states) + 20.0 * (s.n_factors - s.n_forcing_factors));
+    int64_t per_launch = 0, launches = 0;
+    const auto launch = [&](double *points, int64_t t0, int steps, int chunk_points, int write_first) {
+        return sim_dispatch(s.n_states, [&](auto ns) {
+            const auto kernel = simulate_ensemble_kernel<decltype(ns)::value>;
+            if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, tab.norm_src, tab.norm_lo,
+                               tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline, tab.bern,
+                               (const double *)d_coef, (const double *)d_forcing, d_state, d_sat, points, (int64_t)ld, t0, steps,
+                               chunk_points, write_first);
+            return hipGetLastError();
+        });
+    };
+    if (const int failed = sim_run(ctx, s, ld, env_int("FOKL_SIMULATE_STEPS_PER_LAUNCH", 512), out, flops_per_step, buf, launch,
+                                   per_launch, launches))
+        return failed;
     HIP_TRY(ctx, hipMemcpy(first_saturation, d_sat, E * sizeof(int32_t), hipMemcpyDeviceToHost));
     int64_t *rep = ctx->simulate_report;
-    rep[0] = n_states;
-    rep[1] = n_members;
+    rep[0] = s.n_states;
+    rep[1] = s.n_members;
     rep[2] = grid;
     rep[3] = (int64_t)lds_bytes;
     rep[4] = launches;
-    rep[5] = n_factors - n_bern_factors;
+    rep[5] = s.n_factors - n_bern_factors;
     rep[6] = n_bern_factors;
     rep[7] = per_launch;
     return FOKL_OK;

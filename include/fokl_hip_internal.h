@@ -1122,38 +1122,57 @@ int fokl_infer_rng(uint32_t seed, uint32_t draw_id, uint32_t iteration, int purp
 #define FOKL_SIMULATE_MAX_STATES 8
 
 /*
- * Classical Runge-Kutta integration of d(state k)/dt = model_k(its inputs), k < n_states <= 8, for n_members members at
- * once, over n_steps steps of size h.  The plan is assembled by dynamics._prepare and the arithmetic is stated by
+ * A system of fitted models as dynamics._prepare assembles it: what fokl_simulate_ensemble, fokl_simulate_adaptive,
+ * fokl_simulate_stiff, fokl_assimilate_ensemble, fokl_control_solve, fokl_control_pooled_solve and fokl_control_cvar_solve
+ * integrate.  Host memory, row-major; the call reads it and keeps no pointer.
+ */
+typedef struct fokl_system {
+    int n_members;          /* members = posterior draws / initial states (the control and filter calls: n_draws) */
+    int n_states;           /* d(state k)/dt = model_k(its inputs), k < n_states <= FOKL_SIMULATE_MAX_STATES */
+    int64_t n_steps;        /* steps of size h; the time axis has n_steps + 1 points */
+    double h;
+    int n_forcing_cols;
+    const double *forcing;  /* [n_steps, n_forcing_cols] true scale; row s serves every stage of step s */
+    /* the normalised inputs v = (x - lo) / span clamped to [0, 1]: the first n_norm_forcing read forcing column
+     * -(src + 1), the others state src, in ascending order of src */
+    int n_norm_forcing, n_norm;
+    const int32_t *norm_src; /* [n_norm] */
+    const double *norm_lo, *norm_span;
+    /* the distinct factors, the first n_forcing_factors on forcing inputs, inside either group kind 0 (cubic splines)
+     * before kind 1 (Bernoulli); fac_row is the factor's row of its table, fac_degree a Bernoulli factor's order (<= 20) */
+    int n_forcing_factors, n_factors;
+    const int32_t *fac_norm, *fac_kind, *fac_row, *fac_degree; /* [n_factors] */
+    int n_spline_rows;
+    const double *spline_table; /* [n_spline_rows, 499, 4]: c0 .. c3 of every piece */
+    int n_bern_rows;
+    const double *bern_table; /* [n_bern_rows, 21], lowest power first */
+    /* entries [n_entries][4] int32 {slot, slot, slot, coefficient}: slot 0 is 1.0, slot f + 1 factor f; coefficient -1:
+     * the product continues in the next entry.  Model k owns entries [entry_begin[k], entry_begin[k] + entry_count[k])
+     * and its constant is coefficient constant[k] */
+    int n_entries;
+    const int32_t *entries, *entry_begin, *entry_count, *constant;
+    int n_coef;
+    /* The one layout that differs between the calls: the simulate calls take coef as [n_coef][n_members] (a coefficient's
+     * members are contiguous), the assimilate and control calls as [n_draws][n_coef] (a draw's coefficients are) */
+    const double *coef;
+    const double *y0;  /* [n_states, n_members] */
+    const double *box; /* [n_states, 2] true scale: lower < upper */
+} fokl_system;
+
+/*
+ * Classical Runge-Kutta integration of `system` for all its members at once.  The arithmetic is stated by
  * dynamics.simulate_host (the module docstring of fokl_gpy_amd/dynamics.py): a member's trajectory equals the host
- * statement's bit for bit.  Host memory, row-major:
- *   forcing [n_steps, n_forcing_cols] true scale; row s serves the four stages of step s
- *   norm_src / norm_lo / norm_span [n_norm]: the normalised inputs v = (x - lo) / span clamped to [0, 1]; the first
- *          n_norm_forcing read forcing column -(src + 1), the others state src, in ascending order of src
- *   fac_norm / fac_kind / fac_row / fac_degree [n_factors]: the distinct factors, the first n_forcing_factors on forcing
- *          inputs, inside either group kind 0 (cubic splines) before kind 1 (Bernoulli); fac_row is the factor's row of
- *          spline_table [n_spline_rows, 499, 4] (c0 .. c3 of every piece) or of bern_table [n_bern_rows, 21] (lowest
- *          power first), fac_degree a Bernoulli factor's order (<= 20)
- *   entries [n_entries, 4] int32 {slot, slot, slot, coefficient}: slot 0 is 1.0, slot f + 1 factor f; coefficient -1: the
- *          product continues in the next entry.  Model k owns entries [entry_begin[k], entry_begin[k] + entry_count[k]) and
- *          its constant is coefficient constant[k]
- *   coef [n_coef, n_members], y0 [n_states, n_members], box [n_states, 2] (true scale: lower < upper)
+ * statement's bit for bit.  coef [n_coef, n_members].  Host memory, row-major:
  *   mean [n_states, n_steps + 1]; bounds [n_states, n_steps + 1, 2] or NULL (sorted[cut], sorted[n_members - cut], at most
  *   16 384 members); members [n_members, n_states, n_steps + 1] or NULL; first_saturation [n_members] int32: the first step
  *   in which a clamp or the slope rule acted, -1 never.
  * One lane per member, one wavefront per workgroup, (1 + n_factors + n_norm - n_norm_forcing + n_coef) values per lane in
  * LDS (at most 144 KB).  The steps are cut into launches of FOKL_SIMULATE_STEPS_PER_LAUNCH (environment, default 512): the
  * cut changes no bit.  Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched, the dataset and
- * pending launches are left alone): more than 8 states, an index outside its table, an empty box, the LDS budget, bounds
- * over fewer than 2 or more than 16 384 members.  Kernel times: FOKL_K_INTEGRATE, FOKL_K_BAND.  Blocking.
+ * pending launches are left alone): a NULL system, more than 8 states, an index outside its table, an empty box, the LDS
+ * budget, bounds over fewer than 2 or more than 16 384 members.  Kernel times: FOKL_K_INTEGRATE, FOKL_K_BAND.  Blocking.
  */
-int fokl_simulate_ensemble(fokl_ctx *ctx, int n_members, int n_states, int64_t n_steps, double h, int n_forcing_cols,
-                           const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
-                           const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
-                           const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
-                           const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
-                           const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
-                           const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
-                           const double *y0, const double *box, int cut, double *mean, double *bounds, double *members,
+int fokl_simulate_ensemble(fokl_ctx *ctx, const fokl_system *system, int cut, double *mean, double *bounds, double *members,
                            int32_t *first_saturation);
 
 /*
@@ -1177,7 +1196,7 @@ int fokl_simulate_report(const fokl_ctx *ctx, int64_t *out);
  * inside each output step by step doubling on a dyadic grid: at level k a trial is one step of 2 g and two steps of
  * g = h / 2^(k + 1), accepted where |y2 - y1| <= 15 (atol_j + rtol max(|y_j|, |y2_j|)) for every state j or k == max_halvings.
  * The arithmetic is stated by dynamics.simulate_adaptive_host (the module docstring of fokl_gpy_amd/dynamics.py): every
- * output equals the host statement's bit for bit.  The arguments up to `cut` are fokl_simulate_ensemble's; then
+ * output equals the host statement's bit for bit.  `system` and `cut` are fokl_simulate_ensemble's; then
  *   rtol, atol [n_states]; min_halvings <= max_halvings: the levels a member may use
  *   mean, bounds, members, first_saturation: as fokl_simulate_ensemble's
  *   pairs, rejected [n_members] int64: accepted pairs of half steps, rejected trials
@@ -1191,17 +1210,10 @@ int fokl_simulate_report(const fokl_ctx *ctx, int64_t *out);
  * nothing is launched): what fokl_simulate_ensemble refuses, rtol or an atol that is negative or not finite, rtol == 0 with
  * a zero atol, levels outside 0 <= min_halvings <= max_halvings <= 12.  Kernel times: FOKL_K_INTEGRATE, FOKL_K_BAND.  Blocking.
  */
-int fokl_simulate_adaptive(fokl_ctx *ctx, int n_members, int n_states, int64_t n_steps, double h, int n_forcing_cols,
-                           const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
-                           const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
-                           const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
-                           const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
-                           const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
-                           const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
-                           const double *y0, const double *box, int cut, double rtol, const double *atol, int min_halvings,
-                           int max_halvings, double *mean, double *bounds, double *members, int32_t *first_saturation,
-                           int64_t *pairs, int64_t *rejected, int32_t *max_level, double *error, int32_t *first_unresolved,
-                           int8_t *levels);
+int fokl_simulate_adaptive(fokl_ctx *ctx, const fokl_system *system, int cut, double rtol, const double *atol,
+                           int min_halvings, int max_halvings, double *mean, double *bounds, double *members,
+                           int32_t *first_saturation, int64_t *pairs, int64_t *rejected, int32_t *max_level, double *error,
+                           int32_t *first_unresolved, int8_t *levels);
 
 /*
  * The last fokl_simulate_adaptive call on `ctx`, out [FOKL_SIMULATE_ADAPTIVE_REPORT_LEN] (host values, no launch); zeros
@@ -1236,14 +1248,7 @@ int fokl_simulate_adaptive_report(const fokl_ctx *ctx, int64_t *out);
  * Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched): what fokl_simulate_adaptive refuses, and a
  * system whose LDS need exceeds the 144 KB of a wavefront.  Kernel times: FOKL_K_INTEGRATE, FOKL_K_BAND.  Blocking.
  */
-int fokl_simulate_stiff(fokl_ctx *ctx, int n_members, int n_states, int64_t n_steps, double h, int n_forcing_cols,
-                        const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
-                        const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
-                        const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
-                        const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
-                        const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
-                        const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
-                        const double *y0, const double *box, int cut, double rtol, const double *atol, int min_halvings,
+int fokl_simulate_stiff(fokl_ctx *ctx, const fokl_system *system, int cut, double rtol, const double *atol, int min_halvings,
                         int max_halvings, double *mean, double *bounds, double *members, int32_t *first_saturation,
                         int64_t *steps, int64_t *rejected, int64_t *swaps, int32_t *max_level, double *error,
                         int32_t *first_unresolved, int8_t *levels);
@@ -1268,11 +1273,11 @@ int fokl_simulate_stiff_report(const fokl_ctx *ctx, int64_t *out);
 /*
  * A bootstrap particle filter per posterior draw: 64 particles follow fokl_simulate_ensemble's Runge-Kutta step with the
  * draw's coefficients, receive process noise, and are weighted and resampled at the observed points.  The plan of the system
- * is dynamics._prepare's (the arguments up to `box` mean what they mean for fokl_simulate_ensemble, except coef), the
+ * is dynamics._prepare's (`system`, with coef by draw), the
  * arithmetic is stated by dynamics.assimilate_host (the module docstring of fokl_gpy_amd/dynamics.py).  Host memory,
  * row-major:
- *   coef [n_draws, n_coef] (a draw's coefficients are contiguous); y0 [n_states, n_draws]; draw_ids [n_draws]: the second
- *          key word of a draw's random numbers (fokl_assimilate_rng)
+ *   coef [n_draws, n_coef] with n_draws = system->n_members; draw_ids [n_draws]: the second key word of a draw's random
+ *          numbers (fokl_assimilate_rng)
  *   obs_state [n_observed] the state every measured column reads (distinct), obs_sd [n_observed] > 0
  *   obs_row [n_steps + 1] int32: the row of `data` measured at a point, -1 none; the rows appear as 0, 1, ... n_obs - 1
  *   data [n_obs, n_observed] true scale, NaN = missing; obs_const [n_obs] = the sum over a row's present entries of
@@ -1295,14 +1300,7 @@ int fokl_simulate_stiff_report(const fokl_ctx *ctx, int64_t *out);
  * an observation table that is not 0, 1, ... in order or disagrees with n_obs.
  * Kernel time: FOKL_K_INTEGRATE.  Blocking; everything uploaded is freed before it returns.
  */
-int fokl_assimilate_ensemble(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
-                             const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
-                             const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
-                             const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
-                             const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
-                             const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
-                             const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
-                             const double *y0, const double *box, const uint32_t *draw_ids, int n_observed,
+int fokl_assimilate_ensemble(fokl_ctx *ctx, const fokl_system *system, const uint32_t *draw_ids, int n_observed,
                              const int32_t *obs_state, const double *obs_sd, int n_obs, const int32_t *obs_row,
                              const double *data, const double *obs_const, const double *process_q, const double *y0_sd,
                              double threshold, uint32_t seed, double *stats, double *particles_out, double *weights_out,
@@ -1336,18 +1334,31 @@ int fokl_assimilate_rng(uint32_t seed, const uint32_t *draw_ids, int n_draws, ui
 #define FOKL_CONTROL_MAX_STEPS 4096
 
 /*
+ * The control problem of fokl_control_solve, fokl_control_pooled_solve and fokl_control_cvar_solve over a fokl_system.
+ * Host memory, row-major; D = n_controls x n_segments decision values, d = control x n_segments + segment.
+ */
+typedef struct fokl_control_problem {
+    int n_controls, n_segments;
+    const int32_t *seg_first;    /* [n_segments]: the first step of every hold (0 first, increasing, below n_steps) */
+    const int32_t *norm_control; /* [n_norm_forcing]: the control a forcing input reads, -1: a column of `forcing` */
+    const double *ctl_lo, *ctl_width; /* [n_controls]: u = lo + z width, z in [0, 1] */
+    const double *ref;           /* [n_states, n_steps + 1] targets, NaN: not tracked */
+    const double *track_weight, *terminal_weight; /* [n_states]: h w_j, and the terminal weights */
+    const double *limit_lo, *limit_hi; /* [n_states] (-inf / +inf: open) */
+    double limit_weight;         /* h x the soft limits' weight */
+    const double *move_weight, *previous; /* [n_controls]; the move of segment 0 counts only with has_previous */
+    int has_previous, n_starts;
+    const double *z0;            /* [n_starts, D] in [0, 1] */
+    int max_iter;                /* 0: the first tangent pass only */
+    double tol;                  /* on the projected gradient in z */
+} fokl_control_problem;
+
+/*
  * One bounded least-squares solve per (posterior draw, start): projected Gauss-Newton on the cost of dynamics.control, the
  * Jacobian from forward sensitivities of fokl_simulate_ensemble's Runge-Kutta step as executed.  The plan of the system is
- * dynamics._prepare's with the controls as forcing columns (the arguments up to `box` mean what they mean for
- * fokl_assimilate_ensemble), the arithmetic is stated by dynamics.control_host (the module docstring of
- * fokl_gpy_amd/dynamics.py).  Host memory, row-major:
- *   seg_first [n_segments] int32: the first step of every hold (0 first, increasing, below n_steps)
- *   norm_control [n_norm_forcing] int32: the control a forcing input reads, -1: a column of `forcing`
- *   ctl_lo / ctl_width [n_controls]: u = lo + z width, z in [0, 1]; decision value d = control x n_segments + segment
- *   ref [n_states, n_steps + 1] targets, NaN: not tracked; track_weight [n_states] = h w_j, terminal_weight [n_states],
- *          limit_lo / limit_hi [n_states] (-inf / +inf: open), limit_weight = h x the soft limits' weight
- *   move_weight / previous [n_controls]; the move of segment 0 counts only with has_previous
- *   z0 [n_starts, D] in [0, 1]; max_iter (0: the first tangent pass only), tol on the projected gradient in z
+ * dynamics._prepare's with the controls as forcing columns (`system` as fokl_assimilate_ensemble takes it: coef
+ * [n_draws, n_coef]), the problem is `problem` below, the arithmetic is stated by dynamics.control_host (the module
+ * docstring of fokl_gpy_amd/dynamics.py).  Host memory, row-major:
  *   z [n_draws, n_starts, D], cost / cost_start [n_draws, n_starts], status (0 converged, 1 iteration limit, 2 non-finite,
  *          3 stalled) / iterations / descent_steps (iterations whose accepted trial was a steepest-descent lane)
  *          [n_draws, n_starts] int32; best_start [n_draws] int32
@@ -1364,17 +1375,7 @@ int fokl_assimilate_rng(uint32_t seed, const uint32_t *draw_ids, int n_draws, ui
  * control box or one outside the training range, negative weights, no residual at all, n_starts < 1, n_draws x n_starts
  * above 1 048 576, a start outside [0, 1], the LDS bytes above.  Kernel time: FOKL_K_INTEGRATE.  Blocking.
  */
-int fokl_control_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
-                       const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src, const double *norm_lo,
-                       const double *norm_span, int n_forcing_factors, int n_factors, const int32_t *fac_norm,
-                       const int32_t *fac_kind, const int32_t *fac_row, const int32_t *fac_degree, int n_spline_rows,
-                       const double *spline_table, int n_bern_rows, const double *bern_table, int n_entries,
-                       const int32_t *entries, const int32_t *entry_begin, const int32_t *entry_count, const int32_t *constant,
-                       int n_coef, const double *coef, const double *y0, const double *box, int n_controls, int n_segments,
-                       const int32_t *seg_first, const int32_t *norm_control, const double *ctl_lo, const double *ctl_width,
-                       const double *ref, const double *track_weight, const double *terminal_weight, const double *limit_lo,
-                       const double *limit_hi, double limit_weight, const double *move_weight, const double *previous,
-                       int has_previous, int n_starts, const double *z0, int max_iter, double tol, double *z, double *cost,
+int fokl_control_solve(fokl_ctx *ctx, const fokl_system *system, const fokl_control_problem *problem, double *z, double *cost,
                        double *cost_start, int32_t *status, int32_t *iterations, int32_t *descent_steps, int32_t *best_start,
                        double *members, int32_t *first_saturation, double *first_F, double *first_g, double *first_H);
 
@@ -1417,7 +1418,7 @@ typedef struct fokl_control_first_trial {
 /*
  * One bounded least-squares solve per start over ALL draws: the expected cost sum_e w_e F_e(z) of fokl_control_solve's cost,
  * minimised over one decision vector by the same projected Gauss-Newton iteration with the pooled F, noise, g and H in place
- * of one draw's.  The arithmetic is stated by dynamics.control_pooled_host; every argument up to `tol` means what it means
+ * of one draw's.  The arithmetic is stated by dynamics.control_pooled_host; `system` and `problem` mean what they mean
  * for fokl_control_solve.  Host memory, row-major:
  *   draw_weights [n_draws]: used as given (the caller normalises them to sum 1); a draw of weight 0 is never evaluated
  *   z [n_starts, D], cost / cost_start [n_starts], status / iterations / descent_steps [n_starts] int32; best_start [1] int32
@@ -1440,18 +1441,7 @@ typedef struct fokl_control_first_trial {
  * a workspace of n_draws x n_starts x (n + 64) x 8 bytes plus (n + 64) x 8 per (start, chunk) beyond the device's free
  * memory, of which FOKL_CONTROL_POOLED_FREE_BYTES (environment) caps what counts.  Kernel time: FOKL_K_INTEGRATE.  Blocking.
  */
-int fokl_control_pooled_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
-                              const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
-                              const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
-                              const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
-                              const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
-                              const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
-                              const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
-                              const double *y0, const double *box, int n_controls, int n_segments, const int32_t *seg_first,
-                              const int32_t *norm_control, const double *ctl_lo, const double *ctl_width, const double *ref,
-                              const double *track_weight, const double *terminal_weight, const double *limit_lo,
-                              const double *limit_hi, double limit_weight, const double *move_weight, const double *previous,
-                              int has_previous, int n_starts, const double *z0, int max_iter, double tol,
+int fokl_control_pooled_solve(fokl_ctx *ctx, const fokl_system *system, const fokl_control_problem *problem,
                               const double *draw_weights, double *z, double *cost, double *cost_start, int32_t *status,
                               int32_t *iterations, int32_t *descent_steps, int32_t *best_start, double *members,
                               int32_t *first_saturation, double *cost_draws, double *first_pooled, double *first_rows,
@@ -1476,7 +1466,7 @@ int fokl_control_pooled_report(const fokl_ctx *ctx, int64_t *out);
 /*
  * fokl_control_pooled_solve with the smoothed conditional value at risk at level `alpha` of the draws' costs in place of
  * their weighted mean: phi(z) = min_a a + sum_e w_e s_eps(F_e(z) - a) / (1 - alpha).  The arithmetic is stated by
- * dynamics.control_cvar_host (the risk: dynamics.cvar_smooth); every argument up to `draw_weights`, and every output up to
+ * dynamics.control_cvar_host (the risk: dynamics.cvar_smooth); `system`, `problem`, `draw_weights`, and every output up to
  * `cost_draws`, means what it means for fokl_control_pooled_solve, `cost` being phi.  Further, host memory:
  *   alpha in [0, 1); alpha == 0 IS fokl_control_pooled_solve (which is called: first_a reads NaN, first_q the weights,
  *          first_c 0, this call's report stays zero and the pooled call's is written)
@@ -1497,18 +1487,7 @@ int fokl_control_pooled_report(const fokl_ctx *ctx, int64_t *out);
  * (3 + 2 D + 2 D D) x 8 per (start, chunk) plus 64 x (4 + D) x 8 per start beyond the device's free memory, of which
  * FOKL_CONTROL_CVAR_FREE_BYTES (environment) caps what counts.  Kernel time: FOKL_K_INTEGRATE.  Blocking.
  */
-int fokl_control_cvar_solve(fokl_ctx *ctx, int n_draws, int n_states, int64_t n_steps, double h, int n_forcing_cols,
-                            const double *forcing, int n_norm_forcing, int n_norm, const int32_t *norm_src,
-                            const double *norm_lo, const double *norm_span, int n_forcing_factors, int n_factors,
-                            const int32_t *fac_norm, const int32_t *fac_kind, const int32_t *fac_row,
-                            const int32_t *fac_degree, int n_spline_rows, const double *spline_table, int n_bern_rows,
-                            const double *bern_table, int n_entries, const int32_t *entries, const int32_t *entry_begin,
-                            const int32_t *entry_count, const int32_t *constant, int n_coef, const double *coef,
-                            const double *y0, const double *box, int n_controls, int n_segments, const int32_t *seg_first,
-                            const int32_t *norm_control, const double *ctl_lo, const double *ctl_width, const double *ref,
-                            const double *track_weight, const double *terminal_weight, const double *limit_lo,
-                            const double *limit_hi, double limit_weight, const double *move_weight, const double *previous,
-                            int has_previous, int n_starts, const double *z0, int max_iter, double tol,
+int fokl_control_cvar_solve(fokl_ctx *ctx, const fokl_system *system, const fokl_control_problem *problem,
                             const double *draw_weights, double alpha, double smoothing, double epsilon, double *z,
                             double *cost, double *cost_start, int32_t *status, int32_t *iterations, int32_t *descent_steps,
                             int32_t *best_start, double *members, int32_t *first_saturation, double *cost_draws,

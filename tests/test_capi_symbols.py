@@ -55,6 +55,88 @@ def test_binding_table_matches_header():
     assert sorted(_capi.SIGNATURES.keys()) == sorted(declared_symbols(HEADER) + declared_symbols(INTERNAL))
 
 
+def declared_functions(path):
+    """{name: [parameter text, ...]} of every function a header declares ((void): no parameter)."""
+    text = re.sub(r'/\*.*?\*/', '', open(path).read(), flags=re.S)
+    out = {}
+    for name, params in re.findall(r'\b(fokl_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;', text):
+        params = ' '.join(params.split())
+        out[name] = [] if params in ('', 'void') else [part.strip() for part in params.split(',')]
+    return out
+
+
+def parameter_class(text):
+    """'pointer', 'double', 'int64' or 'int32' of a C parameter as the headers write them."""
+    if '*' in text or '[' in text:
+        return 'pointer'
+    kind = text.split()[-2] if len(text.split()) > 1 else text
+    return {'double': 'double', 'int64_t': 'int64', 'uint64_t': 'int64', 'size_t': 'int64', 'int': 'int32', 'int32_t': 'int32',
+            'uint32_t': 'int32', 'unsigned': 'int32'}[kind]
+
+
+def ctypes_class(kind):
+    if kind in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(kind, ctypes._Pointer):
+        return 'pointer'
+    if kind is ctypes.c_double:
+        return 'double'
+    assert issubclass(kind, ctypes._SimpleCData) and kind._type_ in 'iIlLqQ', kind
+    return 'int64' if ctypes.sizeof(kind) == 8 else 'int32'
+
+
+SYSTEM_CALLS = ('fokl_simulate_ensemble', 'fokl_simulate_adaptive', 'fokl_simulate_stiff', 'fokl_assimilate_ensemble',
+                'fokl_control_solve', 'fokl_control_pooled_solve', 'fokl_control_cvar_solve')
+SYSTEM_REPORTS = ('fokl_simulate_report', 'fokl_simulate_adaptive_report', 'fokl_simulate_stiff_report', 'fokl_assimilate_report',
+                  'fokl_control_report', 'fokl_control_pooled_report', 'fokl_control_cvar_report')
+
+
+def test_binding_signatures_match_the_headers():
+    """Every declared function without a function-pointer parameter has as many argtypes as parameters; for the calls that
+    take a fokl_system and their reports every parameter's class (pointer, double, 64-bit, 32-bit integer) matches too."""
+    declared = {**declared_functions(HEADER), **declared_functions(INTERNAL)}
+    assert sorted(declared) == sorted(_capi.SIGNATURES)
+    miscounted = {name: (len(params), len(_capi.SIGNATURES[name][1])) for name, params in declared.items()
+                  if not any('(' in p for p in params) and len(params) != len(_capi.SIGNATURES[name][1])}
+    assert miscounted == {}
+    for name in SYSTEM_CALLS + SYSTEM_REPORTS:
+        header = [parameter_class(p) for p in declared[name]]
+        binding = [ctypes_class(kind) for kind in _capi.SIGNATURES[name][1]]
+        assert header == binding, name
+
+
+def test_struct_layouts_match_the_header(tmp_path):
+    """sizeof and every offsetof of fokl_system and fokl_control_problem as a C compiler lays them out equal the ctypes
+    classes', field by field and by name."""
+    import shutil
+    import subprocess
+    cc = shutil.which('gcc') or shutil.which('cc')
+    assert cc, "no C compiler: the layout of the structs cannot be checked"
+    structs = {'fokl_system': _capi._SystemStruct, 'fokl_control_problem': _capi._ControlProblemStruct}
+    lines = []
+    for c_name, cls in structs.items():
+        lines.append(f'    printf("{c_name} sizeof %zu\\n", sizeof({c_name}));')
+        lines += [f'    printf("{c_name} {field} %zu\\n", offsetof({c_name}, {field}));' for field, _ in cls._fields_]
+    source = tmp_path / 'layout.c'
+    source.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "fokl_hip_internal.h"\nint main(void)\n{\n' +
+                      '\n'.join(lines) + '\n    return 0;\n}\n')
+    program = tmp_path / 'layout'
+    res = subprocess.run([cc, '-std=c99', '-Wall', '-I', os.path.dirname(INTERNAL), '-o', str(program), str(source)],
+                         capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    printed = subprocess.run([str(program)], capture_output=True, text=True, check=True).stdout.split('\n')
+    in_c = {(s, f): int(v) for s, f, v in (line.split() for line in printed if line)}
+    in_python = {}
+    for c_name, cls in structs.items():
+        in_python[(c_name, 'sizeof')] = ctypes.sizeof(cls)
+        in_python.update({(c_name, field): getattr(cls, field).offset for field, _ in cls._fields_})
+    assert in_python == in_c
+    # and the classes name every field the header has: a field missing in Python would shift nothing it checks above
+    text = re.sub(r'/\*.*?\*/', '', open(INTERNAL).read(), flags=re.S)
+    for c_name, cls in structs.items():
+        body = re.search(r'typedef struct ' + c_name + r' \{(.*?)\} ' + c_name + ';', text, flags=re.S).group(1)
+        fields = [name for decl in body.split(';') for name in re.findall(r'(\w+)\s*(?:,|$)', decl.strip())]
+        assert fields == [field for field, _ in cls._fields_], c_name
+
+
 def test_no_device_is_reported_not_hidden():
     """Without a GPU the context constructor must raise (no CPU fallback); with one it must succeed."""
     n = _capi.device_count()
