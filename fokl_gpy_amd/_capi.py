@@ -49,6 +49,8 @@ INFER_U1, INFER_U2, INFER_U3, INFER_JITTER = 0, 1, 2, 3      # fokl_infer_rng's 
 ASSIMILATE_PARTICLES = 64                 # fokl_assimilate_ensemble: the particles of one draw are one wavefront
 # fokl_assimilate_rng's purposes (csrc/fokl_philox.h); 0 .. 7 are the process-noise normals of state j
 ASSIMILATE_INIT, ASSIMILATE_RESAMPLE, ASSIMILATE_DRAW_INDEX = 8, 9, 10
+CALIBRATE_WALKERS = 128                   # fokl_calibrate_ensemble: an ensemble is two halves of one wavefront's 64 lanes
+CALIBRATE_MAX_UNKNOWN = 16
 # fokl_fit_report's kernel names, by id: Gram / residual / basis launch
 GRAM_KERNELS = ('none', 'valu', 'tiles', 'dma', 'panel', 'tiles4')
 RESID_KERNELS = ('none', 'columns', 'matrix_free')
@@ -217,6 +219,9 @@ SIGNATURES = {
     'fokl_assimilate_ensemble': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, ctypes.c_uint32,
                                          c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_assimilate_report': (c_int, [c_vp, c_vp]),
+    'fokl_calibrate_ensemble': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_calibrate_report': (c_int, [c_vp, c_vp]),
+    'fokl_calibrate_rng': (c_int, [ctypes.c_uint32, c_vp, c_int, ctypes.c_uint32, c_int, c_int, c_vp]),
     'fokl_control_solve': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_control_report': (c_int, [c_vp, c_vp]),
     'fokl_control_pooled_solve': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
@@ -347,6 +352,17 @@ def assimilate_rng(seed, draw_ids, step, purpose, count):
     out = np.empty((ids.shape[0], int(count)), dtype=np.float64)
     _check(load().fokl_assimilate_rng(int(seed) & 0xFFFFFFFF, _ptr(ids), int(ids.shape[0]), int(step), int(purpose), int(count),
                                       _ptr(out)))
+    return out
+
+
+def calibrate_rng(seed, draw_ids, iteration, purpose, count):
+    """The numbers ``dynamics.calibrate``'s sampler draws (fokl_calibrate_rng: Philox 4x32-10 keyed by (seed, draw id), counter
+    (iteration, purpose, index, 3)) -> [len(draw_ids), count]; purposes INFER_U1 .. INFER_U3 uniforms of walker ``index``
+    (0 .. 127), INFER_JITTER the normal of index 128 i + w; host code, no device."""
+    ids = np.ascontiguousarray(draw_ids, dtype=np.uint32)
+    out = np.empty((ids.shape[0], int(count)), dtype=np.float64)
+    _check(load().fokl_calibrate_rng(int(seed) & 0xFFFFFFFF, _ptr(ids), int(ids.shape[0]), int(iteration), int(purpose),
+                                     int(count), _ptr(out)))
     return out
 
 
@@ -1829,6 +1845,14 @@ class _ControlProblemStruct(ctypes.Structure):
                 ('n_starts', c_int), ('z0', c_vp), ('max_iter', c_int), ('tol', c_dbl)]
 
 
+class _CalibrateProblemStruct(ctypes.Structure):
+    """fokl_calibrate_problem (include/fokl_hip_internal.h)"""
+    _fields_ = [('n_unknown', c_int), ('unknown_src', c_vp), ('norm_param', c_vp), ('lo', c_vp), ('hi', c_vp), ('prior_mean', c_vp),
+                ('prior_prec', c_vp), ('starts', c_vp), ('n_observed', c_int), ('obs_state', c_vp), ('obs_hp', c_vp), ('n_obs', c_int),
+                ('obs_row', c_vp), ('data', c_vp), ('draw_ids', c_vp), ('burnin', c_int), ('draws_kept', c_int), ('thin', c_int),
+                ('jump_every', c_int), ('seed', ctypes.c_uint32)]
+
+
 _i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
 _f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
 
@@ -1873,6 +1897,26 @@ def _control_problem_struct(p, who):
     struct = _ControlProblemStruct(n_controls=nc, n_segments=a['seg_first'].shape[0], limit_weight=float(p['hl']),
                                    has_previous=int(bool(p['has_previous'])), n_starts=S, max_iter=int(p['max_iter']),
                                    tol=float(p['tol']), **{name: _ptr(arr) for name, arr in a.items()})
+    return struct, a
+
+
+def _calibrate_problem_struct(p, who):
+    """The fokl_calibrate_problem of a ``p`` prepared by ``dynamics._prepare_calibrate`` -> (struct, the arrays it points into)."""
+    E, P, d = int(p['E']), int(p['n_steps']) + 1, int(p['d'])
+    a = dict(unknown_src=_i32(p['unknown_src']), norm_param=_i32(p['norm_param']), lo=_f64(p['lo']), hi=_f64(p['hi']),
+             prior_mean=_f64(p['prior_mean']), prior_prec=_f64(p['prior_prec']), starts=_f64(p['starts']),
+             obs_state=_i32(p['obs_state']), obs_hp=_f64(p['obs_hp']), obs_row=_i32(p['obs_row']), data=_f64(p['data']),
+             draw_ids=np.ascontiguousarray(p['draw_ids'], dtype=np.uint32))
+    if a['unknown_src'].shape != (d,) or a['norm_param'].shape != (int(p['n_norm_forcing']),) or \
+            any(a[key].shape != (d,) for key in ('lo', 'hi', 'prior_mean', 'prior_prec')) or \
+            a['starts'].shape != (CALIBRATE_WALKERS, d) or a['obs_state'].ndim != 1 or a['obs_hp'].shape != a['obs_state'].shape or \
+            a['data'].ndim != 2 or a['data'].shape[1] != a['obs_state'].shape[0] or a['obs_row'].shape != (P,) or \
+            a['draw_ids'].shape != (E,):
+        raise ValueError(f"{who}: array shapes disagree")
+    struct = _CalibrateProblemStruct(n_unknown=d, n_observed=a['obs_state'].shape[0], n_obs=a['data'].shape[0],
+                                     burnin=int(p['burnin']), draws_kept=int(p['draws_kept']), thin=int(p['thin']),
+                                     jump_every=int(p['jump_every']), seed=int(p['seed']) & 0xFFFFFFFF,
+                                     **{name: _ptr(arr) for name, arr in a.items()})
     return struct, a
 
 
@@ -2489,6 +2533,39 @@ class DeviceContext:
         self._ck(self._lib.fokl_assimilate_report(self._h, _ptr(out)))
         keys = ('NS', 'draws', 'grid', 'lds_bytes', 'launches', 'steps_per_launch', 'observations', 'spline_factors',
                 'bernoulli_factors')
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def calibrate(self, p):
+        """fokl_calibrate_ensemble for a system prepared by ``dynamics._prepare_calibrate`` -> (x [E, kept, 128, d] or None, lp
+        [E, kept, 128] or None, saturated [E, kept, 128] bool or None, sums [E, 128, 2, 2, d], accepted [E, 128, 2] int32,
+        evaluations [E] int64, invalid [E] bool, trajectories [E, 128, n_states, P] or None).  Needs no uploaded dataset and
+        leaves one alone."""
+        K, E, P, d = int(p['K']), int(p['E']), int(p['n_steps']) + 1, int(p['d'])
+        system, held = _system_struct(p, 'calibrate', coef_by_draw=True)
+        problem, held_problem = _calibrate_problem_struct(p, 'calibrate')
+        kept = -(-int(p['draws_kept']) // max(int(p['thin']), 1))
+        rows = bool(p['want_rows'])
+        x = np.empty((E, kept, CALIBRATE_WALKERS, d), dtype=np.float64) if rows else None
+        lp = np.empty((E, kept, CALIBRATE_WALKERS), dtype=np.float64) if rows else None
+        sat = np.empty((E, kept, CALIBRATE_WALKERS), dtype=np.int32) if rows else None
+        sums = np.empty((E, CALIBRATE_WALKERS, 2, 2, d), dtype=np.float64)
+        accepted = np.empty((E, CALIBRATE_WALKERS, 2), dtype=np.int32)
+        evaluations, invalid = np.empty(E, dtype=np.int64), np.empty(E, dtype=np.int32)
+        trajectories = np.empty((E, CALIBRATE_WALKERS, K, P), dtype=np.float64) if p['want_trajectories'] else None
+        self._ck(self._lib.fokl_calibrate_ensemble(
+            self._h, ctypes.byref(system), ctypes.byref(problem), _ptr(x), _ptr(lp), _ptr(sat), _ptr(sums), _ptr(accepted),
+            _ptr(evaluations), _ptr(invalid), _ptr(trajectories)))
+        del held, held_problem
+        return x, lp, (sat != 0 if rows else None), sums, accepted, evaluations, invalid != 0, trajectories
+
+    def calibrate_report(self):
+        """What the last ``calibrate`` on this context ran (fokl_calibrate_report; host values, no launch): ``NS`` (the kernel
+        instance = states), ``draws`` (= workgroups = wavefronts), ``lds_bytes``, ``launches`` (the replay of the final
+        ensemble included) of ``iterations_per_launch`` iterations, ``evaluations`` (trajectories integrated, all draws),
+        ``kernel_us`` and ``iterations``.  Zeros after a refused call."""
+        out = np.zeros(8, dtype=np.int64)
+        self._ck(self._lib.fokl_calibrate_report(self._h, _ptr(out)))
+        keys = ('NS', 'draws', 'lds_bytes', 'launches', 'iterations_per_launch', 'evaluations', 'kernel_us', 'iterations')
         return dict(zip(keys, (int(v) for v in out)))
 
     def control_solve(self, p):

@@ -41,3 +41,19 @@ extern "C" int fokl_assimilate_rng(uint32_t seed, const uint32_t *draw_ids, int 
                                                  : fokl::asm_normal(seed, draw_ids[e], step, (uint32_t)purpose, (uint32_t)j);
     return FOKL_OK;
 }
+
+// ... and of the calibration of such a system (fokl_calibrate_device.inc; dynamics.calibrate_host draws through this entry):
+// out [n_draws][count], one row per draw id
+extern "C" int fokl_calibrate_rng(uint32_t seed, const uint32_t *draw_ids, int n_draws, uint32_t iteration, int purpose, int count,
+                                  double *out)
+{
+    if (count < 0 || n_draws < 0 || (n_draws > 0 && !draw_ids) || (count > 0 && n_draws > 0 && !out) ||
+        purpose < fokl::INF_PURPOSE_PARTNER || purpose > fokl::INF_PURPOSE_LAST)
+        return FOKL_ERR_ARG;
+    for (int e = 0; e < n_draws; ++e)
+        for (int j = 0; j < count; ++j)
+            out[(size_t)e * count + j] = purpose == fokl::INF_PURPOSE_JITTER
+                                             ? fokl::cal_normal(seed, draw_ids[e], iteration, (uint32_t)purpose, (uint32_t)j)
+                                             : fokl::cal_uniform(seed, draw_ids[e], iteration, (uint32_t)purpose, (uint32_t)j);
+    return FOKL_OK;
+}

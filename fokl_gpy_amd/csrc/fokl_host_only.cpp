@@ -78,6 +78,15 @@ extern "C" int fokl_assimilate_ensemble(fokl_ctx *, const fokl_system *, const u
 }
 extern "C" int fokl_assimilate_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor does the calibration of such a system (fokl_calibrate_device.inc); its statement is dynamics.calibrate_host, and its
+// random numbers (fokl_calibrate_rng) are host code and present here.
+extern "C" int fokl_calibrate_ensemble(fokl_ctx *, const fokl_system *, const fokl_calibrate_problem *, double *, double *, int32_t *,
+                                       double *, int32_t *, int64_t *, int32_t *, double *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_calibrate_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // Nor does the optimal control of such a system (fokl_control_device.inc); its statement is dynamics.control_host.
 extern "C" int fokl_control_solve(fokl_ctx *, const fokl_system *, const fokl_control_problem *, double *, double *, double *,
                                   int32_t *, int32_t *, int32_t *, int32_t *, double *, int32_t *, double *, double *, double *)

@@ -13,6 +13,9 @@
 // The particle filter over a fitted dynamic system (fokl_assimilate_device.inc) draws from a third family: the same key and
 // counter layout with the fourth counter word 2 (asm_uniform, asm_normal below).
 //
+// The calibration of a fitted dynamic system (fokl_calibrate_device.inc) draws from a fourth family: the same key and
+// counter layout with the fourth counter word 3 (cal_uniform, cal_normal below).
+//
 // Nothing here touches numpy's global stream or the fit's MT19937 machinery.
 #ifndef FOKL_PHILOX_H
 #define FOKL_PHILOX_H
@@ -111,6 +114,24 @@ FOKL_HD double asm_normal(uint32_t seed, uint32_t draw_id, uint32_t step, uint32
 {
     uint32_t w[4];
     philox4x32_10(step, purpose, index, 2u, seed, draw_id, w);
+    return sqrt(-2.0 * log(1.0 - emb_unit(w[0], w[1]))) * cos(6.283185307179586476925 * emb_unit(w[2], w[3]));
+}
+
+// fokl_calibrate_device.inc / dynamics.calibrate: the ensemble sampler over the unknowns of a dynamic system, 128 walkers.
+// key = (seed, posterior draw), counter = (iteration, purpose, index, 3): the fourth word keeps these streams apart from
+// every one above (0, 1 and 2).  The purposes are the ensemble sampler's (INF_PURPOSE_*): u1, u2, u3 with index = walker
+// 0 .. 127, and the jump move's normal of coordinate i of walker w with index 128 i + w.
+FOKL_HD double cal_uniform(uint32_t seed, uint32_t draw_id, uint32_t iteration, uint32_t purpose, uint32_t index)
+{
+    uint32_t w[4];
+    philox4x32_10(iteration, purpose, index, 3u, seed, draw_id, w);
+    return emb_unit(w[0], w[1]);
+}
+
+FOKL_HD double cal_normal(uint32_t seed, uint32_t draw_id, uint32_t iteration, uint32_t purpose, uint32_t index)
+{
+    uint32_t w[4];
+    philox4x32_10(iteration, purpose, index, 3u, seed, draw_id, w);
     return sqrt(-2.0 * log(1.0 - emb_unit(w[0], w[1]))) * cos(6.283185307179586476925 * emb_unit(w[2], w[3]));
 }
 

@@ -144,6 +144,57 @@ Pooling over the draws at observation k: draw e weighs exp(log_evidence[e, k]) n
 are -inf); ``mean`` is the weighted mean of ``draw_mean``, ``sd`` the root of the weighted within-draw variance plus
 the weighted squared distance of ``draw_mean`` to ``mean``.
 
+``calibrate(models, states, inputs, ..., unknown=['y0:c', 'k'], observe, data, ...)`` answers what comes before filtering and
+control: a run of the plant was measured; which initial state and which constant operating inputs produced it?  One
+affine-invariant ensemble sampler (``infer.py``'s: stretch moves, a differential-evolution jump every few iterations,
+counter-based Philox numbers) of W = 128 walkers over the d unknowns per posterior draw, every draw at once on the device, so
+the answer carries the model's own uncertainty.  ``calibrate_host`` is its statement in numpy, not a fallback.
+
+  unknowns        ``'y0:<state>'`` is that state's initial value, its box the state's box; any other name is a parameter: an
+                  input column that is neither a state nor a key of ``forcing`` (``control``'s rule for ``controls``),
+                  constant over the run and per walker.  It passes through ``_prepare`` as a placeholder forcing column;
+                  ``norm_param[n]`` is the unknown forcing input n reads, -1 for a real forcing column.  A parameter's box
+                  is the intersection of the training ranges of the columns that read it; ``unknown_bounds`` may narrow a
+                  box and may not leave it.  1 <= d <= 16.  theta is in true scale throughout
+  trajectory      for draw e and walker theta: ``simulate``'s, operation for operation, with the draw's coefficients, y0
+                  overwritten in the unknown states, and every parameter held at its value: the normalised value of a
+                  parameter is clamp((theta - lo_n) / span_n) per reading column n, exactly as a forcing value.  The
+                  factors that read a parameter are formed once per trajectory, those of a real forcing column once per
+                  step
+  target          ss = 0; over the observed points in ascending order (point 0 may be observed) and the observed columns in
+                  ascending order, where ``data`` is not NaN: r = data - y; ss = ss + hp_o (r r), hp_o = 0.5 / obs_sd_o^2
+                  formed once; pp = 0; for i = 0 .. d - 1: dl = theta_i - mean_i; pp = pp + prec_i (dl dl), prec_i =
+                  1 / sd_i^2 formed once (0: no prior beyond the box); lp = -ss - 0.5 pp.  Outside the open box
+                  lo < theta < hi lp = -inf and nothing is integrated.  Only + - * /, ceil and comparisons: lp is the
+                  device's bit for bit.  ``saturated``: a clamp or the slope rule acted somewhere along the trajectory
+  starts          ``optimize.start_points(128, lo, hi)``, the same for every draw, or user ``starts`` [128, d] strictly
+                  inside the box
+  iteration t     t = 0, 1, ... (burn-in included) updates half 0 (walkers 0 .. 63), then half 1 (64 .. 127); a moving
+                  walker w of half hf reads the OTHER half as it stands at that moment (half 1 sees half 0 already moved).
+                  With the uniforms u1, u2, u3 of walker w at iteration t:
+    stretch       j = 64 (1 - hf) + floor(64 u1); z = (1 + u2)^2 / 2; y = x_j + z (x_w - x_j);
+                  log_ratio = (d - 1) log z + lp(y) - lp(x_w)
+    jump          when jump_every > 0 and t % jump_every == jump_every - 1: a = floor(64 u1),
+                  b = (a + 1 + floor(63 u2)) mod 64, both in the other half; y_i = (x_w,i + (x_a,i - x_b,i)) +
+                  (1e-5 (hi_i - lo_i)) n_i; log_ratio = lp(y) - lp(x_w)
+    acceptance    a proposal outside the box is rejected without an evaluation; otherwise it is accepted iff
+                  log(u3) < log_ratio.  A walker whose lp is NaN is never left and never copied by an accept (both
+                  comparisons are false); ``invalid[e]`` says that a start of draw e had no finite lp, and no other draw
+                  is touched
+  random numbers  Philox 4x32-10, key (seed, the draw's row of ``betas``), counter (t, purpose, index, 3); purposes 0, 1, 2
+                  are u1, u2, u3 with index = walker 0 .. 127, purpose 3 the jitter normal n_i (Box-Muller) with index
+                  128 i + w; the host reads them through ``_capi.calibrate_rng``
+  kept            row r is the state after both halves of iteration burnin + r thin, r < ceil(draws_kept / thin); per
+                  walker and half of the ``draws_kept`` post-burn-in iterations (the first draws_kept // 2, then the rest)
+                  the sum and the sum of squares of theta_i - (lo_i + hi_i) / 2 in iteration order (split R-hat over 256
+                  chains); per walker the accepted stretch and jump moves; per draw the trajectories integrated
+
+No transcendental enters a stretch proposal or lp; log z, log u3 and the jump's normal pass through log / cos and agree
+between the device and this host to the two maths libraries' last bits, which can flip an acceptance: compare flags, and
+states where the flags agree.  Counter-based numbers make draw e alone the draw e of the full run, and a thin = 3 run's rows
+every third row of the thin = 1 run, bit for bit.  LDS bytes of the kernel: (1 + factors + normalised states + 7 d) x 64 x
+8 + coefficients x 8, at most 144 KB (``calibrate_lds_bytes``).
+
 ``control(models, states, inputs, controls=[...], ..., targets, limits, move_weight, ...)`` answers what such a system is
 fitted for: which inputs, held piecewise constant over the coming horizon, make the states do what is wanted -- one bounded
 least-squares solve per posterior draw and start, every solve at once on the device, so the answer comes with its
@@ -1213,20 +1264,15 @@ def _per(name, values, count, what):
     return out
 
 
-def _prepare_assimilate(models, states, inputs, forcing=None, y0=None, t=None, draws=None, bounds=None, observe=None, data=None,
-                        obs_points=None, every=None, obs_sd=None, process_sd=None, y0_sd=None, resample_below=0.5, seed=0,
-                        keep=None):
-    """``_prepare`` and what the filter adds; touches no device."""
-    if keep not in (None, 'particles'):
-        raise ValueError("keep must be None or 'particles'")
-    p = _prepare(models, states, inputs, forcing, y0, t, draws, bounds, False, None, lds_per_member=False)
-    K, E, P = p['K'], p['E'], p['n_steps'] + 1
+def _prepare_observations(states, P, observe, data, obs_points, every, obs_sd):
+    """The checks of ``observe``, ``data``, ``obs_points`` / ``every`` and ``obs_sd`` that ``assimilate`` and ``calibrate``
+    share -> (names, points, data, obs_sd)."""
     names = [str(name) for name in (observe if observe is not None else [])]
     if not names:
         raise ValueError("observe must name at least one measured state")
     for name in names:
-        if name not in p['states']:
-            raise ValueError(f"observe: '{name}' is not a state ({p['states']})")
+        if name not in states:
+            raise ValueError(f"observe: '{name}' is not a state ({states})")
     if len(set(names)) != len(names):
         raise ValueError(f"observe names a state twice: {names}")
     if (obs_points is None) == (every is None):
@@ -1256,6 +1302,18 @@ def _prepare_assimilate(models, states, inputs, forcing=None, y0=None, t=None, d
     obs_sd = _per('obs_sd', obs_sd if obs_sd is not None else [], len(names), 'observed state')
     if not np.all(np.isfinite(obs_sd) & (obs_sd > 0)):
         raise ValueError(f"obs_sd must be positive and finite, got {obs_sd.tolist()}")
+    return names, points, data, obs_sd
+
+
+def _prepare_assimilate(models, states, inputs, forcing=None, y0=None, t=None, draws=None, bounds=None, observe=None, data=None,
+                        obs_points=None, every=None, obs_sd=None, process_sd=None, y0_sd=None, resample_below=0.5, seed=0,
+                        keep=None):
+    """``_prepare`` and what the filter adds; touches no device."""
+    if keep not in (None, 'particles'):
+        raise ValueError("keep must be None or 'particles'")
+    p = _prepare(models, states, inputs, forcing, y0, t, draws, bounds, False, None, lds_per_member=False)
+    K, E, P = p['K'], p['E'], p['n_steps'] + 1
+    names, points, data, obs_sd = _prepare_observations(p['states'], P, observe, data, obs_points, every, obs_sd)
     process_sd = _per('process_sd', 0.0 if process_sd is None else process_sd, K, 'state')
     if not np.all(np.isfinite(process_sd) & (process_sd >= 0)):
         raise ValueError(f"process_sd must be non-negative and finite, got {process_sd.tolist()}")
@@ -1487,6 +1545,30 @@ def _named(name, given, states, what, default):
     return out
 
 
+def _column_box(p, readers, name, given, option, what):
+    """(lo, hi) of an input column the caller chooses (a control, a calibrated parameter): the intersection of the training
+    ranges of the normalised inputs ``readers`` that read it, or ``given[name]`` inside that range (``option`` names the
+    argument, ``what`` the column's role in the messages)."""
+    range_lo, range_hi = np.max(p['norm_lo'][readers]), np.min(p['norm_hi'][readers])
+    if name in given:
+        pair = np.asarray(given[name], dtype=np.float64)
+        if pair.shape != (2,) or not np.isfinite(pair).all():
+            raise ValueError(f"{option}['{name}'] must be two finite numbers (lo, hi) in true scale")
+        lo, hi = pair
+        if not lo < hi:
+            raise ValueError(f"{option}['{name}'] is empty (lower {lo}, upper {hi})")
+        for n in readers:
+            if (lo - p['norm_lo'][n]) / p['norm_span'][n] < -1e-12 or (hi - p['norm_lo'][n]) / p['norm_span'][n] > 1 + 1e-12:
+                raise ValueError(f"{option}['{name}'] reaches outside the training range [{range_lo}, {range_hi}] "
+                                 f"of the columns that read it: the models are not extrapolated")
+    else:
+        lo, hi = range_lo, range_hi
+        if not lo < hi:
+            raise ValueError(f"{what} '{name}': its box is empty, the training ranges of the columns that read it have "
+                             f"no interval in common")
+    return float(lo), float(hi)
+
+
 def _prepare_control(models, states, inputs, controls, forcing, y0, t, draws, bounds, segments, control_bounds, targets,
                      weights, terminal, limits, limit_weight, move_weight, previous, init, starts, max_iter, tol, keep):
     """``_prepare`` with the controls as forcing columns, and what the solver adds; touches no device."""
@@ -1555,24 +1637,7 @@ def _prepare_control(models, states, inputs, controls, forcing, y0, t, draws, bo
             raise ValueError(f"control_bounds: '{name}' is not a control ({controls})")
     lo, hi = np.empty(nc), np.empty(nc)
     for c, name in enumerate(controls):
-        readers = np.flatnonzero(norm_control == c)
-        range_lo, range_hi = np.max(p['norm_lo'][readers]), np.min(p['norm_hi'][readers])
-        if name in given:
-            pair = np.asarray(given[name], dtype=np.float64)
-            if pair.shape != (2,) or not np.isfinite(pair).all():
-                raise ValueError(f"control_bounds['{name}'] must be two finite numbers (lo, hi) in true scale")
-            lo[c], hi[c] = pair
-            if not lo[c] < hi[c]:
-                raise ValueError(f"control_bounds['{name}'] is empty (lower {lo[c]}, upper {hi[c]})")
-            for n in readers:
-                if (lo[c] - p['norm_lo'][n]) / p['norm_span'][n] < -1e-12 or (hi[c] - p['norm_lo'][n]) / p['norm_span'][n] > 1 + 1e-12:
-                    raise ValueError(f"control_bounds['{name}'] reaches outside the training range [{range_lo}, {range_hi}] "
-                                     f"of the columns that read it: the models are not extrapolated")
-        else:
-            lo[c], hi[c] = range_lo, range_hi
-            if not lo[c] < hi[c]:
-                raise ValueError(f"control '{name}': its box is empty, the training ranges of the columns that read it have "
-                                 f"no interval in common")
+        lo[c], hi[c] = _column_box(p, np.flatnonzero(norm_control == c), name, given, 'control_bounds', 'control')
     width = hi - lo
 
     # ---- the cost ----
@@ -2598,3 +2663,369 @@ def control_cvar_host(models, states, inputs, controls=None, forcing=None, y0=No
 
 control_cvar.__doc__ += _CONTROL_CVAR_SIGNATURE
 control_cvar_host.__doc__ += _CONTROL_CVAR_SIGNATURE
+
+
+# ---------------------------------------------------------------------------------------------------------
+# calibrate: an ensemble sampler over initial states and constant parameters, per posterior draw (module docstring)
+# ---------------------------------------------------------------------------------------------------------
+
+WALKERS = _capi.CALIBRATE_WALKERS
+HALF_WALKERS = WALKERS // 2
+MAX_UNKNOWN = _capi.CALIBRATE_MAX_UNKNOWN
+JITTER = 1e-5
+_KEEP_CALIBRATE = ('x', 'trajectories')
+
+
+def calibrate_lds_bytes(n_factors, n_norm_state, n_coef, d):
+    """LDS bytes of a draw's wavefront: slot 0, the factors and the normalised states as [item][lane], 7 d rows (both
+    halves' positions, the proposal, two halves x (sum, sum of squares)), and the draw's coefficients once."""
+    return (1 + n_factors + n_norm_state + 7 * d) * LANES * 8 + n_coef * 8
+
+
+def _prepare_calibrate(models, states, inputs, forcing=None, y0=None, t=None, draws=None, bounds=None, unknown=None, observe=None,
+                       data=None, obs_points=None, every=None, obs_sd=None, prior=None, unknown_bounds=None, starts=None,
+                       burnin=300, draws_kept=200, thin=10, jump_every=8, seed=0, keep='x'):
+    """``_prepare`` with the parameters as placeholder forcing columns, and what the sampler adds; touches no device."""
+    wanted = {keep} if isinstance(keep, str) else set(keep or ())
+    if not wanted <= set(_KEEP_CALIBRATE):
+        raise ValueError("keep must be None, 'x', 'trajectories' or a list of the two")
+    if unknown is None or isinstance(unknown, str):
+        unknown = [unknown] if unknown is not None else []
+    unknown = [str(name) for name in unknown]
+    d = len(unknown)
+    if d < 1 or d > MAX_UNKNOWN:
+        raise ValueError(f"unknown must list 1 to {MAX_UNKNOWN} unknowns ('y0:<state>' or a parameter's name), got {d}")
+    for name in unknown:
+        if unknown.count(name) > 1:
+            raise ValueError(f"unknown names '{name}' twice")
+    forcing = {str(key): values for key, values in dict(forcing or {}).items()}
+    state_names = [str(name) for name in states]
+    parameters = []
+    for name in unknown:
+        if name.startswith('y0:'):
+            if name[3:] not in state_names:
+                raise ValueError(f"unknown: '{name}' names no state ({state_names})")
+            continue
+        if name in state_names:
+            raise ValueError(f"unknown: '{name}' is a state (its initial value is 'y0:{name}')")
+        if name in forcing:
+            raise ValueError(f"unknown: '{name}' is a forcing key")
+        parameters.append(name)
+    start, stop, h = (float(v) for v in t)
+    if not (np.isfinite([start, stop, h]).all() and h > 0):
+        raise ValueError("t = (start, stop, h) needs finite numbers and h > 0")
+    n_steps = max(len(np.arange(start, stop + h, h)) - 1, 0)
+    placeholder = np.zeros(n_steps)
+    p = _prepare(models, states, inputs, {**forcing, **{name: placeholder for name in parameters}}, y0, t, draws, bounds, False,
+                 None, lds_per_member=False)
+    K, E, P = p['K'], p['E'], p['n_steps'] + 1
+    states = p['states']
+    names, points, data, obs_sd = _prepare_observations(states, P, observe, data, obs_points, every, obs_sd)
+
+    # ---- the unknowns: their sources and the open box ----
+    unknown_src = np.empty(d, dtype=np.int32)
+    for i, name in enumerate(unknown):
+        if name.startswith('y0:'):
+            unknown_src[i] = states.index(name[3:])
+        else:
+            if name not in p['forcing_cols']:
+                raise ValueError(f"unknown: no model reads '{name}' (no term of any model has an order on it)")
+            unknown_src[i] = -(p['forcing_cols'].index(name) + 1)
+    norm_param = np.full(p['n_norm_forcing'], -1, dtype=np.int32)
+    for n in range(p['n_norm_forcing']):
+        hit = np.flatnonzero(unknown_src == p['norm_src'][n])
+        if hit.size:
+            norm_param[n] = hit[0]
+    given = {str(key): value for key, value in dict(unknown_bounds or {}).items()}
+    for name in given:
+        if name not in unknown:
+            raise ValueError(f"unknown_bounds: '{name}' is not an unknown ({unknown})")
+    lo, hi = np.empty(d), np.empty(d)
+    for i, name in enumerate(unknown):
+        if unknown_src[i] < 0:
+            lo[i], hi[i] = _column_box(p, np.flatnonzero(norm_param == i), name, given, 'unknown_bounds', 'parameter')
+            continue
+        box_lo, box_hi = p['box'][unknown_src[i]]
+        if name in given:
+            pair = np.asarray(given[name], dtype=np.float64)
+            if pair.shape != (2,) or not np.isfinite(pair).all():
+                raise ValueError(f"unknown_bounds['{name}'] must be two finite numbers (lo, hi) in true scale")
+            lo[i], hi[i] = pair
+            if not lo[i] < hi[i]:
+                raise ValueError(f"unknown_bounds['{name}'] is empty (lower {lo[i]}, upper {hi[i]})")
+            if lo[i] < box_lo or hi[i] > box_hi:
+                raise ValueError(f"unknown_bounds['{name}'] reaches outside the box [{box_lo}, {box_hi}] of the state")
+        else:
+            lo[i], hi[i] = box_lo, box_hi
+        if not np.isfinite([lo[i], hi[i]]).all():
+            raise ValueError(f"unknown '{name}': its box [{lo[i]}, {hi[i]}] is not finite (no model reads the state): give "
+                             f"bounds or unknown_bounds")
+
+    # ---- the prior, the starts, the sampler's settings ----
+    prior_mean, prior_prec = np.zeros(d), np.zeros(d)
+    for key, pair in dict(prior or {}).items():
+        if str(key) not in unknown:
+            raise ValueError(f"prior: '{key}' is not an unknown ({unknown})")
+        if np.ndim(pair) != 1 or len(pair) != 2:
+            raise ValueError(f"prior['{key}'] must be (mean, sd) with a finite mean and sd > 0 (true scale)")
+        mu, sd = float(pair[0]), float(pair[1])
+        if not (np.isfinite(mu) and sd > 0 and np.isfinite(sd)):
+            raise ValueError(f"prior['{key}'] must be (mean, sd) with a finite mean and sd > 0 (true scale)")
+        i = unknown.index(str(key))
+        prior_mean[i], prior_prec[i] = mu, 1.0 / (sd * sd)
+    if starts is None:
+        x0 = start_points(WALKERS, lo, hi)
+    else:
+        x0 = np.array(starts, dtype=np.float64)
+        if x0.shape != (WALKERS, d) or not np.isfinite(x0).all():
+            raise ValueError(f"starts must be finite numbers [{WALKERS}, {d}] (true scale)")
+    if not np.all((x0 > lo) & (x0 < hi)):
+        raise ValueError("every start must lie strictly inside the box")
+    for name, value, least in (('burnin', burnin, 0), ('draws_kept', draws_kept, 1), ('thin', thin, 1),
+                               ('jump_every', jump_every, 0)):
+        if isinstance(value, str) or np.ndim(value) != 0 or int(value) != value or int(value) < least:
+            raise ValueError(f"{name} must be an integer >= {least}")
+    if int(seed) != seed:
+        raise ValueError("seed must be an integer")
+    n_factors, n_norm_state, n_coef = p['fac_norm'].shape[0], p['norm_src'].shape[0] - p['n_norm_forcing'], p['coef'].shape[0]
+    lds_bytes = calibrate_lds_bytes(n_factors, n_norm_state, n_coef, d)
+    if lds_bytes > LDS_BUDGET:
+        raise ValueError(f"the problem needs {lds_bytes} bytes of LDS ((1 + {n_factors} factors + {n_norm_state} normalised "
+                         f"states + 7 x {d} unknowns) x {LANES} x 8 + {n_coef} coefficients x 8), a wavefront has {LDS_BUDGET}")
+    obs_row = np.full(P, -1, dtype=np.int32)
+    obs_row[points] = np.arange(points.shape[0], dtype=np.int32)
+    n_rows = np.atleast_2d(np.asarray(_model_fields(models[0], 0)['betas'])).shape[0]
+    p.update(d=d, unknown=unknown, unknown_src=unknown_src, norm_param=norm_param, lo=lo, hi=hi, prior_mean=prior_mean,
+             prior_prec=prior_prec, starts=np.ascontiguousarray(x0), obs_names=names,
+             obs_state=np.array([states.index(name) for name in names], dtype=np.int32), obs_sd=obs_sd,
+             obs_hp=0.5 / (obs_sd * obs_sd), obs_points=points.astype(np.int64), obs_row=obs_row,
+             data=np.ascontiguousarray(data), burnin=int(burnin), draws_kept=int(draws_kept), thin=int(thin),
+             jump_every=int(jump_every), seed=int(seed) & 0xFFFFFFFF, draw_ids=_draw_ids(n_rows, draws, E),
+             want_rows='x' in wanted, want_trajectories='trajectories' in wanted, lds_bytes=lds_bytes)
+    return p
+
+
+def calibrate_target(p, theta, trajectories=False):
+    """lp [E, n] and saturated [E, n] at theta [E, n, d] (true scale, inside the box): the module docstring's trajectory and
+    sums in its order, vectorised over (draw, walker).  ``trajectories``: also the points [E, n, K, P]."""
+    K, E, S, n, d = p['K'], p['E'], p['n_steps'], theta.shape[1], p['d']
+    M = E * n
+    wide = dict(p, coef=np.repeat(p['coef'], n, axis=1))              # member e * n + i is walker i of draw e
+    th = np.ascontiguousarray(theta.reshape(M, d).T)
+    y = np.repeat(p['y0'], n, axis=1)
+    for i in range(d):
+        if p['unknown_src'][i] >= 0:
+            y[p['unknown_src'][i]] = th[i]
+    fac = np.ones((1 + p['fac_norm'].shape[0], M))
+    xn = np.zeros((p['norm_src'].shape[0], M))
+    acted = np.zeros(M, dtype=bool)
+    constant = [f for f in range(p['n_forcing_factors']) if p['norm_param'][p['fac_norm'][f]] >= 0]
+    stepwise = [f for f in range(p['n_forcing_factors']) if p['norm_param'][p['fac_norm'][f]] < 0]
+    for f in constant:                                                # once per trajectory
+        m = p['fac_norm'][f]
+        xn[m], clamp = _clamped((th[p['norm_param'][m]] - p['norm_lo'][m]) / p['norm_span'][m])
+        acted |= clamp
+        _factor_values(p, fac, xn, f, f + 1)
+    points = np.empty((K, S + 1, M)) if trajectories else None
+    ss = np.zeros(M)
+
+    def observe(point, ss):
+        r = p['obs_row'][point]
+        if r < 0:
+            return ss
+        for o in range(p['obs_state'].shape[0]):
+            if not np.isnan(p['data'][r, o]):
+                res = p['data'][r, o] - y[p['obs_state'][o]]
+                ss = ss + p['obs_hp'][o] * (res * res)
+        return ss
+
+    if trajectories:
+        points[:, 0] = y
+    ss = observe(0, ss)
+    for s in range(S):
+        for f in stepwise:                                            # once per step
+            m = p['fac_norm'][f]
+            x = np.full(M, p['forcing'][s, -(p['norm_src'][m] + 1)])
+            xn[m], clamp = _clamped((x - p['norm_lo'][m]) / p['norm_span'][m])
+            acted |= clamp
+            _factor_values(p, fac, xn, f, f + 1)
+        y, stages_acted = _stages(wide, fac, xn, y)
+        acted |= stages_acted
+        if trajectories:
+            points[:, s + 1] = y
+        ss = observe(s + 1, ss)
+    pp = np.zeros(M)
+    for i in range(d):
+        dl = th[i] - p['prior_mean'][i]
+        pp = pp + p['prior_prec'][i] * (dl * dl)
+    lp = (-ss - 0.5 * pp).reshape(E, n)
+    if trajectories:
+        return lp, acted.reshape(E, n), np.ascontiguousarray(points.reshape(K, S + 1, E, n).transpose(2, 3, 0, 1))
+    return lp, acted.reshape(E, n)
+
+
+def _run_calibrate_host(p):
+    """-> (x [E, kept, 128, d], lp [E, kept, 128], saturated [E, kept, 128] (the three None without rows), sums [E, 128, 2, 2,
+    d], accepted [E, 128, 2], evaluations [E], invalid [E], trajectories [E, 128, K, P] or None): what
+    ``DeviceContext.calibrate`` returns."""
+    E, d, W, H = p['E'], p['d'], WALKERS, HALF_WALKERS
+    lo, hi, ids, seed, thin, rows = p['lo'], p['hi'], p['draw_ids'], p['seed'], p['thin'], p['want_rows']
+    burnin, draws, jump_every = p['burnin'], p['draws_kept'], p['jump_every']
+    x = np.broadcast_to(p['starts'], (E, W, d)).copy()
+    with np.errstate(all='ignore'):
+        lp, sat = calibrate_target(p, x)
+    invalid = ~np.isfinite(lp).all(axis=1)
+    iterations, first_half, kept = burnin + draws, draws // 2, -(-draws // thin)
+    x_rows = np.empty((E, kept, W, d)) if rows else None
+    lp_rows = np.empty((E, kept, W)) if rows else None
+    sat_rows = np.empty((E, kept, W), dtype=bool) if rows else None
+    sums = np.zeros((E, W, 2, 2, d))
+    acc = np.zeros((E, W, 2, d))
+    accepted = np.zeros((E, W, 2), dtype=np.int32)
+    evaluations = np.full(E, W, dtype=np.int64)
+    shift = 0.5 * (lo + hi)
+    rng = lambda t, purpose, count: _capi.calibrate_rng(seed, ids, t, purpose, count)
+    for t in range(iterations):
+        jump = jump_every > 0 and t % jump_every == jump_every - 1
+        u1, u2, u3 = (rng(t, purpose, W) for purpose in (_capi.INFER_U1, _capi.INFER_U2, _capi.INFER_U3))
+        if jump:
+            normal = rng(t, _capi.INFER_JITTER, W * d).reshape(E, d, W)
+        for half in (0, 1):
+            mv = slice(H * half, H * half + H)
+            other = H * (1 - half)
+            xw = x[:, mv]
+            take = lambda j: np.take_along_axis(x, j[..., np.newaxis], axis=1)
+            with np.errstate(all='ignore'):
+                if not jump:
+                    j = other + np.minimum((64.0 * u1[:, mv]).astype(np.int64), H - 1)
+                    z = ((1.0 + u2[:, mv]) * (1.0 + u2[:, mv])) * 0.5
+                    xj = take(j)
+                    prop = xj + z[..., np.newaxis] * (xw - xj)
+                    log_z = (d - 1.0) * np.log(z)
+                else:
+                    a = np.minimum((64.0 * u1[:, mv]).astype(np.int64), H - 1)
+                    b = (a + 1 + np.minimum((63.0 * u2[:, mv]).astype(np.int64), H - 2)) % H
+                    n = normal[:, :, mv].transpose(0, 2, 1)
+                    prop = (xw + (take(other + a) - take(other + b))) + (JITTER * (hi - lo)) * n
+                    log_z = 0.0
+                inside = ((prop > lo) & (prop < hi)).all(axis=-1)
+                if inside.any():
+                    lp_y, sat_y = calibrate_target(p, np.where(inside[..., np.newaxis], prop, xw))
+                    accept = inside & (np.log(u3[:, mv]) < (log_z + lp_y) - lp[:, mv])
+                    x[:, mv] = np.where(accept[..., np.newaxis], prop, xw)
+                    lp[:, mv] = np.where(accept, lp_y, lp[:, mv])
+                    sat[:, mv] = np.where(accept, sat_y, sat[:, mv])
+                    accepted[:, mv, 1 if jump else 0] += accept
+            evaluations += inside.sum(axis=1)
+        if t < burnin:
+            continue
+        r = t - burnin
+        if r == first_half and first_half > 0:
+            sums[:, :, 0] = acc
+            acc[:] = 0.0
+        c = x - shift
+        acc[:, :, 0] = acc[:, :, 0] + c
+        acc[:, :, 1] = acc[:, :, 1] + c * c
+        if rows and r % thin == 0:
+            x_rows[:, r // thin], lp_rows[:, r // thin], sat_rows[:, r // thin] = x, lp, sat
+    sums[:, :, 1] = acc
+    trajectories = None
+    if p['want_trajectories']:
+        with np.errstate(all='ignore'):
+            trajectories = calibrate_target(p, x, trajectories=True)[2]
+    return x_rows, lp_rows, sat_rows, sums, accepted, evaluations, invalid, trajectories
+
+
+def _assemble_calibrate(p, x, lp, saturated, sums, accepted, evaluations, invalid, trajectories):
+    """A SimulateResult from the sampler's outputs: the kept rows, pooled summaries, per-draw diagnostics."""
+    from .infer import split_rhat
+    E, d = p['E'], p['d']
+    iterations = p['burnin'] + p['draws_kept']
+    n_jump = sum(1 for t in range(iterations) if p['jump_every'] > 0 and t % p['jump_every'] == p['jump_every'] - 1)
+    tried = np.array([iterations - n_jump, n_jump], dtype=np.float64) * WALKERS
+    with np.errstate(divide='ignore', invalid='ignore'):
+        accept = accepted.sum(axis=1) / tried
+    if p['draws_kept'] >= 2:
+        rhat, mean_e, sd_e = split_rhat(sums, p['draws_kept'], 0.5 * (p['lo'] + p['hi']))
+    else:                                                             # one kept iteration: no first half, no R-hat
+        mean_e = sums[:, :, :, 0].sum(axis=(1, 2)) / float(WALKERS)
+        sd_e = np.sqrt(np.maximum(sums[:, :, :, 1].sum(axis=(1, 2)) / float(WALKERS) - mean_e * mean_e, 0.0))
+        rhat, mean_e = np.full((E, d), np.nan), mean_e + 0.5 * (p['lo'] + p['hi'])
+    total = sums[:, :, :, 0].sum(axis=(0, 1, 2)) / float(E * WALKERS * p['draws_kept'])
+    res = SimulateResult(unknown=list(p['unknown']), draws=E, walkers=WALKERS, accept=accept, rhat=rhat,
+                         rhat_max=float(np.nanmax(rhat)) if np.isfinite(rhat).any() else float('nan'),
+                         evals=np.asarray(evaluations, dtype=np.int64), invalid=np.asarray(invalid, dtype=bool),
+                         mean_per_draw=mean_e, sd_per_draw=sd_e, draw_ids=p['draw_ids'].astype(np.int64),
+                         mean=total + 0.5 * (p['lo'] + p['hi']), x=None, lp=None, draw=None, saturated=None, cov=None,
+                         quantiles=None, box=np.stack([p['lo'], p['hi']], axis=1), states=list(p['states']), t=p['T'])
+    if x is not None:
+        rows = x.reshape(-1, d)
+        n = rows.shape[0]
+        cut = bounds_cut(n)
+        srt = np.sort(rows, axis=0)
+        res.update(x=rows, lp=lp.reshape(-1), saturated=np.asarray(saturated, dtype=bool).reshape(-1),
+                   draw=np.repeat(p['draw_ids'].astype(np.int64), x.shape[1] * WALKERS), mean=rows.mean(axis=0),
+                   cov=np.atleast_2d(np.cov(rows, rowvar=False)) if n > 1 else None,
+                   quantiles=np.stack([srt[min(cut, n - 1)], srt[max(n - cut, 0)]], axis=1))
+    if trajectories is not None:
+        flat = trajectories.reshape(E * WALKERS, p['K'], -1)
+        n = flat.shape[0]
+        cut = bounds_cut(n)
+        srt = np.sort(flat, axis=0)
+        res.update(trajectories=trajectories, fit_mean=np.mean(flat, axis=0), fit_bounds=np.stack([srt[cut], srt[n - cut]], axis=-1))
+    return res
+
+
+_CALIBRATE_SIGNATURE = """
+    models, states, inputs, forcing, y0, t, draws, bounds : as for ``simulate``; the entries of ``y0`` at unknown states are
+                  placeholders (any finite number).  Draw e's random numbers are keyed by the row of ``betas`` it selects,
+                  so a subset of the draws reproduces the full run's
+    unknown     : 1 to 16 names: 'y0:<state>' is that state's initial value, any other name a parameter -- an input column
+                  that is neither a state nor a key of ``forcing``, held constant over the run
+    observe, data, obs_points, every, obs_sd : the measurements, as for ``assimilate`` (NaN = missing; point 0 may be observed
+                  through ``obs_points``)
+    prior       : {unknown: (mean, sd)} independent normal priors in true scale; none: flat inside the box
+    unknown_bounds : {unknown: (lo, hi)} in true scale, inside the default box: for a parameter the intersection of the
+                  training ranges of the columns that read it, for 'y0:<state>' the state's box
+    starts      : None -- ``optimize.start_points(128, lo, hi)`` -- or [128, d] in true scale, strictly inside the box
+    burnin, draws_kept, thin : iterations dropped, iterations after them, every ``thin``-th of those is kept
+    jump_every  : a jump move instead of the stretch move at every ``jump_every``-th iteration; 0: never
+    seed        : of the counter-based random numbers; numpy's stream is not touched
+    keep        : 'x' the kept rows, 'trajectories' the final ensemble's trajectories, a list of the two, or None (sums,
+                  acceptance and R-hat only)
+
+    Returns a ``SimulateResult`` (a dict with attribute access): x [E * kept * 128, d] in true scale (draw-major, then kept
+    row, then walker), lp, draw (the row of ``betas`` a sample came from) and saturated (a clamp or the slope rule acted
+    along the sample's trajectory) [E * kept * 128]; pooled over the draws mean [d], cov [d, d], quantiles [d, 2] =
+    (sorted[cut], sorted[n - cut]) with ``evaluate``'s cut = floor(0.025 n) + 1; per draw accept [E, 2] (stretch, jump
+    acceptance rates), rhat [E, d] (split R-hat over the 128 walkers' halves) and rhat_max, evals [E] trajectories
+    integrated, invalid [E] (a start had no finite lp), mean_per_draw, sd_per_draw [E, d]; with 'trajectories' trajectories
+    [E, 128, n_states, P] of the final ensemble, fit_mean [n_states, P] and fit_bounds [n_states, P, 2] over (draw, walker).
+    Without 'x' the row fields are None and mean comes from the sums."""
+
+
+def calibrate(models, states, inputs, forcing=None, y0=None, t=None, draws=None, bounds=None, unknown=None, observe=None,
+              data=None, obs_points=None, every=None, obs_sd=None, prior=None, unknown_bounds=None, starts=None, burnin=300,
+              draws_kept=200, thin=10, jump_every=8, seed=0, keep='x', device=None):
+    """Which initial state and which constant inputs produced a measured run?  One ensemble of 128 walkers per posterior
+    draw, on the device (module docstring).
+
+    device      : device index (default: the process's device, as for ``fit``), a backend or a ``_capi.DeviceContext``"""
+    p = _prepare_calibrate(models, states, inputs, forcing, y0, t, draws, bounds, unknown, observe, data, obs_points, every,
+                           obs_sd, prior, unknown_bounds, starts, burnin, draws_kept, thin, jump_every, seed, keep)
+    ctx = _device_context(device)
+    return _assemble_calibrate(p, *ctx.calibrate(p))
+
+
+def calibrate_host(models, states, inputs, forcing=None, y0=None, t=None, draws=None, bounds=None, unknown=None, observe=None,
+                   data=None, obs_points=None, every=None, obs_sd=None, prior=None, unknown_bounds=None, starts=None,
+                   burnin=300, draws_kept=200, thin=10, jump_every=8, seed=0, keep='x'):
+    """``calibrate`` in numpy on this host, vectorised over (draws, the 64 walkers of the moving half): the statement the
+    kernel is tested against (module docstring), not a fallback.  Same arguments, same result fields."""
+    p = _prepare_calibrate(models, states, inputs, forcing, y0, t, draws, bounds, unknown, observe, data, obs_points, every,
+                           obs_sd, prior, unknown_bounds, starts, burnin, draws_kept, thin, jump_every, seed, keep)
+    return _assemble_calibrate(p, *_run_calibrate_host(p))
+
+
+calibrate.__doc__ += _CALIBRATE_SIGNATURE
+calibrate_host.__doc__ += _CALIBRATE_SIGNATURE

@@ -39,6 +39,7 @@
  *   fokl_simulate_adaptive / fokl_simulate_adaptive_report
  *   fokl_simulate_stiff / fokl_simulate_stiff_report
  *   fokl_assimilate_ensemble / fokl_assimilate_report / fokl_assimilate_rng
+ *   fokl_calibrate_ensemble / fokl_calibrate_report / fokl_calibrate_rng
  *   fokl_control_solve / fokl_control_report
  *   fokl_control_pooled_solve / fokl_control_pooled_report
  *   fokl_control_cvar_solve / fokl_control_cvar_report
@@ -1123,8 +1124,8 @@ int fokl_infer_rng(uint32_t seed, uint32_t draw_id, uint32_t iteration, int purp
 
 /*
  * A system of fitted models as dynamics._prepare assembles it: what fokl_simulate_ensemble, fokl_simulate_adaptive,
- * fokl_simulate_stiff, fokl_assimilate_ensemble, fokl_control_solve, fokl_control_pooled_solve and fokl_control_cvar_solve
- * integrate.  Host memory, row-major; the call reads it and keeps no pointer.
+ * fokl_simulate_stiff, fokl_assimilate_ensemble, fokl_calibrate_ensemble, fokl_control_solve, fokl_control_pooled_solve and
+ * fokl_control_cvar_solve integrate.  Host memory, row-major; the call reads it and keeps no pointer.
  */
 typedef struct fokl_system {
     int n_members;          /* members = posterior draws / initial states (the control and filter calls: n_draws) */
@@ -1153,7 +1154,7 @@ typedef struct fokl_system {
     const int32_t *entries, *entry_begin, *entry_count, *constant;
     int n_coef;
     /* The one layout that differs between the calls: the simulate calls take coef as [n_coef][n_members] (a coefficient's
-     * members are contiguous), the assimilate and control calls as [n_draws][n_coef] (a draw's coefficients are) */
+     * members are contiguous), the assimilate, calibrate and control calls as [n_draws][n_coef] (a draw's coefficients are) */
     const double *coef;
     const double *y0;  /* [n_states, n_members] */
     const double *box; /* [n_states, 2] true scale: lower < upper */
@@ -1324,6 +1325,83 @@ int fokl_assimilate_report(const fokl_ctx *ctx, int64_t *out);
  */
 int fokl_assimilate_rng(uint32_t seed, const uint32_t *draw_ids, int n_draws, uint32_t step, int purpose, int count,
                         double *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Calibration of such a system against measurements (csrc/fokl_calibrate_device.inc; dynamics.py)           */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_CALIBRATE_REPORT_LEN 8
+#define FOKL_CALIBRATE_WALKERS 128
+#define FOKL_CALIBRATE_MAX_UNKNOWN 16
+
+/*
+ * What fokl_calibrate_ensemble samples over a fokl_system: d unknowns (initial values of states and constant parameters
+ * that enter the models as forcing columns), the measurements and the sampler's settings.  Host memory, row-major.
+ */
+typedef struct fokl_calibrate_problem {
+    int n_unknown;               /* d, 1 .. FOKL_CALIBRATE_MAX_UNKNOWN */
+    const int32_t *unknown_src;  /* [d]: >= 0 the state whose initial value unknown i is, -(c + 1) the parameter in forcing
+                                  * column c (that column of `forcing` is a placeholder and is never read) */
+    const int32_t *norm_param;   /* [n_norm_forcing]: the unknown a forcing input reads, -1: a column of `forcing` */
+    const double *lo, *hi;       /* [d] the open box, true scale */
+    const double *prior_mean, *prior_prec; /* [d] true scale; precision 0: no prior beyond the box */
+    const double *starts;        /* [128, d] strictly inside the box */
+    int n_observed;
+    const int32_t *obs_state;    /* [n_observed] the state every measured column reads (distinct) */
+    const double *obs_hp;        /* [n_observed] 0.5 / obs_sd^2 > 0 */
+    int n_obs;
+    const int32_t *obs_row;      /* [n_steps + 1]: the row of `data` measured at a point, -1 none; rows appear as 0, 1, ... */
+    const double *data;          /* [n_obs, n_observed] true scale, NaN = missing */
+    const uint32_t *draw_ids;    /* [n_draws]: the second key word of a draw's random numbers */
+    int burnin, draws_kept, thin, jump_every;
+    uint32_t seed;
+} fokl_calibrate_problem;
+
+/*
+ * One affine-invariant ensemble of 128 walkers over the unknowns per posterior draw: which initial states and constant
+ * parameters produced the measured run.  A walker's log posterior is -(sum over the present measurements of
+ * obs_hp (data - y)^2) - 0.5 sum_i prec_i (theta_i - mean_i)^2 along fokl_simulate_ensemble's trajectory with the draw's
+ * coefficients (`system` as fokl_assimilate_ensemble takes it: coef [n_draws, n_coef]); the arithmetic and the sampler are
+ * stated by dynamics.calibrate_host (the module docstring of fokl_gpy_amd/dynamics.py): lp is the host's bit for bit.
+ *   x_out [n_draws, kept, 128, d], lp_out [n_draws, kept, 128], saturated_out [n_draws, kept, 128] int32 (1: a clamp or the
+ *          slope rule acted along the sample's trajectory), kept = ceil(draws_kept / thin); all three or none NULL
+ *   sums_out [n_draws, 128, 2, 2, d]: per walker and half of the post-burn-in iterations the sum and the sum of squares of
+ *          theta_i - (lo_i + hi_i) / 2; accept_out [n_draws, 128, 2] int32 accepted stretch and jump moves;
+ *          evals_out [n_draws] int64 trajectories integrated; invalid_out [n_draws] int32: 1 where a start had no finite lp
+ *   trajectories [n_draws, 128, n_states, n_steps + 1] of the final ensemble, or NULL
+ * One wavefront per workgroup and draw; lane l is walker l while half 0 moves and walker 64 + l while half 1 moves, so every
+ * half step integrates 64 trajectories on 64 lanes.  LDS bytes = (1 + n_factors + n_norm - n_norm_forcing + 7 d) x 64 x 8 +
+ * n_coef x 8, at most 144 KB.  No scratch, no atomics: the same arguments give the same bits, and a draw alone equals that
+ * draw of a larger call.  The iterations are cut into launches of max(1, FOKL_CALIBRATE_STEPS_PER_LAUNCH / (2 n_steps))
+ * iterations (environment, default 65 536 steps): the cut changes no bit.
+ * Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched): what fokl_assimilate_ensemble refuses of a
+ * system and of observations, d outside 1 .. 16, an unknown outside the states / the forcing columns, one that no model
+ * reads, one named twice, a norm_param that disagrees with unknown_src, an empty or non-finite box, a start that is not
+ * strictly inside it, a prior precision that is negative or not finite, thin < 1, draws_kept < 1, burnin < 0 or
+ * jump_every < 0 (or above 2^30), the LDS bytes above the budget, outputs beyond the device's free memory
+ * (FOKL_CALIBRATE_FREE_BYTES caps what counts as free).  Kernel time: FOKL_K_INTEGRATE.  Blocking.
+ */
+int fokl_calibrate_ensemble(fokl_ctx *ctx, const fokl_system *system, const fokl_calibrate_problem *problem, double *x_out,
+                            double *lp_out, int32_t *saturated_out, double *sums_out, int32_t *accept_out, int64_t *evals_out,
+                            int32_t *invalid_out, double *trajectories);
+
+/*
+ * The last fokl_calibrate_ensemble call on `ctx`, out [FOKL_CALIBRATE_REPORT_LEN] (host values, no launch); zeros after a
+ * call that was refused or failed:
+ *   out[0]  NS: the kernel instance (states)     out[1]  draws = workgroups = wavefronts     out[2]  dynamic LDS bytes
+ *   out[3]  launches (the replay of the final ensemble included)     out[4]  iterations per launch
+ *   out[5]  trajectories integrated, all draws     out[6]  kernel microseconds     out[7]  iterations
+ */
+int fokl_calibrate_report(const fokl_ctx *ctx, int64_t *out);
+
+/*
+ * out[e * count + j], e < n_draws, j < count: the number the sampler draws for draw id draw_ids[e] at `iteration` for
+ * `purpose` and index j.  Philox 4x32-10, key (seed, draw id), counter (iteration, purpose, index, 3).  Purposes 0, 1, 2:
+ * the uniforms u1, u2, u3 of walker `index` (0 .. 127); 3: the jump move's normal of coordinate i of walker w, index
+ * 128 i + w.  Host code, no device.  FOKL_ERR_ARG for another purpose.
+ */
+int fokl_calibrate_rng(uint32_t seed, const uint32_t *draw_ids, int n_draws, uint32_t iteration, int purpose, int count,
+                       double *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* Optimal control of such a system, per posterior draw (csrc/fokl_control_device.inc; dynamics.py)          */
