@@ -216,6 +216,8 @@ SIGNATURES = {
     'fokl_simulate_stiff': (c_int, [c_vp, c_vp, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                     c_vp]),
     'fokl_simulate_stiff_report': (c_int, [c_vp, c_vp]),
+    'fokl_steady_states': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_steady_report': (c_int, [c_vp, c_vp]),
     'fokl_assimilate_ensemble': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, ctypes.c_uint32,
                                          c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_assimilate_report': (c_int, [c_vp, c_vp]),
@@ -2495,6 +2497,38 @@ class DeviceContext:
         self._ck(self._lib.fokl_simulate_stiff_report(self._h, _ptr(out)))
         keys = ('NS', 'members', 'workgroups', 'launches', 'steps_per_launch', 'lds_bytes', 'min_halvings', 'max_halvings',
                 'steps', 'rejected', 'swaps')
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def steady_states(self, p):
+        """fokl_steady_states for a system prepared by ``dynamics._prepare_steady`` -> (y [Q, E S, n_states], residual [Q, E S],
+        iterations [Q, E S] int32, status [Q, E S] int8, halvings [Q, E S] int32, on_wall [Q, E S, n_states] bool, jacobian
+        [Q, E S, n_states, n_states]); member e S + s is draw e from start s, so a draw's coefficients are repeated per start.
+        Needs no uploaded dataset and leaves one alone."""
+        K, E, S, Q = int(p['K']), int(p['E']), int(p['S']), int(p['Q'])
+        M = E * S
+        starts, ftol = _f64(p['starts']), _f64(p['ftol'])
+        if starts.shape != (S, K) or ftol.shape != (K,) or int(p['n_steps']) != Q:
+            raise ValueError("steady_states: array shapes disagree")
+        members = dict(p, E=M, coef=np.repeat(_f64(p['coef']), S, axis=1), y0=np.tile(starts.T, (1, E)))
+        system, held = _system_struct(members, 'steady_states', coef_by_draw=False)
+        y, residual = np.empty((Q, M, K), dtype=np.float64), np.empty((Q, M), dtype=np.float64)
+        iterations, halvings = np.empty((Q, M), dtype=np.int32), np.empty((Q, M), dtype=np.int32)
+        status, on_wall = np.empty((Q, M), dtype=np.int8), np.empty((Q, M, K), dtype=np.uint8)
+        jacobian = np.empty((Q, M, K, K), dtype=np.float64)
+        self._ck(self._lib.fokl_steady_states(self._h, ctypes.byref(system), _ptr(ftol), int(p['max_iter']), int(p['max_halvings']),
+                                              _ptr(y), _ptr(residual), _ptr(iterations), _ptr(status), _ptr(halvings),
+                                              _ptr(on_wall), _ptr(jacobian)))
+        del held
+        return y, residual, iterations, status, halvings, on_wall.astype(bool), jacobian
+
+    def steady_report(self):
+        """What the last ``steady_states`` on this context ran (fokl_steady_report; host values, no launch): ``NS`` (the kernel
+        instance = states), ``members`` (draws x starts), ``workgroups`` (= wavefronts = ceil(members / 64) x points),
+        ``lds_bytes``, ``launches``, ``points`` and the totals ``iterations`` and ``halvings`` over the members.  Zeros after a
+        refused call."""
+        out = np.zeros(8, dtype=np.int64)
+        self._ck(self._lib.fokl_steady_report(self._h, _ptr(out)))
+        keys = ('NS', 'members', 'workgroups', 'lds_bytes', 'launches', 'points', 'iterations', 'halvings')
         return dict(zip(keys, (int(v) for v in out)))
 
     def assimilate_ensemble(self, p):

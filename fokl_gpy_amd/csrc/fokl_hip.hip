@@ -102,6 +102,7 @@ struct fokl_ctx {
     int64_t simulate_report[FOKL_SIMULATE_REPORT_LEN] = {};       // ... and the last fokl_simulate_ensemble call
     int64_t simulate_adaptive_report[FOKL_SIMULATE_ADAPTIVE_REPORT_LEN] = {};     // ... and the last fokl_simulate_adaptive call
     int64_t simulate_stiff_report[FOKL_SIMULATE_STIFF_REPORT_LEN] = {};   // ... and the last fokl_simulate_stiff call
+    int64_t steady_report[FOKL_STEADY_REPORT_LEN] = {};           // ... and the last fokl_steady_states call
     int64_t assimilate_report[FOKL_ASSIMILATE_REPORT_LEN] = {};   // ... and the last fokl_assimilate_ensemble call
     int64_t calibrate_report[FOKL_CALIBRATE_REPORT_LEN] = {};     // ... and the last fokl_calibrate_ensemble call
     int64_t control_report[FOKL_CONTROL_REPORT_LEN] = {};         // ... and the last fokl_control_solve call
@@ -1819,6 +1820,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_simulate_device.inc"
 #include "fokl_simulate_adaptive_device.inc"
 #include "fokl_simulate_stiff_device.inc"
+#include "fokl_steady_device.inc"
 #include "fokl_assimilate_device.inc"
 #include "fokl_calibrate_device.inc"
 #include "fokl_control_device.inc"

@@ -68,6 +68,14 @@ extern "C" int fokl_simulate_stiff(fokl_ctx *, const fokl_system *, int, double,
 }
 extern "C" int fokl_simulate_stiff_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor the steady states of such a system (fokl_steady_device.inc); their statement is dynamics.steady_states_host.
+extern "C" int fokl_steady_states(fokl_ctx *, const fokl_system *, const double *, int, int, double *, double *, int32_t *, int8_t *,
+                                  int32_t *, uint8_t *, double *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_steady_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // Nor does the particle filter over such a system (fokl_assimilate_device.inc); its statement is dynamics.assimilate_host,
 // and its random numbers (fokl_assimilate_rng) are host code and present here.
 extern "C" int fokl_assimilate_ensemble(fokl_ctx *, const fokl_system *, const uint32_t *, int, const int32_t *, const double *, int,

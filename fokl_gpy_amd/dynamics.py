@@ -106,6 +106,40 @@ FULL = 2^K; the forcing factors of row s are formed once as above (the system is
 A zero pivot is not special: the division gives inf or NaN, the trial fails, and at k == K the member takes the NaN as a NaN
 coefficient's member does above.  Three evaluations of F, one Jacobian and one factorisation per trial.
 
+``steady_states(models, states, inputs, at={...}, starts=9, ...)`` says where the same system comes to rest: a damped Newton
+iteration on F(y) = 0 per member (operating point q, posterior draw e, start s), every member at once on the device.  F and J
+are the stage and the Jacobian of ``simulate_stiff`` above with a step of 1, clamps and slope rule included, so a rest point
+found here is a rest point of ``simulate``.  ``steady_states_host`` is its statement in numpy; only + - * /, ceil, comparisons
+and integer bookkeeping, in fixed orders, so the device agrees bit for bit in every per-member field.
+
+  operating point ``at`` gives every input column that is not a state, a number or [Q] values in true scale; row q is a
+                  forcing row: its factors are formed once, as ``simulate`` forms them
+  starts          the same S for every (q, e).  An integer S: start 0 is lo + (hi - lo) 0.5, start i >= 1 is
+                  lo_j + u_ij (hi_j - lo_j) with u_ij the radical inverse of i in base 2, 3, 5, 7, 11, 13, 17, 19 for state
+                  j = 0 .. 7 (r = 0, f = 1; while i > 0: f = f / base, r = r + f (i mod base), i = i div base)
+  ratio(F)        r = 0.0; per state j in order: q = |F_j| / ftol_j; r = q where q > r or q != q (a NaN is taken and kept)
+
+Per member, from y = its start, iterations = halvings = 0:
+
+  1. evaluate     (F, J) = (F0, J) of ``simulate_stiff`` at y; r = ratio(F).  ``residual`` = r, ``jacobian`` = J and
+                  ``on_wall`` = held (3.) are those of the last evaluation
+  2. end          status 3 unless r < inf (r is NaN or inf); else status 0 if r <= 1; else status 1 if iterations == max_iter
+  3. held         row k is held if F_k == 0 and J[k][d] == 0 for every d: a state on the wall with its slope switched off, or
+                  a model that is flat there
+  4. step         W[r][d] = -J[r][d]; W[k][k] = 1.0 on held rows; delta = solve(F) by ``stiff_lu`` / ``stiff_solve`` of W;
+                  delta_k = 0.0 on held rows (a held state does not move)
+  5. line search  for b = 0 .. max_halvings: y_t = y + delta 2^-b (an exact scaling), per state lo where y_t < lo and hi where
+                  y_t > hi (a NaN stays); F_t = F(y_t) by the value operations alone; r_t = ratio(F_t); the first b with
+                  r_t < r is taken (a NaN compares false) and halvings += b.  No b: status 2 (stalled), y stays,
+                  halvings += max_halvings + 1
+  6. accept       y = y_t; iterations += 1; go to 1
+
+Both loops have fixed bounds (max_iter + 1 evaluations, max_halvings + 1 trial points), so a member ends for any input.  A
+singular W gives inf or NaN in delta, every trial point fails its test and the member stalls; a NaN coefficient ends the
+member at its first evaluation with status 3; neither touches another member.  What follows from the per-member fields is
+numpy on the host, the same code after both functions: the eigenvalues of the free sub-block of J (``np.linalg.eigvals``),
+``stable``, the distinct roots of every (q, e) and the summaries over the draws (``steady_states``'s docstring).
+
 ``assimilate(models, states, inputs, ..., observe, data, ...)`` filters the same system against measurements: a bootstrap
 particle filter of 64 particles per posterior draw, every draw at once on the device.  It returns the filtered states
 (per draw and pooled over the draws), and per draw the log marginal likelihood of the measurements, which normalised
@@ -1199,6 +1233,317 @@ def simulate_stiff_host(models, states, inputs, forcing=None, y0=None, t=None, d
 
 simulate_stiff.__doc__ += _SIGNATURE_STIFF
 simulate_stiff_host.__doc__ += _SIGNATURE_STIFF
+
+
+# ---------------------------------------------------------------------------------------------------------
+# steady_states: a damped Newton iteration on simulate_stiff's F and J per (operating point, draw, start) (module docstring)
+# ---------------------------------------------------------------------------------------------------------
+
+STEADY_MAX_ITER = 200
+STEADY_MAX_HALVINGS = 30
+_HALTON_BASES = (2, 3, 5, 7, 11, 13, 17, 19)
+
+
+class SteadyResult(SimulateResult):
+    """``steady_states``'s result: a dict whose entries are also attributes."""
+
+
+def _radical_inverse(i, base):
+    r, f = 0.0, 1.0
+    while i > 0:
+        f = f / base
+        r = r + f * (i % base)
+        i //= base
+    return r
+
+
+def steady_starts(S, box):
+    """The S starts of an integer ``starts`` in the box [K, 2]: its centre, then Halton points (module docstring) -> [S, K]."""
+    lo, width = box[:, 0], box[:, 1] - box[:, 0]
+    out = np.empty((S, box.shape[0]))
+    out[0] = lo + width * 0.5
+    for i in range(1, S):
+        out[i] = lo + np.array([_radical_inverse(i, _HALTON_BASES[j]) for j in range(box.shape[0])]) * width
+    return out
+
+
+def _whole(name, value, low, high):
+    if isinstance(value, (bool, np.bool_)) or np.ndim(value) != 0 or not isinstance(value, (int, np.integer, float, np.floating)) \
+            or int(value) != value or not low <= int(value) <= high:
+        raise ValueError(f"{name} must be an integer in {low}..{high}, got {value!r}")
+    return int(value)
+
+
+def _prepare_steady(models, states, inputs, at, draws, bounds, starts, ftol, time_scale, max_iter, max_halvings, merge_tol, keep):
+    """``_prepare`` with the operating points as forcing rows, and what the iteration adds; touches no device."""
+    if keep not in (None, 'jacobian'):
+        raise ValueError("keep must be None or 'jacobian'")
+    names = [str(name) for name in states]
+    at = {str(name): np.asarray(values, dtype=np.float64) for name, values in dict(at or {}).items()}
+    both = [name for name in at if name in names]
+    if both:
+        raise ValueError(f"at: {both} are states: a state is solved for, not given")
+    read = []
+    for columns in inputs:
+        read += [str(name) for name in columns if str(name) not in names and str(name) not in read]
+    missing = [name for name in read if name not in at]
+    if missing:
+        raise ValueError(f"at: the input columns {missing} are no states and at gives no value for them (at holds {list(at)})")
+    lengths = {}
+    for name, values in at.items():
+        if values.ndim > 1 or (values.ndim == 1 and values.shape[0] == 0):
+            raise ValueError(f"at['{name}'] must be a number or [Q] values, Q >= 1")
+        if values.ndim == 1:
+            lengths[name] = values.shape[0]
+    if len(set(lengths.values())) > 1:
+        raise ValueError(f"at: the arrays have unequal lengths {lengths}: every array holds one value per operating point")
+    Q = next(iter(lengths.values()), 1)
+    forcing = {name: np.array(np.broadcast_to(values, (Q,))) for name, values in at.items()}
+    for name, values in forcing.items():
+        if not np.isfinite(values).all():
+            raise ValueError(f"at['{name}'] must hold finite numbers")
+    max_iter = _whole('max_iter', max_iter, 1, STEADY_MAX_ITER)
+    max_halvings = _whole('max_halvings', max_halvings, 0, STEADY_MAX_HALVINGS)
+    try:
+        time_scale, merge_tol = float(time_scale), float(merge_tol)
+    except (TypeError, ValueError):
+        time_scale, merge_tol = np.nan, np.nan
+    if not (np.isfinite(time_scale) and time_scale > 0):
+        raise ValueError(f"time_scale must be positive and finite, got {time_scale}")
+    if not (np.isfinite(merge_tol) and merge_tol >= 0):
+        raise ValueError(f"merge_tol must be finite and not negative, got {merge_tol}")
+
+    p = _prepare(models, names, inputs, forcing, np.zeros(len(names)), (0.0, float(Q), 1.0), draws, bounds, False, None)
+    K, box = p['K'], p['box']
+    n_factors, n_norm_state, n_coef = p['fac_norm'].shape[0], p['norm_src'].shape[0] - p['n_norm_forcing'], p['coef'].shape[0]
+    need = stiff_lds_rows(n_factors, n_norm_state, n_coef)
+    if need > LDS_ROWS:
+        raise ValueError(f"the system needs {need} values per member in LDS (2 x (1 + {n_factors} factors + {n_norm_state} "
+                         f"normalised states) + {n_coef} coefficients: simulate's and one set of tangent rows), a wavefront's "
+                         f"{LDS_BUDGET // 1024} KB hold {LDS_ROWS}")
+    width = box[:, 1] - box[:, 0]
+    unbounded = [name for k, name in enumerate(names) if not np.isfinite(width[k])]
+    if isinstance(starts, (bool, np.bool_)) or (np.ndim(starts) == 0 and not isinstance(starts, (int, np.integer))):
+        raise ValueError(f"starts must be an integer S >= 1 or an array [S, {K}], got {starts!r}")
+    if np.ndim(starts) == 0:
+        if int(starts) < 1:
+            raise ValueError(f"starts must be an integer S >= 1 or an array [S, {K}], got {starts!r}")
+        if unbounded:
+            raise ValueError(f"states {unbounded}: the box is unbounded, so the centre and the Halton points of starts={starts} "
+                             f"do not exist: pass starts as an array [S, {K}] (or bounds)")
+        starts = steady_starts(int(starts), box)
+    else:
+        starts = np.array(starts, dtype=np.float64)
+        if starts.ndim != 2 or starts.shape[0] == 0 or starts.shape[1] != K:
+            raise ValueError(f"starts as an array must be [S, {K}] (true scale), S >= 1, got shape {starts.shape}")
+        if np.isnan(starts).any():
+            raise ValueError("starts holds NaN")
+        outside = (starts < box[:, 0]) | (starts > box[:, 1])
+        if outside.any():
+            s, k = np.argwhere(outside)[0]
+            raise ValueError(f"starts[{s}]: state '{names[k]}' = {starts[s, k]} lies outside its box [{box[k, 0]}, {box[k, 1]}]")
+    if ftol is None:
+        if unbounded:
+            raise ValueError(f"states {unbounded}: the box is unbounded, so the default ftol (1e-9 x the box's width / time_scale) "
+                             f"does not exist: pass ftol")
+        ftol = 1e-9 * width / time_scale
+    else:
+        ftol = _per('ftol', ftol, K, 'state')
+    if not np.all(np.isfinite(ftol) & (ftol > 0)):
+        raise ValueError(f"ftol must be positive and finite for every state, got {np.asarray(ftol).tolist()}")
+    p.update(Q=Q, S=starts.shape[0], starts=np.ascontiguousarray(starts), ftol=np.ascontiguousarray(ftol, dtype=np.float64),
+             max_iter=max_iter, max_halvings=max_halvings, merge_tol=merge_tol, want_jacobian=keep == 'jacobian', lds_rows=need,
+             at={name: forcing[name] for name in forcing})
+    return p
+
+
+def _steady_ratio(F, ftol):
+    r = np.zeros(F.shape[1])
+    for j in range(F.shape[0]):
+        q = _abs(F[j]) / ftol[j]
+        r = np.where((q > r) | (q != q), q, r)
+    return r
+
+
+def _run_steady_host(p):
+    """-> (y [Q, M, K], residual [Q, M], iterations [Q, M] int32, status [Q, M] int8, halvings [Q, M] int32, on_wall [Q, M, K]
+    bool, jacobian [Q, M, K, K]) with M = E S, member e S + s of a point being draw e from start s."""
+    K, E, S, Q = p['K'], p['E'], p['S'], p['Q']
+    top, limit, ftol, box = p['max_halvings'], p['max_iter'], p['ftol'], p['box']
+    N = Q * E * S
+    point, draw, start = np.repeat(np.arange(Q), E * S), np.tile(np.repeat(np.arange(E), S), Q), np.tile(np.arange(S), Q * E)
+    coef = p['coef'][:, draw]
+    y = np.ascontiguousarray(p['starts'].T[:, start])
+    n_norms = p['norm_src'].shape[0]
+    fac, xn = np.ones((1 + p['fac_norm'].shape[0], N)), np.zeros((n_norms, N))
+    for n in range(p['n_norm_forcing']):
+        xn[n], _ = _clamped((p['forcing'][point, -(p['norm_src'][n] + 1)] - p['norm_lo'][n]) / p['norm_span'][n])
+    _factor_values(p, fac, xn, 0, p['n_forcing_factors'])
+    status = np.full(N, -1, dtype=np.int8)
+    iterations, halvings = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.int32)
+    residual, jacobian, on_wall = np.full(N, np.nan), np.full((N, K, K), np.nan), np.zeros((N, K), dtype=bool)
+    with np.errstate(all='ignore'):
+        for it in range(limit + 1):
+            live = np.flatnonzero(status < 0)                         # the members still iterating: a mask
+            if live.size == 0:
+                break
+            q = dict(p, coef=coef[:, live], h=1.0)
+            qfac, at = np.ascontiguousarray(fac[:, live]), y[:, live]
+            F, J, _ = _stage_dual(q, qfac, np.zeros((n_norms, live.size)), at)
+            r = _steady_ratio(F, ftol)
+            held = (F == 0) & ~np.any(J != 0, axis=1)
+            residual[live], jacobian[live], on_wall[live] = r, J.transpose(2, 0, 1), held.T
+            ended = np.where(~(r < np.inf), 3, np.where(r <= 1, 0, 1 if it == limit else -1)).astype(np.int8)
+            status[live] = ended
+            go = ended < 0
+            if not go.any():
+                continue
+            live, F, J, r, held, at, qfac = live[go], F[:, go], J[:, :, go], r[go], held[:, go], at[:, go], qfac[:, go]
+            W = -J
+            for k in range(K):
+                W[k, k] = np.where(held[k], 1.0, W[k, k])
+            LU, rows, _ = stiff_lu(W)
+            delta = np.where(held, 0.0, stiff_solve(LU, rows, F))
+            found = np.zeros(live.size, dtype=bool)
+            for b in range(top + 1):
+                todo = np.flatnonzero(~found)
+                if todo.size == 0:
+                    break
+                yt = at[:, todo] + delta[:, todo] * np.ldexp(1.0, -b)
+                yt = np.where(yt < box[:, :1], box[:, :1], yt)
+                yt = np.where(yt > box[:, 1:], box[:, 1:], yt)
+                Ft, _ = _stage(dict(p, coef=coef[:, live[todo]], h=1.0), np.ascontiguousarray(qfac[:, todo]),
+                               np.zeros((n_norms, todo.size)), yt)
+                ok = _steady_ratio(Ft, ftol) < r[todo]
+                took = todo[ok]
+                y[:, live[took]] = yt[:, ok]
+                halvings[live[took]] += b
+                found[took] = True
+            status[live[~found]] = 2
+            halvings[live[~found]] += top + 1
+            iterations[live[found]] += 1
+    M = E * S
+    return (np.ascontiguousarray(y.T).reshape(Q, M, K), residual.reshape(Q, M), iterations.reshape(Q, M), status.reshape(Q, M),
+            halvings.reshape(Q, M), on_wall.reshape(Q, M, K), jacobian.reshape(Q, M, K, K))
+
+
+def _steady_roots(y, converged, stable, tol):
+    """The distinct roots among the converged members of every (point, draw): y [N, S, K], converged and stable [N, S] ->
+    (roots [N, S, K], root_stable [N, S], n_roots [N]; the first n_roots[i] entries of row i count).  In lexicographic order a
+    member joins the first root it is within ``tol`` of in every state, or founds one; all N rows at once."""
+    N, S, K = y.shape
+    order = np.lexsort(tuple(y[..., k] for k in range(K - 1, -1, -1)) + (~converged,), axis=-1)
+    rows = np.arange(N)
+    roots, flags, count = np.full((N, S, K), np.nan), np.zeros((N, S), dtype=bool), np.zeros(N, dtype=np.int64)
+    for i in range(S):
+        at = order[:, i]
+        point, joined = y[rows, at], ~converged[rows, at]
+        for r in range(int(count.max(initial=0))):
+            with np.errstate(invalid='ignore'):
+                joined |= (r < count) & np.all(np.abs(point - roots[:, r]) <= tol, axis=1)
+        new = np.flatnonzero(~joined)
+        roots[new, count[new]], flags[new, count[new]] = point[new], stable[new, at[new]]
+        count[new] += 1
+    return roots, flags, count
+
+
+def _assemble_steady(p, y, residual, iterations, status, halvings, on_wall, jacobian):
+    """The result from the per-member fields, the same numpy after the device and the host statement."""
+    K, E, S, Q = p['K'], p['E'], p['S'], p['Q']
+    shape = (Q, E, S)
+    y, residual, iterations = y.reshape(shape + (K,)), residual.reshape(shape), iterations.reshape(shape).astype(np.int32)
+    status, halvings = status.reshape(shape).astype(np.int8), halvings.reshape(shape).astype(np.int32)
+    on_wall, jacobian = on_wall.reshape(shape + (K,)).astype(bool), jacobian.reshape(shape + (K, K))
+    converged = status == 0
+    eig = np.full(shape + (K,), np.nan + 0j, dtype=np.complex128)
+    flat_wall, flat_jac, flat_eig = on_wall.reshape(-1, K), jacobian.reshape(-1, K, K), eig.reshape(-1, K)
+    patterns, which = np.unique(flat_wall, axis=0, return_inverse=True)
+    which = which.reshape(-1)
+    negative = np.ones(flat_wall.shape[0], dtype=bool)                # no free state: nothing can grow
+    for i, held in enumerate(patterns):                               # one batched call per set of held states
+        free, rows = np.flatnonzero(~held), np.flatnonzero(which == i)
+        if free.size == 0:
+            continue
+        blocks = flat_jac[rows][:, free][:, :, free]
+        finite = np.isfinite(blocks).all(axis=(1, 2))
+        values = np.full((rows.size, free.size), np.nan + 0j, dtype=np.complex128)
+        if finite.any():
+            values[finite] = np.linalg.eigvals(blocks[finite])
+        flat_eig[np.ix_(rows, free)] = values
+        negative[rows] = np.all(values.real < 0, axis=1)
+    stable = converged & negative.reshape(shape)
+    width = p['box'][:, 1] - p['box'][:, 0]
+    tol = p['merge_tol'] * np.where(np.isfinite(width), width, 1.0)
+    found, flags, count = _steady_roots(y.reshape(Q * E, S, K), converged.reshape(Q * E, S), stable.reshape(Q * E, S), tol)
+    roots = [[found[q * E + e, :count[q * E + e]] for e in range(E)] for q in range(Q)]
+    root_stable = [[flags[q * E + e, :count[q * E + e]] for e in range(E)] for q in range(Q)]
+    n_roots = count.reshape(Q, E)
+    n_stable = np.sum(flags, axis=1).reshape(Q, E)
+    most = int(n_roots.max())
+    multiplicity = np.stack([np.mean(n_roots == k, axis=1) for k in range(most + 1)], axis=1)
+    unique_mean, unique_bounds = np.full((Q, K), np.nan), np.full((Q, K, 2), np.nan)
+    for q in range(Q):
+        single = [roots[q][e][0] for e in range(E) if n_roots[q, e] == 1]
+        if len(single) >= 2:
+            srt, cut = np.sort(np.array(single), axis=0), bounds_cut(len(single))
+            unique_mean[q] = np.mean(np.array(single), axis=0)
+            unique_bounds[q] = np.stack([srt[cut], srt[len(single) - cut]], axis=-1)
+    res = SteadyResult(states=list(p['states']), at=p['at'], starts=p['starts'], ftol=p['ftol'], y=y, residual=residual,
+                       iterations=iterations, status=status, halvings=halvings, on_wall=on_wall, stable=stable, roots=roots,
+                       root_stable=root_stable, n_roots=n_roots, n_stable=n_stable, multiplicity=multiplicity,
+                       unique_fraction=np.mean(n_roots == 1, axis=1), unique_mean=unique_mean, unique_bounds=unique_bounds)
+    if p['want_jacobian']:
+        res.update(jacobian=jacobian, eig=eig)
+    return res
+
+
+_STEADY_SIGNATURE = """
+    models, states, inputs, draws, bounds : as ``simulate``'s
+    at          : {name: a number or [Q] values} in true scale, one entry per input column that is not a state; numbers are
+                  shared by the Q >= 1 operating points
+    starts      : an integer S (the centre of the box and S - 1 Halton points inside it; needs a bounded box) or [S, n_states]
+                  in true scale inside the closed box; every (point, draw) iterates from every start
+    ftol        : a number or one per state, default 1e-9 x (box_hi - box_lo) / time_scale: a member has converged where
+                  max_j |F_j| / ftol_j <= 1
+    time_scale  : the time in which a state crosses its box at a slope worth resolving; it only scales the default ftol
+    max_iter    : 1..200 Newton iterations per member;  max_halvings : 0..30 halvings of a step in its line search
+    merge_tol   : converged members of one (point, draw) within merge_tol x (box_hi - box_lo) in every state are one root
+                  (merge_tol itself for a state whose box is unbounded)
+    keep        : 'jacobian' also returns ``jacobian`` and ``eig``
+
+    Returns a ``SteadyResult`` (a dict with attribute access).  Per member (point q, draw e, start s): y [Q, E, S, n], residual
+    [Q, E, S], iterations int32, status int8 (0 converged, 1 iteration limit, 2 stalled, 3 not finite), halvings int32,
+    on_wall [Q, E, S, n] bool (the state was held at the end), stable [Q, E, S] (converged and every eigenvalue of the
+    Jacobian's free sub-block has a negative real part), with keep='jacobian' jacobian [Q, E, S, n, n] and eig [Q, E, S, n]
+    complex (NaN at held states).  Per (point, draw): roots[q][e] [R, n] sorted lexicographically, root_stable[q][e] [R], n_roots
+    and n_stable [Q, E].  Over the draws: multiplicity [Q, Rmax + 1] (the share of draws with k distinct roots),
+    unique_fraction [Q], unique_mean [Q, n] and unique_bounds [Q, n, 2] over the draws with exactly one root (``evaluate``'s order
+    statistics; NaN with fewer than two such draws).  It finds the roots its starts lead to and does not prove that there are no
+    others; a root on a wall is a rest point of the clamped system, not of the models; Newton does not prefer stable roots.
+    Nothing is drawn at random."""
+
+
+def steady_states(models, states, inputs, at=None, draws=None, bounds=None, starts=9, ftol=None, time_scale=1.0, max_iter=50,
+                  max_halvings=8, merge_tol=1e-6, keep=None, device=None):
+    """The rest points of a system of fitted models and their stability, per operating point, posterior draw and start, on the
+    device (module docstring).
+
+    device      : device index (default: the process's device, as for ``fit``), a backend or a ``_capi.DeviceContext``"""
+    p = _prepare_steady(models, states, inputs, at, draws, bounds, starts, ftol, time_scale, max_iter, max_halvings, merge_tol, keep)
+    ctx = _device_context(device)
+    return _assemble_steady(p, *ctx.steady_states(p))
+
+
+def steady_states_host(models, states, inputs, at=None, draws=None, bounds=None, starts=9, ftol=None, time_scale=1.0, max_iter=50,
+                       max_halvings=8, merge_tol=1e-6, keep=None):
+    """``steady_states`` in numpy on this host, vectorised over members with masks: the statement the kernel is tested against
+    (module docstring), not a fallback.  Same arguments, same result fields."""
+    p = _prepare_steady(models, states, inputs, at, draws, bounds, starts, ftol, time_scale, max_iter, max_halvings, merge_tol, keep)
+    return _assemble_steady(p, *_run_steady_host(p))
+
+
+steady_states.__doc__ += _STEADY_SIGNATURE
+steady_states_host.__doc__ += _STEADY_SIGNATURE
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -38,6 +38,7 @@
  *   fokl_simulate_ensemble / fokl_simulate_report
  *   fokl_simulate_adaptive / fokl_simulate_adaptive_report
  *   fokl_simulate_stiff / fokl_simulate_stiff_report
+ *   fokl_steady_states / fokl_steady_report
  *   fokl_assimilate_ensemble / fokl_assimilate_report / fokl_assimilate_rng
  *   fokl_calibrate_ensemble / fokl_calibrate_report / fokl_calibrate_rng
  *   fokl_control_solve / fokl_control_report
@@ -1124,8 +1125,9 @@ int fokl_infer_rng(uint32_t seed, uint32_t draw_id, uint32_t iteration, int purp
 
 /*
  * A system of fitted models as dynamics._prepare assembles it: what fokl_simulate_ensemble, fokl_simulate_adaptive,
- * fokl_simulate_stiff, fokl_assimilate_ensemble, fokl_calibrate_ensemble, fokl_control_solve, fokl_control_pooled_solve and
- * fokl_control_cvar_solve integrate.  Host memory, row-major; the call reads it and keeps no pointer.
+ * fokl_simulate_stiff, fokl_steady_states, fokl_assimilate_ensemble, fokl_calibrate_ensemble, fokl_control_solve,
+ * fokl_control_pooled_solve and fokl_control_cvar_solve integrate (fokl_steady_states: bring to rest).  Host memory, row-major;
+ * the call reads it and keeps no pointer.
  */
 typedef struct fokl_system {
     int n_members;          /* members = posterior draws / initial states (the control and filter calls: n_draws) */
@@ -1263,6 +1265,48 @@ int fokl_simulate_stiff(fokl_ctx *ctx, const fokl_system *system, int cut, doubl
  *   out[10] row exchanges of the accepted steps, all members
  */
 int fokl_simulate_stiff_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Where the same system comes to rest: steady states (csrc/fokl_steady_device.inc; dynamics.py)             */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_STEADY_REPORT_LEN 8
+#define FOKL_STEADY_MAX_ITER 200
+#define FOKL_STEADY_MAX_HALVINGS 30
+
+/*
+ * A damped Newton iteration on F(y) = 0 for every (operating point, member), F and its Jacobian J being fokl_simulate_stiff's
+ * stage with a step of 1 (clamps and slope rule included): W = -J with 1 on the diagonal of a held row (F_k == 0 and row k of
+ * J zero), delta = W^-1 F by the same LU, and the first of y + delta 2^-b, b = 0 .. max_halvings, clipped to the box, that
+ * lowers r = max_j |F_j| / ftol_j.  The arithmetic is stated by dynamics.steady_states_host (the module docstring of
+ * fokl_gpy_amd/dynamics.py): every output equals the host statement's bit for bit.  In `system` n_steps = Q is the number of
+ * operating points and row q of forcing is point q; n_members = draws x starts, member e S + s being draw e from start s, so
+ * coef [n_coef, n_members] repeats a draw's coefficients per start and y0 [n_states, n_members] holds the starts; h is not
+ * used.  Host memory, row-major:
+ *   ftol [n_states]; max_iter in 1 .. 200; max_halvings in 0 .. 30
+ *   y [Q, n_members, n_states]: the final state; residual [Q, n_members]: the final r; iterations, halvings [Q, n_members]
+ *   int32 (halvings: the trial points refused, all iterations); status [Q, n_members] int8: 0 converged (r <= 1), 1 the
+ *   iteration limit, 2 stalled (no trial point lowered r), 3 r not finite; on_wall [Q, n_members, n_states] uint8: the state
+ *   was held at the last evaluation; jacobian [Q, n_members, n_states, n_states] or NULL: J at the final state.
+ * One lane per member, one wavefront per workgroup and operating point, fokl_simulate_stiff's LDS rows and bound; both loops
+ * have the bounds above, and a lane that has ended waits for the slowest lane of its wavefront.  The points are cut into
+ * launches of at most FOKL_STEADY_POINTS_PER_LAUNCH (environment, default 4 096): the cut changes no bit.  No atomics: a
+ * member of a large run equals that member run alone.  Refused (FOKL_ERR_ARG with a text that names the limit, nothing is
+ * launched): what fokl_simulate_stiff refuses of a system, the LDS budget included, no operating point, max_iter or
+ * max_halvings outside their ranges, an ftol that is not positive and finite.  Kernel time: FOKL_K_INTEGRATE.  Blocking.
+ */
+int fokl_steady_states(fokl_ctx *ctx, const fokl_system *system, const double *ftol, int max_iter, int max_halvings, double *y,
+                       double *residual, int32_t *iterations, int8_t *status, int32_t *halvings, uint8_t *on_wall,
+                       double *jacobian);
+
+/*
+ * The last fokl_steady_states call on `ctx`, out [FOKL_STEADY_REPORT_LEN] (host values, no launch); zeros after a call that
+ * was refused or failed:
+ *   out[0]  NS: the kernel instance (states)     out[1]  members     out[2]  workgroups = ceil(members / 64) x points
+ *   out[3]  dynamic LDS bytes     out[4]  launches     out[5]  operating points     out[6]  iterations, all members
+ *   out[7]  halvings, all members
+ */
+int fokl_steady_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* A particle filter of such a system against measurements (csrc/fokl_assimilate_device.inc; dynamics.py)    */
