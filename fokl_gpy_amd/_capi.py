@@ -173,12 +173,15 @@ SIGNATURES = {
     'fokl_spectrum_release': (None, [c_vp, c_vp]),
     'fokl_spectrum_retain': (c_int, [c_vp, c_vp]),
     'fokl_search_model_begin': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
+    'fokl_search_model_request': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
+    'fokl_search_model_abandon': (None, [c_vp, c_vp, c_vp]),
     'fokl_search_model_commit': (c_int, [c_vp, c_vp, c_vp, c_dbl, c_int, c_vp]),
     'fokl_run_create': (c_int, [c_vp, c_vp, c_vp]),
     'fokl_run_set_update': (c_int, [c_vp, c_int, c_int, c_int]),
     'fokl_run_search': (c_int, [c_vp, c_vp]),
     'fokl_run_result': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_run_arrays': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_run_order': (c_int, [c_vp, c_vp, c_int]),
     'fokl_run_error': (ctypes.c_char_p, [c_vp]),
     'fokl_run_destroy': (None, [c_vp]),
     'fokl_search_score': (c_int, [c_vp, c_vp, c_dbl, c_dbl, c_int, c_int, c_vp]),
@@ -1678,6 +1681,8 @@ class _RunParams(ctypes.Structure):
 
 RUN_STATS = ('terms_physical', 'substages', 'forecasts_used', 'forecasts_early', 'resid_matrix_free', 't_resid',
              'phase_prepare', 'phase_model', 'phase_statistics', 'phase_tests', 'phase_wrap_up')
+# fokl_run_order's columns: when (monotonic clock, seconds) each step of a sub-stage's model went out; None: not there
+RUN_ORDER = ('k1_ahead', 'g2_wait_begun', 'g2_arrived', 'chain_submitted', 'orders_placed', 'k3_launched', 'ahead_gram_launched')
 
 
 def backend_ops(backend, kernel_id):
@@ -1744,9 +1749,16 @@ def backend_ops(backend, kernel_id):
     def bic_resid_fetch(_c, dst, _allreduce):
         out(dst, pending.pop('resid'))
 
+    def bic_resid_terms_launch(_c, terms, n_terms, betahat):
+        m = pending['m']
+        pending['resid'] = backend.bic_resid_terms_launch(arr(terms, n_terms * m, ctypes.c_int32, np.int32).reshape(n_terms, m),
+                                                          arr(betahat, n_terms + 1, ctypes.c_double, np.float64))
+
     table = dict(reserve_slots=reserve_slots, build_terms=build_terms, gram=gram, gram_launch=gram_launch,
                  gram_fetch=gram_fetch, bic_resid=bic_resid, bic_resid_launch=bic_resid_launch,
                  bic_resid_fetch=bic_resid_fetch)
+    if hasattr(backend, 'bic_resid_terms_launch'):          # (a stand-in with a matrix-free pass: -> the moments, fetched as above)
+        table['bic_resid_terms_launch'] = bic_resid_terms_launch
     keep = [pending, raised]
     for name, fn in table.items():
         cb = _OPS_TYPES[name](guard(fn))
@@ -1809,7 +1821,11 @@ class NativeRun:
         for size in sizes[:subs.value]:
             per.append(dict(mean_abs=mean_abs[at:at + size].copy(), rel_std=rel_std[at:at + size].copy()))
             at += int(size)
-        return (mtx.astype(np.float64), evs, per, best.value, last.value, dict(zip(RUN_STATS, stats[:len(RUN_STATS)])))
+        st = dict(zip(RUN_STATS, stats[:len(RUN_STATS)]))
+        order = np.full((max(self._lib.fokl_run_order(self._h, None, 0), 1), len(RUN_ORDER)), np.nan)
+        rows = self._lib.fokl_run_order(self._h, _ptr(order), order.shape[0])
+        st['substage_order'] = [{k: (None if np.isnan(v) else float(v)) for k, v in zip(RUN_ORDER, row)} for row in order[:rows]]
+        return (mtx.astype(np.float64), evs, per, best.value, last.value, st)
 
     def close(self):
         if self._h is not None and self._h:

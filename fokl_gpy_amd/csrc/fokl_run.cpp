@@ -213,6 +213,7 @@ struct fokl_run {
     std::vector<double> stat_mean_abs, stat_rel_std;
     std::vector<int32_t> stat_sizes;
     double stats[FOKL_RUN_STATS] = {};
+    std::vector<double> order;                              // [sub-stages][FOKL_RUN_ORDER_STAMPS]: fokl_run_order
     std::string error;
 };
 
@@ -274,6 +275,14 @@ int matrix_free_pay_from(const fokl_backend_ops &ops, const std::vector<int32_t>
 // per fit in t_resid for 1.3 gained in t_eigh.)
 static const bool g_build_at_start = !(std::getenv("FOKL_BUILD_AHEAD_AT") && std::strcmp(std::getenv("FOKL_BUILD_AHEAD_AT"), "model") == 0);
 
+// What the driver does once a model's eigenpairs are there: its chain, the first tests' orders, K3, the coming sub-stage's
+// Gram (default).  FOKL_MODEL_ORDER=k3first puts the K3 launch in front of the orders (the A/B of DESIGN.md 9c).
+static const bool g_k3_before_orders = std::getenv("FOKL_MODEL_ORDER") && std::strcmp(std::getenv("FOKL_MODEL_ORDER"), "k3first") == 0;
+
+// fokl_run_order's columns
+enum OrderStamp { O_K1_AHEAD, O_WAIT_BEGUN, O_G2_ARRIVED, O_CHAIN, O_ORDERS, O_K3, O_AHEAD_GRAM, O_COUNT };
+static_assert(O_COUNT == FOKL_RUN_ORDER_STAMPS, "fokl_run_order: FOKL_RUN_ORDER_STAMPS columns");
+
 // the loop's state
 struct Loop {
     fokl_run *r;
@@ -310,6 +319,7 @@ struct Loop {
     std::vector<Forecast> forecasts;
     std::vector<fokl_outcome *> outcomes, retiring;
     int rc_cb = FOKL_OK;                                    // an error inside a callback of the kill-test loop
+    bool resid_launched = false;                            // a residual pass is on the device, its moments not fetched yet
 
     Loop(fokl_run *run, fokl_search *search) : r(run), s(search), ops(run->ops), prm(run->prm), m(run->prm.m) {}
 
@@ -633,48 +643,71 @@ int Loop::run()
             then_sizes.push_back(p.first);
             then_model.push_back(p.second ? 1 : 0);
         }
+        double stamp[FOKL_RUN_ORDER_STAMPS];
+        for (double &v : stamp) v = NAN;
+        if (guessed) stamp[O_ORDERS] = now_s();
         fokl_spectrum *spectrum = nullptr;
         fokl_tape *tape = nullptr;
-        if ((rc = fokl_search_model_begin(s, cur->data(), A + 1, idx.data(), A, spectral_job.h, then_sizes.data(),
-                                          then_model.data(), (int)then_sizes.size(), &spectrum, &tape)) != FOKL_OK)
+        // the request only: the model's tape (walked from now on), the tapes behind it, G2 submitted or adopted
+        if ((rc = fokl_search_model_request(s, cur->data(), A + 1, idx.data(), A, spectral_job.h, then_sizes.data(),
+                                            then_model.data(), (int)then_sizes.size(), &spectrum, &tape)) != FOKL_OK)
             return rc;
-        // K1 of the coming sub-stage: launched while this thread would only wait for the model's eigenpairs (the model's tape
-        // is on request, its G2 on its way)
+        // K1 of the coming sub-stage: its host work and its device time run under the model's G2, which is waited for only
+        // behind it (the model's tape is on request, its G2 on its way)
         if (g_build_at_start && have_coming && prm.foresight > 0) {
             if ((rc = build_ahead_columns(coming_indvec, &ahead)) != FOKL_OK) {
-                fokl_spectrum_release(s, spectrum);
+                fokl_search_model_abandon(s, spectrum, tape);
                 return rc;
             }
+            stamp[O_K1_AHEAD] = now_s();
         }
         const double *buffer = nullptr;
         int p1_check = 0;
+        stamp[O_WAIT_BEGUN] = now_s();
         if ((rc = fokl_spectrum_wait(s, spectrum, &buffer, &p1_check)) != FOKL_OK) {
-            fokl_spectrum_release(s, spectrum);
+            fokl_search_model_abandon(s, spectrum, tape);
             return rc;
         }
-        const double *betahat = buffer + 2 * (size_t)A;
+        stamp[O_G2_ARRIVED] = now_s();
+        // The eigenpairs are there.  The chain first: it needs nothing of what follows (spectrum, tape, dtd, vm), and every
+        // microsecond in front of it is one the statistics arrive later.  Then the first tests' orders (the walker starts on
+        // their tapes; the coming model's tape lies behind all of them), then the device: K3, the coming sub-stage's Gram
+        // rows right behind it.  (a commit, failed or not, takes over the references on spectrum and tape)
+        fokl_outcome *full = nullptr;
+        if ((rc = fokl_search_model_commit(s, spectrum, tape, (*cur)[(size_t)A * (A + 1) + A], vm, &full)) != FOKL_OK) return rc;
+        stamp[O_CHAIN] = now_s();
+        release(spectral_job);
+        outcomes.push_back(full);                           // (from here on an error releases it: fokl_run_search)
+        const double *betahat = buffer + 2 * (size_t)A;     // (the outcome keeps the spectrum's buffer alive)
+        // G2 of the model has just arrived: the likely first tests' G2 jobs and tapes go out now, not after the residual pass
+        auto place_orders = [&]() -> int {
+            if (guessed || prm.lookahead <= 0 || vm <= 0) return FOKL_OK;
+            fokl_spectrum *own = nullptr;
+            int rcg = fokl_outcome_spectrum(s, full, &own);
+            if (rcg != FOKL_OK) return rcg;
+            rcg = guess_first_tests(own, vm, NAN, false);
+            fokl_spectrum_release(s, own);
+            guessed = rcg == FOKL_OK;
+            stamp[O_ORDERS] = now_s();
+            return rcg;
+        };
+        if (!g_k3_before_orders && (rc = place_orders()) != FOKL_OK) return rc;
         if (!terms_arr.empty() && A >= terms_pay_from) {
             rc = ops.bic_resid_terms_launch(ops.ctx, terms_arr.data() + m, A - 1, betahat);
             R->stats[R_RESID_MATRIX_FREE] += 1;
         } else {
             rc = ops.bic_resid_launch(ops.ctx, active_slots.data(), A, betahat);
         }
+        if (rc != FOKL_OK) return rc;
+        resid_launched = true;                              // (fetched below; on an error in between by fokl_run_search)
+        stamp[O_K3] = now_s();
+        if (g_k3_before_orders && (rc = place_orders()) != FOKL_OK) return rc;
         // (the coming sub-stage's columns went out at this sub-stage's start: their Gram rows right behind the residual pass)
-        if (rc == FOKL_OK && ahead.built && !ahead.valid) rc = launch_ahead_gram(active_slots, &ahead);
-        if (rc == FOKL_OK && !guessed && prm.lookahead > 0 && vm > 0) {
-            // G2 of the model has just arrived: the likely first tests' G2 jobs and tapes go out now, under the device's
-            // residual pass, not after it
-            rc = guess_first_tests(spectrum, vm, NAN, false);
-            guessed = rc == FOKL_OK;
+        if (ahead.built && !ahead.valid) {
+            if ((rc = launch_ahead_gram(active_slots, &ahead)) != FOKL_OK) return rc;
+            stamp[O_AHEAD_GRAM] = now_s();
         }
-        fokl_outcome *full = nullptr;
-        if (rc == FOKL_OK) rc = fokl_search_model_commit(s, spectrum, tape, (*cur)[(size_t)A * (A + 1) + A], vm, &full);
-        if (rc != FOKL_OK) {
-            fokl_spectrum_release(s, spectrum);
-            return rc;
-        }
-        release(spectral_job);
-        outcomes.push_back(full);
+        R->order.insert(R->order.end(), stamp, stamp + FOKL_RUN_ORDER_STAMPS);
         // the coming model's G2 for the kill set this model's least-squares fit predicts: its Gram block was launched at the
         // sub-stage's start and lies in front of the residual pass in the device's queue
         auto forecast_now = [&]() {
@@ -690,6 +723,7 @@ int Loop::run()
         {
             const double t0 = now_s();
             double mom[2] = {0, 0};
+            resid_launched = false;
             if ((rc = ops.bic_resid_fetch(ops.ctx, mom, 0)) != FOKL_OK) return rc;
             R->stats[R_T_RESID] += now_s() - t0;
             forecast_now();
@@ -945,6 +979,15 @@ extern "C" int fokl_run_search(fokl_run *r, fokl_search *search)
         for (fokl_outcome *o : loop.outcomes) fokl_outcome_drop(search, o);
         for (fokl_outcome *o : loop.retiring) fokl_outcome_drop(search, o);
         if (loop.ahead.valid && loop.ahead.pending) (void)loop.fetch_block(loop.ahead);
+        // ... and the backend is left as a next fit expects it: no residual pass waiting to be fetched, the slots of columns
+        // built ahead (Gram launched or not) back in the pool
+        if (loop.resid_launched) {
+            double dummy[2];
+            (void)r->ops.bic_resid_fetch(r->ops.ctx, dummy, 0);
+            loop.resid_launched = false;
+        }
+        r->pool.give(loop.ahead.slots);
+        loop.ahead = Ahead();
     }
     return rc;
 }
@@ -973,6 +1016,15 @@ extern "C" int fokl_run_arrays(const fokl_run *r, int32_t *mtx, double *evs, int
     if (stat_rel_std) std::memcpy(stat_rel_std, r->stat_rel_std.data(), sizeof(double) * r->stat_rel_std.size());
     if (stats) std::memcpy(stats, r->stats, sizeof(double) * FOKL_RUN_STATS);
     return (int)r->stat_mean_abs.size();
+}
+
+extern "C" int fokl_run_order(const fokl_run *r, double *stamps, int capacity)
+{
+    if (!r) return run_fail(nullptr, FOKL_ERR_ARG, "fokl_run_order: null run");
+    const int rows = (int)(r->order.size() / FOKL_RUN_ORDER_STAMPS);
+    if (stamps && capacity > 0)
+        std::memcpy(stamps, r->order.data(), sizeof(double) * FOKL_RUN_ORDER_STAMPS * (size_t)std::min(rows, capacity));
+    return rows;
 }
 
 extern "C" const char *fokl_run_error(const fokl_run *r) { return r ? r->error.c_str() : ""; }

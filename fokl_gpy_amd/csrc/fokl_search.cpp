@@ -1889,15 +1889,16 @@ extern "C" void fokl_spectrum_release(fokl_search *s, fokl_spectrum *h)
     if (s && h) unref(s, reinterpret_cast<Spectrum *>(h));
 }
 
-// A sub-stage's MODEL in two halves around the driver's K3 launch: begin = its tape (committed from the order, or
-// requested), the tapes on order after it (`then`), G2 waited for; commit = its chain.  The BIC comes from the driver
-// (fokl_search_score: residual moments of the device pass).
-extern "C" int fokl_search_model_begin(fokl_search *s, const double *gram, int ld, const int32_t *idx, int p1,
-                                       fokl_spectrum *given, const int32_t *then_sizes, const int32_t *then_model,
-                                       int then_count, fokl_spectrum **spectrum_out, fokl_tape **tape_out)
+// A sub-stage's MODEL in halves around the driver's launches: request = its tape (committed from the order, or
+// requested), the tapes on order after it (`then`), G2 submitted or adopted -- nothing is waited for: the caller waits
+// (fokl_spectrum_wait) when it has nothing else to launch; begin = request + that wait; commit = its chain.  The BIC
+// comes from the driver (fokl_search_score: residual moments of the device pass).
+extern "C" int fokl_search_model_request(fokl_search *s, const double *gram, int ld, const int32_t *idx, int p1,
+                                         fokl_spectrum *given, const int32_t *then_sizes, const int32_t *then_model,
+                                         int then_count, fokl_spectrum **spectrum_out, fokl_tape **tape_out)
 {
     if (!s || !gram || !idx || p1 < 1 || !spectrum_out || !tape_out)
-        return fail(s, FOKL_ERR_ARG, "fokl_search_model_begin: bad arguments");
+        return fail(s, FOKL_ERR_ARG, "fokl_search_model_request: bad arguments");
     Tape *t = tape_for(s, p1, true);                        // requested first: it is walked while G2 runs
     if (!t) return FOKL_ERR_STATE;
     std::vector<std::pair<int, bool>> want;
@@ -1913,14 +1914,35 @@ extern "C" int fokl_search_model_begin(fokl_search *s, const double *gram, int l
         return FOKL_ERR_STATE;
     }
     flush_spectra(s);
-    const int rc = wait_spectrum(s, sp);
-    if (rc != FOKL_OK) {
-        unref(s, sp);
-        unref(s, t);
-        return rc;
-    }
     *spectrum_out = reinterpret_cast<fokl_spectrum *>(sp);
     *tape_out = reinterpret_cast<fokl_tape *>(t);
+    return FOKL_OK;
+}
+
+// A requested model that will not be committed (its G2 failed, or the driver's own launches did): both references go back.
+extern "C" void fokl_search_model_abandon(fokl_search *s, fokl_spectrum *spectrum, fokl_tape *tape)
+{
+    if (!s) return;
+    if (spectrum) unref(s, reinterpret_cast<Spectrum *>(spectrum));
+    if (tape) unref(s, reinterpret_cast<Tape *>(tape));
+}
+
+extern "C" int fokl_search_model_begin(fokl_search *s, const double *gram, int ld, const int32_t *idx, int p1,
+                                       fokl_spectrum *given, const int32_t *then_sizes, const int32_t *then_model,
+                                       int then_count, fokl_spectrum **spectrum_out, fokl_tape **tape_out)
+{
+    if (!s || !gram || !idx || p1 < 1 || !spectrum_out || !tape_out)
+        return fail(s, FOKL_ERR_ARG, "fokl_search_model_begin: bad arguments");
+    fokl_spectrum *spectrum = nullptr;
+    fokl_tape *tape = nullptr;
+    int rc = fokl_search_model_request(s, gram, ld, idx, p1, given, then_sizes, then_model, then_count, &spectrum, &tape);
+    if (rc != FOKL_OK) return rc;
+    if ((rc = wait_spectrum(s, reinterpret_cast<Spectrum *>(spectrum))) != FOKL_OK) {
+        fokl_search_model_abandon(s, spectrum, tape);
+        return rc;
+    }
+    *spectrum_out = spectrum;
+    *tape_out = tape;
     return FOKL_OK;
 }
 

@@ -1422,6 +1422,7 @@ class ForwardSelection:
         self.stats['forecasts_early'] = self.stats.get('forecasts_early', 0) + int(st['forecasts_early'])
         self.stats['t_resid'] += st['t_resid']
         self.stats['substage_loop'] = 'native'
+        self.stats['substage_order'] = st['substage_order']
         phase = self.stats.setdefault('phases', dict(prepare=0.0, model=0.0, statistics=0.0, tests=0.0, wrap_up=0.0))
         for key in phase:
             phase[key] += st['phase_' + key]

@@ -408,6 +408,12 @@ void fokl_spectrum_release(fokl_search *search, fokl_spectrum *spectrum);
 int fokl_search_model_begin(fokl_search *search, const double *gram, int ld, const int32_t *idx, int p1,
                             fokl_spectrum *given, const int32_t *then_sizes, const int32_t *then_model, int then_count,
                             fokl_spectrum **spectrum_out, fokl_tape **tape_out);
+/* model_begin without its wait for G2 (the caller launches what it has, then fokl_spectrum_wait); _abandon gives both
+ * references back when the model is not committed after all (a commit, failed or not, has taken them over) */
+int fokl_search_model_request(fokl_search *search, const double *gram, int ld, const int32_t *idx, int p1,
+                              fokl_spectrum *given, const int32_t *then_sizes, const int32_t *then_model, int then_count,
+                              fokl_spectrum **spectrum_out, fokl_tape **tape_out);
+void fokl_search_model_abandon(fokl_search *search, fokl_spectrum *spectrum, fokl_tape *tape);
 int fokl_search_model_commit(fokl_search *search, fokl_spectrum *spectrum, fokl_tape *tape, double dtd, int new_terms,
                              fokl_outcome **out);
 int fokl_search_score(fokl_search *search, fokl_outcome *outcome, double sum_r, double sum_r2, int n_prev, int kill,
@@ -524,6 +530,12 @@ int fokl_run_result(const fokl_run *run, int32_t *mtx_rows, int32_t *evs_count, 
  * statistics arrays */
 int fokl_run_arrays(const fokl_run *run, int32_t *mtx, double *evs, int32_t *stat_sizes, double *stat_mean_abs,
                     double *stat_rel_std, double *stats);
+/* In which order a sub-stage's model went out: per sub-stage FOKL_RUN_ORDER_STAMPS readings of the monotonic clock (seconds)
+ * -- K1 of the coming sub-stage launched, wait for G2 begun, G2 arrived, chain submitted, first tests' orders placed, K3
+ * launched, the coming sub-stage's Gram launched; NaN: that step did not happen there.  stamps [capacity rows] (NULL: only
+ * count) -> sub-stages recorded */
+#define FOKL_RUN_ORDER_STAMPS 7
+int fokl_run_order(const fokl_run *run, double *stamps, int capacity);
 const char *fokl_run_error(const fokl_run *run);
 void fokl_run_destroy(fokl_run *run);
 
