@@ -35,6 +35,7 @@ from . import update as _update
 from . import optimize as _optimize
 from . import population as _population
 from . import score as _score
+from . import predictive as _predictive
 from . import design as _design
 from . import infer as _infer
 from . import resample as _resample
@@ -1376,6 +1377,49 @@ class FoKL:
             inputs = self.clean(inputs, kwargs_from_other=kwargs_to_clean)
         kwargs.setdefault('device', self._backend())
         return _score.score(betas, sigsqd, mtx, self.phis, self.kernel, inputs, data, **kwargs)
+
+    def predictive(self, post=None, inputs=None, data=None, clean=False, betas=None, sigsqd=None, mtx=None, **kwargs):
+        """The posterior predictive distribution of every row over every posterior draw on the device: its CDF at the
+        observed value (PIT), its quantiles -- prediction intervals for NEW measurements, where ``evaluate(ReturnBounds=True)``
+        and ``coverage3`` band the mean -- and the coverage of those intervals: ``predictive.predictive`` with this model's
+        ``mtx``, ``phis`` and ``kernel``, which documents the keywords -- quantiles, draws, max_passes, ftol, xtol -- and the
+        result.  ``post`` is what ``resample`` returned (its ``betas`` and ``sigsqd``), or pass ``betas=`` and ``sigsqd=``: the
+        predictive needs sigma^2 per draw, which a fit does not keep.  ``inputs`` / ``data`` default to the model's own
+        cleaned training set; with other ``inputs`` ``data`` is optional (quantiles alone), and ``clean=True`` normalises
+        them with the model's ``minmax`` exactly as ``evaluate`` does.  Numpy's random stream and ``setnos`` are left alone."""
+        if post is not None:
+            if betas is not None or sigsqd is not None:
+                raise ValueError("predictive takes a resample's result OR betas= and sigsqd=, not both")
+            try:
+                betas, sigsqd = post['betas'], post['sigsqd']
+            except (KeyError, TypeError, IndexError):
+                raise ValueError("predictive needs what resample returned (betas and sigsqd per draw) as its first "
+                                 "argument") from None
+            if betas is None or sigsqd is None:
+                raise ValueError("this resample kept no rows (keep=...): predictive needs betas and sigsqd per draw")
+        if betas is None or sigsqd is None:
+            raise ValueError("predictive needs sigma^2 for every draw and a fit keeps the betas only: draw both with "
+                             "post = model.resample(...) and call model.predictive(post), or pass betas= and sigsqd=")
+        if mtx is None:
+            mtx = getattr(self, 'mtx', None)
+        if mtx is None:
+            raise ValueError("predictive needs a fitted model: call fit first (there is no interaction matrix mtx)")
+        if inputs is None:
+            if _str_to_bool(clean):
+                warnings.warn("Cleaning was already performed on default 'inputs', so overriding 'clean' to False.",
+                              category=UserWarning)
+            inputs = getattr(self, 'inputs', None)
+            if data is None:
+                data = getattr(self, 'data', None)
+        elif _str_to_bool(clean):
+            if not hasattr(self, 'minmax'):
+                raise ValueError("predictive(clean=True) needs the model's minmax (set by clean / fit, or model.minmax = "
+                                 "[[min, max], ...])")
+            kwargs_to_clean = dict(_CLEAN_DEFAULTS)
+            kwargs_to_clean['minmax'] = self.minmax
+            inputs = self.clean(inputs, kwargs_from_other=kwargs_to_clean)
+        kwargs.setdefault('device', self._backend())
+        return _predictive.predictive(betas, sigsqd, mtx, self.phis, self.kernel, inputs, data, **kwargs)
 
     def design(self, post=None, pool=None, clean=False, picks=64, criterion='variance', target=None, tausqd=None, inputs=None,
                mtx=None, **kwargs):

@@ -23,6 +23,7 @@ K_RESAMPLE = 12
 K_SCORE = 13
 K_INFER = 14
 K_DESIGN = 15
+K_PREDICTIVE = 16
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
@@ -33,6 +34,8 @@ POPULATION_COEFFICIENTS = ('none', 'registers', 'table')      # fokl_population_
 POPULATION_MAX_CUTS = 32
 SCORE_INSTANCES = ('none', 'waic', 'waic_loo')                # fokl_score_report: the instance of score_kernel that ran
 SCORE_MAX_TAIL = 512                      # fokl_score_rows: entries (M + 1) of a row's list of largest log ratios in LDS
+PREDICTIVE_INSTANCES = ('none', 'pit', 'quantiles', 'pit_quantiles')   # fokl_predictive_report: what the launch computed
+PREDICTIVE_MAX_QUANTILES = 8              # fokl_predictive_rows: quantiles of one call (registers of a lane)
 RESAMPLE_MAX_COLUMNS = 768                # fokl_resample_chains: 12 eigen-coordinates per lane
 RESAMPLE_ATTEMPT_CAP = 64                 # Marsaglia-Tsang attempts per gamma variate
 RESAMPLE_SEGMENTS = 3                     # per-chain sums: first half, second half, the odd last iteration
@@ -96,6 +99,9 @@ SIGNATURES = {
     'fokl_resample_report': (c_int, [c_vp, c_vp]),
     'fokl_score_rows': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     'fokl_score_report': (c_int, [c_vp, c_vp]),
+    'fokl_predictive_rows': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_dbl, c_int, c_vp, c_vp, c_int, c_int, c_dbl,
+                                     c_dbl, c_vp]),
+    'fokl_predictive_report': (c_int, [c_vp, c_vp]),
     'fokl_design_select': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                    c_vp]),
     'fokl_design_report': (c_int, [c_vp, c_vp]),
@@ -2273,6 +2279,45 @@ class DeviceContext:
         v = [int(x) for x in out]
         return dict(instance=SCORE_INSTANCES[v[0]], grid=v[1], row_tiles=v[2], lds_bytes=v[3], tail_capacity=v[4],
                     raw_rows=v[5], kernel_ms=v[6] / 1000.0)
+
+    def predictive_rows(self, slots, betas, sd, rinv, with_data, p, z, max_passes=32, ftol=1e-13, xtol=1e-15):
+        """fokl_predictive_rows over the uploaded rows: the mixture over the rows of ``betas`` [E, nc] of N(X_i . beta_d,
+        sd_d^2) per uploaded row, ``sd`` [E] and ``rinv`` [E] = 1 / (sd sqrt(2)) as the caller formed them, the uploaded y read
+        only ``with_data``; ``p`` [Q] and their standard normal quantiles ``z`` [Q], Q <= 8 -> the block [S, 6 + 5 Q] = mu_0,
+        s1, s2, min mu, max mu, pit, then per quantile q, residual, lo, hi, passes.  predictive.predictive_rows_host is its
+        statement.  Two calls with the same arguments return the same bits."""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        if betas.ndim != 2 or betas.shape[1] != s.shape[0]:
+            raise ValueError("betas columns must match the slot list")
+        E = betas.shape[0]
+        sd = np.ascontiguousarray(np.reshape(sd, -1), dtype=np.float64)
+        rinv = np.ascontiguousarray(np.reshape(rinv, -1), dtype=np.float64)
+        if sd.shape[0] != E or rinv.shape[0] != E:
+            raise ValueError("predictive_rows: one sd and one rinv per row of betas")
+        p = np.ascontiguousarray(np.reshape(p, -1), dtype=np.float64)
+        z = np.ascontiguousarray(np.reshape(z, -1), dtype=np.float64)
+        if z.shape[0] != p.shape[0]:
+            raise ValueError("predictive_rows: one z per p")
+        Q = p.shape[0]
+        out = np.empty((self.n, 6 + 5 * Q), dtype=np.float64)
+        self._ck(self._lib.fokl_predictive_rows(self._h, _ptr(s), s.shape[0], _ptr(betas), _ptr(sd), _ptr(rinv), E,
+                                                float(np.mean(sd * sd)), int(bool(with_data)), _ptr(p) if Q else None,
+                                                _ptr(z) if Q else None, Q, int(max_passes), float(ftol), float(xtol), _ptr(out)))
+        return out
+
+    def predictive_report(self):
+        """What the last ``predictive_rows`` on this context ran (fokl_predictive_report): ``instance`` ('pit': data only,
+        'quantiles', 'pit_quantiles'), ``with_data`` and ``with_quantiles``, the ``grid`` of one-wavefront workgroups over
+        ``row_tiles`` 16-row tiles, ``lds_bytes``, ``quantiles`` (Q), ``passes_max`` (the most passes any tile ran; pass 0 is
+        not counted), ``passes_sum`` (over the tiles), the ``unresolved`` pairs and ``kernel_ms``.  'none' and zeros after a
+        refused call."""
+        out = np.zeros(9, dtype=np.int64)
+        self._ck(self._lib.fokl_predictive_report(self._h, _ptr(out)))
+        v = [int(x) for x in out]
+        return dict(instance=PREDICTIVE_INSTANCES[v[0]], with_data=bool(v[0] & 1), with_quantiles=bool(v[0] & 2), grid=v[1],
+                    row_tiles=v[2], lds_bytes=v[3], quantiles=v[4], passes_max=v[5], passes_sum=v[6], unresolved=v[7],
+                    kernel_ms=v[8] / 1000.0)
 
     def design_select(self, slots, C0, CMC0=None, picks=1, replicates=False, refresh_every=64, keep=False, grid_cap=0):
         """fokl_design_select over the uploaded rows (the pool): greedy selection of ``picks`` rows given C0 = (G + I / tau^2)^-1

@@ -226,6 +226,12 @@ class HipBackend:
     def score_report(self):
         return self.ctx.score_report()
 
+    def predictive_rows(self, slots, betas, sd, rinv, with_data, p, z, max_passes=32, ftol=1e-13, xtol=1e-15):
+        return self.ctx.predictive_rows(slots, betas, sd, rinv, with_data, p, z, max_passes, ftol, xtol)
+
+    def predictive_report(self):
+        return self.ctx.predictive_report()
+
     def design_select(self, slots, C0, CMC0=None, picks=1, replicates=False, refresh_every=64, keep=False, grid_cap=0):
         return self.ctx.design_select(slots, C0, CMC0, picks, replicates, refresh_every, keep, grid_cap)
 

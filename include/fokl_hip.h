@@ -56,7 +56,8 @@ extern "C" {
 #define FOKL_K_SCORE   13       /* score(): pointwise log predictive density, WAIC and PSIS-LOO (fokl_hip_internal.h: fokl_score_rows) */
 #define FOKL_K_INFER   14       /* infer_inputs(): ensemble samplers over unknown inputs (fokl_hip_internal.h: fokl_infer_inputs) */
 #define FOKL_K_DESIGN  15       /* design(): greedy optimal design over a candidate pool (fokl_hip_internal.h: fokl_design_select) */
-#define FOKL_K_COUNT   16
+#define FOKL_K_PREDICTIVE 16    /* predictive(): PIT and quantiles of the predictive distribution per row (fokl_hip_internal.h: fokl_predictive_rows) */
+#define FOKL_K_COUNT   17
 
 typedef struct fokl_ctx fokl_ctx;
 

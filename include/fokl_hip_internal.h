@@ -28,6 +28,9 @@
  *   fokl_score_rows / fokl_score_report
  *                              the log predictive density of every row over all draws: WAIC and PSIS-LOO
  *                              (fokl_gpy_amd/score.py), and what its last launch ran
+ *   fokl_predictive_rows / fokl_predictive_report
+ *                              the predictive distribution of every row over all draws: PIT, quantiles and their brackets
+ *                              (fokl_gpy_amd/predictive.py), and what its last launch ran
  *   fokl_design_select / fokl_design_report
  *                              greedy D- / I-optimal selection from a candidate pool (fokl_gpy_amd/design.py), and what
  *                              its last call ran
@@ -998,6 +1001,59 @@ int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const double *b
  *   out[5]  rows that took the khat = +inf branch     out[6]  kernel microseconds
  */
 int fokl_score_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* The predictive distribution per row: PIT and quantiles (csrc/fokl_predictive_device.inc; fokl_gpy_amd/predictive.py) */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/* out[0] of fokl_predictive_report: the instance that ran, a sum of these (0: no call yet, or the last one was refused) */
+enum {
+    FOKL_PREDICTIVE_NONE = 0,
+    FOKL_PREDICTIVE_PIT = 1,        /* with_data: the CDF at the uploaded y from pass 0 */
+    FOKL_PREDICTIVE_QUANTILES = 2   /* nq > 0: brackets, first trial and the pass loop */
+};
+#define FOKL_PREDICTIVE_REPORT_LEN 9
+#define FOKL_PREDICTIVE_BASE 6            /* columns of a result row before the quantiles' */
+#define FOKL_PREDICTIVE_PER_QUANTILE 5    /* ... and per quantile */
+/* Quantiles of one call: a lane keeps q, residual, bracket and two partial sums of each in registers. */
+#define FOKL_PREDICTIVE_MAX_QUANTILES 8
+
+/*
+ * The predictive of row i is the equal-weight mixture over the draws d of N(mu_id, sd[d]^2), mu_id = X_i . betas[d], over
+ * the uploaded rows (X_i: the columns `slots`, nc of them, as for fokl_predict; y: FOKL_SLOT_Y, read only with with_data).
+ * Host memory, row-major: betas [draws, nc]; sd [draws] = sqrt(sigsqd) and rinv [draws] = 1 / (sd sqrt(2)), positive and
+ * finite, formed by the caller; mean_sigsqd = the mean of sigsqd as the caller rounds it; p [nq] strictly inside (0, 1) and
+ * distinct, z [nq] their standard normal quantiles (any finite values: only the bracket and the first trial use them);
+ * 0 <= nq <= FOKL_PREDICTIVE_MAX_QUANTILES.
+ *   out [rows, 6 + 5 nq]    mu_0; s1 = sum_d (mu_d - mu_0); s2 = sum_d (mu_d - mu_0)^2; min_d mu_d; max_d mu_d; pit =
+ *                           sum_d 0.5 erfc((mu_d - y) rinv_d) / draws (0 without with_data); then per quantile q, the
+ *                           residual r = F(q) - p as last evaluated (+inf: never), the final bracket lo, hi and the passes
+ *                           used.  Pass 0 gives lo = min_d (mu_d + sd_d z), hi = max_d (mu_d + sd_d z) and the first trial
+ *                           mean + z sqrt(var) (inside the bracket, else its midpoint); each of up to max_passes further
+ *                           passes evaluates F and its density at q, moves the bracket and takes a safeguarded Newton step
+ *                           or the midpoint, until |r| <= ftol or hi - lo <= xtol (max mu - min mu + max sd).
+ * The rule is stated to the last operation in numpy by predictive.predictive_rows_host.  One launch of predictive_kernel on
+ * v_mfma_f64_16x16x4_f64, one wavefront per 16-row tile; the product is recomputed in every pass (no limit on the draws);
+ * merges across lanes in a fixed order, no atomics: the same arguments give the same bits.
+ * Refused (FOKL_ERR_ARG with a text, nothing is launched; the dataset, its slots and pending launches are left alone):
+ * nq outside its range; p outside (0, 1), not finite or repeated; max_passes < 0; ftol or xtol negative or not finite;
+ * neither with_data nor quantiles; basis values beyond the LDS of a compute unit; coefficient table and results together
+ * beyond the device's free memory (the environment's FOKL_PREDICTIVE_FREE_BYTES, if set, caps what counts as free).
+ * Kernel time: FOKL_K_PREDICTIVE, with the flops of the passes that ran.  Blocking.
+ */
+int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sd, const double *rinv,
+                         int draws, double mean_sigsqd, int with_data, const double *p, const double *z, int nq, int max_passes,
+                         double ftol, double xtol, double *out);
+
+/*
+ * The last fokl_predictive_rows call on `ctx`, out [FOKL_PREDICTIVE_REPORT_LEN] (host):
+ *   out[0]  the instance (above); zeros after a call that returned an error
+ *   out[1]  the grid (workgroups = wavefronts)     out[2]  16-row tiles (more than the grid: the tile loop went round)
+ *   out[3]  dynamic LDS bytes     out[4]  nq
+ *   out[5]  the most passes any tile ran (pass 0 not counted)     out[6]  the sum of passes over the tiles
+ *   out[7]  unresolved (row, quantile) pairs: |r| > ftol     out[8]  kernel microseconds
+ */
+int fokl_predictive_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* Which pool rows to measure next: greedy optimal design (csrc/fokl_design_device.inc; fokl_gpy_amd/design.py) */
