@@ -39,6 +39,7 @@ from . import predictive as _predictive
 from . import design as _design
 from . import infer as _infer
 from . import resample as _resample
+from . import robust as _robust
 
 
 def _column_min_max(a):
@@ -221,6 +222,18 @@ class _DeviceInputs:
 
     def fetch(self):
         return self.backend.download_inputs()
+
+
+def _refuse_student_noise(post, who):
+    """``score`` and ``predictive`` assume a Gaussian likelihood: a ``resample_robust`` result with finite nu is refused."""
+    try:
+        nu = post['nu']
+    except (KeyError, TypeError, IndexError):
+        return
+    if nu is not None and np.isfinite(nu):
+        raise ValueError(f"{who} assumes a Gaussian likelihood and this posterior was drawn under Student-t noise (nu = "
+                         f"{float(nu):g}): its sigsqd is the scale of a t distribution, and {who} under t noise is not "
+                         f"implemented (resample_robust(nu=np.inf) keeps the row weights under Gaussian noise)")
 
 
 class FoKL:
@@ -1337,6 +1350,30 @@ class FoKL:
         kwargs.setdefault('device', self._backend())
         return _resample.resample(mtx, self.phis, self.kernel, inputs, data, self.a, self.b, self.atau, self.btau, **kwargs)
 
+    def resample_robust(self, inputs=None, data=None, betas=None, mtx=None, **kwargs):
+        """The fitted model's posterior under Student-t noise and given row weights, sampled on the device: bad rows lose
+        their say instead of inflating sigma^2 and bending the coefficients -- ``robust.resample_robust`` with this model's
+        ``mtx``, ``phis``, ``kernel`` and the hyper-parameters the fit used, which documents the keywords -- nu, weights,
+        chains, draws, burnin, thin, seed, init, keep -- and the result (``weight_mean``: how much each row was trusted).
+        Arguments are handled as ``resample`` handles them: ``inputs`` / ``data`` default to the model's own cleaned
+        training set.  ``fit``'s results, ``setnos`` and numpy's random stream are left alone."""
+        known = ('nu', 'weights', 'chains', 'draws', 'burnin', 'thin', 'seed', 'init', 'keep', 'device')
+        unknown = [k for k in kwargs if k not in known]
+        if unknown:
+            raise ValueError(f"Unexpected keyword argument: {unknown[0]} (resample_robust takes {', '.join(known)})")
+        if mtx is None:
+            mtx = getattr(self, 'mtx', None)
+        if mtx is None:
+            raise ValueError("resample_robust needs a fitted model: call fit first (there is no interaction matrix mtx)")
+        if betas is not None and np.shape(betas)[-1] != np.atleast_2d(mtx).shape[0] * (np.size(mtx) > 0) + 1:
+            raise ValueError("betas do not belong to mtx: they need terms + 1 columns")
+        if inputs is None:
+            inputs = getattr(self, 'inputs', None)
+        if data is None:
+            data = getattr(self, 'data', None)
+        kwargs.setdefault('device', self._backend())
+        return _robust.resample_robust(mtx, self.phis, self.kernel, inputs, data, self.a, self.b, self.atau, self.btau, **kwargs)
+
     def score(self, post=None, inputs=None, data=None, clean=False, betas=None, sigsqd=None, mtx=None, **kwargs):
         """Score the fitted model pointwise over every posterior draw on the device: WAIC and PSIS-LOO of the training rows,
         or the log predictive density of held-out rows -- ``score.score`` with this model's ``mtx``, ``phis`` and ``kernel``,
@@ -1348,6 +1385,7 @@ class FoKL:
         if post is not None:
             if betas is not None or sigsqd is not None:
                 raise ValueError("score takes a resample's result OR betas= and sigsqd=, not both")
+            _refuse_student_noise(post, 'score')
             try:
                 betas, sigsqd = post['betas'], post['sigsqd']
             except (KeyError, TypeError, IndexError):
@@ -1390,6 +1428,7 @@ class FoKL:
         if post is not None:
             if betas is not None or sigsqd is not None:
                 raise ValueError("predictive takes a resample's result OR betas= and sigsqd=, not both")
+            _refuse_student_noise(post, 'predictive')
             try:
                 betas, sigsqd = post['betas'], post['sigsqd']
             except (KeyError, TypeError, IndexError):

@@ -24,6 +24,7 @@ K_SCORE = 13
 K_INFER = 14
 K_DESIGN = 15
 K_PREDICTIVE = 16
+K_ROBUST = 17
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
@@ -41,6 +42,10 @@ RESAMPLE_ATTEMPT_CAP = 64                 # Marsaglia-Tsang attempts per gamma v
 RESAMPLE_SEGMENTS = 3                     # per-chain sums: first half, second half, the odd last iteration
 # fokl_embedded_rng's purposes of the resampler (csrc/fokl_philox.h)
 RES_BETA, RES_SIG_NORMAL, RES_SIG_UNIFORM, RES_TAU_NORMAL, RES_TAU_UNIFORM, RES_START = 3, 4, 5, 6, 7, 8
+ROBUST_MAX_COLUMNS = 127                  # fokl_robust_*: P + 1; [1 | X | y] fills eight 16-column blocks
+# fokl_robust_rng's purposes (csrc/fokl_philox.h): the lam variate's normal / uniform (index = row), z (index = coordinate),
+# the normal / uniform of sigma^2's and tau^2's gamma variates (index 0); the attempt rides in the purpose word
+ROB_LAM_NORMAL, ROB_LAM_UNIFORM, ROB_BETA, ROB_SIG_NORMAL, ROB_SIG_UNIFORM, ROB_TAU_NORMAL, ROB_TAU_UNIFORM = 0, 1, 2, 3, 4, 5, 6
 DESIGN_INSTANCES = ('none', 'variance', 'ivr')                # fokl_design_report: the instance of the design kernels that ran
 DESIGN_MAX_COLUMNS = 768                  # fokl_design_select: a 16-row tile of basis values in LDS is 96 KiB
 OPTIMIZE_INSTANCES = ('none', 'uniform', 'per_lane')          # fokl_optimize_report / fokl_system_optimize_report
@@ -97,6 +102,14 @@ SIGNATURES = {
     'fokl_resample_chains': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_vp, c_vp, c_int,
                                      c_int, c_int, ctypes.c_uint32, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_resample_report': (c_int, [c_vp, c_vp]),
+    'fokl_robust_pass': (c_int, [c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_dbl, c_dbl, ctypes.c_uint32, ctypes.c_uint32,
+                                 ctypes.c_uint32, c_int, c_vp, c_vp, c_vp]),
+    'fokl_robust_step': (c_int, [c_vp, c_int, c_vp, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, ctypes.c_uint32, ctypes.c_uint32,
+                                 ctypes.c_uint32, c_int, c_vp, c_vp, c_vp]),
+    'fokl_robust_chains': (c_int, [c_vp, c_vp, c_int, c_vp, c_i64, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_int, c_vp, c_vp,
+                                   c_vp, c_int, c_int, c_int, ctypes.c_uint32, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_robust_report': (c_int, [c_vp, c_vp]),
+    'fokl_robust_rng': (c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int, c_int, ctypes.c_uint32, c_i64, c_vp]),
     'fokl_score_rows': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     'fokl_score_report': (c_int, [c_vp, c_vp]),
     'fokl_predictive_rows': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_dbl, c_int, c_vp, c_vp, c_int, c_int, c_dbl,
@@ -351,6 +364,16 @@ def embedded_rng(seed, chain, draw, purpose, count):
     counter (draw, purpose, index); purposes 0 .. 2 the embedded sampler's, RES_* the resampler's); host code, no device."""
     out = np.empty(int(count), dtype=np.float64)
     _check(load().fokl_embedded_rng(int(seed) & 0xFFFFFFFF, int(chain), int(draw), int(purpose), int(count), _ptr(out)))
+    return out
+
+
+def robust_rng(seed, chain, iteration, purpose, count, attempt=0, first=0):
+    """The numbers the robust resampler draws (fokl_robust_rng: Philox 4x32-10 keyed by (seed, chain), counter (iteration,
+    purpose + 16 attempt, index, 4)) for the indices first .. first + count - 1; purposes ROB_*: uniforms for the *_UNIFORM
+    ones, normals otherwise; host code, no device."""
+    out = np.empty(int(count), dtype=np.float64)
+    _check(load().fokl_robust_rng(int(seed) & 0xFFFFFFFF, int(chain), int(iteration), int(purpose), int(attempt), int(first),
+                                  int(count), _ptr(out)))
     return out
 
 
@@ -2245,6 +2268,86 @@ class DeviceContext:
         v = [int(x) for x in out]
         return dict(instance=v[0], chains=v[1], iterations=v[2], chains_per_group=v[3], attempts=v[4], attempts_max=v[5],
                     kernel_ms=v[6] / 1000.0, grid=v[7], flagged=v[8], kept=v[9])
+
+    def robust_pass(self, slots, weights, beta, sigsqd, nu, seed, chain, iteration, attempt_cap=0, want_rows=True):
+        """fokl_robust_pass over the uploaded rows: one row pass of chain ``chain`` at ``iteration`` over the columns ``slots``
+        (the intercept's included) and the uploaded y, ``weights`` [n] or None -> (G [nc + 1, nc + 1], lam [n], attempts [n]
+        int32; the last two None without ``want_rows``).  robust.pass_host is its statement."""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        nc = s.shape[0]
+        w = None if weights is None else np.ascontiguousarray(np.reshape(weights, -1), dtype=np.float64)
+        b = None if beta is None else np.ascontiguousarray(np.reshape(beta, -1), dtype=np.float64)
+        if b is not None and b.shape[0] != nc:
+            raise ValueError("robust_pass: one coefficient per slot")
+        G = np.empty((nc + 1, nc + 1), dtype=np.float64)
+        lam = np.empty(self.n, dtype=np.float64) if want_rows else None
+        att = np.empty(self.n, dtype=np.int32) if want_rows else None
+        self._ck(self._lib.fokl_robust_pass(self._h, _ptr(s), nc, _ptr(w), 0 if w is None else w.shape[0], _ptr(b), float(sigsqd),
+                                            float(nu), int(seed) & 0xFFFFFFFF, int(chain), int(iteration), int(attempt_cap),
+                                            _ptr(G), _ptr(lam), _ptr(att)))
+        return G, lam, att
+
+    def robust_step(self, G, sigsqd, tausqd, hyper, seed, chain, iteration, attempt_cap=0):
+        """fokl_robust_step on a given G [nc + 1, nc + 1] (its upper triangle is read) -> (beta [nc], sigsqd, tausqd, flag);
+        ``hyper``: dict(astar, atau_star, b, btau).  robust.step_host is its statement."""
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        if G.ndim != 2 or G.shape[0] != G.shape[1] or G.shape[0] < 2:
+            raise ValueError("robust_step: G must be [nc + 1, nc + 1]")
+        nc = G.shape[0] - 1
+        beta, state, counts = np.empty(nc, dtype=np.float64), np.empty(2, dtype=np.float64), np.empty(4, dtype=np.int64)
+        self._ck(self._lib.fokl_robust_step(self._h, nc, _ptr(G), float(sigsqd), float(tausqd), float(hyper['astar']),
+                                            float(hyper['atau_star']), float(hyper['b']), float(hyper['btau']),
+                                            int(seed) & 0xFFFFFFFF, int(chain), int(iteration), int(attempt_cap), _ptr(beta),
+                                            _ptr(state), _ptr(counts)))
+        return beta, float(state[0]), float(state[1]), int(counts[1])
+
+    def robust_chains(self, slots, weights, nu, hyper, shift, sigsqd0, tausqd0, burnin, draws, thin, seed, rows=True,
+                      attempt_cap=0, chain_ids=None, want_lam=True):
+        """fokl_robust_chains over the uploaded rows: one chain per entry of ``sigsqd0`` / ``tausqd0``, burnin + draws iterations
+        of pass, reduce and step each -> dict(betas [chains, kept, nc], sigsqd, tausqd [chains, kept], attempts [chains, kept]
+        int64 -- None without ``rows`` --, sums [chains, 3, 2, nc + 2], counts [chains, 4], lam_sum [chains, n]);
+        robust.robust_host is its statement and documents the fields."""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        nc = s.shape[0]
+        w = None if weights is None else np.ascontiguousarray(np.reshape(weights, -1), dtype=np.float64)
+        shift, sigsqd0, tausqd0 = (np.ascontiguousarray(np.reshape(v, -1), dtype=np.float64) for v in (shift, sigsqd0, tausqd0))
+        chains = sigsqd0.shape[0]
+        if shift.shape[0] != nc or tausqd0.shape[0] != chains:
+            raise ValueError("robust_chains: shift [nc] and one start per chain")
+        ids = None if chain_ids is None else np.ascontiguousarray(np.reshape(chain_ids, -1), dtype=np.int32)
+        if ids is not None and ids.shape[0] != chains:
+            raise ValueError("robust_chains: one chain id per chain")
+        burnin, draws, thin = int(burnin), int(draws), int(thin)
+        if draws < 1 or thin < 1:
+            raise ValueError("robust_chains: draws >= 1 and thin >= 1")
+        kept = -(-draws // thin)
+        betas = sig = tau = att = None
+        if rows:
+            betas = np.empty((chains, kept, nc), dtype=np.float64)
+            sig, tau = np.empty((chains, kept), dtype=np.float64), np.empty((chains, kept), dtype=np.float64)
+            att = np.empty((chains, kept), dtype=np.int64)
+        sums = np.empty((chains, RESAMPLE_SEGMENTS, 2, nc + 2), dtype=np.float64)
+        counts = np.empty((chains, 4), dtype=np.int64)
+        lam_sum = np.empty((chains, self.n), dtype=np.float64) if want_lam else None
+        self._ck(self._lib.fokl_robust_chains(self._h, _ptr(s), nc, _ptr(w), 0 if w is None else w.shape[0], float(nu),
+                                              float(hyper['astar']), float(hyper['atau_star']), float(hyper['b']),
+                                              float(hyper['btau']), _ptr(shift), chains, _ptr(ids), _ptr(sigsqd0), _ptr(tausqd0),
+                                              burnin, draws, thin, int(seed) & 0xFFFFFFFF, int(attempt_cap), _ptr(betas), _ptr(sig),
+                                              _ptr(tau), _ptr(att), _ptr(sums), _ptr(counts), _ptr(lam_sum)))
+        return dict(betas=betas, sigsqd=sig, tausqd=tau, attempts=att, sums=sums, counts=counts, lam_sum=lam_sum)
+
+    def robust_report(self):
+        """What the last ``robust_pass`` / ``robust_step`` / ``robust_chains`` on this context ran (fokl_robust_report): the
+        ``grid`` (workgroups of the pass per chain, chains), the ``partials`` per chain and the doubles of one, ``lds_bytes``
+        of the pass and of the step, ``columns`` of [X|y] and their 16-column ``blocks``, ``iterations``, rows ``kept`` per
+        chain, Marsaglia-Tsang ``attempts``, ``flagged`` chains, and the kernel time: ``pass_ms``, ``reduce_ms``, ``step_ms``
+        summed over the ``timed_iterations`` last iterations, ``total_ms`` of the whole run.  Zeros after a refused call."""
+        out = np.zeros(16, dtype=np.int64)
+        self._ck(self._lib.fokl_robust_report(self._h, _ptr(out)))
+        v = [int(x) for x in out]
+        return dict(grid=(v[0], v[1]), partials=v[0], partial_doubles=v[2], lds_bytes=v[3], step_lds_bytes=v[4], columns=v[5],
+                    blocks=v[6], iterations=v[7], kept=v[8], attempts=v[9], flagged=v[10], pass_ms=v[11] / 1000.0,
+                    reduce_ms=v[12] / 1000.0, step_ms=v[13] / 1000.0, timed_iterations=v[14], total_ms=v[15] / 1000.0)
 
     def score_rows(self, slots, betas, sigsqd, want_loo=True, want_tail=False):
         """fokl_score_rows over the uploaded rows: ll[i, d] of the uploaded y against the columns ``slots`` times every row of

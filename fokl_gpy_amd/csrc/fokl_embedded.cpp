@@ -57,3 +57,19 @@ extern "C" int fokl_calibrate_rng(uint32_t seed, const uint32_t *draw_ids, int n
                                              : fokl::cal_uniform(seed, draw_ids[e], iteration, (uint32_t)purpose, (uint32_t)j);
     return FOKL_OK;
 }
+
+// ... and of the robust resampler (fokl_robust_device.inc; robust.pass_host / step_host draw through this entry): the numbers
+// of indices first .. first + count - 1 at Marsaglia-Tsang attempt `attempt` (0 for the coordinates' normals)
+extern "C" int fokl_robust_rng(uint32_t seed, uint32_t chain, uint32_t iteration, int purpose, int attempt, uint32_t first,
+                               int64_t count, double *out)
+{
+    if (count < 0 || (count > 0 && !out) || purpose < fokl::ROB_PURPOSE_LAM_NORMAL || purpose > fokl::ROB_PURPOSE_LAST ||
+        attempt < 0 || attempt > (1 << 20))
+        return FOKL_ERR_ARG;
+    const uint32_t word = (uint32_t)purpose + (uint32_t)fokl::ROB_ATTEMPT_STRIDE * (uint32_t)attempt;
+    const bool uniform = fokl::rob_purpose_is_uniform(purpose);
+    for (int64_t j = 0; j < count; ++j)
+        out[j] = uniform ? fokl::rob_uniform(seed, chain, iteration, word, first + (uint32_t)j)
+                         : fokl::rob_normal(seed, chain, iteration, word, first + (uint32_t)j);
+    return FOKL_OK;
+}

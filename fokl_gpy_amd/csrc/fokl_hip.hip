@@ -98,6 +98,7 @@ struct fokl_ctx {
     int64_t resample_report[FOKL_RESAMPLE_REPORT_LEN] = {};       // ... and the last fokl_resample_chains call
     int64_t score_report[FOKL_SCORE_REPORT_LEN] = {};             // ... and the last fokl_score_rows call
     int64_t predictive_report[FOKL_PREDICTIVE_REPORT_LEN] = {};   // ... and the last fokl_predictive_rows call
+    int64_t robust_report[FOKL_ROBUST_REPORT_LEN] = {};           // ... and the last fokl_robust_pass / _step / _chains call
     int64_t infer_report[FOKL_INFER_REPORT_LEN] = {};             // ... and the last fokl_infer_inputs call
     int64_t design_report[FOKL_DESIGN_REPORT_LEN] = {};           // ... and the last fokl_design_select call
     int64_t simulate_report[FOKL_SIMULATE_REPORT_LEN] = {};       // ... and the last fokl_simulate_ensemble call
@@ -1835,6 +1836,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_infer_device.inc"
 #include "fokl_embedded_device.inc"
 #include "fokl_resample_device.inc"
+#include "fokl_robust_device.inc"
 #include "fokl_score_device.inc"
 #include "fokl_predictive_device.inc"
 #include "fokl_design_device.inc"

@@ -188,6 +188,26 @@ extern "C" int fokl_resample_chains(fokl_ctx *, int, const double *, const doubl
 }
 extern "C" int fokl_resample_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor do the robust chains (fokl_robust_device.inc); their statement is robust.robust_host, and their random numbers
+// (fokl_robust_rng) are host code and present here.
+extern "C" int fokl_robust_pass(fokl_ctx *, const int32_t *, int, const double *, int64_t, const double *, double, double, uint32_t,
+                                uint32_t, uint32_t, int, double *, double *, int32_t *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_robust_step(fokl_ctx *, int, const double *, double, double, double, double, double, double, uint32_t, uint32_t,
+                                uint32_t, int, double *, double *, int64_t *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_robust_chains(fokl_ctx *, const int32_t *, int, const double *, int64_t, double, double, double, double, double,
+                                  const double *, int, const int32_t *, const double *, const double *, int, int, int, uint32_t,
+                                  int, double *, double *, double *, int64_t *, double *, int64_t *, double *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_robust_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // Nor does the pointwise score (fokl_score_device.inc); its statement is score.score_rows_host.
 extern "C" int fokl_score_rows(fokl_ctx *, const int32_t *, int, const double *, const double *, int, int, double *, double *)
 {

@@ -16,6 +16,10 @@
 // The calibration of a fitted dynamic system (fokl_calibrate_device.inc) draws from a fourth family: the same key and
 // counter layout with the fourth counter word 3 (cal_uniform, cal_normal below).
 //
+// The robust resampler (fokl_robust_device.inc, robust.py) draws from a fifth family: key (seed, chain), counter (iteration,
+// purpose + 16 attempt, index, 4) (rob_uniform, rob_normal below): the attempt of a Marsaglia-Tsang variate rides in the
+// purpose word, so that the index is free to name the row.
+//
 // Nothing here touches numpy's global stream or the fit's MT19937 machinery.
 #ifndef FOKL_PHILOX_H
 #define FOKL_PHILOX_H
@@ -132,6 +136,37 @@ FOKL_HD double cal_normal(uint32_t seed, uint32_t draw_id, uint32_t iteration, u
 {
     uint32_t w[4];
     philox4x32_10(iteration, purpose, index, 3u, seed, draw_id, w);
+    return sqrt(-2.0 * log(1.0 - emb_unit(w[0], w[1]))) * cos(6.283185307179586476925 * emb_unit(w[2], w[3]));
+}
+
+// fokl_robust_device.inc / robust.py: Gibbs chains under Student-t noise.  key = (seed, chain), counter = (iteration,
+// purpose + 16 attempt, index, 4): the fourth word keeps these streams apart from every one above (0 .. 3).
+constexpr int ROB_PURPOSE_LAM_NORMAL = 0;    // the latent precision of row `index`: the normal of Marsaglia-Tsang attempt `attempt` ...
+constexpr int ROB_PURPOSE_LAM_UNIFORM = 1;   // ... and its uniform
+constexpr int ROB_PURPOSE_BETA = 2;          // the normal z of coordinate `index`
+constexpr int ROB_PURPOSE_SIG_NORMAL = 3;    // sigma^2's gamma (index 0): the normal of attempt `attempt` ...
+constexpr int ROB_PURPOSE_SIG_UNIFORM = 4;   // ... and its uniform
+constexpr int ROB_PURPOSE_TAU_NORMAL = 5;    // tau^2's gamma: the same two
+constexpr int ROB_PURPOSE_TAU_UNIFORM = 6;
+constexpr int ROB_PURPOSE_LAST = ROB_PURPOSE_TAU_UNIFORM;
+constexpr int ROB_ATTEMPT_STRIDE = 16;       // purpose word = purpose + 16 attempt
+
+FOKL_HD bool rob_purpose_is_uniform(int purpose)
+{
+    return purpose == ROB_PURPOSE_LAM_UNIFORM || purpose == ROB_PURPOSE_SIG_UNIFORM || purpose == ROB_PURPOSE_TAU_UNIFORM;
+}
+
+FOKL_HD double rob_uniform(uint32_t seed, uint32_t chain, uint32_t iteration, uint32_t purpose_word, uint32_t index)
+{
+    uint32_t w[4];
+    philox4x32_10(iteration, purpose_word, index, 4u, seed, chain, w);
+    return emb_unit(w[0], w[1]);
+}
+
+FOKL_HD double rob_normal(uint32_t seed, uint32_t chain, uint32_t iteration, uint32_t purpose_word, uint32_t index)
+{
+    uint32_t w[4];
+    philox4x32_10(iteration, purpose_word, index, 4u, seed, chain, w);
     return sqrt(-2.0 * log(1.0 - emb_unit(w[0], w[1]))) * cos(6.283185307179586476925 * emb_unit(w[2], w[3]));
 }
 

@@ -226,6 +226,20 @@ class HipBackend:
     def score_report(self):
         return self.ctx.score_report()
 
+    def robust_pass(self, slots, weights, beta, sigsqd, nu, seed, chain, iteration, attempt_cap=0, want_rows=True):
+        return self.ctx.robust_pass(slots, weights, beta, sigsqd, nu, seed, chain, iteration, attempt_cap, want_rows)
+
+    def robust_step(self, G, sigsqd, tausqd, hyper, seed, chain, iteration, attempt_cap=0):
+        return self.ctx.robust_step(G, sigsqd, tausqd, hyper, seed, chain, iteration, attempt_cap)
+
+    def robust_chains(self, slots, weights, nu, hyper, shift, sigsqd0, tausqd0, burnin, draws, thin, seed, rows=True,
+                      attempt_cap=0, chain_ids=None, want_lam=True):
+        return self.ctx.robust_chains(slots, weights, nu, hyper, shift, sigsqd0, tausqd0, burnin, draws, thin, seed, rows,
+                                      attempt_cap, chain_ids, want_lam)
+
+    def robust_report(self):
+        return self.ctx.robust_report()
+
     def predictive_rows(self, slots, betas, sd, rinv, with_data, p, z, max_passes=32, ftol=1e-13, xtol=1e-15):
         return self.ctx.predictive_rows(slots, betas, sd, rinv, with_data, p, z, max_passes, ftol, xtol)
 

@@ -25,6 +25,10 @@
  *   fokl_resample_chains / fokl_resample_report
  *                              many independent Gibbs chains of a fitted model, drawing their own counter-based numbers
  *                              (fokl_gpy_amd/resample.py)
+ *   fokl_robust_pass / fokl_robust_step / fokl_robust_chains / fokl_robust_report / fokl_robust_rng
+ *                              Gibbs chains under Student-t noise and given row weights: a weighted pass over the rows per
+ *                              iteration (fokl_gpy_amd/robust.py), one pass or one step alone, what the last call ran, and
+ *                              the host's view of their random numbers
  *   fokl_score_rows / fokl_score_report
  *                              the log predictive density of every row over all draws: WAIC and PSIS-LOO
  *                              (fokl_gpy_amd/score.py), and what its last launch ran
@@ -882,6 +886,82 @@ int fokl_resample_chains(fokl_ctx *ctx, int p1, const double *lamb, const double
  *   out[7]  the grid     out[8]  flagged chains     out[9]  rows kept per chain (the call's kept, also without rows)
  */
 int fokl_resample_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* A robust posterior: Student-t noise and row weights (csrc/fokl_robust_device.inc; fokl_gpy_amd/robust.py)  */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_ROBUST_REPORT_LEN 16
+#define FOKL_ROBUST_MAX_COLUMNS 127        /* P + 1: [1 | X | y] fills eight 16-column blocks of the weighted Gram */
+
+/*
+ * The model: y_i = x_i . beta + eps_i, eps_i | lam_i ~ N(0, sigsqd / (w_i lam_i)), lam_i ~ Gamma(nu / 2, rate nu / 2); nu
+ * fixed (INFINITY: lam = 1), w given.  Iteration k of a chain is a row pass, a reduce and a step (robust.py states every
+ * operation).  Random numbers: Philox 4x32-10 keyed by (seed, chain), counter (iteration, purpose + 16 attempt, index, 4)
+ * (csrc/fokl_philox.h, ROB_PURPOSE_*; fokl_robust_rng below).  X_i: the columns `slots`, nc = P + 1 of them, of the
+ * uploaded rows; y: FOKL_SLOT_Y.  weights [n_weights] host, n_weights = the uploaded rows, or NULL: ones.
+ *
+ * fokl_robust_pass: one row pass.  At iteration 0 or nu = INFINITY lam = 1 (beta and sigsqd are not read); otherwise
+ * r_i = y_i - x_i . beta, lam_i = g_i / ((nu + w_i r_i^2 / sigsqd) / 2), g_i a standard gamma of shape (nu + 1) / 2 by
+ * Marsaglia-Tsang, at most attempt_cap attempts (0: the default, FOKL_RESAMPLE_ATTEMPT_CAP), NaN beyond.
+ *   G_out [nc + 1, nc + 1] = [X|y]' diag(w lam) [X|y], exactly symmetric; lam_out [rows], attempts_out [rows], or NULL.
+ * robust_pass_kernel accumulates the upper block triangle of G on v_mfma_f64_16x16x4_f64 per workgroup of four wavefronts
+ * over a range of rows that depends on the number of rows alone; robust_reduce_kernel sums the workgroups' partials in
+ * their order.  No atomics: the same arguments give the same bits.
+ */
+int fokl_robust_pass(fokl_ctx *ctx, const int32_t *slots, int nc, const double *weights, int64_t n_weights, const double *beta,
+                     double sigsqd, double nu, uint32_t seed, uint32_t chain, uint32_t iteration, int attempt_cap,
+                     double *G_out, double *lam_out, int32_t *attempts_out);
+
+/*
+ * fokl_robust_step: one step on a given G [nc + 1, nc + 1] (host; symmetric: its upper triangle is read), needs no dataset:
+ * A = G_xx + I / tausqd = L L' without pivoting, L u = G_xy, L' beta = u + sqrt(sigsqd) z; S = G_yy - 2 beta . G_xy +
+ * beta' G_xx beta; bstar = b + (S + beta . beta / tausqd) / 2; sigsqd' = 1 / Gamma(astar, 1 / bstar); tausqd' = 1 /
+ * Gamma(atau_star, 1 / (beta . beta / (2 sigsqd') + btau)).
+ *   beta_out [nc]; state_out [2] = sigsqd', tausqd'; counts_out [4] = `iteration` if the step flagged else -1, why (1: bstar
+ *   < 0; 2: a gamma variate met the attempt cap, or G is NaN because a row of the pass did; 3: a pivot was not positive),
+ *   the attempts of the two variates, the most of one.  A flagged step's outputs are NaN.
+ */
+int fokl_robust_step(fokl_ctx *ctx, int nc, const double *G, double sigsqd, double tausqd, double astar, double atau_star,
+                     double b, double btau, uint32_t seed, uint32_t chain, uint32_t iteration, int attempt_cap,
+                     double *beta_out, double *state_out, int64_t *counts_out);
+
+/*
+ * fokl_robust_chains: `chains` chains of burnin + draws iterations, chain c keyed by chain_ids[c] (NULL: c) and started at
+ * sigsqd0[c], tausqd0[c]; three launches per iteration queued on the context's stream, no host round trip between them
+ * (nu = INFINITY: the pass and the reduce run once, G does not change).  Outputs (host) as fokl_resample_chains', with
+ * betas_out [chains kept, nc] in place of w_out, attempts_out [chains kept] int64 (the rows' variates included), sums_out
+ * [chains, 3, 2, nc + 2] of beta - shift | sigsqd | tausqd, counts_out [chains, 4] as fokl_robust_step's; and lam_sum_out
+ * [chains, rows] (or NULL): the sum of lam_i over the passes of the post-burn-in iterations.  A flagged chain runs on, NaN
+ * from there; the other chains are not affected; chain c does not depend on how many chains run with it.
+ * Refused (FOKL_ERR_ARG with a text, nothing is launched; the dataset, its slots and pending launches are left alone):
+ * nc > FOKL_ROBUST_MAX_COLUMNS; a slot outside the table; n_weights that is not the number of rows; nu < 1 or NaN; a shape
+ * below 1; rows, row weights and partial Grams beyond the device's free memory (the environment's FOKL_ROBUST_FREE_BYTES,
+ * if set, caps what counts as free).  Kernel time: FOKL_K_ROBUST, three launches per iteration.  Blocking.
+ */
+int fokl_robust_chains(fokl_ctx *ctx, const int32_t *slots, int nc, const double *weights, int64_t n_weights, double nu,
+                       double astar, double atau_star, double b, double btau, const double *shift, int chains,
+                       const int32_t *chain_ids, const double *sigsqd0, const double *tausqd0, int burnin, int draws, int thin,
+                       uint32_t seed, int attempt_cap, double *betas_out, double *sig_out, double *tau_out,
+                       int64_t *attempts_out, double *sums_out, int64_t *counts_out, double *lam_sum_out);
+
+/*
+ * The last fokl_robust_pass / _step / _chains call on `ctx`, out [FOKL_ROBUST_REPORT_LEN] (host); zeros after a refused call:
+ *   out[0]  workgroups of the pass per chain = partial Grams (0: a step alone)     out[1]  chains (the grid's second dimension)
+ *   out[2]  doubles of one partial     out[3]  LDS bytes of the pass     out[4]  LDS bytes of the step
+ *   out[5]  columns of [X|y]     out[6]  16-column blocks     out[7]  iterations     out[8]  rows kept per chain
+ *   out[9]  Marsaglia-Tsang attempts in all     out[10] flagged chains
+ *   out[11 .. 13]  microseconds of the pass, the reduce and the step, summed over out[14] iterations (the last ones of a
+ *   run, 64 at most, timed launch by launch)     out[15] microseconds of the whole run
+ */
+int fokl_robust_report(const fokl_ctx *ctx, int64_t *out);
+
+/*
+ * The numbers of indices first .. first + count - 1 of (seed, chain, iteration, purpose, attempt): uniforms for the purposes
+ * 1, 4, 6, normals otherwise (csrc/fokl_philox.h: ROB_PURPOSE_*).  Host code, no device.
+ */
+int fokl_robust_rng(uint32_t seed, uint32_t chain, uint32_t iteration, int purpose, int attempt, uint32_t first, int64_t count,
+                    double *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* What a prediction ran (csrc/fokl_predict.inc)                                                             */
