@@ -2426,8 +2426,11 @@ class DeviceContext:
         """fokl_design_select over the uploaded rows (the pool): greedy selection of ``picks`` rows given C0 = (G + I / tau^2)^-1
         [nc, nc] and, for integrated variance reduction, CMC0 = C0 M C0 (None: greedy D-optimal) -> dict(index [picks] int64,
         gain [picks], vstar [picks], x [picks, nc] and, with ``keep``, v [S] (and w [S] with CMC0) after the last pick).
-        design.select_host is its statement.  ``grid_cap``: 0 the device's grids; a test hook.  Two calls with the same
-        arguments return the same bits."""
+        design.select_host is its statement: on integer data the first pick (index, gain, vstar, x), the first downdate (v
+        and w with ``picks=1, keep=True``) and the second pick's index and gain are its bits, everything later is equal to
+        rounding (C is no longer integer after a pick).  A pick that finds no row (all masked, or every criterion NaN) is
+        index -1, gain -inf, x = 0.  ``grid_cap``: 0 the device's grids; a test hook.  Two calls with the same arguments
+        return the same bits."""
         s = np.ascontiguousarray(slots, dtype=np.int32)
         nc = s.shape[0]
         C0 = np.ascontiguousarray(C0, dtype=np.float64)

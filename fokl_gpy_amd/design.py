@@ -66,7 +66,14 @@ def quadratic_forms(X, C, block=1 << 16):
 
 def select_host(X, C0, CMC0=None, picks=1, replicates=False, refresh_every=64, keep=False):
     """The statement of ``fokl_design_select``: X [S, nc] the pool's columns, C0 and (for 'ivr') CMC0 [nc, nc] ->
-    dict(index [picks] int64, gain, vstar [picks], x [picks, nc], v and w [S] after the last pick with ``keep``, else None)."""
+    dict(index [picks] int64, gain, vstar [picks], x [picks, nc], v and w [S] after the last pick with ``keep``, else None).
+    A pick that finds no row (all masked, or every criterion NaN) has index -1, gain -inf, x* = 0 and so v* = 0.
+
+    On integer data (X, C0, CMC0 small integers, every sum below 2^53) the device returns the same BITS for the first pick
+    (index, gain, v*, x*), the first downdate (v and w of every row with ``picks=1, keep=True``) and the second pick's index
+    and gain: up to there every sum is exact in any order, and the divisions that follow are written alike on both sides.
+    After a pick C and CMC are no longer integer, the two sides sum in different orders, and everything later (the second
+    v*, later picks' gains, a refresh) is equal to rounding (tests/test_design_select_gpu.py)."""
     X = np.asarray(X, dtype=np.float64)
     S, nc = X.shape
     C = np.array(C0, dtype=np.float64)

@@ -127,6 +127,87 @@ def test_nothing_random_is_touched_and_the_same_call_gives_the_same_bits():
     assert np.allclose(a.variance, np.einsum('si,ij,sj->s', columns(pool), Ck, columns(pool)), rtol=1e-10, atol=0.0)
 
 
+def integer_case(S, nc, seed=0):
+    """(X [S, nc], C0, CMC0 [nc, nc]) as int64: X = [1 | integers in -3..3], C0 = B'B + I with B 3 x nc from {-1, 0, 1},
+    CMC0 = D'D + 2 I with D 2 x nc from {-1, 0, 1}.  Symmetric positive definite, and every sum that ``select_host`` or the
+    kernels form before the first division is an integer below 2^53: exact in float64 whatever its order.  (Shared with
+    tests/test_design_select_gpu.py.)"""
+    rng = np.random.default_rng([S, nc, seed])
+    X = np.concatenate([np.ones((S, 1), dtype=np.int64), rng.integers(-3, 4, size=(S, nc - 1))], axis=1)
+    B, D = rng.integers(-1, 2, size=(3, nc)), rng.integers(-1, 2, size=(2, nc))
+    eye = np.eye(nc, dtype=np.int64)
+    return X, B.T @ B + eye, D.T @ D + 2 * eye
+
+
+def exact_first_pick(X, C0, CMC0):
+    """The first pick and the first downdate in int64 up to the one division each value needs:
+    -> (index, gain, v*, v [S], w [S] or None), float64."""
+    ivr = CMC0 is not None
+    f = lambda a: np.asarray(a, dtype=np.int64).astype(np.float64)
+    v0 = np.einsum('sj,sj->s', X @ C0, X)
+    w0 = np.einsum('sj,sj->s', X @ CMC0, X) if ivr else None
+    crit = f(w0) / (1.0 + f(v0)) if ivr else f(v0)             # one correctly rounded division
+    i = int(np.argmax(crit))                                     # the first of the largest
+    x = X[i]
+    u = C0 @ x
+    vstar = int(x @ u)
+    p = X @ u
+    assert int(np.max(np.abs(p))) ** 2 < 2 ** 53 and int(v0.max()) < 2 ** 53
+    d = float(1 + vstar)
+    v = f(v0) - f(p * p) / d
+    w = None
+    if ivr:
+        a = CMC0 @ x
+        wstar, q = int(x @ a), X @ a
+        assert max(int(w0.max()), 2 * int(np.max(np.abs(p * q))), wstar) < 2 ** 53
+        w = f(w0) - 2.0 * f(p) * f(q) / d + f(p) * f(p) * float(wstar) / (d * d)
+    return i, crit[i], float(vstar), v, w
+
+
+EXACT_SHAPES = [(17, 1), (1029, 17), (33, 513), (1029, 768)]
+
+
+@pytest.mark.parametrize('criterion', dg.CRITERIA)
+@pytest.mark.parametrize('S, nc', EXACT_SHAPES)
+def test_select_host_first_pick_and_downdate_are_the_integer_arithmetic_bit_for_bit(S, nc, criterion):
+    """On integer data the statement's first pick and first downdate are one rounding away from int64 arithmetic, and that
+    rounding is a division both sides do alike: equal as bits, not to a tolerance."""
+    X, C0, CMC0 = integer_case(S, nc)
+    if criterion == 'variance':
+        CMC0 = None
+    i, gain, vstar, v, w = exact_first_pick(X, C0, CMC0)
+    Xf = X.astype(np.float64)
+    res = dg.select_host(Xf, C0, CMC0, picks=1, keep=True)
+    assert res['index'][0] == i
+    assert res['gain'].tobytes() == np.array([gain]).tobytes() and res['vstar'].tobytes() == np.array([vstar]).tobytes()
+    assert np.array_equal(res['x'][0], Xf[i])
+    assert res['v'].tobytes() == v.tobytes()
+    assert (res['w'] is None) if w is None else (res['w'].tobytes() == w.tobytes())
+    # the second pick is the first argmax of the criterion formed from those bit-exact v and w, the first pick masked
+    crit = w / (1.0 + v) if criterion == 'ivr' else v.copy()
+    crit[i] = -np.inf
+    two = dg.select_host(Xf, C0, CMC0, picks=2)
+    assert two['index'][0] == i and two['index'][1] == int(np.argmax(crit))
+    assert two['gain'].tobytes() == np.array([gain, crit.max()]).tobytes()
+
+
+@pytest.mark.parametrize('criterion', dg.CRITERIA)
+@pytest.mark.parametrize('refresh_every', (0, 5))
+def test_select_host_nan_rows_never_win_and_the_empty_pick_is_minus_one(criterion, refresh_every):
+    X, C0, CMC0 = integer_case(40, 17)
+    Xf = X.astype(np.float64)
+    Xf[[3, 20, 35], 5] = np.nan
+    res = dg.select_host(Xf, C0, CMC0 if criterion == 'ivr' else None, picks=40, refresh_every=refresh_every, keep=True)
+    finite = sorted(set(range(40)) - {3, 20, 35})
+    assert sorted(res['index'][:37].tolist()) == finite
+    assert np.all(res['index'][37:] == -1) and np.all(res['gain'][37:] == -np.inf)
+    assert np.array_equal(res['vstar'][37:], np.zeros(3)) and not res['x'][37:].any()
+    assert np.all(np.isfinite(res['gain'][:37])) and np.array_equal(np.flatnonzero(np.isnan(res['v'])), [3, 20, 35])
+    # a NaN in one row changes no other row's exact arithmetic: the first pick is the finite rows' own
+    i, gain, vstar, _, _ = exact_first_pick(X[finite], C0, CMC0 if criterion == 'ivr' else None)
+    assert res['index'][0] == finite[i] and res['gain'][0] == gain and res['vstar'][0] == vstar
+
+
 def wide_mtx(terms):
     rows = [r for r in itertools.product(range(10), repeat=3) if any(r)]
     return np.array(rows[:terms])
