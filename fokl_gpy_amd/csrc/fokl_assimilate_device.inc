@@ -354,7 +354,7 @@ extern "C" int fokl_assimilate_ensemble(fokl_ctx *ctx, const fokl_system *system
                               (double)E * SIM_LANES * steps * 4.0 * stage_flops);
             const hipError_t launched = sim_dispatch(n_states, [&](auto ns) {
                 const auto kernel = assimilate_kernel<decltype(ns)::value>;
-                if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+                if (hipError_t e = lds_opt_in(kernel, lds_bytes, SIM_LDS_BUDGET)) return e;
                 hipLaunchKernelGGL(kernel, dim3(n_draws), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, ap, tab.norm_src,
                                    tab.norm_lo, tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline,
                                    tab.bern, (const double *)d_coef, (const double *)d_forcing, (const double *)d_y0,

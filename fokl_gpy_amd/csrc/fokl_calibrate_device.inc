@@ -448,11 +448,8 @@ extern "C" int fokl_calibrate_ensemble(fokl_ctx *ctx, const fokl_system *system,
     const size_t want_bytes = (rows * (d + 1) + traj + W * (size_t)(7 * d + 1) + E * n_coef + (size_t)n_steps * s.n_forcing_cols) * sizeof(double) +
                               (rows + W * 3 + E * 4) * sizeof(int32_t) + E * 8;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    // FOKL_CALIBRATE_FREE_BYTES: count at most this much of the device's free memory as available to a call (a share of a
-    // device that other work uses; the tests' way to meet the refusal with buffers of ordinary size)
-    if (const char *cap = std::getenv("FOKL_CALIBRATE_FREE_BYTES")) free_bytes = std::min<size_t>(free_bytes, std::strtoull(cap, nullptr, 10));
+    size_t free_bytes = 0;
+    HIP_TRY(ctx, capped_free_bytes("FOKL_CALIBRATE_FREE_BYTES", &free_bytes));
     if (want_bytes + (64 << 20) > free_bytes)
         return fail(ctx, FOKL_ERR_ARG, who + "the call wants " + std::to_string(want_bytes) + " bytes on the device and 64 MiB to spare (" +
                                            std::to_string(rows * (d + 1) * sizeof(double) + rows * sizeof(int32_t)) +
@@ -496,10 +493,9 @@ extern "C" int fokl_calibrate_ensemble(fokl_ctx *ctx, const fokl_system *system,
     HIP_TRY(ctx, hipMemsetAsync(d_sums, 0, W * 4 * d * sizeof(double), ctx->stream));
 
     const double stage_flops = 8.0 * sim_terms_per_stage(sys, n_states) + 20.0 * (n_factors - s.n_forcing_factors);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipError_t err = hipEventCreate(&ev0);
-    if (err == hipSuccess) err = hipEventCreate(&ev1);
-    if (err == hipSuccess) err = hipEventRecord(ev0, ctx->stream);
+    hipError_t err = hipSuccess;
+    StreamStopwatch watch(ctx, err);
+    const int t0 = watch.mark();
     int64_t launches = 0;
     const auto launch = [&](int64_t t0, int count, int first, double *points) {
         TimedRegion timed(ctx, FOKL_K_INTEGRATE, 8.0 * (double)W * (7.0 * d + 2.0) * 2.0,
@@ -507,7 +503,7 @@ extern "C" int fokl_calibrate_ensemble(fokl_ctx *ctx, const fokl_system *system,
         ++launches;
         return sim_dispatch(n_states, [&](auto ns) {
             const auto kernel = calibrate_kernel<decltype(ns)::value>;
-            if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+            if (hipError_t e = lds_opt_in(kernel, lds_bytes, SIM_LDS_BUDGET)) return e;
             hipLaunchKernelGGL(kernel, dim3(n_draws), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, tab.norm_src, tab.norm_lo,
                                tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline, tab.bern,
                                (const int *)d_param, (const double *)d_coef, (const double *)d_forcing, (const double *)d_y0,
@@ -520,12 +516,9 @@ extern "C" int fokl_calibrate_ensemble(fokl_ctx *ctx, const fokl_system *system,
     for (int64_t t0 = 0; err == hipSuccess && t0 < iterations; t0 += per_launch)
         err = launch(t0, (int)std::min<int64_t>(per_launch, iterations - t0), t0 == 0, nullptr);
     if (err == hipSuccess && trajectories) err = launch(iterations, 0, 0, d_traj);
-    float ms = 0.f;
-    if (err == hipSuccess) err = hipEventRecord(ev1, ctx->stream);
+    const int t1 = watch.mark();
     if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (err == hipSuccess) err = hipEventElapsedTime(&ms, ev0, ev1);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
+    const double kernel_us = watch.us(t0, t1);
     if (err == hipSuccess && x_out) err = hipMemcpy(x_out, d_x, rows * d * sizeof(double), hipMemcpyDeviceToHost);
     if (err == hipSuccess && x_out) err = hipMemcpy(lp_out, d_lp_out, rows * sizeof(double), hipMemcpyDeviceToHost);
     if (err == hipSuccess && x_out) err = hipMemcpy(saturated_out, d_sat_out, rows * sizeof(int32_t), hipMemcpyDeviceToHost);
@@ -545,7 +538,7 @@ extern "C" int fokl_calibrate_ensemble(fokl_ctx *ctx, const fokl_system *system,
     rep[3] = launches;
     rep[4] = per_launch;
     rep[5] = evaluations;
-    rep[6] = (int64_t)std::llround((double)ms * 1000.0);
+    rep[6] = (int64_t)std::llround(kernel_us);
     rep[7] = iterations;
     return FOKL_OK;
 }

@@ -332,7 +332,7 @@ extern "C" int fokl_control_cvar_solve(fokl_ctx *ctx, const fokl_system *system,
         HIP_TRY(ctx, pooled_fill_nan(d_phi_t, S * SIM_LANES));
         HIP_TRY(ctx, pooled_fill_nan(d_a_t, S * SIM_LANES));
     }
-    HIP_TRY(ctx, sim_lds_attribute(control_cvar_risk_kernel, risk_lds));
+    HIP_TRY(ctx, lds_opt_in(control_cvar_risk_kernel, risk_lds, SIM_LDS_BUDGET));
 
     const double pass_flops = (double)B * SIM_LANES * (double)s.n_steps * 4.0 * (8.0 * sim_terms_per_stage(sys, n_states) + 20.0 * s.n_factors);
     const int chunk_blocks = (n + n2 + CTL_POOL_BLOCK - 1) / CTL_POOL_BLOCK;

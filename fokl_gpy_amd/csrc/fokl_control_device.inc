@@ -682,7 +682,7 @@ hipError_t ctl_iterate(fokl_ctx *ctx, int n_states, int grid, size_t lds_bytes, 
 {
     return sim_dispatch(n_states, [&](auto ns) {
         const auto kernel = control_iterate_kernel<decltype(ns)::value>;
-        if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+        if (hipError_t e = lds_opt_in(kernel, lds_bytes, SIM_LDS_BUDGET)) return e;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, d.tab.norm_src, d.tab.norm_lo,
                            d.tab.norm_span, d.tab.fac_norm, d.tab.fac_row, d.tab.fac_degree, d.tab.entries, d.tab.spline, d.tab.bern,
                            d.ct.norm_control, d.ct.seg_first, d.ct.ref, (const double *)d.coef, (const double *)d.forcing,
@@ -698,7 +698,7 @@ hipError_t ctl_trajectory(fokl_ctx *ctx, int n_states, int grid, size_t lds_byte
 {
     return sim_dispatch(n_states, [&](auto ns) {
         const auto kernel = control_trajectory_kernel<decltype(ns)::value>;
-        if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+        if (hipError_t e = lds_opt_in(kernel, lds_bytes, SIM_LDS_BUDGET)) return e;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, d.tab.norm_src, d.tab.norm_lo,
                            d.tab.norm_span, d.tab.fac_norm, d.tab.fac_row, d.tab.fac_degree, d.tab.entries, d.tab.spline, d.tab.bern,
                            d.ct.norm_control, d.ct.seg_first, d.ct.ref, (const double *)d.coef, (const double *)d.forcing,

@@ -281,7 +281,7 @@ hipError_t pooled_tangent(fokl_ctx *ctx, int n_states, int grid, size_t lds_byte
 {
     return sim_dispatch(n_states, [&](auto ns) {
         const auto kernel = control_pooled_tangent_kernel<decltype(ns)::value>;
-        if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+        if (hipError_t e = lds_opt_in(kernel, lds_bytes, SIM_LDS_BUDGET)) return e;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, d.tab.norm_src, d.tab.norm_lo,
                            d.tab.norm_span, d.tab.fac_norm, d.tab.fac_row, d.tab.fac_degree, d.tab.entries, d.tab.spline, d.tab.bern,
                            d.ct.norm_control, d.ct.seg_first, d.ct.ref, (const double *)d.coef, (const double *)d.forcing,
@@ -295,7 +295,7 @@ hipError_t pooled_trial(fokl_ctx *ctx, int n_states, int grid, size_t lds_bytes,
 {
     return sim_dispatch(n_states, [&](auto ns) {
         const auto kernel = control_pooled_trial_kernel<decltype(ns)::value>;
-        if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+        if (hipError_t e = lds_opt_in(kernel, lds_bytes, SIM_LDS_BUDGET)) return e;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, cp, d.tab.norm_src, d.tab.norm_lo,
                            d.tab.norm_span, d.tab.fac_norm, d.tab.fac_row, d.tab.fac_degree, d.tab.entries, d.tab.spline, d.tab.bern,
                            d.ct.norm_control, d.ct.seg_first, d.ct.ref, (const double *)d.coef, (const double *)d.forcing,
@@ -481,9 +481,8 @@ struct PooledWork {
 // `what` spells the workspace out for the refusal
 int pooled_workspace_fits(fokl_ctx *ctx, const std::string &who, size_t workspace, const char *cap_env, const std::string &what)
 {
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    if (const char *cap = std::getenv(cap_env)) free_bytes = std::min<size_t>(free_bytes, std::strtoull(cap, nullptr, 10));
+    size_t free_bytes = 0;
+    HIP_TRY(ctx, capped_free_bytes(cap_env, &free_bytes));
     if (workspace > free_bytes)
         return fail(ctx, FOKL_ERR_ARG, who + "the workspace needs " + std::to_string(workspace) + " bytes (" + what + "), the device has " +
                                            std::to_string(free_bytes) + " free (" + cap_env +

@@ -9,8 +9,9 @@
 //   CMC <- CMC - (u a' + a u') / d + u u' w* / d^2
 //   v_s <- v_s - p_s^2 / d,  w_s <- w_s - 2 p_s q_s / d + p_s^2 w* / d^2     with p_s = x_s' u, q_s = x_s' a
 // Three kernels, all queued on the context's stream by fokl_design_select with no host round trip between the picks:
-//   design_quadform_kernel   v (and w) of every row from the matrices: the first pass and every refresh.  score_kernel's
-//                            shape: one wavefront per 16-row tile, the tile's basis values in LDS [jp][16], the symmetric
+//   design_quadform_kernel   v (and w) of every row from the matrices: the first pass and every refresh.  The draw tile's
+//                            shape and tile load (fokl_draw_tile.inc) with a product of its own: one wavefront per 16-row
+//                            tile, the tile's basis values in LDS [jp][16], the symmetric
 //                            matrix streamed from global memory as the A operand of v_mfma_f64_16x16x4_f64, 16 of its rows
 //                            at a time: D[j][row] = sum_k C[j][k] x[k][row], and each lane multiplies its D[j][row] by
 //                            x[j][row] and accumulates; the four quarters of a row merge in their order.
@@ -52,8 +53,7 @@ __global__ __launch_bounds__(WAVE) void design_quadform_kernel(double *const *__
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t r = tile * 16 + col;
         const bool in = r < n;
-        for (int k = quad; k < jp; k += 4)
-            xs[k * 16 + col] = (in && k < nc) ? *(__attribute__((address_space(1))) const double *)(slot_ptr[slots[k]] + r) : 0.0;
+        draw_tile_load(xs, slot_ptr, slots, nc, jp, r, in, quad, col);
         __syncthreads();                                 // one wavefront per workgroup: orders the LDS traffic
 
         double sv = 0.0, sw = 0.0;
@@ -315,11 +315,8 @@ extern "C" int fokl_design_select(fokl_ctx *ctx, const int32_t *slots, int nc, c
     const size_t mat_doubles = (size_t)jp * jp;
     const size_t row_bytes = (size_t)n * (sizeof(double) * (ivr ? 2 : 1) + 1);
     const size_t fixed_bytes = mat_doubles * sizeof(double) * (ivr ? 2 : 1) + (size_t)picks * (nc + 3) * sizeof(double);
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    // FOKL_DESIGN_FREE_BYTES: count at most this much of the device's free memory as available to a call (as
-    // FOKL_SCORE_FREE_BYTES does for fokl_score_rows)
-    if (const char *cap = std::getenv("FOKL_DESIGN_FREE_BYTES")) free_bytes = std::min<size_t>(free_bytes, std::strtoull(cap, nullptr, 10));
+    size_t free_bytes = 0;
+    HIP_TRY(ctx, capped_free_bytes("FOKL_DESIGN_FREE_BYTES", &free_bytes));
     if (row_bytes + fixed_bytes + (64 << 20) > free_bytes)
         return fail(ctx, FOKL_ERR_ARG, "fokl_design_select: the call wants " + std::to_string(row_bytes + fixed_bytes) +
                     " bytes on the device and 64 MiB to spare (" + std::to_string(row_bytes) + " per-row bytes = rows x " +
@@ -366,34 +363,16 @@ extern "C" int fokl_design_select(fokl_ctx *ctx, const int32_t *slots, int nc, c
     auto quadform = ivr ? design_quadform_kernel<true> : design_quadform_kernel<false>;
     auto step = ivr ? design_step_kernel<true> : design_step_kernel<false>;
     auto pivot = ivr ? design_pivot_kernel<true> : design_pivot_kernel<false>;
-    if (lds_bytes > 64 * 1024)
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(quadform), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         160 * 1024));
+    HIP_TRY(ctx, lds_opt_in(quadform, lds_bytes, 160 * 1024));
 
-    // events: the whole queue and every first-pass / refresh launch always; with timing on also every step and pivot launch
-    std::vector<hipEvent_t> events;
-    struct EventsGuard {
-        std::vector<hipEvent_t> &ev;
-        ~EventsGuard()
-        {
-            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        }
-    } guard{events};
+    // marks: the whole queue and every first-pass / refresh launch always; with timing on also every step and pivot launch
     hipError_t e = hipSuccess;
-    auto mark = [&]() -> int {
-        hipEvent_t ev = nullptr;
-        if (e == hipSuccess) e = hipEventCreate(&ev);
-        if (e == hipSuccess) {
-            events.push_back(ev);
-            e = hipEventRecord(ev, ctx->stream);
-        }
-        return (int)events.size() - 1;
-    };
+    StreamStopwatch watch(ctx, e);
     std::vector<std::pair<int, int>> q_marks, s_marks, p_marks;
     const bool split = ctx->timing;
     int refreshes = 0;
     int64_t launches = 0;
-    const int total0 = mark();
+    const int total0 = watch.mark();
     {
         const double nn = (double)n, passes = 1.0 + (refresh_every ? (picks - 1) / refresh_every : 0);
         TimedRegion timed(ctx, FOKL_K_DESIGN, 8.0 * nn * ((double)nc * (passes + picks) + 4.0 * picks),
@@ -401,26 +380,26 @@ extern "C" int fokl_design_select(fokl_ctx *ctx, const int32_t *slots, int nc, c
         for (int k = 0; k < picks && e == hipSuccess; ++k) {
             const bool fresh = k == 0 || (refresh_every > 0 && k % refresh_every == 0);
             if (fresh) {
-                const int m0 = mark();
+                const int m0 = watch.mark();
                 hipLaunchKernelGGL(quadform, dim3(grid_q), dim3(WAVE), lds_bytes, ctx->stream, ctx->d_slot_ptr, d_slots, nc, ncp,
                                    jp, d_C, d_CMC, n, d_v, d_w);
                 if (e == hipSuccess) e = hipGetLastError();
-                q_marks.push_back({m0, mark()});
+                q_marks.push_back({m0, watch.mark()});
                 refreshes += k > 0;
                 ++launches;
             }
-            const int m1 = split ? mark() : 0;
+            const int m1 = split ? watch.mark() : 0;
             hipLaunchKernelGGL(step, dim3(grid_s), dim3(DS_STEP_THREADS), 0, ctx->stream, ctx->d_slot_ptr, d_slots, nc, jp, d_u,
                                d_a, d_scal, fresh ? 0 : 1, d_mask, n, d_v, d_w, d_part, d_part_i);
             if (e == hipSuccess) e = hipGetLastError();
-            const int m2 = split ? mark() : 0;
+            const int m2 = split ? watch.mark() : 0;
             hipLaunchKernelGGL(pivot, dim3(1), dim3(DS_PIVOT_THREADS), 0, ctx->stream, ctx->d_slot_ptr, d_slots, nc, jp, d_part,
                                d_part_i, grid_s, k, replicates ? 1 : 0, d_C, d_CMC, d_u, d_a, d_scal, d_mask, d_index, d_gain,
                                d_vstar, d_x);
             if (e == hipSuccess) e = hipGetLastError();
             if (split) {
                 s_marks.push_back({m1, m2});
-                p_marks.push_back({m2, mark()});
+                p_marks.push_back({m2, watch.mark()});
             }
             launches += 2;
         }
@@ -431,24 +410,14 @@ extern "C" int fokl_design_select(fokl_ctx *ctx, const int32_t *slots, int nc, c
             ++launches;
         }
     }
-    const int total1 = mark();
+    const int total1 = watch.mark();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     auto span = [&](const std::vector<std::pair<int, int>> &marks) -> int64_t {
         double sum = 0.0;
-        for (const auto &m : marks) {
-            float ms = 0.f;
-            if (e == hipSuccess) e = hipEventElapsedTime(&ms, events[m.first], events[m.second]);
-            sum += ms;
-        }
-        return (int64_t)std::llround(sum * 1000.0);
+        for (const auto &m : marks) sum += watch.us(m.first, m.second);
+        return (int64_t)std::llround(sum);
     };
-    int64_t us_total = 0, us_q = 0, us_s = 0, us_p = 0;
-    if (e == hipSuccess) {
-        us_total = span({{total0, total1}});
-        us_q = span(q_marks);
-        us_s = span(s_marks);
-        us_p = span(p_marks);
-    }
+    const int64_t us_total = span({{total0, total1}}), us_q = span(q_marks), us_s = span(s_marks), us_p = span(p_marks);
     std::vector<double> res((size_t)picks * (nc + 2));
     if (e == hipSuccess) e = hipMemcpy(index_out, d_index, (size_t)picks * sizeof(int64_t), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(res.data(), d_res, res.size() * sizeof(double), hipMemcpyDeviceToHost);

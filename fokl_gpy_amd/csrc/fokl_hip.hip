@@ -174,6 +174,33 @@ struct DeviceBuffers {
     }
 };
 
+// The device's free bytes as a call may count on them: at most what the environment variable `cap_env` says (a share of a
+// device that other work uses; the tests' way to meet a call's refusal with buffers of ordinary size)
+static hipError_t capped_free_bytes(const char *cap_env, size_t *free_bytes)
+{
+    size_t total_bytes = 0;
+    const hipError_t e = hipMemGetInfo(free_bytes, &total_bytes);
+    if (e != hipSuccess) return e;
+    if (const char *cap = std::getenv(cap_env)) *free_bytes = std::min<size_t>(*free_bytes, std::strtoull(cap, nullptr, 10));
+    return hipSuccess;
+}
+
+// A kernel that wants more than 64 KiB of dynamic LDS has to be told so; `limit` is the most the call site lets it have
+template <class Kernel>
+static hipError_t lds_opt_in(Kernel kernel, size_t lds_bytes, size_t limit)
+{
+    if (lds_bytes <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit);
+}
+
+// betas[draws][nc] as the draw tile's coefficient table (fokl_draw_tile.inc: draw_product): transposed to dst[ncp][dp],
+// the padding columns nc .. ncp and the padding draws draws .. dp zero
+static void fill_draw_table(double *dst, const double *betas, int draws, int nc, int ncp, int dp)
+{
+    for (int k = 0; k < ncp; ++k)
+        for (int d = 0; d < dp; ++d) dst[(size_t)k * dp + d] = (k < nc && d < draws) ? betas[(size_t)d * nc + k] : 0.0;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // timing helpers: HIP events on the context's own stream
 // ---------------------------------------------------------------------------------------------------------
@@ -210,6 +237,41 @@ struct TimedRegion {
         if (!ctx->timing || !start || !stop) return;
         (void)hipEventRecord(stop, ctx->stream);
         ctx->pending.push_back({id, start, stop});
+    }
+};
+
+// The time of a call's own launches on the context's stream, for its report, whether timing is on or not: mark() before and
+// after them, us(a, b) once the caller has synchronised the stream.  It shares the caller's error variable `e`: after the
+// first HIP error, its own or the caller's, mark() and us() do nothing (us: 0.0), and whatever it records lands there.  The
+// events are destroyed on every way out of the scope.
+struct StreamStopwatch {
+    hipStream_t stream;
+    hipError_t &e;
+    std::vector<hipEvent_t> events;
+    StreamStopwatch(fokl_ctx *ctx, hipError_t &err) : stream(ctx->stream), e(err) {}
+    StreamStopwatch(const StreamStopwatch &) = delete;
+    StreamStopwatch &operator=(const StreamStopwatch &) = delete;
+    ~StreamStopwatch()
+    {
+        for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
+    }
+    // a new event recorded on the stream; its index (meaningless after an error, when us() does not look at it)
+    int mark()
+    {
+        hipEvent_t ev = nullptr;
+        if (e == hipSuccess) e = hipEventCreate(&ev);
+        if (e == hipSuccess) {
+            events.push_back(ev);
+            e = hipEventRecord(ev, stream);
+        }
+        return (int)events.size() - 1;
+    }
+    // microseconds from mark a to mark b, not rounded
+    double us(int a, int b)
+    {
+        float ms = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, events[a], events[b]);
+        return (double)ms * 1000.0;
     }
 };
 
@@ -1816,6 +1878,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_comm.inc"
 #include "fokl_chain_device.inc"
 #include "fokl_spectral_device.inc"
+#include "fokl_draw_tile.inc"
 #include "fokl_predict.inc"
 #include "fokl_population.inc"
 #include "fokl_integrate_device.inc"

@@ -233,11 +233,8 @@ extern "C" int fokl_infer_inputs(fokl_ctx *ctx, int d, int n_terms, const int32_
     const size_t want_bytes = (rows * (d + 1) + E * K * nc + E * OP_LANES * 4 * d) * sizeof(double) + E * OP_LANES * 2 * sizeof(int32_t) +
                               E * 24;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    // FOKL_INFER_FREE_BYTES: count at most this much of the device's free memory as available to a call (a share of a
-    // device that other work uses; the tests' way to meet the refusal with buffers of ordinary size)
-    if (const char *cap = std::getenv("FOKL_INFER_FREE_BYTES")) free_bytes = std::min<size_t>(free_bytes, std::strtoull(cap, nullptr, 10));
+    size_t free_bytes = 0;
+    HIP_TRY(ctx, capped_free_bytes("FOKL_INFER_FREE_BYTES", &free_bytes));
     if (want_bytes + (64 << 20) > free_bytes)
         return fail(ctx, FOKL_ERR_ARG, who + "the call wants " + std::to_string(want_bytes) + " bytes on the device and 64 MiB to spare (" +
                                            std::to_string(rows * (d + 1) * sizeof(double)) + " bytes of kept rows = draws x kept x 64 x (d + 1) x 8, " +
@@ -287,18 +284,15 @@ extern "C" int fokl_infer_inputs(fokl_ctx *ctx, int d, int n_terms, const int32_
     HIP_TRY(ctx, buf.get(&d_evals, E));
     HIP_TRY(ctx, hipMemsetAsync(d_sums, 0, E * OP_LANES * 4 * d * sizeof(double), ctx->stream));
 
-    if (lds_bytes > 64 * 1024)
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(infer_inputs_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)OP_LDS_BUDGET));
+    HIP_TRY(ctx, lds_opt_in(infer_inputs_kernel, lds_bytes, OP_LDS_BUDGET));
     // a launch is asked for at most `cap` term evaluations by a wavefront: whole draws, at least one
     const int64_t iterations = (int64_t)burnin + draws;
     const double per_draw = (2.0 * (double)iterations + 1.0) * (double)K * (double)std::max(1, n_terms);
     const int64_t cap = term_cap ? term_cap : FOKL_INFER_TERM_CAP;
     const int64_t per_launch = (int64_t)std::max(1.0, std::min((double)n_draws, std::floor((double)cap / per_draw)));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipError_t err = hipEventCreate(&ev0);
-    if (err == hipSuccess) err = hipEventCreate(&ev1);
-    if (err == hipSuccess) err = hipEventRecord(ev0, ctx->stream);
+    hipError_t err = hipSuccess;
+    StreamStopwatch watch(ctx, err);
+    const int t0 = watch.mark();
     int64_t launches = 0;
     for (int64_t first = 0; err == hipSuccess && first < n_draws; first += per_launch) {
         const int grid = (int)std::min<int64_t>(per_launch, n_draws - first);
@@ -311,12 +305,9 @@ extern "C" int fokl_infer_inputs(fokl_ctx *ctx, int d, int n_terms, const int32_
         err = hipGetLastError();
         ++launches;
     }
-    float ms = 0.f;
-    if (err == hipSuccess) err = hipEventRecord(ev1, ctx->stream);
+    const int t1 = watch.mark();
     if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (err == hipSuccess) err = hipEventElapsedTime(&ms, ev0, ev1);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
+    const double kernel_us = watch.us(t0, t1);
     if (err == hipSuccess && x_out) err = hipMemcpy(x_out, d_x, rows * d * sizeof(double), hipMemcpyDeviceToHost);
     if (err == hipSuccess && x_out) err = hipMemcpy(lp_out, d_lp, rows * sizeof(double), hipMemcpyDeviceToHost);
     if (err == hipSuccess) err = hipMemcpy(sums_out, d_sums, E * OP_LANES * 4 * d * sizeof(double), hipMemcpyDeviceToHost);
@@ -331,7 +322,7 @@ extern "C" int fokl_infer_inputs(fokl_ctx *ctx, int d, int n_terms, const int32_
     rep[1] = (int64_t)lds_rows;
     rep[2] = std::min<int64_t>(per_launch, n_draws);
     rep[3] = launches;
-    rep[4] = (int64_t)std::llround((double)ms * 1000.0);
+    rep[4] = (int64_t)std::llround(kernel_us);
     rep[5] = iterations;
     rep[6] = evaluations;
     rep[7] = per_launch;

@@ -412,9 +412,7 @@ hipError_t op_pick(Kernel *uniform, Kernel *per_lane, int n_starts, size_t lds_b
 {
     *kernel = n_starts % fokl::OP_LANES == 0 ? uniform : per_lane;
     *raised = lds_bytes > 64 * 1024;
-    if (!*raised) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(*kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)fokl::OP_LDS_BUDGET);
+    return lds_opt_in(*kernel, lds_bytes, fokl::OP_LDS_BUDGET);
 }
 
 }  // namespace

@@ -274,9 +274,7 @@ extern "C" int fokl_population_stats(fokl_ctx *ctx, const int32_t *slots, int nc
     unsigned long long *d_above = reinterpret_cast<unsigned long long *>(d_buf + above_off);
 
     auto fn = reg ? fokl::population_kernel<true> : fokl::population_kernel<false>;
-    hipError_t e = hipSuccess;
-    if (lds_bytes > 64 * 1024)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
+    hipError_t e = lds_opt_in(fn, lds_bytes, 136 * 1024);
     if (e == hipSuccess) {
         const double *dev_betas = reinterpret_cast<const double *>(ctx->d_args + beta_off);
         const double *dev_data = with_data ? ctx->slot_ptr[FOKL_SLOT_Y] : nullptr;

@@ -111,11 +111,10 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__re
     }
 }
 
-// The same on the matrix pipe, for the case that costs: bounds over many draws.  One wavefront per tile of 16 rows;
-// D[draw][row] = betas[draw][:] . X[row][:] comes out of v_mfma_f64_16x16x4_f64 in tiles of 16 draws (A = draw
-// coefficients, transposed and zero padded on the host to [ncp][dp] so that a fragment is one 128-byte run per term;
-// B = the tile's basis values in LDS [term][row]), PM_DT tiles at a time so that the pipe sees independent chains.
-// A lane ends up with the draws (l >> 4) + 4 v of row l & 15, i.e. a quarter of the draws of one row.
+// The same on the matrix pipe, for the case that costs: bounds over many draws.  One wavefront per tile of 16 rows, the
+// tile's basis values in LDS [term][row], and D[draw][row] = betas[draw][:] . X[row][:] in blocks of PM_DT x 16 draws: the
+// draw tile's product (fokl_draw_tile.inc: the coefficient table, the lane map and what happens past the last draw); a lane
+// ends up with a quarter of the draws of one row.
 //
 // Order statistics without sorting a thousand values per row: the row's predictions have mean x'mean(beta) and
 // variance x'Cov(beta)x (O(P^2) per row, against O(P draws) for the predictions), so only values beyond
@@ -151,8 +150,7 @@ __global__ __launch_bounds__(PM_THREADS) void predict_mfma_kernel(double *const 
     for (; tile < n_tiles; tile += gridDim.x) {
         const int64_t r = tile * 16 + col;
         const bool in = r < n;
-        for (int k = quad; k < ncp; k += 4)
-            xs[k * 16 + col] = (in && k < nc) ? *(__attribute__((address_space(1))) const double *)(slot_ptr[slots[k]] + r) : 0.0;
+        draw_tile_load(xs, slot_ptr, slots, nc, ncp, r, in, quad, col);
         __syncthreads();                                 // one wavefront per workgroup: orders the LDS traffic
 
         // moments of this row's predictions over the draws; the covariance entries are wave uniform (scalar loads)
@@ -177,6 +175,7 @@ __global__ __launch_bounds__(PM_THREADS) void predict_mfma_kernel(double *const 
             }
             total = 0.0;
             for (int d0 = 0; d0 < dp; d0 += 16 * PM_DT) {
+                // draw_product<PM_DT> written out (fokl_draw_tile.inc states the format, and why this kernel has a copy)
                 d4 acc[PM_DT];
                 const double *a_ptr[PM_DT];
 #pragma unroll
@@ -379,8 +378,7 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
         std::memcpy(ctx->h_args, slots, (size_t)nc * sizeof(int));
         double *bt = reinterpret_cast<double *>(ctx->h_args + beta_off);
         std::memset(bt, 0, arg_bytes - beta_off);
-        for (int d = 0; d < draws; ++d)
-            for (int k = 0; k < nc; ++k) bt[(size_t)k * dp + d] = betas[(size_t)d * nc + k];
+        fill_draw_table(bt, betas, draws, nc, ncp, dp);
         // mean and (population) covariance of the draws: the filter's model of a row's predictions
         double *bm = bt + (size_t)ncp * dp, *bc = bm + ncp;
         for (int k = 0; k < nc; ++k) {
@@ -410,10 +408,7 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
         unsigned long long *d_tally = reinterpret_cast<unsigned long long *>(ctx->d_args + tally_off);
         const int64_t tiles = ((int64_t)n + 15) / 16;
         const int grid = (int)std::min<int64_t>(tiles, (int64_t)cu_count(ctx) * 16);
-        hipError_t le = hipSuccess;
-        if (lds_mfma > 64 * 1024)
-            le = hipFuncSetAttribute(reinterpret_cast<const void *>(predict_mfma_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+        hipError_t le = lds_opt_in(predict_mfma_kernel, lds_mfma, 152 * 1024);
         if (le != hipSuccess) {
             (void)hipFree(d_res);
             return fail(ctx, FOKL_ERR_HIP, std::string("fokl_predict: ") + hipGetErrorString(le));
@@ -485,9 +480,7 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
     {
         auto fn = wide ? (global_lists ? predict_kernel<true, true> : predict_kernel<false, true>)
                        : (global_lists ? predict_kernel<true, false> : predict_kernel<false, false>);
-        hipError_t e = hipSuccess;
-        if (lds_bytes > 64 * 1024)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+        hipError_t e = lds_opt_in(fn, lds_bytes, 152 * 1024);
         if (e == hipSuccess) {
             TimedRegion timed(ctx, FOKL_K_PREDICT, 8.0 * (double)n * (nc + 3), 2.0 * (double)n * nc * draws);
             hipLaunchKernelGGL(fn, dim3(grid), dim3(PR_THREADS), lds_bytes, ctx->stream, ctx->d_slot_ptr,

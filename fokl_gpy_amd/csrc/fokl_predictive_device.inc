@@ -2,10 +2,9 @@
 // (textually included by fokl_hip.hip).  The statement is fokl_gpy_amd/predictive.py: predictive_rows_host.
 //
 // The predictive of a row is the equal-weight mixture over the draws of N(mu_d, sd_d^2), mu_d = X_row . beta_d.  The product
-// is score_kernel's: one wavefront per tile of 16 rows, the tile's basis values in LDS [ncp][16], D[draw][row] out of
-// v_mfma_f64_16x16x4_f64 in blocks of PD_DT x 16 draws (A = the transposed coefficients [ncp][dp]); lane l ends up with the
-// draws (l >> 4) + 4 v of row l & 15.  mu is never stored: the PASS LOOP goes around the product, which is recomputed in
-// every pass, so that there is no limit on the draws and LDS holds the columns only.
+// is the draw tile's (fokl_draw_tile.inc: the coefficient table and the lane map): one wavefront per tile of 16 rows, the
+// tile's basis values in LDS [ncp][16], blocks of PD_DT x 16 draws.  mu is never stored: the PASS LOOP goes around the
+// product, which is recomputed in every pass, so that there is no limit on the draws and LDS holds the columns only.
 //   pass 0      s1 = sum(mu - mu0), s2 = sum((mu - mu0)^2), min and max of mu, per quantile j the exact bracket lo_j =
 //               min(mu + sd z_j), hi_j = max(mu + sd z_j) and, with data, pit = sum 0.5 erfc((mu - y) rinv) / E
 //   first trial q_j = mean + z_j sqrt(var) where strictly inside (lo_j, hi_j), else the midpoint
@@ -30,31 +29,6 @@ struct PdArgs {
     double ftol, xtol, mean_sigsqd, sd_max, e_sqrt_pi;
     int Q, max_passes;
 };
-
-// acc[t][v] = mu of draw d0 + 16 t + quad + 4 v of row col (blocks past dp re-read the last one and are skipped later)
-__device__ __forceinline__ void pd_product(const double *xs, const double *__restrict__ betas_t, int ncp, int dp, int d0,
-                                           int quad, int col, d4 (&acc)[PD_DT])
-{
-    const double *a_ptr[PD_DT];
-#pragma unroll
-    for (int t = 0; t < PD_DT; ++t) {
-        acc[t] = (d4){0.0, 0.0, 0.0, 0.0};
-        a_ptr[t] = betas_t + (size_t)quad * dp + min(d0 + 16 * t, dp - 16) + col;
-    }
-    double a_now[PD_DT], a_next[PD_DT];
-#pragma unroll
-    for (int t = 0; t < PD_DT; ++t) a_now[t] = a_ptr[t][0];
-    for (int k0 = 0; k0 < ncp; k0 += 4) {
-        const double b = xs[(k0 + quad) * 16 + col];
-        const int kn = k0 + 4 < ncp ? k0 + 4 : k0;               // the next step's coefficients travel during this step's MFMAs
-#pragma unroll
-        for (int t = 0; t < PD_DT; ++t) a_next[t] = a_ptr[t][(size_t)kn * dp];
-#pragma unroll
-        for (int t = 0; t < PD_DT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_now[t], b, acc[t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < PD_DT; ++t) a_now[t] = a_next[t];
-    }
-}
 
 // acc[i >> 2][i & 3] for a wave-uniform i: a chain of selects, so that the loop over a lane's sixteen draws can stay rolled
 // without the accumulators leaving their registers
@@ -90,8 +64,7 @@ __global__ __launch_bounds__(PD_THREADS) void predictive_kernel(double *const *_
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t r = tile * 16 + col;
         const bool in = r < n;
-        for (int k = quad; k < ncp; k += 4)
-            xs[k * 16 + col] = (in && k < nc) ? *(__attribute__((address_space(1))) const double *)(slot_ptr[slots[k]] + r) : 0.0;
+        draw_tile_load(xs, slot_ptr, slots, nc, ncp, r, in, quad, col);
         const double yv = (in && data) ? data[r] : 0.0;
         __syncthreads();                                 // one wavefront per workgroup: orders the LDS traffic
 
@@ -106,7 +79,7 @@ __global__ __launch_bounds__(PD_THREADS) void predictive_kernel(double *const *_
         }
         for (int d0 = 0; d0 < dp; d0 += 16 * PD_DT) {
             d4 acc[PD_DT];
-            pd_product(xs, betas_t, ncp, dp, d0, quad, col, acc);
+            draw_product<PD_DT>(xs, betas_t, ncp, dp, d0, quad, col, acc);
             if (d0 == 0) mu0 = __shfl(acc[0][0], col, WAVE);         // draw 0 of row col: quarter 0, v = 0
 #pragma unroll 1
             for (int i = 0; i < 4 * PD_DT; ++i) {                    // rolled: one copy of erfc in the code, not sixteen
@@ -177,7 +150,7 @@ __global__ __launch_bounds__(PD_THREADS) void predictive_kernel(double *const *_
                 }
                 for (int d0 = 0; d0 < dp; d0 += 16 * PD_DT) {
                     d4 acc[PD_DT];
-                    pd_product(xs, betas_t, ncp, dp, d0, quad, col, acc);
+                    draw_product<PD_DT>(xs, betas_t, ncp, dp, d0, quad, col, acc);
 #pragma unroll 1
                     for (int i = 0; i < 4 * PD_DT; ++i) {            // rolled: QM copies of erfc and exp, not 16 QM
                         const int d = d0 + 16 * (i >> 2) + quad + 4 * (i & 3);
@@ -299,11 +272,8 @@ extern "C" int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc,
     const size_t table_bytes = ((size_t)ncp + 2) * dp * sizeof(double);
     const size_t out_bytes = (size_t)n * stride * sizeof(double);
     const size_t count_bytes = (size_t)tiles * sizeof(int);
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    // FOKL_PREDICTIVE_FREE_BYTES: count at most this much of the device's free memory as available to a call (a share of a
-    // device that other work uses; the tests' way to meet the refusal with buffers of ordinary size)
-    if (const char *cap = std::getenv("FOKL_PREDICTIVE_FREE_BYTES")) free_bytes = std::min<size_t>(free_bytes, std::strtoull(cap, nullptr, 10));
+    size_t free_bytes = 0;
+    HIP_TRY(ctx, capped_free_bytes("FOKL_PREDICTIVE_FREE_BYTES", &free_bytes));
     if (table_bytes + out_bytes + count_bytes + (64 << 20) > free_bytes)
         return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: the call wants " + std::to_string(table_bytes + out_bytes + count_bytes) +
                     " bytes on the device and 64 MiB to spare (" + std::to_string(table_bytes) +
@@ -313,8 +283,7 @@ extern "C" int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc,
 
     // coefficients transposed and zero padded [ncp][dp] | sd [dp] | rinv [dp] (padding draws: zeros, never used)
     std::vector<double> table(((size_t)ncp + 2) * dp, 0.0);
-    for (int d = 0; d < draws; ++d)
-        for (int k = 0; k < nc; ++k) table[(size_t)k * dp + d] = betas[(size_t)d * nc + k];
+    fill_draw_table(table.data(), betas, draws, nc, ncp, dp);
     double *scal = table.data() + (size_t)ncp * dp;
     for (int d = 0; d < draws; ++d) {
         scal[d] = sd[d];
@@ -347,14 +316,9 @@ extern "C" int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc,
     const int waves = nq == 0 ? 16 : nq <= 4 ? 12 : 8;
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(waves, 160 * 1024 / lds_bytes));
     const int grid = (int)std::min<int64_t>(tiles, (int64_t)cu_count(ctx) * per_cu);
-    hipError_t e = hipSuccess;
-    if (lds_bytes > 64 * 1024)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (e == hipSuccess) e = hipEventCreate(&ev0);
-    if (e == hipSuccess) e = hipEventCreate(&ev1);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventRecord(ev0, ctx->stream);
+    hipError_t e = lds_opt_in(fn, lds_bytes, 160 * 1024);
+    StreamStopwatch watch(ctx, e);
+    const int t0 = watch.mark();
     if (e == hipSuccess) {
         TimedRegion timed(ctx, FOKL_K_PREDICTIVE, 0.0, 0.0);             // bytes and flops: below, of the passes that ran
         hipLaunchKernelGGL(fn, dim3(grid), dim3(PD_THREADS), lds_bytes, ctx->stream, ctx->d_slot_ptr, d_slots, nc, ncp, d_table,
@@ -362,11 +326,9 @@ extern "C" int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc,
                            args, d_out, d_count);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipEventRecord(ev1, ctx->stream);
+    const int t1 = watch.mark();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
+    const double kernel_us = watch.us(t0, t1);
     std::vector<int> count((size_t)tiles, 0);
     if (e == hipSuccess) e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(count.data(), d_count, count_bytes, hipMemcpyDeviceToHost);
@@ -395,6 +357,6 @@ extern "C" int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc,
     rep[5] = most;
     rep[6] = sum;
     rep[7] = unresolved;
-    rep[8] = (int64_t)std::llround((double)ms * 1000.0);
+    rep[8] = (int64_t)std::llround(kernel_us);
     return FOKL_OK;
 }

@@ -266,11 +266,9 @@ extern "C" int fokl_resample_chains(fokl_ctx *ctx, int p1, const double *lamb, c
     // the smallest instance that holds the model: T = 1, 2, 3, 4, 6, 8, 12 elements per lane
     const int need = (p1 + 63) / 64;
     const int T = need <= 4 ? need : need <= 6 ? 6 : need <= 8 ? 8 : 12;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    HIP_TRY(ctx, hipEventCreate(&ev0));
-    hipError_t e = hipEventCreate(&ev1);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventRecord(ev0, ctx->stream);
+    hipError_t e = hipSuccess;
+    StreamStopwatch watch(ctx, e);
+    const int t0 = watch.mark();
     if (e == hipSuccess) {
         const int64_t iters = (int64_t)burnin + draws;
         TimedRegion timed(ctx, FOKL_K_RESAMPLE, (double)row_bytes, 40.0 * (double)chains * (double)iters * p1);
@@ -284,11 +282,9 @@ extern "C" int fokl_resample_chains(fokl_ctx *ctx, int p1, const double *lamb, c
         default: e = launch_resample<12>(args, waves, ctx->stream); break;
         }
     }
-    if (e == hipSuccess) e = hipEventRecord(ev1, ctx->stream);
+    const int t1 = watch.mark();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
-    (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
+    const double kernel_us = watch.us(t0, t1);
     if (e == hipSuccess) e = hipMemcpy(sums_out, args.sums, n_sums * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(counts_out, args.counts, (size_t)chains * 4 * sizeof(int64_t), hipMemcpyDeviceToHost);
     if (e == hipSuccess && rows) e = hipMemcpy(w_out, args.w, row_bytes, hipMemcpyDeviceToHost);
@@ -310,7 +306,7 @@ extern "C" int fokl_resample_chains(fokl_ctx *ctx, int p1, const double *lamb, c
     rep[3] = waves;
     rep[4] = attempts;
     rep[5] = most;
-    rep[6] = (int64_t)std::llround((double)ms * 1000.0);
+    rep[6] = (int64_t)std::llround(kernel_us);
     rep[7] = (chains + waves - 1) / waves;
     rep[8] = flagged;
     rep[9] = kept;

@@ -471,14 +471,6 @@ static int robust_check_columns(fokl_ctx *ctx, int nc, const char *who)
     return FOKL_OK;
 }
 
-static size_t robust_free_bytes(size_t free_bytes)
-{
-    // FOKL_ROBUST_FREE_BYTES: count at most this much of the device's free memory as available to a call (a share of a
-    // device that other work uses; the tests' way to meet the refusal with buffers of ordinary size)
-    if (const char *cap = std::getenv("FOKL_ROBUST_FREE_BYTES")) free_bytes = std::min<size_t>(free_bytes, std::strtoull(cap, nullptr, 10));
-    return free_bytes;
-}
-
 // The workspaces of `chains` chains (state, partials, G, counters) and the slot list with y behind the columns.
 static int robust_workspaces(fokl_ctx *ctx, RobustRun &run, const int32_t *slots, const double *weights, const int32_t *chain_ids)
 {
@@ -599,9 +591,8 @@ extern "C" int fokl_robust_pass(fokl_ctx *ctx, const int32_t *slots, int nc, con
     if (rc) return rc;
     RobustArgs &a = run.args;
     const size_t ld = (size_t)16 * a.nb;
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    free_bytes = robust_free_bytes(free_bytes);
+    size_t free_bytes = 0;
+    HIP_TRY(ctx, capped_free_bytes("FOKL_ROBUST_FREE_BYTES", &free_bytes));
     const size_t want = ((size_t)a.groups * run.partial_doubles + ld * ld + (size_t)n * 3) * sizeof(double);
     if (want + (64 << 20) > free_bytes)
         return fail(ctx, FOKL_ERR_ARG, "fokl_robust_pass: the call wants " + std::to_string(want) + " bytes on the device (rows and "
@@ -756,9 +747,8 @@ extern "C" int fokl_robust_chains(fokl_ctx *ctx, const int32_t *slots, int nc, c
     const size_t lam_bytes = lam_sum_out ? (size_t)chains * n * sizeof(double) : 0;
     const size_t partial_bytes = (size_t)chains * a.groups * run.partial_doubles * sizeof(double);
     const size_t other = (size_t)chains * (ld * ld + RB_STATE_LD + 8 * stride + 64) * sizeof(double) + (size_t)n * sizeof(double);
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    free_bytes = robust_free_bytes(free_bytes);
+    size_t free_bytes = 0;
+    HIP_TRY(ctx, capped_free_bytes("FOKL_ROBUST_FREE_BYTES", &free_bytes));
     if (row_bytes + lam_bytes + partial_bytes + other + (64 << 20) > free_bytes)
         return fail(ctx, FOKL_ERR_ARG, "fokl_robust_chains: the call wants " + std::to_string(row_bytes) + " bytes of rows (chains x "
                     "kept x (P + 4) x 8), " + std::to_string(lam_bytes) + " of row weights (chains x rows x 8) and " +

@@ -2,9 +2,8 @@
 // included by fokl_hip.hip).  The statement is fokl_gpy_amd/score.py: score_rows_host.
 //
 // ll[row][d] = c_d - (y_row - X_row . beta_d)^2 h_d with c_d = -log(2 pi sigsqd_d) / 2 and h_d = 0.5 / sigsqd_d (formed on
-// the host).  The product has the shape of predict_mfma_kernel: one wavefront per tile of 16 rows, D[draw][row] out of
-// v_mfma_f64_16x16x4_f64 in blocks of SC_DT x 16 draws (A = the transposed coefficients [ncp][dp], B = the tile's basis
-// values in LDS [column][row]); lane l ends up with the draws (l >> 4) + 4 v of row l & 15.  ll is never stored.  Per row
+// the host).  The product is the draw tile's (fokl_draw_tile.inc: the coefficient table and the lane map): one wavefront per
+// tile of 16 rows, the tile's basis values in LDS [column][row], blocks of SC_DT x 16 draws.  ll is never stored.  Per row
 // the four lanes that share it keep, each over its quarter of the draws,
 //   * an online max and sum of exp(ll - max)                          -> lppd
 //   * sum(ll - ll0) and sum((ll - ll0)^2), ll0 = ll[row][0]           -> ll_mean, p_waic
@@ -76,8 +75,7 @@ __global__ __launch_bounds__(SC_THREADS) void score_kernel(double *const *__rest
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t r = tile * 16 + col;
         const bool in = r < n;
-        for (int k = quad; k < ncp; k += 4)
-            xs[k * 16 + col] = (in && k < nc) ? *(__attribute__((address_space(1))) const double *)(slot_ptr[slots[k]] + r) : 0.0;
+        draw_tile_load(xs, slot_ptr, slots, nc, ncp, r, in, quad, col);
         if (LOO)
             for (int k = quad; k < cnt; k += 4) list[k * 16 + col] = -INFINITY;
         const double yv = in ? data[r] : 0.0;
@@ -88,6 +86,7 @@ __global__ __launch_bounds__(SC_THREADS) void score_kernel(double *const *__rest
         int pos = 0;
 
         for (int d0 = 0; d0 < dp; d0 += 16 * SC_DT) {
+            // draw_product<SC_DT> written out (fokl_draw_tile.inc states the format, and why this kernel has a copy)
             d4 acc[SC_DT];
             const double *a_ptr[SC_DT];
 #pragma unroll
@@ -343,11 +342,8 @@ extern "C" int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, cons
     const size_t tail_bytes = tail_out ? (size_t)n * cnt * sizeof(double) : 0;
     const size_t table_bytes = ((size_t)ncp + 2) * dp * sizeof(double);
     const size_t stats_bytes = (size_t)n * 8 * sizeof(double);
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_bytes, &total_bytes));
-    // FOKL_SCORE_FREE_BYTES: count at most this much of the device's free memory as available to a call (a share of a
-    // device that other work uses; the tests' way to meet the refusal with buffers of ordinary size)
-    if (const char *cap = std::getenv("FOKL_SCORE_FREE_BYTES")) free_bytes = std::min<size_t>(free_bytes, std::strtoull(cap, nullptr, 10));
+    size_t free_bytes = 0;
+    HIP_TRY(ctx, capped_free_bytes("FOKL_SCORE_FREE_BYTES", &free_bytes));
     if (tail_bytes + table_bytes + stats_bytes + (64 << 20) > free_bytes)
         return fail(ctx, FOKL_ERR_ARG, "fokl_score_rows: the call wants " + std::to_string(tail_bytes + table_bytes + stats_bytes) +
                     " bytes on the device and 64 MiB to spare (" + std::to_string(tail_bytes) + " bytes of tail_out = rows x (M + 1) x 8, " +
@@ -358,8 +354,7 @@ extern "C" int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, cons
 
     // coefficients transposed and zero padded [ncp][dp] | c [dp] | h [dp] (padding draws: c = 0, h = 0, never used)
     std::vector<double> table(((size_t)ncp + 2) * dp, 0.0);
-    for (int d = 0; d < draws; ++d)
-        for (int k = 0; k < nc; ++k) table[(size_t)k * dp + d] = betas[(size_t)d * nc + k];
+    fill_draw_table(table.data(), betas, draws, nc, ncp, dp);
     double *cons = table.data() + (size_t)ncp * dp;
     for (int d = 0; d < draws; ++d) {
         cons[d] = -0.5 * std::log(2.0 * M_PI * sigsqd[d]);
@@ -377,25 +372,18 @@ extern "C" int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, cons
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(16, 160 * 1024 / lds_bytes));
     const int grid = (int)std::min<int64_t>(tiles, (int64_t)cu_count(ctx) * per_cu);
     auto fn = want_loo ? score_kernel<true> : score_kernel<false>;
-    hipError_t e = hipSuccess;
-    if (lds_bytes > 64 * 1024)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (e == hipSuccess) e = hipEventCreate(&ev0);
-    if (e == hipSuccess) e = hipEventCreate(&ev1);
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventRecord(ev0, ctx->stream);
+    hipError_t e = lds_opt_in(fn, lds_bytes, 160 * 1024);
+    StreamStopwatch watch(ctx, e);
+    const int t0 = watch.mark();
     if (e == hipSuccess) {
         TimedRegion timed(ctx, FOKL_K_SCORE, 8.0 * (double)n * (nc + 9) + (double)tail_bytes, 2.0 * (double)n * ncp * draws);
         hipLaunchKernelGGL(fn, dim3(grid), dim3(SC_THREADS), lds_bytes, ctx->stream, ctx->d_slot_ptr, d_slots, nc, ncp,
                            d_table, d_table + (size_t)ncp * dp, draws, dp, ctx->slot_ptr[FOKL_SLOT_Y], n, M, d_stats, d_tail);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipEventRecord(ev1, ctx->stream);
+    const int t1 = watch.mark();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
+    const double kernel_us = watch.us(t0, t1);
     if (e == hipSuccess) e = hipMemcpy(stats_out, d_stats, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess && tail_out) e = hipMemcpy(tail_out, d_tail, tail_bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(ctx, FOKL_ERR_HIP, std::string("fokl_score_rows: ") + hipGetErrorString(e));
@@ -410,6 +398,6 @@ extern "C" int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, cons
     rep[3] = (int64_t)lds_bytes;
     rep[4] = want_loo ? cnt : 0;
     rep[5] = raw_rows;
-    rep[6] = (int64_t)std::llround((double)ms * 1000.0);
+    rep[6] = (int64_t)std::llround(kernel_us);
     return FOKL_OK;
 }

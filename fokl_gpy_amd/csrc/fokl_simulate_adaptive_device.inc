@@ -221,7 +221,7 @@ int sim_adaptive_run(fokl_ctx *ctx, const fokl_system &s, const SimSystem &sys, 
     const auto launch = [&](double *points, int64_t t0, int steps, int chunk_points, int write_first) {
         return sim_dispatch(s.n_states, [&](auto ns) {
             const auto kernel = kernel_of(ns);
-            if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+            if (hipError_t e = lds_opt_in(kernel, lds_bytes, SIM_LDS_BUDGET)) return e;
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, ad, tab.norm_src, tab.norm_lo,
                                tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline, tab.bern,
                                (const double *)d_coef, (const double *)d_forcing, d_state, d_lane_i32, d_lane_i64, d_error,

@@ -225,14 +225,6 @@ hipError_t sim_dispatch(int n_states, F &&f)
     return hipErrorInvalidValue;
 }
 
-// A kernel that wants more than 64 KB of dynamic LDS has to be told so
-template <class Kernel>
-hipError_t sim_lds_attribute(Kernel kernel, size_t lds_bytes, size_t limit = SIM_LDS_BUDGET)
-{
-    if (lds_bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit);
-}
-
 // What the simulate calls and the filter refuse of n_steps (sim_check's steps_test; control has its own)
 int sim_steps_fit(fokl_ctx *ctx, const std::string &who, const fokl_system &s)
 {
@@ -404,7 +396,7 @@ int sim_run(fokl_ctx *ctx, const fokl_system &s, size_t ld, int64_t bound, const
     int npow2 = 2;
     while (npow2 < n_members) npow2 <<= 1;
     const size_t band_lds = out.bounds ? (size_t)npow2 * sizeof(double) : 0;
-    HIP_TRY(ctx, sim_lds_attribute(ensemble_band_kernel, band_lds, GI_BAND_MAX_MEMBERS * sizeof(double)));
+    HIP_TRY(ctx, lds_opt_in(ensemble_band_kernel, band_lds, GI_BAND_MAX_MEMBERS * sizeof(double)));
 
     launches = 0;
     for (int64_t t0 = 0, p_first = 0; p_first < n_points;) {
@@ -497,7 +489,7 @@ extern "C" int fokl_simulate_ensemble(fokl_ctx *ctx, const fokl_system *system, 
     const auto launch = [&](double *points, int64_t t0, int steps, int chunk_points, int write_first) {
         return sim_dispatch(s.n_states, [&](auto ns) {
             const auto kernel = simulate_ensemble_kernel<decltype(ns)::value>;
-            if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+            if (hipError_t e = lds_opt_in(kernel, lds_bytes, SIM_LDS_BUDGET)) return e;
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, tab.norm_src, tab.norm_lo,
                                tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries, tab.spline, tab.bern,
                                (const double *)d_coef, (const double *)d_forcing, d_state, d_sat, points, (int64_t)ld, t0, steps,

@@ -242,7 +242,7 @@ extern "C" int fokl_steady_states(fokl_ctx *ctx, const fokl_system *system, cons
     const auto launch = [&](int64_t q0, size_t points) {
         return sim_dispatch(NS, [&](auto ns) {
             const auto kernel = steady_states_kernel<decltype(ns)::value>;
-            if (hipError_t e = sim_lds_attribute(kernel, lds_bytes)) return e;
+            if (hipError_t e = lds_opt_in(kernel, lds_bytes, SIM_LDS_BUDGET)) return e;
             hipLaunchKernelGGL(kernel, dim3(grid, (unsigned)points), dim3(SIM_LANES), lds_bytes, ctx->stream, sys, pl,
                                tab.norm_src, tab.norm_lo, tab.norm_span, tab.fac_norm, tab.fac_row, tab.fac_degree, tab.entries,
                                tab.spline, tab.bern, (const double *)d_coef, (const double *)d_forcing, (const double *)d_starts,

@@ -32,6 +32,7 @@ def test_kept_lp_and_replay_are_the_host_statements_bit_for_bit(device_ctx, name
     E, d = p['E'], p['d']
     assert rep['NS'] == NS[name] and rep['draws'] == E and rep['lds_bytes'] == LDS_BYTES[name] == p['lds_bytes']
     assert rep['launches'] == 2 and rep['iterations'] == 6 and rep['evaluations'] == int(dev.evals.sum())
+    assert rep['kernel_us'] > 0
     assert dev.x.shape == (E * 6 * W, d) and not dev.invalid.any()
     assert np.all((dev.x > p['lo']) & (dev.x < p['hi']))
     with np.errstate(all='ignore'):
