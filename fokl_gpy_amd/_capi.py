@@ -230,6 +230,7 @@ SIGNATURES = {
                                   c_dbl, c_vp, c_vp]),
     'fokl_gp_integrate_ensemble': (c_int, [c_vp, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_vp, c_vp, c_int, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
+    'fokl_gp_integrate_report': (c_int, [c_vp, c_vp]),
     'fokl_simulate_ensemble': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     'fokl_simulate_report': (c_int, [c_vp, c_vp]),
     'fokl_simulate_adaptive': (c_int, [c_vp, c_vp, c_int, c_dbl, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
@@ -2569,6 +2570,18 @@ class DeviceContext:
             _ptr(cols), sources, _ptr(n_src), _ptr(forcing), _ptr(norms), _ptr(table), int(n_basis), int(width), float(h),
             _ptr(y0), int(y0.ndim == 2), int(cut or 0), _ptr(mean), _ptr(bounds), _ptr(members)))
         return mean, bounds, members
+
+    def gp_integrate_report(self):
+        """What the last ``gp_integrate_ensemble`` on this context ran (fokl_gp_integrate_report; host values, no launch):
+        ``NS`` (the kernel instance = states), ``members``, ``workgroups`` (= wavefronts = ceil(members / 64)), ``lds_bytes``
+        of the integration kernel, its ``launches`` and ``steps_per_launch``, ``band_lds_bytes`` (the band kernel's sorted
+        list, 0 without bounds), ``band_rows`` and ``band_workgroups`` of the first launch (fewer workgroups than rows: a
+        workgroup goes round the grid) and the device's ``compute_units``.  Zeros after a refused call."""
+        out = np.zeros(10, dtype=np.int64)
+        self._ck(self._lib.fokl_gp_integrate_report(self._h, _ptr(out)))
+        keys = ('NS', 'members', 'workgroups', 'lds_bytes', 'launches', 'steps_per_launch', 'band_lds_bytes', 'band_rows',
+                'band_workgroups', 'compute_units')
+        return dict(zip(keys, (int(v) for v in out)))
 
     def simulate_ensemble(self, p):
         """fokl_simulate_ensemble for a system prepared by ``dynamics._prepare`` -> (mean [n_states, P], bounds

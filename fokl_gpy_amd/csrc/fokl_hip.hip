@@ -101,6 +101,7 @@ struct fokl_ctx {
     int64_t robust_report[FOKL_ROBUST_REPORT_LEN] = {};           // ... and the last fokl_robust_pass / _step / _chains call
     int64_t infer_report[FOKL_INFER_REPORT_LEN] = {};             // ... and the last fokl_infer_inputs call
     int64_t design_report[FOKL_DESIGN_REPORT_LEN] = {};           // ... and the last fokl_design_select call
+    int64_t integrate_report[FOKL_INTEGRATE_REPORT_LEN] = {};     // ... and the last fokl_gp_integrate_ensemble call
     int64_t simulate_report[FOKL_SIMULATE_REPORT_LEN] = {};       // ... and the last fokl_simulate_ensemble call
     int64_t simulate_adaptive_report[FOKL_SIMULATE_ADAPTIVE_REPORT_LEN] = {};     // ... and the last fokl_simulate_adaptive call
     int64_t simulate_stiff_report[FOKL_SIMULATE_STIFF_REPORT_LEN] = {};   // ... and the last fokl_simulate_stiff call

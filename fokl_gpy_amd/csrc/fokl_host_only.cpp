@@ -44,6 +44,7 @@ extern "C" int fokl_gp_integrate_ensemble(fokl_ctx *, int, int, int, int64_t, co
 {
     return FOKL_ERR_HIP;
 }
+extern "C" int fokl_gp_integrate_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
 // Neither does dynamics.simulate (fokl_simulate_device.inc); its statement is dynamics.simulate_host.
 extern "C" int fokl_simulate_ensemble(fokl_ctx *, const fokl_system *, int, double *, double *, double *, int32_t *)

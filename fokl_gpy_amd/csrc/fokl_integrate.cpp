@@ -32,8 +32,12 @@ struct Model {
 
 inline double spline_value(const double *table, int width, int order, double x)
 {
-    int piece = (int)std::floor(x * 498.0);                 // GI:106 (the table has width = 499 pieces)
-    if (piece == 498) piece -= 1;                           // GI:109-115
+    // GI:106, and GI:109-115's "498 -> 497" (the table has width = 499 pieces).  Clamped on both sides as
+    // the device's gi_cubic clamps it: for x in [0, 1] nothing changes; an input beyond (a forcing value outside its
+    // normalisation) extends the outermost cubic instead of indexing outside the table, and a NaN (a NaN coefficient's
+    // state, for which the reference raises) takes piece 0 and gives NaN
+    const double scaled = std::floor(x * 498.0);
+    const int piece = scaled >= 497.0 ? 497 : scaled >= 0.0 ? (int)scaled : 0;
     const double r = 1.0 / 498.0;
     const double xmin = r * (double)piece;
     const double X = (x - xmin) / r;                        // GI:117-119

@@ -24,8 +24,13 @@
 //
 // ensemble_band_kernel: one workgroup per (state, point) row: the mean as 256 strided partial sums combined by a fixed
 // tree (bitwise reproducible), and for the bounds the row sorted in LDS (bitonic network over the next power of two,
-// padded with +inf) -- sorted[cut] and sorted[E - cut] are then order statistics of the stored values, equal to numpy's
-// on the returned members.  E <= GI_BAND_MAX_MEMBERS (16 384 values = 128 KB of LDS); bounds over more are refused.
+// padded with +inf) in numpy's order, in which a NaN member counts as the largest value, above +inf.  A `>` is no order
+// once a NaN is in the row -- the network then leaves even the finite values out of place -- so a NaN enters the list as
+// +inf and is counted: with n of them, sorted[k] is NaN for k >= E - n and the list's value below (the values that stand
+// in for the NaN sit at the top, level with a member's own +inf).  sorted[cut] and sorted[E - cut] are then order
+// statistics of the stored values, equal to np.sort's on the returned members: the upper bound is NaN once `cut` members
+// are NaN, the lower one once E - cut are, and the mean is NaN with the first NaN member.  A row without NaN is sorted as
+// it always was.  E <= GI_BAND_MAX_MEMBERS (16 384 values = 128 KB of LDS); bounds over more are refused.
 
 namespace fokl {
 
@@ -49,7 +54,8 @@ struct GiSystem {
 };
 
 // spline_value() of fokl_integrate.cpp.  The piece is clamped on both sides: for x in [0, 1] that is the reference's
-// "498 -> 497"; beyond (a forcing value outside its normalisation, a NaN) the host reads outside its table, this does not.
+// "498 -> 497"; beyond (a forcing value outside its normalisation, a NaN) the host clamps the same way: the outermost cubic
+// is extended, a NaN takes piece 0 and gives NaN.
 __device__ __forceinline__ double gi_cubic(const double *__restrict__ table, int order_slot, double x)
 {
     int piece = (int)floor(x * 498.0);
@@ -179,6 +185,7 @@ __global__ __launch_bounds__(GI_BAND_THREADS) void ensemble_band_kernel(const do
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double partial[GI_BAND_THREADS];
+    __shared__ int nan_count[GI_BAND_THREADS];
     const int tid = threadIdx.x;
     const int n_rows = n_states * chunk_points;
     for (int r = blockIdx.x; r < n_rows; r += gridDim.x) {
@@ -187,11 +194,21 @@ __global__ __launch_bounds__(GI_BAND_THREADS) void ensemble_band_kernel(const do
         double sum = 0.0;
         for (int i = tid; i < members; i += GI_BAND_THREADS) sum += src[i];
         partial[tid] = sum;
-        if (bounds)
-            for (int i = tid; i < npow2; i += GI_BAND_THREADS) lds[i] = i < members ? src[i] : INFINITY;
+        if (bounds) {
+            int nans = 0;                                              // a NaN member enters the list as +inf and is counted
+            for (int i = tid; i < npow2; i += GI_BAND_THREADS) {
+                const double v = i < members ? src[i] : INFINITY;
+                nans += v != v;
+                lds[i] = v != v ? INFINITY : v;
+            }
+            nan_count[tid] = nans;
+        }
         __syncthreads();
         for (int half = GI_BAND_THREADS / 2; half > 0; half >>= 1) {
-            if (tid < half) partial[tid] += partial[tid + half];
+            if (tid < half) {
+                partial[tid] += partial[tid + half];
+                if (bounds) nan_count[tid] += nan_count[tid + half];
+            }
             __syncthreads();
         }
         if (tid == 0) mean[dst] = partial[0] / (double)members;
@@ -209,9 +226,10 @@ __global__ __launch_bounds__(GI_BAND_THREADS) void ensemble_band_kernel(const do
                     }
                     __syncthreads();
                 }
-            if (tid == 0) {
-                bounds[2 * dst] = lds[cut];
-                bounds[2 * dst + 1] = lds[members - cut];
+            if (tid == 0) {                                            // sorted[k] is NaN from k = members - (NaN members) on
+                const int first_nan = members - nan_count[0];
+                bounds[2 * dst] = cut < first_nan ? lds[cut] : NAN;
+                bounds[2 * dst + 1] = members - cut < first_nan ? lds[members - cut] : NAN;
             }
         }
         __syncthreads();
@@ -261,6 +279,13 @@ hipError_t gi_allow_lds(size_t lds_bytes)
 
 }  // namespace
 
+extern "C" int fokl_gp_integrate_report(const fokl_ctx *ctx, int64_t *out)
+{
+    if (!ctx || !out) return fail(nullptr, FOKL_ERR_ARG, "fokl_gp_integrate_report: null argument");
+    std::memcpy(out, ctx->integrate_report, sizeof ctx->integrate_report);
+    return FOKL_OK;
+}
+
 extern "C" int fokl_gp_integrate_ensemble(fokl_ctx *ctx, int n_members, int n_states, int n_other, int64_t n_steps,
                                           const double *const *betas, const int32_t *betas_per_member,
                                           const int32_t *const *mtx, const int32_t *mtx_rows, const int32_t *mtx_cols,
@@ -271,6 +296,7 @@ extern "C" int fokl_gp_integrate_ensemble(fokl_ctx *ctx, int n_members, int n_st
 {
     const char *who = "fokl_gp_integrate_ensemble: ";
     if (!ctx) return fail(nullptr, FOKL_ERR_ARG, std::string(who) + "null context");
+    std::memset(ctx->integrate_report, 0, sizeof ctx->integrate_report);
     if (n_members <= 0 || n_states <= 0 || n_other < 0 || n_steps < 0 || !betas || !betas_per_member || !mtx ||
         !mtx_rows || !mtx_cols || !source || !n_source || !norms || !spline_table || !y0 || !mean ||
         (n_other > 0 && !forcing))
@@ -432,6 +458,7 @@ extern "C" int fokl_gp_integrate_ensemble(fokl_ctx *ctx, int n_members, int n_st
     const int grid = (int)(ld / GI_LANES);
     double terms_per_stage = 0.0;
     for (int k = 0; k < n_states; ++k) terms_per_stage += sys.entry_count[k];
+    int64_t launches = 0, first_rows = 0, first_band_grid = 0;
     for (int64_t t0 = 0, p_first = 0; p_first < n_points;) {
         const int write_first = t0 == 0;
         const int steps = (int)std::min<int64_t>(per_launch, n_steps - t0);
@@ -455,6 +482,10 @@ extern "C" int fokl_gp_integrate_ensemble(fokl_ctx *ctx, int n_members, int n_st
                                d_points, (int64_t)ld, n_members, n_states, chunk_points, n_points, p_first, npow2, cut,
                                d_mean, d_bounds);
             HIP_TRY(ctx, hipGetLastError());
+            if (launches++ == 0) {
+                first_rows = rows;
+                first_band_grid = band_grid;
+            }
         }
         if (members) {
             hipLaunchKernelGGL(ensemble_transpose_kernel, dim3((n_members + 31) / 32, (chunk_points + 31) / 32, n_states),
@@ -473,5 +504,16 @@ extern "C" int fokl_gp_integrate_ensemble(fokl_ctx *ctx, int n_members, int n_st
     HIP_TRY(ctx, hipMemcpy(mean, d_mean, (size_t)n_states * n_points * sizeof(double), hipMemcpyDeviceToHost));
     if (bounds)
         HIP_TRY(ctx, hipMemcpy(bounds, d_bounds, (size_t)n_states * n_points * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    int64_t *rep = ctx->integrate_report;
+    rep[0] = n_states;
+    rep[1] = n_members;
+    rep[2] = grid;
+    rep[3] = (int64_t)lds_bytes;
+    rep[4] = launches;
+    rep[5] = per_launch;
+    rep[6] = (int64_t)band_lds;
+    rep[7] = first_rows;
+    rep[8] = first_band_grid;
+    rep[9] = cu_count(ctx);
     return FOKL_OK;
 }

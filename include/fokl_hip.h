@@ -373,12 +373,14 @@ int fokl_gp_integrate(int n_states, int n_other, int64_t n_steps, const double *
  *   mean    [n_states, n_steps + 1]                 mean over members (fixed summation order: reproducible bit for bit);
  *   bounds  [n_states, n_steps + 1, 2] or NULL      (sorted[cut], sorted[n_members - cut]) of the members' values at that
  *                                                   point, fokl_predict's convention (FR:973-977): 1 <= cut < n_members.
- *                                                   Sorted in LDS: at most 16 384 members, FOKL_ERR_ARG beyond (mean and
- *                                                   members have no such limit);
+ *                                                   Sorted in numpy's order: a NaN member counts as the largest value,
+ *                                                   so the upper bound is NaN once `cut` members are NaN (the mean with
+ *                                                   the first).  Sorted in LDS: at most 16 384 members, FOKL_ERR_ARG
+ *                                                   beyond (mean and members have no such limit);
  *   members [n_members, n_states, n_steps + 1] or NULL   every trajectory (point 0 is the initial state).
  * A member's arithmetic is fokl_gp_integrate's operation for operation, except that a cubic's X^2 and X^3 are products
- * where the host calls pow (<= 1 ulp per cubic), and that the piece index is clamped to the table for inputs outside
- * [0, 1] (a forcing value beyond its normalisation) where the host reads past it.
+ * where the host calls pow (<= 1 ulp per cubic); both clamp the piece index to the table for inputs outside [0, 1] (a
+ * forcing value beyond its normalisation, a NaN state).
  * Limits (FOKL_ERR_ARG, nothing is launched): width must be 499; orders within the table; at most
  * FOKL_INTEGRATE_MAX_STATES states (the kernel keeps the stage vectors in registers); coefficients + distinct
  * (input, order) factors of all models + states together at most 287 (they live in LDS, 64 members wide).

@@ -42,6 +42,8 @@
  *                              unknown inputs inferred from observed outputs: one affine-invariant ensemble of 64 walkers
  *                              per posterior draw (fokl_gpy_amd/infer.py), what its last launches ran, and its
  *                              counter-based random numbers as the host sees them
+ *   fokl_gp_integrate_report   what the last fokl_gp_integrate_ensemble (fokl_hip.h) ran: the kernel instance, its LDS, the
+ *                              band kernel's list and grid
  *   fokl_simulate_ensemble / fokl_simulate_report
  *   fokl_simulate_adaptive / fokl_simulate_adaptive_report
  *   fokl_simulate_stiff / fokl_simulate_stiff_report
@@ -1263,6 +1265,23 @@ int fokl_infer_report(const fokl_ctx *ctx, int64_t *out);
  * no device.  FOKL_ERR_ARG for another purpose.
  */
 int fokl_infer_rng(uint32_t seed, uint32_t draw_id, uint32_t iteration, int purpose, int count, double *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* What the last fokl_gp_integrate_ensemble (fokl_hip.h; csrc/fokl_integrate_device.inc) ran                */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_INTEGRATE_REPORT_LEN 10
+
+/*
+ * The last fokl_gp_integrate_ensemble call on `ctx`, out [FOKL_INTEGRATE_REPORT_LEN] (host values, no launch); zeros after a
+ * call that was refused or failed:
+ *   out[0]  NS: the kernel instance (states)     out[1]  members     out[2]  workgroups = wavefronts = ceil(members / 64)
+ *   out[3]  the integration kernel's dynamic LDS bytes     out[4]  integration launches     out[5]  steps per launch
+ *   out[6]  the band kernel's dynamic LDS bytes: its sorted list, 0 without bounds
+ *   out[7]  (state, point) rows of the first launch, the largest     out[8]  workgroups of the band kernel in that launch
+ *   (fewer than the rows: a workgroup goes round the grid)     out[9]  compute units of the device
+ */
+int fokl_gp_integrate_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* A system of fitted models over every posterior draw (csrc/fokl_simulate_device.inc; fokl_gpy_amd/dynamics.py) */

@@ -61,6 +61,32 @@ def test_models_that_ignore_the_forcing_and_single_state():
     np.testing.assert_allclose(Y[0], want, rtol=1e-12, atol=1e-14)
 
 
+def test_inputs_outside_the_table_stay_inside_it():
+    """A NaN coefficient makes its state NaN after one step, and the next stage evaluates a cubic at NaN; a forcing value may
+    lie outside [0, 1].  The piece is clamped to the table (as the device's gi_cubic clamps it): NaN gives NaN from there
+    on, an input beyond the ends extends the outermost cubic -- no index outside the table."""
+    g, phis, betas, mtx = _case()
+    broken = [betas[0].copy(), betas[1].copy()]
+    broken[1][2] = np.nan
+    y0 = g['y0'].copy()
+    T, Y = GP_Integrate(broken, mtx, g['b'], g['norms'], phis, float(g['start']), float(g['stop']), y0, float(g['h']),
+                        [row for row in g['used']])
+    assert np.array_equal(Y[:, 0], g['y0']) and np.isnan(Y[:, 1:]).all() and np.isnan(y0).all()
+    # one state driven by a forcing column alone: dy/dt = 0.5 phi_1(u) with u = -0.25, 0.5, 1.75
+    tab = np.load(os.path.join(GOLDEN, 'spline_phis.npz'))['table']
+    u = np.array([-0.25, 0.5, 1.75])
+    T, Y = GP_Integrate([np.array([0.0, 0.5])], [np.array([[1]])], u, np.array([[-10.0], [10.0]]), phis, 0.0, 0.375, np.array([0.0]),
+                        0.125, [np.array([0, 1])])
+    want = [0.0]
+    for x in u:
+        p = min(max(int(np.floor(x * 498)), 0), 497)
+        X = (x - p / 498) / (1 / 498)
+        c = tab[0, :, p]
+        want.append(want[-1] + 0.125 * 0.5 * (c[0] + c[1] * X + c[2] * X ** 2 + c[3] * X ** 3))
+    assert Y.shape == (1, 4) and np.isfinite(Y).all()
+    np.testing.assert_allclose(Y[0], want, rtol=1e-12, atol=1e-14)
+
+
 def test_argument_errors():
     g, phis, betas, mtx = _case()
     args = (g['norms'], phis, 2.0, 3.0)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from helpers import GOLDEN
+from band_reference import band_next_to_nan, band_rows, mean_rows, same_rows
 from fokl_gpy_amd import _capi, getKernels
 from fokl_gpy_amd.GP_Integrate import GP_Integrate, GP_Integrate_ensemble, bounds_cut
 
@@ -236,6 +237,108 @@ def test_other_system_shapes(device_ctx):
     assert np.max(np.abs(members - _host_members(*args, E))) <= 1e-13
     srt = np.sort(members, axis=0)
     assert np.array_equal(bounds[..., 0], srt[bounds_cut(E)]) and np.array_equal(bounds[..., 1], srt[E - bounds_cut(E)])
+
+
+@pytest.mark.gpu
+def test_four_states(device_ctx):
+    """integrate_ensemble_kernel<4>: models of 7, 2, 4 and 3 input columns, two forcing columns (the second used forcing
+    input appends its column once more: four states + three forcing inputs), and a term of seven factors, which spans
+    three term entries.  Every member against the host integrator at the file's gate."""
+    g, phis, betas, mtx = _case()
+    rng = np.random.default_rng(9)
+    E = 70
+    b2 = np.stack([g['b'], 0.5 + 0.4 * np.cos(np.arange(g['b'].shape[0]) / 9.0)], axis=1)
+    used = [np.array([1, 1, 1, 1, 1, 1]), np.array([1, 0, 1, 0, 0, 0]), np.array([0, 1, 1, 1, 1, 1]), np.array([0, 0, 0, 1, 1, 0])]
+    mtx4 = [np.array([[1, 0, 0, 0, 0, 0, 0], [0, 1, 0, 0, 1, 0, 0], [1, 2, 1, 1, 1, 2, 3], [0, 0, 3, 0, 0, 0, 0], [0, 0, 0, 2, 0, 1, 0]]),
+            np.array([[1, 0], [0, 1], [1, 1]]),
+            np.array([[1, 0, 0, 0], [0, 2, 0, 0], [0, 0, 1, 1]]),
+            np.array([[1, 0, 0], [0, 1, 1], [2, 0, 3]])]
+    means = [np.array([0.02, -0.4, 0.3, 0.5, 0.2, -0.1]), np.array([-0.03, 0.3, -0.35, 0.2]),
+             np.array([0.01, -0.25, -0.3, 0.4]), np.array([0.02, -0.3, 0.25, -0.2])]
+    assert all(np.abs(mk).sum() <= 2.0 for mk in means)
+    d4 = [mk * (1 + 0.1 * rng.standard_normal((E, mk.shape[0]))) for mk in means]
+    norms4 = np.array([[0.0, 0.1, -0.2, -1.0], [1.0, 0.9, 0.6, 1.0]])
+    y04 = norms4[0] - 0.05 * (norms4[1] - norms4[0]) + 1.1 * (norms4[1] - norms4[0]) * rng.random((E, 4))
+    args = (d4, mtx4, b2, norms4, phis, 0.0, 1.95, y04, 0.05, used)
+    T, mean, bounds, members = GP_Integrate_ensemble(*args, ReturnMembers=True, device=device_ctx)
+    rep = device_ctx.gp_integrate_report()
+    assert rep['NS'] == 4 and rep['members'] == E and rep['workgroups'] == 2 and len(T) <= 41
+    routed = [[0, 1, 2, 3, -1, -2, -2], [0, 2], [1, 2, 3, -1, -2, -2], [3, -1, -2]]     # a model's inputs: states, then forcing
+    factors = {(routed[k][j], order) for k in range(4) for row in mtx4[k] for j, order in enumerate(row) if order}
+    assert len(factors) == 12 and rep['lds_bytes'] == (1 + len(factors) + 4 + sum(mk.shape[0] for mk in means)) * 512
+    assert members.shape == (E, 4, len(T))
+    want = _host_members(*args, E)
+    err = np.max(np.abs(members - want))
+    print(f"\nfour states, {len(T) - 1} steps: max abs difference to the host integrator {err:.3e}")
+    assert err <= 1e-13
+    assert (np.abs(np.diff(want, axis=2)) > 0).any(axis=(0, 2)).all()      # every state moves
+    srt = np.sort(members, axis=0)
+    assert np.array_equal(bounds[..., 0], srt[bounds_cut(E)]) and np.array_equal(bounds[..., 1], srt[E - bounds_cut(E)])
+
+
+def _wide_model(rows, rng, E=70):
+    """One state ruled by ``rows`` terms of itself alone, orders 1 .. 3 in turn (duplicate rows), sum |beta| = 1.5."""
+    mtx = (np.arange(rows) % 3 + 1)[:, None]
+    mean = rng.standard_normal(rows + 1)
+    mean *= 1.5 / np.abs(mean).sum()
+    draws = mean * (1 + 0.1 * rng.standard_normal((E, rows + 1)))
+    phis = _case()[1]
+    return ([draws], [mtx], np.zeros((0,)), np.array([[0.0], [1.0]]), phis, 0.0, 1.95, rng.random((E, 1)), 0.05, [np.array([1])])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('rows', [130, 282])
+def test_wide_models_opt_in_to_more_lds(device_ctx, rows):
+    """LDS rows per member = 1 + factors + states + coefficients.  130 terms: 1 + 3 + 1 + 131 = 136 rows of 512 bytes, above
+    the 64 KB a kernel has without asking; 282 terms: 288 rows, exactly the 144 KB budget -- the largest admitted system."""
+    args = _wide_model(rows, np.random.default_rng(rows))
+    T, mean, bounds, members = GP_Integrate_ensemble(*args, ReturnMembers=True, device=device_ctx)
+    rep = device_ctx.gp_integrate_report()
+    assert rep['lds_bytes'] == (1 + 3 + 1 + rows + 1) * 512 > 64 * 1024 and rep['NS'] == 1 and len(T) <= 41
+    assert rows != 282 or rep['lds_bytes'] == 288 * 512 == 144 * 1024
+    want = _host_members(*args, 70)
+    err = np.max(np.abs(members - want))
+    print(f"\n{rows} terms, {len(T) - 1} steps: max abs difference to the host integrator {err:.3e}")
+    assert err <= 1e-13 and np.ptp(want[:, 0, -1]) > 0.01 and (np.abs(want[:, 0, -1] - want[:, 0, 0]) > 1e-3).any()
+    srt = np.sort(members, axis=0)
+    assert np.array_equal(bounds[..., 0], srt[bounds_cut(70)]) and np.array_equal(bounds[..., 1], srt[70 - bounds_cut(70)])
+
+
+@pytest.mark.gpu
+def test_one_term_above_the_lds_budget_is_refused(device_ctx):
+    g, phis, betas, mtx = _case()
+    golden = lambda: GP_Integrate_ensemble(*_golden_args(g, phis, betas, mtx, g['y0'].copy()), ReturnBounds=False,
+                                           ReturnMembers=True, device=device_ctx)
+    before = golden()
+    with pytest.raises(_capi.FoklNativeError, match="do not fit a wavefront's LDS") as err:
+        GP_Integrate_ensemble(*_wide_model(283, np.random.default_rng(283)), device=device_ctx)
+    assert err.value.code == -2 and device_ctx.gp_integrate_report()['members'] == 0
+    after = golden()                                          # the context still integrates, bit for bit
+    assert np.max(np.abs(after[2][0] - g['Y'])) <= 1e-13
+    for a, b in zip(before, after):
+        assert np.array_equal(a, b)
+
+
+@pytest.mark.gpu
+def test_the_band_next_to_nan_members(device_ctx):
+    """Three NaN-coefficient members among 130 (cut 4): each is NaN from its first step on, like its host trajectory; the
+    bounds are np.sort's order statistics of the returned members (the three NaN sort last, so the upper bound is the
+    largest finite value), the mean is the kernel's summation tree and NaN from point 1 on."""
+    g, phis, betas, mtx = _case()
+    E, gone = 130, (5, 64, 129)
+    draws, y0 = _spread(g, betas, E, 21)
+    for e, (k, c) in zip(gone, ((0, 1), (1, 2), (0, 0))):
+        draws[k][e, c] = np.nan
+    args = _golden_args(g, phis, draws, mtx, y0)
+    T, mean, bounds, members = GP_Integrate_ensemble(*args, ReturnMembers=True, device=device_ctx)
+    want = _host_members(*args, E)
+    assert np.array_equal(np.isnan(members), np.isnan(want)) and np.isnan(members[list(gone)][:, :, 1:]).all()
+    alive = np.delete(np.arange(E), gone)
+    assert np.max(np.abs(members[alive] - want[alive])) <= 1e-13
+    lower, upper = band_rows(members, bounds_cut(E))
+    assert same_rows(bounds[..., 0], lower) and same_rows(bounds[..., 1], upper) and same_rows(mean, mean_rows(members))
+    band_next_to_nan(members, mean, bounds, gone, bounds_cut(E))
+    assert bounds_cut(E) == 4 and np.isfinite(bounds).all() and np.isnan(mean[:, 1:]).all()
 
 
 @pytest.mark.gpu

@@ -196,10 +196,12 @@ def test_the_wall_of_the_box_is_reported_as_unresolved():
 # 5. a NaN member ends and stays local
 # ---------------------------------------------------------------------------------------------------------
 
-def nan_system():
-    args = two_state_system(steps=4, draws=3)
-    args['models'][1]['betas'][1, 2] = np.nan
-    return dict(args, ReturnBounds=False, max_halvings=5)
+def nan_system(draws=3, nan_draws=(1,), ReturnBounds=False):
+    """The two-state system with a NaN coefficient in the second model of the draws ``nan_draws``: those members are NaN
+    from their first step on.  With more draws and ``ReturnBounds`` the band is formed next to them."""
+    args = two_state_system(steps=4, draws=draws)
+    args['models'][1]['betas'][list(nan_draws), 2] = np.nan
+    return dict(args, ReturnBounds=ReturnBounds, max_halvings=5)
 
 
 def test_a_nan_member_ends_and_stays_local():

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 from helpers import GOLDEN
+from band_reference import band_next_to_nan, band_rows, mean_rows, same_rows
+from test_simulate_adaptive_host import nan_system
 from fokl_gpy_amd import dynamics, getKernels
 from fokl_gpy_amd.GP_Integrate import bounds_cut
 
@@ -179,6 +181,22 @@ def test_saturation_flags_and_trajectories(device_ctx):
     assert (host.first_saturation[::2] >= 0).all() and host.first_saturation[5] == 0
     assert 0 < (host.first_saturation < 0).sum() < E and 0.5 <= dev.saturated_fraction < 1.0
     assert (host.members[::2, 0, -1] >= 0.5).all()                   # the box of p is [-0.5, 0.5]
+
+
+@pytest.mark.parametrize('nan_draws', [(1,), (1, 40)])
+def test_the_band_next_to_nan_members(device_ctx, nan_draws):
+    """The two-state system of tests/test_simulate_adaptive_host.py with 70 draws, of which ``nan_draws`` hold a NaN
+    coefficient: every member is the host statement's bit for bit (NaN where it is NaN), the bounds are np.sort's order
+    statistics of the returned members and the host statement's own, the mean is the band kernel's summation tree over the
+    host's members.  Cut 2: with one NaN member the upper bound is the largest finite value, with two it is NaN."""
+    args = {key: value for key, value in nan_system(draws=70, nan_draws=nan_draws, ReturnBounds=True).items() if key != 'max_halvings'}
+    host = dynamics.simulate_host(**args, keep='members')
+    dev = dynamics.simulate(**args, keep='members', device=device_ctx)
+    assert same_rows(dev.members, host.members) and np.array_equal(dev.first_saturation, host.first_saturation)
+    lower, upper = band_rows(dev.members, bounds_cut(70))
+    assert same_rows(dev.bounds[..., 0], lower) and same_rows(dev.bounds[..., 1], upper) and same_rows(dev.bounds, host.bounds)
+    assert same_rows(dev.mean, mean_rows(host.members)) and np.array_equal(np.isnan(dev.mean), np.isnan(host.mean))
+    band_next_to_nan(dev.members, dev.mean, dev.bounds, nan_draws, bounds_cut(70))
 
 
 def test_end_to_end_between_fits(device_ctx):

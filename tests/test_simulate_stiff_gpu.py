@@ -9,6 +9,7 @@ import pytest
 
 from fokl_gpy_amd import dynamics
 from fokl_gpy_amd.GP_Integrate import bounds_cut
+from band_reference import band_next_to_nan, band_rows, mean_rows, same_rows
 from test_simulate_adaptive_gpu import _system
 from test_simulate_adaptive_host import nan_system, stiff_linear, wall_system
 from test_simulate_stiff_host import DTYPES, RATES, closed_form, rotating_system
@@ -42,13 +43,16 @@ def _compare(ctx, **args):
     assert rep['NS'] == host.members.shape[1] and rep['members'] == E and rep['workgroups'] == -(-E // 64)
     finite = np.isfinite(host.members).all(axis=0)
     if args.get('ReturnBounds', True):
-        srt, cut = np.sort(dev.members, axis=0), bounds_cut(E)
-        assert np.array_equal(dev.bounds[..., 0], srt[cut]) and np.array_equal(dev.bounds[..., 1], srt[E - cut])
+        lower, upper = band_rows(dev.members, bounds_cut(E))          # np.sort's order statistics: a NaN member sorts last
+        assert same_rows(dev.bounds[..., 0], lower) and same_rows(dev.bounds[..., 1], upper)
+        assert same_rows(dev.bounds, host.bounds)                    # the members are the host's, so are the bounds
     else:
         assert 'bounds' not in dev
     with np.errstate(invalid='ignore'):
         close = np.abs(dev.mean - dev.members.mean(0)) <= E * 2.0 ** -52 * np.max(np.abs(dev.members), axis=0)
     assert np.all(close[finite]) and np.isnan(dev.mean[~finite]).all()
+    # the mean bit for bit: the kernel's order of additions over the host's members, NaN where the host's mean is NaN
+    assert same_rows(dev.mean, mean_rows(host.members)) and np.array_equal(np.isnan(dev.mean), np.isnan(host.mean))
     return dev, host
 
 
@@ -169,6 +173,14 @@ def test_a_nan_member_ends_and_stays_local(device_ctx):
         assert np.array_equal(alone.members[0], dev.members[e])
         for key in RECORD:
             assert np.array_equal(alone[key][0], dev[key][e]), key
+
+
+@pytest.mark.parametrize('nan_draws', [(1,), (1, 40)])
+def test_the_band_next_to_nan_members(device_ctx, nan_draws):
+    """70 draws, cut 2: with one NaN member the upper bound is the largest finite value, with two it is NaN; the lower
+    bound stays finite and the mean is NaN wherever a member is -- the host statement's np.sort and np.mean (``_compare``)."""
+    dev, host = _compare(device_ctx, **nan_system(draws=70, nan_draws=nan_draws, ReturnBounds=True))
+    band_next_to_nan(dev.members, dev.mean, dev.bounds, nan_draws, bounds_cut(70))
 
 
 # ---------------------------------------------------------------------------------------------------------
