@@ -232,8 +232,50 @@ def _refuse_student_noise(post, who):
         return
     if nu is not None and np.isfinite(nu):
         raise ValueError(f"{who} assumes a Gaussian likelihood and this posterior was drawn under Student-t noise (nu = "
-                         f"{float(nu):g}): its sigsqd is the scale of a t distribution, and {who} under t noise is not "
-                         f"implemented (resample_robust(nu=np.inf) keeps the row weights under Gaussian noise)")
+                         f"{float(nu):g}): its sigsqd is the scale of a t distribution (resample_robust(nu=np.inf) keeps the row "
+                         f"weights under Gaussian noise); to use the likelihood the posterior was drawn under, t noise and "
+                         f"row weights included, pass likelihood='posterior'")
+
+
+LIKELIHOODS = ('gaussian', 'posterior')
+
+
+def _posterior_noise(post, who, likelihood, weights, training_rows):
+    """The ``nu=`` / ``weights=`` keywords of ``score.score`` / ``predictive.predictive`` for ``likelihood`` -> a dict, empty for
+    the Gaussian unweighted likelihood (the call then takes the entry point it always took).  'gaussian' refuses a finite-nu
+    posterior, as ever; 'posterior' reads nu from ``post`` (missing, None or infinite: Gaussian) and, when the training rows
+    are scored (``training_rows`` is their number, else None), the row weights from ``post['weights']``."""
+    if likelihood not in LIKELIHOODS:
+        raise ValueError(f"likelihood must be one of {LIKELIHOODS}, it is {likelihood!r}")
+    if likelihood == 'gaussian':
+        if weights is not None:
+            raise ValueError(f"{who}(weights=...) needs likelihood='posterior': the default likelihood is N(mu, sigsqd) for every row")
+        if post is not None:
+            _refuse_student_noise(post, who)
+        return {}
+    nu = own = None
+    if post is not None:
+        try:
+            nu = post['nu']
+        except (KeyError, TypeError, IndexError):
+            nu = None
+        try:
+            own = post['weights']
+        except (KeyError, TypeError, IndexError):
+            own = None
+    if weights is None and training_rows is not None and own is not None:
+        weights = np.asarray(own, dtype=np.float64).reshape(-1)
+        if weights.shape[0] != training_rows:
+            raise ValueError(f"{who}: the posterior's weights hold {weights.shape[0]} values and {training_rows} rows are being "
+                             f"scored: pass weights= for these rows (or inputs= and data= of the rows the posterior was drawn on)")
+    if weights is not None and np.ndim(weights) and np.all(np.asarray(weights) == 1.0):
+        weights = None                                               # ones: the unweighted likelihood, to the bit
+    out = {}
+    if nu is not None and not np.isinf(nu):
+        out['nu'] = float(nu)
+    if weights is not None:
+        out['weights'] = weights
+    return out
 
 
 class FoKL:
@@ -1374,18 +1416,25 @@ class FoKL:
         kwargs.setdefault('device', self._backend())
         return _robust.resample_robust(mtx, self.phis, self.kernel, inputs, data, self.a, self.b, self.atau, self.btau, **kwargs)
 
-    def score(self, post=None, inputs=None, data=None, clean=False, betas=None, sigsqd=None, mtx=None, **kwargs):
+    def score(self, post=None, inputs=None, data=None, clean=False, betas=None, sigsqd=None, mtx=None, likelihood='gaussian',
+              weights=None, **kwargs):
         """Score the fitted model pointwise over every posterior draw on the device: WAIC and PSIS-LOO of the training rows,
         or the log predictive density of held-out rows -- ``score.score`` with this model's ``mtx``, ``phis`` and ``kernel``,
         which documents the keywords -- method, draws -- and the result.  ``post`` is what ``resample`` returned (its
         ``betas`` and ``sigsqd``), or pass ``betas=`` and ``sigsqd=``: the log density needs sigma^2 per draw, which a fit
         does not keep.  ``inputs`` / ``data`` default to the model's own cleaned training set; ``clean=True`` normalises
         other inputs with the model's ``minmax`` exactly as ``evaluate`` does.  Numpy's random stream and ``setnos`` are
-        left alone."""
+        left alone.
+
+        ``likelihood='gaussian'`` (default) scores N(mu, sigsqd) and refuses a ``resample_robust`` result with a finite nu;
+        ``likelihood='posterior'`` scores the likelihood ``post`` was drawn under: Student-t noise with ``post['nu']`` and,
+        over the training rows, the row weights ``post['weights']``; with other ``inputs``, ``weights=`` gives their [S]
+        precisions (default ones).  ``score.compare`` of a t result with a Gaussian one over the same rows says which noise
+        model predicts the data better."""
+        _posterior_noise(post, 'score', likelihood, weights, None)               # the refusals first, as ever
         if post is not None:
             if betas is not None or sigsqd is not None:
                 raise ValueError("score takes a resample's result OR betas= and sigsqd=, not both")
-            _refuse_student_noise(post, 'score')
             try:
                 betas, sigsqd = post['betas'], post['sigsqd']
             except (KeyError, TypeError, IndexError):
@@ -1399,6 +1448,7 @@ class FoKL:
             mtx = getattr(self, 'mtx', None)
         if mtx is None:
             raise ValueError("score needs a fitted model: call fit first (there is no interaction matrix mtx)")
+        training = inputs is None
         if inputs is None:
             if _str_to_bool(clean):
                 warnings.warn("Cleaning was already performed on default 'inputs', so overriding 'clean' to False.",
@@ -1414,9 +1464,11 @@ class FoKL:
             kwargs_to_clean['minmax'] = self.minmax
             inputs = self.clean(inputs, kwargs_from_other=kwargs_to_clean)
         kwargs.setdefault('device', self._backend())
+        kwargs.update(_posterior_noise(post, 'score', likelihood, weights, np.shape(inputs)[0] if training and np.ndim(inputs) else None))
         return _score.score(betas, sigsqd, mtx, self.phis, self.kernel, inputs, data, **kwargs)
 
-    def predictive(self, post=None, inputs=None, data=None, clean=False, betas=None, sigsqd=None, mtx=None, **kwargs):
+    def predictive(self, post=None, inputs=None, data=None, clean=False, betas=None, sigsqd=None, mtx=None,
+                   likelihood='gaussian', weights=None, **kwargs):
         """The posterior predictive distribution of every row over every posterior draw on the device: its CDF at the
         observed value (PIT), its quantiles -- prediction intervals for NEW measurements, where ``evaluate(ReturnBounds=True)``
         and ``coverage3`` band the mean -- and the coverage of those intervals: ``predictive.predictive`` with this model's
@@ -1424,11 +1476,16 @@ class FoKL:
         result.  ``post`` is what ``resample`` returned (its ``betas`` and ``sigsqd``), or pass ``betas=`` and ``sigsqd=``: the
         predictive needs sigma^2 per draw, which a fit does not keep.  ``inputs`` / ``data`` default to the model's own
         cleaned training set; with other ``inputs`` ``data`` is optional (quantiles alone), and ``clean=True`` normalises
-        them with the model's ``minmax`` exactly as ``evaluate`` does.  Numpy's random stream and ``setnos`` are left alone."""
+        them with the model's ``minmax`` exactly as ``evaluate`` does.  Numpy's random stream and ``setnos`` are left alone.
+
+        ``likelihood='gaussian'`` (default) mixes N(mu, sigsqd) and refuses a ``resample_robust`` result with a finite nu;
+        ``likelihood='posterior'`` mixes what ``post`` was drawn under: t components with ``post['nu']`` degrees of freedom
+        (a t scale is no variance: the Gaussian formula covers too little) and, over the training rows, the row weights
+        ``post['weights']``; with other ``inputs``, ``weights=`` gives their [S] precisions (default ones)."""
+        _posterior_noise(post, 'predictive', likelihood, weights, None)          # the refusals first, as ever
         if post is not None:
             if betas is not None or sigsqd is not None:
                 raise ValueError("predictive takes a resample's result OR betas= and sigsqd=, not both")
-            _refuse_student_noise(post, 'predictive')
             try:
                 betas, sigsqd = post['betas'], post['sigsqd']
             except (KeyError, TypeError, IndexError):
@@ -1443,6 +1500,7 @@ class FoKL:
             mtx = getattr(self, 'mtx', None)
         if mtx is None:
             raise ValueError("predictive needs a fitted model: call fit first (there is no interaction matrix mtx)")
+        training = inputs is None
         if inputs is None:
             if _str_to_bool(clean):
                 warnings.warn("Cleaning was already performed on default 'inputs', so overriding 'clean' to False.",
@@ -1458,6 +1516,8 @@ class FoKL:
             kwargs_to_clean['minmax'] = self.minmax
             inputs = self.clean(inputs, kwargs_from_other=kwargs_to_clean)
         kwargs.setdefault('device', self._backend())
+        kwargs.update(_posterior_noise(post, 'predictive', likelihood, weights,
+                                       np.shape(inputs)[0] if training and np.ndim(inputs) else None))
         return _predictive.predictive(betas, sigsqd, mtx, self.phis, self.kernel, inputs, data, **kwargs)
 
     def design(self, post=None, pool=None, clean=False, picks=64, criterion='variance', target=None, tausqd=None, inputs=None,

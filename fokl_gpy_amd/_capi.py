@@ -37,6 +37,9 @@ SCORE_INSTANCES = ('none', 'waic', 'waic_loo')                # fokl_score_repor
 SCORE_MAX_TAIL = 512                      # fokl_score_rows: entries (M + 1) of a row's list of largest log ratios in LDS
 PREDICTIVE_INSTANCES = ('none', 'pit', 'quantiles', 'pit_quantiles')   # fokl_predictive_report: what the launch computed
 PREDICTIVE_MAX_QUANTILES = 8              # fokl_predictive_rows: quantiles of one call (registers of a lane)
+NOISES = ('gaussian', 'gaussian_weighted', 'student')        # fokl_score_report / fokl_predictive_report: the noise instance
+PREDICTIVE_NU_MAX = 64                    # fokl_predictive_rows_noise: the largest finite nu (FOKL_PREDICTIVE_NU_MAX)
+PREDICTIVE_STUDENT_ITERATIONS = 40        # ... and the fixed bound of the t CDF's continued fraction, host and device
 RESAMPLE_MAX_COLUMNS = 768                # fokl_resample_chains: 12 eigen-coordinates per lane
 RESAMPLE_ATTEMPT_CAP = 64                 # Marsaglia-Tsang attempts per gamma variate
 RESAMPLE_SEGMENTS = 3                     # per-chain sums: first half, second half, the odd last iteration
@@ -111,9 +114,12 @@ SIGNATURES = {
     'fokl_robust_report': (c_int, [c_vp, c_vp]),
     'fokl_robust_rng': (c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int, c_int, ctypes.c_uint32, c_i64, c_vp]),
     'fokl_score_rows': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    'fokl_score_rows_noise': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_vp]),
     'fokl_score_report': (c_int, [c_vp, c_vp]),
     'fokl_predictive_rows': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_dbl, c_int, c_vp, c_vp, c_int, c_int, c_dbl,
                                      c_dbl, c_vp]),
+    'fokl_predictive_rows_noise': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_dbl, c_int, c_vp, c_vp, c_int, c_int,
+                                           c_dbl, c_dbl, c_vp, c_dbl, c_vp]),
     'fokl_predictive_report': (c_int, [c_vp, c_vp]),
     'fokl_design_select': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                    c_vp]),
@@ -2350,7 +2356,22 @@ class DeviceContext:
                     blocks=v[6], iterations=v[7], kept=v[8], attempts=v[9], flagged=v[10], pass_ms=v[11] / 1000.0,
                     reduce_ms=v[12] / 1000.0, step_ms=v[13] / 1000.0, timed_iterations=v[14], total_ms=v[15] / 1000.0)
 
-    def score_rows(self, slots, betas, sigsqd, want_loo=True, want_tail=False):
+    def _sw(self, sw, who):
+        """``sw`` [rows] (sqrt of the rows' precisions) as the noise entry points take it, or None."""
+        if sw is None:
+            return None
+        sw = np.ascontiguousarray(np.reshape(sw, -1), dtype=np.float64)
+        if sw.shape[0] != self.n:
+            raise ValueError(f"{who}: sw holds {sw.shape[0]} values, {self.n} rows are uploaded")
+        return sw
+
+    def score_rows_noise(self, slots, betas, sigsqd, want_loo=True, want_tail=False, nu=np.inf, sw=None):
+        """fokl_score_rows_noise: ``score_rows`` under Student-t noise with ``nu`` degrees of freedom (np.inf: Gaussian) and
+        row precisions ``sw`` [rows] = sqrt(w) (None: ones).  score.score_rows_host(nu=, sw=) is its statement.  nu = inf with
+        sw = None is routed to ``score_rows``' instances and returns its bits."""
+        return self.score_rows(slots, betas, sigsqd, want_loo, want_tail, _noise=(float(nu), self._sw(sw, 'score_rows_noise')))
+
+    def score_rows(self, slots, betas, sigsqd, want_loo=True, want_tail=False, _noise=None):
         """fokl_score_rows over the uploaded rows: ll[i, d] of the uploaded y against the columns ``slots`` times every row of
         ``betas`` [E, nc] with ``sigsqd`` [E], reduced over the DRAWS per row -> stats [S, 8] = lppd, ll_mean, p_waic and, with
         ``want_loo`` (else zeros), elpd_loo, khat, sigma, max r, M'; with ``want_tail`` also the sorted top M + 1 shifted
@@ -2369,22 +2390,35 @@ class DeviceContext:
         if want_tail:
             M = int(min(E // 5, np.ceil(3.0 * np.sqrt(E))))
             tail = np.empty((self.n, M + 1), dtype=np.float64)
-        self._ck(self._lib.fokl_score_rows(self._h, _ptr(s), s.shape[0], _ptr(betas), _ptr(sigsqd), E, int(bool(want_loo)),
-                                           _ptr(stats), _ptr(tail)))
+        if _noise is not None:
+            self._ck(self._lib.fokl_score_rows_noise(self._h, _ptr(s), s.shape[0], _ptr(betas), _ptr(sigsqd), E,
+                                                     int(bool(want_loo)), _ptr(stats), _ptr(tail), _noise[0], _ptr(_noise[1])))
+        else:
+            self._ck(self._lib.fokl_score_rows(self._h, _ptr(s), s.shape[0], _ptr(betas), _ptr(sigsqd), E, int(bool(want_loo)),
+                                               _ptr(stats), _ptr(tail)))
         return (stats, tail) if want_tail else stats
 
     def score_report(self):
         """What the last ``score_rows`` on this context ran (fokl_score_report): ``instance`` ('waic': no list, 'waic_loo'),
         the ``grid`` of one-wavefront workgroups over ``row_tiles`` 16-row tiles, ``lds_bytes``, the ``tail_capacity`` used
-        (M + 1; 0 without want_loo), the ``raw_rows`` that took the khat = inf branch and ``kernel_ms``.  'none' and zeros
-        after a refused call."""
-        out = np.zeros(7, dtype=np.int64)
+        (M + 1; 0 without want_loo), the ``raw_rows`` that took the khat = inf branch, ``kernel_ms`` and the ``noise``
+        instance ('gaussian', 'gaussian_weighted', 'student').  'none' and zeros after a refused call."""
+        out = np.zeros(8, dtype=np.int64)
         self._ck(self._lib.fokl_score_report(self._h, _ptr(out)))
         v = [int(x) for x in out]
         return dict(instance=SCORE_INSTANCES[v[0]], grid=v[1], row_tiles=v[2], lds_bytes=v[3], tail_capacity=v[4],
-                    raw_rows=v[5], kernel_ms=v[6] / 1000.0)
+                    raw_rows=v[5], kernel_ms=v[6] / 1000.0, noise=NOISES[v[7]])
 
-    def predictive_rows(self, slots, betas, sd, rinv, with_data, p, z, max_passes=32, ftol=1e-13, xtol=1e-15):
+    def predictive_rows_noise(self, slots, betas, sd, rinv, with_data, p, z, max_passes=32, ftol=1e-13, xtol=1e-15, nu=np.inf,
+                              sw=None):
+        """fokl_predictive_rows_noise: ``predictive_rows`` for mixtures of t_nu components (``nu`` finite, at most
+        PREDICTIVE_NU_MAX; ``z`` are then quantiles of the standard t_nu) with the scale sd_d / sw_i, ``sw`` [rows] = sqrt of
+        the rows' precisions (None: ones).  predictive.predictive_rows_host(nu=, sw=) is its statement.  nu = inf with sw =
+        None is routed to ``predictive_rows``' instances and returns its bits."""
+        return self.predictive_rows(slots, betas, sd, rinv, with_data, p, z, max_passes, ftol, xtol,
+                                    _noise=(float(nu), self._sw(sw, 'predictive_rows_noise')))
+
+    def predictive_rows(self, slots, betas, sd, rinv, with_data, p, z, max_passes=32, ftol=1e-13, xtol=1e-15, _noise=None):
         """fokl_predictive_rows over the uploaded rows: the mixture over the rows of ``betas`` [E, nc] of N(X_i . beta_d,
         sd_d^2) per uploaded row, ``sd`` [E] and ``rinv`` [E] = 1 / (sd sqrt(2)) as the caller formed them, the uploaded y read
         only ``with_data``; ``p`` [Q] and their standard normal quantiles ``z`` [Q], Q <= 8 -> the block [S, 6 + 5 Q] = mu_0,
@@ -2405,23 +2439,26 @@ class DeviceContext:
             raise ValueError("predictive_rows: one z per p")
         Q = p.shape[0]
         out = np.empty((self.n, 6 + 5 * Q), dtype=np.float64)
-        self._ck(self._lib.fokl_predictive_rows(self._h, _ptr(s), s.shape[0], _ptr(betas), _ptr(sd), _ptr(rinv), E,
-                                                float(np.mean(sd * sd)), int(bool(with_data)), _ptr(p) if Q else None,
-                                                _ptr(z) if Q else None, Q, int(max_passes), float(ftol), float(xtol), _ptr(out)))
+        args = (self._h, _ptr(s), s.shape[0], _ptr(betas), _ptr(sd), _ptr(rinv), E, float(np.mean(sd * sd)), int(bool(with_data)),
+                _ptr(p) if Q else None, _ptr(z) if Q else None, Q, int(max_passes), float(ftol), float(xtol), _ptr(out))
+        if _noise is not None:
+            self._ck(self._lib.fokl_predictive_rows_noise(*args, _noise[0], _ptr(_noise[1])))
+        else:
+            self._ck(self._lib.fokl_predictive_rows(*args))
         return out
 
     def predictive_report(self):
         """What the last ``predictive_rows`` on this context ran (fokl_predictive_report): ``instance`` ('pit': data only,
         'quantiles', 'pit_quantiles'), ``with_data`` and ``with_quantiles``, the ``grid`` of one-wavefront workgroups over
         ``row_tiles`` 16-row tiles, ``lds_bytes``, ``quantiles`` (Q), ``passes_max`` (the most passes any tile ran; pass 0 is
-        not counted), ``passes_sum`` (over the tiles), the ``unresolved`` pairs and ``kernel_ms``.  'none' and zeros after a
-        refused call."""
-        out = np.zeros(9, dtype=np.int64)
+        not counted), ``passes_sum`` (over the tiles), the ``unresolved`` pairs, ``kernel_ms`` and the ``noise`` instance
+        ('gaussian', 'gaussian_weighted', 'student').  'none' and zeros after a refused call."""
+        out = np.zeros(10, dtype=np.int64)
         self._ck(self._lib.fokl_predictive_report(self._h, _ptr(out)))
         v = [int(x) for x in out]
         return dict(instance=PREDICTIVE_INSTANCES[v[0]], with_data=bool(v[0] & 1), with_quantiles=bool(v[0] & 2), grid=v[1],
                     row_tiles=v[2], lds_bytes=v[3], quantiles=v[4], passes_max=v[5], passes_sum=v[6], unresolved=v[7],
-                    kernel_ms=v[8] / 1000.0)
+                    kernel_ms=v[8] / 1000.0, noise=NOISES[v[9]])
 
     def design_select(self, slots, C0, CMC0=None, picks=1, replicates=False, refresh_every=64, keep=False, grid_cap=0):
         """fokl_design_select over the uploaded rows (the pool): greedy selection of ``picks`` rows given C0 = (G + I / tau^2)^-1

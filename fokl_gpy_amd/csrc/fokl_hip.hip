@@ -1901,6 +1901,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_embedded_device.inc"
 #include "fokl_resample_device.inc"
 #include "fokl_robust_device.inc"
+#include "fokl_student.inc"
 #include "fokl_score_device.inc"
 #include "fokl_predictive_device.inc"
 #include "fokl_design_device.inc"

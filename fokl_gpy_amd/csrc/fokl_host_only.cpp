@@ -214,11 +214,22 @@ extern "C" int fokl_score_rows(fokl_ctx *, const int32_t *, int, const double *,
 {
     return FOKL_ERR_HIP;
 }
+extern "C" int fokl_score_rows_noise(fokl_ctx *, const int32_t *, int, const double *, const double *, int, int, double *, double *,
+                                     double, const double *)
+{
+    return FOKL_ERR_HIP;
+}
 extern "C" int fokl_score_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
 // Nor does the predictive distribution per row (fokl_predictive_device.inc); its statement is predictive.predictive_rows_host.
 extern "C" int fokl_predictive_rows(fokl_ctx *, const int32_t *, int, const double *, const double *, const double *, int, double,
                                     int, const double *, const double *, int, int, double, double, double *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_predictive_rows_noise(fokl_ctx *, const int32_t *, int, const double *, const double *, const double *, int,
+                                          double, int, const double *, const double *, int, int, double, double, double *, double,
+                                          const double *)
 {
     return FOKL_ERR_HIP;
 }

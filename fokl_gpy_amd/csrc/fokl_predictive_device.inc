@@ -17,12 +17,38 @@
 // four lanes.  Nothing is accumulated with atomics: the same arguments give the same bits.  Rows past n compute on zeros,
 // count as done and store nothing; padding draws (to a multiple of 16) are skipped.  The test that ends a tile's passes is
 // wave-uniform (__any), every loop has a fixed bound.
+//
+// NOISE selects the instance (fokl_predictive_rows_noise; the statement is predictive.noise_rows_from_means):
+//   PD_GAUSSIAN           the text above, and the code it compiled to before there was a choice
+//   PD_GAUSSIAN_WEIGHTED  row i's components are N(mu_d, sd_d^2 / w_i): sw_i = sqrt(w_i) is read once per row next to y, rinv_d
+//                         sw_i stands for rinv_d, sd_d / sw_i for sd_d in the brackets and the width, mean_sigsqd / sw_i^2 in
+//                         the first trial
+//   PD_STUDENT            the components are t_nu with the scale sd_d / sw_i: scal's second row holds 1 / sd_d, k = sw_i / sd_d
+//                         stands for rinv_d, F = sum T_nu(t) / E and f = sum f_nu(t) k / E with student_terms
+//                         (fokl_student.inc).  ONE copy of student_terms is in the code: the loop over the quantiles inside
+//                         the per-draw loop is rolled too (q, and the sums it adds to, are picked by chains of selects), and
+//                         the PIT is taken in a pass of its own in front of pass 1 (k = 0: the target is y, nothing is
+//                         decided), not in pass 0.  Every lane calls student_terms on every draw, padding draws included
+//                         (their k is 0), and adds only what counts.
 
 namespace fokl {
 
 constexpr int PD_THREADS = 64;
 constexpr int PD_DT = 4;                         // 16-draw tiles per block: independent MFMA chains
 constexpr int PD_QMAX = FOKL_PREDICTIVE_MAX_QUANTILES;
+
+enum { PD_GAUSSIAN = FOKL_NOISE_GAUSSIAN, PD_GAUSSIAN_WEIGHTED = FOKL_NOISE_GAUSSIAN_WEIGHTED, PD_STUDENT = FOKL_NOISE_STUDENT };
+
+// what an instance needs beyond the Gaussian one's arguments: the last kernel argument, empty for PD_GAUSSIAN
+template <int NOISE> struct PdNoise {};
+template <> struct PdNoise<PD_GAUSSIAN_WEIGHTED> {
+    const double *sw;                            // [n] or null (ones)
+};
+template <> struct PdNoise<PD_STUDENT> {
+    const double *sw;                            // [n] or null (ones)
+    const double *tab;                           // the continued fractions' coefficients [4][ST_ROW]
+    StudentArgs k;
+};
 
 struct PdArgs {
     double p[PD_QMAX], z[PD_QMAX];
@@ -42,14 +68,25 @@ __device__ __forceinline__ double pd_pick(const d4 (&acc)[PD_DT], int i)
     return m;
 }
 
+// q[j] for a wave-uniform j, as pd_pick
+template <int QA>
+__device__ __forceinline__ double pd_pick_q(const double (&q)[QA], int j)
+{
+    double m = q[0];
+#pragma unroll
+    for (int t = 1; t < QA; ++t) m = (j == t) ? q[t] : m;
+    return m;
+}
+
 // QM: the quantiles the instance keeps in registers (0: PIT only); args.Q <= QM of them are live
-template <int QM>
+template <int QM, int NOISE>
 __global__ __launch_bounds__(PD_THREADS) void predictive_kernel(double *const *__restrict__ slot_ptr,
                                                                 const int *__restrict__ slots, int nc, int ncp,
                                                                 const double *__restrict__ betas_t,
                                                                 const double *__restrict__ scal, int draws, int dp,
                                                                 const double *__restrict__ data, int64_t n, const PdArgs args,
-                                                                double *__restrict__ out, int *__restrict__ tile_passes)
+                                                                double *__restrict__ out, int *__restrict__ tile_passes,
+                                                                const PdNoise<NOISE> nz)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *xs = lds;                                // [ncp][16]
@@ -66,6 +103,11 @@ __global__ __launch_bounds__(PD_THREADS) void predictive_kernel(double *const *_
         const bool in = r < n;
         draw_tile_load(xs, slot_ptr, slots, nc, ncp, r, in, quad, col);
         const double yv = (in && data) ? data[r] : 0.0;
+        [[maybe_unused]] double swv = 1.0, isw = 1.0;
+        if constexpr (NOISE != PD_GAUSSIAN) {
+            swv = (in && nz.sw) ? nz.sw[r] : 1.0;
+            isw = 1.0 / swv;
+        }
         __syncthreads();                                 // one wavefront per workgroup: orders the LDS traffic
 
         // ---- pass 0
@@ -91,11 +133,17 @@ __global__ __launch_bounds__(PD_THREADS) void predictive_kernel(double *const *_
                 s2 += dd * dd;
                 mn = fmin(mn, m);
                 mx = fmax(mx, m);
-                if (data) ps += 0.5 * erfc((m - yv) * scal[dp + d]);
+                if constexpr (NOISE == PD_GAUSSIAN) {
+                    if (data) ps += 0.5 * erfc((m - yv) * scal[dp + d]);
+                } else if constexpr (NOISE == PD_GAUSSIAN_WEIGHTED) {
+                    if (data) ps += 0.5 * erfc((m - yv) * (scal[dp + d] * swv));
+                }
 #pragma unroll
                 for (int j = 0; j < QM; ++j) {
                     if (j >= Q) break;
-                    const double c = m + sdv * args.z[j];
+                    double c;
+                    if constexpr (NOISE == PD_GAUSSIAN) c = m + sdv * args.z[j];
+                    else c = m + (sdv * isw) * args.z[j];
                     lo[j] = fmin(lo[j], c);
                     hi[j] = fmax(hi[j], c);
                 }
@@ -123,8 +171,15 @@ __global__ __launch_bounds__(PD_THREADS) void predictive_kernel(double *const *_
             hi[j] = b;
         }
         const double mean = mu0 + S1 / E;
-        const double var = fmax((S2 - S1 * S1 / E) / E, 0.0) + args.mean_sigsqd;
-        const double sdp = sqrt(var), width = MX - MN + args.sd_max;
+        double var, width;
+        if constexpr (NOISE == PD_GAUSSIAN) {
+            var = fmax((S2 - S1 * S1 / E) / E, 0.0) + args.mean_sigsqd;
+            width = MX - MN + args.sd_max;
+        } else {
+            var = fmax((S2 - S1 * S1 / E) / E, 0.0) + args.mean_sigsqd * (isw * isw);
+            width = MX - MN + args.sd_max * isw;
+        }
+        const double sdp = sqrt(var);
         unsigned done = in ? 0u : all_done;
 #pragma unroll
         for (int j = 0; j < QM; ++j) {
@@ -138,10 +193,15 @@ __global__ __launch_bounds__(PD_THREADS) void predictive_kernel(double *const *_
 
         // ---- passes 1 .. max_passes
         int ran = 0;
-        if (QM > 0) {
-            for (int k = 1; k <= args.max_passes; ++k) {
-                if (!__any(done != all_done)) break;                 // wave uniform: every row of the tile is done
-                ++ran;
+        if (QM > 0 || NOISE == PD_STUDENT) {
+            for (int k = (NOISE == PD_STUDENT && data) ? 0 : 1; k <= args.max_passes; ++k) {
+                if constexpr (NOISE == PD_STUDENT) {
+                    if (k > 0 && (QM == 0 || !__any(done != all_done))) break;
+                    ran += k > 0;                                    // the PIT's pass is not counted, as pass 0 is not
+                } else {
+                    if (!__any(done != all_done)) break;             // wave uniform: every row of the tile is done
+                    ++ran;
+                }
                 double Fs[QA], fs[QA];
 #pragma unroll
                 for (int j = 0; j < QA; ++j) {
@@ -151,11 +211,43 @@ __global__ __launch_bounds__(PD_THREADS) void predictive_kernel(double *const *_
                 for (int d0 = 0; d0 < dp; d0 += 16 * PD_DT) {
                     d4 acc[PD_DT];
                     draw_product<PD_DT>(xs, betas_t, ncp, dp, d0, quad, col, acc);
+                    if constexpr (NOISE == PD_STUDENT) {
+                        const int targets = k == 0 ? 1 : Q;
+#pragma unroll 1
+                        for (int i = 0; i < 4 * PD_DT; ++i) {
+                            const int d = d0 + 16 * (i >> 2) + quad + 4 * (i & 3);
+                            const bool valid = d < draws;            // no lane leaves: student_terms is a wavefront's call
+                            const double m = pd_pick(acc, i), kv = scal[dp + min(d, dp - 1)] * swv;
+#pragma unroll 1
+                            for (int jj = 0; jj < targets; ++jj) {   // rolled: ONE copy of student_terms
+                                if (k > 0 && !__any(!((done >> jj) & 1u))) continue;     // wave uniform
+                                const double target = k == 0 ? yv : pd_pick_q(q, jj);
+                                double T, f;
+                                student_terms((target - m) * kv, nz.k, nz.tab, T, f);
+                                if (k == 0) {
+                                    if (valid) ps += T;
+                                    continue;
+                                }
+                                const bool add = valid && !((done >> jj) & 1u);
+#pragma unroll
+                                for (int j = 0; j < QM; ++j) {
+                                    if (j == jj && add) {
+                                        Fs[j] += T;
+                                        fs[j] += f * kv;
+                                    }
+                                }
+                            }
+                        }
+                        continue;
+                    }
 #pragma unroll 1
                     for (int i = 0; i < 4 * PD_DT; ++i) {            // rolled: QM copies of erfc and exp, not 16 QM
                         const int d = d0 + 16 * (i >> 2) + quad + 4 * (i & 3);
                         if (d >= draws) continue;                    // padding draws (and blocks past dp)
-                        const double m = pd_pick(acc, i), rv = scal[dp + d];
+                        const double m = pd_pick(acc, i);
+                        double rv;
+                        if constexpr (NOISE == PD_GAUSSIAN) rv = scal[dp + d];
+                        else rv = scal[dp + d] * swv;
 #pragma unroll
                         for (int j = 0; j < QM; ++j) {
                             if ((done >> j) & 1u) continue;
@@ -163,6 +255,13 @@ __global__ __launch_bounds__(PD_THREADS) void predictive_kernel(double *const *_
                             Fs[j] += 0.5 * erfc(-tt);
                             fs[j] += exp(-(tt * tt)) * rv;
                         }
+                    }
+                }
+                if constexpr (NOISE == PD_STUDENT) {
+                    if (k == 0) {                                    // the PIT's pass: the quarters in their order, no decision
+#pragma unroll
+                        for (int qd = 0; qd < 4; ++qd) PS += __shfl(ps, col + 16 * qd, WAVE);
+                        continue;
                     }
                 }
 #pragma unroll
@@ -224,70 +323,87 @@ extern "C" int fokl_predictive_report(const fokl_ctx *ctx, int64_t *out)
     return FOKL_OK;
 }
 
-extern "C" int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sd,
-                                    const double *rinv, int draws, double mean_sigsqd, int with_data, const double *p,
-                                    const double *z, int nq, int max_passes, double ftol, double xtol, double *out)
+// fokl_predictive_rows (nu = INFINITY, sw = null: the Gaussian instances) and fokl_predictive_rows_noise; `name` opens the messages
+static int predictive_rows_any(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sd,
+                               const double *rinv, int draws, double mean_sigsqd, int with_data, const double *p, const double *z,
+                               int nq, int max_passes, double ftol, double xtol, double *out, double nu, const double *sw,
+                               const char *name)
 {
     using namespace fokl;
-    if (!ctx) return fail(nullptr, FOKL_ERR_ARG, "fokl_predictive_rows: null context");
+    const std::string who = name;
+    if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + ": null context");
     std::memset(ctx->predictive_report, 0, sizeof ctx->predictive_report);
-    if (!ctx->have_data) return fail(ctx, FOKL_ERR_STATE, "fokl_predictive_rows: call fokl_upload first");
+    if (!ctx->have_data) return fail(ctx, FOKL_ERR_STATE, who + ": call fokl_upload first");
     if (nc <= 0 || draws <= 0 || !betas || !sd || !rinv || !out || (nq > 0 && (!p || !z)))
-        return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: bad argument");
-    if (draws > (1 << 22) || nc > (1 << 20)) return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: too many draws or columns");
+        return fail(ctx, FOKL_ERR_ARG, who + ": bad argument");
+    if (draws > (1 << 22) || nc > (1 << 20)) return fail(ctx, FOKL_ERR_ARG, who + ": too many draws or columns");
     if (nq < 0 || nq > FOKL_PREDICTIVE_MAX_QUANTILES)
-        return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: " + std::to_string(nq) + " quantiles, one call takes at most "
+        return fail(ctx, FOKL_ERR_ARG, who + ": " + std::to_string(nq) + " quantiles, one call takes at most "
                     "FOKL_PREDICTIVE_MAX_QUANTILES = " + std::to_string(FOKL_PREDICTIVE_MAX_QUANTILES));
     if (!with_data && nq == 0)
-        return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: neither data nor quantiles, nothing would be computed");
-    if (max_passes < 0) return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: max_passes must be >= 0");
+        return fail(ctx, FOKL_ERR_ARG, who + ": neither data nor quantiles, nothing would be computed");
+    if (max_passes < 0) return fail(ctx, FOKL_ERR_ARG, who + ": max_passes must be >= 0");
     if (!std::isfinite(ftol) || ftol < 0.0 || !std::isfinite(xtol) || xtol < 0.0)
-        return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: ftol and xtol must be finite and >= 0");
+        return fail(ctx, FOKL_ERR_ARG, who + ": ftol and xtol must be finite and >= 0");
+    if (!(nu >= 1.0))
+        return fail(ctx, FOKL_ERR_ARG, who + ": nu is NaN or < 1: Student-t noise needs nu >= 1 (INFINITY is Gaussian noise)");
+    const bool student = std::isfinite(nu);
+    if (student && nu > FOKL_PREDICTIVE_NU_MAX)
+        return fail(ctx, FOKL_ERR_ARG, who + ": nu = " + std::to_string(nu) + " is beyond FOKL_PREDICTIVE_NU_MAX = " +
+                    std::to_string(FOKL_PREDICTIVE_NU_MAX) + ", as far as the t CDF's continued fraction is bounded and tested");
+    const int noise = student ? PD_STUDENT : sw ? PD_GAUSSIAN_WEIGHTED : PD_GAUSSIAN;
     if (!std::isfinite(mean_sigsqd) || !(mean_sigsqd > 0.0))
-        return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: the mean of sigsqd must be positive and finite");
+        return fail(ctx, FOKL_ERR_ARG, who + ": the mean of sigsqd must be positive and finite");
     double sd_max = 0.0;
     for (int d = 0; d < draws; ++d) {
         if (!(sd[d] > 0.0) || !std::isfinite(sd[d]) || !(rinv[d] > 0.0) || !std::isfinite(rinv[d]))
-            return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: every sd and rinv must be positive and finite");
+            return fail(ctx, FOKL_ERR_ARG, who + ": every sd and rinv must be positive and finite");
         sd_max = std::max(sd_max, sd[d]);
     }
     for (int j = 0; j < nq; ++j) {
         if (!std::isfinite(p[j]) || !(p[j] > 0.0) || !(p[j] < 1.0) || !std::isfinite(z[j]))
-            return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: every quantile must lie strictly inside (0, 1), with a finite z");
+            return fail(ctx, FOKL_ERR_ARG, who + ": every quantile must lie strictly inside (0, 1), with a finite z");
         for (int k = 0; k < j; ++k)
-            if (p[k] == p[j]) return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: the quantiles repeat a value");
+            if (p[k] == p[j]) return fail(ctx, FOKL_ERR_ARG, who + ": the quantiles repeat a value");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = check_slots(ctx, slots, nc, "fokl_predictive_rows");
+    int rc = check_slots(ctx, slots, nc, who.c_str());
     if (rc) return rc;
     const int64_t n = ctx->n;
-    if (n <= 0) return fail(ctx, FOKL_ERR_STATE, "fokl_predictive_rows: the dataset has no rows");
+    if (n <= 0) return fail(ctx, FOKL_ERR_STATE, who + ": the dataset has no rows");
+    if (sw)
+        for (int64_t i = 0; i < n; ++i)
+            if (!(sw[i] > 0.0) || !std::isfinite(sw[i]))
+                return fail(ctx, FOKL_ERR_ARG, who + ": every sw (the square root of a row's precision) must be finite and > 0");
 
     const int ncp = (nc + 3) & ~3, dp = (draws + 15) & ~15, stride = 6 + 5 * nq;
     const size_t lds_bytes = ((size_t)ncp * 16 + 16) * sizeof(double);
     if (lds_bytes > 160 * 1024)
-        return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: " + std::to_string(nc) + " columns want " + std::to_string(lds_bytes) +
+        return fail(ctx, FOKL_ERR_ARG, who + ": " + std::to_string(nc) + " columns want " + std::to_string(lds_bytes) +
                     " bytes of LDS per 16-row tile, a compute unit has 163840");
     const int64_t tiles = (n + 15) / 16;
     const size_t table_bytes = ((size_t)ncp + 2) * dp * sizeof(double);
     const size_t out_bytes = (size_t)n * stride * sizeof(double);
     const size_t count_bytes = (size_t)tiles * sizeof(int);
+    const size_t noise_bytes = (sw ? (size_t)n : 0) * sizeof(double) + (student ? 4 * ST_ROW * sizeof(double) : 0);
     size_t free_bytes = 0;
     HIP_TRY(ctx, capped_free_bytes("FOKL_PREDICTIVE_FREE_BYTES", &free_bytes));
-    if (table_bytes + out_bytes + count_bytes + (64 << 20) > free_bytes)
-        return fail(ctx, FOKL_ERR_ARG, "fokl_predictive_rows: the call wants " + std::to_string(table_bytes + out_bytes + count_bytes) +
+    if (table_bytes + out_bytes + count_bytes + noise_bytes + (64 << 20) > free_bytes)
+        return fail(ctx, FOKL_ERR_ARG, who + ": the call wants " + std::to_string(table_bytes + out_bytes + count_bytes + noise_bytes) +
                     " bytes on the device and 64 MiB to spare (" + std::to_string(table_bytes) +
                     " bytes of coefficients = (columns + 2) x draws x 8, " + std::to_string(out_bytes) + " of results = rows x (6 + 5 Q) x 8, " +
-                    std::to_string(count_bytes) + " of pass counts), the device has " + std::to_string(free_bytes) + " free" +
+                    std::to_string(count_bytes) + " of pass counts" +
+                    (noise_bytes ? ", " + std::to_string(noise_bytes) + " of row precisions and t coefficients" : std::string()) +
+                    "), the device has " + std::to_string(free_bytes) + " free" +
                     (table_bytes > out_bytes ? " (thin the draws)" : " (take the rows in parts)"));
 
-    // coefficients transposed and zero padded [ncp][dp] | sd [dp] | rinv [dp] (padding draws: zeros, never used)
+    // coefficients transposed and zero padded [ncp][dp] | sd [dp] | rinv [dp], under t noise 1 / sd [dp] (padding draws: zeros)
     std::vector<double> table(((size_t)ncp + 2) * dp, 0.0);
     fill_draw_table(table.data(), betas, draws, nc, ncp, dp);
     double *scal = table.data() + (size_t)ncp * dp;
     for (int d = 0; d < draws; ++d) {
         scal[d] = sd[d];
-        scal[dp + d] = rinv[d];
+        scal[dp + d] = student ? 1.0 / sd[d] : rinv[d];
     }
     PdArgs args = {};
     for (int j = 0; j < nq; ++j) {
@@ -298,7 +414,7 @@ extern "C" int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc,
     args.xtol = xtol;
     args.mean_sigsqd = mean_sigsqd;
     args.sd_max = sd_max;
-    args.e_sqrt_pi = (double)draws * std::sqrt(M_PI);
+    args.e_sqrt_pi = student ? (double)draws : (double)draws * std::sqrt(M_PI);     // what the sum of densities is divided by
     args.Q = nq;
     args.max_passes = max_passes;
 
@@ -309,30 +425,50 @@ extern "C" int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc,
     HIP_TRY(ctx, buf.upload(&d_slots, slots, (size_t)nc));
     HIP_TRY(ctx, buf.get(&d_out, (size_t)n * stride));
     HIP_TRY(ctx, buf.get(&d_count, (size_t)tiles));
+    double *d_sw = nullptr, *d_tab = nullptr;
+    StudentArgs sk = {};
+    if (sw) HIP_TRY(ctx, buf.upload(&d_sw, sw, (size_t)n));
+    if (student) {
+        std::vector<double> tab(4 * ST_ROW);
+        sk = student_fill(nu, tab.data());
+        HIP_TRY(ctx, buf.upload(&d_tab, tab.data(), tab.size()));
+    }
 
-    // the instance: 0, 4 or 8 quantiles in registers (2, 1 and 1 wavefronts per SIMD as compiled).  The grid asks for more
-    // workgroups per CU than are resident: the rest queue behind them, which evens out tiles of different pass counts
-    auto fn = nq == 0 ? predictive_kernel<0> : nq <= 4 ? predictive_kernel<4> : predictive_kernel<8>;
+    // the instance: 0, 4 or 8 quantiles in registers (Gaussian: 2, 1 and 1 wavefronts per SIMD as compiled).  The grid asks
+    // for more workgroups per CU than are resident: the rest queue behind them, which evens out tiles of different pass counts
     const int waves = nq == 0 ? 16 : nq <= 4 ? 12 : 8;
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(waves, 160 * 1024 / lds_bytes));
     const int grid = (int)std::min<int64_t>(tiles, (int64_t)cu_count(ctx) * per_cu);
-    hipError_t e = lds_opt_in(fn, lds_bytes, 160 * 1024);
-    StreamStopwatch watch(ctx, e);
-    const int t0 = watch.mark();
-    if (e == hipSuccess) {
-        TimedRegion timed(ctx, FOKL_K_PREDICTIVE, 0.0, 0.0);             // bytes and flops: below, of the passes that ran
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(PD_THREADS), lds_bytes, ctx->stream, ctx->d_slot_ptr, d_slots, nc, ncp, d_table,
-                           d_table + (size_t)ncp * dp, draws, dp, with_data ? ctx->slot_ptr[FOKL_SLOT_Y] : (double *)nullptr, n,
-                           args, d_out, d_count);
-        e = hipGetLastError();
-    }
-    const int t1 = watch.mark();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    const double kernel_us = watch.us(t0, t1);
+    hipError_t e = hipSuccess;
+    double kernel_us = 0.0;
+    auto run = [&](auto fn, auto nz) {
+        e = lds_opt_in(fn, lds_bytes, 160 * 1024);
+        StreamStopwatch watch(ctx, e);
+        const int t0 = watch.mark();
+        if (e == hipSuccess) {
+            TimedRegion timed(ctx, FOKL_K_PREDICTIVE, 0.0, 0.0);         // bytes and flops: below, of the passes that ran
+            hipLaunchKernelGGL(fn, dim3(grid), dim3(PD_THREADS), lds_bytes, ctx->stream, ctx->d_slot_ptr, d_slots, nc, ncp, d_table,
+                               d_table + (size_t)ncp * dp, draws, dp, with_data ? ctx->slot_ptr[FOKL_SLOT_Y] : (double *)nullptr, n,
+                               args, d_out, d_count, nz);
+            e = hipGetLastError();
+        }
+        const int t1 = watch.mark();
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        kernel_us = watch.us(t0, t1);
+    };
+    auto pick = [&](auto tag, auto nz) {
+        constexpr int NOISE = decltype(tag)::value;
+        if (nq == 0) run(predictive_kernel<0, NOISE>, nz);
+        else if (nq <= 4) run(predictive_kernel<4, NOISE>, nz);
+        else run(predictive_kernel<8, NOISE>, nz);
+    };
+    if (noise == PD_STUDENT) pick(std::integral_constant<int, PD_STUDENT>(), PdNoise<PD_STUDENT>{d_sw, d_tab, sk});
+    else if (noise == PD_GAUSSIAN_WEIGHTED) pick(std::integral_constant<int, PD_GAUSSIAN_WEIGHTED>(), PdNoise<PD_GAUSSIAN_WEIGHTED>{d_sw});
+    else pick(std::integral_constant<int, PD_GAUSSIAN>(), PdNoise<PD_GAUSSIAN>{});
     std::vector<int> count((size_t)tiles, 0);
     if (e == hipSuccess) e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(count.data(), d_count, count_bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(ctx, FOKL_ERR_HIP, std::string("fokl_predictive_rows: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, FOKL_ERR_HIP, std::string(who + ": ") + hipGetErrorString(e));
 
     int64_t most = 0, sum = 0, unresolved = 0;
     for (int64_t t = 0; t < tiles; ++t) {
@@ -358,5 +494,24 @@ extern "C" int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc,
     rep[6] = sum;
     rep[7] = unresolved;
     rep[8] = (int64_t)std::llround(kernel_us);
+    rep[9] = noise;
     return FOKL_OK;
+}
+
+extern "C" int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sd,
+                                    const double *rinv, int draws, double mean_sigsqd, int with_data, const double *p,
+                                    const double *z, int nq, int max_passes, double ftol, double xtol, double *out)
+{
+    return predictive_rows_any(ctx, slots, nc, betas, sd, rinv, draws, mean_sigsqd, with_data, p, z, nq, max_passes, ftol, xtol,
+                               out, INFINITY, nullptr, "fokl_predictive_rows");
+}
+
+// nu = INFINITY with sw = null is routed to fokl_predictive_rows' instances: the same kernel, the same bits
+extern "C" int fokl_predictive_rows_noise(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sd,
+                                          const double *rinv, int draws, double mean_sigsqd, int with_data, const double *p,
+                                          const double *z, int nq, int max_passes, double ftol, double xtol, double *out, double nu,
+                                          const double *sw)
+{
+    return predictive_rows_any(ctx, slots, nc, betas, sd, rinv, draws, mean_sigsqd, with_data, p, z, nq, max_passes, ftol, xtol,
+                               out, nu, sw, "fokl_predictive_rows_noise");
 }

@@ -22,6 +22,12 @@
 //
 // Every merge across lanes runs in the order of the quarters, nothing is accumulated with atomics: the same arguments give
 // the same bits.  Rows past n compute on zeros and store nothing; padding draws (to a multiple of 16) are skipped.
+//
+// NOISE selects the likelihood (fokl_score_rows_noise; the statement is score.log_likelihood with nu and sw); only ll differs:
+//   SC_GAUSSIAN           the text above, and the code it compiled to before there was a choice
+//   SC_GAUSSIAN_WEIGHTED  ll = (c_d + lw) - (sw e)^2 h_d: sw = sqrt(w_row) is read once per row next to y, lw = log(sw) there
+//   SC_STUDENT            ll = (c_d + lw) - hp log1p((sw e)^2 g_d), hp = (nu + 1) / 2, with the t constant c_d and g_d = 1 / (nu
+//                         sigsqd_d) in the two rows of cons (sw = 1, lw = 0 without weights)
 
 namespace fokl {
 
@@ -55,13 +61,26 @@ __device__ inline void sc_lse_merge(double &m, double &s, double m2, double s2)
     m = nm;
 }
 
-template <bool LOO>
+enum { SC_GAUSSIAN = FOKL_NOISE_GAUSSIAN, SC_GAUSSIAN_WEIGHTED = FOKL_NOISE_GAUSSIAN_WEIGHTED, SC_STUDENT = FOKL_NOISE_STUDENT };
+
+// what an instance needs beyond the Gaussian one's arguments: the last kernel argument, empty for SC_GAUSSIAN
+template <int NOISE> struct ScNoise {};
+template <> struct ScNoise<SC_GAUSSIAN_WEIGHTED> {
+    const double *sw;                            // [n] or null (ones)
+};
+template <> struct ScNoise<SC_STUDENT> {
+    const double *sw;                            // [n] or null (ones)
+    double hp;                                   // (nu + 1) / 2
+};
+
+template <bool LOO, int NOISE>
 __global__ __launch_bounds__(SC_THREADS) void score_kernel(double *const *__restrict__ slot_ptr,
                                                            const int *__restrict__ slots, int nc, int ncp,
                                                            const double *__restrict__ betas_t,
                                                            const double *__restrict__ cons, int draws, int dp,
                                                            const double *__restrict__ data, int64_t n, int M,
-                                                           double *__restrict__ stats, double *__restrict__ tail_out)
+                                                           double *__restrict__ stats, double *__restrict__ tail_out,
+                                                           const ScNoise<NOISE> nz)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *xs = lds;                                // [ncp][16]
@@ -79,6 +98,11 @@ __global__ __launch_bounds__(SC_THREADS) void score_kernel(double *const *__rest
         if (LOO)
             for (int k = quad; k < cnt; k += 4) list[k * 16 + col] = -INFINITY;
         const double yv = in ? data[r] : 0.0;
+        [[maybe_unused]] double swv = 1.0, lwv = 0.0;
+        if constexpr (NOISE != SC_GAUSSIAN) {
+            swv = (in && nz.sw) ? nz.sw[r] : 1.0;
+            lwv = log(swv);
+        }
         __syncthreads();                                 // one wavefront per workgroup: orders the LDS traffic
 
         double lm = -INFINITY, ls = 0.0, s1 = 0.0, s2 = 0.0, ll0 = 0.0;
@@ -113,8 +137,14 @@ __global__ __launch_bounds__(SC_THREADS) void score_kernel(double *const *__rest
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     const int d = min(d0 + 16 * t + quad + 4 * v, dp - 1);
-                    const double e = yv - acc[t][v];
-                    llv[t][v] = cons[d] - (e * e) * cons[dp + d];
+                    if constexpr (NOISE == SC_GAUSSIAN) {
+                        const double e = yv - acc[t][v];
+                        llv[t][v] = cons[d] - (e * e) * cons[dp + d];
+                    } else {
+                        const double e = swv * (yv - acc[t][v]);
+                        if constexpr (NOISE == SC_STUDENT) llv[t][v] = (cons[d] + lwv) - nz.hp * log1p((e * e) * cons[dp + d]);
+                        else llv[t][v] = (cons[d] + lwv) - (e * e) * cons[dp + d];
+                    }
                 }
             if (d0 == 0) ll0 = __shfl(llv[0][0], col, WAVE);         // draw 0 of row col: quarter 0, v = 0
 #pragma unroll
@@ -302,53 +332,65 @@ extern "C" int fokl_score_report(const fokl_ctx *ctx, int64_t *out)
     return FOKL_OK;
 }
 
-extern "C" int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sigsqd,
-                               int draws, int want_loo, double *stats_out, double *tail_out)
+// fokl_score_rows (nu = INFINITY, sw = null: the Gaussian instances) and fokl_score_rows_noise; `name` opens the messages
+static int score_rows_any(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sigsqd, int draws,
+                          int want_loo, double *stats_out, double *tail_out, double nu, const double *sw, const char *name)
 {
     using namespace fokl;
-    if (!ctx) return fail(nullptr, FOKL_ERR_ARG, "fokl_score_rows: null context");
+    const std::string who = name;
+    if (!ctx) return fail(nullptr, FOKL_ERR_ARG, who + ": null context");
     std::memset(ctx->score_report, 0, sizeof ctx->score_report);
-    if (!ctx->have_data) return fail(ctx, FOKL_ERR_STATE, "fokl_score_rows: call fokl_upload first");
+    if (!ctx->have_data) return fail(ctx, FOKL_ERR_STATE, who + ": call fokl_upload first");
     if (nc <= 0 || draws <= 0 || !betas || !sigsqd || !stats_out)
-        return fail(ctx, FOKL_ERR_ARG, "fokl_score_rows: bad argument");
-    if (draws > (1 << 22) || nc > (1 << 20)) return fail(ctx, FOKL_ERR_ARG, "fokl_score_rows: too many draws or columns");
-    if (tail_out && !want_loo) return fail(ctx, FOKL_ERR_ARG, "fokl_score_rows: tail_out is an output of want_loo");
+        return fail(ctx, FOKL_ERR_ARG, who + ": bad argument");
+    if (draws > (1 << 22) || nc > (1 << 20)) return fail(ctx, FOKL_ERR_ARG, who + ": too many draws or columns");
+    if (tail_out && !want_loo) return fail(ctx, FOKL_ERR_ARG, who + ": tail_out is an output of want_loo");
     for (int d = 0; d < draws; ++d)
         if (!(sigsqd[d] > 0.0) || !std::isfinite(sigsqd[d]))
-            return fail(ctx, FOKL_ERR_ARG, "fokl_score_rows: every sigsqd must be positive and finite");
+            return fail(ctx, FOKL_ERR_ARG, who + ": every sigsqd must be positive and finite");
+    if (!(nu >= 1.0))
+        return fail(ctx, FOKL_ERR_ARG, who + ": nu is NaN or < 1: Student-t noise needs nu >= 1 (INFINITY is Gaussian noise)");
+    const bool student = std::isfinite(nu);
+    const int noise = student ? SC_STUDENT : sw ? SC_GAUSSIAN_WEIGHTED : SC_GAUSSIAN;
     int M = 0;
     if (want_loo) {
         if (draws < FOKL_SCORE_MIN_DRAWS)
-            return fail(ctx, FOKL_ERR_ARG, "fokl_score_rows: PSIS needs at least " + std::to_string(FOKL_SCORE_MIN_DRAWS) +
+            return fail(ctx, FOKL_ERR_ARG, who + ": PSIS needs at least " + std::to_string(FOKL_SCORE_MIN_DRAWS) +
                         " draws, there are " + std::to_string(draws));
         M = std::min(draws / 5, (int)std::ceil(3.0 * std::sqrt((double)draws)));
         if (M + 1 > FOKL_SCORE_MAX_TAIL)
-            return fail(ctx, FOKL_ERR_ARG, "fokl_score_rows: " + std::to_string(draws) + " draws want a tail list of " +
+            return fail(ctx, FOKL_ERR_ARG, who + ": " + std::to_string(draws) + " draws want a tail list of " +
                         std::to_string(M + 1) + " entries per row, the kernel's LDS list holds FOKL_SCORE_MAX_TAIL = " +
                         std::to_string(FOKL_SCORE_MAX_TAIL) + " (thin the draws; want_loo = 0 has no limit)");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = check_slots(ctx, slots, nc, "fokl_score_rows");
+    int rc = check_slots(ctx, slots, nc, who.c_str());
     if (rc) return rc;
     const int64_t n = ctx->n;
-    if (n <= 0) return fail(ctx, FOKL_ERR_STATE, "fokl_score_rows: the dataset has no rows");
+    if (n <= 0) return fail(ctx, FOKL_ERR_STATE, who + ": the dataset has no rows");
+    if (sw)
+        for (int64_t i = 0; i < n; ++i)
+            if (!(sw[i] > 0.0) || !std::isfinite(sw[i]))
+                return fail(ctx, FOKL_ERR_ARG, who + ": every sw (the square root of a row's precision) must be finite and > 0");
 
     const int ncp = (nc + 3) & ~3, dp = (draws + 15) & ~15, cnt = M + 1;
     const size_t lds_bytes = ((size_t)ncp * 16 + (want_loo ? (size_t)cnt * 16 + (size_t)SC_GRID_MAX * 16 : 16)) * sizeof(double);
     if (lds_bytes > 160 * 1024)
-        return fail(ctx, FOKL_ERR_ARG, "fokl_score_rows: " + std::to_string(nc) + " columns and a tail list of " +
+        return fail(ctx, FOKL_ERR_ARG, who + ": " + std::to_string(nc) + " columns and a tail list of " +
                     std::to_string(want_loo ? cnt : 0) + " entries want " + std::to_string(lds_bytes) +
                     " bytes of LDS per 16-row tile, a compute unit has 163840");
     const size_t tail_bytes = tail_out ? (size_t)n * cnt * sizeof(double) : 0;
     const size_t table_bytes = ((size_t)ncp + 2) * dp * sizeof(double);
     const size_t stats_bytes = (size_t)n * 8 * sizeof(double);
+    const size_t sw_bytes = sw ? (size_t)n * sizeof(double) : 0;
     size_t free_bytes = 0;
     HIP_TRY(ctx, capped_free_bytes("FOKL_SCORE_FREE_BYTES", &free_bytes));
-    if (tail_bytes + table_bytes + stats_bytes + (64 << 20) > free_bytes)
-        return fail(ctx, FOKL_ERR_ARG, "fokl_score_rows: the call wants " + std::to_string(tail_bytes + table_bytes + stats_bytes) +
+    if (tail_bytes + table_bytes + stats_bytes + sw_bytes + (64 << 20) > free_bytes)
+        return fail(ctx, FOKL_ERR_ARG, who + ": the call wants " + std::to_string(tail_bytes + table_bytes + stats_bytes + sw_bytes) +
                     " bytes on the device and 64 MiB to spare (" + std::to_string(tail_bytes) + " bytes of tail_out = rows x (M + 1) x 8, " +
                     std::to_string(table_bytes) + " of coefficients = (columns + 2) x draws x 8, " + std::to_string(stats_bytes) +
-                    " of statistics = rows x 64), the device has " + std::to_string(free_bytes) + " free" +
+                    " of statistics = rows x 64" + (sw ? ", " + std::to_string(sw_bytes) + " of row precisions" : std::string()) +
+                    "), the device has " + std::to_string(free_bytes) + " free" +
                     (tail_bytes > table_bytes + stats_bytes ? " (pass no tail_out, or score the rows in parts)"
                      : table_bytes > stats_bytes ? " (thin the draws)" : " (score the rows in parts)"));
 
@@ -360,6 +402,13 @@ extern "C" int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, cons
         cons[d] = -0.5 * std::log(2.0 * M_PI * sigsqd[d]);
         cons[dp + d] = 0.5 / sigsqd[d];
     }
+    if (student) {                                   // c [dp] | g [dp] of the t likelihood (score.student_constants)
+        const double lead = std::log(student_gamma_ratio(0.5 * nu));
+        for (int d = 0; d < draws; ++d) {
+            cons[d] = lead - 0.5 * std::log(nu * M_PI * sigsqd[d]);
+            cons[dp + d] = 1.0 / (nu * sigsqd[d]);
+        }
+    }
     DeviceBuffers buf;
     double *d_table = nullptr, *d_stats = nullptr, *d_tail = nullptr;
     int *d_slots = nullptr;
@@ -367,26 +416,40 @@ extern "C" int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, cons
     HIP_TRY(ctx, buf.upload(&d_slots, slots, (size_t)nc));
     HIP_TRY(ctx, buf.get(&d_stats, (size_t)n * 8));
     if (tail_out) HIP_TRY(ctx, buf.get(&d_tail, (size_t)n * cnt));
+    double *d_sw = nullptr;
+    if (sw) HIP_TRY(ctx, buf.upload(&d_sw, sw, (size_t)n));
 
     const int64_t tiles = (n + 15) / 16;
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(16, 160 * 1024 / lds_bytes));
     const int grid = (int)std::min<int64_t>(tiles, (int64_t)cu_count(ctx) * per_cu);
-    auto fn = want_loo ? score_kernel<true> : score_kernel<false>;
-    hipError_t e = lds_opt_in(fn, lds_bytes, 160 * 1024);
-    StreamStopwatch watch(ctx, e);
-    const int t0 = watch.mark();
-    if (e == hipSuccess) {
-        TimedRegion timed(ctx, FOKL_K_SCORE, 8.0 * (double)n * (nc + 9) + (double)tail_bytes, 2.0 * (double)n * ncp * draws);
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(SC_THREADS), lds_bytes, ctx->stream, ctx->d_slot_ptr, d_slots, nc, ncp,
-                           d_table, d_table + (size_t)ncp * dp, draws, dp, ctx->slot_ptr[FOKL_SLOT_Y], n, M, d_stats, d_tail);
-        e = hipGetLastError();
+    hipError_t e = hipSuccess;
+    double kernel_us = 0.0;
+    auto run = [&](auto fn, auto nz) {
+        e = lds_opt_in(fn, lds_bytes, 160 * 1024);
+        StreamStopwatch watch(ctx, e);
+        const int t0 = watch.mark();
+        if (e == hipSuccess) {
+            TimedRegion timed(ctx, FOKL_K_SCORE, 8.0 * (double)n * (nc + 9) + (double)tail_bytes, 2.0 * (double)n * ncp * draws);
+            hipLaunchKernelGGL(fn, dim3(grid), dim3(SC_THREADS), lds_bytes, ctx->stream, ctx->d_slot_ptr, d_slots, nc, ncp,
+                               d_table, d_table + (size_t)ncp * dp, draws, dp, ctx->slot_ptr[FOKL_SLOT_Y], n, M, d_stats, d_tail, nz);
+            e = hipGetLastError();
+        }
+        const int t1 = watch.mark();
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        kernel_us = watch.us(t0, t1);
+    };
+    if (noise == SC_STUDENT) {
+        const ScNoise<SC_STUDENT> nz = {d_sw, 0.5 * (nu + 1.0)};
+        want_loo ? run(score_kernel<true, SC_STUDENT>, nz) : run(score_kernel<false, SC_STUDENT>, nz);
+    } else if (noise == SC_GAUSSIAN_WEIGHTED) {
+        const ScNoise<SC_GAUSSIAN_WEIGHTED> nz = {d_sw};
+        want_loo ? run(score_kernel<true, SC_GAUSSIAN_WEIGHTED>, nz) : run(score_kernel<false, SC_GAUSSIAN_WEIGHTED>, nz);
+    } else {
+        want_loo ? run(score_kernel<true, SC_GAUSSIAN>, ScNoise<SC_GAUSSIAN>{}) : run(score_kernel<false, SC_GAUSSIAN>, ScNoise<SC_GAUSSIAN>{});
     }
-    const int t1 = watch.mark();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    const double kernel_us = watch.us(t0, t1);
     if (e == hipSuccess) e = hipMemcpy(stats_out, d_stats, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess && tail_out) e = hipMemcpy(tail_out, d_tail, tail_bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(ctx, FOKL_ERR_HIP, std::string("fokl_score_rows: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, FOKL_ERR_HIP, std::string(who + ": ") + hipGetErrorString(e));
 
     int64_t raw_rows = 0;
     if (want_loo)
@@ -399,5 +462,19 @@ extern "C" int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, cons
     rep[4] = want_loo ? cnt : 0;
     rep[5] = raw_rows;
     rep[6] = (int64_t)std::llround(kernel_us);
+    rep[7] = noise;
     return FOKL_OK;
+}
+
+extern "C" int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sigsqd,
+                               int draws, int want_loo, double *stats_out, double *tail_out)
+{
+    return score_rows_any(ctx, slots, nc, betas, sigsqd, draws, want_loo, stats_out, tail_out, INFINITY, nullptr, "fokl_score_rows");
+}
+
+// nu = INFINITY with sw = null is routed to fokl_score_rows' instances: the same kernel, the same bits
+extern "C" int fokl_score_rows_noise(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sigsqd,
+                                     int draws, int want_loo, double *stats_out, double *tail_out, double nu, const double *sw)
+{
+    return score_rows_any(ctx, slots, nc, betas, sigsqd, draws, want_loo, stats_out, tail_out, nu, sw, "fokl_score_rows_noise");
 }

@@ -223,6 +223,9 @@ class HipBackend:
     def score_rows(self, slots, betas, sigsqd, want_loo=True, want_tail=False):
         return self.ctx.score_rows(slots, betas, sigsqd, want_loo, want_tail)
 
+    def score_rows_noise(self, slots, betas, sigsqd, want_loo=True, want_tail=False, nu=float('inf'), sw=None):
+        return self.ctx.score_rows_noise(slots, betas, sigsqd, want_loo, want_tail, nu, sw)
+
     def score_report(self):
         return self.ctx.score_report()
 
@@ -242,6 +245,10 @@ class HipBackend:
 
     def predictive_rows(self, slots, betas, sd, rinv, with_data, p, z, max_passes=32, ftol=1e-13, xtol=1e-15):
         return self.ctx.predictive_rows(slots, betas, sd, rinv, with_data, p, z, max_passes, ftol, xtol)
+
+    def predictive_rows_noise(self, slots, betas, sd, rinv, with_data, p, z, max_passes=32, ftol=1e-13, xtol=1e-15,
+                              nu=float('inf'), sw=None):
+        return self.ctx.predictive_rows_noise(slots, betas, sd, rinv, with_data, p, z, max_passes, ftol, xtol, nu, sw)
 
     def predictive_report(self):
         return self.ctx.predictive_report()

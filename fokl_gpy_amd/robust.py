@@ -371,7 +371,8 @@ _SIGNATURE = """
                 iteration; ESS (initial positive sequence) of the kept rows, None under keep=None
       chain_mean, chain_var   dicts with the same keys, per chain
       flagged [chains], flagged_at, flag_reason (FLAG_*), attempts_total, attempts_max, sigsqd0, tausqd0, sums, shift
-    ``FoKL.score`` and ``FoKL.predictive`` assume a Gaussian likelihood and refuse a result whose ``nu`` is finite.
+    ``FoKL.score`` and ``FoKL.predictive`` assume a Gaussian likelihood and refuse a result whose ``nu`` is finite, unless
+    they are called with ``likelihood='posterior'``, which reads ``nu`` and ``weights`` from the result.
     numpy's global random stream is not consumed and nothing of a model is changed."""
 
 

@@ -27,6 +27,16 @@ PSIS (E >= 25), M = min(E // 5, ceil(3 sqrt(E))):
 Totals are sums over the rows, standard errors sqrt(S var(pointwise)) (numpy's default divisor), p_loo = sum(lppd_i -
 elpd_loo_i), khat_threshold = min(1 - 1 / log10(E), 0.7).
 
+Under Student-t noise with ``nu`` degrees of freedom (finite nu >= 1: sigsqd_d is the squared SCALE, as ``resample_robust``
+draws it) and / or known row precisions w_i (``weights``; sw_i = sqrt(w_i), lw_i = log(sw_i) = 0.5 log(w_i)) only ll changes:
+
+  Student            ll[i, d] = c_d + lw_i - ((nu + 1) / 2) log1p((sw_i e)^2 g_d),   e = y_i - X_i . beta_d,
+                     c_d = log(Gamma((nu + 1) / 2) / Gamma(nu / 2)) - 0.5 log(nu pi sigsqd_d)  (``student_constants``: the
+                     ratio of the two Gammas is formed as ONE number, never as a difference of two lgamma), g_d = 1 / (nu sigsqd_d)
+  weighted Gaussian  ll[i, d] = c_d + lw_i - (sw_i e)^2 h_d, with c_d and h_d as above
+
+and everything after ll is the text above (``fokl_score_rows_noise``).  With nu = inf and no weights it IS the text above.
+
 ``score`` runs columns and reduction on the device (``fokl_score_rows``, csrc/fokl_score_device.inc; without the library or
 a gfx950 device it raises, there is no host fallback).  ``score_host`` is the same function in numpy with no device: the
 STATEMENT the kernel is tested against (``score_rows_host``).  They share ``_prepare`` (every check; touches no device) and
@@ -83,11 +93,39 @@ def likelihood_constants(sigsqd):
     return c, 0.5 / sigsqd
 
 
-def log_likelihood(X, y, betas, sigsqd):
-    """ll [S, E]: the matrix the device never stores."""
-    c, h = likelihood_constants(sigsqd)
+def gamma_ratio(a):
+    """Gamma(a + 1/2) / Gamma(a) for a >= 1/2: ``math.gamma`` twice below 80 (a few ulp), above it sqrt(a) times exp of the
+    asymptotic series (-1 / 8 + 1 / (192 a^2) - 1 / (640 a^4) + 17 / (14336 a^6)) / a (the next term is below 1e-18 there).
+    The difference of two ``lgamma`` loses every digit that their size has in front of the point (1e-6 at nu = 1e9); this
+    does not.  The native entry points hold the same text."""
+    a = float(a)
+    if a < 80.0:
+        return math.gamma(a + 0.5) / math.gamma(a)
+    r = 1.0 / (a * a)
+    return math.sqrt(a) * math.exp((-1.0 / 8.0 + (1.0 / 192.0 + (-1.0 / 640.0 + 17.0 / 14336.0 * r) * r) * r) / a)
+
+
+def student_constants(sigsqd, nu):
+    """(c, g, hp) with ll = c + lw - hp log1p((sw e)^2 g) under Student-t noise (module docstring)."""
+    sigsqd = np.asarray(sigsqd, dtype=np.float64).reshape(-1)
+    lead = math.log(gamma_ratio(0.5 * nu))
+    c = np.array([lead - 0.5 * math.log(nu * math.pi * float(s)) for s in sigsqd])
+    return c, 1.0 / (nu * sigsqd), 0.5 * (nu + 1.0)
+
+
+def log_likelihood(X, y, betas, sigsqd, nu=np.inf, sw=None):
+    """ll [S, E]: the matrix the device never stores.  ``nu`` finite: Student-t noise; ``sw`` [S]: sqrt of the row precisions."""
     e = np.asarray(y, dtype=np.float64).reshape(-1, 1) - np.asarray(X, dtype=np.float64) @ np.asarray(betas, dtype=np.float64).T
-    return c - (e * e) * h
+    if not np.isfinite(nu) and sw is None:
+        c, h = likelihood_constants(sigsqd)
+        return c - (e * e) * h
+    sw = np.ones(e.shape[0]) if sw is None else np.asarray(sw, dtype=np.float64).reshape(-1)
+    lw, e = np.log(sw)[:, None], sw[:, None] * e
+    if np.isfinite(nu):
+        c, g, hp = student_constants(sigsqd, nu)
+        return (c + lw) - hp * np.log1p((e * e) * g)
+    c, h = likelihood_constants(sigsqd)
+    return (c + lw) - (e * e) * h
 
 
 def _logsumexp(a):
@@ -138,10 +176,10 @@ def psis_row(ll):
     return _logsumexp(lw + llo) - _logsumexp(lw), khat, sigma, rmax, n_tail, s[E - M - 1:]
 
 
-def score_rows_host(X, y, betas, sigsqd, want_loo=True, want_tail=False):
-    """The statement of ``fokl_score_rows`` -> stats [S, 8] (columns ``STATS``; 3 .. 7 are zero without ``want_loo``), with
-    ``want_tail`` also tail [S, M + 1]."""
-    ll = log_likelihood(X, y, betas, sigsqd)
+def score_rows_host(X, y, betas, sigsqd, want_loo=True, want_tail=False, nu=np.inf, sw=None):
+    """The statement of ``fokl_score_rows`` (and, with ``nu`` or ``sw``, of ``fokl_score_rows_noise``) -> stats [S, 8] (columns
+    ``STATS``; 3 .. 7 are zero without ``want_loo``), with ``want_tail`` also tail [S, M + 1]."""
+    ll = log_likelihood(X, y, betas, sigsqd, nu, sw)
     S, E = ll.shape
     stats = np.zeros((S, 8))
     m = ll.max(axis=1)
@@ -168,10 +206,16 @@ def _methods(method):
     return tuple(name for name in METHODS if name in names)
 
 
-def _prepare(betas, sigsqd, mtx, phis, kernel, inputs, data, method, draws):
+def _prepare(betas, sigsqd, mtx, phis, kernel, inputs, data, method, draws, nu=np.inf, weights=None):
     """Every check of ``score`` / ``score_host`` (ValueError) and the arguments in the form both use.  Touches no device."""
     kid = _kernel_id(kernel)
     methods = _methods(method)
+    try:
+        nu = float(np.inf if nu is None else nu)
+    except (TypeError, ValueError):
+        raise ValueError(f"nu must be a number >= 1 or np.inf, it is {nu!r}") from None
+    if not nu >= 1.0:
+        raise ValueError(f"nu = {nu:g} is NaN or < 1: Student-t noise needs nu >= 1 (nu = np.inf is Gaussian noise)")
     if betas is None or sigsqd is None:
         raise ValueError("score needs betas [draws, terms + 1] AND sigsqd [draws]: a fit keeps no sigma^2 per draw, resample does")
     betas = np.asarray(betas, dtype=np.float64)
@@ -203,6 +247,16 @@ def _prepare(betas, sigsqd, mtx, phis, kernel, inputs, data, method, draws):
         raise ValueError(f"data must hold one finite value per row of inputs ({S})")
     if not np.isfinite(inputs).all():
         raise ValueError("inputs must be finite")
+    sw = None
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != S:
+            raise ValueError(f"weights must hold one value per row ({S}), there are {w.shape[0]}")
+        if not np.isfinite(w).all() or np.any(w <= 0.0):
+            raise ValueError("weights must be finite and > 0 (drop a row instead of giving it no weight)")
+        sw = np.sqrt(w)
+        if not np.isfinite(np.log(sw)).all() or np.any(sw <= 0.0):
+            raise ValueError("weights must be finite and > 0 after their square root as well")
     if kid == _population.getKernels.KERNEL_SPLINES and (inputs.min() < 0.0 or inputs.max() > 1.0):
         raise ValueError("Inputs are not normalized correctly: they must lie in [0, 1] (clean=True normalises them)")
     if draws is not None:
@@ -232,14 +286,17 @@ def _prepare(betas, sigsqd, mtx, phis, kernel, inputs, data, method, draws):
                              f"holds FOKL_SCORE_MAX_TAIL = {MAX_TAIL} (at most {max_draws_loo()} draws: thin them with an index "
                              f"array; 'waic' and 'lpd' have no limit)")
     return dict(kid=kid, betas=np.ascontiguousarray(betas), sigsqd=np.ascontiguousarray(sigsqd), mtx=mtx.astype(np.int32),
-                phis=phis, kernel=kernel, inputs=np.ascontiguousarray(inputs), data=data, methods=methods, S=S, M=M, E=E)
+                phis=phis, kernel=kernel, inputs=np.ascontiguousarray(inputs), data=data, methods=methods, S=S, M=M, E=E, nu=nu,
+                sw=sw)
 
 
 def _assemble(p, stats):
     """A ScoreResult from the per-row statistics [S, 8]."""
     S, E, methods = p['S'], p['E'], p['methods']
     se = lambda v: float(np.sqrt(S * np.var(v)))
-    res = ScoreResult(method=methods, rows=S, draws=E, pointwise=dict(lppd=stats[:, 0].copy()))
+    nu = p.get('nu', np.inf)
+    res = ScoreResult(method=methods, rows=S, draws=E, pointwise=dict(lppd=stats[:, 0].copy()), nu=nu,
+                      noise='student' if np.isfinite(nu) else 'gaussian', weighted=p.get('sw') is not None)
     pw = res['pointwise']
     res.update(lppd=float(pw['lppd'].sum()), se_lppd=se(pw['lppd']))
     if 'waic' in methods or 'loo' in methods:
@@ -277,32 +334,41 @@ _SIGNATURE = """
     method        : 'waic', 'loo', 'lpd' or several: 'lpd' is the log predictive density alone (held-out rows)
     draws         : None uses ALL rows of betas, an integer the last ``draws`` rows, an integer array those rows (rows of
                     several chains are chain-major, so thinning needs the array form).  Nothing is drawn at random.
+    nu            : np.inf (default): Gaussian noise; finite nu >= 1: sigsqd is the squared SCALE of Student-t noise with nu
+                    degrees of freedom, as ``resample_robust`` draws it
+    weights       : None (ones) or [S] known relative precisions of the rows, finite and > 0: row i's noise has the scale
+                    sqrt(sigsqd / w_i).  With nu = np.inf and no weights the call is today's, to the bit.
 
     Returns a ``ScoreResult`` (a dict with attribute access): rows, draws, method, lppd, se_lppd; with 'waic' elpd_waic,
     p_waic, se_waic, waic; with 'loo' elpd_loo, p_loo, se_loo, looic, khat [S], khat_threshold, khat_bad (rows above it),
-    khat_bad_rows (their indices, at most 1 000), tail_length (M); ``pointwise`` holds the per-row arrays [S] by name."""
+    khat_bad_rows (their indices, at most 1 000), tail_length (M); ``pointwise`` holds the per-row arrays [S] by name; nu,
+    noise ('gaussian' or 'student') and weighted say which likelihood was scored."""
 
 
-def score(betas, sigsqd, mtx, phis, kernel, inputs, data, method=('waic', 'loo'), draws=None, device=None):
+def score(betas, sigsqd, mtx, phis, kernel, inputs, data, method=('waic', 'loo'), draws=None, device=None, nu=np.inf,
+          weights=None):
     """Score every row over every draw on the device.
 
     device        : device index (default: the process's device, as for ``fit``) or a backend.  The rows replace the
                     dataset uploaded to that device's context, as ``evaluate`` and ``propagate`` do."""
-    p = _prepare(betas, sigsqd, mtx, phis, kernel, inputs, data, method, draws)
+    p = _prepare(betas, sigsqd, mtx, phis, kernel, inputs, data, method, draws, nu, weights)
     backend = device if hasattr(device, 'score_rows') and hasattr(device, 'build_terms') else None
     if backend is None:
         from . import FoKLRoutines
         backend = FoKLRoutines.device_backend(device)
     columns = _population._DeviceColumns(p, backend)
+    if np.isfinite(p['nu']) or p['sw'] is not None:
+        return _assemble(p, backend.score_rows_noise(columns.slots, p['betas'], p['sigsqd'], 'loo' in p['methods'], nu=p['nu'],
+                                                     sw=p['sw']))
     return _assemble(p, backend.score_rows(columns.slots, p['betas'], p['sigsqd'], 'loo' in p['methods']))
 
 
-def score_host(betas, sigsqd, mtx, phis, kernel, inputs, data, method=('waic', 'loo'), draws=None):
+def score_host(betas, sigsqd, mtx, phis, kernel, inputs, data, method=('waic', 'loo'), draws=None, nu=np.inf, weights=None):
     """``score`` with columns and reduction in numpy on this host: the statement of the computation (module docstring), for
     tests and for reading.  Same arguments, same result fields."""
-    p = _prepare(betas, sigsqd, mtx, phis, kernel, inputs, data, method, draws)
+    p = _prepare(betas, sigsqd, mtx, phis, kernel, inputs, data, method, draws, nu, weights)
     X = basis_matrix(p['inputs'], p['mtx'], p['phis'], p['kernel']) if p['mtx'].shape[0] else np.ones((p['S'], 1))
-    return _assemble(p, score_rows_host(X, p['data'], p['betas'], p['sigsqd'], 'loo' in p['methods']))
+    return _assemble(p, score_rows_host(X, p['data'], p['betas'], p['sigsqd'], 'loo' in p['methods'], nu=p['nu'], sw=p['sw']))
 
 
 score.__doc__ += _SIGNATURE

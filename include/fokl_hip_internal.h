@@ -29,10 +29,10 @@
  *                              Gibbs chains under Student-t noise and given row weights: a weighted pass over the rows per
  *                              iteration (fokl_gpy_amd/robust.py), one pass or one step alone, what the last call ran, and
  *                              the host's view of their random numbers
- *   fokl_score_rows / fokl_score_report
+ *   fokl_score_rows / fokl_score_rows_noise / fokl_score_report
  *                              the log predictive density of every row over all draws: WAIC and PSIS-LOO
  *                              (fokl_gpy_amd/score.py), and what its last launch ran
- *   fokl_predictive_rows / fokl_predictive_report
+ *   fokl_predictive_rows / fokl_predictive_rows_noise / fokl_predictive_report
  *                              the predictive distribution of every row over all draws: PIT, quantiles and their brackets
  *                              (fokl_gpy_amd/predictive.py), and what its last launch ran
  *   fokl_design_select / fokl_design_report
@@ -1044,7 +1044,13 @@ enum {
     FOKL_SCORE_WAIC = 1,      /* want_loo = 0: lppd, ll_mean, p_waic only, no list in LDS */
     FOKL_SCORE_WAIC_LOO = 2   /* also the top-(M + 1) list, the Pareto fit and elpd_loo */
 };
-#define FOKL_SCORE_REPORT_LEN 7
+/* the last entry of fokl_score_report and of fokl_predictive_report: the noise instance of the kernel that ran */
+enum {
+    FOKL_NOISE_GAUSSIAN = 0,           /* N(mu, sigsqd): the instance of fokl_score_rows / fokl_predictive_rows */
+    FOKL_NOISE_GAUSSIAN_WEIGHTED = 1,  /* N(mu, sigsqd / w_i) */
+    FOKL_NOISE_STUDENT = 2             /* t_nu(mu, scale sqrt(sigsqd / w_i)), weighted or not */
+};
+#define FOKL_SCORE_REPORT_LEN 8
 #define FOKL_SCORE_STATS 8
 #define FOKL_SCORE_MIN_DRAWS 25      /* PSIS needs a tail of at least 5 draws */
 /* Entries (M + 1) of a row's list of largest log ratios in LDS: 512 x 16 rows x 8 B = 64 KiB of the compute unit's 160 KiB,
@@ -1080,9 +1086,23 @@ int fokl_score_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const double *b
  *   out[0]  the instance (above); zeros after a call that returned an error
  *   out[1]  the grid (workgroups = wavefronts)     out[2]  16-row tiles (more than the grid: the tile loop went round)
  *   out[3]  dynamic LDS bytes     out[4]  tail capacity used, M + 1 (0 without want_loo)
- *   out[5]  rows that took the khat = +inf branch     out[6]  kernel microseconds
+ *   out[5]  rows that took the khat = +inf branch     out[6]  kernel microseconds     out[7]  the noise instance (FOKL_NOISE_*)
  */
 int fokl_score_report(const fokl_ctx *ctx, int64_t *out);
+
+/*
+ * fokl_score_rows under Student-t noise and / or known row precisions: its arguments, then
+ *   nu   INFINITY: Gaussian noise; finite and >= 1: sigsqd[d] is the squared SCALE of t noise with nu degrees of freedom and
+ *        ll[i][d] = c_d + log(sw_i) - ((nu + 1) / 2) log1p((sw_i e)^2 / (nu sigsqd[d])), e = y_i - X_i . betas[d],
+ *        c_d = log(Gamma((nu + 1) / 2) / Gamma(nu / 2)) - log(nu pi sigsqd[d]) / 2 (the ratio formed as one number)
+ *   sw   NULL (ones) or [rows] (host): sqrt of the rows' precisions w_i, finite and > 0; uploaded with the call, its 8 rows
+ *        bytes count in the free-memory test.  Gaussian with sw: ll = c_d + log(sw_i) - (sw_i e)^2 (0.5 / sigsqd[d]).
+ * Everything after ll is fokl_score_rows' text: new instances of score_kernel, the same tile, merge order and report.
+ * nu = INFINITY with sw = NULL is ROUTED to fokl_score_rows (its instance, its bits).  Refused as well: nu NaN or < 1; an sw
+ * that is not finite or <= 0.  score.score_rows_host(nu=, sw=) is the statement.
+ */
+int fokl_score_rows_noise(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sigsqd, int draws,
+                          int want_loo, double *stats_out, double *tail_out, double nu, const double *sw);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* The predictive distribution per row: PIT and quantiles (csrc/fokl_predictive_device.inc; fokl_gpy_amd/predictive.py) */
@@ -1094,11 +1114,18 @@ enum {
     FOKL_PREDICTIVE_PIT = 1,        /* with_data: the CDF at the uploaded y from pass 0 */
     FOKL_PREDICTIVE_QUANTILES = 2   /* nq > 0: brackets, first trial and the pass loop */
 };
-#define FOKL_PREDICTIVE_REPORT_LEN 9
+#define FOKL_PREDICTIVE_REPORT_LEN 10
 #define FOKL_PREDICTIVE_BASE 6            /* columns of a result row before the quantiles' */
 #define FOKL_PREDICTIVE_PER_QUANTILE 5    /* ... and per quantile */
 /* Quantiles of one call: a lane keeps q, residual, bracket and two partial sums of each in registers. */
 #define FOKL_PREDICTIVE_MAX_QUANTILES 8
+/* The largest finite nu of fokl_predictive_rows_noise and the fixed bound of the continued fraction behind the t CDF
+ * (csrc/fokl_student.inc; predictive.student_terms is its statement): within the bound every argument has converged for
+ * every nu in [1, NU_MAX] (nu = 64 takes 32 iterations at most), and the CDF is within 1e-14 of scipy.special.stdtr there
+ * (tests/test_student_host.py).  The CDF itself holds that bound with 64 iterations up to nu = 1 000 (4e-15); the limit stays
+ * where the density also agrees with scipy.stats.t.pdf to 1e-14, which it no longer does at nu = 256 (1e-13). */
+#define FOKL_PREDICTIVE_NU_MAX 64
+#define FOKL_PREDICTIVE_STUDENT_ITERATIONS 40
 
 /*
  * The predictive of row i is the equal-weight mixture over the draws d of N(mu_id, sd[d]^2), mu_id = X_i . betas[d], over
@@ -1134,8 +1161,28 @@ int fokl_predictive_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const doub
  *   out[3]  dynamic LDS bytes     out[4]  nq
  *   out[5]  the most passes any tile ran (pass 0 not counted)     out[6]  the sum of passes over the tiles
  *   out[7]  unresolved (row, quantile) pairs: |r| > ftol     out[8]  kernel microseconds
+ *   out[9]  the noise instance (FOKL_NOISE_*)
  */
 int fokl_predictive_report(const fokl_ctx *ctx, int64_t *out);
+
+/*
+ * fokl_predictive_rows under Student-t noise and / or known row precisions: its arguments, then
+ *   nu   INFINITY: Gaussian components; finite, 1 <= nu <= FOKL_PREDICTIVE_NU_MAX: row i's predictive is the mixture over d
+ *        of t_nu(mu_id, scale sd[d] / sw_i); z [nq] are then the quantiles of the standard t_nu (any finite values)
+ *   sw   NULL (ones) or [rows] (host): sqrt of the rows' precisions, finite and > 0; uploaded with the call, its 8 rows
+ *        bytes count in the free-memory test
+ * The passes and the decision rule are fokl_predictive_rows' with k_id = sw_i / sd[d] (Student; Gaussian: rinv[d] sw_i) in
+ * the place of rinv[d]: t = (q - mu_d) k_id, F = mean_d T_nu(t), f = mean_d f_nu(t) k_id, pit = mean_d T_nu((y - mu_d) k_id);
+ * brackets min / max over d of mu_d + (sd[d] / sw_i) z; first trial mean + z sqrt(var_mu + mean_sigsqd / sw_i^2); width
+ * max mu - min mu + max sd / sw_i.  T_nu and f_nu are student_terms (csrc/fokl_student.inc), one continued fraction with
+ * the fixed bound above; predictive.predictive_rows_host(nu=, sw=) is the statement.  New instances of predictive_kernel:
+ * the same tile, merge order and report; the Student instances take the PIT in a pass of its own (counted in out[5], out[6]).
+ * nu = INFINITY with sw = NULL is ROUTED to fokl_predictive_rows (its instance, its bits).  Refused as well: nu NaN or < 1;
+ * a finite nu beyond FOKL_PREDICTIVE_NU_MAX; an sw that is not finite or <= 0.
+ */
+int fokl_predictive_rows_noise(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, const double *sd,
+                               const double *rinv, int draws, double mean_sigsqd, int with_data, const double *p, const double *z,
+                               int nq, int max_passes, double ftol, double xtol, double *out, double nu, const double *sw);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* Which pool rows to measure next: greedy optimal design (csrc/fokl_design_device.inc; fokl_gpy_amd/design.py) */
