@@ -37,6 +37,7 @@ from . import population as _population
 from . import score as _score
 from . import predictive as _predictive
 from . import design as _design
+from . import acquire as _acquire
 from . import infer as _infer
 from . import resample as _resample
 from . import robust as _robust
@@ -1578,6 +1579,53 @@ class FoKL:
         kwargs.setdefault('device', self._backend())
         res = _design.design(mtx, self.phis, self.kernel, inputs, pool, picks=picks, criterion=criterion, target=target,
                              inv_tausqd=inv_tausqd, sigsqd_mean=sigsqd_mean, **kwargs)
+        if raw_pool is not pool:
+            raw = np.asarray(raw_pool, dtype=np.float64)
+            res['x_normalised'], res['x'] = res['x'], (raw[:, np.newaxis] if raw.ndim == 1 else raw)[res['index']]
+        return res
+
+    def acquire(self, post=None, pool=None, clean=False, picks=8, criterion='ei', sense='max', incumbent='training', draws=None,
+                lazy=True, keep=None, betas=None, inputs=None, mtx=None, **kwargs):
+        """Which points should be measured next to find a better optimum?  Expected improvement (``criterion='ei'``) or
+        probability of improvement (``'pi'``) over every posterior draw, as a greedy batch of ``picks`` rows out of a
+        ``pool`` [S, m] of candidate inputs, on the device -- ``acquire.acquire`` with this model's ``mtx``, ``phis``,
+        ``kernel`` and training ``inputs``, which documents the keywords -- sense, incumbent, draws, lazy, keep -- and the
+        result.  ``post=None`` uses the fit's own ``betas`` (no sigma^2 is needed: the improvement is in the latent
+        function); what ``resample`` or ``resample_robust`` returned uses its ``betas`` (thin flagged chains' NaN rows away
+        with ``draws=``).  ``clean=True`` normalises ``pool`` with the model's ``minmax`` exactly as ``evaluate`` does, and
+        ``res.x`` are the chosen rows of ``pool`` as they were passed: measure there, then ``fitupdate``.  Nothing is drawn
+        at random: numpy's stream, ``setnos`` and everything ``fit`` set are left alone."""
+        if mtx is None:
+            mtx = getattr(self, 'mtx', None)
+        if mtx is None:
+            raise ValueError("acquire needs a fitted model: call fit first (there is no interaction matrix mtx)")
+        if inputs is None:
+            inputs = getattr(self, 'inputs', None)
+        if post is not None:
+            if betas is not None:
+                raise ValueError("acquire takes a resample's result OR betas=, not both")
+            try:
+                betas = post['betas']
+            except (KeyError, TypeError, IndexError):
+                raise ValueError("acquire needs what resample returned (betas per draw) as its first argument, or nothing: "
+                                 "the fit's own betas") from None
+            if betas is None:
+                raise ValueError("this resample kept no rows (keep=...): acquire needs betas per draw")
+        if betas is None:
+            betas = getattr(self, 'betas', None)
+        raw_pool = pool
+        if _str_to_bool(clean) and pool is not None:
+            if not hasattr(self, 'minmax'):
+                raise ValueError("acquire(clean=True) needs the model's minmax (set by clean / fit, or model.minmax = "
+                                 "[[min, max], ...])")
+            kwargs_to_clean = dict(_CLEAN_DEFAULTS)
+            kwargs_to_clean['minmax'] = self.minmax
+            if not np.isfinite(np.asarray(pool, dtype=np.float64)).all():
+                raise ValueError("pool rows must be finite")
+            pool = self.clean(pool, kwargs_from_other=kwargs_to_clean)
+        kwargs.setdefault('device', self._backend())
+        res = _acquire.acquire(betas, mtx, self.phis, self.kernel, inputs, pool, picks=picks, criterion=criterion, sense=sense,
+                               incumbent=incumbent, draws=draws, lazy=lazy, keep=keep, **kwargs)
         if raw_pool is not pool:
             raw = np.asarray(raw_pool, dtype=np.float64)
             res['x_normalised'], res['x'] = res['x'], (raw[:, np.newaxis] if raw.ndim == 1 else raw)[res['index']]

@@ -25,6 +25,7 @@ K_INFER = 14
 K_DESIGN = 15
 K_PREDICTIVE = 16
 K_ROBUST = 17
+K_ACQUIRE = 18
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
@@ -51,6 +52,8 @@ ROBUST_MAX_COLUMNS = 127                  # fokl_robust_*: P + 1; [1 | X | y] fi
 ROB_LAM_NORMAL, ROB_LAM_UNIFORM, ROB_BETA, ROB_SIG_NORMAL, ROB_SIG_UNIFORM, ROB_TAU_NORMAL, ROB_TAU_UNIFORM = 0, 1, 2, 3, 4, 5, 6
 DESIGN_INSTANCES = ('none', 'variance', 'ivr')                # fokl_design_report: the instance of the design kernels that ran
 DESIGN_MAX_COLUMNS = 768                  # fokl_design_select: a 16-row tile of basis values in LDS is 96 KiB
+ACQUIRE_INSTANCES = ('none', 'ei', 'pi')                      # fokl_acquire_report / fokl_acquire_select's criterion
+ACQUIRE_MAX_COLUMNS = 1280                # fokl_acquire_select: a 16-row tile of basis values in LDS is 160 KiB
 OPTIMIZE_INSTANCES = ('none', 'uniform', 'per_lane')          # fokl_optimize_report / fokl_system_optimize_report
 OPTIMIZE_TRIALS = 31                                          # trial points of one arc search (optimize.MAX_HALVINGS + 1)
 INFER_MAPPINGS = ('none', 'walker_per_lane')                  # fokl_infer_report: the lane mapping that ran
@@ -124,6 +127,9 @@ SIGNATURES = {
     'fokl_design_select': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                    c_vp]),
     'fokl_design_report': (c_int, [c_vp, c_vp]),
+    'fokl_acquire_select': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
+                                    c_vp, c_vp, c_vp]),
+    'fokl_acquire_report': (c_int, [c_vp, c_vp]),
     'fokl_read_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_write_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_timing_enable': (c_int, [c_vp, c_int]),
@@ -2501,6 +2507,52 @@ class DeviceContext:
         v = [int(x) for x in out]
         return dict(instance=DESIGN_INSTANCES[v[0]], grid=v[1], step_grid=v[2], row_tiles=v[3], lds_bytes=v[4], picks=v[5],
                     refreshes=v[6], launches=v[7], kernel_us=v[8], quadform_us=v[9], step_us=v[10], pivot_us=v[11])
+
+    def acquire_select(self, slots, betas, incumbent, picks=1, criterion='ei', lazy=True, grid_cap=0, trace_pick=-1):
+        """fokl_acquire_select over the uploaded rows (the pool): greedy selection of ``picks`` rows by expected improvement
+        ('ei') or probability of improvement ('pi') over the rows of ``betas`` [E, nc] given the incumbent [E] of every draw
+        (finite or -inf), sense 'max' -> dict(index [picks] int64, gain [picks], incumbent_after [E], tiles_evaluated [picks]
+        int64 and, with ``trace_pick=k``, trace_g [S] -- every row's gain as it stood when pick k was taken -- and, under
+        ``lazy``, trace_eval [tiles] uint8; else None).  acquire.select_host is its statement: on integer data every field is
+        its bits.  A pick that finds no row (every gain NaN) is index -1, gain -inf.  ``report['launches']`` is 2 per pick
+        without ``lazy``, 2 + 4 (picks - 1) with it; nothing waits on the host between them.  ``grid_cap``: 0 the device's
+        grids; a test hook.  Two calls with the same arguments return the same bits."""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        nc = s.shape[0]
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        if betas.ndim != 2 or betas.shape[1] != nc:
+            raise ValueError("betas columns must match the slot list")
+        E = betas.shape[0]
+        incumbent = np.ascontiguousarray(np.reshape(incumbent, -1), dtype=np.float64)
+        if incumbent.shape[0] != E:
+            raise ValueError("acquire_select: one incumbent per row of betas")
+        if criterion not in ACQUIRE_INSTANCES[1:]:
+            raise ValueError(f"acquire_select: criterion must be one of {ACQUIRE_INSTANCES[1:]}")
+        picks, trace_pick = int(picks), int(trace_pick)
+        rows = max(picks, 0)
+        index, tiles = np.empty(rows, dtype=np.int64), np.empty(rows, dtype=np.int64)
+        gain, after = np.empty(rows), np.empty(E)
+        trace_g = np.empty(self.n, dtype=np.float64) if trace_pick >= 0 else None
+        trace_eval = np.empty(-(-self.n // 16), dtype=np.uint8) if trace_pick >= 0 and lazy else None
+        self._ck(self._lib.fokl_acquire_select(self._h, _ptr(s), nc, _ptr(betas), E, _ptr(incumbent),
+                                               ACQUIRE_INSTANCES.index(criterion), int(bool(lazy)), picks, int(grid_cap),
+                                               trace_pick, _ptr(index), _ptr(gain), _ptr(after), _ptr(tiles), _ptr(trace_g),
+                                               _ptr(trace_eval)))
+        return dict(index=index, gain=gain, incumbent_after=after, tiles_evaluated=tiles, trace_g=trace_g, trace_eval=trace_eval)
+
+    def acquire_report(self):
+        """What the last ``acquire_select`` on this context ran (fokl_acquire_report): ``instance`` ('ei', 'pi'), ``lazy``,
+        the ``grid`` of one-wavefront workgroups of the pass kernel over ``row_tiles`` 16-row tiles and its ``lds_bytes``, the
+        ``bound_grid``, ``dt`` (16-draw tiles per block of the product), the ``picks``, the ``launches`` in all,
+        ``tiles_evaluated`` over all picks, ``tiles_evaluated_max_lazy`` (by the most expensive pick after the first under
+        ``lazy``), ``kernel_us`` of the whole queue; ``pass_us``, ``bound_us`` and ``pivot_us`` are measured while the
+        context's timing is enabled (else 0).  'none' and zeros after a refused call."""
+        out = np.zeros(15, dtype=np.int64)
+        self._ck(self._lib.fokl_acquire_report(self._h, _ptr(out)))
+        v = [int(x) for x in out]
+        return dict(instance=ACQUIRE_INSTANCES[v[0]], lazy=bool(v[1]), grid=v[2], bound_grid=v[3], row_tiles=v[4], lds_bytes=v[5],
+                    dt=v[6], picks=v[7], launches=v[8], tiles_evaluated=v[9], tiles_evaluated_max_lazy=v[10], kernel_us=v[11],
+                    pass_us=v[12], bound_us=v[13], pivot_us=v[14])
 
     def infer_inputs(self, mtx_u, betas, h, table, lo, hi, prior_mean, prior_prec, y, known_prod, starts, burnin, draws,
                      thin, jump_every, seed, draw_ids=None, rows=True, term_cap=0):

@@ -243,6 +243,14 @@ extern "C" int fokl_design_select(fokl_ctx *, const int32_t *, int, const double
 }
 extern "C" int fokl_design_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor does the batch acquisition over a pool (fokl_acquire_device.inc); its statement is acquire.select_host.
+extern "C" int fokl_acquire_select(fokl_ctx *, const int32_t *, int, const double *, int, const double *, int, int, int, int, int,
+                                   int64_t *, double *, double *, int64_t *, double *, unsigned char *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_acquire_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // Nor does the ensemble sampler over unknown inputs (fokl_infer_device.inc); its statement is infer.sample_host, and its
 // random numbers (fokl_infer_rng) are host code and present here.
 extern "C" int fokl_infer_inputs(fokl_ctx *, int, int, const int32_t *, int, const double *, const double *, const uint32_t *,

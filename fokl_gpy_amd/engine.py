@@ -259,6 +259,12 @@ class HipBackend:
     def design_report(self):
         return self.ctx.design_report()
 
+    def acquire_select(self, slots, betas, incumbent, picks=1, criterion='ei', lazy=True, grid_cap=0, trace_pick=-1):
+        return self.ctx.acquire_select(slots, betas, incumbent, picks, criterion, lazy, grid_cap, trace_pick)
+
+    def acquire_report(self):
+        return self.ctx.acquire_report()
+
 
 class SlotPool:
     """Free list of device column slots (slot 0 = ones, slot 1 = y are never handed out)."""

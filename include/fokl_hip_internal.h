@@ -38,6 +38,9 @@
  *   fokl_design_select / fokl_design_report
  *                              greedy D- / I-optimal selection from a candidate pool (fokl_gpy_amd/design.py), and what
  *                              its last call ran
+ *   fokl_acquire_select / fokl_acquire_report
+ *                              expected improvement and probability of improvement over a candidate pool, greedy batch
+ *                              selection with lazy evaluation (fokl_gpy_amd/acquire.py), and what its last call ran
  *   fokl_infer_inputs / fokl_infer_report / fokl_infer_rng
  *                              unknown inputs inferred from observed outputs: one affine-invariant ensemble of 64 walkers
  *                              per posterior draw (fokl_gpy_amd/infer.py), what its last launches ran, and its
@@ -1239,6 +1242,66 @@ int fokl_design_select(fokl_ctx *ctx, const int32_t *slots, int nc, const double
  *   out[10], out[11]  ... of the step and of the pivot launches (measured only while fokl_timing_enable is on, else 0)
  */
 int fokl_design_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Which pool rows to measure next to find a better optimum: EI and PI over the draws, greedy batch          */
+/* (csrc/fokl_acquire_device.inc; fokl_gpy_amd/acquire.py)                                                   */
+/* ------------------------------------------------------------------------------------------------------ */
+
+/* `criterion` of fokl_acquire_select and out[0] of fokl_acquire_report: the instance of the kernels that ran */
+enum {
+    FOKL_ACQUIRE_NONE = 0,     /* no call yet, or the last one was refused or failed */
+    FOKL_ACQUIRE_EI = 1,       /* expected improvement: (sum_d max(f_sd - b_d, 0)) / E; a pick sets b_d = max(b_d, f_s*d) */
+    FOKL_ACQUIRE_PI = 2        /* probability of improvement: (sum_d [f_sd > b_d]) / E; a pick sets b_d = +inf where f_s*d > b_d */
+};
+#define FOKL_ACQUIRE_REPORT_LEN 15
+
+/*
+ * Greedy selection of `picks` rows of the uploaded dataset (the pool; X_s: the columns `slots`, nc of them, ones first, as
+ * for fokl_predict) by expected improvement or probability of improvement over the posterior draws betas [draws, nc]
+ * (host, row-major), given the incumbent b [draws] of every draw (finite or -inf).  f_sd = X_s . beta_d is the fitted
+ * function, with no noise term; the gain of a row and what a pick does to b are stated at the enum above.  The sense is
+ * 'max': a caller that minimises passes -betas and -b (negation is exact).  A pick takes the largest gain among the rows
+ * not yet picked (compared with >: NaN never wins; on equal values the lowest row); a row is taken once.  The statement in
+ * numpy is acquire.select_host.
+ *   lazy != 0: every pick after the first (1) finds the row with the largest gain left from earlier picks
+ *   (acquire_bound_kernel), (2) evaluates its 16-row tile fresh, tau = the largest fresh gain among that tile's rows not yet
+ *   picked (acquire_pivot_kernel, candidate mode), (3) evaluates only the tiles in which some row not yet picked has an old
+ *   gain that is not strictly below tau (acquire_pass_kernel), (4) takes the arg-max (acquire_pivot_kernel, pick mode).
+ *   Gains only fall as b rises, exactly so in floating point, so the index and the gain BITS are those of lazy = 0, which
+ *   evaluates every tile for every pick (pass, pivot).
+ *   index_out     [picks] int64   the rows in pick order (-1: nothing could be taken: every gain NaN)
+ *   gain_out      [picks]         the gain of each pick when it was taken (-inf with index -1)
+ *   incumbent_out [draws]         b after the last pick ('pi': +inf where the batch improves on the draw)
+ *   tiles_out     [picks] int64   16-row tiles evaluated for each pick (lazy = 0: all of them)
+ *   trace_pick = k in 0 .. picks - 1 (-1: off): trace_g_out [rows] = the gain of every row as it stood when pick k was taken
+ *   (under lazy a skipped tile's rows hold their old gain) and, under lazy, trace_eval_out [tiles] = 1 where the tile was
+ *   evaluated for pick k, else 0.  acquire_pass_kernel's own body writes both.
+ * Launches: 2 per pick with lazy = 0; 2 for the first pick and 4 for every later one with lazy != 0.  All are queued on
+ * the context's stream and synchronised once; nothing is accumulated with atomics and the best of two rows does not
+ * depend on the order they are met in, so the same arguments give the same bits whatever the grid.  grid_cap > 0 caps the
+ * grids (a test hook; 0: the device's).
+ * Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched; the dataset, its slots and pending launches
+ * are left alone): nc < 1, draws < 1, picks < 1, picks above the rows, a coefficient that is not finite, an incumbent that
+ * is NaN or +inf, columns whose 16-row tile exceeds 160 KiB of LDS (more than 1280), coefficients and per-row values
+ * beyond the device's free memory (the environment's FOKL_ACQUIRE_FREE_BYTES, if set, caps what counts as free).
+ * Kernel time: FOKL_K_ACQUIRE.  Blocking; everything uploaded is freed before it returns.
+ */
+int fokl_acquire_select(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, int draws, const double *incumbent,
+                        int criterion, int lazy, int picks, int grid_cap, int trace_pick, int64_t *index_out, double *gain_out,
+                        double *incumbent_out, int64_t *tiles_out, double *trace_g_out, unsigned char *trace_eval_out);
+
+/*
+ * The last fokl_acquire_select call on `ctx`, out [FOKL_ACQUIRE_REPORT_LEN] (host):
+ *   out[0]  the instance (above); zeros after a call that returned an error     out[1]  lazy (1) or not (0)
+ *   out[2]  the grid of acquire_pass_kernel (workgroups = wavefronts)           out[3]  the grid of acquire_bound_kernel
+ *   out[4]  16-row tiles     out[5]  dynamic LDS bytes of a tile     out[6]  16-draw tiles per block of the product (DT)
+ *   out[7]  picks     out[8]  launches in all     out[9]  tiles evaluated in total
+ *   out[10] tiles evaluated by the most expensive pick after the first under lazy (0 without lazy or with one pick)
+ *   out[11] kernel microseconds of the whole queue
+ *   out[12], out[13], out[14]  ... of the pass, bound and pivot launches (measured only while fokl_timing_enable is on, else 0)
+ */
+int fokl_acquire_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* Unknown inputs from observed outputs (csrc/fokl_infer_device.inc; fokl_gpy_amd/infer.py)                  */
