@@ -1631,6 +1631,13 @@ class FoKL:
             res['x_normalised'], res['x'] = res['x'], (raw[:, np.newaxis] if raw.ndim == 1 else raw)[res['index']]
         return res
 
+    def acquire_system(self, others, xvars, yvars, objective, pool, **kwargs):
+        """``acquire`` under limits on other fitted models' outputs: ``acquire.acquire_system([self] + others, ...)`` on
+        this model's device, which documents every argument and the result.  This model is ``models[0]``; ``xvars`` and
+        ``yvars`` name the inputs and the output of every model in that order, ``pool`` is in TRUE scale."""
+        kwargs.setdefault('device', self._backend())
+        return _acquire.acquire_system([self] + list(others), xvars, yvars, objective, pool, **kwargs)
+
     def infer_inputs(self, post=None, unknown=None, known=None, data=None, clean=False, betas=None, sigsqd=None, mtx=None,
                      **kwargs):
         """Which inputs produced these observed outputs, and how sure can one be?  One ensemble sampler of 64 walkers over

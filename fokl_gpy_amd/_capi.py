@@ -26,6 +26,7 @@ K_DESIGN = 15
 K_PREDICTIVE = 16
 K_ROBUST = 17
 K_ACQUIRE = 18
+K_ACQUIRE_SYSTEM = 19
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
@@ -54,7 +55,9 @@ DESIGN_INSTANCES = ('none', 'variance', 'ivr')                # fokl_design_repo
 DESIGN_MAX_COLUMNS = 768                  # fokl_design_select: a 16-row tile of basis values in LDS is 96 KiB
 ACQUIRE_INSTANCES = ('none', 'ei', 'pi')                      # fokl_acquire_report / fokl_acquire_select's criterion
 ACQUIRE_MAX_COLUMNS = 1280                # fokl_acquire_select: a 16-row tile of basis values in LDS is 160 KiB
-OPTIMIZE_INSTANCES = ('none', 'uniform', 'per_lane')          # fokl_optimize_report / fokl_system_optimize_report
+ACQUIRE_SYSTEM_INSTANCES = ('none', 'ei', 'pi', 'incumbent')  # fokl_acquire_system_report: what the last call ran
+ACQUIRE_SYSTEM_MAX_MODELS = 8             # fokl_acquire_system_*: the objective and up to 7 constraint models
+OPTIMIZE_INSTANCES = ('none', 'uniform', 'per_lane')         # fokl_optimize_report / fokl_system_optimize_report
 OPTIMIZE_TRIALS = 31                                          # trial points of one arc search (optimize.MAX_HALVINGS + 1)
 INFER_MAPPINGS = ('none', 'walker_per_lane')                  # fokl_infer_report: the lane mapping that ran
 INFER_WALKERS = 64                        # fokl_infer_inputs: one ensemble is one wavefront
@@ -130,6 +133,10 @@ SIGNATURES = {
     'fokl_acquire_select': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
                                     c_vp, c_vp, c_vp]),
     'fokl_acquire_report': (c_int, [c_vp, c_vp]),
+    'fokl_acquire_system_select': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                                           c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'fokl_acquire_system_incumbent': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
+    'fokl_acquire_system_report': (c_int, [c_vp, c_vp]),
     'fokl_read_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_write_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_timing_enable': (c_int, [c_vp, c_int]),
@@ -2553,6 +2560,78 @@ class DeviceContext:
         return dict(instance=ACQUIRE_INSTANCES[v[0]], lazy=bool(v[1]), grid=v[2], bound_grid=v[3], row_tiles=v[4], lds_bytes=v[5],
                     dt=v[6], picks=v[7], launches=v[8], tiles_evaluated=v[9], tiles_evaluated_max_lazy=v[10], kernel_us=v[11],
                     pass_us=v[12], bound_us=v[13], pivot_us=v[14])
+
+    def _acquire_system_arguments(self, who, slots, betas, lo, hi):
+        """The models of ``acquire_system_select`` / ``acquire_system_incumbent`` as the library takes them: slots and betas
+        one model behind the other, the widths, the limits."""
+        slots = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in slots]
+        betas = [np.ascontiguousarray(b, dtype=np.float64) for b in betas]
+        if len(slots) != len(betas) or len(slots) < 1:
+            raise ValueError(f"{who}: one slot list and one betas per model")
+        E = betas[0].shape[0] if betas[0].ndim == 2 else -1
+        for s, b in zip(slots, betas):
+            if b.ndim != 2 or b.shape[1] != s.shape[0] or b.shape[0] != E:
+                raise ValueError(f"{who}: every model's betas must be [E, its slots], with one E")
+        lo = np.ascontiguousarray(np.reshape(lo, -1), dtype=np.float64)
+        hi = np.ascontiguousarray(np.reshape(hi, -1), dtype=np.float64)
+        if lo.shape[0] != len(slots) - 1 or hi.shape[0] != len(slots) - 1:
+            raise ValueError(f"{who}: one (lo, hi) per constraint model, i.e. per model after the first")
+        widths = np.array([s.shape[0] for s in slots], dtype=np.int32)
+        return (np.ascontiguousarray(np.concatenate(slots)), widths, np.ascontiguousarray(np.concatenate([b.ravel() for b in betas])),
+                E, lo, hi)
+
+    def acquire_system_select(self, slots, betas, incumbent, lo, hi, picks=1, criterion='ei', lazy=True, grid_cap=0,
+                              trace_pick=-1):
+        """fokl_acquire_system_select over the uploaded rows (the pool): ``acquire_select`` under limits on other models'
+        outputs.  ``slots`` = [objective's slots, constraint model 1's, ...], ``betas`` = [B0 [E, nc_0], B1 [E, nc_1], ...],
+        ``lo`` / ``hi`` [K] the limits of the constraint models (infinite: none) -> ``acquire_select``'s dict and feasible
+        [picks] int64, the draws in which each pick is feasible.  acquire.select_system_host is its statement: on integer
+        data every field is its bits; with infinite limits every field is ``acquire_select``'s.  Launches as for
+        ``acquire_select``."""
+        s, widths, flat, E, lo, hi = self._acquire_system_arguments('acquire_system_select', slots, betas, lo, hi)
+        incumbent = np.ascontiguousarray(np.reshape(incumbent, -1), dtype=np.float64)
+        if incumbent.shape[0] != E:
+            raise ValueError("acquire_system_select: one incumbent per row of betas")
+        if criterion not in ACQUIRE_INSTANCES[1:]:
+            raise ValueError(f"acquire_system_select: criterion must be one of {ACQUIRE_INSTANCES[1:]}")
+        picks, trace_pick = int(picks), int(trace_pick)
+        rows = max(picks, 0)
+        index, tiles, feasible = (np.empty(rows, dtype=np.int64) for _ in range(3))
+        gain, after = np.empty(rows), np.empty(E)
+        trace_g = np.empty(self.n, dtype=np.float64) if trace_pick >= 0 else None
+        trace_eval = np.empty(-(-self.n // 16), dtype=np.uint8) if trace_pick >= 0 and lazy else None
+        self._ck(self._lib.fokl_acquire_system_select(self._h, _ptr(s), _ptr(widths), len(widths) - 1, _ptr(flat), E,
+                                                      _ptr(incumbent), _ptr(lo), _ptr(hi), ACQUIRE_INSTANCES.index(criterion),
+                                                      int(bool(lazy)), picks, int(grid_cap), trace_pick, _ptr(index), _ptr(gain),
+                                                      _ptr(after), _ptr(tiles), _ptr(feasible), _ptr(trace_g), _ptr(trace_eval)))
+        return dict(index=index, gain=gain, incumbent_after=after, tiles_evaluated=tiles, feasible=feasible, trace_g=trace_g,
+                    trace_eval=trace_eval)
+
+    def acquire_system_incumbent(self, slots, betas, lo, hi, grid_cap=0):
+        """fokl_acquire_system_incumbent over the uploaded rows (the measured points), arguments as for
+        ``acquire_system_select`` -> (best [E]: per draw the largest objective over the rows feasible in that draw, -inf with
+        none, NaN where a feasible row's value is not finite; count [E] int64: the feasible rows).
+        acquire.incumbent_system_host is its statement.  The same arguments give the same bits whatever ``grid_cap``."""
+        s, widths, flat, E, lo, hi = self._acquire_system_arguments('acquire_system_incumbent', slots, betas, lo, hi)
+        best, count = np.empty(E), np.empty(E, dtype=np.int64)
+        self._ck(self._lib.fokl_acquire_system_incumbent(self._h, _ptr(s), _ptr(widths), len(widths) - 1, _ptr(flat), E, _ptr(lo),
+                                                         _ptr(hi), int(grid_cap), _ptr(best), _ptr(count)))
+        return best, count
+
+    def acquire_system_report(self):
+        """What the last ``acquire_system_select`` or ``acquire_system_incumbent`` on this context ran
+        (fokl_acquire_system_report): ``instance`` ('ei', 'pi', 'incumbent'), ``lazy``, ``constraints`` (K), the ``grid`` of
+        one-wavefront workgroups over ``row_tiles`` 16-row tiles and its ``lds_bytes``, the ``bound_grid`` (of the merge
+        after 'incumbent'), ``draw_group`` (draws per block of the product), ``picks``, ``launches``, ``tiles_evaluated``,
+        ``tiles_evaluated_max_lazy``, ``kernel_us`` of the whole queue; ``pass_us``, ``bound_us`` and ``pivot_us`` of a
+        selection are measured while the context's timing is enabled (else 0), after 'incumbent' the first two hold its two
+        kernels.  'none' and zeros after a refused call."""
+        out = np.zeros(16, dtype=np.int64)
+        self._ck(self._lib.fokl_acquire_system_report(self._h, _ptr(out)))
+        v = [int(x) for x in out]
+        return dict(instance=ACQUIRE_SYSTEM_INSTANCES[v[0]], lazy=bool(v[1]), constraints=v[2], grid=v[3], bound_grid=v[4],
+                    row_tiles=v[5], lds_bytes=v[6], draw_group=v[7], picks=v[8], launches=v[9], tiles_evaluated=v[10],
+                    tiles_evaluated_max_lazy=v[11], kernel_us=v[12], pass_us=v[13], bound_us=v[14], pivot_us=v[15])
 
     def infer_inputs(self, mtx_u, betas, h, table, lo, hi, prior_mean, prior_prec, y, known_prod, starts, burnin, draws,
                      thin, jump_every, seed, draw_ids=None, rows=True, term_cap=0):

@@ -251,6 +251,20 @@ extern "C" int fokl_acquire_select(fokl_ctx *, const int32_t *, int, const doubl
 }
 extern "C" int fokl_acquire_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// ... nor under limits on other models' outputs (fokl_acquire_system_device.inc); acquire.select_system_host.
+extern "C" int fokl_acquire_system_select(fokl_ctx *, const int32_t *, const int32_t *, int, const double *, int, const double *,
+                                          const double *, const double *, int, int, int, int, int, int64_t *, double *, double *,
+                                          int64_t *, int64_t *, double *, unsigned char *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_acquire_system_incumbent(fokl_ctx *, const int32_t *, const int32_t *, int, const double *, int, const double *,
+                                             const double *, int, double *, int64_t *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_acquire_system_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // Nor does the ensemble sampler over unknown inputs (fokl_infer_device.inc); its statement is infer.sample_host, and its
 // random numbers (fokl_infer_rng) are host code and present here.
 extern "C" int fokl_infer_inputs(fokl_ctx *, int, int, const int32_t *, int, const double *, const double *, const uint32_t *,

@@ -265,6 +265,16 @@ class HipBackend:
     def acquire_report(self):
         return self.ctx.acquire_report()
 
+    def acquire_system_select(self, slots, betas, incumbent, lo, hi, picks=1, criterion='ei', lazy=True, grid_cap=0,
+                              trace_pick=-1):
+        return self.ctx.acquire_system_select(slots, betas, incumbent, lo, hi, picks, criterion, lazy, grid_cap, trace_pick)
+
+    def acquire_system_incumbent(self, slots, betas, lo, hi, grid_cap=0):
+        return self.ctx.acquire_system_incumbent(slots, betas, lo, hi, grid_cap)
+
+    def acquire_system_report(self):
+        return self.ctx.acquire_system_report()
+
 
 class SlotPool:
     """Free list of device column slots (slot 0 = ones, slot 1 = y are never handed out)."""

@@ -59,7 +59,8 @@ extern "C" {
 #define FOKL_K_PREDICTIVE 16    /* predictive(): PIT and quantiles of the predictive distribution per row (fokl_hip_internal.h: fokl_predictive_rows) */
 #define FOKL_K_ROBUST  17       /* resample_robust(): Gibbs chains under Student-t noise, a weighted pass per iteration (fokl_hip_internal.h: fokl_robust_chains) */
 #define FOKL_K_ACQUIRE 18       /* acquire(): EI / PI over a candidate pool, greedy batch (fokl_hip_internal.h: fokl_acquire_select) */
-#define FOKL_K_COUNT   19
+#define FOKL_K_ACQUIRE_SYSTEM 19 /* acquire_system(): EI / PI under limits on other models' outputs (fokl_hip_internal.h: fokl_acquire_system_select) */
+#define FOKL_K_COUNT   20
 
 typedef struct fokl_ctx fokl_ctx;
 

@@ -41,6 +41,9 @@
  *   fokl_acquire_select / fokl_acquire_report
  *                              expected improvement and probability of improvement over a candidate pool, greedy batch
  *                              selection with lazy evaluation (fokl_gpy_amd/acquire.py), and what its last call ran
+ *   fokl_acquire_system_select / fokl_acquire_system_incumbent / fokl_acquire_system_report
+ *                              the same selection under limits on other models' outputs, feasibility per (row, draw); the
+ *                              best objective over the feasible measured rows per draw; what the last of either ran
  *   fokl_infer_inputs / fokl_infer_report / fokl_infer_rng
  *                              unknown inputs inferred from observed outputs: one affine-invariant ensemble of 64 walkers
  *                              per posterior draw (fokl_gpy_amd/infer.py), what its last launches ran, and its
@@ -1302,6 +1305,66 @@ int fokl_acquire_select(fokl_ctx *ctx, const int32_t *slots, int nc, const doubl
  *   out[12], out[13], out[14]  ... of the pass, bound and pivot launches (measured only while fokl_timing_enable is on, else 0)
  */
 int fokl_acquire_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* The same selection under limits on other models' outputs (csrc/fokl_acquire_system_device.inc;            */
+/* fokl_gpy_amd/acquire.py: acquire_system)                                                                  */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_ACQUIRE_SYSTEM_MAX_MODELS 8       /* the objective and up to 7 constraint models */
+#define FOKL_ACQUIRE_SYSTEM_INCUMBENT 3        /* out[0] of the report after the incumbent call (1, 2: the criterion of a selection) */
+#define FOKL_ACQUIRE_SYSTEM_REPORT_LEN 16
+
+/*
+ * The greedy selection above with feasibility per (row, draw).  Model 0 is the objective, models 1 .. n_constraints
+ * (1 to 7) are constraint models; draw d is row d of every model's coefficients.
+ *   widths [n_constraints + 1]   the columns nc_k of every model (>= 1)
+ *   slots  [sum nc_k]            the models' column slots one model behind the other (ones first in each, as for fokl_predict)
+ *   betas                        the models' coefficients one model behind the other, [draws, nc_k] row-major each (host)
+ *   lo, hi [n_constraints]       the limits of constraint model k + 1; either may be infinite, neither NaN
+ * With f_sd = X0_s . beta0_d and g_ksd = Xk_s . betak_d, a draw is feasible at a row when every k has lo <= g_ksd <= hi (a
+ * NaN g is infeasible).  The gain of a row is the sum over its FEASIBLE draws of fokl_acquire_select's terms, over `draws`;
+ * an infeasible draw contributes exactly 0.0 whatever f is, and a pick changes b in its feasible draws only.  Everything
+ * else -- the arg-max, ties, NaN, lazy, the traces, the launches per pick, grid_cap -- is fokl_acquire_select's, and with
+ * infinite limits every output is its output, bit for bit.  The statement in numpy is acquire.select_system_host.
+ *   feasible_out [picks] int64   the draws in which each picked row is feasible (0 with index -1)
+ * A 16-row tile holds every model's basis values, each model padded to a multiple of 4 columns on its own.
+ * Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched): what fokl_acquire_select refuses,
+ * n_constraints outside 1 .. 7, a width below 1, a NaN limit, padded columns of all models beyond 1280 (160 KiB of LDS),
+ * the memory rule with FOKL_ACQUIRE_FREE_BYTES.  Kernel time: FOKL_K_ACQUIRE_SYSTEM.  Blocking; everything uploaded is freed
+ * before it returns.
+ */
+int fokl_acquire_system_select(fokl_ctx *ctx, const int32_t *slots, const int32_t *widths, int n_constraints, const double *betas,
+                               int draws, const double *incumbent, const double *lo, const double *hi, int criterion, int lazy,
+                               int picks, int grid_cap, int trace_pick, int64_t *index_out, double *gain_out,
+                               double *incumbent_out, int64_t *tiles_out, int64_t *feasible_out, double *trace_g_out,
+                               unsigned char *trace_eval_out);
+
+/*
+ * Over the uploaded rows (the measured points), per draw: best_out [draws] = the largest f over the rows feasible in that
+ * draw, -inf if there is none, NaN if a feasible row's f is not finite; count_out [draws] int64 = the feasible rows.
+ * Arguments and refusals as above.  One wavefront per 16-row tile keeps its workgroup's result per draw, a second kernel
+ * merges the workgroups in index order: no atomics, and the same arguments give the same bits whatever the grid (grid_cap
+ * > 0 caps it; a test hook).  The statement in numpy is acquire.incumbent_system_host.  Kernel time:
+ * FOKL_K_ACQUIRE_SYSTEM.  Blocking.
+ */
+int fokl_acquire_system_incumbent(fokl_ctx *ctx, const int32_t *slots, const int32_t *widths, int n_constraints,
+                                  const double *betas, int draws, const double *lo, const double *hi, int grid_cap,
+                                  double *best_out, int64_t *count_out);
+
+/*
+ * The last fokl_acquire_system_select or fokl_acquire_system_incumbent call on `ctx`, out [FOKL_ACQUIRE_SYSTEM_REPORT_LEN]:
+ *   out[0]  the instance: FOKL_ACQUIRE_EI / FOKL_ACQUIRE_PI of a selection, FOKL_ACQUIRE_SYSTEM_INCUMBENT; zeros after a
+ *           call that returned an error            out[1]  lazy (1) or not (0)       out[2]  constraint models (K)
+ *   out[3]  the grid of the pass kernel (of the incumbent kernel)     out[4]  the grid of acquire_bound_kernel (of the merge)
+ *   out[5]  16-row tiles     out[6]  dynamic LDS bytes of a tile     out[7]  draws per block of the product: the draw group (64)
+ *   out[8]  picks     out[9]  launches in all     out[10] tiles evaluated in total
+ *   out[11] tiles evaluated by the most expensive pick after the first under lazy (0 without lazy or with one pick)
+ *   out[12] kernel microseconds of the whole queue
+ *   out[13], out[14], out[15]  ... of the pass, bound and pivot launches (a selection: measured only while
+ *           fokl_timing_enable is on, else 0; the incumbent call: its two kernels in out[13] and out[14])
+ */
+int fokl_acquire_system_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* Unknown inputs from observed outputs (csrc/fokl_infer_device.inc; fokl_gpy_amd/infer.py)                  */
