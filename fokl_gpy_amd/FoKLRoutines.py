@@ -38,6 +38,7 @@ from . import score as _score
 from . import predictive as _predictive
 from . import design as _design
 from . import acquire as _acquire
+from . import pooloptimum as _pooloptimum
 from . import infer as _infer
 from . import resample as _resample
 from . import robust as _robust
@@ -1637,6 +1638,52 @@ class FoKL:
         ``yvars`` name the inputs and the output of every model in that order, ``pool`` is in TRUE scale."""
         kwargs.setdefault('device', self._backend())
         return _acquire.acquire_system([self] + list(others), xvars, yvars, objective, pool, **kwargs)
+
+    def optimize_pool(self, post=None, pool=None, clean=False, betas=None, mtx=None, **kwargs):
+        """For every posterior draw, which row of ``pool`` [S, m] is that draw's best?  The share of the draws in which a
+        row is the best one (with its entropy), the best ``top`` rows per draw and, with ``picks=q``, a Thompson batch of q
+        rows, on the device -- ``pooloptimum.optimize_pool`` with this model's ``mtx``, ``phis`` and ``kernel``, which
+        documents the keywords -- sense, top, picks, seed, exclude, draws -- and the result.  ``post=None`` uses the fit's
+        own ``betas``; what ``resample`` or ``resample_robust`` returned uses its ``betas`` (thin flagged chains' NaN rows
+        away with ``draws=``).  ``clean=True`` normalises ``pool`` with the model's ``minmax`` exactly as ``evaluate`` does;
+        ``res.x_best`` (and the batch's ``res.x``) are then the rows of ``pool`` as they were passed, ``res.x_normalised``
+        the normalised ``x_best`` (and ``res.x_batch_normalised`` the normalised ``x``).  The batch draws its order of the draws from a generator of its own (``seed``): numpy's stream,
+        ``setnos`` and everything ``fit`` set are left alone."""
+        if mtx is None:
+            mtx = getattr(self, 'mtx', None)
+        if mtx is None:
+            raise ValueError("optimize_pool needs a fitted model: call fit first (there is no interaction matrix mtx)")
+        if post is not None:
+            if betas is not None:
+                raise ValueError("optimize_pool takes a resample's result OR betas=, not both")
+            try:
+                betas = post['betas']
+            except (KeyError, TypeError, IndexError):
+                raise ValueError("optimize_pool needs what resample returned (betas per draw) as its first argument, or "
+                                 "nothing: the fit's own betas") from None
+            if betas is None:
+                raise ValueError("this resample kept no rows (keep=...): optimize_pool needs betas per draw")
+        if betas is None:
+            betas = getattr(self, 'betas', None)
+        raw_pool = pool
+        if _str_to_bool(clean) and pool is not None:
+            if not hasattr(self, 'minmax'):
+                raise ValueError("optimize_pool(clean=True) needs the model's minmax (set by clean / fit, or model.minmax = "
+                                 "[[min, max], ...])")
+            kwargs_to_clean = dict(_CLEAN_DEFAULTS)
+            kwargs_to_clean['minmax'] = self.minmax
+            if not np.isfinite(np.asarray(pool, dtype=np.float64)).all():
+                raise ValueError("pool rows must be finite")
+            pool = self.clean(pool, kwargs_from_other=kwargs_to_clean)
+        kwargs.setdefault('device', self._backend())
+        res = _pooloptimum.optimize_pool(betas, mtx, self.phis, self.kernel, pool, **kwargs)
+        if raw_pool is not pool:
+            raw = np.asarray(raw_pool, dtype=np.float64)
+            raw = raw[:, np.newaxis] if raw.ndim == 1 else raw
+            res['x_normalised'], res['x_best'] = res['x_best'], _pooloptimum.rows_of(raw, res['best'])
+            if 'x' in res:
+                res['x_batch_normalised'], res['x'] = res['x'], raw[res['index']]
+        return res
 
     def infer_inputs(self, post=None, unknown=None, known=None, data=None, clean=False, betas=None, sigsqd=None, mtx=None,
                      **kwargs):

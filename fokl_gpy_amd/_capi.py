@@ -27,6 +27,7 @@ K_PREDICTIVE = 16
 K_ROBUST = 17
 K_ACQUIRE = 18
 K_ACQUIRE_SYSTEM = 19
+K_DRAWBEST = 20
 INTEGRATE_MAX_STATES = 4
 RESID_TERMS_MAX_FACTORS = 32
 RESID_TERMS_MAX_ORDER = 8
@@ -57,6 +58,9 @@ ACQUIRE_INSTANCES = ('none', 'ei', 'pi')                      # fokl_acquire_rep
 ACQUIRE_MAX_COLUMNS = 1280                # fokl_acquire_select: a 16-row tile of basis values in LDS is 160 KiB
 ACQUIRE_SYSTEM_INSTANCES = ('none', 'ei', 'pi', 'incumbent')  # fokl_acquire_system_report: what the last call ran
 ACQUIRE_SYSTEM_MAX_MODELS = 8             # fokl_acquire_system_*: the objective and up to 7 constraint models
+DRAWBEST_INSTANCES = ('none', 'ran')                          # fokl_drawbest_report: whether the last call ran
+DRAWBEST_MAX_RANKS = 64                  # fokl_drawbest_rows: one pass over the pool per rank
+DRAWBEST_MAX_COLUMNS = 1280               # ... and a 16-row tile of basis values in LDS is 160 KiB
 OPTIMIZE_INSTANCES = ('none', 'uniform', 'per_lane')         # fokl_optimize_report / fokl_system_optimize_report
 OPTIMIZE_TRIALS = 31                                          # trial points of one arc search (optimize.MAX_HALVINGS + 1)
 INFER_MAPPINGS = ('none', 'walker_per_lane')                  # fokl_infer_report: the lane mapping that ran
@@ -137,6 +141,8 @@ SIGNATURES = {
                                            c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'fokl_acquire_system_incumbent': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
     'fokl_acquire_system_report': (c_int, [c_vp, c_vp]),
+    'fokl_drawbest_rows': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp]),
+    'fokl_drawbest_report': (c_int, [c_vp, c_vp]),
     'fokl_read_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_write_slot': (c_int, [c_vp, c_int, c_i64, c_i64, c_vp]),
     'fokl_timing_enable': (c_int, [c_vp, c_int]),
@@ -2632,6 +2638,46 @@ class DeviceContext:
         return dict(instance=ACQUIRE_SYSTEM_INSTANCES[v[0]], lazy=bool(v[1]), constraints=v[2], grid=v[3], bound_grid=v[4],
                     row_tiles=v[5], lds_bytes=v[6], draw_group=v[7], picks=v[8], launches=v[9], tiles_evaluated=v[10],
                     tiles_evaluated_max_lazy=v[11], kernel_us=v[12], pass_us=v[13], bound_us=v[14], pivot_us=v[15])
+
+    def drawbest_rows(self, slots, betas, mask=None, ranks=1, grid_cap=0):
+        """fokl_drawbest_rows over the uploaded rows (the pool): for every row of ``betas`` [E, nc] (a draw) its best
+        ``ranks`` rows, f_sd = x_s . beta_d, sense 'max' -> dict(index [ranks, E] int64, value [ranks, E]).  ``mask`` [S]:
+        rows that are no candidates where non-zero (None: none).  A NaN f never ranks, +-inf compare as numbers; value
+        descending, on equal values the lower row; a draw with fewer than r + 1 candidates has index -1 and value -inf from
+        rank r on.  pooloptimum.ranks_host is its statement: on integer data both fields are its bits.
+        ``report['launches']`` is 2 * ranks (one pass over the pool and one merge per rank); nothing waits on the host
+        between them.  At most ``DRAWBEST_MAX_COLUMNS`` columns and ``DRAWBEST_MAX_RANKS`` ranks.  ``grid_cap``: 0 the
+        device's row chunks; a test hook.  The same arguments give the same bits whatever the grid."""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        nc = s.shape[0]
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        if betas.ndim != 2 or betas.shape[1] != nc:
+            raise ValueError("betas columns must match the slot list")
+        E = betas.shape[0]
+        if mask is not None:
+            mask = np.ascontiguousarray(np.reshape(mask, -1) != 0, dtype=np.uint8)
+            if mask.shape[0] != self.n:
+                raise ValueError("drawbest_rows: one mask entry per uploaded row")
+        ranks = int(ranks)
+        rows = max(ranks, 0)
+        index, value = np.empty((rows, E), dtype=np.int64), np.empty((rows, E))
+        self._ck(self._lib.fokl_drawbest_rows(self._h, _ptr(s), nc, _ptr(betas), E, _ptr(mask), ranks, int(grid_cap),
+                                              _ptr(index), _ptr(value)))
+        return dict(index=index, value=value)
+
+    def drawbest_report(self):
+        """What the last ``drawbest_rows`` on this context ran (fokl_drawbest_report): ``instance`` ('ran'), ``ranks``,
+        ``row_tiles`` 16-row tiles in ``row_chunks`` chunks of ``tiles_per_chunk``, ``draw_blocks`` of 128 draws, the ``grid``
+        of the pass kernel (row chunks rounded up to 8, times draw blocks) and the ``merge_grid``, ``lds_bytes``,
+        ``coefficients`` ('registers': at most 128 columns; 'table'), the ``launches`` in all (2 * ranks), ``kernel_us`` of
+        the whole queue; ``pass_us`` and ``merge_us`` are measured while the context's timing is enabled (else 0).  'none'
+        and zeros after a refused call."""
+        out = np.zeros(14, dtype=np.int64)
+        self._ck(self._lib.fokl_drawbest_report(self._h, _ptr(out)))
+        v = [int(x) for x in out]
+        return dict(instance=DRAWBEST_INSTANCES[v[0]], ranks=v[1], row_tiles=v[2], row_chunks=v[3], draw_blocks=v[4], grid=v[5],
+                    merge_grid=v[6], lds_bytes=v[7], coefficients=POPULATION_COEFFICIENTS[v[8]], launches=v[9],
+                    tiles_per_chunk=v[10], kernel_us=v[11], pass_us=v[12], merge_us=v[13])
 
     def infer_inputs(self, mtx_u, betas, h, table, lo, hi, prior_mean, prior_prec, y, known_prod, starts, burnin, draws,
                      thin, jump_every, seed, draw_ids=None, rows=True, term_cap=0):

@@ -103,6 +103,7 @@ struct fokl_ctx {
     int64_t design_report[FOKL_DESIGN_REPORT_LEN] = {};           // ... and the last fokl_design_select call
     int64_t acquire_report[FOKL_ACQUIRE_REPORT_LEN] = {};         // ... and the last fokl_acquire_select call
     int64_t acquire_system_report[FOKL_ACQUIRE_SYSTEM_REPORT_LEN] = {};   // ... and the last fokl_acquire_system_* call
+    int64_t drawbest_report[FOKL_DRAWBEST_REPORT_LEN] = {};       // ... and the last fokl_drawbest_rows call
     int64_t integrate_report[FOKL_INTEGRATE_REPORT_LEN] = {};     // ... and the last fokl_gp_integrate_ensemble call
     int64_t simulate_report[FOKL_SIMULATE_REPORT_LEN] = {};       // ... and the last fokl_simulate_ensemble call
     int64_t simulate_adaptive_report[FOKL_SIMULATE_ADAPTIVE_REPORT_LEN] = {};     // ... and the last fokl_simulate_adaptive call
@@ -1909,6 +1910,7 @@ extern "C" int fokl_timing_get(fokl_ctx *ctx, int kernel_id, double *total_ms, i
 #include "fokl_design_device.inc"
 #include "fokl_acquire_device.inc"
 #include "fokl_acquire_system_device.inc"
+#include "fokl_drawbest_device.inc"
 
 #if defined(FOKL_GT_STAMP) || defined(FOKL_GD_STAMP)
 // diagnostic builds only (tools/k2_clock.sh, tools/k2_phases.sh): the clock stamps of the last Gram launch

@@ -265,6 +265,14 @@ extern "C" int fokl_acquire_system_incumbent(fokl_ctx *, const int32_t *, const 
 }
 extern "C" int fokl_acquire_system_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
 
+// Nor do every draw's best rows of a pool (fokl_drawbest_device.inc); their statement is pooloptimum.ranks_host.
+extern "C" int fokl_drawbest_rows(fokl_ctx *, const int32_t *, int, const double *, int, const unsigned char *, int, int, int64_t *,
+                                  double *)
+{
+    return FOKL_ERR_HIP;
+}
+extern "C" int fokl_drawbest_report(const fokl_ctx *, int64_t *) { return FOKL_ERR_HIP; }
+
 // Nor does the ensemble sampler over unknown inputs (fokl_infer_device.inc); its statement is infer.sample_host, and its
 // random numbers (fokl_infer_rng) are host code and present here.
 extern "C" int fokl_infer_inputs(fokl_ctx *, int, int, const int32_t *, int, const double *, const double *, const uint32_t *,

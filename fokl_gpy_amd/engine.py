@@ -275,6 +275,12 @@ class HipBackend:
     def acquire_system_report(self):
         return self.ctx.acquire_system_report()
 
+    def drawbest_rows(self, slots, betas, mask=None, ranks=1, grid_cap=0):
+        return self.ctx.drawbest_rows(slots, betas, mask, ranks, grid_cap)
+
+    def drawbest_report(self):
+        return self.ctx.drawbest_report()
+
 
 class SlotPool:
     """Free list of device column slots (slot 0 = ones, slot 1 = y are never handed out)."""

@@ -60,7 +60,8 @@ extern "C" {
 #define FOKL_K_ROBUST  17       /* resample_robust(): Gibbs chains under Student-t noise, a weighted pass per iteration (fokl_hip_internal.h: fokl_robust_chains) */
 #define FOKL_K_ACQUIRE 18       /* acquire(): EI / PI over a candidate pool, greedy batch (fokl_hip_internal.h: fokl_acquire_select) */
 #define FOKL_K_ACQUIRE_SYSTEM 19 /* acquire_system(): EI / PI under limits on other models' outputs (fokl_hip_internal.h: fokl_acquire_system_select) */
-#define FOKL_K_COUNT   20
+#define FOKL_K_DRAWBEST 20      /* optimize_pool(): every draw's best rows of a pool, ranked (fokl_hip_internal.h: fokl_drawbest_rows) */
+#define FOKL_K_COUNT   21
 
 typedef struct fokl_ctx fokl_ctx;
 

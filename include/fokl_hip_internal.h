@@ -44,6 +44,9 @@
  *   fokl_acquire_system_select / fokl_acquire_system_incumbent / fokl_acquire_system_report
  *                              the same selection under limits on other models' outputs, feasibility per (row, draw); the
  *                              best objective over the feasible measured rows per draw; what the last of either ran
+ *   fokl_drawbest_rows / fokl_drawbest_report
+ *                              for every posterior draw its best rows of a candidate pool, ranked
+ *                              (fokl_gpy_amd/pooloptimum.py), and what its last call ran
  *   fokl_infer_inputs / fokl_infer_report / fokl_infer_rng
  *                              unknown inputs inferred from observed outputs: one affine-invariant ensemble of 64 walkers
  *                              per posterior draw (fokl_gpy_amd/infer.py), what its last launches ran, and its
@@ -1365,6 +1368,46 @@ int fokl_acquire_system_incumbent(fokl_ctx *ctx, const int32_t *slots, const int
  *           fokl_timing_enable is on, else 0; the incumbent call: its two kernels in out[13] and out[14])
  */
 int fokl_acquire_system_report(const fokl_ctx *ctx, int64_t *out);
+
+/* ------------------------------------------------------------------------------------------------------ */
+/* Every draw's best rows of a pool, ranked (csrc/fokl_drawbest_device.inc; fokl_gpy_amd/pooloptimum.py)     */
+/* ------------------------------------------------------------------------------------------------------ */
+
+#define FOKL_DRAWBEST_MAX_RANKS 64
+#define FOKL_DRAWBEST_MAX_COLUMNS 1280         /* a 16-row tile of basis values in LDS: 160 KiB */
+#define FOKL_DRAWBEST_REPORT_LEN 14
+
+/*
+ * Over the uploaded rows (the pool), f_sd = sum_k column(slots[k])[s] * betas[d][k], sense 'max'.  The candidates of draw
+ * d are the rows with mask[s] == 0 (mask NULL: all) whose f_sd is not NaN; +inf and -inf compare as numbers.  The order is
+ * value descending, on equal values row ascending.  index_out [ranks][draws] int64, value_out [ranks][draws]: the r-th
+ * candidate of draw d in that order and its f; a draw with fewer than r + 1 candidates has index -1 and value -inf from
+ * there on.  f is never stored.  The statement in numpy is pooloptimum.ranks_host: on integer data both outputs are its
+ * bits; on continuous data the sums run in another order and a row may differ where two values tie to rounding.
+ * Host memory, row-major: slots [nc], betas [draws, nc] finite, mask [rows] or NULL.
+ * Rank r is one launch of drawbest_kernel over row chunks x blocks of 128 draws (rank r > 0: only what lies strictly after
+ * rank r - 1 of the draw, read on the device) and one of drawbest_merge_kernel over the chunks' records: 2 * ranks launches
+ * on the context's stream with no host wait between them.  No atomics; the same arguments give the same bits whatever the
+ * grid (grid_cap > 0 caps the row chunks; a test hook).
+ * Refused (FOKL_ERR_ARG with a text that names the limit, nothing is launched): more than FOKL_DRAWBEST_MAX_COLUMNS
+ * columns, ranks outside 1..FOKL_DRAWBEST_MAX_RANKS, a coefficient that is not finite, a call whose buffers and 64 MiB to
+ * spare reach beyond the device's free memory (the environment's FOKL_ACQUIRE_FREE_BYTES, if set, caps what counts as
+ * free).  Kernel time: FOKL_K_DRAWBEST (the whole queue).  Blocking; everything uploaded is freed before it returns.
+ */
+int fokl_drawbest_rows(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, int draws,
+                       const unsigned char *mask, int ranks, int grid_cap, int64_t *index_out, double *value_out);
+
+/*
+ * The last fokl_drawbest_rows call on `ctx`, out [FOKL_DRAWBEST_REPORT_LEN] (host):
+ *   out[0]  the instance: 0 none (no call yet, or the last one was refused or failed: all zeros), 1 ran     out[1]  ranks
+ *   out[2]  16-row tiles     out[3]  row chunks     out[4]  draw blocks (128 draws)
+ *   out[5]  the grid of drawbest_kernel: row chunks, rounded up to 8, x draw blocks     out[6]  the grid of the merge
+ *   out[7]  dynamic LDS bytes     out[8]  where the coefficients lived (FOKL_POPULATION_REGISTERS: at most 128 columns, padded
+ *           to 4; FOKL_POPULATION_TABLE)     out[9]  launches in all     out[10] 16-row tiles per chunk
+ *   out[11] kernel microseconds of the whole queue
+ *   out[12], out[13]  ... of the passes and of the merges (measured only while fokl_timing_enable is on, else 0)
+ */
+int fokl_drawbest_report(const fokl_ctx *ctx, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------------------ */
 /* Unknown inputs from observed outputs (csrc/fokl_infer_device.inc; fokl_gpy_amd/infer.py)                  */
