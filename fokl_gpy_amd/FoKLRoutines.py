@@ -890,6 +890,8 @@ class FoKL:
         """
         Posterior-mean prediction (and optionally 95 % bounds) at ``inputs`` (FR:851-980).
         Keywords: minmax, draws, clean, ReturnBounds (+ the keywords of ``clean``).
+        Draws that are not finite are not refused: the bounds follow numpy's order, NaN last, so a row's upper bound is NaN
+        once ``cut`` of its predictions are.  Thin a flagged chain's rows away first.
         """
         if not hasattr(self, 'minmax'):
             raise ValueError("To set minmax manually call model.minmax = ([input_min, input_max],[data_min, "

@@ -229,6 +229,8 @@ extern "C" int fokl_population_stats(fokl_ctx *ctx, const int32_t *slots, int nc
     if (rc) return rc;
     const int64_t n = ctx->n;
     if (n <= 0) return fail(ctx, FOKL_ERR_STATE, "fokl_population_stats: the dataset has no rows");
+    for (size_t i = 0; i < (size_t)draws * nc; ++i)
+        if (!std::isfinite(betas[i])) return fail(ctx, FOKL_ERR_ARG, "fokl_population_stats: every coefficient must be finite");
 
     const int ncp = (nc + 3) & ~3;
     const int n_blocks = (draws + PP_DRAWS - 1) / PP_DRAWS, ep = n_blocks * PP_DRAWS;

@@ -4,6 +4,14 @@
 // largest draw.  One wavefront per 64 rows; a row's basis values sit in LDS as [column][lane], the draw
 // coefficients are wave-uniform (scalar loads), four draws are accumulated at a time, and each lane keeps
 // its cut + 1 smallest and cut largest predictions in two small sorted LDS lists.
+//
+// Predictions that are not finite keep numpy's order: +-inf are numbers like any other, NaN sorts last.  A NaN passes
+// neither of the lists' strict comparisons, so it is counted per row instead, and with D of them the bounds read out are
+// NaN where sorted[cut] / sorted[draws - cut] lie among the NaN (draws - D <= cut / D >= cut) and else the klo-th smallest and
+// the (khi - D)-th largest number (tests/test_predict_nonfinite_gpu.py).  predict_mfma_kernel below counts nothing: after
+// it, predict_flag_kernel looks for a mean that is not finite (such a row holds a NaN or an infinity, or its sum overflowed),
+// and if there is one this kernel runs once more with `repair` set, over the 64-row blocks that hold such a row, and
+// writes those rows again.
 
 namespace fokl {
 
@@ -23,7 +31,8 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__re
                                                              const int *__restrict__ slots, int nc,
                                                              const double *__restrict__ betas, int draws, int klo,
                                                              int khi, int64_t n, double *__restrict__ mean,
-                                                             double *__restrict__ bounds, double *__restrict__ lists)
+                                                             double *__restrict__ bounds, double *__restrict__ lists,
+                                                             int repair)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *xrow = lds;                              // [nc][64] (none with GLOBAL_X)
@@ -37,6 +46,11 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__re
     for (int64_t base = (int64_t)blockIdx.x * PR_THREADS; base < n; base += (int64_t)gridDim.x * PR_THREADS) {
         const int64_t r = base + lane;
         const bool in = r < n;
+        bool mine = in;                                  // the rows this pass writes
+        if (repair) {
+            mine = in && !(fabs(mean[r]) < INFINITY);
+            if (!__any(mine)) continue;                  // wave-uniform: nothing to repair in this block
+        }
         if (!GLOBAL_X)
             for (int j = 0; j < nc; ++j)
                 xrow[j * PR_THREADS + lane] = in ? *(__attribute__((address_space(1))) const double *)(slot_ptr[slots[j]] + r) : 0.0;
@@ -45,6 +59,7 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__re
             for (int k = 0; k < khi; ++k) hi[k * PR_THREADS + lane] = -INFINITY;
         }
         double total = 0.0;
+        int n_nan = 0;                                   // NaN predictions of this row: they enter neither list
         for (int d0 = 0; d0 < draws; d0 += 4) {
             double acc[4] = {0.0, 0.0, 0.0, 0.0};
             const int nd = min(4, draws - d0);
@@ -82,6 +97,7 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__re
                 const double v = acc[q];
                 total += v;
                 if (want_bounds) {
+                    n_nan += v != v;
                     if (v < lo[(klo - 1) * PR_THREADS + lane]) {       // insert into the ascending list
                         int k = klo - 1;
                         while (k > 0 && lo[(k - 1) * PR_THREADS + lane] > v) {
@@ -101,14 +117,27 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__re
                 }
             }
         }
-        if (in) {
+        if (mine) {
             mean[r] = total / (double)draws;
             if (want_bounds) {
-                bounds[2 * r] = lo[(klo - 1) * PR_THREADS + lane];
-                bounds[2 * r + 1] = hi[(khi - 1) * PR_THREADS + lane];
+                // numpy's order, NaN last: the klo-th smallest is a number while klo numbers exist, and the khi-th largest
+                // of all is the (khi - n_nan)-th largest number
+                bounds[2 * r] = draws - n_nan >= klo ? lo[(klo - 1) * PR_THREADS + lane] : NAN;
+                bounds[2 * r + 1] = n_nan < khi ? hi[(khi - 1 - n_nan) * PR_THREADS + lane] : NAN;
             }
         }
     }
+}
+
+// 1 into *flag if a mean is not finite (all such lanes store the same value): whether predict_mfma_kernel's rows need the
+// repair pass above.
+__global__ __launch_bounds__(256) void predict_flag_kernel(const double *__restrict__ mean, int64_t n,
+                                                           unsigned long long *__restrict__ flag)
+{
+    bool any = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        any |= !(fabs(mean[i]) < INFINITY);
+    if (any) *flag = 1ull;
 }
 
 // The same on the matrix pipe, for the case that costs: bounds over many draws.  One wavefront per tile of 16 rows, the
@@ -125,6 +154,9 @@ __global__ __launch_bounds__(PR_THREADS) void predict_kernel(double *const *__re
 // per-lane sorted lists of the klo / khi best kept up to date draw by draw, merged the same way.  What a launch did is
 // counted for fokl_predict_report: tally[0] += the tiles a wavefront processed (lane 0, once, at its end), tally[1] += 1
 // for a tile on its way into the fallback (lane 0; nothing is counted inside the filter pass itself).
+// NaN is no concern of this kernel: its lists take numbers only, and rows with one are written again by predict_kernel's
+// repair pass.  (With a coefficient that is not finite the host's moments are NaN, nothing passes the filter and every tile
+// takes the fallback.)
 constexpr int PM_THREADS = 64;
 constexpr int PM_DT = 4;
 constexpr int PM_CAP = 32;
@@ -367,12 +399,18 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
     const size_t lds_mfma = ((size_t)ncp * 16 + 2 * (size_t)std::max(PM_CAP, std::max(klo, khi)) * PM_THREADS) * sizeof(double);
     const char *forced = std::getenv("FOKL_PREDICT_PATH");
     const bool use_mfma = bounds && draws >= 64 && lds_mfma <= 150 * 1024 && !(forced && std::strcmp(forced, "valu") == 0);
+    // mean | bounds on the device; `repair`: the matrix-pipe kernel has filled them, and rows whose mean is not finite are
+    // written again by the VALU kernel, which counts a row's NaN predictions (what ran is then still the former's report)
+    double *d_res = nullptr;
+    bool repair = false;
+    int64_t mfma_report[4] = {0, 0, 0, 0};
     if (use_mfma) {
         const size_t beta_off = ((size_t)nc * sizeof(int) + 7) & ~(size_t)7;
-        // argument block: slots | betas' | their mean | their covariance | the kernel's two tile counts (zero on arrival)
+        // argument block: slots | betas' | their mean | their covariance | the kernel's two tile counts and predict_flag_kernel's
+        // flag (zero on arrival)
         const size_t arg_doubles = (size_t)ncp * dp + ncp + (size_t)ncp * ncp;
         const size_t tally_off = beta_off + arg_doubles * sizeof(double);
-        const size_t arg_bytes = tally_off + 2 * sizeof(unsigned long long);
+        const size_t arg_bytes = tally_off + 3 * sizeof(unsigned long long);
         rc = begin_args(ctx, arg_bytes);
         if (rc) return rc;
         std::memcpy(ctx->h_args, slots, (size_t)nc * sizeof(int));
@@ -403,7 +441,6 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
         const double z = 0.5 * (z_lo + z_hi);
         rc = push_args(ctx, arg_bytes);
         if (rc) return rc;
-        double *d_res = nullptr;
         HIP_TRY(ctx, hipMalloc((void **)&d_res, n * 3 * sizeof(double)));
         unsigned long long *d_tally = reinterpret_cast<unsigned long long *>(ctx->d_args + tally_off);
         const int64_t tiles = ((int64_t)n + 15) / 16;
@@ -426,18 +463,34 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
                 (void)hipFree(d_res);
                 return fail(ctx, FOKL_ERR_HIP, std::string("predict_mfma_kernel launch: ") + hipGetErrorString(le));
             }
+            const int flag_grid = (int)std::min<int64_t>(((int64_t)n + 255) / 256, (int64_t)cu_count(ctx) * 8);
+            hipLaunchKernelGGL(predict_flag_kernel, dim3(flag_grid), dim3(256), 0, ctx->stream, d_res, ctx->n, d_tally + 2);
+            le = hipGetLastError();
+            if (le != hipSuccess) {
+                (void)hipFree(d_res);
+                return fail(ctx, FOKL_ERR_HIP, std::string("predict_flag_kernel launch: ") + hipGetErrorString(le));
+            }
         }
-        unsigned long long tally[2] = {0, 0};
+        unsigned long long tally[3] = {0, 0, 0};
         hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipMemcpy(mean, d_res, n * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(bounds, d_res + n, n * 2 * sizeof(double), hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(tally, d_tally, sizeof tally, hipMemcpyDeviceToHost);
-        (void)hipFree(d_res);
-        if (e != hipSuccess) return fail(ctx, FOKL_ERR_HIP, std::string("fokl_predict: ") + hipGetErrorString(e));
-        predict_note(ctx, FOKL_PREDICT_MFMA, false, grid, tiles);
-        ctx->predict_report[4] = (int64_t)tally[0];
-        ctx->predict_report[5] = (int64_t)tally[1];
-        return FOKL_OK;
+        repair = e == hipSuccess && tally[2] != 0;
+        if (!repair) {
+            if (e == hipSuccess) e = hipMemcpy(mean, d_res, n * sizeof(double), hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(bounds, d_res + n, n * 2 * sizeof(double), hipMemcpyDeviceToHost);
+            (void)hipFree(d_res);
+            if (e != hipSuccess) return fail(ctx, FOKL_ERR_HIP, std::string("fokl_predict: ") + hipGetErrorString(e));
+        }
+        mfma_report[0] = grid;
+        mfma_report[1] = tiles;
+        mfma_report[2] = (int64_t)tally[0];
+        mfma_report[3] = (int64_t)tally[1];
+        if (!repair) {
+            predict_note(ctx, FOKL_PREDICT_MFMA, false, mfma_report[0], mfma_report[1]);
+            ctx->predict_report[4] = mfma_report[2];
+            ctx->predict_report[5] = mfma_report[3];
+            return FOKL_OK;
+        }
     }
 
     // the sorted lists of the order statistics move to device memory when they do not fit LDS next to the basis values
@@ -462,8 +515,7 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
     rc = push_args(ctx, arg_bytes);
     if (rc) return rc;
 
-    double *d_res = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&d_res, n * 3 * sizeof(double)));
+    if (!repair) HIP_TRY(ctx, hipMalloc((void **)&d_res, n * 3 * sizeof(double)));
     double *d_mean = d_res, *d_bounds = bounds ? d_res + n : nullptr;
     const int64_t row_blocks = ((int64_t)n + PR_THREADS - 1) / PR_THREADS;
     // wavefronts per CU: what LDS admits once the basis values are not in it, enough of them to hide the columns' latency
@@ -486,7 +538,7 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
             hipLaunchKernelGGL(fn, dim3(grid), dim3(PR_THREADS), lds_bytes, ctx->stream, ctx->d_slot_ptr,
                                reinterpret_cast<const int *>(ctx->d_args), nc,
                                reinterpret_cast<const double *>(ctx->d_args + beta_off), draws, klo, khi, ctx->n, d_mean,
-                               d_bounds, d_lists);
+                               d_bounds, d_lists, repair ? 1 : 0);
             e = hipGetLastError();
         }
         if (e != hipSuccess) {
@@ -501,6 +553,12 @@ extern "C" int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const d
     if (e == hipSuccess && bounds) e = hipMemcpy(bounds, d_bounds, n * 2 * sizeof(double), hipMemcpyDeviceToHost);
     (void)hipFree(d_res);
     if (e != hipSuccess) return fail(ctx, FOKL_ERR_HIP, std::string("fokl_predict: ") + hipGetErrorString(e));
+    if (repair) {
+        predict_note(ctx, FOKL_PREDICT_MFMA, false, mfma_report[0], mfma_report[1]);
+        ctx->predict_report[4] = mfma_report[2];
+        ctx->predict_report[5] = mfma_report[3];
+        return FOKL_OK;
+    }
     predict_note(ctx, global_lists ? FOKL_PREDICT_VALU_GLOBAL : FOKL_PREDICT_VALU_LDS, wide, grid, row_blocks);
     return FOKL_OK;
 }

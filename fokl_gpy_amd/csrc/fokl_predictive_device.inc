@@ -371,6 +371,8 @@ static int predictive_rows_any(fokl_ctx *ctx, const int32_t *slots, int nc, cons
     if (rc) return rc;
     const int64_t n = ctx->n;
     if (n <= 0) return fail(ctx, FOKL_ERR_STATE, who + ": the dataset has no rows");
+    for (size_t i = 0; i < (size_t)draws * nc; ++i)
+        if (!std::isfinite(betas[i])) return fail(ctx, FOKL_ERR_ARG, who + ": every coefficient must be finite");
     if (sw)
         for (int64_t i = 0; i < n; ++i)
             if (!(sw[i] > 0.0) || !std::isfinite(sw[i]))

@@ -233,6 +233,10 @@ int fokl_bic_resid_terms_launch(fokl_ctx *ctx, const int32_t *terms, int n_terms
  * For the rows currently uploaded: modells[i, d] = sum_j betas[d, j] * col(slots[j])[i] (FR:966-968),
  * mean[i] = mean_d modells[i, d] (FR:969) and, when `bounds` != NULL, bounds[i] = (sorted[cut],
  * sorted[draws - cut]) of row i's draws (FR:973-977).  betas is [draws, nc] row-major in host memory.
+ * Coefficients that are not finite are NOT refused: the statement is numpy's for them too.  The sort puts NaN last and
+ * infinities count as numbers, so with D NaN among row i's draws bounds[i][0] is NaN iff draws - D <= cut, else the
+ * (cut + 1)-th smallest number, and bounds[i][1] is NaN iff D >= cut, else the (cut - D)-th largest number; mean[i] is NaN
+ * with any NaN or both infinities, +-inf with one.  D is the row's own (0 x inf is NaN).  Finite draws: the bits as before.
  */
 int fokl_predict(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, int draws, int cut,
                  double *mean, double *bounds);

@@ -996,7 +996,9 @@ enum {
  *           than workgroups means the kernel's grid-stride loop went round again
  *   out[4]  tiles predict_mfma_kernel counted as processed (= out[3] if every one was visited once), 0 for predict_kernel
  *   out[5]  those among them whose filter pass did not yield the bounds and which went through the exact fallback pass
- *           (same numbers at about a third of the speed), 0 for predict_kernel
+ *           (same numbers at about a third of the speed), 0 for predict_kernel.  (= out[4] with a coefficient that is not finite: the
+ *           filter's moments are NaN.  Rows whose mean is not finite are then written again by predict_kernel's repair pass,
+ *           which counts their NaN predictions -- include/fokl_hip.h, fokl_predict; this report stays the first kernel's)
  * Host values and two device counters copied back with the results: no launch, no synchronisation of its own.
  */
 int fokl_predict_report(const fokl_ctx *ctx, int64_t *out);
@@ -1027,6 +1029,8 @@ enum {
  * One launch of population_kernel on v_mfma_f64_16x16x4_f64 (a lane keeps the accumulators of one draw in registers;
  * each (row chunk, draw) leaves one record) and one of population_reduce_kernel, which adds the records in the order
  * of the chunks: no floating-point atomics, the same arguments give the same bits.  y itself is never stored.
+ * Refused (FOKL_ERR_ARG, "every coefficient must be finite", before anything is allocated or launched): a NaN or infinite
+ * entry of betas.
  * Kernel time: FOKL_K_POPULATION (both launches).  Blocking.
  */
 int fokl_population_stats(fokl_ctx *ctx, const int32_t *slots, int nc, const double *betas, int draws,
@@ -1082,6 +1086,7 @@ enum {
  * of score_kernel on v_mfma_f64_16x16x4_f64, one wavefront per 16-row tile; merges across lanes in a fixed order, no
  * floating-point atomics: the same arguments give the same bits.
  * Refused (FOKL_ERR_ARG with a text, nothing is launched; the dataset, its slots and pending launches are left alone):
+ * a NaN or infinite entry of betas ("every coefficient must be finite"; fokl_score_rows_noise too);
  * want_loo with fewer than FOKL_SCORE_MIN_DRAWS draws or with M + 1 > FOKL_SCORE_MAX_TAIL; basis values and list beyond the
  * LDS of a compute unit; tail_out, coefficient table and statistics together beyond the device's free memory (the message
  * says which is the largest; the environment's FOKL_SCORE_FREE_BYTES, if set, caps what counts as free).
@@ -1154,6 +1159,7 @@ enum {
  * v_mfma_f64_16x16x4_f64, one wavefront per 16-row tile; the product is recomputed in every pass (no limit on the draws);
  * merges across lanes in a fixed order, no atomics: the same arguments give the same bits.
  * Refused (FOKL_ERR_ARG with a text, nothing is launched; the dataset, its slots and pending launches are left alone):
+ * a NaN or infinite entry of betas ("every coefficient must be finite"; fokl_predictive_rows_noise too);
  * nq outside its range; p outside (0, 1), not finite or repeated; max_passes < 0; ftol or xtol negative or not finite;
  * neither with_data nor quantiles; basis values beyond the LDS of a compute unit; coefficient table and results together
  * beyond the device's free memory (the environment's FOKL_PREDICTIVE_FREE_BYTES, if set, caps what counts as free).

@@ -256,6 +256,11 @@ def test_refusals_launch_nothing(device_ctx, monkeypatch):
         refused('ftol and xtol must be finite and >= 0', xtol=float('nan'))
         refused('neither data nor quantiles', with_data=False, p=[], z=[])
         refused('positive and finite', sd=-sd)
+        for bad in (np.nan, -np.inf):                            # draws of a flagged chain, or overflowed ones
+            spoiled = betas.copy()
+            spoiled[29, 3] = bad
+            refused('fokl_predictive_rows: every coefficient must be finite', betas=spoiled)
+            refused('fokl_predictive_rows: every coefficient must be finite', betas=spoiled, with_data=False)
         with pytest.raises(_capi.FoklNativeError, match='slot'):
             ctx.predictive_rows(np.array([0, 2, 3, 9999], dtype=np.int32), betas, sd, rinv, True, p, z)
         with pytest.raises(ValueError):

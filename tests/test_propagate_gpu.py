@@ -151,6 +151,17 @@ def test_refusals(device_ctx):
     with pytest.raises(_capi.FoklNativeError):
         device_ctx.population_stats(np.array([0, 2, 9999], dtype=np.int32), betas, shift, cuts)
     assert device_ctx.population_report()['coefficients'] == 'none' and device_ctx.population_report()['grid'] == 0
+    before = device_ctx.population_stats(slots, betas, shift, cuts, True)
+    for bad in (np.nan, np.inf):                             # draws of a flagged chain, or overflowed ones: refused natively
+        spoiled = betas.copy()
+        spoiled[-1, -1] = bad
+        with pytest.raises(_capi.FoklNativeError, match='fokl_population_stats: every coefficient must be finite') as exc:
+            device_ctx.population_stats(slots, spoiled, shift, cuts, True)
+        assert exc.value.code == -2
+        assert device_ctx.population_report()['coefficients'] == 'none' and device_ctx.population_report()['grid'] == 0
+        assert np.array_equal(device_ctx.read_slot(2), cols[:, 0]) and np.array_equal(device_ctx.read_slot(_capi.SLOT_Y), y)
+        again = device_ctx.population_stats(slots, betas, shift, cuts, True)
+        assert np.array_equal(again[0], before[0]) and np.array_equal(again[1], before[1])
     device_ctx.population_stats(slots, betas, shift, cuts)
     assert device_ctx.population_report()['coefficients'] == 'registers'
 

@@ -207,6 +207,14 @@ def test_refusals_leave_the_dataset_intact(device_ctx):
     with pytest.raises(_capi.FoklNativeError, match='positive') as exc:
         ctx.score_rows(slots, betas, -sig, True)
     assert exc.value.code == -2
+    for bad in (np.nan, np.inf):                             # draws of a flagged chain, or overflowed ones: refused natively
+        spoiled = betas.copy()
+        spoiled[17, 2] = bad
+        for want_loo in (True, False):
+            with pytest.raises(_capi.FoklNativeError, match='fokl_score_rows: every coefficient must be finite') as exc:
+                ctx.score_rows(slots, spoiled, sig, want_loo)
+            assert exc.value.code == -2
+            intact()
     with pytest.raises(_capi.FoklNativeError, match='slot'):
         ctx.score_rows(np.array([0, 2, 3, 9999], dtype=np.int32), betas, sig, True)
     with pytest.raises(ValueError):

@@ -330,6 +330,11 @@ def test_refusals_launch_nothing(device_ctx, monkeypatch):
             check('every sw .* must be finite and > 0', sw=np.r_[np.ones(199), 0.0])
             check('every sw .* must be finite and > 0', sw=np.r_[np.ones(199), np.inf])
             check('every sw .* must be finite and > 0', sw=np.r_[np.nan, np.ones(199)])
+            for bad in (np.nan, np.inf):                         # draws of a flagged chain, or overflowed ones
+                spoiled = betas.copy()
+                spoiled[0, 0] = bad
+                check('_rows_noise: every coefficient must be finite', betas=spoiled)
+                check('_rows_noise: every coefficient must be finite', betas=spoiled, nu=np.inf, sw=None)
         refused(f'beyond FOKL_PREDICTIVE_NU_MAX = {_capi.PREDICTIVE_NU_MAX}', nu=_capi.PREDICTIVE_NU_MAX + 1.0)
         refused('fokl_predictive_rows_noise: .*at most FOKL_PREDICTIVE_MAX_QUANTILES = 8', p=np.linspace(0.1, 0.9, 9), z=np.zeros(9))
         refused('max_passes must be >= 0', max_passes=-1)
